@@ -24,8 +24,14 @@ host memory to the stabilized frames, crop bounds, paths and score back in host 
 runs, min beside it.  This is the ">= 500 frames/s end-to-end stabilize()" figure of BASELINE.json; it is never the
 default `value`, which is the HBM-resident rate.
 
+A plain run sets up, warms up, times the K steps and prints the line; the figures below that take runs of their own come with --full.
+--dump-outputs DIR writes what the timed path handed its caller in the last step (rank 0) as DIR/<name>.npy: the stabilized frames
+(float32; a fixed hashed sample of them when there are more than DUMP_VALUES values), the clip's crop bounds and the stabilized vertex
+paths (float64), and in --mode e2e the stability score.  The inputs are the seeded synthetic clip, so two builds compare file for file.
+
 Rank 0 prints ONE JSON line (fields: see the task's bench contract) including
   roofline:     warp kernel, algorithmic bytes 2*H*W*3 per frame over its HIP-event time, vs 8 TB/s HBM
+and with --full:
   end_to_end:   the e2e figure above for the same workload (mean and min of 5 runs), N = 1 only
   cpu_baseline: the C oracle (oracle/warp_oracle.c, OpenMP) timed on this box's host cores on a bounded sample of the
                 same workload (kind "port"), and under "reference_faithful" the reference's own formulation -- dense
@@ -187,15 +193,16 @@ def cfg1_status():
     return 'skipped: decoder present but the CPU reference leg is not part of this bench (run the reference directly)'
 
 
-def host_clip(stab, frames, disp, hom, runs, **kw):
-    """stabilize_clip() from host frames to host frames, `runs` times: list of seconds."""
+def host_clip(stab, frames, disp, hom, runs, keep_last=False, **kw):
+    """stabilize_clip() from host frames to host frames, `runs` times: list of seconds (and, keep_last, what the last run returned)."""
     times = []
+    out = None
     for _ in range(runs):
+        out = None                                  # (the previous clip's frames go before the next run allocates its own)
         t0 = time.perf_counter()
         out = stab.stabilize_clip(frames, disp, hom, **kw)
         times.append(time.perf_counter() - t0)
-        del out
-    return times
+    return (times, out) if keep_last else times
 
 
 def end_to_end(stab, d_frames, disp, hom, F, runs=5):
@@ -337,6 +344,45 @@ def frame_checksums(frames):
     words = frames.reshape(n, -1)
     weights = (torch.arange(words.shape[1], device=frames.device, dtype=torch.int64) % 65521) + 1
     return [int(((words[i].to(torch.int64) * weights).sum() & 0x7FFFFFFFFFFFFFFF).item()) for i in range(n)]
+
+
+DUMP_VALUES = 1 << 22          # per array written by --dump-outputs: 16 MB of float32 frames + at most 32 MB of float64 paths
+
+
+def sample_index(n, count=DUMP_VALUES, seed=7):
+    """`count` flat indices into n values, sorted, from the project's hash (the same on every machine and NumPy version)."""
+    from meshflow_amd import synthetic
+    i = np.arange(count, dtype=np.int64)
+    h = (synthetic.hash32(2 * i, seed).astype(np.uint64) << np.uint64(32)) | synthetic.hash32(2 * i + 1, seed).astype(np.uint64)
+    return np.sort((h % np.uint64(n)).astype(np.int64))
+
+
+def dump_outputs(path, frames, bounds, paths, score=None):
+    """--dump-outputs: frames = a device tensor (n, H, W, 3) or a list of host frames, bounds = the 4 crop bounds, paths = the stabilized
+    vertex displacements (device tensor or array).  An array of more than DUMP_VALUES values is written as the values at sample_index()."""
+    import torch
+
+    def values(a, dtype):
+        n = a.numel() if torch.is_tensor(a) else a.size
+        if n <= DUMP_VALUES:
+            return (a.cpu().numpy() if torch.is_tensor(a) else np.asarray(a)).astype(dtype)
+        idx = sample_index(n)
+        return a.reshape(-1)[torch.from_numpy(idx).to(a.device)].cpu().numpy().astype(dtype)
+
+    os.makedirs(path, exist_ok=True)
+    if torch.is_tensor(frames):
+        out = values(frames, np.float32)
+    else:                                      # host frames one array each: sample them without stacking the clip
+        per, n = frames[0].size, len(frames) * frames[0].size
+        idx = sample_index(n) if n > DUMP_VALUES else np.arange(n)
+        parts = np.split(idx, np.searchsorted(idx, np.arange(1, len(frames)) * per))
+        out = np.concatenate([np.asarray(f).reshape(-1)[p - k * per] for k, (f, p) in enumerate(zip(frames, parts))]).astype(np.float32)
+    np.save(os.path.join(path, 'frames.npy'), out)
+    np.save(os.path.join(path, 'crop_bounds.npy'), np.asarray([int(v) for v in bounds], dtype=np.float64))
+    np.save(os.path.join(path, 'stabilized_vertex_displacements.npy'),
+            values(paths if torch.is_tensor(paths) else np.asarray(paths), np.float64))
+    if score is not None:
+        np.save(os.path.join(path, 'stability_score.npy'), np.asarray([score], dtype=np.float64))
 
 
 def visible_gpus():
@@ -628,6 +674,14 @@ def build_parser():
     ap.add_argument('--as-rank-of', type=int, default=0, metavar='N',
                     help='single process only: do the work rank 0 of an N-GPU "shard" run does (clip of N x frames, own '
                          'frame range, replicated Jacobi) without the collective -- predicts weak scaling on one GPU')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure everything beside the timed steps: single-clip latency, the serial pipeline, the warp and Jacobi '
+                         'kernels alone, crop + resize and vertex motion, the host-to-host clip, the other configurations, the CPU '
+                         'baselines and (N > 1) the gather to rank 0; --cpu-frames, --no-faithful, --no-e2e, --no-workloads, '
+                         '--workload-steps and --no-gather shape these')
+    ap.add_argument('--dump-outputs', metavar='DIR', default='',
+                    help='after the timed steps, write what the last step returned (rank 0) as DIR/<name>.npy, float32 / float64, '
+                         'at most 48 MB')
     return ap
 
 
@@ -696,9 +750,12 @@ def main():
         host_clip(stab, frames_h, disp, hom, max(args.warmup, 1))
         barrier()
         t0 = time.perf_counter()
-        times = host_clip(stab, frames_h, disp, hom, args.steps)
+        times, last = host_clip(stab, frames_h, disp, hom, args.steps, keep_last=True)
         barrier()
         elapsed = max_over_ranks(time.perf_counter() - t0)
+        if rank == 0 and args.dump_outputs:
+            dump_outputs(args.dump_outputs, last[0], last[1], last[2], score=float(last[3]))
+        del last
         if rank == 0:
             print(json.dumps({
                 'metric': 'frames/sec end-to-end stabilize_clip(): host frames in -> stabilized host frames + crop bounds + paths + score out (PCIe both ways)',
@@ -733,26 +790,28 @@ def main():
     m = kp.measure(args.steps, args.warmup, serial_mode, barrier, max_over_ranks)
     elapsed, spinup_steps, bounds, d_out = m['elapsed'], m['spinup_steps'], m['bounds'], kp.d_out
     ev, jev = m['ev'], m['jev']
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, d_out, bounds.tolist(), m['d_stab'])
 
     # Beside the timed figure, outside the timed region (N = 1): the latency of ONE clip through the same pipeline from an idle GPU
     # (synchronise, issue one clip, synchronise: the sweep and the first frame range's table cannot hide behind anything), and the
     # K steps again with everything on one stream.
     extra = {}
-    if world == 1 and not serial_mode and not os.environ.get('MF_BENCH_NO_EXTRAS'):
+    if args.full and world == 1 and not serial_mode and not os.environ.get('MF_BENCH_NO_EXTRAS'):
         extra['latency_ms_single_clip'] = kp.latency()
         extra['serial'] = kp.serial(args.steps, max(args.warmup, 3))
 
     warp_ms = float('nan') if no_events else float(np.mean([a.elapsed_time(b) for a, b in ev]))
-    warp_alone = kp.warp_alone_ms(m['d_stab']) if (not serial_mode and stab._sweep_gate(d_disp) == 'plan') else None
+    warp_alone = kp.warp_alone_ms(m['d_stab']) if (args.full and not serial_mode and stab._sweep_gate(d_disp) == 'plan') else None
     if os.environ.get('MF_BENCH_PER_STEP') and rank == 0 and not no_events:          # tuning aid: the launches one by one (clock transients)
         print('warp ms per step:', [round(a.elapsed_time(b), 3) for a, b in ev], file=sys.stderr)
     jac_ms = float('nan') if no_events else float(np.mean([a.elapsed_time(b) for a, b in jev]))
     # Jacobi kernel alone (the per-step figure above includes the host-side coefficient set-up), outside the timed region
-    jac_kernel_ms, jac_flops, jac_series = kp.jacobi_kernel_ms(omega, iters)
+    jac_kernel_ms, jac_flops, jac_series = kp.jacobi_kernel_ms(omega, iters) if args.full else (None, None, int(d_disp[0].numel()))
     # Next row on the path, measured outside the timed region: crop to the clip-level bounds and
     # resize back, device-resident (mfs.py:1111-1157).
     resize_ms = None
-    if not (bounds[2] < bounds[0] or bounds[3] < bounds[1]):
+    if args.full and not (bounds[2] < bounds[0] or bounds[3] < bounds[1]):
         r0, r1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         scratch = torch.empty_like(d_frames)
         rect = bounds.tolist()                       # one D2H of the 4 bounds, outside the timed launches
@@ -768,7 +827,7 @@ def main():
     # The row before the path, also outside the timed region: matched features -> vertex displacements
     # (mfs.py:236-452 after the tracker), synthetic features for the same number of frame pairs.
     motion_row = None
-    if rank == 0:
+    if args.full and rank == 0:
         try:                                          # rank 0 only: a failure here must not strand the other ranks
             from meshflow_amd import host as mfhost
             Fm = min(F, per_gpu)                          # one GPU's worth of frame pairs, whatever N is
@@ -801,12 +860,13 @@ def main():
             motion_row = {'error': f'{type(e).__name__}: {e}'}
     # north_star's "single RCCL gather over xGMI at the end": timed once, after the timed region (it is 7 x 1.87 GB into
     # one GPU -- an order of magnitude above a step -- and a consumer in host memory is better served by every rank
-    # draining its own shard over its own PCIe link).  Both figures are reported side by side;
-    # --no-gather skips them.
+    # draining its own shard over its own PCIe link).  Both figures are reported side by side
+    # with --full; --no-gather skips them.
     gather_ms = gather_error = d2h_ms = checksum = None
-    if args.checksum and not (world > 1 and not clips_mode and not args.no_gather):
+    gather = args.full and world > 1 and not clips_mode and not args.no_gather
+    if args.checksum and not gather:
         checksum = frame_checksums(d_out)
-    if world > 1 and not clips_mode and not args.no_gather:
+    if gather:
         try:
             # pre-flight: rank 0 receives G x ceil(F/G) frames next to its own shard, input and output; every rank agrees on whether it fits
             per_rank = -(-F // world)
@@ -856,7 +916,8 @@ def main():
                           'sweep on the prep stream (the NEXT clip\'s sweep runs beside THIS clip\'s table + plan, never beside a warp)' if stab.resident_chunks <= 0 else
                           f'product (MeshFlowStabilizer.stabilize_resident), {stab.resident_chunks} frame ranges: sweep + tables + crop scan + rectangle on the prep '
                           'stream beside the warp chunks on the main stream') +
-                         '; clips issued back to back, `spinup_steps` untimed steps in front of the warm-up; `latency_ms_single_clip` and `serial` beside it'),
+                         '; clips issued back to back, `spinup_steps` untimed steps in front of the warm-up' +
+                         ('; `latency_ms_single_clip` and `serial` beside it' if extra else '')),
             'scaling': 'weak', 'vs_baseline': None, 'dtype': 'f64',
             'dtype_note': 'float64 vertex paths and pixel coordinates (as the reference), integer fixed-point interpolation on uint8',
             'data': f'synthetic ({args.frames_kind} frames, injected random mesh motion, seed 0)',
@@ -884,13 +945,15 @@ def main():
                                        'note': 'the same launch with nothing beside it, 8 launches between two events outside the timed steps'}} if warp_alone else {})},
             'jacobi': {'avg_ms_in_pipeline': jac_ms, 'on_prep_stream': not serial_mode, 'kernel_ms': jac_kernel_ms,
                        'note': 'avg_ms_in_pipeline: HIP events around the stage (coefficient upload + sweep) on the stream it is issued on -- on the prep '
-                               'stream it shares the chip with the previous clip\'s warp, so this is NOT the kernel\'s own time; kernel_ms: the kernel alone, measured after the timed region', 'series': jac_series, 'frames': F,
-                       'bound': 'fp64 vector ALU + LDS (the state never leaves the chip)', 'achieved': jac_flops / (jac_kernel_ms * 1e-3) / 1e12,
-                       'peak': 78.6, 'unit': 'TFLOP/s', 'frac': jac_flops / (jac_kernel_ms * 1e-3) / 78.6e12},
+                               'stream it shares the chip with the previous clip\'s warp, so this is NOT the kernel\'s own time; kernel_ms: the kernel alone, measured after the timed region (--full)', 'series': jac_series, 'frames': F,
+                       'bound': 'fp64 vector ALU + LDS (the state never leaves the chip)',
+                       **({'achieved': jac_flops / (jac_kernel_ms * 1e-3) / 1e12, 'peak': 78.6, 'unit': 'TFLOP/s',
+                           'frac': jac_flops / (jac_kernel_ms * 1e-3) / 78.6e12} if jac_kernel_ms is not None else {})},
             'crop_bounds': [int(v) for v in bounds.tolist()],
             'communicator': comm,
-            'cfg1': cfg1_status(),
         }
+        if args.full:
+            result['cfg1'] = cfg1_status()
         result.update(extra)
         # the same figures under one key (the bench contract of this tier keeps the HBM-resident rate in `value`: "inputs already resident in
         # HBM when the timed region starts ... the PCIe-inclusive rate is never `value`"; BASELINE.json's host-to-host figure is `end_to_end`,
@@ -921,7 +984,7 @@ def main():
         if checksum is not None:
             result['frames_checksum'] = checksum
             result['frames_checksum_range'] = [0, F] if gather_ms is not None else [lo, hi]
-        if world == 1 and not args.no_e2e and args.as_rank_of <= 1:
+        if args.full and world == 1 and not args.no_e2e and args.as_rank_of <= 1:
             try:
                 result['end_to_end'] = end_to_end(stab, d_frames, disp, hom, F)
                 # north_star's ">= 500 frames/sec end-to-end stabilize()" is quoted on THIS figure (host frames in -> cropped host frames
@@ -932,7 +995,7 @@ def main():
                 result['roofline']['end_to_end_fps'] = result['end_to_end']['with_crop']['value']
             except Exception as e:                      # (host memory): never let the side measurement take the line down
                 result['end_to_end'] = {'error': f'{type(e).__name__}: {e}'}
-        if world == 1 and args.workload == 'cfg2' and not sliced and not args.no_workloads and args.as_rank_of <= 1 and not serial_mode:
+        if args.full and world == 1 and args.workload == 'cfg2' and not sliced and not args.no_workloads and args.as_rank_of <= 1 and not serial_mode:
             # the other single-GPU configurations in the same run, so that whoever runs this line observes them too
             del kp, d_out, d_frames
             torch.cuda.empty_cache()
@@ -944,7 +1007,7 @@ def main():
                 except Exception as e:
                     result['workloads'][name] = {'error': f'{type(e).__name__}: {e}'}
                 torch.cuda.empty_cache()
-        if world == 1 and args.cpu_frames > 0:
+        if args.full and world == 1 and args.cpu_frames > 0:
             try:
                 result['cpu_baseline'], stab_cpu = cpu_baseline(H, W, F, R, C, omega, iters, disp, hom, args.cpu_frames)
             except Exception as e:                      # e.g. no C compiler and no prebuilt oracle on the box

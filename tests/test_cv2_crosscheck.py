@@ -180,13 +180,23 @@ def test_median_blur_3x3_float32():
         check_coords(mt.median_blur3_f32(img), cv2.medianBlur(img, 3), f'medianBlur 3x3 float32 {shape} (mfs.py:359-360)')
 
 
-def test_vertex_velocities_against_reference_code_with_real_cv2():
-    """The reference's own _get_unstabilized_vertex_velocities with the real cv2 (needs /root/reference importable)."""
-    ref_dir = os.environ.get('MESHFLOW_REFERENCE_DIR', '/root/reference')
+def _reference():
+    """The reference's module `meshflowstabilizer` (not part of this repository): the stand-in tests/test_cv2_crosscheck_bitrot.py puts in
+    its place, else the reference itself from the directory MESHFLOW_REFERENCE_DIR names."""
+    stand_in = sys.modules.get('meshflowstabilizer')
+    if getattr(stand_in, '__stand_in__', False):
+        return stand_in
+    ref_dir = os.environ.get('MESHFLOW_REFERENCE_DIR', '')
     if not os.path.exists(os.path.join(ref_dir, 'meshflowstabilizer.py')):
-        pytest.skip('reference not present')
+        pytest.skip('reference not present (MESHFLOW_REFERENCE_DIR)')
     sys.path.insert(0, ref_dir)
-    import meshflowstabilizer as mfs
+    import meshflowstabilizer
+    return meshflowstabilizer
+
+
+def test_vertex_velocities_against_reference_code_with_real_cv2():
+    """The reference's own _get_unstabilized_vertex_velocities with the real cv2 (needs the reference importable: _reference())."""
+    mfs = _reference()
     from oracle import gen_golden, motion_oracle as mt
     W, H, R, C, er, ec = 640, 360, 8, 8, 5, 5
     feats, hom = gen_golden.motion_inputs(W, H, R, C, 4, (120, 180), 3)
@@ -268,12 +278,8 @@ def test_cfg2_resize_of_the_real_crop_rectangle():
 def test_reference_with_real_cv2_reproduces_the_committed_goldens(name):
     """The reference's OWN _get_stabilized_frames_and_crop_boundaries (mfs.py:909-1108) with the REAL cv2 against tests/golden/warp_*.npz
     (made by the same method under the stub cv2 whose four calls are the oracle's restatements): equal crop bounds, and frames equal up to
-    rounding ties of the two homography solvers.  Needs /root/reference (or MESHFLOW_REFERENCE_DIR) importable."""
-    ref_dir = os.environ.get('MESHFLOW_REFERENCE_DIR', '/root/reference')
-    if not os.path.exists(os.path.join(ref_dir, 'meshflowstabilizer.py')):
-        pytest.skip('reference not present')
-    sys.path.insert(0, ref_dir)
-    import meshflowstabilizer as mfs
+    rounding ties of the two homography solvers.  Needs the reference importable (_reference())."""
+    mfs = _reference()
     g = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', name + '.npz'))
     s = mfs.MeshFlowStabilizer(mesh_row_count=int(g['R']), mesh_col_count=int(g['C']),
                                color_outside_image_area_bgr=tuple(int(v) for v in g['border']))

@@ -3,7 +3,9 @@ calls -- and it has never executed (no cv2 in the build image or on the GPU box:
 rotting: it imports that file with a STAND-IN `cv2` whose entry points are the oracle's own restatements (the stub oracle/gen_golden.py
 runs the reference under, plus cv2.resize) and runs every test in it, so that a renamed oracle function, a changed signature or a
 default that moved (the 4-point solver's did in round 4) breaks HERE, on the CPU, and not on the day a real cv2 turns up.  Passing
-proves nothing about OpenCV -- the stand-in IS the oracle; it proves the cross-check still calls the current oracle API correctly."""
+proves nothing about OpenCV -- the stand-in IS the oracle; it proves the cross-check still calls the current oracle API correctly.
+The reference is not part of this repository either: its two methods the cross-check calls come from a stand-in as well, which answers
+with the reference's recorded outputs (tests/golden/) or the oracle's restatement of its warp loop."""
 import importlib.util
 import os
 import sys
@@ -42,12 +44,50 @@ def _stand_in_cv2():
     return m
 
 
+def _stand_in_reference():
+    """A stand-in for the reference's module (not part of this repository) with the two methods the cross-check calls:
+    _get_unstabilized_vertex_velocities hands back what the reference's own code returned for the same inputs under the stand-in cv2,
+    recorded by oracle/gen_golden.py in tests/golden/motion_*.npz (inputs it has no record of raise LookupError);
+    _get_stabilized_frames_and_crop_boundaries is the oracle's restatement of the reference's per-cell loop (meshflow_oracle.py)."""
+    from oracle import meshflow_oracle as mo
+    m = types.ModuleType('meshflowstabilizer')
+    m.__stand_in__ = True
+
+    class MeshFlowStabilizer:
+        def __init__(self, mesh_row_count=16, mesh_col_count=16, feature_ellipse_row_count=10, feature_ellipse_col_count=10,
+                     color_outside_image_area_bgr=(0, 0, 255), **_):
+            self.R, self.C, self.er, self.ec = mesh_row_count, mesh_col_count, feature_ellipse_row_count, feature_ellipse_col_count
+            self.border = color_outside_image_area_bgr
+
+        def _get_unstabilized_vertex_velocities(self, early_frame, late_frame):
+            early, late, hom = self._get_matched_features_and_homography(early_frame, late_frame)
+            H, W = early_frame.shape[:2]
+            for name in ('motion_small', 'motion_1080p', 'motion_ragged'):
+                g = np.load(os.path.join(HERE, 'golden', name + '.npz'))
+                if (int(g['width']), int(g['height']), int(g['R']), int(g['C']), int(g['ell_rows']), int(g['ell_cols'])) != \
+                        (W, H, self.R, self.C, self.er, self.ec):
+                    continue
+                for t in range(int(g['F']) - 1):
+                    lo, hi = g['offsets'][t], g['offsets'][t + 1]
+                    if np.array_equal(g['hom'][t], hom) and np.array_equal(g['early'][lo:hi], np.reshape(early, (-1, 2))) and \
+                            np.array_equal(g['late'][lo:hi], np.reshape(late, (-1, 2))):
+                        return (g['velocities'][t],)
+            raise LookupError('no recorded output of the reference for these inputs')
+
+        def _get_stabilized_frames_and_crop_boundaries(self, num_frames, frames, unstab, stab):
+            out, bounds, _ = mo.stabilized_frames_and_crop_boundaries(frames, self.R, self.C, unstab, stab, self.border)
+            return out, bounds
+
+    m.MeshFlowStabilizer = MeshFlowStabilizer
+    return m
+
+
 @pytest.fixture(scope='module')
 def crosscheck():
-    """tests/test_cv2_crosscheck.py imported under the stand-in (under another module name; sys.modules is put back afterwards)."""
+    """tests/test_cv2_crosscheck.py imported under the stand-ins (under another module name; sys.modules is put back afterwards)."""
     saved = {k: sys.modules.get(k) for k in ('cv2', 'meshflowstabilizer')}
     sys.modules['cv2'] = _stand_in_cv2()
-    sys.modules.pop('meshflowstabilizer', None)
+    sys.modules['meshflowstabilizer'] = _stand_in_reference()
     try:
         spec = importlib.util.spec_from_file_location('_cv2_crosscheck_under_stand_in', os.path.join(HERE, 'test_cv2_crosscheck.py'))
         mod = importlib.util.module_from_spec(spec)

@@ -18,6 +18,8 @@ def _named_files(text):
 
 
 def _exists(path):
+    if os.path.isabs(path):                 # a file outside the repository is not one the repository has
+        return False
     pattern = re.sub(r'\{[^}]*\}', '*', path)
     return any(glob.glob(os.path.join(REPO, root, pattern)) for root in ROOTS)
 

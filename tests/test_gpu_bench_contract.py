@@ -31,7 +31,7 @@ def _contract(d, n_gpus, steps, warmup):
 
 
 def test_bench_json_line_contract():
-    d = _run('--steps', '3', '--warmup', '1', '--cpu-frames', '4')
+    d = _run('--full', '--steps', '3', '--warmup', '1', '--cpu-frames', '4')
     _contract(d, 1, 3, 1)
     r = d['roofline']
     for key in ('bound', 'achieved', 'peak', 'unit', 'frac', 'traffic'):
@@ -57,10 +57,34 @@ def test_bench_json_line_contract():
     assert d['communicator']['world_size'] == 1
 
 
+def test_bench_plain_run_is_lean_and_dumps_the_last_step(tmp_path):
+    """Without --full the line carries the timed steps only; --dump-outputs writes what the last step returned, the same from run to run:
+    the crop bounds of the line and the stabilized paths of the oracle's Jacobi, a sample of the frames."""
+    import numpy as np
+    from meshflow_amd import synthetic
+    from oracle import meshflow_oracle as mo
+    runs = [_run('--steps', '3', '--warmup', '1', '--dump-outputs', str(tmp_path / k)) for k in 'ab']
+    d = runs[0]
+    _contract(d, 1, 3, 1)
+    assert d['cpu_baseline'] is None and d['kernel_path']['serial'] is None and d['jacobi']['kernel_ms'] is None
+    for key in ('end_to_end', 'workloads', 'next_rows', 'cfg1'):
+        assert key not in d, key
+    names = ('frames.npy', 'crop_bounds.npy', 'stabilized_vertex_displacements.npy')
+    assert sorted(p.name for p in (tmp_path / 'a').iterdir()) == sorted(names)
+    assert sum(p.stat().st_size for p in (tmp_path / 'a').iterdir()) <= 64 << 20
+    got = {n: np.load(tmp_path / 'a' / n) for n in names}
+    for n in names:
+        assert got[n].dtype in (np.float32, np.float64) and np.array_equal(got[n], np.load(tmp_path / 'b' / n)), n
+    assert got['crop_bounds.npy'].tolist() == d['crop_bounds'] == runs[1]['crop_bounds']
+    disp, hom = synthetic.motion(64, 16, 16, seed=0)
+    assert np.abs(got['stabilized_vertex_displacements.npy'] - mo.stabilized_vertex_displacements(640, 360, 0, disp, hom, 10, 100)).max() < 1e-9
+    assert got['frames.npy'].shape == (1 << 22,) and got['frames.npy'].max() <= 255
+
+
 def test_bench_default_run_carries_the_other_configurations():
-    """The driver's own command line (default workload = BASELINE configs[1]): the line also measures configs 3 and 4-shard in the same
-    run -- warp launch time and roofline fraction, step time, Jacobi kernel, host-to-host clip against the PCIe rate of this run."""
-    proc = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py'), '--gpus', '1', '--steps', '5', '--warmup', '2', '--cpu-frames', '8',
+    """The driver's own command line (default workload = BASELINE configs[1]) with --full: the line also measures configs 3 and 4-shard in
+    the same run -- warp launch time and roofline fraction, step time, Jacobi kernel, host-to-host clip against the PCIe rate of this run."""
+    proc = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py'), '--gpus', '1', '--steps', '5', '--warmup', '2', '--full', '--cpu-frames', '8',
                            '--no-faithful', '--workload-steps', '4'], cwd=REPO, capture_output=True, text=True, timeout=1500)
     assert proc.returncode == 0, proc.stderr[-3000:]
     lines = [l for l in proc.stdout.splitlines() if l.strip().startswith('{')]
@@ -104,7 +128,7 @@ def test_bench_two_ranks_started_by_bench_itself():
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_PORT')}
     env['MESHFLOW_DIST_BACKEND'] = 'gloo'
     proc = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py'), '--workload', 'small', '--gpus', '2', '--steps', '2',
-                           '--warmup', '1'], cwd=REPO, capture_output=True, text=True, timeout=900, env=env)
+                           '--warmup', '1', '--full'], cwd=REPO, capture_output=True, text=True, timeout=900, env=env)
     assert proc.returncode == 0, proc.stderr[-3000:]
     lines = [l for l in proc.stdout.splitlines() if l.strip().startswith('{')]
     assert len(lines) == 1, proc.stdout[-2000:]
@@ -135,7 +159,7 @@ def test_bench_two_ranks_under_the_drivers_own_launcher():
     port = 29500 + os.getpid() % 400
     proc = subprocess.run([sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr', '127.0.0.1',
                            '--master-port', str(port), os.path.join(REPO, 'bench.py'), '--workload', 'small', '--gpus', '2', '--steps', '2',
-                           '--warmup', '1'], cwd=REPO, capture_output=True, text=True, timeout=900, env=env)
+                           '--warmup', '1', '--full'], cwd=REPO, capture_output=True, text=True, timeout=900, env=env)
     assert proc.returncode == 0, proc.stderr[-3000:]
     lines = [l for l in proc.stdout.splitlines() if l.strip().startswith('{')]
     assert len(lines) == 1, proc.stdout[-2000:]
@@ -163,7 +187,7 @@ def test_bench_eight_ranks_under_the_drivers_own_launcher():
     port = 29900 + os.getpid() % 90
     common = ['--workload', 'small', '--steps', '2', '--warmup', '1', '--cpu-frames', '0', '--checksum']
     proc = subprocess.run([sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '8', '--master-addr', '127.0.0.1',
-                           '--master-port', str(port), os.path.join(REPO, 'bench.py'), '--gpus', '8', '--frames', '6'] + common,
+                           '--master-port', str(port), os.path.join(REPO, 'bench.py'), '--gpus', '8', '--frames', '6', '--full'] + common,
                           cwd=REPO, capture_output=True, text=True, timeout=1500, env=env)
     assert proc.returncode == 0, proc.stderr[-3000:]
     lines = [l for l in proc.stdout.splitlines() if l.strip().startswith('{')]

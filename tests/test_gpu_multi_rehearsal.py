@@ -104,7 +104,7 @@ def test_ragged_split_300_frames_over_8_ranks_with_the_hip_operators(dev):
 
 def test_two_rank_bench_gathers_the_whole_clip(dev):
     """`python bench.py --gpus 2` (gloo: both ranks on this GPU): the frames GATHERED on rank 0 equal one process warping all of them."""
-    d = _bench('--workload', 'small', '--gpus', '2', '--steps', '1', '--warmup', '0', '--checksum', env={'MESHFLOW_DIST_BACKEND': 'gloo'})
+    d = _bench('--workload', 'small', '--gpus', '2', '--steps', '1', '--warmup', '0', '--full', '--checksum', env={'MESHFLOW_DIST_BACKEND': 'gloo'})
     assert d['frames_checksum_range'] == [0, 128] and d['gather_to_rank0_ms'] > 0
     want, bounds = _whole_clip(dev, 'small', 128)
     assert d['frames_checksum'] == want

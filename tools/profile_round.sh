@@ -6,9 +6,9 @@
 tag=${1:-r01}
 export TMPDIR=/tmp; R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/prof_$tag; mkdir -p $O; cd /tmp
 WORKLOAD=${WORKLOAD:-cfg2}
-BENCH="python3 $R/bench.py --steps 5 --warmup 1 --cpu-frames 0 --no-e2e --workload $WORKLOAD"
+BENCH="python3 $R/bench.py --full --steps 5 --warmup 1 --cpu-frames 0 --no-e2e --workload $WORKLOAD"
 # >= 50 launches per kernel for the duration statistics (the PMC passes serialise kernels and need fewer)
-BENCH_STATS="python3 $R/bench.py --steps ${STATS_STEPS:-50} --warmup 5 --cpu-frames 0 --no-e2e --workload $WORKLOAD"
+BENCH_STATS="python3 $R/bench.py --full --steps ${STATS_STEPS:-50} --warmup 5 --cpu-frames 0 --no-e2e --workload $WORKLOAD"
 rm -rf /tmp/ps /tmp/pf /tmp/pw /tmp/cf /tmp/cw
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/ps -o r -- $BENCH_STATS > $O/stats_run.log 2>&1
 grep -E "\"Name\"|mf::" /tmp/ps/r_kernel_stats.csv > $O/kernel_stats.csv

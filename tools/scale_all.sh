@@ -30,9 +30,9 @@ if [ "$DRY" = 0 ]; then
 fi
 run() {     # name, then the bench flags
     local name=$1; shift
-    if [ "$DRY" = 1 ]; then echo "python bench.py $*"; return; fi
-    echo "== $name: python bench.py $*" | tee -a "$OUT/scale.jsonl" >&2
-    if timeout 1500 python bench.py "$@" >> "$OUT/scale.jsonl" 2> "$OUT/$name.err"; then :; else
+    if [ "$DRY" = 1 ]; then echo "python bench.py --full $*"; return; fi
+    echo "== $name: python bench.py --full $*" | tee -a "$OUT/scale.jsonl" >&2
+    if timeout 1500 python bench.py --full "$@" >> "$OUT/scale.jsonl" 2> "$OUT/$name.err"; then :; else
         echo "{\"failed\": \"$name\", \"rc\": $?}" >> "$OUT/scale.jsonl"
     fi
 }

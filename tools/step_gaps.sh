@@ -1,7 +1,7 @@
 #!/bin/bash
 # Kernel timeline of bench.py steps: durations and the idle gaps between consecutive kernels (rocprofv3 kernel trace).
 export TMPDIR=/tmp; R=$GRAFT_REPO_ROOT; cd /tmp; rm -rf /tmp/kt
-timeout 300 rocprofv3 --kernel-trace --output-format csv -d /tmp/kt -o r -- python3 $R/bench.py --steps 8 --warmup 2 --cpu-frames 0 --no-e2e > /tmp/kt.log 2>&1
+timeout 300 rocprofv3 --kernel-trace --output-format csv -d /tmp/kt -o r -- python3 $R/bench.py --full --steps 8 --warmup 2 --cpu-frames 0 --no-e2e > /tmp/kt.log 2>&1
 python3 - <<'PY'
 import csv
 rows = sorted(((int(r['Start_Timestamp']), int(r['End_Timestamp']), r['Kernel_Name'].split('(')[0].replace('void ', '').replace('mf::', '')[:28])

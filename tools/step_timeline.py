@@ -1,7 +1,7 @@
 """Timeline of the kernels of bench.py's timed steps from a rocprofv3 --kernel-trace CSV: per kernel the mean duration and the mean idle
 gap in front of it (end of the previous kernel on any stream -> its start), over the steps between the first and last warp launch.
 
-    rocprofv3 --kernel-trace --output-format csv -d /tmp/kt -o r -- python3 bench.py --steps 20 --warmup 5 --cpu-frames 0 --no-e2e
+    rocprofv3 --kernel-trace --output-format csv -d /tmp/kt -o r -- python3 bench.py --full --steps 20 --warmup 5 --cpu-frames 0 --no-e2e
     python tools/step_timeline.py /tmp/kt/r_kernel_trace.csv [skip_first_n_warps]
 """
 import csv
