@@ -146,6 +146,23 @@ int mf_warp_clip_u8c3(const uint8_t* d_frames, uint8_t* d_out, const double* d_u
                       int R, int C, const uint8_t border_bgr[3], void* d_table, int32_t* d_crop, int32_t* d_bounds, int32_t* d_status,
                       int chunks, void* prep_stream, void* stream);
 
+/* ---- the same warp for uint16 frames (mfs.py:1063-1069: cv2.remap takes CV_16UC3 unchanged) ----
+ * d_frames, d_out: [n][H][W][3] uint16 (BGR), 2-byte aligned is enough; all offsets are 64-bit.  Ownership, coordinates, the crop
+ * flags and the clip rectangle are those of the uint8 calls on the same table (d_crop / d_bounds come out identical); the pixels follow
+ * cv2.remap's 16U bilinear path (imgwarp.cpp remapBilinear<Cast<float, ushort>, RemapNoVec, float>): the same 1/32-pixel map
+ * quantisation, float32 weights (1 - fy/32)(1 - fx/32) ..., t = ((S00 w0 + S01 w1) + S10 w2) + S11 w3 in float32 (each product and sum
+ * rounded, no FMA), out = min(rint_half_even(t), 65535); outside taps are border_bgr[k] as given (the default (0, 0, 255) is NOT scaled
+ * to 16 bits), a 2 x 2 footprint wholly outside gives border_bgr.  mf_warp_clip_u16c3 is mf_warp_clip_u8c3 with the same `chunks` /
+ * `prep_stream` semantics.  Null pointers, d_frames == d_out, bad sizes and R or C > 64 return MF_ERR_INVALID_ARG before anything is
+ * launched (the clip call: before its cell table). */
+int mf_warp_u16c3(const uint16_t* d_frames, uint16_t* d_out, const void* d_table, int n, int W, int H,
+                  int R, int C, const uint16_t border_bgr[3], int32_t* d_crop, void* stream);
+int mf_warp_bounds_u16c3(const uint16_t* d_frames, uint16_t* d_out, const void* d_table, int n, int W, int H,
+                         int R, int C, const uint16_t border_bgr[3], int32_t* d_crop, int32_t* d_bounds, void* stream);
+int mf_warp_clip_u16c3(const uint16_t* d_frames, uint16_t* d_out, const double* d_unstab, const double* d_stab, int n, int W, int H,
+                       int R, int C, const uint16_t border_bgr[3], void* d_table, int32_t* d_crop, int32_t* d_bounds, int32_t* d_status,
+                       int chunks, void* prep_stream, void* stream);
+
 /* Clip-level crop bounds (mfs.py:1103-1106): {max left, max top, min right, min bottom} over n frames.
  * d_bounds: [4] int32. */
 int mf_crop_reduce(const int32_t* d_crop, int n, int W, int H, int32_t* d_bounds, void* stream);
@@ -158,6 +175,12 @@ int mf_crop_reduce(const int32_t* d_crop, int n, int W, int H, int32_t* d_bounds
 size_t mf_crop_resize_workspace_bytes(int W, int H);
 int mf_crop_resize_u8c3(const uint8_t* d_frames, uint8_t* d_out, int n, int W, int H, int left, int top, int right,
                         int bottom, void* d_work, void* stream);
+/* The same for uint16 frames (mfs.py:1150-1155: cv2.resize takes CV_16UC3 unchanged): resize.cpp's float path (resizeGeneric_ with
+ * HResizeLinear<ushort, float, float> + VResizeLinear<ushort, float, float, Cast<float, ushort>>) -- the 8-bit index and fraction
+ * tables, float32 coefficients (1 - f, f), t = S[sx] a0 + S[sx+1] a1 and out = saturate_cast<ushort>(t0 b0 + t1 b1), float32, unfused,
+ * rounded half to even.  The same workspace size; the same refusals. */
+int mf_crop_resize_u16c3(const uint16_t* d_frames, uint16_t* d_out, int n, int W, int H, int left, int top, int right,
+                         int bottom, void* d_work, void* stream);
 
 /* ---- the row before the path: vertex-motion accumulation (mfs.py:236-452 from the matched features on) ----
  * Replaces the Python loops of _get_vertex_nearby_feature_residual_velocities (mfs.py:365-452), the medians, global

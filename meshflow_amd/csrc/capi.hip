@@ -116,6 +116,18 @@ int mf_warp_u8c3(const uint8_t* d_frames, uint8_t* d_out, const void* d_table, i
     return launch_warp(d_frames, d_out, tv, n, W, H, R, C, pack_border(border_bgr), d_crop, (hipStream_t)stream);
 }
 
+static uint64_t pack_border16(const uint16_t b[3]) { return (uint64_t)b[0] | ((uint64_t)b[1] << 16) | ((uint64_t)b[2] << 32); }
+
+int mf_warp_u16c3(const uint16_t* d_frames, uint16_t* d_out, const void* d_table, int n, int W, int H,
+                  int R, int C, const uint16_t border_bgr[3], int32_t* d_crop, void* stream)
+{
+    if (!d_frames || !d_out || !d_table || !border_bgr || !d_crop) { set_error("mf_warp_u16c3: null pointer"); return MF_ERR_INVALID_ARG; }
+    if (d_frames == d_out) { set_error("mf_warp_u16c3: d_frames and d_out alias"); return MF_ERR_INVALID_ARG; }
+    if (n <= 0 || R <= 0 || C <= 0) { set_error("mf_warp_u16c3: bad sizes"); return MF_ERR_INVALID_ARG; }
+    const TableView tv = table_view(const_cast<void*>(d_table), n, W, H, R, C);
+    return launch_warp_u16(d_frames, d_out, tv, n, W, H, R, C, pack_border16(border_bgr), d_crop, (hipStream_t)stream);
+}
+
 int mf_crop_scan_f64(const void* d_table, int n, int W, int H, int R, int C, int32_t* d_crop, void* stream)
 {
     if (!d_table || !d_crop) { set_error("mf_crop_scan_f64: null pointer"); return MF_ERR_INVALID_ARG; }
@@ -147,6 +159,17 @@ int mf_warp_bounds_u8c3(const uint8_t* d_frames, uint8_t* d_out, const void* d_t
     return launch_warp(d_frames, d_out, tv, n, W, H, R, C, pack_border(border_bgr), d_crop, (hipStream_t)stream);
 }
 
+int mf_warp_bounds_u16c3(const uint16_t* d_frames, uint16_t* d_out, const void* d_table, int n, int W, int H,
+                         int R, int C, const uint16_t border_bgr[3], int32_t* d_crop, int32_t* d_bounds, void* stream)
+{
+    if (!d_frames || !d_out || !d_table || !border_bgr || !d_crop || !d_bounds) { set_error("mf_warp_bounds_u16c3: null pointer"); return MF_ERR_INVALID_ARG; }
+    if (d_frames == d_out) { set_error("mf_warp_bounds_u16c3: d_frames and d_out alias"); return MF_ERR_INVALID_ARG; }
+    if (n <= 0 || R <= 0 || C <= 0) { set_error("mf_warp_bounds_u16c3: bad sizes"); return MF_ERR_INVALID_ARG; }
+    TableView tv = table_view(const_cast<void*>(d_table), n, W, H, R, C);
+    tv.bounds = d_bounds;
+    return launch_warp_u16(d_frames, d_out, tv, n, W, H, R, C, pack_border16(border_bgr), d_crop, (hipStream_t)stream);
+}
+
 int mf_crop_scan_bounds_f64(const void* d_table, int n, int W, int H, int R, int C, int32_t* d_crop, int32_t* d_bounds, void* stream)
 {
     if (!d_table || !d_crop || !d_bounds) { set_error("mf_crop_scan_bounds_f64: null pointer"); return MF_ERR_INVALID_ARG; }
@@ -173,6 +196,14 @@ int mf_crop_resize_u8c3(const uint8_t* d_frames, uint8_t* d_out, int n, int W, i
     if (!d_frames || !d_out || !d_work) { set_error("mf_crop_resize_u8c3: null pointer"); return MF_ERR_INVALID_ARG; }
     if (d_frames == d_out) { set_error("mf_crop_resize_u8c3: d_frames and d_out alias"); return MF_ERR_INVALID_ARG; }
     return launch_crop_resize(d_frames, d_out, n, W, H, left, top, right, bottom, d_work, (hipStream_t)stream);
+}
+
+int mf_crop_resize_u16c3(const uint16_t* d_frames, uint16_t* d_out, int n, int W, int H, int left, int top, int right,
+                         int bottom, void* d_work, void* stream)
+{
+    if (!d_frames || !d_out || !d_work) { set_error("mf_crop_resize_u16c3: null pointer"); return MF_ERR_INVALID_ARG; }
+    if (d_frames == d_out) { set_error("mf_crop_resize_u16c3: d_frames and d_out alias"); return MF_ERR_INVALID_ARG; }
+    return launch_crop_resize_u16(d_frames, d_out, n, W, H, left, top, right, bottom, d_work, (hipStream_t)stream);
 }
 
 size_t mf_vertex_motion_workspace_bytes(int total_features, int max_per_pair, int P, int R, int C)

@@ -52,18 +52,41 @@ ClipSide* clip_side_for_current_device()
 
 using namespace mf;
 
-extern "C" int mf_warp_clip_u8c3(const uint8_t* d_frames, uint8_t* d_out, const double* d_unstab, const double* d_stab, int n, int W, int H,
-                                 int R, int C, const uint8_t border_bgr[3], void* d_table, int32_t* d_crop, int32_t* d_bounds,
-                                 int32_t* d_status, int chunks, void* prep_stream, void* stream)
+namespace {
+
+// The warp of one frame range, per pixel type: uint8 (launch_warp, border packed B | G << 8 | R << 16) or uint16 (launch_warp_u16,
+// B | G << 16 | R << 32).
+int warp_range(const uint8_t* frames, uint8_t* out, const TableView& tv, int n, int W, int H, int R, int C, const uint8_t border_bgr[3],
+               int32_t* crop, hipStream_t st)
+{
+    const uint32_t border = (uint32_t)border_bgr[0] | ((uint32_t)border_bgr[1] << 8) | ((uint32_t)border_bgr[2] << 16);
+    return launch_warp(frames, out, tv, n, W, H, R, C, border, crop, st);
+}
+int warp_range(const uint16_t* frames, uint16_t* out, const TableView& tv, int n, int W, int H, int R, int C, const uint16_t border_bgr[3],
+               int32_t* crop, hipStream_t st)
+{
+    const uint64_t border = (uint64_t)border_bgr[0] | ((uint64_t)border_bgr[1] << 16) | ((uint64_t)border_bgr[2] << 32);
+    return launch_warp_u16(frames, out, tv, n, W, H, R, C, border, crop, st);
+}
+
+template <typename T>
+int warp_clip(const char* name, const T* d_frames, T* d_out, const double* d_unstab, const double* d_stab, int n, int W, int H,
+              int R, int C, const T border_bgr[3], void* d_table, int32_t* d_crop, int32_t* d_bounds,
+              int32_t* d_status, int chunks, void* prep_stream, void* stream)
 {
     if (!d_frames || !d_out || !d_unstab || !d_stab || !border_bgr || !d_table || !d_crop || !d_bounds || !d_status) {
-        set_error("mf_warp_clip_u8c3: null pointer");
+        set_error("%s: null pointer", name);
         return MF_ERR_INVALID_ARG;
     }
-    if (d_frames == d_out) { set_error("mf_warp_clip_u8c3: d_frames and d_out alias"); return MF_ERR_INVALID_ARG; }
-    if (n <= 0 || R <= 0 || C <= 0 || W < 2 || H < 2) { set_error("mf_warp_clip_u8c3: bad sizes"); return MF_ERR_INVALID_ARG; }
+    if (d_frames == d_out) { set_error("%s: d_frames and d_out alias", name); return MF_ERR_INVALID_ARG; }
+    if (n <= 0 || R <= 0 || C <= 0 || W < 2 || H < 2) { set_error("%s: bad sizes", name); return MF_ERR_INVALID_ARG; }
+    // (the uint16 call refuses what its warp would refuse before the cell table is launched; the uint8 one keeps its order)
+    if (sizeof(T) == 2 && (R > 64 || C > 64 || W > 32767 || H > 32767)) {
+        set_error("%s: unsupported shape W=%d H=%d R=%d C=%d", name, W, H, R, C);
+        return MF_ERR_INVALID_ARG;
+    }
     ClipSide* side = clip_side_for_current_device();
-    if (!side) { set_error("mf_warp_clip_u8c3: no stream / events on this device"); return MF_ERR_HIP; }
+    if (!side) { set_error("%s: no stream / events on this device", name); return MF_ERR_HIP; }
     if (chunks <= 0) {
         // IN ORDER (the default of the product pipeline -- measured: kernels that run beside the warp kernel cost it more than they take
         // alone): the whole table on `stream`, then the warp by itself.  The rectangle comes from the warp's own fused
@@ -71,7 +94,6 @@ extern "C" int mf_warp_clip_u8c3(const uint8_t* d_frames, uint8_t* d_out, const 
         // there, beside the first microseconds of the warp) -- what a sharded run wants: its all-reduce then hides behind the warp as well.
         const hipStream_t st = (hipStream_t)stream;
         const hipStream_t prep = (hipStream_t)prep_stream;
-        const uint32_t border = (uint32_t)border_bgr[0] | ((uint32_t)border_bgr[1] << 8) | ((uint32_t)border_bgr[2] << 16);
         TableView tv = table_view(d_table, n, W, H, R, C);
         tv.bounds = d_bounds;                  // the kernels fold the clip-level rectangle into the caller's 16 bytes themselves: no reduction launch
         if (const int rc = launch_cell_table(d_unstab, d_stab, n, W, H, R, C, tv, d_crop, d_status, st)) return rc;
@@ -84,7 +106,7 @@ extern "C" int mf_warp_clip_u8c3(const uint8_t* d_frames, uint8_t* d_out, const 
             if (const int rc = launch_crop_scan(tv, n, W, H, R, C, d_crop, prep)) return rc;
             MF_HIP_TRY(hipEventRecord(side->done, prep));
         }
-        if (const int rc = launch_warp(d_frames, d_out, tv, n, W, H, R, C, border, d_crop, st)) return rc;
+        if (const int rc = warp_range(d_frames, d_out, tv, n, W, H, R, C, border_bgr, d_crop, st)) return rc;
         if (early) MF_HIP_TRY(hipStreamWaitEvent(st, side->done, 0));
         return MF_OK;
     }
@@ -92,7 +114,6 @@ extern "C" int mf_warp_clip_u8c3(const uint8_t* d_frames, uint8_t* d_out, const 
     if (chunks > n) chunks = n;
     const hipStream_t st = (hipStream_t)stream;
     hipStream_t prep = (hipStream_t)prep_stream;
-    const uint32_t border = (uint32_t)border_bgr[0] | ((uint32_t)border_bgr[1] << 8) | ((uint32_t)border_bgr[2] << 16);
     TableView tv = table_view(d_table, n, W, H, R, C);
     tv.bounds = d_bounds;                      // (the first chunk's cell table sets the defaults there, the scan and the warps fold into it)
     const size_t vb1 = (size_t)(R + 1) * (C + 1) * 2, fb = (size_t)W * H * 3;
@@ -118,9 +139,27 @@ extern "C" int mf_warp_clip_u8c3(const uint8_t* d_frames, uint8_t* d_out, const 
     for (int i0 = 0; i0 < n; i0 += per, ++nk) {
         const int m = n - i0 < per ? n - i0 : per;
         if (!one_stream) MF_HIP_TRY(hipStreamWaitEvent(st, side->ready[nk], 0));
-        if (const int rc = launch_warp(d_frames + fb * i0, d_out + fb * i0, table_slice(tv, i0, W, H, R, C), m, W, H, R, C, border,
-                                       d_crop + 4 * (size_t)i0, st)) return rc;
+        if (const int rc = warp_range(d_frames + fb * i0, d_out + fb * i0, table_slice(tv, i0, W, H, R, C), m, W, H, R, C, border_bgr,
+                                      d_crop + 4 * (size_t)i0, st)) return rc;
     }
     if (!one_stream) MF_HIP_TRY(hipStreamWaitEvent(st, side->done, 0));          // `stream` order now also implies: d_bounds is final
     return MF_OK;
+}
+
+}  // namespace
+
+extern "C" int mf_warp_clip_u8c3(const uint8_t* d_frames, uint8_t* d_out, const double* d_unstab, const double* d_stab, int n, int W, int H,
+                                 int R, int C, const uint8_t border_bgr[3], void* d_table, int32_t* d_crop, int32_t* d_bounds,
+                                 int32_t* d_status, int chunks, void* prep_stream, void* stream)
+{
+    return warp_clip("mf_warp_clip_u8c3", d_frames, d_out, d_unstab, d_stab, n, W, H, R, C, border_bgr, d_table, d_crop, d_bounds, d_status,
+                     chunks, prep_stream, stream);
+}
+
+extern "C" int mf_warp_clip_u16c3(const uint16_t* d_frames, uint16_t* d_out, const double* d_unstab, const double* d_stab, int n, int W, int H,
+                                  int R, int C, const uint16_t border_bgr[3], void* d_table, int32_t* d_crop, int32_t* d_bounds,
+                                  int32_t* d_status, int chunks, void* prep_stream, void* stream)
+{
+    return warp_clip("mf_warp_clip_u16c3", d_frames, d_out, d_unstab, d_stab, n, W, H, R, C, border_bgr, d_table, d_crop, d_bounds, d_status,
+                     chunks, prep_stream, stream);
 }

@@ -582,6 +582,171 @@ __device__ __forceinline__ uint3 blend(const uint32_t (&bx)[4], const uint32_t (
 }
 
 
+// ---- uint16 frames: cv2.remap of CV_16UC3 (imgwarp.cpp RemapInvoker + remapBilinear<Cast<float, ushort>, RemapNoVec, float>) ----------
+// The map quantisation is the 8-bit one (sx = cvRound(32 u), ix = sx >> 5, fx = sx & 31); the weights are BilinearTab_f[fy][fx] =
+// {(1 - fy/32)(1 - fx/32), (1 - fy/32) fx/32, fy/32 (1 - fx/32), fy/32 fx/32}, float32 and exact (dyadic); the blend is the scalar
+// float32 chain ((S00 w0 + S01 w1) + S10 w2) + S11 w3 with every product and sum rounded on its own (no FMA: -ffp-contract=off), and
+// out = saturate_cast<ushort>(t) = min(rint(t), 65535).  Products of 16-bit samples and 10-bit weights need 26 bits: they DO round, so
+// the integer tricks of the 8-bit blend do not carry over.
+__device__ __forceinline__ uint32_t blend16(float s00, float s01, float s10, float s11, float w0, float w1, float w2, float w3)
+{
+    const float t = ((s00 * w0 + s01 * w1) + s10 * w2) + s11 * w3;     // (t >= 0: non-negative samples and weights)
+    return min((uint32_t)rintf(t), 65535u);
+}
+// ... for two pixels at once: the same chain per element, on packed float32 (v_pk_mul_f32 / v_pk_add_f32 round each element like the
+// scalar instructions)
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ f32x2 blend16x2(f32x2 s00, f32x2 s01, f32x2 s10, f32x2 s11, f32x2 w0, f32x2 w1, f32x2 w2, f32x2 w3)
+{
+    return ((s00 * w0 + s01 * w1) + s10 * w2) + s11 * w3;
+}
+
+// Footprint-level tail of the U16 instantiation of footprint_body: the lane's four pixels at source coordinates (u, v) -- taps, blend,
+// crop flags, store.  Deep-interior footprints (every tap two pixels inside the frame, no crop flag possible) take each pixel's two tap
+// rows as one 12-byte load apiece (the frame may be only 2-byte aligned: unaligned dword loads); the others take every tap at its
+// position clamped into the frame and replace outside taps by the border colour, and a 2 x 2 footprint wholly outside the frame gives the
+// border colour itself (float products of the border colour need not sum back to it exactly).  All offsets are 64-bit.
+__device__ __forceinline__ void remap_store_u16(const float (&u)[4], const float (&v)[4], uint32_t f, int x0, int y, bool active, int W, int H,
+                                                const uint16_t* __restrict__ frames, uint16_t* __restrict__ out, uint64_t border16,
+                                                int32_t* __restrict__ crop, int32_t* __restrict__ clip)
+{
+    const uint64_t frame_samples = 3ull * (uint64_t)((uint32_t)W * (uint32_t)H);
+    const uint16_t* __restrict__ src = frames + (uint64_t)f * frame_samples;
+    uint16_t* __restrict__ dst = out + (uint64_t)f * frame_samples;
+    const int lane = threadIdx.x;
+    uint32_t bx[4], by[4];
+    fixed_point(u, v, bx, by);
+    uint32_t dxm = 0, dym = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        dxm = max(dxm, bx[j] - (0x4B400000u + 64u));
+        dym = max(dym, by[j] - (0x4B400000u + 64u));
+    }
+    // deep interior (as in footprint_body): 2 <= ix <= W-3 and 2 <= iy <= H-3 for all four pixels
+    const bool deep = W >= 5 && H >= 5 && dxm <= (uint32_t)(32 * (W - 3) + 31 - 64) && dym <= (uint32_t)(32 * (H - 3) + 31 - 64);
+    const bool fast = __ballot(active && !deep) == 0;
+    uint32_t o[4][3];                                                   // the lane's 12 output samples
+    int c_left = 0, c_top = 0, c_right = W - 1, c_bottom = H - 1;
+    if (active) {
+        if (fast) {
+            // taps as float, [pixel][channel][S00, S01, S10, S11]; then pixels 0 + 1 and 2 + 3 blended pairwise (weights too)
+            float sv[4][3][4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const uint32_t ix = __builtin_amdgcn_ubfe(bx[j], 5, 17), iy = __builtin_amdgcn_ubfe(by[j], 5, 17);
+                const uint16_t* __restrict__ p0 = src + 3ull * (uint64_t)(iy * (uint32_t)W + ix);
+                uint32_t a[3], b[3];                                    // B0 G0 | R0 B1 | G1 R1 of rows iy and iy + 1
+                __builtin_memcpy(a, p0, 12);
+                __builtin_memcpy(b, p0 + 3ull * (uint32_t)W, 12);
+                const uint32_t ha[6] = { a[0] & 0xFFFFu, a[0] >> 16, a[1] & 0xFFFFu, a[1] >> 16, a[2] & 0xFFFFu, a[2] >> 16 };
+                const uint32_t hb[6] = { b[0] & 0xFFFFu, b[0] >> 16, b[1] & 0xFFFFu, b[1] >> 16, b[2] & 0xFFFFu, b[2] >> 16 };
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    sv[j][c][0] = (float)ha[c]; sv[j][c][1] = (float)ha[3 + c];
+                    sv[j][c][2] = (float)hb[c]; sv[j][c][3] = (float)hb[3 + c];
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < 4; j += 2) {
+                const f32x2 ax = f32x2{ (float)(bx[j] & 31u), (float)(bx[j + 1] & 31u) } * 0.03125f;
+                const f32x2 ay = f32x2{ (float)(by[j] & 31u), (float)(by[j + 1] & 31u) } * 0.03125f;
+                const f32x2 ax0 = 1.0f - ax, ay0 = 1.0f - ay;
+                const f32x2 w0 = ay0 * ax0, w1 = ay0 * ax, w2 = ay * ax0, w3 = ay * ax;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    const f32x2 t = blend16x2(f32x2{ sv[j][c][0], sv[j + 1][c][0] }, f32x2{ sv[j][c][1], sv[j + 1][c][1] },
+                                              f32x2{ sv[j][c][2], sv[j + 1][c][2] }, f32x2{ sv[j][c][3], sv[j + 1][c][3] }, w0, w1, w2, w3);
+                    // (no clamp: the seven roundings of the chain move t by less than 7 * 2^-9 from the exact blend, a convex combination of
+                    // samples <= 65535, so rint(t) <= 65535 -- saturate_cast's clamp never acts here)
+                    o[j][c] = (uint32_t)rintf(t.x);
+                    o[j + 1][c] = (uint32_t)rintf(t.y);
+                }
+            }
+        } else {
+            // frame borders, uncovered pixels (at (W+1, H+1)), crop flags, out-of-range coordinates
+            const float fWm1 = (float)(W - 1), fHm1 = (float)(H - 1);
+            uint32_t spread = 0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                spread = max(spread, max(bx[j] - (0x4B400000u - 0x200000u), by[j] - (0x4B400000u - 0x200000u)));
+            const bool narrow = __ballot(spread >= 0x400000u) == 0;
+            const uint32_t cval[3] = { (uint32_t)(border16 & 0xFFFFu), (uint32_t)((border16 >> 16) & 0xFFFFu), (uint32_t)((border16 >> 32) & 0xFFFFu) };
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float uu = u[j], vv = v[j];
+                const int x = x0 + j;
+                if (x < W) {                                            // crop-boundary scan, mfs.py:1075-1098 (exact: Sterbenz)
+                    if (fabsf(uu) < 1.0f) c_left = max(c_left, x);
+                    if (fabsf(uu - fWm1) < 1.0f) c_right = min(c_right, x);
+                    if (fabsf(vv) < 1.0f) c_top = max(c_top, y);
+                    if (fabsf(vv - fHm1) < 1.0f) c_bottom = min(c_bottom, y);
+                }
+                const int sxx = narrow ? (int)(bx[j] - 0x4B400000u) : cv_round_f32(uu * 32.0f);
+                const int syy = narrow ? (int)(by[j] - 0x4B400000u) : cv_round_f32(vv * 32.0f);
+                const int ix = sxx >> 5, iy = syy >> 5;                 // (saturation to int16 cannot change any decision below)
+                if (ix >= W || ix + 1 < 0 || iy >= H || iy + 1 < 0) {  // the 2 x 2 footprint lies wholly outside: cval
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) o[j][c] = cval[c];
+                    continue;
+                }
+                const bool in_x0 = (unsigned)ix < (unsigned)W, in_x1 = (unsigned)(ix + 1) < (unsigned)W;
+                const bool in_y0 = (unsigned)iy < (unsigned)H, in_y1 = (unsigned)(iy + 1) < (unsigned)H;
+                const uint32_t cx0 = (uint32_t)min(max(ix, 0), W - 1), cx1 = (uint32_t)min(max(ix + 1, 0), W - 1);
+                const uint32_t r0 = (uint32_t)min(max(iy, 0), H - 1) * (uint32_t)W, r1 = (uint32_t)min(max(iy + 1, 0), H - 1) * (uint32_t)W;
+                const uint16_t* __restrict__ q00 = src + 3ull * (uint64_t)(r0 + cx0);
+                const uint16_t* __restrict__ q01 = src + 3ull * (uint64_t)(r0 + cx1);
+                const uint16_t* __restrict__ q10 = src + 3ull * (uint64_t)(r1 + cx0);
+                const uint16_t* __restrict__ q11 = src + 3ull * (uint64_t)(r1 + cx1);
+                const float ax = (float)(sxx & 31) * 0.03125f, ay = (float)(syy & 31) * 0.03125f;
+                const float ax0 = 1.0f - ax, ay0 = 1.0f - ay;
+                const float w0 = ay0 * ax0, w1 = ay0 * ax, w2 = ay * ax0, w3 = ay * ax;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    const uint32_t s00 = in_x0 && in_y0 ? (uint32_t)q00[c] : cval[c], s01 = in_x1 && in_y0 ? (uint32_t)q01[c] : cval[c];
+                    const uint32_t s10 = in_x0 && in_y1 ? (uint32_t)q10[c] : cval[c], s11 = in_x1 && in_y1 ? (uint32_t)q11[c] : cval[c];
+                    o[j][c] = blend16((float)s00, (float)s01, (float)s10, (float)s11, w0, w1, w2, w3);
+                }
+            }
+        }
+    }
+    if (!fast) {
+        // crop bounds: wave reduction, then at most one atomic per bound and wavefront (per frame, mfs.py:1075-1098, and the clip-level
+        // rectangle, mfs.py:1103-1106)
+        const bool any = c_left != 0 || c_top != 0 || c_right != W - 1 || c_bottom != H - 1;
+        if (__ballot(any) != 0) {
+#pragma unroll
+            for (int off = 32; off >= 1; off >>= 1) {
+                c_left = max(c_left, __shfl_xor(c_left, off));
+                c_top = max(c_top, __shfl_xor(c_top, off));
+                c_right = min(c_right, __shfl_xor(c_right, off));
+                c_bottom = min(c_bottom, __shfl_xor(c_bottom, off));
+            }
+            if (lane == 0) {
+                if (c_left != 0) { atomicMax(&crop[4 * f + 0], c_left); atomicMax(&clip[0], c_left); }
+                if (c_top != 0) { atomicMax(&crop[4 * f + 1], c_top); atomicMax(&clip[1], c_top); }
+                if (c_right != W - 1) { atomicMin(&crop[4 * f + 2], c_right); atomicMin(&clip[2], c_right); }
+                if (c_bottom != H - 1) { atomicMin(&crop[4 * f + 3], c_bottom); atomicMin(&clip[3], c_bottom); }
+            }
+        }
+    }
+    if (active) {
+        uint16_t* __restrict__ d = dst + 3ull * (uint64_t)((uint32_t)y * (uint32_t)W + (uint32_t)x0);
+        if (x0 + 3 < W) {                                               // 24 bytes at a 2-byte aligned address: unaligned dword stores
+            uint32_t w[6];
+#pragma unroll
+            for (int k = 0; k < 6; ++k) w[k] = o[(2 * k) / 3][(2 * k) % 3] | (o[(2 * k + 1) / 3][(2 * k + 1) % 3] << 16);
+            __builtin_memcpy(d, w, 24);
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (x0 + j < W) {
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) d[3 * j + c] = (uint16_t)o[j][c];
+                }
+        }
+    }
+}
+
 // ---- EXPERIMENT builds only (tools/phase_profile.sh; nothing of this is in the product library) ------------------------------------
 // -DMF_EXP_SKIP=mask: TIMING-ONLY kernels in which the wavefronts of a path class return right after the plan test that selects
 // them (their output is garbage): 1 hot, 2 border, 4 pair, 8 multi, 16 everything else, 32 every wavefront right after the plan and
@@ -605,13 +770,18 @@ __device__ unsigned long long mf_exp_phase[8];
 // SCAN: the crop-boundary scan ALONE (crop_scan_kernel below): the same ownership and coordinate code for footprint t of frame f,
 // then only the four edge tests of mfs.py:1075-1098 -- no window, no taps, no blend, no store.  The certified paths (hot, pair,
 // multi) are compiled out: their footprints cannot set a crop flag (MF_REGION_DEEP / MF_REGION_NOFLAG) and are never handed in.
-template <bool STAGE_OK, bool SCAN>
+// U16: the same ownership and coordinates for uint16 BGR frames (warp16_kernel): `frames` / `out` then point to uint16 samples, the border
+// colour is `border16` (B | G << 16 | R << 32) and the pixels go through remap_store_u16 at the end of the general path -- the plan's staged
+// windows are sized for 3-byte pixels, so the U16 instantiation has no staged path (STAGE_OK = false).
+template <bool STAGE_OK, bool SCAN, bool U16 = false>
 __device__ __forceinline__ void footprint_body(const uint32_t f, const uint32_t t, const FootPlan* __restrict__ plan, const FootRegion* __restrict__ regions,
                                                const WarpGeom& g, const uint8_t* __restrict__ frames,
                                                const double* __restrict__ records, uint8_t* __restrict__ out,
                                                const float* __restrict__ edges, int n, int W,
-                                               int H, int C, uint32_t border, int32_t* __restrict__ crop, int32_t* __restrict__ clip)
+                                               int H, int C, uint32_t border, int32_t* __restrict__ crop, int32_t* __restrict__ clip,
+                                               uint64_t border16 = 0)
 {
+    static_assert(!U16 || (!STAGE_OK && !SCAN), "the uint16 warp takes its taps from global memory");
     // inverse homographies of the footprint's candidate cells: [entry][Hi0..Hi8, pad] (80-byte rows)
     __shared__ __attribute__((aligned(16))) double s_hi[1][9][10];                // row 8: the "no cell" matrix, see OWN_NONE
     // source region of the footprint: MF_STAGE_ROWS rows of MF_STAGE_PITCH bytes (+ slack for the third dword of the last tap)
@@ -1367,6 +1537,11 @@ __device__ __forceinline__ void footprint_body(const uint32_t f, const uint32_t 
             }
             return;
         }
+        if constexpr (U16) {
+            remap_store_u16(u, v, f, x0, y, active, W, H, reinterpret_cast<const uint16_t*>(frames), reinterpret_cast<uint16_t*>(out), border16,
+                            crop, clip);
+            return;
+        }
         // cv2.remap: 1/32-pixel fixed point (round half to even), bilinear gather, store.
         uint32_t bx[4], by[4];
         fixed_point(u, v, bx, by);
@@ -1552,6 +1727,22 @@ __global__ __launch_bounds__(64) MF_WARP_ATTR void warp_kernel(const FootPlan* _
 #endif
     if (t >= g.per_frame) return;
     footprint_body<STAGE_OK, false>(f, t, plan, regions, g, frames, records, out, edges, n, W, H, C, border, crop, clip);
+}
+
+// The mesh warp of uint16 frames: warp_kernel's footprint order and ownership / coordinate code (footprint_body's general path: the staged
+// windows are sized for 3-byte pixels), cv2.remap's CV_16UC3 arithmetic at the end (remap_store_u16).  The same d_crop rows and clip
+// rectangle as warp_kernel on the same table.
+__global__ __launch_bounds__(64) void warp16_footprint(const FootPlan* __restrict__ plan, const FootRegion* __restrict__ regions,
+                                                       WarpGeom g, const uint16_t* __restrict__ frames,
+                                                       const double* __restrict__ records, uint16_t* __restrict__ out,
+                                                       const float* __restrict__ edges, int n, int W,
+                                                       int H, int C, uint64_t border16, int32_t* __restrict__ crop, int32_t* __restrict__ clip)
+{
+    const uint32_t f = blockIdx.y;
+    const uint32_t t = ((blockIdx.x + f) & 7u) * g.per_xcd + (blockIdx.x >> 3);
+    if (t >= g.per_frame) return;
+    footprint_body<false, false, true>(f, t, plan, regions, g, reinterpret_cast<const uint8_t*>(frames), records, reinterpret_cast<uint8_t*>(out),
+                                       edges, n, W, H, C, 0u, crop, clip, border16);
 }
 
 // The crop-boundary scan WITHOUT the pixels (mfs.py:1075-1106 depends on the coordinate maps only, i.e. on the cell table): fills
@@ -1805,6 +1996,34 @@ int launch_warp(const uint8_t* frames, uint8_t* out, const TableView& tv, int n,
             hipLaunchKernelGGL(warp_kernel<false>, grid, dim3(64), 0, st, pl, rgn, g, fr, rec, o, ed, m, W, H, C, border, crop + 4 * (size_t)f0, tv.bounds);
     }
     return hip_fail(hipGetLastError(), "warp_kernel launch");
+}
+
+int launch_warp_u16(const uint16_t* frames, uint16_t* out, const TableView& tv, int n, int W, int H, int R, int C,
+                    uint64_t border16, int32_t* crop, hipStream_t st)
+{
+    if (n <= 0 || W < 2 || H < 2 || W > 32767 || H > 32767 || R <= 0 || C <= 0 || R > MAX_MESH || C > MAX_MESH) {
+        set_error("mf_warp_u16c3: unsupported shape n=%d W=%d H=%d R=%d C=%d", n, W, H, R, C);
+        return MF_ERR_INVALID_ARG;
+    }
+    WarpGeom g;
+    uint64_t per_launch = make_warp_geom(W, H, R, C, g);
+    if (per_launch == 0) {
+        set_error("mf_warp_u16c3: frame too large");
+        return MF_ERR_INVALID_ARG;
+    }
+    if (const char* e = getenv("MF_WARP_FRAMES_PER_LAUNCH")) {      // testing aid, as in launch_warp
+        const long v = atol(e);
+        if (v > 0 && (uint64_t)v < per_launch) per_launch = (uint64_t)v;
+    }
+    const uint64_t frame_samples = 3ull * (uint64_t)W * (uint64_t)H;
+    for (int f0 = 0; f0 < n; f0 += (int)per_launch) {
+        const int m = n - f0 < (int)per_launch ? n - f0 : (int)per_launch;
+        const dim3 grid(g.per_xcd * 8u, (uint32_t)m);
+        hipLaunchKernelGGL(warp16_footprint, grid, dim3(64), 0, st, tv.plan + (size_t)f0 * g.per_frame, tv.regions + (size_t)f0 * g.per_frame, g,
+                           frames + (size_t)f0 * frame_samples, tv.records + (size_t)f0 * R * C * MF_CELL_DOUBLES, out + (size_t)f0 * frame_samples,
+                           tv.edges + (size_t)f0 * R * C * MF_EDGE_FLOATS, m, W, H, C, border16, crop + 4 * (size_t)f0, tv.bounds);
+    }
+    return hip_fail(hipGetLastError(), "warp16_footprint launch");
 }
 
 int launch_crop_scan(const TableView& tv, int n, int W, int H, int R, int C, int32_t* crop, hipStream_t st)

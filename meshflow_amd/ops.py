@@ -30,6 +30,25 @@ def _need(t, dtype, name):
         raise ValueError(f'{name} must be contiguous')
 
 
+_FRAME_DTYPES = (torch.uint8, torch.uint16)
+
+
+def _need_frames(t, name):
+    """Frames of either pixel type the device path takes (uint8 or uint16 BGR): returns the dtype."""
+    if isinstance(t, torch.Tensor) and t.dtype in _FRAME_DTYPES:
+        _need(t, t.dtype, name)
+        return t.dtype
+    _need(t, torch.uint8, name)          # (raises: not a tensor, or another dtype)
+
+
+def _border(border_bgr, dtype):
+    """The border colour as the C call takes it: clamp(round(v), 0, 255) for uint8, clamp(round(v), 0, 65535) for uint16 -- the value
+    itself, not scaled to 16 bits (cv2.remap's saturate_cast of borderValue)."""
+    if dtype == torch.uint16:
+        return (ctypes.c_uint16 * 3)(*[int(np.clip(round(float(v)), 0, 65535)) for v in border_bgr[:3]])
+    return (ctypes.c_uint8 * 3)(*[int(np.clip(round(float(v)), 0, 255)) for v in border_bgr[:3]])
+
+
 def jacobi(b, taps, lam, inv_on, omega, iters, out=None):
     """`iters` Jacobi sweeps for all S series at once (mfs.py:844-878 x every vertex).
     b: (F, S) float64 device tensor, frame-major.  Returns x (F, S)."""
@@ -122,24 +141,27 @@ def cell_table(unstab, stab, W, H, R, C, table=None, reset_status=True, bounds=N
 
 
 def warp(frames, table, border_bgr=(0, 0, 255), out=None, bounds=None):
-    """Mesh warp + crop scan of n frames (mfs.py:1000-1100).  frames: (n, H, W, 3) uint8 device tensor.
-    Returns the stabilized frames; per-frame crop values accumulate in table.crop, the clip-level rectangle in `bounds` (the tensor
-    `cell_table` was given) or, without one, in table.clip_bounds."""
-    _need(frames, torch.uint8, 'frames')
+    """Mesh warp + crop scan of n frames (mfs.py:1000-1100).  frames: (n, H, W, 3) uint8 or uint16 device tensor (uint16: cv2.remap's
+    16U arithmetic, include/meshflow_hip.h mf_warp_u16c3; the crop values are those of the uint8 warp of the same table).
+    Returns the stabilized frames (the input's dtype); per-frame crop values accumulate in table.crop, the clip-level rectangle in
+    `bounds` (the tensor `cell_table` was given) or, without one, in table.clip_bounds."""
+    dtype = _need_frames(frames, 'frames')
     n, H, W, ch = frames.shape
     if ch != 3 or (n, W, H) != (table.n, table.W, table.H):
         raise ValueError('frames do not match the cell table (n, H, W, 3)')
     if out is None:
         out = torch.empty_like(frames)
-    _need(out, torch.uint8, 'out')
-    border = (ctypes.c_uint8 * 3)(*[int(np.clip(round(float(v)), 0, 255)) for v in border_bgr[:3]])
+    _need(out, dtype, 'out')
+    border = _border(border_bgr, dtype)
+    u16 = dtype == torch.uint16
     if bounds is None:
-        _lib.check(_lib_.mf_warp_u8c3(_ptr(frames), _ptr(out), _ptr(table.buf), n, W, H, table.R, table.C, border,
-                                      _ptr(table.crop), _stream()))
+        fn = _lib_.mf_warp_u16c3 if u16 else _lib_.mf_warp_u8c3
+        _lib.check(fn(_ptr(frames), _ptr(out), _ptr(table.buf), n, W, H, table.R, table.C, border, _ptr(table.crop), _stream()))
     else:
         _need_bounds(bounds)
-        _lib.check(_lib_.mf_warp_bounds_u8c3(_ptr(frames), _ptr(out), _ptr(table.buf), n, W, H, table.R, table.C, border,
-                                             _ptr(table.crop), _ptr(bounds), _stream()))
+        fn = _lib_.mf_warp_bounds_u16c3 if u16 else _lib_.mf_warp_bounds_u8c3
+        _lib.check(fn(_ptr(frames), _ptr(out), _ptr(table.buf), n, W, H, table.R, table.C, border, _ptr(table.crop), _ptr(bounds),
+                      _stream()))
     return out
 
 
@@ -150,8 +172,8 @@ def warp_clip(frames, unstab, stab, table, border_bgr=(0, 0, 255), out=None, chu
     stream -- table, warp alone, rectangle (early on `prep_stream` when one is given).  Returns (stabilized frames,
     bounds): bounds = int32 {left, top, right, bottom} of the clip -- the caller's tensor when one is given, else table.bounds --,
     folded together by the kernels, final on the prep stream right after the tables' crop scan (and on the current stream after
-    the call); per-frame values in table.crop; table.status accumulates degenerate cells."""
-    _need(frames, torch.uint8, 'frames')
+    the call); per-frame values in table.crop; table.status accumulates degenerate cells.  frames: uint8 or uint16 (see `warp`)."""
+    dtype = _need_frames(frames, 'frames')
     _need(unstab, torch.float64, 'unstab')
     _need(stab, torch.float64, 'stab')
     n, H, W, ch = frames.shape
@@ -160,17 +182,18 @@ def warp_clip(frames, unstab, stab, table, border_bgr=(0, 0, 255), out=None, chu
         raise ValueError('frames / displacements do not match the cell table')
     if out is None:
         out = torch.empty_like(frames)
-    _need(out, torch.uint8, 'out')
+    _need(out, dtype, 'out')
     if bounds is None:                  # (without a caller-owned tensor: one per table, rewritten by the next call on it)
         if table.bounds is None:
             table.bounds = torch.empty(4, dtype=torch.int32, device=frames.device)
         bounds = table.bounds
     else:
         _need_bounds(bounds)
-    border = (ctypes.c_uint8 * 3)(*[int(np.clip(round(float(v)), 0, 255)) for v in border_bgr[:3]])
+    border = _border(border_bgr, dtype)
     prep = ctypes.c_void_p(prep_stream.cuda_stream) if prep_stream is not None else None
-    _lib.check(_lib_.mf_warp_clip_u8c3(_ptr(frames), _ptr(out), _ptr(unstab), _ptr(stab), n, W, H, table.R, table.C, border,
-                                       _ptr(table.buf), _ptr(table.crop), _ptr(bounds), _ptr(table.status), int(chunks), prep, _stream()))
+    fn = _lib_.mf_warp_clip_u16c3 if dtype == torch.uint16 else _lib_.mf_warp_clip_u8c3
+    _lib.check(fn(_ptr(frames), _ptr(out), _ptr(unstab), _ptr(stab), n, W, H, table.R, table.C, border,
+                  _ptr(table.buf), _ptr(table.crop), _ptr(bounds), _ptr(table.status), int(chunks), prep, _stream()))
     return out, bounds
 
 
@@ -196,17 +219,19 @@ def crop_reduce(crop, W, H):
 
 
 def crop_resize(frames, bounds, out=None):
-    """Crop to the inclusive (left, top, right, bottom) and resize back to (W, H): mfs.py:1111-1157."""
-    _need(frames, torch.uint8, 'frames')
+    """Crop to the inclusive (left, top, right, bottom) and resize back to (W, H): mfs.py:1111-1157.  frames: uint8 or uint16 (uint16:
+    cv2.resize's float path, mf_crop_resize_u16c3); the output has the input's dtype."""
+    dtype = _need_frames(frames, 'frames')
     n, H, W, ch = frames.shape
     if ch != 3:
         raise ValueError('frames must be (n, H, W, 3)')
     left, top, right, bottom = (int(v) for v in bounds)
     if out is None:
         out = torch.empty_like(frames)
-    _need(out, torch.uint8, 'out')
+    _need(out, dtype, 'out')
     work = torch.empty(_lib_.mf_crop_resize_workspace_bytes(W, H), dtype=torch.uint8, device=frames.device)
-    _lib.check(_lib_.mf_crop_resize_u8c3(_ptr(frames), _ptr(out), n, W, H, left, top, right, bottom, _ptr(work), _stream()))
+    fn = _lib_.mf_crop_resize_u16c3 if dtype == torch.uint16 else _lib_.mf_crop_resize_u8c3
+    _lib.check(fn(_ptr(frames), _ptr(out), n, W, H, left, top, right, bottom, _ptr(work), _stream()))
     return out
 
 

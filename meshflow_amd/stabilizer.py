@@ -662,8 +662,8 @@ class MeshFlowStabilizer:
     def stabilize_resident(self, d_frames, d_disp, homographies, adaptive_weights_definition=ADAPTIVE_WEIGHTS_DEFINITION_ORIGINAL,
                            out=None, frame_range=None, inputs_ready=None, check=True, collective=False, warp_events=None,
                            jacobi_events=None):
-        """mfs.py:150-158 for a clip whose frames (n, H, W, 3) uint8 and vertex displacements (F, R+1, C+1, 2) float64 are RESIDENT in
-        HBM: Jacobi sweep -> cell tables -> warp + crop rectangle, nothing leaves the device, one call per clip, NO synchronisation:
+        """mfs.py:150-158 for a clip whose frames (n, H, W, 3) uint8 or uint16 and vertex displacements (F, R+1, C+1, 2) float64 are
+        RESIDENT in HBM (uint16 frames: cv2.remap's 16U arithmetic, `ops.warp`; the sweep, tables and rectangle are the uint8 call's): Jacobi sweep -> cell tables -> warp + crop rectangle, nothing leaves the device, one call per clip, NO synchronisation:
         calls issued back to back pipeline by themselves (the sweep runs on this object's prep stream, the next clip's beside this
         clip's cell table + plan; see `resident_chunks` for the other arrangement).
         frame_range = (lo, hi): d_frames holds frames lo..hi-1 of the clip (a frame-range shard; the sweep still covers all F);
