@@ -163,6 +163,22 @@ int mf_warp_clip_u16c3(const uint16_t* d_frames, uint16_t* d_out, const double* 
                        int R, int C, const uint16_t border_bgr[3], void* d_table, int32_t* d_crop, int32_t* d_bounds, int32_t* d_status,
                        int chunks, void* prep_stream, void* stream);
 
+/* ---- the same warp for single-channel uint8 frames (mfs.py:942, 1063-1069: the reference reads shape[:2] only and hands a grey frame
+ * to cv2.remap with borderValue = color_outside_image_area_bgr, of which a 1-channel image uses the first component) ----
+ * d_frames, d_out: [n][H][W] uint8, any alignment (a 4-byte aligned clip gets the staged taps).  cv2.remap's 8-bit path works per
+ * channel, so the output is byte for byte channel 0 of mf_warp_u8c3 on the frames repeated three times with border (b, b, b); the
+ * ownership, coordinates, crop flags and clip rectangle are the uint8 BGR call's on the same table (d_crop / d_bounds identical).
+ * border: the border byte (saturate_cast<uchar>(borderValue[0])).  Limits: 2 <= W, H <= 32,767, R, C <= 64.  mf_warp_clip_u8c1 is
+ * mf_warp_clip_u8c3 (mfs.py:909-1108) with the same `chunks` / `prep_stream` semantics; it refuses what its warp would refuse before
+ * the cell table is launched.  Null pointers, d_frames == d_out and bad sizes return MF_ERR_INVALID_ARG before anything is launched. */
+int mf_warp_u8c1(const uint8_t* d_frames, uint8_t* d_out, const void* d_table, int n, int W, int H,
+                 int R, int C, uint8_t border, int32_t* d_crop, void* stream);
+int mf_warp_bounds_u8c1(const uint8_t* d_frames, uint8_t* d_out, const void* d_table, int n, int W, int H,
+                        int R, int C, uint8_t border, int32_t* d_crop, int32_t* d_bounds, void* stream);
+int mf_warp_clip_u8c1(const uint8_t* d_frames, uint8_t* d_out, const double* d_unstab, const double* d_stab, int n, int W, int H,
+                      int R, int C, uint8_t border, void* d_table, int32_t* d_crop, int32_t* d_bounds, int32_t* d_status,
+                      int chunks, void* prep_stream, void* stream);
+
 /* Clip-level crop bounds (mfs.py:1103-1106): {max left, max top, min right, min bottom} over n frames.
  * d_bounds: [4] int32. */
 int mf_crop_reduce(const int32_t* d_crop, int n, int W, int H, int32_t* d_bounds, void* stream);
@@ -181,6 +197,11 @@ int mf_crop_resize_u8c3(const uint8_t* d_frames, uint8_t* d_out, int n, int W, i
  * rounded half to even.  The same workspace size; the same refusals. */
 int mf_crop_resize_u16c3(const uint16_t* d_frames, uint16_t* d_out, int n, int W, int H, int left, int top, int right,
                          int bottom, void* d_work, void* stream);
+/* The same for single-channel uint8 frames [n][H][W] (mfs.py:1129, 1150-1155: cv2.resize of a 2-D frame): output = channel 0 of
+ * mf_crop_resize_u8c3 on the frames repeated three times (the same tables, the same workspace size).  1 <= W, H <= 32,767; the same
+ * refusals. */
+int mf_crop_resize_u8c1(const uint8_t* d_frames, uint8_t* d_out, int n, int W, int H, int left, int top, int right,
+                        int bottom, void* d_work, void* stream);
 
 /* ---- the row before the path: vertex-motion accumulation (mfs.py:236-452 from the matched features on) ----
  * Replaces the Python loops of _get_vertex_nearby_feature_residual_velocities (mfs.py:365-452), the medians, global
@@ -271,6 +292,17 @@ int mf_warp_crop_u8c3_host_frames(const uint8_t* const* frames, uint8_t* const* 
  * ring of chunk buffers and copy threads as the warp wrappers (upload, resize, download of the chunks all overlap).  An empty or
  * out-of-frame rectangle is MF_ERR_INVALID_ARG before any output byte is written. */
 int mf_crop_resize_u8c3_host_frames(const uint8_t* const* frames, uint8_t* const* cropped, int n, int W, int H, int left, int top,
+                                    int right, int bottom, float* kernel_ms);
+/* The three host calls for single-channel uint8 frames (mfs.py:909-1108 and 1111-1157 on 2-D frames, mfs.py:942, 1129): frames[i] /
+ * out[i] / cropped[i] point to H*W bytes each; the border byte as in mf_warp_u8c1.  The same ring: chunks are sized by bytes (~8 frames of
+ * 1080p grey per chunk), the same up-front crop scan, overlap refusal and degenerate-mesh refusal before any output byte.  The frames and
+ * crop values are those of mf_warp_u8c1 / mf_crop_resize_u8c1.  Limits: 2 <= W, H <= 32,767 (1 for the resize alone), R, C <= 64. */
+int mf_warp_u8c1_host_frames(const uint8_t* const* frames, uint8_t* const* out, const double* unstab, const double* stab,
+                             int n, int W, int H, int R, int C, uint8_t border, int32_t* crop /* [n][4] */, float* kernel_ms);
+int mf_warp_crop_u8c1_host_frames(const uint8_t* const* frames, uint8_t* const* out /* may be NULL */, uint8_t* const* cropped,
+                                  const double* unstab, const double* stab, int n, int W, int H, int R, int C,
+                                  uint8_t border, int32_t* crop /* [n][4] */, int32_t bounds[4], float* kernel_ms);
+int mf_crop_resize_u8c1_host_frames(const uint8_t* const* frames, uint8_t* const* cropped, int n, int W, int H, int left, int top,
                                     int right, int bottom, float* kernel_ms);
 int mf_host_cache_release(void);
 

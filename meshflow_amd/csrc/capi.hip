@@ -128,6 +128,16 @@ int mf_warp_u16c3(const uint16_t* d_frames, uint16_t* d_out, const void* d_table
     return launch_warp_u16(d_frames, d_out, tv, n, W, H, R, C, pack_border16(border_bgr), d_crop, (hipStream_t)stream);
 }
 
+int mf_warp_u8c1(const uint8_t* d_frames, uint8_t* d_out, const void* d_table, int n, int W, int H,
+                 int R, int C, uint8_t border, int32_t* d_crop, void* stream)
+{
+    if (!d_frames || !d_out || !d_table || !d_crop) { set_error("mf_warp_u8c1: null pointer"); return MF_ERR_INVALID_ARG; }
+    if (d_frames == d_out) { set_error("mf_warp_u8c1: d_frames and d_out alias"); return MF_ERR_INVALID_ARG; }
+    if (n <= 0 || R <= 0 || C <= 0) { set_error("mf_warp_u8c1: bad sizes"); return MF_ERR_INVALID_ARG; }
+    const TableView tv = table_view(const_cast<void*>(d_table), n, W, H, R, C);
+    return launch_warp_u8c1(d_frames, d_out, tv, n, W, H, R, C, border, d_crop, (hipStream_t)stream);
+}
+
 int mf_crop_scan_f64(const void* d_table, int n, int W, int H, int R, int C, int32_t* d_crop, void* stream)
 {
     if (!d_table || !d_crop) { set_error("mf_crop_scan_f64: null pointer"); return MF_ERR_INVALID_ARG; }
@@ -170,6 +180,17 @@ int mf_warp_bounds_u16c3(const uint16_t* d_frames, uint16_t* d_out, const void* 
     return launch_warp_u16(d_frames, d_out, tv, n, W, H, R, C, pack_border16(border_bgr), d_crop, (hipStream_t)stream);
 }
 
+int mf_warp_bounds_u8c1(const uint8_t* d_frames, uint8_t* d_out, const void* d_table, int n, int W, int H,
+                        int R, int C, uint8_t border, int32_t* d_crop, int32_t* d_bounds, void* stream)
+{
+    if (!d_frames || !d_out || !d_table || !d_crop || !d_bounds) { set_error("mf_warp_bounds_u8c1: null pointer"); return MF_ERR_INVALID_ARG; }
+    if (d_frames == d_out) { set_error("mf_warp_bounds_u8c1: d_frames and d_out alias"); return MF_ERR_INVALID_ARG; }
+    if (n <= 0 || R <= 0 || C <= 0) { set_error("mf_warp_bounds_u8c1: bad sizes"); return MF_ERR_INVALID_ARG; }
+    TableView tv = table_view(const_cast<void*>(d_table), n, W, H, R, C);
+    tv.bounds = d_bounds;
+    return launch_warp_u8c1(d_frames, d_out, tv, n, W, H, R, C, border, d_crop, (hipStream_t)stream);
+}
+
 int mf_crop_scan_bounds_f64(const void* d_table, int n, int W, int H, int R, int C, int32_t* d_crop, int32_t* d_bounds, void* stream)
 {
     if (!d_table || !d_crop || !d_bounds) { set_error("mf_crop_scan_bounds_f64: null pointer"); return MF_ERR_INVALID_ARG; }
@@ -204,6 +225,14 @@ int mf_crop_resize_u16c3(const uint16_t* d_frames, uint16_t* d_out, int n, int W
     if (!d_frames || !d_out || !d_work) { set_error("mf_crop_resize_u16c3: null pointer"); return MF_ERR_INVALID_ARG; }
     if (d_frames == d_out) { set_error("mf_crop_resize_u16c3: d_frames and d_out alias"); return MF_ERR_INVALID_ARG; }
     return launch_crop_resize_u16(d_frames, d_out, n, W, H, left, top, right, bottom, d_work, (hipStream_t)stream);
+}
+
+int mf_crop_resize_u8c1(const uint8_t* d_frames, uint8_t* d_out, int n, int W, int H, int left, int top, int right,
+                        int bottom, void* d_work, void* stream)
+{
+    if (!d_frames || !d_out || !d_work) { set_error("mf_crop_resize_u8c1: null pointer"); return MF_ERR_INVALID_ARG; }
+    if (d_frames == d_out) { set_error("mf_crop_resize_u8c1: d_frames and d_out alias"); return MF_ERR_INVALID_ARG; }
+    return launch_crop_resize_u8c1(d_frames, d_out, n, W, H, left, top, right, bottom, d_work, (hipStream_t)stream);
 }
 
 size_t mf_vertex_motion_workspace_bytes(int total_features, int max_per_pair, int P, int R, int C)

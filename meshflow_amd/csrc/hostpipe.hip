@@ -188,6 +188,7 @@ struct PipeJob {
     const uint8_t* const* frames; uint8_t* const* out; uint8_t* const* cropped;
     const double* unstab; const double* stab;
     int n, W, H, R, C;
+    int channels;                                    // 3: BGR (launch_warp / launch_crop_resize), 1: grey (the u8c1 launches, border & 0xFF)
     uint32_t border;
     int32_t* crop; int32_t* bounds; float* kernel_ms;
     bool warp;
@@ -207,7 +208,7 @@ int run_host_pipeline(PipeJob job)
     if (dev < 0 || dev >= PIPE_MAX_DEVICES) { set_error("%s: device %d out of range", job.name, dev); return MF_ERR_INVALID_ARG; }
     PipeCache& pc = g_pipe[dev];
     std::lock_guard<std::mutex> cache_guard(pc.lock);
-    const size_t fb = (size_t)W * H * 3;
+    const size_t fb = (size_t)W * H * (size_t)job.channels;           // (chunks are sized by bytes: ~3 x the frames per chunk for grey)
     if ((out && ranges_overlap(frames, out, n, fb)) || (cropped && ranges_overlap(frames, cropped, n, fb)) ||
         (out && cropped && ranges_overlap(out, cropped, n, fb))) {
         set_error("%s: input and output frames overlap in memory (in-place operation is not supported)", job.name);
@@ -411,7 +412,9 @@ int run_host_pipeline(PipeJob job)
         if (job.warp) {
             const TableView tv = table_view(pc.table.p, m, W, H, R, C);
             rc = launch_cell_table(d_unstab + v2 * i0, d_stab + v2 * i0, m, W, H, R, C, tv, d_crop + 4 * (size_t)i0, (int32_t*)pc.status.p, pc.compute);
-            if (rc == MF_OK) rc = launch_warp(slot_in(k), slot_out(k), tv, m, W, H, R, C, border, d_crop + 4 * (size_t)i0, pc.compute);
+            if (rc == MF_OK)
+                rc = job.channels == 1 ? launch_warp_u8c1(slot_in(k), slot_out(k), tv, m, W, H, R, C, (uint8_t)border, d_crop + 4 * (size_t)i0, pc.compute)
+                                       : launch_warp(slot_in(k), slot_out(k), tv, m, W, H, R, C, border, d_crop + 4 * (size_t)i0, pc.compute);
             if (rc != MF_OK) { sh.fail(hipErrorUnknown, "kernel launch"); break; }
             if (out) {
                 e = hipEventRecord(warp_done[k], pc.compute);
@@ -420,8 +423,9 @@ int run_host_pipeline(PipeJob job)
             }
         }
         if (cropped) {                                     // _crop_frames (mfs.py:1111-1157) of this chunk, its source still in the caches
-            rc = job.warp ? launch_crop_resize(slot_out(k), slot_in(k), m, W, H, rect[0], rect[1], rect[2], rect[3], pc.work.p, pc.compute)
-                          : launch_crop_resize(slot_in(k), slot_out(k), m, W, H, rect[0], rect[1], rect[2], rect[3], pc.work.p, pc.compute);
+            const auto resize = job.channels == 1 ? launch_crop_resize_u8c1 : launch_crop_resize;
+            rc = job.warp ? resize(slot_out(k), slot_in(k), m, W, H, rect[0], rect[1], rect[2], rect[3], pc.work.p, pc.compute)
+                          : resize(slot_in(k), slot_out(k), m, W, H, rect[0], rect[1], rect[2], rect[3], pc.work.p, pc.compute);
             if (rc != MF_OK) { sh.fail(hipErrorUnknown, "kernel launch"); break; }
             e = hipEventRecord(resize_done[k], pc.compute);
             if (e != hipSuccess) { sh.fail(e, "hipEventRecord"); break; }
@@ -469,16 +473,19 @@ int run_host_pipeline(PipeJob job)
 }
 
 int warp_host_frames(const uint8_t* const* frames, uint8_t* const* out, uint8_t* const* cropped, const double* unstab, const double* stab,
-                     int n, int W, int H, int R, int C, const uint8_t border_bgr[3], int32_t* crop, int32_t* bounds, float* kernel_ms)
+                     int n, int W, int H, int R, int C, const uint8_t border_bgr[3], int32_t* crop, int32_t* bounds, float* kernel_ms,
+                     int channels = 3)
 {
     PipeJob job{};
     job.frames = frames; job.out = out; job.cropped = cropped; job.unstab = unstab; job.stab = stab;
     job.n = n; job.W = W; job.H = H; job.R = R; job.C = C;
-    job.border = (uint32_t)border_bgr[0] | ((uint32_t)border_bgr[1] << 8) | ((uint32_t)border_bgr[2] << 16);
+    job.channels = channels;
+    job.border = channels == 1 ? (uint32_t)border_bgr[0] : (uint32_t)border_bgr[0] | ((uint32_t)border_bgr[1] << 8) | ((uint32_t)border_bgr[2] << 16);
     job.crop = crop; job.bounds = bounds; job.kernel_ms = kernel_ms;
     job.warp = true;
     job.rect[0] = 0; job.rect[1] = 0; job.rect[2] = W - 1; job.rect[3] = H - 1;
-    job.name = cropped ? "mf_warp_crop_u8c3_host_frames" : "mf_warp_u8c3_host";
+    if (channels == 1) job.name = cropped ? "mf_warp_crop_u8c1_host_frames" : "mf_warp_u8c1_host_frames";
+    else job.name = cropped ? "mf_warp_crop_u8c3_host_frames" : "mf_warp_u8c3_host";
     return run_host_pipeline(job);
 }
 
@@ -528,26 +535,58 @@ int mf_warp_u8c3_host(const uint8_t* frames, uint8_t* out, const double* unstab,
     return warp_host_frames(in.data(), outp.data(), nullptr, unstab, stab, n, W, H, R, C, border_bgr, crop, nullptr, kernel_ms);
 }
 
-int mf_crop_resize_u8c3_host_frames(const uint8_t* const* frames, uint8_t* const* cropped, int n, int W, int H, int left, int top,
-                                    int right, int bottom, float* kernel_ms)
+static int crop_resize_host(const char* name, int channels, const uint8_t* const* frames, uint8_t* const* cropped, int n, int W, int H,
+                            int left, int top, int right, int bottom, float* kernel_ms)
 {
-    if (!frames || !cropped) { set_error("mf_crop_resize_u8c3_host_frames: null pointer"); return MF_ERR_INVALID_ARG; }
-    if (n <= 0 || W < 1 || H < 1 || W > 32767 || H > 32767) { set_error("mf_crop_resize_u8c3_host_frames: unsupported shape n=%d W=%d H=%d", n, W, H); return MF_ERR_INVALID_ARG; }
+    if (!frames || !cropped) { set_error("%s: null pointer", name); return MF_ERR_INVALID_ARG; }
+    if (n <= 0 || W < 1 || H < 1 || W > 32767 || H > 32767) { set_error("%s: unsupported shape n=%d W=%d H=%d", name, n, W, H); return MF_ERR_INVALID_ARG; }
     if (left < 0 || top < 0 || right >= W || bottom >= H || right < left || bottom < top) {        // before any output page is touched
-        set_error("mf_crop_resize_u8c3_host_frames: empty or out-of-frame crop rectangle (%d, %d, %d, %d) for %dx%d (cv2.resize would "
-                  "fail on an empty source)", left, top, right, bottom, W, H);
+        set_error("%s: empty or out-of-frame crop rectangle (%d, %d, %d, %d) for %dx%d (cv2.resize would "
+                  "fail on an empty source)", name, left, top, right, bottom, W, H);
         return MF_ERR_INVALID_ARG;
     }
     for (int i = 0; i < n; ++i)
-        if (!frames[i] || !cropped[i]) { set_error("mf_crop_resize_u8c3_host_frames: null frame pointer %d", i); return MF_ERR_INVALID_ARG; }
+        if (!frames[i] || !cropped[i]) { set_error("%s: null frame pointer %d", name, i); return MF_ERR_INVALID_ARG; }
     PipeJob job{};
     job.frames = frames; job.cropped = cropped;
     job.n = n; job.W = W; job.H = H; job.R = 1; job.C = 1;
+    job.channels = channels;
     job.kernel_ms = kernel_ms;
     job.warp = false;
     job.rect[0] = left; job.rect[1] = top; job.rect[2] = right; job.rect[3] = bottom;
-    job.name = "mf_crop_resize_u8c3_host_frames";
+    job.name = name;
     return run_host_pipeline(job);
+}
+
+int mf_crop_resize_u8c3_host_frames(const uint8_t* const* frames, uint8_t* const* cropped, int n, int W, int H, int left, int top,
+                                    int right, int bottom, float* kernel_ms)
+{
+    return crop_resize_host("mf_crop_resize_u8c3_host_frames", 3, frames, cropped, n, W, H, left, top, right, bottom, kernel_ms);
+}
+
+int mf_warp_u8c1_host_frames(const uint8_t* const* frames, uint8_t* const* out, const double* unstab, const double* stab, int n,
+                             int W, int H, int R, int C, uint8_t border, int32_t* crop, float* kernel_ms)
+{
+    if (!out) { set_error("mf_warp_u8c1_host_frames: null pointer"); return MF_ERR_INVALID_ARG; }
+    const uint8_t b[3] = { border, 0, 0 };
+    if (const int rc = check_host_args("mf_warp_u8c1_host_frames", frames, out, nullptr, unstab, stab, n, W, H, R, C, b, crop)) return rc;
+    return warp_host_frames(frames, out, nullptr, unstab, stab, n, W, H, R, C, b, crop, nullptr, kernel_ms, 1);
+}
+
+int mf_warp_crop_u8c1_host_frames(const uint8_t* const* frames, uint8_t* const* out, uint8_t* const* cropped, const double* unstab,
+                                  const double* stab, int n, int W, int H, int R, int C, uint8_t border, int32_t* crop,
+                                  int32_t bounds[4], float* kernel_ms)
+{
+    if (!cropped || !bounds) { set_error("mf_warp_crop_u8c1_host_frames: null pointer"); return MF_ERR_INVALID_ARG; }
+    const uint8_t b[3] = { border, 0, 0 };
+    if (const int rc = check_host_args("mf_warp_crop_u8c1_host_frames", frames, out, cropped, unstab, stab, n, W, H, R, C, b, crop)) return rc;
+    return warp_host_frames(frames, out, cropped, unstab, stab, n, W, H, R, C, b, crop, bounds, kernel_ms, 1);
+}
+
+int mf_crop_resize_u8c1_host_frames(const uint8_t* const* frames, uint8_t* const* cropped, int n, int W, int H, int left, int top,
+                                    int right, int bottom, float* kernel_ms)
+{
+    return crop_resize_host("mf_crop_resize_u8c1_host_frames", 1, frames, cropped, n, W, H, left, top, right, bottom, kernel_ms);
 }
 
 int mf_host_cache_release(void)

@@ -248,6 +248,9 @@ int launch_crop_scan(const TableView& tv, int n, int W, int H, int R, int C, int
 // (uint16 frames: warp.hip's warp16_footprint; border16 = B | G << 16 | R << 32)
 int launch_warp_u16(const uint16_t* frames, uint16_t* out, const TableView& tv, int n, int W, int H, int R, int C,
                     uint64_t border16, int32_t* crop, hipStream_t st);
+// (single-channel uint8 frames: warp.hip's warp8c1_footprint; one border byte)
+int launch_warp_u8c1(const uint8_t* frames, uint8_t* out, const TableView& tv, int n, int W, int H, int R, int C,
+                     uint8_t border, int32_t* crop, hipStream_t st);
 int check_d16_zero_fill(hipStream_t st);          // warp.hip: one-time device check the byte-tap kernels rely on
 int launch_selftest_recip(unsigned long long n, unsigned long long seed, unsigned long long* d_mismatches, hipStream_t st);
 int launch_selftest_fast64(unsigned long long n, unsigned long long seed, unsigned long long* d_counters, hipStream_t st, unsigned long long* d_margin = nullptr);
@@ -256,6 +259,12 @@ int launch_crop_resize(const uint8_t* frames, uint8_t* out, int n, int W, int H,
                        int bottom, void* work, hipStream_t st);
 int launch_crop_resize_u16(const uint16_t* frames, uint16_t* out, int n, int W, int H, int left, int top, int right,
                            int bottom, void* work, hipStream_t st);      // resize16.hip: the same workspace
+int launch_crop_resize_u8c1(const uint8_t* frames, uint8_t* out, int n, int W, int H, int left, int top, int right,
+                            int bottom, void* work, hipStream_t st);     // resize_c1.hip: the same tables and workspace
+// resize.hip: the checks of every crop-resize call, then resize_tables_kernel's tables for the rectangle in `work` (W x-entries, then H
+// y-entries; x: ofs = sx, w = 16 a0 | 16 a1 << 16 (pre-scaled, see resize_kernel);  y: ofs = sy0 | sy1 << 16, w = b0 | b1 << 16)
+struct ResizeTab { int32_t ofs; uint32_t w; };
+int launch_resize_tables(const char* name, int n, int W, int H, int left, int top, int right, int bottom, void* work, hipStream_t st);
 size_t vertex_motion_workspace_bytes(int total_features, int max_per_pair, int P, int R, int C);
 int launch_vertex_motion(const double* early, const double* late, const int32_t* offsets, const double* hom, int P,
                          int total_features, int max_per_pair, int W, int H, int R, int C, int ell_rows, int ell_cols,

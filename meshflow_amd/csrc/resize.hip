@@ -17,9 +17,6 @@
 
 namespace mf {
 
-// x: ofs = sx, w = 16 a0 | 16 a1 << 16 (pre-scaled, see resize_kernel);  y: ofs = sy0 | sy1 << 16, w = b0 | b1 << 16
-struct ResizeTab { int32_t ofs; uint32_t w; };
-
 __device__ __forceinline__ int cv_round_pos(float v) { return (int)rintf(v); }
 
 __global__ __launch_bounds__(256) void resize_tables_kernel(int cw, int ch, int W, int H, double scale_x, double scale_y,
@@ -295,17 +292,15 @@ __global__ __launch_bounds__(64 * kWaves) void resize_kernel(const uint8_t* __re
 
 size_t crop_resize_workspace_bytes(int W, int H) { return (size_t)(W + H) * sizeof(ResizeTab); }
 
-int launch_crop_resize(const uint8_t* frames, uint8_t* out, int n, int W, int H, int left, int top, int right, int bottom,
-                       void* work, hipStream_t st)
+int launch_resize_tables(const char* name, int n, int W, int H, int left, int top, int right, int bottom, void* work, hipStream_t st)
 {
-    if (const int rc = check_d16_zero_fill(st)) return rc;
     if (n <= 0 || W < 1 || H < 1 || W > 32767 || H > 32767) {           // (any number of frames that make_tile_order can count: 2^31 tiles)
-        set_error("mf_crop_resize_u8c3: unsupported shape n=%d W=%d H=%d", n, W, H);
+        set_error("%s: unsupported shape n=%d W=%d H=%d", name, n, W, H);
         return MF_ERR_INVALID_ARG;
     }
     if (left < 0 || top < 0 || right >= W || bottom >= H || right < left || bottom < top) {
-        set_error("mf_crop_resize_u8c3: empty or out-of-frame crop rectangle (%d, %d, %d, %d) for %dx%d (cv2.resize would "
-                  "fail on an empty source)", left, top, right, bottom, W, H);
+        set_error("%s: empty or out-of-frame crop rectangle (%d, %d, %d, %d) for %dx%d (cv2.resize would "
+                  "fail on an empty source)", name, left, top, right, bottom, W, H);
         return MF_ERR_INVALID_ARG;
     }
     const int cw = right - left + 1, ch = bottom - top + 1;
@@ -314,8 +309,17 @@ int launch_crop_resize(const uint8_t* frames, uint8_t* out, int n, int W, int H,
     ResizeTab* ytab = xtab + W;
     const int m = W > H ? W : H;
     hipLaunchKernelGGL(resize_tables_kernel, dim3((m + 255) / 256), dim3(256), 0, st, cw, ch, W, H, scale_x, scale_y, xtab, ytab);
-    int rc = hip_fail(hipGetLastError(), "resize_tables_kernel launch");
-    if (rc != MF_OK) return rc;
+    return hip_fail(hipGetLastError(), "resize_tables_kernel launch");
+}
+
+int launch_crop_resize(const uint8_t* frames, uint8_t* out, int n, int W, int H, int left, int top, int right, int bottom,
+                       void* work, hipStream_t st)
+{
+    if (const int rc = check_d16_zero_fill(st)) return rc;
+    if (const int rc = launch_resize_tables("mf_crop_resize_u8c3", n, W, H, left, top, right, bottom, work, st)) return rc;
+    const int cw = right - left + 1;
+    const ResizeTab* xtab = (const ResizeTab*)work;
+    const ResizeTab* ytab = xtab + W;
     TileOrder order;
     if (!make_tile_order((W + 255) / 256, (H + kWaves * kRows - 1) / (kWaves * kRows), n, order)) {
         set_error("mf_crop_resize_u8c3: too many tiles");

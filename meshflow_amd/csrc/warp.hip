@@ -747,6 +747,133 @@ __device__ __forceinline__ void remap_store_u16(const float (&u)[4], const float
     }
 }
 
+// ---- single-channel uint8 frames: cv2.remap of CV_8UC1 -- the 8-bit fixed-point path of every channel of CV_8UC3, on one channel ------
+// out = (sum w_k s_k + 2^14) >> 15 with w = 32 (32 - fx or fx)(32 - fy or fy) (BilinearTab_i) = (t0 (32 - fy) + t1 fy + 512) >> 10, t0 / t1
+// the horizontal lerps of the two tap rows.
+__device__ __forceinline__ uint32_t blend_c1(uint32_t s00, uint32_t s01, uint32_t s10, uint32_t s11, uint32_t sx, uint32_t sy)
+{
+    const uint32_t fx = sx & 31u, fy = sy & 31u;
+    const uint32_t t0 = umad24(s01, fx, __umul24(s00, 32u - fx)), t1 = umad24(s11, fx, __umul24(s10, 32u - fx));
+    return (umad24(t1, fy, __umul24(t0, 32u - fy)) + 512u) >> 10;
+}
+
+// The grey window: the plan's STAGED window (cut for 3-byte pixels) re-cut for 1-byte pixels.  The region words give the window's first
+// row sy0 and byte column bs = 3 sx0 & ~3 only as origin = P sy0 + bs and src = 3 W sy0 + bs (P = 160, or 112 for COMPACT), so sy0 =
+// (src - origin) / (3 W - P) (exact in float32: the quotient is below 2^15 and the error of the two roundings below 1e-2) and the first grey
+// column is bs / 3 <= sx0.  The window copies MF_C1_PITCH bytes of each row from column gx = min(bs / 3 & ~3, W - MF_C1_PITCH): every tap
+// the plan certifies (columns sx0 .. sx0 + 53 at most: MF_STAGE_COLS + 2, or clamped to W - 1) lies in it, and the copy never leaves the
+// frame (the plan stages only frames with W % 4 == 0, and the grey window only frames of at least MF_C1_PITCH columns).
+constexpr int MF_C1_PITCH = 80;             // 5 chunks of 16 bytes: rows 0..7 of a footprint start 20 banks apart (0, 20, 8, 28, ...)
+struct GreyWindow { bool on; uint32_t row0, col0; };
+
+// Footprint-level tail of the GREY instantiation of footprint_body: the lane's four pixels at source coordinates (u, v) -- taps, blend,
+// crop flags, store.  Deep-interior footprints take their taps from the grey window in LDS when the plan staged one (`win.on`), else four
+// byte loads per pixel from the frame; the others take every tap at its position clamped into the frame and replace outside taps by
+// `border` (byte loads only: nothing outside the frame is ever read).  All frame offsets are 64-bit.
+__device__ __forceinline__ void remap_store_u8c1(const float (&u)[4], const float (&v)[4], uint32_t f, int x0, int y, bool active, int W, int H,
+                                                 const uint8_t* __restrict__ frames, uint8_t* __restrict__ out, uint32_t border,
+                                                 int32_t* __restrict__ crop, int32_t* __restrict__ clip, const GreyWindow& win,
+                                                 const uint8_t* s_win)
+{
+    const uint64_t frame_px = (uint64_t)((uint32_t)W * (uint32_t)H);
+    const uint8_t* __restrict__ src = frames + (uint64_t)f * frame_px;
+    uint8_t* __restrict__ dst = out + (uint64_t)f * frame_px;
+    const int lane = threadIdx.x;
+    uint32_t bx[4], by[4];
+    fixed_point(u, v, bx, by);
+    uint32_t dxm = 0, dym = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        dxm = max(dxm, bx[j] - (0x4B400000u + 64u));
+        dym = max(dym, by[j] - (0x4B400000u + 64u));
+    }
+    // deep interior (as in footprint_body): 2 <= ix <= W-3 and 2 <= iy <= H-3 for all four pixels
+    const bool deep = W >= 5 && H >= 5 && dxm <= (uint32_t)(32 * (W - 3) + 31 - 64) && dym <= (uint32_t)(32 * (H - 3) + 31 - 64);
+    const bool fast = __ballot(active && !deep) == 0;
+    uint32_t o[4];                                                      // the lane's 4 output bytes
+    int c_left = 0, c_top = 0, c_right = W - 1, c_bottom = H - 1;
+    if (win.on) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // the grey window has landed in LDS
+    if (active) {
+        if (fast && win.on) {
+            const lds_bytes_t w = lds_ptr(s_win);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const uint32_t ix = __builtin_amdgcn_ubfe(bx[j], 5, 17), iy = __builtin_amdgcn_ubfe(by[j], 5, 17);
+                const uint32_t a = umad24(iy - win.row0, (uint32_t)MF_C1_PITCH, ix - win.col0);
+                o[j] = blend_c1(w[a], w[a + 1], w[a + MF_C1_PITCH], w[a + MF_C1_PITCH + 1], bx[j], by[j]);
+            }
+        } else if (fast) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const uint32_t ix = __builtin_amdgcn_ubfe(bx[j], 5, 17), iy = __builtin_amdgcn_ubfe(by[j], 5, 17);
+                const uint8_t* __restrict__ p = src + (uint64_t)(iy * (uint32_t)W + ix);
+                o[j] = blend_c1(p[0], p[1], p[W], p[W + 1], bx[j], by[j]);
+            }
+        } else {
+            // frame borders, uncovered pixels (at (W+1, H+1)), crop flags, out-of-range coordinates
+            const float fWm1 = (float)(W - 1), fHm1 = (float)(H - 1);
+            uint32_t spread = 0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                spread = max(spread, max(bx[j] - (0x4B400000u - 0x200000u), by[j] - (0x4B400000u - 0x200000u)));
+            const bool narrow = __ballot(spread >= 0x400000u) == 0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float uu = u[j], vv = v[j];
+                const int x = x0 + j;
+                if (x < W) {                                            // crop-boundary scan, mfs.py:1075-1098 (exact: Sterbenz)
+                    if (fabsf(uu) < 1.0f) c_left = max(c_left, x);
+                    if (fabsf(uu - fWm1) < 1.0f) c_right = min(c_right, x);
+                    if (fabsf(vv) < 1.0f) c_top = max(c_top, y);
+                    if (fabsf(vv - fHm1) < 1.0f) c_bottom = min(c_bottom, y);
+                }
+                const int sxx = narrow ? (int)(bx[j] - 0x4B400000u) : cv_round_f32(uu * 32.0f);
+                const int syy = narrow ? (int)(by[j] - 0x4B400000u) : cv_round_f32(vv * 32.0f);
+                const int ix = sxx >> 5, iy = syy >> 5;                 // (saturation to int16 cannot change any decision below)
+                // (a 2 x 2 footprint wholly outside needs no special case: four border taps with weights summing to 1024 give the border)
+                const bool in_x0 = (unsigned)ix < (unsigned)W, in_x1 = (unsigned)(ix + 1) < (unsigned)W;
+                const bool in_y0 = (unsigned)iy < (unsigned)H, in_y1 = (unsigned)(iy + 1) < (unsigned)H;
+                const uint32_t cx0 = (uint32_t)min(max(ix, 0), W - 1), cx1 = (uint32_t)min(max(ix + 1, 0), W - 1);
+                const uint32_t r0 = (uint32_t)min(max(iy, 0), H - 1) * (uint32_t)W, r1 = (uint32_t)min(max(iy + 1, 0), H - 1) * (uint32_t)W;
+                const uint32_t s00 = src[r0 + cx0], s01 = src[r0 + cx1], s10 = src[r1 + cx0], s11 = src[r1 + cx1];
+                o[j] = blend_c1(in_x0 && in_y0 ? s00 : border, in_x1 && in_y0 ? s01 : border, in_x0 && in_y1 ? s10 : border,
+                                in_x1 && in_y1 ? s11 : border, (uint32_t)sxx, (uint32_t)syy);
+            }
+        }
+    }
+    if (!fast) {
+        // crop bounds: wave reduction, then at most one atomic per bound and wavefront (per frame, mfs.py:1075-1098, and the clip-level
+        // rectangle, mfs.py:1103-1106)
+        const bool any = c_left != 0 || c_top != 0 || c_right != W - 1 || c_bottom != H - 1;
+        if (__ballot(any) != 0) {
+#pragma unroll
+            for (int off = 32; off >= 1; off >>= 1) {
+                c_left = max(c_left, __shfl_xor(c_left, off));
+                c_top = max(c_top, __shfl_xor(c_top, off));
+                c_right = min(c_right, __shfl_xor(c_right, off));
+                c_bottom = min(c_bottom, __shfl_xor(c_bottom, off));
+            }
+            if (lane == 0) {
+                if (c_left != 0) { atomicMax(&crop[4 * f + 0], c_left); atomicMax(&clip[0], c_left); }
+                if (c_top != 0) { atomicMax(&crop[4 * f + 1], c_top); atomicMax(&clip[1], c_top); }
+                if (c_right != W - 1) { atomicMin(&crop[4 * f + 2], c_right); atomicMin(&clip[2], c_right); }
+                if (c_bottom != H - 1) { atomicMin(&crop[4 * f + 3], c_bottom); atomicMin(&clip[3], c_bottom); }
+            }
+        }
+    }
+    if (active) {
+        uint8_t* __restrict__ d = dst + (uint32_t)y * (uint32_t)W + (uint32_t)x0;
+        if (x0 + 3 < W) {                                               // 4 bytes, dword-aligned when W % 4 == 0 (else an unaligned store)
+            const uint32_t w4 = o[0] | (o[1] << 8) | (o[2] << 16) | (o[3] << 24);
+            __builtin_memcpy(d, &w4, 4);
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (x0 + j < W) d[j] = (uint8_t)o[j];
+        }
+    }
+}
+
 // ---- EXPERIMENT builds only (tools/phase_profile.sh; nothing of this is in the product library) ------------------------------------
 // -DMF_EXP_SKIP=mask: TIMING-ONLY kernels in which the wavefronts of a path class return right after the plan test that selects
 // them (their output is garbage): 1 hot, 2 border, 4 pair, 8 multi, 16 everything else, 32 every wavefront right after the plan and
@@ -773,7 +900,10 @@ __device__ unsigned long long mf_exp_phase[8];
 // U16: the same ownership and coordinates for uint16 BGR frames (warp16_kernel): `frames` / `out` then point to uint16 samples, the border
 // colour is `border16` (B | G << 16 | R << 32) and the pixels go through remap_store_u16 at the end of the general path -- the plan's staged
 // windows are sized for 3-byte pixels, so the U16 instantiation has no staged path (STAGE_OK = false).
-template <bool STAGE_OK, bool SCAN, bool U16 = false>
+// GREY: the same for single-channel uint8 frames (warp8c1_footprint): `frames` / `out` hold W H bytes per frame, the border is the low byte
+// of `border`, and the pixels go through remap_store_u8c1.  GREY_STAGE: the clip is 4-byte aligned -- the plan's STAGED windows (not the
+// BORDER ones) are then re-cut for 1-byte pixels (GreyWindow) and copied to LDS at the start, like warp_kernel's.
+template <bool STAGE_OK, bool SCAN, bool U16 = false, bool GREY = false, bool GREY_STAGE = false>
 __device__ __forceinline__ void footprint_body(const uint32_t f, const uint32_t t, const FootPlan* __restrict__ plan, const FootRegion* __restrict__ regions,
                                                const WarpGeom& g, const uint8_t* __restrict__ frames,
                                                const double* __restrict__ records, uint8_t* __restrict__ out,
@@ -782,6 +912,8 @@ __device__ __forceinline__ void footprint_body(const uint32_t f, const uint32_t 
                                                uint64_t border16 = 0)
 {
     static_assert(!U16 || (!STAGE_OK && !SCAN), "the uint16 warp takes its taps from global memory");
+    static_assert(!GREY || (!STAGE_OK && !SCAN && !U16), "the grey warp stages its own window");
+    static_assert(!GREY_STAGE || GREY, "GREY_STAGE is a variant of the grey warp");
     // inverse homographies of the footprint's candidate cells: [entry][Hi0..Hi8, pad] (80-byte rows)
     __shared__ __attribute__((aligned(16))) double s_hi[1][9][10];                // row 8: the "no cell" matrix, see OWN_NONE
     // source region of the footprint: MF_STAGE_ROWS rows of MF_STAGE_PITCH bytes (+ slack for the third dword of the last tap)
@@ -892,6 +1024,27 @@ __device__ __forceinline__ void footprint_body(const uint32_t f, const uint32_t 
         __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gbase + o1), (__attribute__((address_space(3))) void*)(window + 1024), 16, 0, 0);
         }
     }
+    GreyWindow gwin{false, 0u, 0u};
+    if constexpr (GREY_STAGE) {
+        // the plan's window re-cut for 1-byte pixels (GreyWindow), issued before the coordinate work like warp_kernel's: lane i < 5 rows
+        // fetches chunk i (row i / 5, bytes 16 (i % 5) ..) to LDS byte 16 i
+        if ((rg & (MF_REGION_STAGED | MF_REGION_BORDER)) == MF_REGION_STAGED && W >= MF_C1_PITCH) {
+            const bool cmp = (rg & MF_REGION_COMPACT) != 0;
+            const uint32_t P = cmp ? (uint32_t)MF_COMPACT_PITCH : (uint32_t)MF_STAGE_PITCH, rows = cmp ? (uint32_t)MF_COMPACT_ROWS : (uint32_t)MF_STAGE_ROWS;
+            const uint32_t origin = rg & MF_REGION_ORIGIN_MASK, sbytes = src_dwords << 2;
+            const uint32_t sy0 = __builtin_amdgcn_readfirstlane((uint32_t)((float)(sbytes - origin) / (float)(3u * (uint32_t)W - P) + 0.5f));
+            const uint32_t bs = origin - P * sy0;
+            const uint32_t gx = min((bs / 3u) & ~3u, (uint32_t)W - (uint32_t)MF_C1_PITCH);
+            gwin.on = true; gwin.row0 = sy0; gwin.col0 = gx;
+            const uint8_t* __restrict__ gbase = frames + (uint64_t)f * (uint64_t)((uint32_t)W * (uint32_t)H) + (uint64_t)(sy0 * (uint32_t)W + gx);
+            if ((uint32_t)lane < 5u * rows) {
+                const uint32_t r = ((uint32_t)lane * 205u) >> 10;          // lane / 5 (lane < 64)
+                uint32_t o0 = umad24(r, (uint32_t)W, ((uint32_t)lane - 5u * r) << 4);
+                asm("" : "+v"(o0));
+                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gbase + o0), (__attribute__((address_space(3))) void*)lds_ptr(&s_src[0]), 16, 0, 0);
+            }
+        }
+    }
     // (a wavefront must not END with its global->LDS copy in flight: on this stack that is a GPU memory access fault -- tools/phase_variant_check.py --
     // so the timing-only returns below wait for it; `MF_EXP_RETURN` = that wait + return)
 #define MF_EXP_RETURN do { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); return; } while (0)
@@ -976,7 +1129,64 @@ __device__ __forceinline__ void footprint_body(const uint32_t f, const uint32_t 
         return;
     }
 
+    if constexpr (GREY_STAGE) {
+        if (gwin.on && (pv.x & (MF_PLAN_HOT << 16)) != 0) {
+            // the HOT footprints of the grey warp (one IN cell, certified denominator, deep, staged): the hot path's coordinates -- the cheap
+            // chain where the plan allows it (FAST64), else the trimmed-reciprocal one -- without the general path's ownership code
+            const crec_t rec = frec + (pv.x & 0xFFFu) * MF_CELL_DOUBLES;
+            float u[4], v[4];
+            if (!((pv.x >> 16) & MF_PLAN_FAST64) || !cell_coords_fast(rec, xs0, yy, u, v))
+                cell_coords<false>(rec, xs0, yy, x0, 0xFu, u, v, true);
+            remap_store_u8c1(u, v, f, x0, y, true, W, H, frames, out, border, crop, clip, gwin, &s_src[0]);
+            return;
+        }
+    }
     const cedge_t fedge = (cedge_t)(uintptr_t)(reinterpret_cast<const uint8_t*>(edges) + f * g.edge_frame_bytes);
+    if constexpr (GREY_STAGE) {
+        if (gwin.on && (pv.y & MF_PLAN_HOT) != 0) {
+            // the PAIR footprints of the grey warp (two cells, certified denominators, deep, staged): warp_kernel's per-pixel pair form --
+            // the later cell owns a pixel where its one mask edge passes (one fma), the other cell the rest, both matrices in LDS; a pixel
+            // inside the edge's float32 error band leaves the footprint to the general code
+            const uint32_t k0 = pv.x & 0xFFFu, k1 = (pv.x >> 16) & 0xFFFu;
+            if (lane < 20) {
+                uint32_t lo4 = (uint32_t)lane << 2;
+                asm("" : "+v"(lo4));
+                const uint8_t* __restrict__ g0 = (const uint8_t*)(uintptr_t)(frec + k0 * MF_CELL_DOUBLES + MF_CELL_OFF_HI);
+                const uint8_t* __restrict__ g1 = (const uint8_t*)(uintptr_t)(frec + k1 * MF_CELL_DOUBLES + MF_CELL_OFF_HI);
+                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(g0 + lo4),
+                                                 (__attribute__((address_space(3))) void*)lds_ptr(&s_hi[0][0][0]), 4, 0, 0);
+                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(g1 + lo4),
+                                                 (__attribute__((address_space(3))) void*)lds_ptr(&s_hi[0][1][0]), 4, 0, 0);
+            }
+            const cedge_t eb = fedge + k0 * MF_EDGE_FLOATS + 3u * (pv.z & 3u);
+            const float rb = __builtin_fmaf(eb[1], (float)y, eb[2]), xf0 = (float)x0;
+            uint32_t own[4];
+            float near = 1e30f;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float gb = __builtin_fmaf(eb[0], xf0 + (float)j, rb);
+                own[j] = gb > EDGE_BAND ? 0u : OWN_ROW;
+                near = fminf(near, fabsf(gb));
+            }
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");             // matrices (and the grey window) have landed in LDS
+            if (__ballot(!(near > EDGE_BAND)) == 0) {
+                float u[4], v[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const double* hp = reinterpret_cast<const double*>(reinterpret_cast<const uint8_t*>(&s_hi[0][0][0]) + own[j]);
+                    const double2 h01 = *reinterpret_cast<const double2*>(hp), h23 = *reinterpret_cast<const double2*>(hp + 2);
+                    const double2 h45 = *reinterpret_cast<const double2*>(hp + 4), h67 = *reinterpret_cast<const double2*>(hp + 6);
+                    const double h8 = hp[8];
+                    const double xs = xs0 + (double)j;
+                    const double iw = recip_unit_range((xs * h67.x + yy * h67.y) + h8);
+                    u[j] = (float)(((xs * h01.x + yy * h01.y) + h23.x) * iw);
+                    v[j] = (float)(((xs * h23.y + yy * h45.x) + h45.y) * iw);
+                }
+                remap_store_u8c1(u, v, f, x0, y, true, W, H, frames, out, border, crop, clip, gwin, &s_src[0]);
+                return;
+            }
+        }
+    }
 #ifndef MF_NO_BORDER
     if (STAGE_OK && !SCAN && ((pv.x >> 16) & (MF_PLAN_VALID | MF_PLAN_BORDER)) == MF_PLAN_BORDER) {
         // BORDER path (the ring of footprints along the frame border of a stabilised clip, and the odd footprint a single cell only partly
@@ -1542,6 +1752,10 @@ __device__ __forceinline__ void footprint_body(const uint32_t f, const uint32_t 
                             crop, clip);
             return;
         }
+        if constexpr (GREY) {
+            remap_store_u8c1(u, v, f, x0, y, active, W, H, frames, out, border, crop, clip, gwin, &s_src[0]);
+            return;
+        }
         // cv2.remap: 1/32-pixel fixed point (round half to even), bilinear gather, store.
         uint32_t bx[4], by[4];
         fixed_point(u, v, bx, by);
@@ -1703,6 +1917,33 @@ __device__ __forceinline__ void footprint_body(const uint32_t f, const uint32_t 
     }
 }
 
+// Launch constants of warp_kernel / crop_scan_kernel; returns the frames one launch may cover (the grid's y extent, and 32-bit byte
+// offsets into the plan -- 16 B per footprint -- and the records), 0 when a single frame is already too large.
+static uint32_t make_warp_geom(int W, int H, int R, int C, WarpGeom& g)
+{
+    const uint32_t nfx = (uint32_t)((W + FOOT_W - 1) / FOOT_W), nfy = (uint32_t)((H + FOOT_H - 1) / FOOT_H);
+    const FastDiv by_row = make_fast_div(nfx);
+    g.per_frame = nfx * nfy;
+    g.per_xcd = (g.per_frame + 7u) / 8u;
+    g.nfx = nfx;
+    g.div_m = by_row.m; g.div_s = by_row.s; g.div_pass = nfx == 1u ? 0xFFFFFFFFu : 0u;
+    g.frame_bytes = 3u * (uint32_t)W * (uint32_t)H;
+    g.row_bytes = 3u * (uint32_t)W;
+    g.rec_frame_bytes = (uint32_t)(R * C) * (uint32_t)(MF_CELL_DOUBLES * sizeof(double));
+    g.edge_frame_bytes = (uint32_t)(R * C) * (uint32_t)(MF_EDGE_FLOATS * sizeof(float));
+    // cell column under pixel x of the unwarped grid ~ floor(x C / (W - 1)) = mulhi(x, 2^32 C / (W - 1)) (a guess: the plan decides)
+    g.cell_mul_x = (uint32_t)std::min<uint64_t>(0xFFFFFFFFull, (((uint64_t)C) << 32) / (uint64_t)(W - 1));
+    g.cell_mul_y = (uint32_t)std::min<uint64_t>(0xFFFFFFFFull, (((uint64_t)R) << 32) / (uint64_t)(H - 1));
+    g.mesh_cols = (uint32_t)C;
+    g.cell_last = (uint32_t)(R * C - 1);
+    const uint64_t cap = 0xFFFFFFFFull;
+    uint64_t per_launch = 65535;
+    per_launch = per_launch < cap / (16ull * g.per_frame) ? per_launch : cap / (16ull * g.per_frame);
+    per_launch = per_launch < cap / g.rec_frame_bytes ? per_launch : cap / g.rec_frame_bytes;
+    return (uint32_t)per_launch;
+}
+
+#ifndef MF_WARP_BODY_ONLY          // (warp_c1.hip includes this file for footprint_body and its helpers alone)
 template <bool STAGE_OK>
 __global__ __launch_bounds__(64) MF_WARP_ATTR void warp_kernel(const FootPlan* __restrict__ plan, const FootRegion* __restrict__ regions,
                                                                WarpGeom g, const uint8_t* __restrict__ frames,
@@ -1933,32 +2174,6 @@ int check_d16_zero_fill(hipStream_t st)
     return MF_OK;
 }
 
-// Launch constants of warp_kernel / crop_scan_kernel; returns the frames one launch may cover (the grid's y extent, and 32-bit byte
-// offsets into the plan -- 16 B per footprint -- and the records), 0 when a single frame is already too large.
-static uint32_t make_warp_geom(int W, int H, int R, int C, WarpGeom& g)
-{
-    const uint32_t nfx = (uint32_t)((W + FOOT_W - 1) / FOOT_W), nfy = (uint32_t)((H + FOOT_H - 1) / FOOT_H);
-    const FastDiv by_row = make_fast_div(nfx);
-    g.per_frame = nfx * nfy;
-    g.per_xcd = (g.per_frame + 7u) / 8u;
-    g.nfx = nfx;
-    g.div_m = by_row.m; g.div_s = by_row.s; g.div_pass = nfx == 1u ? 0xFFFFFFFFu : 0u;
-    g.frame_bytes = 3u * (uint32_t)W * (uint32_t)H;
-    g.row_bytes = 3u * (uint32_t)W;
-    g.rec_frame_bytes = (uint32_t)(R * C) * (uint32_t)(MF_CELL_DOUBLES * sizeof(double));
-    g.edge_frame_bytes = (uint32_t)(R * C) * (uint32_t)(MF_EDGE_FLOATS * sizeof(float));
-    // cell column under pixel x of the unwarped grid ~ floor(x C / (W - 1)) = mulhi(x, 2^32 C / (W - 1)) (a guess: the plan decides)
-    g.cell_mul_x = (uint32_t)std::min<uint64_t>(0xFFFFFFFFull, (((uint64_t)C) << 32) / (uint64_t)(W - 1));
-    g.cell_mul_y = (uint32_t)std::min<uint64_t>(0xFFFFFFFFull, (((uint64_t)R) << 32) / (uint64_t)(H - 1));
-    g.mesh_cols = (uint32_t)C;
-    g.cell_last = (uint32_t)(R * C - 1);
-    const uint64_t cap = 0xFFFFFFFFull;
-    uint64_t per_launch = 65535;
-    per_launch = per_launch < cap / (16ull * g.per_frame) ? per_launch : cap / (16ull * g.per_frame);
-    per_launch = per_launch < cap / g.rec_frame_bytes ? per_launch : cap / g.rec_frame_bytes;
-    return (uint32_t)per_launch;
-}
-
 int launch_warp(const uint8_t* frames, uint8_t* out, const TableView& tv, int n, int W, int H, int R, int C,
                 uint32_t border, int32_t* crop, hipStream_t st)
 {
@@ -2081,5 +2296,6 @@ int launch_crop_reduce(const int32_t* crop, int n, int W, int H, int32_t* bounds
     return hip_fail(hipGetLastError(), "crop_reduce_kernel launch");
 }
 
+#endif  // MF_WARP_BODY_ONLY
 }  // namespace mf
 

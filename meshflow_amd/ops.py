@@ -41,6 +41,25 @@ def _need_frames(t, name):
     _need(t, torch.uint8, name)          # (raises: not a tensor, or another dtype)
 
 
+def _frame_shape(frames, dtype):
+    """(n, H, W, channels) of a frame stack: (n, H, W, 3) BGR of either pixel type, or (n, H, W) single-channel uint8 (channels 1).
+    Grey uint16 is refused naming its dtype; other shapes raise ValueError."""
+    if frames.dim() == 3:
+        if dtype != torch.uint8:
+            raise ValueError(f'single-channel frames must be uint8 (got {dtype}): (n, H, W) {dtype} frames are not supported')
+        n, H, W = frames.shape
+        return n, H, W, 1
+    if frames.dim() != 4 or frames.shape[3] != 3:
+        raise ValueError('frames must be (n, H, W, 3), or (n, H, W) uint8')
+    n, H, W, ch = frames.shape
+    return n, H, W, ch
+
+
+def _grey_border(border_bgr):
+    """The border byte of a single-channel warp: cv2.remap uses borderValue[0] for a 1-channel image, saturate_cast<uchar>."""
+    return ctypes.c_uint8(int(np.clip(round(float(border_bgr[0])), 0, 255)))
+
+
 def _border(border_bgr, dtype):
     """The border colour as the C call takes it: clamp(round(v), 0, 255) for uint8, clamp(round(v), 0, 65535) for uint16 -- the value
     itself, not scaled to 16 bits (cv2.remap's saturate_cast of borderValue)."""
@@ -142,16 +161,29 @@ def cell_table(unstab, stab, W, H, R, C, table=None, reset_status=True, bounds=N
 
 def warp(frames, table, border_bgr=(0, 0, 255), out=None, bounds=None):
     """Mesh warp + crop scan of n frames (mfs.py:1000-1100).  frames: (n, H, W, 3) uint8 or uint16 device tensor (uint16: cv2.remap's
-    16U arithmetic, include/meshflow_hip.h mf_warp_u16c3; the crop values are those of the uint8 warp of the same table).
+    16U arithmetic, include/meshflow_hip.h mf_warp_u16c3; the crop values are those of the uint8 warp of the same table), or (n, H, W)
+    uint8 single-channel frames (mf_warp_u8c1: channel 0 of the BGR warp of the frames repeated, border byte = border_bgr[0]).
     Returns the stabilized frames (the input's dtype); per-frame crop values accumulate in table.crop, the clip-level rectangle in
     `bounds` (the tensor `cell_table` was given) or, without one, in table.clip_bounds."""
     dtype = _need_frames(frames, 'frames')
-    n, H, W, ch = frames.shape
-    if ch != 3 or (n, W, H) != (table.n, table.W, table.H):
-        raise ValueError('frames do not match the cell table (n, H, W, 3)')
+    n, H, W, ch = _frame_shape(frames, dtype)
+    if (n, W, H) != (table.n, table.W, table.H):
+        raise ValueError('frames do not match the cell table (n, H, W, 3) or (n, H, W)')
     if out is None:
         out = torch.empty_like(frames)
     _need(out, dtype, 'out')
+    if ch == 1 and out.shape != frames.shape:
+        raise ValueError('out must have the shape of frames')
+    if ch == 1:
+        border = _grey_border(border_bgr)
+        if bounds is None:
+            _lib.check(_lib_.mf_warp_u8c1(_ptr(frames), _ptr(out), _ptr(table.buf), n, W, H, table.R, table.C, border, _ptr(table.crop),
+                                          _stream()))
+        else:
+            _need_bounds(bounds)
+            _lib.check(_lib_.mf_warp_bounds_u8c1(_ptr(frames), _ptr(out), _ptr(table.buf), n, W, H, table.R, table.C, border,
+                                                 _ptr(table.crop), _ptr(bounds), _stream()))
+        return out
     border = _border(border_bgr, dtype)
     u16 = dtype == torch.uint16
     if bounds is None:
@@ -172,13 +204,14 @@ def warp_clip(frames, unstab, stab, table, border_bgr=(0, 0, 255), out=None, chu
     stream -- table, warp alone, rectangle (early on `prep_stream` when one is given).  Returns (stabilized frames,
     bounds): bounds = int32 {left, top, right, bottom} of the clip -- the caller's tensor when one is given, else table.bounds --,
     folded together by the kernels, final on the prep stream right after the tables' crop scan (and on the current stream after
-    the call); per-frame values in table.crop; table.status accumulates degenerate cells.  frames: uint8 or uint16 (see `warp`)."""
+    the call); per-frame values in table.crop; table.status accumulates degenerate cells.  frames: uint8 or uint16, or (n, H, W) uint8
+    (see `warp`)."""
     dtype = _need_frames(frames, 'frames')
     _need(unstab, torch.float64, 'unstab')
     _need(stab, torch.float64, 'stab')
-    n, H, W, ch = frames.shape
+    n, H, W, ch = _frame_shape(frames, dtype)
     V2 = (table.R + 1) * (table.C + 1) * 2
-    if ch != 3 or (n, W, H) != (table.n, table.W, table.H) or unstab.numel() != n * V2 or stab.numel() != n * V2:
+    if (n, W, H) != (table.n, table.W, table.H) or unstab.numel() != n * V2 or stab.numel() != n * V2:
         raise ValueError('frames / displacements do not match the cell table')
     if out is None:
         out = torch.empty_like(frames)
@@ -189,9 +222,11 @@ def warp_clip(frames, unstab, stab, table, border_bgr=(0, 0, 255), out=None, chu
         bounds = table.bounds
     else:
         _need_bounds(bounds)
-    border = _border(border_bgr, dtype)
+    if ch == 1 and out.shape != frames.shape:
+        raise ValueError('out must have the shape of frames')
+    border = _grey_border(border_bgr) if ch == 1 else _border(border_bgr, dtype)
     prep = ctypes.c_void_p(prep_stream.cuda_stream) if prep_stream is not None else None
-    fn = _lib_.mf_warp_clip_u16c3 if dtype == torch.uint16 else _lib_.mf_warp_clip_u8c3
+    fn = _lib_.mf_warp_clip_u8c1 if ch == 1 else _lib_.mf_warp_clip_u16c3 if dtype == torch.uint16 else _lib_.mf_warp_clip_u8c3
     _lib.check(fn(_ptr(frames), _ptr(out), _ptr(unstab), _ptr(stab), n, W, H, table.R, table.C, border,
                   _ptr(table.buf), _ptr(table.crop), _ptr(bounds), _ptr(table.status), int(chunks), prep, _stream()))
     return out, bounds
@@ -220,17 +255,17 @@ def crop_reduce(crop, W, H):
 
 def crop_resize(frames, bounds, out=None):
     """Crop to the inclusive (left, top, right, bottom) and resize back to (W, H): mfs.py:1111-1157.  frames: uint8 or uint16 (uint16:
-    cv2.resize's float path, mf_crop_resize_u16c3); the output has the input's dtype."""
+    cv2.resize's float path, mf_crop_resize_u16c3), or (n, H, W) uint8 (mf_crop_resize_u8c1); the output has the input's dtype and shape."""
     dtype = _need_frames(frames, 'frames')
-    n, H, W, ch = frames.shape
-    if ch != 3:
-        raise ValueError('frames must be (n, H, W, 3)')
+    n, H, W, ch = _frame_shape(frames, dtype)
     left, top, right, bottom = (int(v) for v in bounds)
     if out is None:
         out = torch.empty_like(frames)
     _need(out, dtype, 'out')
+    if ch == 1 and out.shape != frames.shape:
+        raise ValueError('out must have the shape of frames')
     work = torch.empty(_lib_.mf_crop_resize_workspace_bytes(W, H), dtype=torch.uint8, device=frames.device)
-    fn = _lib_.mf_crop_resize_u16c3 if dtype == torch.uint16 else _lib_.mf_crop_resize_u8c3
+    fn = _lib_.mf_crop_resize_u8c1 if ch == 1 else _lib_.mf_crop_resize_u16c3 if dtype == torch.uint16 else _lib_.mf_crop_resize_u8c3
     _lib.check(fn(_ptr(frames), _ptr(out), n, W, H, left, top, right, bottom, _ptr(work), _stream()))
     return out
 

@@ -38,6 +38,7 @@ def _torch_device_of(self):
 def _warp_host_c(self, clip, unstab, stab, crop=False, keep_uncropped=True):
     """Host frames in -> host frames out through the C ABI's own chunked pipeline (csrc/hostpipe.hip:
     `mf_warp_u8c3_host_frames`, upload / kernel / download threads below Python, GIL released for the whole call).
+    Grey clips (HostClip.channels == 1) take the u8c1 twins of these calls and come back as (F, H, W) arrays.
     Returns (stabilized frames (F, H, W, 3) uint8 array, clip-level crop bounds as np.int64 (left, top, right,
     bottom), mfs.py:1103-1106).  crop=True: `mf_warp_crop_u8c3_host_frames` -- the same pipeline followed by `_crop_frames`
     (mfs.py:159, 1111-1157) on the device; returns (stabilized frames or None when keep_uncropped is False, bounds,
@@ -48,27 +49,30 @@ def _warp_host_c(self, clip, unstab, stab, crop=False, keep_uncropped=True):
     dev = self._torch_device()
     n, H, W = clip.num_frames, clip.height, clip.width
     frames = [clip.array[i] for i in range(n)] if clip.array is not None else clip.frames      # (validated by HostClip, every one of them)
-    fb = H * W * 3
+    grey = clip.channels == 1                     # (n, H, W) frames: the u8c1 calls, border byte = color_outside_image_area_bgr[0]
+    fb = H * W * clip.channels
     want_out = keep_uncropped or not crop
-    out = np.empty((n, H, W, 3), dtype=np.uint8) if want_out else None
+    out = np.empty((n,) + clip.frame_shape, dtype=np.uint8) if want_out else None
     pin = (ctypes.c_void_p * n)(*[f.ctypes.data for f in frames])
     pout = (ctypes.c_void_p * n)(*[out.ctypes.data + i * fb for i in range(n)]) if want_out else None
     per_frame = np.empty((n, 4), dtype=np.int32)
     border = (ctypes.c_uint8 * 3)(*[int(max(0, min(255, round(float(c))))) for c in self.color_outside_image_area_bgr])
+    if grey:
+        border = ctypes.c_uint8(border[0])
     args = (unstab.ctypes.data_as(ctypes.c_void_p), stab.ctypes.data_as(ctypes.c_void_p), n, W, H,
             self.mesh_row_count, self.mesh_col_count, border, per_frame.ctypes.data_as(ctypes.c_void_p))
     # the library works on the calling thread's current HIP device: scope it like every other path here does (and leave the
     # caller's current device as it was)
     with torch.cuda.device(dev):
         if not crop:
-            _lib.check(_lib.lib.mf_warp_u8c3_host_frames(pin, pout, *args, None))
+            _lib.check((_lib.lib.mf_warp_u8c1_host_frames if grey else _lib.lib.mf_warp_u8c3_host_frames)(pin, pout, *args, None))
             bounds = (np.int64(per_frame[:, 0].max()), np.int64(per_frame[:, 1].max()),
                       np.int64(per_frame[:, 2].min()), np.int64(per_frame[:, 3].min()))
             return out, bounds
-        cropped = np.empty((n, H, W, 3), dtype=np.uint8)
+        cropped = np.empty((n,) + clip.frame_shape, dtype=np.uint8)
         pcrop = (ctypes.c_void_p * n)(*[cropped.ctypes.data + i * fb for i in range(n)])
         rect = (ctypes.c_int32 * 4)()
-        _lib.check(_lib.lib.mf_warp_crop_u8c3_host_frames(pin, pout, pcrop, *args, rect, None))
+        _lib.check((_lib.lib.mf_warp_crop_u8c1_host_frames if grey else _lib.lib.mf_warp_crop_u8c3_host_frames)(pin, pout, pcrop, *args, rect, None))
     return out, tuple(np.int64(v) for v in rect), cropped
 
 
@@ -359,12 +363,13 @@ class MeshFlowStabilizer:
         H, W = clip.height, clip.width
         frames = [clip.array[i] for i in range(n)] if clip.array is not None else clip.frames       # (every frame validated by HostClip)
         left, top, right, bottom = (int(v) for v in crop_boundaries)
-        out = np.empty((n, H, W, 3), dtype=np.uint8)
-        fb = H * W * 3
+        out = np.empty((n,) + clip.frame_shape, dtype=np.uint8)
+        fb = H * W * clip.channels
         pin = (ctypes.c_void_p * n)(*[f.ctypes.data for f in frames])
         pout = (ctypes.c_void_p * n)(*[out.ctypes.data + i * fb for i in range(n)])
+        fn = _lib.lib.mf_crop_resize_u8c1_host_frames if clip.channels == 1 else _lib.lib.mf_crop_resize_u8c3_host_frames
         with torch.cuda.device(dev):
-            _lib.check(_lib.lib.mf_crop_resize_u8c3_host_frames(pin, pout, n, W, H, left, top, right, bottom, None))
+            _lib.check(fn(pin, pout, n, W, H, left, top, right, bottom, None))
         return list(out)
 
     def compute_scores(self, frame_width, frame_height, vertex_unstabilized_displacements_by_frame_index,
@@ -592,7 +597,7 @@ class MeshFlowStabilizer:
         st = self._resident_state(dev)
         main = torch.cuda.current_stream(dev)
         chunks = self.resident_chunks if chunks is None else chunks
-        n, H, W, _ = d_frames.shape
+        n, H, W = d_frames.shape[:3]
         if n == 0:
             # an EMPTY shard (a clip of fewer frames than ranks, or the tail of an uneven split): nothing to warp; the rectangle's
             # neutral element (mfs.py:992-995), so that the rank still takes part in the all-reduce, and d_stab in stream order
@@ -602,7 +607,7 @@ class MeshFlowStabilizer:
             if self.resident_rectangle == 'early':
                 st['scanned'] = torch.cuda.Event()
                 st['scanned'].record(main)
-            return (out if out is not None else d_frames.new_empty((0, H, W, 3))), bounds, None
+            return (out if out is not None else d_frames.new_empty(tuple(d_frames.shape))), bounds, None
         slot = self._resident_slot(st, n, W, H)
         table = slot['table']
         bounds = torch.empty(4, dtype=torch.int32, device=dev)           # this clip's own: never rewritten by a later one
@@ -662,8 +667,8 @@ class MeshFlowStabilizer:
     def stabilize_resident(self, d_frames, d_disp, homographies, adaptive_weights_definition=ADAPTIVE_WEIGHTS_DEFINITION_ORIGINAL,
                            out=None, frame_range=None, inputs_ready=None, check=True, collective=False, warp_events=None,
                            jacobi_events=None):
-        """mfs.py:150-158 for a clip whose frames (n, H, W, 3) uint8 or uint16 and vertex displacements (F, R+1, C+1, 2) float64 are
-        RESIDENT in HBM (uint16 frames: cv2.remap's 16U arithmetic, `ops.warp`; the sweep, tables and rectangle are the uint8 call's): Jacobi sweep -> cell tables -> warp + crop rectangle, nothing leaves the device, one call per clip, NO synchronisation:
+        """mfs.py:150-158 for a clip whose frames (n, H, W, 3) uint8 or uint16 -- or (n, H, W) uint8 grey -- and vertex displacements
+        (F, R+1, C+1, 2) float64 are RESIDENT in HBM (uint16 and grey frames: `ops.warp`; the sweep, tables and rectangle are the uint8 call's): Jacobi sweep -> cell tables -> warp + crop rectangle, nothing leaves the device, one call per clip, NO synchronisation:
         calls issued back to back pipeline by themselves (the sweep runs on this object's prep stream, the next clip's beside this
         clip's cell table + plan; see `resident_chunks` for the other arrangement).
         frame_range = (lo, hi): d_frames holds frames lo..hi-1 of the clip (a frame-range shard; the sweep still covers all F);
@@ -690,7 +695,9 @@ class MeshFlowStabilizer:
             check = 'never'
         F = d_disp.shape[0]
         lo, hi = frame_range if frame_range is not None else (0, F)
-        n, H, W, _ = d_frames.shape
+        if d_frames.dim() == 3 and d_frames.dtype != torch.uint8:
+            raise ValueError(f'single-channel frames must be uint8 (got {d_frames.dtype}): (n, H, W) {d_frames.dtype} frames are not supported')
+        n, H, W = d_frames.shape[:3]
         if hi - lo != n:
             raise ValueError(f'frame_range {lo, hi} does not match {n} frames')
         dev = d_frames.device
