@@ -1,5 +1,7 @@
 """Randomised parity campaign: HIP kernels vs the C oracle on random geometries (bit-exact or bust).
-Usage: python tests/fuzz_parity.py [cases] [seed]"""
+pixel='u8c3' (the default) draws the original stream; 'u16c3' and 'u8c1' run the same geometries on uint16 BGR frames (against
+tests/cv16_model.py) and single-channel frames (against channel 0 of the C oracle on the frame repeated three times), Jacobi cases skipped.
+Usage: python tests/fuzz_parity.py [cases] [seed] [case] [big|-] [u8c3|u16c3|u8c1]"""
 import sys, os, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -8,8 +10,33 @@ from oracle import clib, meshflow_oracle as mo
 
 
 
-def run(cases=200, seed0=0, only=-1, big=False):
+def _pixel_frames(frames, pixel, case):
+    """The campaign's uint8 BGR frames as the pixel type under test (from a stream of their own: the campaign's draws stay as they are)."""
+    if pixel == 'u8c1':
+        return np.ascontiguousarray(frames[..., 0])
+    if pixel == 'u16c3':
+        return np.random.default_rng(case).integers(0, 65536, frames.shape, dtype=np.uint16)
+    return frames
+
+
+def _to_dev(a, dev):
+    if a.dtype == np.uint16:
+        return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8)).to(dev).view(torch.uint16)
+    return torch.from_numpy(a).to(dev)
+
+
+def _to_np(t):
+    if t.dtype == torch.uint16:
+        return t.contiguous().view(torch.uint8).cpu().numpy().view(np.uint16)
+    return t.cpu().numpy()
+
+
+def run(cases=200, seed0=0, only=-1, big=False, pixel='u8c3'):
     """Returns (number of mismatching cases, per-kind counts)."""
+    assert pixel in ('u8c3', 'u16c3', 'u8c1'), pixel
+    if pixel == 'u16c3':
+        sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+        import cv16_model
     dev = torch.device('cuda:0')
     g = np.random.default_rng(seed0)
     bad_cases = 0
@@ -34,22 +61,32 @@ def run(cases=200, seed0=0, only=-1, big=False):
             use_bbox = bool(g.random() < 0.5)
             if only >= 0 and case != only:
                 continue
+            if pixel == 'u8c1':
+                border = (border[0],) * 3
             want, want_crop, bad = clib.warp_clip(frames, R, C, unstab, stab, border_bgr=border, use_bbox=use_bbox or big, openmp=big)
+            frames = _pixel_frames(frames, pixel, case)
+            if pixel == 'u8c1':
+                want = want[..., 0]
+            elif pixel == 'u16c3':
+                border = tuple(257 * b for b in border)
+                if bad == 0:
+                    want, want_crop16 = cv16_model.warp_clip_u16(frames, R, C, unstab, stab, border)
+                    assert np.array_equal(want_crop16, want_crop)
             table = ops.cell_table(torch.from_numpy(unstab).to(dev), torch.from_numpy(stab).to(dev), W, H, R, C)
-            out = ops.warp(torch.from_numpy(frames).to(dev), table, border)
+            out = ops.warp(_to_dev(frames, dev), table, border)
             torch.cuda.synchronize()
             nbad = int(table.status.item())
             ok = nbad == bad
             if bad == 0:
-                ok = ok and np.array_equal(out.cpu().numpy(), want) and np.array_equal(table.crop.cpu().numpy(), want_crop)
+                ok = ok and np.array_equal(_to_np(out), want) and np.array_equal(table.crop.cpu().numpy(), want_crop)
                 stats['warp'] += 1
             else:
                 stats['warp_degenerate'] += 1
             desc = f'warp W={W} H={H} R={R} C={C} n={n} sigma={sigma:.2f} degenerate={bad}'
             if only >= 0:
-                o = out.cpu().numpy()
+                o = _to_np(out)
                 for f in range(n):
-                    d = np.argwhere((o[f] != want[f]).any(axis=2))
+                    d = np.argwhere((o[f] != want[f]).reshape(H, W, -1).any(axis=2))
                     print('frame', f, 'differing pixels', len(d), d[:20].tolist())
                     for (yy, xx) in d[:5]:
                         print('   at', yy, xx, 'got', o[f][yy, xx], 'want', want[f][yy, xx])
@@ -60,6 +97,8 @@ def run(cases=200, seed0=0, only=-1, big=False):
             if only >= 0: 
                 # keep the random stream in step
                 pass
+            if pixel != 'u8c3':
+                continue
             F = int(g.integers(1, 900)); S = int(g.integers(1, 40)); omega = int(g.choice([1, 2, 5, 10, 10, 30, 30, 17, 40])); iters = int(g.integers(0, 40))
             b = np.cumsum(3.0 * synthetic.normal(np.arange(F * S).reshape(F, S), seed=case), axis=0)
             taps = np.exp(-np.square((3 / omega) * np.arange(-omega, omega + 1)))
@@ -75,8 +114,15 @@ def run(cases=200, seed0=0, only=-1, big=False):
             W = int(g.integers(4, 300)); H = int(g.integers(4, 200)); n = int(g.integers(1, 3))
             l = int(g.integers(0, W)); r = int(g.integers(l, W)); tp = int(g.integers(0, H)); bt = int(g.integers(tp, H))
             frames = synthetic.frames_numpy(n, H, W, seed=case, kind='noise')
-            want = np.stack(mo.crop_frames(list(frames), (l, tp, r, bt)))
-            got = ops.crop_resize(torch.from_numpy(frames).to(dev), (l, tp, r, bt)).cpu().numpy()
+            if pixel == 'u16c3':
+                frames = _pixel_frames(frames, pixel, case)
+                want = cv16_model.crop_frames_u16(frames, (l, tp, r, bt))
+            else:
+                want = np.stack(mo.crop_frames(list(frames), (l, tp, r, bt)))
+                if pixel == 'u8c1':
+                    want = np.ascontiguousarray(want[..., 0])
+                    frames = _pixel_frames(frames, pixel, case)
+            got = _to_np(ops.crop_resize(_to_dev(frames, dev), (l, tp, r, bt)))
             ok = np.array_equal(got, want)
             stats['resize'] += 1
             desc = f'resize W={W} H={H} crop=({l},{tp},{r},{bt})'
@@ -92,4 +138,5 @@ if __name__ == '__main__':
     sd = int(sys.argv[2]) if len(sys.argv) > 2 else 0
     one = int(sys.argv[3]) if len(sys.argv) > 3 else -1            # re-run just this case, verbosely
     big = len(sys.argv) > 4 and sys.argv[4] == 'big'                # frames up to 2100 x 1200, meshes up to 64 x 64
-    sys.exit(1 if run(n, sd, one, big)[0] else 0)
+    px = sys.argv[5] if len(sys.argv) > 5 else 'u8c3'
+    sys.exit(1 if run(n, sd, one, big, px)[0] else 0)

@@ -102,3 +102,21 @@ def test_resize_identity_and_2x_upscale():
     out = m.resize_linear_u16(col, 1, 4)
     assert out[:, 0, 2].tolist() == [0, 16384, 49151, 65535]       # 0.25 * 65535 = 16383.75, 0.75 * 65535 = 49151.25
     np.testing.assert_array_equal(m.crop_frames_u16(src[None], (0, 0, 4, 6))[0], src)
+
+
+def test_fast_blend_rounds_inside_its_samples():
+    """The premise of the unclamped fast blend in warp.hip's remap_store_u16: the float32 chain ((s00 w0 + s01 w1) + s10 w2) + s11 w3
+    rounds (half to even) into [min, max] of its four samples, so saturate_cast's clamp to 65535 never acts there.  Every (fx, fy) of
+    the 32 x 32 weight table, every quadruple of samples from {0, 1, 65533, 65534, 65535}; a change of the blend order that breaks the
+    premise fails here first."""
+    import itertools
+    vals = np.array([0, 1, 65533, 65534, 65535])
+    quads = np.array(list(itertools.product(vals, repeat=4)), np.float32)            # (625, 4)
+    fx, fy = np.meshgrid(np.arange(32), np.arange(32), indexing='ij')
+    w = [wk.reshape(-1, 1) for wk in m.weights_f32(fx.reshape(-1), fy.reshape(-1))]   # (1024, 1) each
+    s = [quads[:, k].reshape(1, -1) for k in range(4)]
+    t = ((s[0] * w[0] + s[1] * w[1]) + s[2] * w[2]) + s[3] * w[3]
+    assert t.dtype == np.float32 and t.shape == (1024, 625)
+    r = np.rint(t.astype(np.float64))
+    assert (r >= quads.min(1)[None, :]).all() and (r <= quads.max(1)[None, :]).all()
+    assert (m.saturate_u16(t) == r).all()
