@@ -24,7 +24,26 @@ int hip_fail(hipError_t e, const char* what)
     return MF_ERR_HIP;
 }
 
-static uint32_t pack_border(const uint8_t b[3]) { return (uint32_t)b[0] | ((uint32_t)b[1] << 8) | ((uint32_t)b[2] << 16); }
+// The checks of every device warp entry, then launch_warp.  has_bounds: an mf_warp_bounds_* entry -- the clip-level rectangle goes to the
+// caller's d_bounds instead of the table's.
+static int warp_entry(const char* name, Px px, const void* d_frames, void* d_out, const void* d_table, int n, int W, int H, int R, int C,
+                      const void* border, int32_t* d_crop, bool has_bounds, int32_t* d_bounds, void* stream)
+{
+    if (!d_frames || !d_out || !d_table || !border || !d_crop || (has_bounds && !d_bounds)) { set_error("%s: null pointer", name); return MF_ERR_INVALID_ARG; }
+    if (d_frames == d_out) { set_error("%s: d_frames and d_out alias", name); return MF_ERR_INVALID_ARG; }
+    if (n <= 0 || R <= 0 || C <= 0) { set_error("%s: bad sizes", name); return MF_ERR_INVALID_ARG; }
+    TableView tv = table_view(const_cast<void*>(d_table), n, W, H, R, C);
+    if (has_bounds) tv.bounds = d_bounds;
+    return launch_warp(px, d_frames, d_out, tv, n, W, H, R, C, pack_border(px, border), d_crop, (hipStream_t)stream);
+}
+
+static int crop_resize_entry(const char* name, Px px, const void* d_frames, void* d_out, int n, int W, int H, int left, int top, int right,
+                             int bottom, void* d_work, void* stream)
+{
+    if (!d_frames || !d_out || !d_work) { set_error("%s: null pointer", name); return MF_ERR_INVALID_ARG; }
+    if (d_frames == d_out) { set_error("%s: d_frames and d_out alias", name); return MF_ERR_INVALID_ARG; }
+    return launch_crop_resize(px, d_frames, d_out, n, W, H, left, top, right, bottom, d_work, (hipStream_t)stream);
+}
 
 }  // namespace mf
 
@@ -109,33 +128,19 @@ int mf_cell_table_f64(const double* d_unstab, const double* d_stab, int n, int W
 int mf_warp_u8c3(const uint8_t* d_frames, uint8_t* d_out, const void* d_table, int n, int W, int H,
                  int R, int C, const uint8_t border_bgr[3], int32_t* d_crop, void* stream)
 {
-    if (!d_frames || !d_out || !d_table || !border_bgr || !d_crop) { set_error("mf_warp_u8c3: null pointer"); return MF_ERR_INVALID_ARG; }
-    if (d_frames == d_out) { set_error("mf_warp_u8c3: d_frames and d_out alias"); return MF_ERR_INVALID_ARG; }
-    if (n <= 0 || R <= 0 || C <= 0) { set_error("mf_warp_u8c3: bad sizes"); return MF_ERR_INVALID_ARG; }
-    const TableView tv = table_view(const_cast<void*>(d_table), n, W, H, R, C);
-    return launch_warp(d_frames, d_out, tv, n, W, H, R, C, pack_border(border_bgr), d_crop, (hipStream_t)stream);
+    return warp_entry("mf_warp_u8c3", Px::U8C3, d_frames, d_out, d_table, n, W, H, R, C, border_bgr, d_crop, false, nullptr, stream);
 }
-
-static uint64_t pack_border16(const uint16_t b[3]) { return (uint64_t)b[0] | ((uint64_t)b[1] << 16) | ((uint64_t)b[2] << 32); }
 
 int mf_warp_u16c3(const uint16_t* d_frames, uint16_t* d_out, const void* d_table, int n, int W, int H,
                   int R, int C, const uint16_t border_bgr[3], int32_t* d_crop, void* stream)
 {
-    if (!d_frames || !d_out || !d_table || !border_bgr || !d_crop) { set_error("mf_warp_u16c3: null pointer"); return MF_ERR_INVALID_ARG; }
-    if (d_frames == d_out) { set_error("mf_warp_u16c3: d_frames and d_out alias"); return MF_ERR_INVALID_ARG; }
-    if (n <= 0 || R <= 0 || C <= 0) { set_error("mf_warp_u16c3: bad sizes"); return MF_ERR_INVALID_ARG; }
-    const TableView tv = table_view(const_cast<void*>(d_table), n, W, H, R, C);
-    return launch_warp_u16(d_frames, d_out, tv, n, W, H, R, C, pack_border16(border_bgr), d_crop, (hipStream_t)stream);
+    return warp_entry("mf_warp_u16c3", Px::U16C3, d_frames, d_out, d_table, n, W, H, R, C, border_bgr, d_crop, false, nullptr, stream);
 }
 
 int mf_warp_u8c1(const uint8_t* d_frames, uint8_t* d_out, const void* d_table, int n, int W, int H,
                  int R, int C, uint8_t border, int32_t* d_crop, void* stream)
 {
-    if (!d_frames || !d_out || !d_table || !d_crop) { set_error("mf_warp_u8c1: null pointer"); return MF_ERR_INVALID_ARG; }
-    if (d_frames == d_out) { set_error("mf_warp_u8c1: d_frames and d_out alias"); return MF_ERR_INVALID_ARG; }
-    if (n <= 0 || R <= 0 || C <= 0) { set_error("mf_warp_u8c1: bad sizes"); return MF_ERR_INVALID_ARG; }
-    const TableView tv = table_view(const_cast<void*>(d_table), n, W, H, R, C);
-    return launch_warp_u8c1(d_frames, d_out, tv, n, W, H, R, C, border, d_crop, (hipStream_t)stream);
+    return warp_entry("mf_warp_u8c1", Px::U8C1, d_frames, d_out, d_table, n, W, H, R, C, &border, d_crop, false, nullptr, stream);
 }
 
 int mf_crop_scan_f64(const void* d_table, int n, int W, int H, int R, int C, int32_t* d_crop, void* stream)
@@ -161,34 +166,19 @@ int mf_cell_table_bounds_f64(const double* d_unstab, const double* d_stab, int n
 int mf_warp_bounds_u8c3(const uint8_t* d_frames, uint8_t* d_out, const void* d_table, int n, int W, int H,
                         int R, int C, const uint8_t border_bgr[3], int32_t* d_crop, int32_t* d_bounds, void* stream)
 {
-    if (!d_frames || !d_out || !d_table || !border_bgr || !d_crop || !d_bounds) { set_error("mf_warp_bounds_u8c3: null pointer"); return MF_ERR_INVALID_ARG; }
-    if (d_frames == d_out) { set_error("mf_warp_bounds_u8c3: d_frames and d_out alias"); return MF_ERR_INVALID_ARG; }
-    if (n <= 0 || R <= 0 || C <= 0) { set_error("mf_warp_bounds_u8c3: bad sizes"); return MF_ERR_INVALID_ARG; }
-    TableView tv = table_view(const_cast<void*>(d_table), n, W, H, R, C);
-    tv.bounds = d_bounds;
-    return launch_warp(d_frames, d_out, tv, n, W, H, R, C, pack_border(border_bgr), d_crop, (hipStream_t)stream);
+    return warp_entry("mf_warp_bounds_u8c3", Px::U8C3, d_frames, d_out, d_table, n, W, H, R, C, border_bgr, d_crop, true, d_bounds, stream);
 }
 
 int mf_warp_bounds_u16c3(const uint16_t* d_frames, uint16_t* d_out, const void* d_table, int n, int W, int H,
                          int R, int C, const uint16_t border_bgr[3], int32_t* d_crop, int32_t* d_bounds, void* stream)
 {
-    if (!d_frames || !d_out || !d_table || !border_bgr || !d_crop || !d_bounds) { set_error("mf_warp_bounds_u16c3: null pointer"); return MF_ERR_INVALID_ARG; }
-    if (d_frames == d_out) { set_error("mf_warp_bounds_u16c3: d_frames and d_out alias"); return MF_ERR_INVALID_ARG; }
-    if (n <= 0 || R <= 0 || C <= 0) { set_error("mf_warp_bounds_u16c3: bad sizes"); return MF_ERR_INVALID_ARG; }
-    TableView tv = table_view(const_cast<void*>(d_table), n, W, H, R, C);
-    tv.bounds = d_bounds;
-    return launch_warp_u16(d_frames, d_out, tv, n, W, H, R, C, pack_border16(border_bgr), d_crop, (hipStream_t)stream);
+    return warp_entry("mf_warp_bounds_u16c3", Px::U16C3, d_frames, d_out, d_table, n, W, H, R, C, border_bgr, d_crop, true, d_bounds, stream);
 }
 
 int mf_warp_bounds_u8c1(const uint8_t* d_frames, uint8_t* d_out, const void* d_table, int n, int W, int H,
                         int R, int C, uint8_t border, int32_t* d_crop, int32_t* d_bounds, void* stream)
 {
-    if (!d_frames || !d_out || !d_table || !d_crop || !d_bounds) { set_error("mf_warp_bounds_u8c1: null pointer"); return MF_ERR_INVALID_ARG; }
-    if (d_frames == d_out) { set_error("mf_warp_bounds_u8c1: d_frames and d_out alias"); return MF_ERR_INVALID_ARG; }
-    if (n <= 0 || R <= 0 || C <= 0) { set_error("mf_warp_bounds_u8c1: bad sizes"); return MF_ERR_INVALID_ARG; }
-    TableView tv = table_view(const_cast<void*>(d_table), n, W, H, R, C);
-    tv.bounds = d_bounds;
-    return launch_warp_u8c1(d_frames, d_out, tv, n, W, H, R, C, border, d_crop, (hipStream_t)stream);
+    return warp_entry("mf_warp_bounds_u8c1", Px::U8C1, d_frames, d_out, d_table, n, W, H, R, C, &border, d_crop, true, d_bounds, stream);
 }
 
 int mf_crop_scan_bounds_f64(const void* d_table, int n, int W, int H, int R, int C, int32_t* d_crop, int32_t* d_bounds, void* stream)
@@ -214,25 +204,19 @@ size_t mf_crop_resize_workspace_bytes(int W, int H)
 int mf_crop_resize_u8c3(const uint8_t* d_frames, uint8_t* d_out, int n, int W, int H, int left, int top, int right,
                         int bottom, void* d_work, void* stream)
 {
-    if (!d_frames || !d_out || !d_work) { set_error("mf_crop_resize_u8c3: null pointer"); return MF_ERR_INVALID_ARG; }
-    if (d_frames == d_out) { set_error("mf_crop_resize_u8c3: d_frames and d_out alias"); return MF_ERR_INVALID_ARG; }
-    return launch_crop_resize(d_frames, d_out, n, W, H, left, top, right, bottom, d_work, (hipStream_t)stream);
+    return crop_resize_entry("mf_crop_resize_u8c3", Px::U8C3, d_frames, d_out, n, W, H, left, top, right, bottom, d_work, stream);
 }
 
 int mf_crop_resize_u16c3(const uint16_t* d_frames, uint16_t* d_out, int n, int W, int H, int left, int top, int right,
                          int bottom, void* d_work, void* stream)
 {
-    if (!d_frames || !d_out || !d_work) { set_error("mf_crop_resize_u16c3: null pointer"); return MF_ERR_INVALID_ARG; }
-    if (d_frames == d_out) { set_error("mf_crop_resize_u16c3: d_frames and d_out alias"); return MF_ERR_INVALID_ARG; }
-    return launch_crop_resize_u16(d_frames, d_out, n, W, H, left, top, right, bottom, d_work, (hipStream_t)stream);
+    return crop_resize_entry("mf_crop_resize_u16c3", Px::U16C3, d_frames, d_out, n, W, H, left, top, right, bottom, d_work, stream);
 }
 
 int mf_crop_resize_u8c1(const uint8_t* d_frames, uint8_t* d_out, int n, int W, int H, int left, int top, int right,
                         int bottom, void* d_work, void* stream)
 {
-    if (!d_frames || !d_out || !d_work) { set_error("mf_crop_resize_u8c1: null pointer"); return MF_ERR_INVALID_ARG; }
-    if (d_frames == d_out) { set_error("mf_crop_resize_u8c1: d_frames and d_out alias"); return MF_ERR_INVALID_ARG; }
-    return launch_crop_resize_u8c1(d_frames, d_out, n, W, H, left, top, right, bottom, d_work, (hipStream_t)stream);
+    return crop_resize_entry("mf_crop_resize_u8c1", Px::U8C1, d_frames, d_out, n, W, H, left, top, right, bottom, d_work, stream);
 }
 
 size_t mf_vertex_motion_workspace_bytes(int total_features, int max_per_pair, int P, int R, int C)

@@ -54,45 +54,23 @@ using namespace mf;
 
 namespace {
 
-// The warp of one frame range, per pixel type: uint8 (launch_warp, border packed B | G << 8 | R << 16) or uint16 (launch_warp_u16,
-// B | G << 16 | R << 32).
-int warp_range(const uint8_t* frames, uint8_t* out, const TableView& tv, int n, int W, int H, int R, int C, const uint8_t border_bgr[3],
-               int32_t* crop, hipStream_t st)
-{
-    const uint32_t border = (uint32_t)border_bgr[0] | ((uint32_t)border_bgr[1] << 8) | ((uint32_t)border_bgr[2] << 16);
-    return launch_warp(frames, out, tv, n, W, H, R, C, border, crop, st);
-}
-int warp_range(const uint16_t* frames, uint16_t* out, const TableView& tv, int n, int W, int H, int R, int C, const uint16_t border_bgr[3],
-               int32_t* crop, hipStream_t st)
-{
-    const uint64_t border = (uint64_t)border_bgr[0] | ((uint64_t)border_bgr[1] << 16) | ((uint64_t)border_bgr[2] << 32);
-    return launch_warp_u16(frames, out, tv, n, W, H, R, C, border, crop, st);
-}
-
-// ... and single-channel uint8 frames (launch_warp_u8c1, the border byte border[0])
-int warp_range_c1(const uint8_t* frames, uint8_t* out, const TableView& tv, int n, int W, int H, int R, int C, const uint8_t* border,
-                  int32_t* crop, hipStream_t st)
-{
-    return launch_warp_u8c1(frames, out, tv, n, W, H, R, C, border[0], crop, st);
-}
-
-// CH: samples per pixel (3: BGR, border_bgr[0..2]; 1: grey, border_bgr[0] only)
-template <typename T, int CH = 3>
-int warp_clip(const char* name, const T* d_frames, T* d_out, const double* d_unstab, const double* d_stab, int n, int W, int H,
-              int R, int C, const T* border_bgr, void* d_table, int32_t* d_crop, int32_t* d_bounds,
+// frames of format px, `border` its px_channels(px) samples
+int warp_clip(const char* name, Px px, const void* d_frames, void* d_out, const double* d_unstab, const double* d_stab, int n, int W, int H,
+              int R, int C, const void* border, void* d_table, int32_t* d_crop, int32_t* d_bounds,
               int32_t* d_status, int chunks, void* prep_stream, void* stream)
 {
-    if (!d_frames || !d_out || !d_unstab || !d_stab || !border_bgr || !d_table || !d_crop || !d_bounds || !d_status) {
+    if (!d_frames || !d_out || !d_unstab || !d_stab || !border || !d_table || !d_crop || !d_bounds || !d_status) {
         set_error("%s: null pointer", name);
         return MF_ERR_INVALID_ARG;
     }
     if (d_frames == d_out) { set_error("%s: d_frames and d_out alias", name); return MF_ERR_INVALID_ARG; }
     if (n <= 0 || R <= 0 || C <= 0 || W < 2 || H < 2) { set_error("%s: bad sizes", name); return MF_ERR_INVALID_ARG; }
-    // (the uint16 and grey calls refuse what their warp would refuse before the cell table is launched; the uint8 BGR one keeps its order)
-    if ((sizeof(T) == 2 || CH == 1) && (R > 64 || C > 64 || W > 32767 || H > 32767)) {
+    // (what the warp would refuse is refused before the cell table is launched)
+    if (R > 64 || C > 64 || W > 32767 || H > 32767) {
         set_error("%s: unsupported shape W=%d H=%d R=%d C=%d", name, W, H, R, C);
         return MF_ERR_INVALID_ARG;
     }
+    const uint64_t packed = pack_border(px, border);
     ClipSide* side = clip_side_for_current_device();
     if (!side) { set_error("%s: no stream / events on this device", name); return MF_ERR_HIP; }
     if (chunks <= 0) {
@@ -114,9 +92,7 @@ int warp_clip(const char* name, const T* d_frames, T* d_out, const double* d_uns
             if (const int rc = launch_crop_scan(tv, n, W, H, R, C, d_crop, prep)) return rc;
             MF_HIP_TRY(hipEventRecord(side->done, prep));
         }
-        const int rc = CH == 1 ? warp_range_c1((const uint8_t*)d_frames, (uint8_t*)d_out, tv, n, W, H, R, C, (const uint8_t*)border_bgr, d_crop, st)
-                               : warp_range(d_frames, d_out, tv, n, W, H, R, C, border_bgr, d_crop, st);
-        if (rc) return rc;
+        if (const int rc = launch_warp(px, d_frames, d_out, tv, n, W, H, R, C, packed, d_crop, st)) return rc;
         if (early) MF_HIP_TRY(hipStreamWaitEvent(st, side->done, 0));
         return MF_OK;
     }
@@ -126,7 +102,7 @@ int warp_clip(const char* name, const T* d_frames, T* d_out, const double* d_uns
     hipStream_t prep = (hipStream_t)prep_stream;
     TableView tv = table_view(d_table, n, W, H, R, C);
     tv.bounds = d_bounds;                      // (the first chunk's cell table sets the defaults there, the scan and the warps fold into it)
-    const size_t vb1 = (size_t)(R + 1) * (C + 1) * 2, fb = (size_t)W * H * CH;
+    const size_t vb1 = (size_t)(R + 1) * (C + 1) * 2, fb = (size_t)W * H * px_bytes(px);
     const int per = (n + chunks - 1) / chunks;
     // the event set is per device: one call at a time records and waits on it (host side only -- the GPU work overlaps freely)
     std::lock_guard<std::mutex> g(side->lock);
@@ -150,10 +126,8 @@ int warp_clip(const char* name, const T* d_frames, T* d_out, const double* d_uns
         const int m = n - i0 < per ? n - i0 : per;
         if (!one_stream) MF_HIP_TRY(hipStreamWaitEvent(st, side->ready[nk], 0));
         const TableView ts = table_slice(tv, i0, W, H, R, C);
-        const int rc = CH == 1 ? warp_range_c1((const uint8_t*)(d_frames + fb * i0), (uint8_t*)(d_out + fb * i0), ts, m, W, H, R, C,
-                                               (const uint8_t*)border_bgr, d_crop + 4 * (size_t)i0, st)
-                               : warp_range(d_frames + fb * i0, d_out + fb * i0, ts, m, W, H, R, C, border_bgr, d_crop + 4 * (size_t)i0, st);
-        if (rc) return rc;
+        if (const int rc = launch_warp(px, (const uint8_t*)d_frames + fb * i0, (uint8_t*)d_out + fb * i0, ts, m, W, H, R, C, packed,
+                                       d_crop + 4 * (size_t)i0, st)) return rc;
     }
     if (!one_stream) MF_HIP_TRY(hipStreamWaitEvent(st, side->done, 0));          // `stream` order now also implies: d_bounds is final
     return MF_OK;
@@ -165,23 +139,22 @@ extern "C" int mf_warp_clip_u8c3(const uint8_t* d_frames, uint8_t* d_out, const 
                                  int R, int C, const uint8_t border_bgr[3], void* d_table, int32_t* d_crop, int32_t* d_bounds,
                                  int32_t* d_status, int chunks, void* prep_stream, void* stream)
 {
-    return warp_clip("mf_warp_clip_u8c3", d_frames, d_out, d_unstab, d_stab, n, W, H, R, C, border_bgr, d_table, d_crop, d_bounds, d_status,
-                     chunks, prep_stream, stream);
+    return warp_clip("mf_warp_clip_u8c3", Px::U8C3, d_frames, d_out, d_unstab, d_stab, n, W, H, R, C, border_bgr, d_table, d_crop, d_bounds,
+                     d_status, chunks, prep_stream, stream);
 }
 
 extern "C" int mf_warp_clip_u16c3(const uint16_t* d_frames, uint16_t* d_out, const double* d_unstab, const double* d_stab, int n, int W, int H,
                                   int R, int C, const uint16_t border_bgr[3], void* d_table, int32_t* d_crop, int32_t* d_bounds,
                                   int32_t* d_status, int chunks, void* prep_stream, void* stream)
 {
-    return warp_clip("mf_warp_clip_u16c3", d_frames, d_out, d_unstab, d_stab, n, W, H, R, C, border_bgr, d_table, d_crop, d_bounds, d_status,
-                     chunks, prep_stream, stream);
+    return warp_clip("mf_warp_clip_u16c3", Px::U16C3, d_frames, d_out, d_unstab, d_stab, n, W, H, R, C, border_bgr, d_table, d_crop, d_bounds,
+                     d_status, chunks, prep_stream, stream);
 }
 
 extern "C" int mf_warp_clip_u8c1(const uint8_t* d_frames, uint8_t* d_out, const double* d_unstab, const double* d_stab, int n, int W, int H,
                                  int R, int C, uint8_t border, void* d_table, int32_t* d_crop, int32_t* d_bounds,
                                  int32_t* d_status, int chunks, void* prep_stream, void* stream)
 {
-    const uint8_t b[1] = { border };
-    return warp_clip<uint8_t, 1>("mf_warp_clip_u8c1", d_frames, d_out, d_unstab, d_stab, n, W, H, R, C, b, d_table, d_crop, d_bounds, d_status,
-                                 chunks, prep_stream, stream);
+    return warp_clip("mf_warp_clip_u8c1", Px::U8C1, d_frames, d_out, d_unstab, d_stab, n, W, H, R, C, &border, d_table, d_crop, d_bounds,
+                     d_status, chunks, prep_stream, stream);
 }

@@ -188,8 +188,8 @@ struct PipeJob {
     const uint8_t* const* frames; uint8_t* const* out; uint8_t* const* cropped;
     const double* unstab; const double* stab;
     int n, W, H, R, C;
-    int channels;                                    // 3: BGR (launch_warp / launch_crop_resize), 1: grey (the u8c1 launches, border & 0xFF)
-    uint32_t border;
+    Px px;                                           // U8C3 or U8C1 (host frames are uint8)
+    uint64_t border;                                 // pack_border's word
     int32_t* crop; int32_t* bounds; float* kernel_ms;
     bool warp;
     int rect[4];
@@ -208,7 +208,7 @@ int run_host_pipeline(PipeJob job)
     if (dev < 0 || dev >= PIPE_MAX_DEVICES) { set_error("%s: device %d out of range", job.name, dev); return MF_ERR_INVALID_ARG; }
     PipeCache& pc = g_pipe[dev];
     std::lock_guard<std::mutex> cache_guard(pc.lock);
-    const size_t fb = (size_t)W * H * (size_t)job.channels;           // (chunks are sized by bytes: ~3 x the frames per chunk for grey)
+    const size_t fb = (size_t)W * H * px_bytes(job.px);                // (chunks are sized by bytes: ~3 x the frames per chunk for grey)
     if ((out && ranges_overlap(frames, out, n, fb)) || (cropped && ranges_overlap(frames, cropped, n, fb)) ||
         (out && cropped && ranges_overlap(out, cropped, n, fb))) {
         set_error("%s: input and output frames overlap in memory (in-place operation is not supported)", job.name);
@@ -274,7 +274,6 @@ int run_host_pipeline(PipeJob job)
     // every chunk's warp directly: the tables of the whole clip are built piece by piece into one scratch table (O(piece) memory) and
     // scanned.  A degenerate mesh or an empty rectangle (cv2.resize would fail on an empty source) ends the call here: no frame has
     // been uploaded, no output page touched.
-    const uint32_t border = job.border;
     int32_t status = 0;
     int32_t rect[4] = { job.rect[0], job.rect[1], job.rect[2], job.rect[3] };
     if (job.warp) {
@@ -413,8 +412,7 @@ int run_host_pipeline(PipeJob job)
             const TableView tv = table_view(pc.table.p, m, W, H, R, C);
             rc = launch_cell_table(d_unstab + v2 * i0, d_stab + v2 * i0, m, W, H, R, C, tv, d_crop + 4 * (size_t)i0, (int32_t*)pc.status.p, pc.compute);
             if (rc == MF_OK)
-                rc = job.channels == 1 ? launch_warp_u8c1(slot_in(k), slot_out(k), tv, m, W, H, R, C, (uint8_t)border, d_crop + 4 * (size_t)i0, pc.compute)
-                                       : launch_warp(slot_in(k), slot_out(k), tv, m, W, H, R, C, border, d_crop + 4 * (size_t)i0, pc.compute);
+                rc = launch_warp(job.px, slot_in(k), slot_out(k), tv, m, W, H, R, C, job.border, d_crop + 4 * (size_t)i0, pc.compute);
             if (rc != MF_OK) { sh.fail(hipErrorUnknown, "kernel launch"); break; }
             if (out) {
                 e = hipEventRecord(warp_done[k], pc.compute);
@@ -423,9 +421,8 @@ int run_host_pipeline(PipeJob job)
             }
         }
         if (cropped) {                                     // _crop_frames (mfs.py:1111-1157) of this chunk, its source still in the caches
-            const auto resize = job.channels == 1 ? launch_crop_resize_u8c1 : launch_crop_resize;
-            rc = job.warp ? resize(slot_out(k), slot_in(k), m, W, H, rect[0], rect[1], rect[2], rect[3], pc.work.p, pc.compute)
-                          : resize(slot_in(k), slot_out(k), m, W, H, rect[0], rect[1], rect[2], rect[3], pc.work.p, pc.compute);
+            rc = job.warp ? launch_crop_resize(job.px, slot_out(k), slot_in(k), m, W, H, rect[0], rect[1], rect[2], rect[3], pc.work.p, pc.compute)
+                          : launch_crop_resize(job.px, slot_in(k), slot_out(k), m, W, H, rect[0], rect[1], rect[2], rect[3], pc.work.p, pc.compute);
             if (rc != MF_OK) { sh.fail(hipErrorUnknown, "kernel launch"); break; }
             e = hipEventRecord(resize_done[k], pc.compute);
             if (e != hipSuccess) { sh.fail(e, "hipEventRecord"); break; }
@@ -473,18 +470,18 @@ int run_host_pipeline(PipeJob job)
 }
 
 int warp_host_frames(const uint8_t* const* frames, uint8_t* const* out, uint8_t* const* cropped, const double* unstab, const double* stab,
-                     int n, int W, int H, int R, int C, const uint8_t border_bgr[3], int32_t* crop, int32_t* bounds, float* kernel_ms,
-                     int channels = 3)
+                     int n, int W, int H, int R, int C, const uint8_t* border, int32_t* crop, int32_t* bounds, float* kernel_ms,
+                     Px px = Px::U8C3)
 {
     PipeJob job{};
     job.frames = frames; job.out = out; job.cropped = cropped; job.unstab = unstab; job.stab = stab;
     job.n = n; job.W = W; job.H = H; job.R = R; job.C = C;
-    job.channels = channels;
-    job.border = channels == 1 ? (uint32_t)border_bgr[0] : (uint32_t)border_bgr[0] | ((uint32_t)border_bgr[1] << 8) | ((uint32_t)border_bgr[2] << 16);
+    job.px = px;
+    job.border = pack_border(px, border);
     job.crop = crop; job.bounds = bounds; job.kernel_ms = kernel_ms;
     job.warp = true;
     job.rect[0] = 0; job.rect[1] = 0; job.rect[2] = W - 1; job.rect[3] = H - 1;
-    if (channels == 1) job.name = cropped ? "mf_warp_crop_u8c1_host_frames" : "mf_warp_u8c1_host_frames";
+    if (px == Px::U8C1) job.name = cropped ? "mf_warp_crop_u8c1_host_frames" : "mf_warp_u8c1_host_frames";
     else job.name = cropped ? "mf_warp_crop_u8c3_host_frames" : "mf_warp_u8c3_host";
     return run_host_pipeline(job);
 }
@@ -535,7 +532,7 @@ int mf_warp_u8c3_host(const uint8_t* frames, uint8_t* out, const double* unstab,
     return warp_host_frames(in.data(), outp.data(), nullptr, unstab, stab, n, W, H, R, C, border_bgr, crop, nullptr, kernel_ms);
 }
 
-static int crop_resize_host(const char* name, int channels, const uint8_t* const* frames, uint8_t* const* cropped, int n, int W, int H,
+static int crop_resize_host(const char* name, Px px, const uint8_t* const* frames, uint8_t* const* cropped, int n, int W, int H,
                             int left, int top, int right, int bottom, float* kernel_ms)
 {
     if (!frames || !cropped) { set_error("%s: null pointer", name); return MF_ERR_INVALID_ARG; }
@@ -550,7 +547,7 @@ static int crop_resize_host(const char* name, int channels, const uint8_t* const
     PipeJob job{};
     job.frames = frames; job.cropped = cropped;
     job.n = n; job.W = W; job.H = H; job.R = 1; job.C = 1;
-    job.channels = channels;
+    job.px = px;
     job.kernel_ms = kernel_ms;
     job.warp = false;
     job.rect[0] = left; job.rect[1] = top; job.rect[2] = right; job.rect[3] = bottom;
@@ -561,16 +558,15 @@ static int crop_resize_host(const char* name, int channels, const uint8_t* const
 int mf_crop_resize_u8c3_host_frames(const uint8_t* const* frames, uint8_t* const* cropped, int n, int W, int H, int left, int top,
                                     int right, int bottom, float* kernel_ms)
 {
-    return crop_resize_host("mf_crop_resize_u8c3_host_frames", 3, frames, cropped, n, W, H, left, top, right, bottom, kernel_ms);
+    return crop_resize_host("mf_crop_resize_u8c3_host_frames", Px::U8C3, frames, cropped, n, W, H, left, top, right, bottom, kernel_ms);
 }
 
 int mf_warp_u8c1_host_frames(const uint8_t* const* frames, uint8_t* const* out, const double* unstab, const double* stab, int n,
                              int W, int H, int R, int C, uint8_t border, int32_t* crop, float* kernel_ms)
 {
     if (!out) { set_error("mf_warp_u8c1_host_frames: null pointer"); return MF_ERR_INVALID_ARG; }
-    const uint8_t b[3] = { border, 0, 0 };
-    if (const int rc = check_host_args("mf_warp_u8c1_host_frames", frames, out, nullptr, unstab, stab, n, W, H, R, C, b, crop)) return rc;
-    return warp_host_frames(frames, out, nullptr, unstab, stab, n, W, H, R, C, b, crop, nullptr, kernel_ms, 1);
+    if (const int rc = check_host_args("mf_warp_u8c1_host_frames", frames, out, nullptr, unstab, stab, n, W, H, R, C, &border, crop)) return rc;
+    return warp_host_frames(frames, out, nullptr, unstab, stab, n, W, H, R, C, &border, crop, nullptr, kernel_ms, Px::U8C1);
 }
 
 int mf_warp_crop_u8c1_host_frames(const uint8_t* const* frames, uint8_t* const* out, uint8_t* const* cropped, const double* unstab,
@@ -578,15 +574,14 @@ int mf_warp_crop_u8c1_host_frames(const uint8_t* const* frames, uint8_t* const* 
                                   int32_t bounds[4], float* kernel_ms)
 {
     if (!cropped || !bounds) { set_error("mf_warp_crop_u8c1_host_frames: null pointer"); return MF_ERR_INVALID_ARG; }
-    const uint8_t b[3] = { border, 0, 0 };
-    if (const int rc = check_host_args("mf_warp_crop_u8c1_host_frames", frames, out, cropped, unstab, stab, n, W, H, R, C, b, crop)) return rc;
-    return warp_host_frames(frames, out, cropped, unstab, stab, n, W, H, R, C, b, crop, bounds, kernel_ms, 1);
+    if (const int rc = check_host_args("mf_warp_crop_u8c1_host_frames", frames, out, cropped, unstab, stab, n, W, H, R, C, &border, crop)) return rc;
+    return warp_host_frames(frames, out, cropped, unstab, stab, n, W, H, R, C, &border, crop, bounds, kernel_ms, Px::U8C1);
 }
 
 int mf_crop_resize_u8c1_host_frames(const uint8_t* const* frames, uint8_t* const* cropped, int n, int W, int H, int left, int top,
                                     int right, int bottom, float* kernel_ms)
 {
-    return crop_resize_host("mf_crop_resize_u8c1_host_frames", 1, frames, cropped, n, W, H, left, top, right, bottom, kernel_ms);
+    return crop_resize_host("mf_crop_resize_u8c1_host_frames", Px::U8C1, frames, cropped, n, W, H, left, top, right, bottom, kernel_ms);
 }
 
 int mf_host_cache_release(void)

@@ -222,6 +222,23 @@ inline bool make_tile_order(int tiles_x, int tiles_y, int n, TileOrder& o)
 
 
 
+// Pixel format of a frame stack: the _u8c3 / _u16c3 / _u8c1 calls of include/meshflow_hip.h.  Every layer takes the format as this one
+// parameter; a new format is a row here plus its kernels.
+enum class Px { U8C3, U16C3, U8C1 };
+constexpr int px_channels(Px p) { return p == Px::U8C1 ? 1 : 3; }
+constexpr int px_sample_bytes(Px p) { return p == Px::U16C3 ? 2 : 1; }
+constexpr int px_bytes(Px p) { return px_channels(p) * px_sample_bytes(p); }
+constexpr const char* px_name(Px p) { return p == Px::U8C3 ? "u8c3" : p == Px::U16C3 ? "u16c3" : "u8c1"; }
+// The border colour as the warp kernels take it, from the caller's px_channels(p) samples: B | G << 8 | R << 16 (u8c3),
+// B | G << 16 | R << 32 (u16c3), the byte (u8c1).
+inline uint64_t pack_border(Px p, const void* samples)
+{
+    uint64_t v = 0;
+    for (int c = 0; c < px_channels(p); ++c)
+        v |= (p == Px::U16C3 ? (uint64_t)((const uint16_t*)samples)[c] : (uint64_t)((const uint8_t*)samples)[c]) << (8 * px_sample_bytes(p) * c);
+    return v;
+}
+
 // Launch constants of the warp kernel (host-made: the kernel's scalar unit has none to spare).  Grid = (8 * per_xcd, frames): the
 // workgroups of a frame go to the 8 XCDs round-robin by blockIdx.x, workgroup L takes footprint (L % 8) * per_xcd + L / 8, so
 // every XCD sweeps one contiguous eighth of each frame in raster order.  All table offsets are 32-bit: launch_warp cuts a clip
@@ -242,29 +259,32 @@ int launch_cell_table(const double* unstab, const double* stab, int n, int W, in
                       const TableView& tv, int32_t* crop, int32_t* status, hipStream_t st, bool first_of_table = true);
 // (first_of_table: this launch also resets the table's clip-level rectangle -- false for the later frame ranges of a table that is
 // built in several launches)
-int launch_warp(const uint8_t* frames, uint8_t* out, const TableView& tv, int n, int W, int H, int R, int C,
-                uint32_t border, int32_t* crop, hipStream_t st);
+// warp.hip: the mesh warp of n frames of format px (border: pack_border's word), cut into launches of at most 65,535 frames
+int launch_warp(Px px, const void* frames, void* out, const TableView& tv, int n, int W, int H, int R, int C,
+                uint64_t border, int32_t* crop, hipStream_t st);
+// One launch of launch_warp: frames f0 .. f0 + m - 1, every pointer already advanced to frame f0.
+struct WarpRange {
+    const FootPlan* plan; const FootRegion* regions; const double* records; const float* edges;
+    const void* frames; void* out; int32_t* crop; int32_t* bounds; int m;
+};
+void launch_warp8c1_range(const WarpGeom& g, const WarpRange& r, int W, int H, int C, uint32_t border, bool stage, hipStream_t st);  // warp_c1.hip
 int launch_crop_scan(const TableView& tv, int n, int W, int H, int R, int C, int32_t* crop, hipStream_t st);
-// (uint16 frames: warp.hip's warp16_footprint; border16 = B | G << 16 | R << 32)
-int launch_warp_u16(const uint16_t* frames, uint16_t* out, const TableView& tv, int n, int W, int H, int R, int C,
-                    uint64_t border16, int32_t* crop, hipStream_t st);
-// (single-channel uint8 frames: warp.hip's warp8c1_footprint; one border byte)
-int launch_warp_u8c1(const uint8_t* frames, uint8_t* out, const TableView& tv, int n, int W, int H, int R, int C,
-                     uint8_t border, int32_t* crop, hipStream_t st);
 int check_d16_zero_fill(hipStream_t st);          // warp.hip: one-time device check the byte-tap kernels rely on
 int launch_selftest_recip(unsigned long long n, unsigned long long seed, unsigned long long* d_mismatches, hipStream_t st);
 int launch_selftest_fast64(unsigned long long n, unsigned long long seed, unsigned long long* d_counters, hipStream_t st, unsigned long long* d_margin = nullptr);
 size_t crop_resize_workspace_bytes(int W, int H);
-int launch_crop_resize(const uint8_t* frames, uint8_t* out, int n, int W, int H, int left, int top, int right,
+// resize.hip: every check of a crop-resize call, then the format's tables and kernel
+int launch_crop_resize(Px px, const void* frames, void* out, int n, int W, int H, int left, int top, int right,
                        int bottom, void* work, hipStream_t st);
-int launch_crop_resize_u16(const uint16_t* frames, uint16_t* out, int n, int W, int H, int left, int top, int right,
-                           int bottom, void* work, hipStream_t st);      // resize16.hip: the same workspace
-int launch_crop_resize_u8c1(const uint8_t* frames, uint8_t* out, int n, int W, int H, int left, int top, int right,
-                            int bottom, void* work, hipStream_t st);     // resize_c1.hip: the same tables and workspace
-// resize.hip: the checks of every crop-resize call, then resize_tables_kernel's tables for the rectangle in `work` (W x-entries, then H
-// y-entries; x: ofs = sx, w = 16 a0 | 16 a1 << 16 (pre-scaled, see resize_kernel);  y: ofs = sy0 | sy1 << 16, w = b0 | b1 << 16)
+// resize_tables_kernel's tables (u8c3, u8c1) for the rectangle in `work` (W x-entries, then H y-entries; x: ofs = sx, w = 16 a0 | 16 a1 << 16
+// (pre-scaled, see resize_kernel);  y: ofs = sy0 | sy1 << 16, w = b0 | b1 << 16)
 struct ResizeTab { int32_t ofs; uint32_t w; };
-int launch_resize_tables(const char* name, int n, int W, int H, int left, int top, int right, int bottom, void* work, hipStream_t st);
+// The kernel launches of the other formats, behind launch_crop_resize's checks: resize16.hip (its own tables in the same workspace),
+// resize_c1.hip (resize.hip's tables, already built)
+int launch_resize16(const uint16_t* frames, uint16_t* out, int W, int H, int left, int top, int right, int bottom, const TileOrder& order,
+                    void* work, hipStream_t st);
+int launch_resize8c1(const uint8_t* frames, uint8_t* out, int n, int W, int H, int left, int top, int cw, const void* work,
+                     const TileOrder& order, hipStream_t st);
 size_t vertex_motion_workspace_bytes(int total_features, int max_per_pair, int P, int R, int C);
 int launch_vertex_motion(const double* early, const double* late, const int32_t* offsets, const double* hom, int P,
                          int total_features, int max_per_pair, int W, int H, int R, int C, int ell_rows, int ell_cols,

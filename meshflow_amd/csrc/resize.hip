@@ -292,17 +292,8 @@ __global__ __launch_bounds__(64 * kWaves) void resize_kernel(const uint8_t* __re
 
 size_t crop_resize_workspace_bytes(int W, int H) { return (size_t)(W + H) * sizeof(ResizeTab); }
 
-int launch_resize_tables(const char* name, int n, int W, int H, int left, int top, int right, int bottom, void* work, hipStream_t st)
+static int launch_resize_tables(int W, int H, int left, int top, int right, int bottom, void* work, hipStream_t st)
 {
-    if (n <= 0 || W < 1 || H < 1 || W > 32767 || H > 32767) {           // (any number of frames that make_tile_order can count: 2^31 tiles)
-        set_error("%s: unsupported shape n=%d W=%d H=%d", name, n, W, H);
-        return MF_ERR_INVALID_ARG;
-    }
-    if (left < 0 || top < 0 || right >= W || bottom >= H || right < left || bottom < top) {
-        set_error("%s: empty or out-of-frame crop rectangle (%d, %d, %d, %d) for %dx%d (cv2.resize would "
-                  "fail on an empty source)", name, left, top, right, bottom, W, H);
-        return MF_ERR_INVALID_ARG;
-    }
     const int cw = right - left + 1, ch = bottom - top + 1;
     const double scale_x = 1.0 / ((double)W / (double)cw), scale_y = 1.0 / ((double)H / (double)ch);
     ResizeTab* xtab = (ResizeTab*)work;
@@ -312,21 +303,36 @@ int launch_resize_tables(const char* name, int n, int W, int H, int left, int to
     return hip_fail(hipGetLastError(), "resize_tables_kernel launch");
 }
 
-int launch_crop_resize(const uint8_t* frames, uint8_t* out, int n, int W, int H, int left, int top, int right, int bottom,
+int launch_crop_resize(Px px, const void* frames, void* out, int n, int W, int H, int left, int top, int right, int bottom,
                        void* work, hipStream_t st)
 {
-    if (const int rc = check_d16_zero_fill(st)) return rc;
-    if (const int rc = launch_resize_tables("mf_crop_resize_u8c3", n, W, H, left, top, right, bottom, work, st)) return rc;
-    const int cw = right - left + 1;
-    const ResizeTab* xtab = (const ResizeTab*)work;
-    const ResizeTab* ytab = xtab + W;
-    TileOrder order;
-    if (!make_tile_order((W + 255) / 256, (H + kWaves * kRows - 1) / (kWaves * kRows), n, order)) {
-        set_error("mf_crop_resize_u8c3: too many tiles");
+    if (px == Px::U8C3)
+        if (const int rc = check_d16_zero_fill(st)) return rc;
+    const char* name = px_name(px);
+    if (n <= 0 || W < 1 || H < 1 || W > 32767 || H > 32767) {           // (any number of frames that make_tile_order can count: 2^31 tiles)
+        set_error("mf_crop_resize_%s: unsupported shape n=%d W=%d H=%d", name, n, W, H);
         return MF_ERR_INVALID_ARG;
     }
-    hipLaunchKernelGGL(resize_kernel, dim3(order.per_xcd * 8u), dim3(64 * kWaves), 0, st, frames, out, n, W, H, left, top, cw, xtab, ytab,
-                       order);
+    if (left < 0 || top < 0 || right >= W || bottom >= H || right < left || bottom < top) {
+        set_error("mf_crop_resize_%s: empty or out-of-frame crop rectangle (%d, %d, %d, %d) for %dx%d (cv2.resize would "
+                  "fail on an empty source)", name, left, top, right, bottom, W, H);
+        return MF_ERR_INVALID_ARG;
+    }
+    // tiles: 256 pixels of kWaves * kRows output rows (resize16_kernel: of one row)
+    const int tile_rows = px == Px::U16C3 ? 1 : kWaves * kRows;
+    TileOrder order;
+    if (!make_tile_order((W + 255) / 256, (H + tile_rows - 1) / tile_rows, n, order)) {
+        set_error("mf_crop_resize_%s: too many tiles", name);
+        return MF_ERR_INVALID_ARG;
+    }
+    if (px == Px::U16C3) return launch_resize16((const uint16_t*)frames, (uint16_t*)out, W, H, left, top, right, bottom, order, work, st);
+    if (const int rc = launch_resize_tables(W, H, left, top, right, bottom, work, st)) return rc;
+    const int cw = right - left + 1;
+    if (px == Px::U8C1) return launch_resize8c1((const uint8_t*)frames, (uint8_t*)out, n, W, H, left, top, cw, work, order, st);
+    const ResizeTab* xtab = (const ResizeTab*)work;
+    const ResizeTab* ytab = xtab + W;
+    hipLaunchKernelGGL(resize_kernel, dim3(order.per_xcd * 8u), dim3(64 * kWaves), 0, st, (const uint8_t*)frames, (uint8_t*)out, n, W, H, left, top,
+                       cw, xtab, ytab, order);
     return hip_fail(hipGetLastError(), "resize_kernel launch");
 }
 

@@ -81,23 +81,10 @@ __global__ __launch_bounds__(256) void resize16_kernel(const uint16_t* __restric
     d[2] = (uint16_t)o[2];
 }
 
-int launch_crop_resize_u16(const uint16_t* frames, uint16_t* out, int n, int W, int H, int left, int top, int right, int bottom,
-                           void* work, hipStream_t st)
+// launch_crop_resize's launches for uint16 frames (shape, rectangle and tile count already checked there)
+int launch_resize16(const uint16_t* frames, uint16_t* out, int W, int H, int left, int top, int right, int bottom, const TileOrder& order,
+                    void* work, hipStream_t st)
 {
-    if (n <= 0 || W < 1 || H < 1 || W > 32767 || H > 32767) {
-        set_error("mf_crop_resize_u16c3: unsupported shape n=%d W=%d H=%d", n, W, H);
-        return MF_ERR_INVALID_ARG;
-    }
-    if (left < 0 || top < 0 || right >= W || bottom >= H || right < left || bottom < top) {
-        set_error("mf_crop_resize_u16c3: empty or out-of-frame crop rectangle (%d, %d, %d, %d) for %dx%d (cv2.resize would "
-                  "fail on an empty source)", left, top, right, bottom, W, H);
-        return MF_ERR_INVALID_ARG;
-    }
-    TileOrder order;
-    if (!make_tile_order((W + 255) / 256, H, n, order)) {
-        set_error("mf_crop_resize_u16c3: too many tiles");
-        return MF_ERR_INVALID_ARG;
-    }
     const int cw = right - left + 1, ch = bottom - top + 1;
     const double scale_x = 1.0 / ((double)W / (double)cw), scale_y = 1.0 / ((double)H / (double)ch);
     Resize16Tab* xtab = (Resize16Tab*)work;

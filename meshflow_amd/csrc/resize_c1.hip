@@ -1,5 +1,5 @@
 // _crop_frames (mfs.py:1111-1157) for single-channel uint8 frames: crop to the inclusive rectangle, resize back to (W, H) with
-// cv2.resize INTER_LINEAR.  The tables are resize.hip's (launch_resize_tables: the same resize_tables_kernel, the same workspace); this
+// cv2.resize INTER_LINEAR.  The tables are resize.hip's (the same resize_tables_kernel, the same workspace, built by launch_crop_resize); this
 // translation unit adds only the kernel, so resize.hip's code object stays what it is (tools/isa_compare.py).
 #include "mf_common.h"
 
@@ -129,18 +129,12 @@ __global__ __launch_bounds__(64 * kWaves) void resize8c1_kernel(const uint8_t* _
     }
 }
 
-int launch_crop_resize_u8c1(const uint8_t* frames, uint8_t* out, int n, int W, int H, int left, int top, int right, int bottom,
-                            void* work, hipStream_t st)
+// launch_crop_resize's launch for single-channel frames (checks done and resize.hip's tables built there)
+int launch_resize8c1(const uint8_t* frames, uint8_t* out, int n, int W, int H, int left, int top, int cw, const void* work,
+                     const TileOrder& order, hipStream_t st)
 {
-    if (const int rc = launch_resize_tables("mf_crop_resize_u8c1", n, W, H, left, top, right, bottom, work, st)) return rc;
-    const int cw = right - left + 1;
     const ResizeTab* xtab = (const ResizeTab*)work;
     const ResizeTab* ytab = xtab + W;
-    TileOrder order;
-    if (!make_tile_order((W + 255) / 256, (H + kWaves * kRows - 1) / (kWaves * kRows), n, order)) {
-        set_error("mf_crop_resize_u8c1: too many tiles");
-        return MF_ERR_INVALID_ARG;
-    }
     hipLaunchKernelGGL(resize8c1_kernel, dim3(order.per_xcd * 8u), dim3(64 * kWaves), 0, st, frames, out, n, W, H, left, top, cw, xtab, ytab,
                        order);
     return hip_fail(hipGetLastError(), "resize8c1_kernel launch");

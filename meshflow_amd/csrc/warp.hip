@@ -892,18 +892,18 @@ __device__ unsigned long long mf_exp_phase[8];
 #define MF_EXP_STAMP(var)
 #endif
 
-// STAGE_OK: the clip is 4-byte aligned, so the plan's STAGED windows can be copied by 16-byte global->LDS loads (always the case
-// for buffers from hipMalloc / torch; the other instantiation ignores the windows).
+// PX: the pixel format.  STAGE: the clip is 4-byte aligned, so the plan's STAGED windows can be copied by 16-byte global->LDS loads (always
+// the case for buffers from hipMalloc / torch; the other instantiation ignores the windows).
 // SCAN: the crop-boundary scan ALONE (crop_scan_kernel below): the same ownership and coordinate code for footprint t of frame f,
 // then only the four edge tests of mfs.py:1075-1098 -- no window, no taps, no blend, no store.  The certified paths (hot, pair,
 // multi) are compiled out: their footprints cannot set a crop flag (MF_REGION_DEEP / MF_REGION_NOFLAG) and are never handed in.
-// U16: the same ownership and coordinates for uint16 BGR frames (warp16_kernel): `frames` / `out` then point to uint16 samples, the border
-// colour is `border16` (B | G << 16 | R << 32) and the pixels go through remap_store_u16 at the end of the general path -- the plan's staged
-// windows are sized for 3-byte pixels, so the U16 instantiation has no staged path (STAGE_OK = false).
-// GREY: the same for single-channel uint8 frames (warp8c1_footprint): `frames` / `out` hold W H bytes per frame, the border is the low byte
-// of `border`, and the pixels go through remap_store_u8c1.  GREY_STAGE: the clip is 4-byte aligned -- the plan's STAGED windows (not the
-// BORDER ones) are then re-cut for 1-byte pixels (GreyWindow) and copied to LDS at the start, like warp_kernel's.
-template <bool STAGE_OK, bool SCAN, bool U16 = false, bool GREY = false, bool GREY_STAGE = false>
+// PX = Px::U16C3: the same ownership and coordinates for uint16 BGR frames (warp16_footprint): `frames` / `out` then point to uint16 samples,
+// the border colour is `border16` (B | G << 16 | R << 32) and the pixels go through remap_store_u16 at the end of the general path -- the
+// plan's staged windows are sized for 3-byte pixels, so this instantiation has no staged path (STAGE = false).
+// PX = Px::U8C1: the same for single-channel uint8 frames (warp8c1_footprint): `frames` / `out` hold W H bytes per frame, the border is the
+// low byte of `border`, and the pixels go through remap_store_u8c1.  With STAGE (GREY_STAGE below) the plan's STAGED windows (not the
+// BORDER ones) are re-cut for 1-byte pixels (GreyWindow) and copied to LDS at the start, like warp_kernel's.
+template <Px PX, bool STAGE, bool SCAN>
 __device__ __forceinline__ void footprint_body(const uint32_t f, const uint32_t t, const FootPlan* __restrict__ plan, const FootRegion* __restrict__ regions,
                                                const WarpGeom& g, const uint8_t* __restrict__ frames,
                                                const double* __restrict__ records, uint8_t* __restrict__ out,
@@ -911,9 +911,11 @@ __device__ __forceinline__ void footprint_body(const uint32_t f, const uint32_t 
                                                int H, int C, uint32_t border, int32_t* __restrict__ crop, int32_t* __restrict__ clip,
                                                uint64_t border16 = 0)
 {
-    static_assert(!U16 || (!STAGE_OK && !SCAN), "the uint16 warp takes its taps from global memory");
-    static_assert(!GREY || (!STAGE_OK && !SCAN && !U16), "the grey warp stages its own window");
-    static_assert(!GREY_STAGE || GREY, "GREY_STAGE is a variant of the grey warp");
+    static_assert(!SCAN || (PX == Px::U8C3 && !STAGE), "the crop scan runs the unstaged BGR body");
+    static_assert(PX != Px::U16C3 || !STAGE, "the uint16 warp takes its taps from global memory");
+    // BGR_STAGE: the uint8 BGR warp of a 4-byte aligned clip -- the staged window and the certified paths (hot, border, pair, multi)
+    constexpr bool BGR_STAGE = PX == Px::U8C3 && STAGE && !SCAN;
+    constexpr bool U16 = PX == Px::U16C3, GREY = PX == Px::U8C1, GREY_STAGE = GREY && STAGE;
     // inverse homographies of the footprint's candidate cells: [entry][Hi0..Hi8, pad] (80-byte rows)
     __shared__ __attribute__((aligned(16))) double s_hi[1][9][10];                // row 8: the "no cell" matrix, see OWN_NONE
     // source region of the footprint: MF_STAGE_ROWS rows of MF_STAGE_PITCH bytes (+ slack for the third dword of the last tap)
@@ -935,7 +937,7 @@ __device__ __forceinline__ void footprint_body(const uint32_t f, const uint32_t 
     typedef uint32_t spec2_t __attribute__((ext_vector_type(2)));
     spec16_t hg_lo;
     spec2_t hg_hi;
-    // ONLY in the instantiation that has a hot path (STAGE_OK && !SCAN).  Anywhere else the registers would be dead right behind the asm
+    // ONLY in the instantiation that has a hot path (BGR_STAGE).  Anywhere else the registers would be dead right behind the asm
     // statement, the compiler would hand them to the plan words' loads two lines further down, and -- scalar loads return out of order
     // -- whichever load lands last would win: a footprint of a frame stack that is not 4-byte aligned (odd frame sizes cut into frame
     // ranges: warp_kernel<false>) then ran on a few bytes of some cell's matrix instead of its plan about once in 200 launches and left
@@ -943,7 +945,7 @@ __device__ __forceinline__ void footprint_body(const uint32_t f, const uint32_t 
 #ifndef MF_GUARD_SELFTEST
     // (... and not in the timing-only builds that compile the hot path out -- MF_EXP_SKIP & (1 | 32 | 64) --: the same hazard, found there as a GPU
     // memory fault and, from the disassembly alone, by tools/isa_guard.py)
-    constexpr bool SPECULATE = STAGE_OK && !SCAN && !(MF_EXP_SKIP & (1 | 32 | 64));
+    constexpr bool SPECULATE = BGR_STAGE && !(MF_EXP_SKIP & (1 | 32 | 64));
 #else       // (tests/test_isa_guard.py builds THIS on purpose -- round 5's bug, the load in the instantiation without a hot path -- to see the guard fail)
     constexpr bool SPECULATE = !SCAN;
 #endif
@@ -969,7 +971,7 @@ __device__ __forceinline__ void footprint_body(const uint32_t f, const uint32_t 
     const uint64_t region = *(cword2_t)rw;                               // both words in one load (the second is needed right after the first)
     const uint32_t rg = (uint32_t)region, src_dwords = (uint32_t)(region >> 32);
     const uint8_t* __restrict__ src = frames + (uint64_t)f * g.frame_bytes;
-    const bool staged = STAGE_OK && !SCAN && (rg & MF_REGION_STAGED) != 0;
+    const bool staged = BGR_STAGE && (rg & MF_REGION_STAGED) != 0;
     if (!SCAN && (MF_EXP_SKIP & 32)) { asm volatile("" :: "s"(pv.x), "s"(pv.y), "s"(pv.z), "s"(pv.w), "s"(rg), "s"(src_dwords)); return; }
 #ifdef MF_EXP_PHASES
     asm volatile("s_waitcnt lgkmcnt(0)" :: "s"(pv.x), "s"(pv.w), "s"(rg) : "memory");
@@ -1052,12 +1054,12 @@ __device__ __forceinline__ void footprint_body(const uint32_t f, const uint32_t 
     // taps are addressed by absolute LDS byte address (= LDS_PITCH iy + 3 ix - lds_origin): the window base is folded in
     const uint32_t lds_origin = (rg & MF_REGION_ORIGIN_MASK) - (uint32_t)(uintptr_t)&s_src[0];
     const crec_t frec = (crec_t)(uintptr_t)(reinterpret_cast<const uint8_t*>(records) + f * g.rec_frame_bytes);
-    const bool compact = STAGE_OK && !SCAN && (rg & MF_REGION_COMPACT) != 0;
+    const bool compact = BGR_STAGE && (rg & MF_REGION_COMPACT) != 0;
     const int y = ya + (int)row;
     const int x0 = xa + (lane & 7) * 4;                                  // first of this lane's 4 pixels
     const double xs0 = (double)x0, yy = (double)y;
 
-    if (STAGE_OK && !SCAN && (pv.x & (MF_PLAN_HOT << 16)) != 0) {
+    if (BGR_STAGE && (pv.x & (MF_PLAN_HOT << 16)) != 0) {
         // The plan certifies everything (~2/3 of the footprints at config-2 geometry): ONE cell owns all 256 pixels, its
         // denominator allows the trimmed reciprocal (UNIT), the footprint lies inside the frame, its window is staged and every
         // tap is at least two pixels inside the frame (DEEP: no crop flag either).  Straight-line code, all lanes active.
@@ -1188,7 +1190,7 @@ __device__ __forceinline__ void footprint_body(const uint32_t f, const uint32_t 
         }
     }
 #ifndef MF_NO_BORDER
-    if (STAGE_OK && !SCAN && ((pv.x >> 16) & (MF_PLAN_VALID | MF_PLAN_BORDER)) == MF_PLAN_BORDER) {
+    if (BGR_STAGE && ((pv.x >> 16) & (MF_PLAN_VALID | MF_PLAN_BORDER)) == MF_PLAN_BORDER) {
         // BORDER path (the ring of footprints along the frame border of a stabilised clip, and the odd footprint a single cell only partly
         // covers: ~3 %): ONE candidate cell -- IN, or MIXED with one or two coded mask edges -- with a certified denominator; whole
         // footprint; every tap of a covered pixel lies in the staged window or on the ring of pixels just outside the frame, which is
@@ -1300,7 +1302,7 @@ __device__ __forceinline__ void footprint_body(const uint32_t f, const uint32_t 
         }
     }
 #endif
-    if (STAGE_OK && !SCAN && (pv.y & MF_PLAN_HOT) != 0) {
+    if (BGR_STAGE && (pv.y & MF_PLAN_HOT) != 0) {
         // Two cells share the footprint and the plan certifies the rest (a quarter of the footprints at config-2 geometry, 45 % at
         // config 3): the later cell wins wherever ONE of its mask edges passes -- one float32 fma per pixel -- and the other cell
         // owns what is left; denominators, window and interior as on the hot path.  Both inverse homographies go to LDS by
@@ -1414,7 +1416,7 @@ __device__ __forceinline__ void footprint_body(const uint32_t f, const uint32_t 
         }
     }
 
-    if (STAGE_OK && !SCAN && (pv.z & MF_PLAN_HOT) != 0) {
+    if (BGR_STAGE && (pv.z & MF_PLAN_HOT) != 0) {
         // Two to four cells, each MIXED one with one or two coded mask edges (the four cells around a mesh vertex, three of them, or a
         // pair the pair path did not take); window, interior and denominators certified, coverage not: a pixel that no listed cell
         // takes -- or one inside the float32 error band of an edge -- sends the wavefront to the general code.
@@ -1917,6 +1919,7 @@ __device__ __forceinline__ void footprint_body(const uint32_t f, const uint32_t 
     }
 }
 
+#ifndef MF_WARP_BODY_ONLY          // (warp_c1.hip includes this file for footprint_body and its helpers alone)
 // Launch constants of warp_kernel / crop_scan_kernel; returns the frames one launch may cover (the grid's y extent, and 32-bit byte
 // offsets into the plan -- 16 B per footprint -- and the records), 0 when a single frame is already too large.
 static uint32_t make_warp_geom(int W, int H, int R, int C, WarpGeom& g)
@@ -1943,7 +1946,6 @@ static uint32_t make_warp_geom(int W, int H, int R, int C, WarpGeom& g)
     return (uint32_t)per_launch;
 }
 
-#ifndef MF_WARP_BODY_ONLY          // (warp_c1.hip includes this file for footprint_body and its helpers alone)
 template <bool STAGE_OK>
 __global__ __launch_bounds__(64) MF_WARP_ATTR void warp_kernel(const FootPlan* __restrict__ plan, const FootRegion* __restrict__ regions,
                                                                WarpGeom g, const uint8_t* __restrict__ frames,
@@ -1967,7 +1969,7 @@ __global__ __launch_bounds__(64) MF_WARP_ATTR void warp_kernel(const FootPlan* _
     const uint32_t t = (blockIdx.x & 7u) * g.per_xcd + (blockIdx.x >> 3);
 #endif
     if (t >= g.per_frame) return;
-    footprint_body<STAGE_OK, false>(f, t, plan, regions, g, frames, records, out, edges, n, W, H, C, border, crop, clip);
+    footprint_body<Px::U8C3, STAGE_OK, false>(f, t, plan, regions, g, frames, records, out, edges, n, W, H, C, border, crop, clip);
 }
 
 // The mesh warp of uint16 frames: warp_kernel's footprint order and ownership / coordinate code (footprint_body's general path: the staged
@@ -1982,8 +1984,8 @@ __global__ __launch_bounds__(64) void warp16_footprint(const FootPlan* __restric
     const uint32_t f = blockIdx.y;
     const uint32_t t = ((blockIdx.x + f) & 7u) * g.per_xcd + (blockIdx.x >> 3);
     if (t >= g.per_frame) return;
-    footprint_body<false, false, true>(f, t, plan, regions, g, reinterpret_cast<const uint8_t*>(frames), records, reinterpret_cast<uint8_t*>(out),
-                                       edges, n, W, H, C, 0u, crop, clip, border16);
+    footprint_body<Px::U16C3, false, false>(f, t, plan, regions, g, reinterpret_cast<const uint8_t*>(frames), records, reinterpret_cast<uint8_t*>(out),
+                                            edges, n, W, H, C, 0u, crop, clip, border16);
 }
 
 // The crop-boundary scan WITHOUT the pixels (mfs.py:1075-1106 depends on the coordinate maps only, i.e. on the cell table): fills
@@ -2007,7 +2009,7 @@ __global__ __launch_bounds__(64) void crop_scan_kernel(const FootPlan* __restric
         todo &= todo - 1;
         const uint32_t fp = __builtin_amdgcn_readfirstlane(base + bit);
         const uint32_t f = fp / g.per_frame, t = fp - f * g.per_frame;
-        footprint_body<false, true>(f, t, plan, regions, g, nullptr, records, nullptr, edges, n, W, H, C, 0u, crop, clip);
+        footprint_body<Px::U8C3, false, true>(f, t, plan, regions, g, nullptr, records, nullptr, edges, n, W, H, C, 0u, crop, clip);
         __builtin_amdgcn_wave_barrier();             // (the next footprint reuses the wavefront's s_hi rows)
     }
 }
@@ -2174,71 +2176,49 @@ int check_d16_zero_fill(hipStream_t st)
     return MF_OK;
 }
 
-int launch_warp(const uint8_t* frames, uint8_t* out, const TableView& tv, int n, int W, int H, int R, int C,
-                uint32_t border, int32_t* crop, hipStream_t st)
+int launch_warp(Px px, const void* frames, void* out, const TableView& tv, int n, int W, int H, int R, int C,
+                uint64_t border, int32_t* crop, hipStream_t st)
 {
-    if (const int rc = check_d16_zero_fill(st)) return rc;
+    if (px == Px::U8C3)
+        if (const int rc = check_d16_zero_fill(st)) return rc;
     // (any number of frames: the launches below take at most 65,535 -- the grid's y extent -- at a time)
-    if (n <= 0 || W < 2 || H < 2 || W > 32767 || H > 32767 || R <= 0 || C <= 0 || R > MAX_MESH ||
-        C > MAX_MESH) {
-        set_error("mf_warp_u8c3: unsupported shape n=%d W=%d H=%d R=%d C=%d", n, W, H, R, C);
+    if (n <= 0 || W < 2 || H < 2 || W > 32767 || H > 32767 || R <= 0 || C <= 0 || R > MAX_MESH || C > MAX_MESH) {
+        set_error("mf_warp_%s: unsupported shape n=%d W=%d H=%d R=%d C=%d", px_name(px), n, W, H, R, C);
         return MF_ERR_INVALID_ARG;
     }
     WarpGeom g;
     uint64_t per_launch = make_warp_geom(W, H, R, C, g);
     if (per_launch == 0) {
-        set_error("mf_warp_u8c3: frame too large");
+        set_error("mf_warp_%s: frame too large", px_name(px));
         return MF_ERR_INVALID_ARG;
     }
     if (const char* e = getenv("MF_WARP_FRAMES_PER_LAUNCH")) {      // testing aid: forces the multi-launch split on small clips
         const long v = atol(e);
         if (v > 0 && (uint64_t)v < per_launch) per_launch = (uint64_t)v;
     }
-    // staging reads dword-aligned 16-byte chunks: needs a 4-byte aligned clip (W % 4 == 0 is checked by the plan)
-    const bool stage_ok = ((uintptr_t)frames & 3u) == 0;
+    // staging reads dword-aligned 16-byte chunks: needs a 4-byte aligned clip (W % 4 == 0 is checked by the plan); the plan's windows
+    // are sized for 1- and 3-byte pixels, so uint16 frames never stage
+    const bool stage = px != Px::U16C3 && ((uintptr_t)frames & 3u) == 0;
+    const size_t frame_bytes = (size_t)W * H * px_bytes(px);
     for (int f0 = 0; f0 < n; f0 += (int)per_launch) {
         const int m = n - f0 < (int)per_launch ? n - f0 : (int)per_launch;
+        const WarpRange r{ tv.plan + (size_t)f0 * g.per_frame, tv.regions + (size_t)f0 * g.per_frame,
+                           tv.records + (size_t)f0 * R * C * MF_CELL_DOUBLES, tv.edges + (size_t)f0 * R * C * MF_EDGE_FLOATS,
+                           (const uint8_t*)frames + f0 * frame_bytes, (uint8_t*)out + f0 * frame_bytes, crop + 4 * (size_t)f0, tv.bounds, m };
         const dim3 grid(g.per_xcd * 8u, (uint32_t)m);                  // one wavefront per 32 x 8 footprint
-        const uint8_t* fr = frames + (size_t)f0 * g.frame_bytes;
-        uint8_t* o = out + (size_t)f0 * g.frame_bytes;
-        const double* rec = tv.records + (size_t)f0 * R * C * MF_CELL_DOUBLES;
-        const float* ed = tv.edges + (size_t)f0 * R * C * MF_EDGE_FLOATS;
-        const FootPlan* pl = tv.plan + (size_t)f0 * g.per_frame;
-        const FootRegion* rgn = tv.regions + (size_t)f0 * g.per_frame;
-        if (stage_ok)
-            hipLaunchKernelGGL(warp_kernel<true>, grid, dim3(64), 0, st, pl, rgn, g, fr, rec, o, ed, m, W, H, C, border, crop + 4 * (size_t)f0, tv.bounds);
+        if (px == Px::U8C1)
+            launch_warp8c1_range(g, r, W, H, C, (uint32_t)border, stage, st);
+        else if (px == Px::U16C3)
+            hipLaunchKernelGGL(warp16_footprint, grid, dim3(64), 0, st, r.plan, r.regions, g, (const uint16_t*)r.frames, r.records, (uint16_t*)r.out,
+                               r.edges, m, W, H, C, border, r.crop, r.bounds);
+        else if (stage)
+            hipLaunchKernelGGL(warp_kernel<true>, grid, dim3(64), 0, st, r.plan, r.regions, g, (const uint8_t*)r.frames, r.records, (uint8_t*)r.out,
+                               r.edges, m, W, H, C, (uint32_t)border, r.crop, r.bounds);
         else
-            hipLaunchKernelGGL(warp_kernel<false>, grid, dim3(64), 0, st, pl, rgn, g, fr, rec, o, ed, m, W, H, C, border, crop + 4 * (size_t)f0, tv.bounds);
+            hipLaunchKernelGGL(warp_kernel<false>, grid, dim3(64), 0, st, r.plan, r.regions, g, (const uint8_t*)r.frames, r.records, (uint8_t*)r.out,
+                               r.edges, m, W, H, C, (uint32_t)border, r.crop, r.bounds);
     }
-    return hip_fail(hipGetLastError(), "warp_kernel launch");
-}
-
-int launch_warp_u16(const uint16_t* frames, uint16_t* out, const TableView& tv, int n, int W, int H, int R, int C,
-                    uint64_t border16, int32_t* crop, hipStream_t st)
-{
-    if (n <= 0 || W < 2 || H < 2 || W > 32767 || H > 32767 || R <= 0 || C <= 0 || R > MAX_MESH || C > MAX_MESH) {
-        set_error("mf_warp_u16c3: unsupported shape n=%d W=%d H=%d R=%d C=%d", n, W, H, R, C);
-        return MF_ERR_INVALID_ARG;
-    }
-    WarpGeom g;
-    uint64_t per_launch = make_warp_geom(W, H, R, C, g);
-    if (per_launch == 0) {
-        set_error("mf_warp_u16c3: frame too large");
-        return MF_ERR_INVALID_ARG;
-    }
-    if (const char* e = getenv("MF_WARP_FRAMES_PER_LAUNCH")) {      // testing aid, as in launch_warp
-        const long v = atol(e);
-        if (v > 0 && (uint64_t)v < per_launch) per_launch = (uint64_t)v;
-    }
-    const uint64_t frame_samples = 3ull * (uint64_t)W * (uint64_t)H;
-    for (int f0 = 0; f0 < n; f0 += (int)per_launch) {
-        const int m = n - f0 < (int)per_launch ? n - f0 : (int)per_launch;
-        const dim3 grid(g.per_xcd * 8u, (uint32_t)m);
-        hipLaunchKernelGGL(warp16_footprint, grid, dim3(64), 0, st, tv.plan + (size_t)f0 * g.per_frame, tv.regions + (size_t)f0 * g.per_frame, g,
-                           frames + (size_t)f0 * frame_samples, tv.records + (size_t)f0 * R * C * MF_CELL_DOUBLES, out + (size_t)f0 * frame_samples,
-                           tv.edges + (size_t)f0 * R * C * MF_EDGE_FLOATS, m, W, H, C, border16, crop + 4 * (size_t)f0, tv.bounds);
-    }
-    return hip_fail(hipGetLastError(), "warp16_footprint launch");
+    return hip_fail(hipGetLastError(), px == Px::U8C3 ? "warp_kernel launch" : px == Px::U16C3 ? "warp16_footprint launch" : "warp8c1_footprint launch");
 }
 
 int launch_crop_scan(const TableView& tv, int n, int W, int H, int R, int C, int32_t* crop, hipStream_t st)

@@ -3,6 +3,7 @@
 torch is used only for device memory, streams and (in `dist.py`) torch.distributed; every operator
 hands raw device pointers to libmeshflow_hip.so through the C ABI (`_lib.py`) on torch's current
 stream, so torch.cuda events and synchronisation see the kernels."""
+import collections
 import ctypes
 
 import numpy as np
@@ -30,42 +31,61 @@ def _need(t, dtype, name):
         raise ValueError(f'{name} must be contiguous')
 
 
-_FRAME_DTYPES = (torch.uint8, torch.uint16)
+def _border_samples(ctype, top, count):
+    """Border colour -> what a C call takes: clamp(round(v), 0, top) of the first `count` components -- the value itself, not scaled to 16
+    bits (cv2.remap's saturate_cast of borderValue; a 1-channel image uses borderValue[0]) -- as an array, or one value for count 1."""
+    def convert(border_bgr):
+        v = [int(np.clip(round(float(c)), 0, top)) for c in border_bgr[:count]]
+        return (ctype * count)(*v) if count > 1 else ctype(v[0])
+    return convert
 
 
-def _need_frames(t, name):
-    """Frames of either pixel type the device path takes (uint8 or uint16 BGR): returns the dtype."""
-    if isinstance(t, torch.Tensor) and t.dtype in _FRAME_DTYPES:
-        _need(t, t.dtype, name)
-        return t.dtype
-    _need(t, torch.uint8, name)          # (raises: not a tensor, or another dtype)
+# One row per pixel format of the device path: the frames it takes and the C calls that serve them (include/meshflow_hip.h).
+PixelFormat = collections.namedtuple('PixelFormat', 'dtype channels border warp warp_bounds warp_clip crop_resize')
 
 
-def _frame_shape(frames, dtype):
-    """(n, H, W, channels) of a frame stack: (n, H, W, 3) BGR of either pixel type, or (n, H, W) single-channel uint8 (channels 1).
-    Grey uint16 is refused naming its dtype; other shapes raise ValueError."""
-    if frames.dim() == 3:
-        if dtype != torch.uint8:
-            raise ValueError(f'single-channel frames must be uint8 (got {dtype}): (n, H, W) {dtype} frames are not supported')
-        n, H, W = frames.shape
-        return n, H, W, 1
-    if frames.dim() != 4 or frames.shape[3] != 3:
+def _row(name, dtype, channels, ctype, top):
+    calls = (getattr(_lib_, f'mf_{op}_{name}') for op in ('warp', 'warp_bounds', 'warp_clip', 'crop_resize'))
+    return PixelFormat(dtype, channels, _border_samples(ctype, top, channels), *calls)
+
+
+_FORMATS = (_row('u8c3', torch.uint8, 3, ctypes.c_uint8, 255),
+            _row('u16c3', torch.uint16, 3, ctypes.c_uint16, 65535),   # cv2.remap's / cv2.resize's 16U arithmetic
+            _row('u8c1', torch.uint8, 1, ctypes.c_uint8, 255))        # channel 0 of the BGR result of the frames repeated
+_FRAME_DTYPES = {f.dtype for f in _FORMATS}
+
+
+def pixel_format(dtype, shape):
+    """The format of frames of this dtype and shape: (n, H, W, 3) uint8 or uint16 BGR, or (n, H, W) uint8 single-channel.  Grey uint16
+    is refused naming its dtype; other shapes and dtypes raise ValueError."""
+    if len(shape) == 3:
+        channels = 1
+    elif len(shape) == 4 and shape[3] == 3:
+        channels = 3
+    else:
         raise ValueError('frames must be (n, H, W, 3), or (n, H, W) uint8')
-    n, H, W, ch = frames.shape
-    return n, H, W, ch
+    for f in _FORMATS:
+        if (f.dtype, f.channels) == (dtype, channels):
+            return f
+    if channels == 1:
+        raise ValueError(f'single-channel frames must be uint8 (got {dtype}): (n, H, W) {dtype} frames are not supported')
+    raise ValueError(f'frames must have dtype {torch.uint8}, got {dtype}')
 
 
-def _grey_border(border_bgr):
-    """The border byte of a single-channel warp: cv2.remap uses borderValue[0] for a 1-channel image, saturate_cast<uchar>."""
-    return ctypes.c_uint8(int(np.clip(round(float(border_bgr[0])), 0, 255)))
+def _frames_format(frames):
+    """Check a device frame stack and return its format."""
+    _need(frames, frames.dtype if isinstance(frames, torch.Tensor) and frames.dtype in _FRAME_DTYPES else torch.uint8, 'frames')
+    return pixel_format(frames.dtype, frames.shape)
 
 
-def _border(border_bgr, dtype):
-    """The border colour as the C call takes it: clamp(round(v), 0, 255) for uint8, clamp(round(v), 0, 65535) for uint16 -- the value
-    itself, not scaled to 16 bits (cv2.remap's saturate_cast of borderValue)."""
-    if dtype == torch.uint16:
-        return (ctypes.c_uint16 * 3)(*[int(np.clip(round(float(v)), 0, 65535)) for v in border_bgr[:3]])
-    return (ctypes.c_uint8 * 3)(*[int(np.clip(round(float(v)), 0, 255)) for v in border_bgr[:3]])
+def _out_for(frames, fmt, out):
+    """`out` (None: a new tensor) checked for `frames`; a single-channel one must have their shape."""
+    if out is None:
+        return torch.empty_like(frames)
+    _need(out, fmt.dtype, 'out')
+    if fmt.channels == 1 and out.shape != frames.shape:
+        raise ValueError('out must have the shape of frames')
+    return out
 
 
 def jacobi(b, taps, lam, inv_on, omega, iters, out=None):
@@ -165,35 +185,18 @@ def warp(frames, table, border_bgr=(0, 0, 255), out=None, bounds=None):
     uint8 single-channel frames (mf_warp_u8c1: channel 0 of the BGR warp of the frames repeated, border byte = border_bgr[0]).
     Returns the stabilized frames (the input's dtype); per-frame crop values accumulate in table.crop, the clip-level rectangle in
     `bounds` (the tensor `cell_table` was given) or, without one, in table.clip_bounds."""
-    dtype = _need_frames(frames, 'frames')
-    n, H, W, ch = _frame_shape(frames, dtype)
+    fmt = _frames_format(frames)
+    n, H, W = frames.shape[:3]
     if (n, W, H) != (table.n, table.W, table.H):
         raise ValueError('frames do not match the cell table (n, H, W, 3) or (n, H, W)')
-    if out is None:
-        out = torch.empty_like(frames)
-    _need(out, dtype, 'out')
-    if ch == 1 and out.shape != frames.shape:
-        raise ValueError('out must have the shape of frames')
-    if ch == 1:
-        border = _grey_border(border_bgr)
-        if bounds is None:
-            _lib.check(_lib_.mf_warp_u8c1(_ptr(frames), _ptr(out), _ptr(table.buf), n, W, H, table.R, table.C, border, _ptr(table.crop),
-                                          _stream()))
-        else:
-            _need_bounds(bounds)
-            _lib.check(_lib_.mf_warp_bounds_u8c1(_ptr(frames), _ptr(out), _ptr(table.buf), n, W, H, table.R, table.C, border,
-                                                 _ptr(table.crop), _ptr(bounds), _stream()))
-        return out
-    border = _border(border_bgr, dtype)
-    u16 = dtype == torch.uint16
+    out = _out_for(frames, fmt, out)
+    border = fmt.border(border_bgr)
     if bounds is None:
-        fn = _lib_.mf_warp_u16c3 if u16 else _lib_.mf_warp_u8c3
-        _lib.check(fn(_ptr(frames), _ptr(out), _ptr(table.buf), n, W, H, table.R, table.C, border, _ptr(table.crop), _stream()))
+        _lib.check(fmt.warp(_ptr(frames), _ptr(out), _ptr(table.buf), n, W, H, table.R, table.C, border, _ptr(table.crop), _stream()))
     else:
         _need_bounds(bounds)
-        fn = _lib_.mf_warp_bounds_u16c3 if u16 else _lib_.mf_warp_bounds_u8c3
-        _lib.check(fn(_ptr(frames), _ptr(out), _ptr(table.buf), n, W, H, table.R, table.C, border, _ptr(table.crop), _ptr(bounds),
-                      _stream()))
+        _lib.check(fmt.warp_bounds(_ptr(frames), _ptr(out), _ptr(table.buf), n, W, H, table.R, table.C, border, _ptr(table.crop),
+                                   _ptr(bounds), _stream()))
     return out
 
 
@@ -206,29 +209,23 @@ def warp_clip(frames, unstab, stab, table, border_bgr=(0, 0, 255), out=None, chu
     folded together by the kernels, final on the prep stream right after the tables' crop scan (and on the current stream after
     the call); per-frame values in table.crop; table.status accumulates degenerate cells.  frames: uint8 or uint16, or (n, H, W) uint8
     (see `warp`)."""
-    dtype = _need_frames(frames, 'frames')
+    fmt = _frames_format(frames)
     _need(unstab, torch.float64, 'unstab')
     _need(stab, torch.float64, 'stab')
-    n, H, W, ch = _frame_shape(frames, dtype)
+    n, H, W = frames.shape[:3]
     V2 = (table.R + 1) * (table.C + 1) * 2
     if (n, W, H) != (table.n, table.W, table.H) or unstab.numel() != n * V2 or stab.numel() != n * V2:
         raise ValueError('frames / displacements do not match the cell table')
-    if out is None:
-        out = torch.empty_like(frames)
-    _need(out, dtype, 'out')
+    out = _out_for(frames, fmt, out)
     if bounds is None:                  # (without a caller-owned tensor: one per table, rewritten by the next call on it)
         if table.bounds is None:
             table.bounds = torch.empty(4, dtype=torch.int32, device=frames.device)
         bounds = table.bounds
     else:
         _need_bounds(bounds)
-    if ch == 1 and out.shape != frames.shape:
-        raise ValueError('out must have the shape of frames')
-    border = _grey_border(border_bgr) if ch == 1 else _border(border_bgr, dtype)
     prep = ctypes.c_void_p(prep_stream.cuda_stream) if prep_stream is not None else None
-    fn = _lib_.mf_warp_clip_u8c1 if ch == 1 else _lib_.mf_warp_clip_u16c3 if dtype == torch.uint16 else _lib_.mf_warp_clip_u8c3
-    _lib.check(fn(_ptr(frames), _ptr(out), _ptr(unstab), _ptr(stab), n, W, H, table.R, table.C, border,
-                  _ptr(table.buf), _ptr(table.crop), _ptr(bounds), _ptr(table.status), int(chunks), prep, _stream()))
+    _lib.check(fmt.warp_clip(_ptr(frames), _ptr(out), _ptr(unstab), _ptr(stab), n, W, H, table.R, table.C, fmt.border(border_bgr),
+                             _ptr(table.buf), _ptr(table.crop), _ptr(bounds), _ptr(table.status), int(chunks), prep, _stream()))
     return out, bounds
 
 
@@ -256,17 +253,12 @@ def crop_reduce(crop, W, H):
 def crop_resize(frames, bounds, out=None):
     """Crop to the inclusive (left, top, right, bottom) and resize back to (W, H): mfs.py:1111-1157.  frames: uint8 or uint16 (uint16:
     cv2.resize's float path, mf_crop_resize_u16c3), or (n, H, W) uint8 (mf_crop_resize_u8c1); the output has the input's dtype and shape."""
-    dtype = _need_frames(frames, 'frames')
-    n, H, W, ch = _frame_shape(frames, dtype)
+    fmt = _frames_format(frames)
+    n, H, W = frames.shape[:3]
     left, top, right, bottom = (int(v) for v in bounds)
-    if out is None:
-        out = torch.empty_like(frames)
-    _need(out, dtype, 'out')
-    if ch == 1 and out.shape != frames.shape:
-        raise ValueError('out must have the shape of frames')
+    out = _out_for(frames, fmt, out)
     work = torch.empty(_lib_.mf_crop_resize_workspace_bytes(W, H), dtype=torch.uint8, device=frames.device)
-    fn = _lib_.mf_crop_resize_u8c1 if ch == 1 else _lib_.mf_crop_resize_u16c3 if dtype == torch.uint16 else _lib_.mf_crop_resize_u8c3
-    _lib.check(fn(_ptr(frames), _ptr(out), n, W, H, left, top, right, bottom, _ptr(work), _stream()))
+    _lib.check(fmt.crop_resize(_ptr(frames), _ptr(out), n, W, H, left, top, right, bottom, _ptr(work), _stream()))
     return out
 
 

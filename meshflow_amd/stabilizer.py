@@ -35,6 +35,11 @@ def _torch_device_of(self):
     return dev
 
 
+# The host-frame C calls (csrc/hostpipe.hip) by HostClip.channels: warp, warp + _crop_frames, _crop_frames alone
+_HOST_CALLS = {3: ('mf_warp_u8c3_host_frames', 'mf_warp_crop_u8c3_host_frames', 'mf_crop_resize_u8c3_host_frames'),
+               1: ('mf_warp_u8c1_host_frames', 'mf_warp_crop_u8c1_host_frames', 'mf_crop_resize_u8c1_host_frames')}
+
+
 def _warp_host_c(self, clip, unstab, stab, crop=False, keep_uncropped=True):
     """Host frames in -> host frames out through the C ABI's own chunked pipeline (csrc/hostpipe.hip:
     `mf_warp_u8c3_host_frames`, upload / kernel / download threads below Python, GIL released for the whole call).
@@ -45,34 +50,32 @@ def _warp_host_c(self, clip, unstab, stab, crop=False, keep_uncropped=True):
     cropped + resized frames (F, H, W, 3))."""
     import ctypes
     import torch
-    from . import _lib, pipeline
+    from . import _lib, ops, pipeline
     dev = self._torch_device()
     n, H, W = clip.num_frames, clip.height, clip.width
     frames = [clip.array[i] for i in range(n)] if clip.array is not None else clip.frames      # (validated by HostClip, every one of them)
-    grey = clip.channels == 1                     # (n, H, W) frames: the u8c1 calls, border byte = color_outside_image_area_bgr[0]
+    warp_fn, warp_crop_fn, _ = (getattr(_lib.lib, name) for name in _HOST_CALLS[clip.channels])
     fb = H * W * clip.channels
     want_out = keep_uncropped or not crop
     out = np.empty((n,) + clip.frame_shape, dtype=np.uint8) if want_out else None
     pin = (ctypes.c_void_p * n)(*[f.ctypes.data for f in frames])
     pout = (ctypes.c_void_p * n)(*[out.ctypes.data + i * fb for i in range(n)]) if want_out else None
     per_frame = np.empty((n, 4), dtype=np.int32)
-    border = (ctypes.c_uint8 * 3)(*[int(max(0, min(255, round(float(c))))) for c in self.color_outside_image_area_bgr])
-    if grey:
-        border = ctypes.c_uint8(border[0])
+    border = ops.pixel_format(torch.uint8, (n,) + clip.frame_shape).border(self.color_outside_image_area_bgr)   # (grey: the first component)
     args = (unstab.ctypes.data_as(ctypes.c_void_p), stab.ctypes.data_as(ctypes.c_void_p), n, W, H,
             self.mesh_row_count, self.mesh_col_count, border, per_frame.ctypes.data_as(ctypes.c_void_p))
     # the library works on the calling thread's current HIP device: scope it like every other path here does (and leave the
     # caller's current device as it was)
     with torch.cuda.device(dev):
         if not crop:
-            _lib.check((_lib.lib.mf_warp_u8c1_host_frames if grey else _lib.lib.mf_warp_u8c3_host_frames)(pin, pout, *args, None))
+            _lib.check(warp_fn(pin, pout, *args, None))
             bounds = (np.int64(per_frame[:, 0].max()), np.int64(per_frame[:, 1].max()),
                       np.int64(per_frame[:, 2].min()), np.int64(per_frame[:, 3].min()))
             return out, bounds
         cropped = np.empty((n,) + clip.frame_shape, dtype=np.uint8)
         pcrop = (ctypes.c_void_p * n)(*[cropped.ctypes.data + i * fb for i in range(n)])
         rect = (ctypes.c_int32 * 4)()
-        _lib.check((_lib.lib.mf_warp_crop_u8c1_host_frames if grey else _lib.lib.mf_warp_crop_u8c3_host_frames)(pin, pout, pcrop, *args, rect, None))
+        _lib.check(warp_crop_fn(pin, pout, pcrop, *args, rect, None))
     return out, tuple(np.int64(v) for v in rect), cropped
 
 
@@ -367,7 +370,7 @@ class MeshFlowStabilizer:
         fb = H * W * clip.channels
         pin = (ctypes.c_void_p * n)(*[f.ctypes.data for f in frames])
         pout = (ctypes.c_void_p * n)(*[out.ctypes.data + i * fb for i in range(n)])
-        fn = _lib.lib.mf_crop_resize_u8c1_host_frames if clip.channels == 1 else _lib.lib.mf_crop_resize_u8c3_host_frames
+        fn = getattr(_lib.lib, _HOST_CALLS[clip.channels][2])
         with torch.cuda.device(dev):
             _lib.check(fn(pin, pout, n, W, H, left, top, right, bottom, None))
         return list(out)
@@ -689,14 +692,13 @@ class MeshFlowStabilizer:
         deferred verdicts are kept per slot); threads that want their own pipelines take their own objects (the host-memory methods,
         `stabilize_clip` and the drop-in pair, may be called from several threads on one object: tests/test_gpu_stabilize_api.py)."""
         import torch
-        from . import dist as mfdist
+        from . import dist as mfdist, ops
         self._check_definition(adaptive_weights_definition)
         if check is False:
             check = 'never'
         F = d_disp.shape[0]
         lo, hi = frame_range if frame_range is not None else (0, F)
-        if d_frames.dim() == 3 and d_frames.dtype != torch.uint8:
-            raise ValueError(f'single-channel frames must be uint8 (got {d_frames.dtype}): (n, H, W) {d_frames.dtype} frames are not supported')
+        ops.pixel_format(d_frames.dtype, d_frames.shape)
         n, H, W = d_frames.shape[:3]
         if hi - lo != n:
             raise ValueError(f'frame_range {lo, hi} does not match {n} frames')

@@ -1,7 +1,7 @@
 """The single-channel kernels in the built library (CPU, tools/codeobj.py): they exist, use no scratch and spill nothing, and the two
 warp_kernel instantiations are still the only kernels whose name contains 'warp_kernel' (tools/isa_guard.py selects by that name).
 The grey warp uses neither the inline-asm byte-tap runs nor the speculative matrix load (footprint_body compiles both into the
-STAGE_OK instantiation only), so isa_guard's invariants do not concern it."""
+staged uint8 BGR instantiation only), so isa_guard's invariants do not concern it."""
 import os
 import sys
 
