@@ -202,6 +202,19 @@ int mf_crop_resize_u16c3(const uint16_t* d_frames, uint16_t* d_out, int n, int W
  * refusals. */
 int mf_crop_resize_u8c1(const uint8_t* d_frames, uint8_t* d_out, int n, int W, int H, int left, int top, int right,
                         int bottom, void* d_work, void* stream);
+/* _crop_frames to a caller-chosen output size: the same crop, scaled to out_W x out_H exactly like cv2.resize(crop, (out_W, out_H)) with
+ * INTER_LINEAR, for the three formats above (u16c3: where the crop is exactly twice the output in both axes, cv::resize takes INTER_AREA's
+ * fast path, (S00 + S01 + S10 + S11 + 2) >> 2, rounded half up; for 8-bit data that equals the bilinear result).  d_out holds
+ * n * out_H * out_W * channels samples.  d_work: mf_crop_resize_workspace_bytes(out_W, out_H) bytes suffice (the tables have one entry per
+ * OUTPUT column and row; no separate workspace call).  out_W, out_H == W, H is the call above, byte for byte.  Refused with
+ * MF_ERR_INVALID_ARG before anything is launched or written: null pointers, d_frames == d_out, out_W or out_H outside 1 .. 32,767, too
+ * many tiles, an empty or out-of-frame rectangle, and every refusal of the call above. */
+int mf_crop_resize_to_u8c3(const uint8_t* d_frames, uint8_t* d_out, int n, int W, int H, int left, int top, int right, int bottom,
+                           int out_W, int out_H, void* d_work, void* stream);
+int mf_crop_resize_to_u16c3(const uint16_t* d_frames, uint16_t* d_out, int n, int W, int H, int left, int top, int right, int bottom,
+                            int out_W, int out_H, void* d_work, void* stream);
+int mf_crop_resize_to_u8c1(const uint8_t* d_frames, uint8_t* d_out, int n, int W, int H, int left, int top, int right, int bottom,
+                           int out_W, int out_H, void* d_work, void* stream);
 
 /* ---- the row before the path: vertex-motion accumulation (mfs.py:236-452 from the matched features on) ----
  * Replaces the Python loops of _get_vertex_nearby_feature_residual_velocities (mfs.py:365-452), the medians, global
@@ -304,6 +317,21 @@ int mf_warp_crop_u8c1_host_frames(const uint8_t* const* frames, uint8_t* const* 
                                   uint8_t border, int32_t* crop /* [n][4] */, int32_t bounds[4], float* kernel_ms);
 int mf_crop_resize_u8c1_host_frames(const uint8_t* const* frames, uint8_t* const* cropped, int n, int W, int H, int left, int top,
                                     int right, int bottom, float* kernel_ms);
+/* The warp + crop and the crop-alone host calls to a caller-chosen output size (both formats): cropped[i] points to out_W * out_H * channels
+ * bytes (mf_crop_resize_to_u8c3 / _u8c1 of the chunk).  The ring's slots and chunks are sized by the larger of the input and the output
+ * frame; the overlap, degenerate-mesh and empty-rectangle refusals are those of the calls above (out_W / out_H outside 1 .. 32,767:
+ * MF_ERR_INVALID_ARG before anything moves). */
+int mf_warp_crop_to_u8c3_host_frames(const uint8_t* const* frames, uint8_t* const* out /* may be NULL */, uint8_t* const* cropped,
+                                     const double* unstab, const double* stab, int n, int W, int H, int R, int C,
+                                     const uint8_t border_bgr[3], int out_W, int out_H, int32_t* crop /* [n][4] */, int32_t bounds[4],
+                                     float* kernel_ms);
+int mf_crop_resize_to_u8c3_host_frames(const uint8_t* const* frames, uint8_t* const* cropped, int n, int W, int H, int left, int top,
+                                       int right, int bottom, int out_W, int out_H, float* kernel_ms);
+int mf_warp_crop_to_u8c1_host_frames(const uint8_t* const* frames, uint8_t* const* out /* may be NULL */, uint8_t* const* cropped,
+                                     const double* unstab, const double* stab, int n, int W, int H, int R, int C,
+                                     uint8_t border, int out_W, int out_H, int32_t* crop /* [n][4] */, int32_t bounds[4], float* kernel_ms);
+int mf_crop_resize_to_u8c1_host_frames(const uint8_t* const* frames, uint8_t* const* cropped, int n, int W, int H, int left, int top,
+                                       int right, int bottom, int out_W, int out_H, float* kernel_ms);
 int mf_host_cache_release(void);
 
 /* ---- multi-GPU exchange steps, on RCCL directly: ONE process drives the GPUs 0..ndev-1 of a node ----

@@ -53,6 +53,9 @@ SIGNATURES = {
     'mf_warp_bounds_u8c1': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, ctypes.c_uint8, _vp, _vp, _vp]),
     'mf_warp_clip_u8c1': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, ctypes.c_uint8, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
     'mf_crop_resize_u8c1': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    'mf_crop_resize_to_u8c3': (_i, [_vp, _vp] + [_i] * 9 + [_vp, _vp]),
+    'mf_crop_resize_to_u16c3': (_i, [_vp, _vp] + [_i] * 9 + [_vp, _vp]),
+    'mf_crop_resize_to_u8c1': (_i, [_vp, _vp] + [_i] * 9 + [_vp, _vp]),
     'mf_vertex_motion_workspace_bytes': (_sz, [_i, _i, _i, _i, _i]),
     'mf_vertex_motion_f64': (_i, [_vp, _vp, _vp, _vp] + [_i] * 9 + [_vp, _vp, _vp, _vp, _vp]),
     'mf_stability_score_f64': (_i, [_vp, _i, _i, _vp, _vp, _vp]),
@@ -68,6 +71,12 @@ SIGNATURES = {
     'mf_warp_u8c1_host_frames': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, ctypes.c_uint8, _vp, ctypes.POINTER(ctypes.c_float)]),
     'mf_warp_crop_u8c1_host_frames': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, ctypes.c_uint8, _vp, _vp, ctypes.POINTER(ctypes.c_float)]),
     'mf_crop_resize_u8c1_host_frames': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, ctypes.POINTER(ctypes.c_float)]),
+    'mf_warp_crop_to_u8c3_host_frames': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _i, _vp, _vp,
+                                              ctypes.POINTER(ctypes.c_float)]),
+    'mf_crop_resize_to_u8c3_host_frames': (_i, [_vp, _vp] + [_i] * 9 + [ctypes.POINTER(ctypes.c_float)]),
+    'mf_warp_crop_to_u8c1_host_frames': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, ctypes.c_uint8, _i, _i, _vp, _vp,
+                                              ctypes.POINTER(ctypes.c_float)]),
+    'mf_crop_resize_to_u8c1_host_frames': (_i, [_vp, _vp] + [_i] * 9 + [ctypes.POINTER(ctypes.c_float)]),
     'mf_host_cache_release': (_i, []),
     'mf_comm_init_all': (_i, [_i]),
     'mf_comm_size': (_i, [ctypes.POINTER(_i)]),

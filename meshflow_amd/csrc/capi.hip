@@ -45,6 +45,14 @@ static int crop_resize_entry(const char* name, Px px, const void* d_frames, void
     return launch_crop_resize(px, d_frames, d_out, n, W, H, left, top, right, bottom, d_work, (hipStream_t)stream);
 }
 
+static int crop_resize_to_entry(const char* name, Px px, const void* d_frames, void* d_out, int n, int W, int H, int left, int top,
+                                int right, int bottom, int out_W, int out_H, void* d_work, void* stream)
+{
+    if (!d_frames || !d_out || !d_work) { set_error("%s: null pointer", name); return MF_ERR_INVALID_ARG; }
+    if (d_frames == d_out) { set_error("%s: d_frames and d_out alias", name); return MF_ERR_INVALID_ARG; }
+    return launch_crop_resize_to(px, d_frames, d_out, n, W, H, left, top, right, bottom, out_W, out_H, d_work, (hipStream_t)stream);
+}
+
 }  // namespace mf
 
 using namespace mf;
@@ -217,6 +225,27 @@ int mf_crop_resize_u8c1(const uint8_t* d_frames, uint8_t* d_out, int n, int W, i
                         int bottom, void* d_work, void* stream)
 {
     return crop_resize_entry("mf_crop_resize_u8c1", Px::U8C1, d_frames, d_out, n, W, H, left, top, right, bottom, d_work, stream);
+}
+
+int mf_crop_resize_to_u8c3(const uint8_t* d_frames, uint8_t* d_out, int n, int W, int H, int left, int top, int right, int bottom,
+                           int out_W, int out_H, void* d_work, void* stream)
+{
+    return crop_resize_to_entry("mf_crop_resize_to_u8c3", Px::U8C3, d_frames, d_out, n, W, H, left, top, right, bottom, out_W, out_H, d_work,
+                                stream);
+}
+
+int mf_crop_resize_to_u16c3(const uint16_t* d_frames, uint16_t* d_out, int n, int W, int H, int left, int top, int right, int bottom,
+                            int out_W, int out_H, void* d_work, void* stream)
+{
+    return crop_resize_to_entry("mf_crop_resize_to_u16c3", Px::U16C3, d_frames, d_out, n, W, H, left, top, right, bottom, out_W, out_H, d_work,
+                                stream);
+}
+
+int mf_crop_resize_to_u8c1(const uint8_t* d_frames, uint8_t* d_out, int n, int W, int H, int left, int top, int right, int bottom,
+                           int out_W, int out_H, void* d_work, void* stream)
+{
+    return crop_resize_to_entry("mf_crop_resize_to_u8c1", Px::U8C1, d_frames, d_out, n, W, H, left, top, right, bottom, out_W, out_H, d_work,
+                                stream);
 }
 
 size_t mf_vertex_motion_workspace_bytes(int total_features, int max_per_pair, int P, int R, int C)

@@ -163,9 +163,10 @@ void populate_frames(uint8_t* const* host, int i0, int i1, size_t fb)
     }
 }
 
-// Every host frame as an address interval; true when an interval of `a` overlaps one of `b` (the populate threads write into
-// the output pages while the uploads are still reading the input: aliasing would corrupt the input silently).
-bool ranges_overlap(const uint8_t* const* a, const uint8_t* const* b, int n, size_t fb)
+// Every host frame as an address interval (fa bytes for a frame of `a`, fb for one of `b`); true when an interval of `a` overlaps one of
+// `b` (the populate threads write into the output pages while the uploads are still reading the input: aliasing would corrupt the input
+// silently).
+bool ranges_overlap(const uint8_t* const* a, const uint8_t* const* b, int n, size_t fa, size_t fb)
 {
     std::vector<std::pair<uintptr_t, int>> v;
     v.reserve(2 * (size_t)n);
@@ -174,7 +175,7 @@ bool ranges_overlap(const uint8_t* const* a, const uint8_t* const* b, int n, siz
     uintptr_t end[2] = { 0, 0 };                       // furthest end seen so far per side
     for (const auto& it : v) {
         if (it.first < end[1 - it.second]) return true;
-        const uintptr_t e = it.first + fb;
+        const uintptr_t e = it.first + (it.second ? fb : fa);
         if (e > end[it.second]) end[it.second] = e;
     }
     return false;
@@ -188,6 +189,7 @@ struct PipeJob {
     const uint8_t* const* frames; uint8_t* const* out; uint8_t* const* cropped;
     const double* unstab; const double* stab;
     int n, W, H, R, C;
+    int oW, oH;                                      // size of a cropped frame (W, H: _crop_frames as the reference calls it)
     Px px;                                           // U8C3 or U8C1 (host frames are uint8)
     uint64_t border;                                 // pack_border's word
     int32_t* crop; int32_t* bounds; float* kernel_ms;
@@ -209,8 +211,10 @@ int run_host_pipeline(PipeJob job)
     PipeCache& pc = g_pipe[dev];
     std::lock_guard<std::mutex> cache_guard(pc.lock);
     const size_t fb = (size_t)W * H * px_bytes(job.px);                // (chunks are sized by bytes: ~3 x the frames per chunk for grey)
-    if ((out && ranges_overlap(frames, out, n, fb)) || (cropped && ranges_overlap(frames, cropped, n, fb)) ||
-        (out && cropped && ranges_overlap(out, cropped, n, fb))) {
+    const size_t fbc = (size_t)job.oW * job.oH * px_bytes(job.px);     // a cropped frame
+    const size_t fbm = std::max(fb, fbc);                                // what a ring slot holds per frame: input, or its cropped output
+    if ((out && ranges_overlap(frames, out, n, fb, fb)) || (cropped && ranges_overlap(frames, cropped, n, fb, fbc)) ||
+        (out && cropped && ranges_overlap(out, cropped, n, fb, fbc))) {
         set_error("%s: input and output frames overlap in memory (in-place operation is not supported)", job.name);
         return MF_ERR_INVALID_ARG;
     }
@@ -223,14 +227,14 @@ int run_host_pipeline(PipeJob job)
     }
     const size_t vb1 = (size_t)(R + 1) * (C + 1) * 2 * sizeof(double);        // vertex displacements of one frame
     // (read at every call: a host may retune between clips)
-    const int by_bytes = (int)std::min<size_t>(4096, std::max<size_t>(1, (PIPE_CHUNK_BYTES + fb / 2) / fb));
+    const int by_bytes = (int)std::min<size_t>(4096, std::max<size_t>(1, (PIPE_CHUNK_BYTES + fbm / 2) / fbm));
     const int cfg_chunk = env_int("MF_PIPE_CHUNK", by_bytes, 1, 4096), cfg_up = env_int("MF_PIPE_UP", PIPE_UP, 1, PIPE_MAX),
               cfg_down = env_int("MF_PIPE_DOWN", PIPE_DOWN, 1, PIPE_MAX), cfg_pop = env_int("MF_PIPE_POPULATE", PIPE_POPULATE, 0, PIPE_MAX),
-              cfg_slots = env_int("MF_PIPE_SLOTS", (int)std::min<size_t>(PIPE_SLOTS_MAX, std::max<size_t>(4, PIPE_RING_BYTES / (fb * cfg_chunk))), 2, PIPE_SLOTS_MAX);
+              cfg_slots = env_int("MF_PIPE_SLOTS", (int)std::min<size_t>(PIPE_SLOTS_MAX, std::max<size_t>(4, PIPE_RING_BYTES / (fbm * cfg_chunk))), 2, PIPE_SLOTS_MAX);
     const int chunk = n < cfg_chunk ? n : cfg_chunk;
     const int nchunks = (n + chunk - 1) / chunk;
     const int slots = nchunks < cfg_slots ? nchunks : cfg_slots;
-    const size_t slot_bytes = fb * chunk;
+    const size_t slot_bytes = fbm * chunk;
     MF_HIP_TRY(pc.frames.need(slot_bytes * slots)); MF_HIP_TRY(pc.out.need(slot_bytes * slots));
     if (job.warp) {
         MF_HIP_TRY(pc.unstab.need(vb1 * n)); MF_HIP_TRY(pc.stab.need(vb1 * n));
@@ -239,7 +243,7 @@ int run_host_pipeline(PipeJob job)
         MF_HIP_TRY(pc.status.need(sizeof(int32_t)));
         MF_HIP_TRY(pc.bounds.need(4 * sizeof(int32_t)));
     }
-    if (cropped) MF_HIP_TRY(pc.work.need(crop_resize_workspace_bytes(W, H)));
+    if (cropped) MF_HIP_TRY(pc.work.need(crop_resize_workspace_bytes(job.oW, job.oH)));
     uint8_t* const ring_in = (uint8_t*)pc.frames.p;
     uint8_t* const ring_out = (uint8_t*)pc.out.p;
     int32_t* d_crop = (int32_t*)pc.crop.p;
@@ -340,7 +344,7 @@ int run_host_pipeline(PipeJob job)
         workers.emplace_back([&, t] {
             for (int k = t; k < nchunks; k += n_pop) {       // chunk by chunk, in the order the downloads will need the pages
                 if (out) { populate_frames(out, k * chunk, chunk_end(k), fb); sh.mark(sh.populated, k); }
-                if (cropped) { populate_frames(cropped, k * chunk, chunk_end(k), fb); sh.mark(sh.populated2, k); }
+                if (cropped) { populate_frames(cropped, k * chunk, chunk_end(k), fbc); sh.mark(sh.populated2, k); }
                 if (trace && (k == nchunks - 1 || k == 0)) fprintf(stderr, "[mf pipe] %8.2f ms  pages of chunk %d populated\n", since(), k);
             }
         });
@@ -383,7 +387,7 @@ int run_host_pipeline(PipeJob job)
                     if (!sh.wait(sh.resize_ready, k) || !sh.wait(sh.populated2, k)) return;
                     hipError_t e = hipStreamWaitEvent(pc.down[t], resize_done[k], 0);
                     if (trace_level == 2 && !out) tr_dn0[k] = since();
-                    if (e == hipSuccess) e = copy_frames(slot_cropped(k), cropped, k * chunk, chunk_end(k), fb, false, pc.down[t]);
+                    if (e == hipSuccess) e = copy_frames(slot_cropped(k), cropped, k * chunk, chunk_end(k), fbc, false, pc.down[t]);
                     if (trace_level == 2) tr_dn1[k] = since();
                     if (e != hipSuccess) { sh.fail(e, "download of a cropped frame chunk"); return; }
                 }
@@ -421,8 +425,10 @@ int run_host_pipeline(PipeJob job)
             }
         }
         if (cropped) {                                     // _crop_frames (mfs.py:1111-1157) of this chunk, its source still in the caches
-            rc = job.warp ? launch_crop_resize(job.px, slot_out(k), slot_in(k), m, W, H, rect[0], rect[1], rect[2], rect[3], pc.work.p, pc.compute)
-                          : launch_crop_resize(job.px, slot_in(k), slot_out(k), m, W, H, rect[0], rect[1], rect[2], rect[3], pc.work.p, pc.compute);
+            rc = job.warp ? launch_crop_resize_to(job.px, slot_out(k), slot_in(k), m, W, H, rect[0], rect[1], rect[2], rect[3], job.oW, job.oH,
+                                                  pc.work.p, pc.compute)
+                          : launch_crop_resize_to(job.px, slot_in(k), slot_out(k), m, W, H, rect[0], rect[1], rect[2], rect[3], job.oW, job.oH,
+                                                  pc.work.p, pc.compute);
             if (rc != MF_OK) { sh.fail(hipErrorUnknown, "kernel launch"); break; }
             e = hipEventRecord(resize_done[k], pc.compute);
             if (e != hipSuccess) { sh.fail(e, "hipEventRecord"); break; }
@@ -471,11 +477,12 @@ int run_host_pipeline(PipeJob job)
 
 int warp_host_frames(const uint8_t* const* frames, uint8_t* const* out, uint8_t* const* cropped, const double* unstab, const double* stab,
                      int n, int W, int H, int R, int C, const uint8_t* border, int32_t* crop, int32_t* bounds, float* kernel_ms,
-                     Px px = Px::U8C3)
+                     Px px = Px::U8C3, int oW = 0, int oH = 0, const char* name = nullptr)
 {
     PipeJob job{};
     job.frames = frames; job.out = out; job.cropped = cropped; job.unstab = unstab; job.stab = stab;
     job.n = n; job.W = W; job.H = H; job.R = R; job.C = C;
+    job.oW = oW > 0 ? oW : W; job.oH = oH > 0 ? oH : H;
     job.px = px;
     job.border = pack_border(px, border);
     job.crop = crop; job.bounds = bounds; job.kernel_ms = kernel_ms;
@@ -483,6 +490,7 @@ int warp_host_frames(const uint8_t* const* frames, uint8_t* const* out, uint8_t*
     job.rect[0] = 0; job.rect[1] = 0; job.rect[2] = W - 1; job.rect[3] = H - 1;
     if (px == Px::U8C1) job.name = cropped ? "mf_warp_crop_u8c1_host_frames" : "mf_warp_u8c1_host_frames";
     else job.name = cropped ? "mf_warp_crop_u8c3_host_frames" : "mf_warp_u8c3_host";
+    if (name) job.name = name;
     return run_host_pipeline(job);
 }
 
@@ -532,11 +540,21 @@ int mf_warp_u8c3_host(const uint8_t* frames, uint8_t* out, const double* unstab,
     return warp_host_frames(in.data(), outp.data(), nullptr, unstab, stab, n, W, H, R, C, border_bgr, crop, nullptr, kernel_ms);
 }
 
+static int check_out_size(const char* name, int oW, int oH)
+{
+    if (oW < 1 || oH < 1 || oW > 32767 || oH > 32767) {
+        set_error("%s: unsupported output size %dx%d (1 .. 32,767 each)", name, oW, oH);
+        return MF_ERR_INVALID_ARG;
+    }
+    return MF_OK;
+}
+
 static int crop_resize_host(const char* name, Px px, const uint8_t* const* frames, uint8_t* const* cropped, int n, int W, int H,
-                            int left, int top, int right, int bottom, float* kernel_ms)
+                            int left, int top, int right, int bottom, int oW, int oH, float* kernel_ms)
 {
     if (!frames || !cropped) { set_error("%s: null pointer", name); return MF_ERR_INVALID_ARG; }
     if (n <= 0 || W < 1 || H < 1 || W > 32767 || H > 32767) { set_error("%s: unsupported shape n=%d W=%d H=%d", name, n, W, H); return MF_ERR_INVALID_ARG; }
+    if (const int rc = check_out_size(name, oW, oH)) return rc;
     if (left < 0 || top < 0 || right >= W || bottom >= H || right < left || bottom < top) {        // before any output page is touched
         set_error("%s: empty or out-of-frame crop rectangle (%d, %d, %d, %d) for %dx%d (cv2.resize would "
                   "fail on an empty source)", name, left, top, right, bottom, W, H);
@@ -547,6 +565,7 @@ static int crop_resize_host(const char* name, Px px, const uint8_t* const* frame
     PipeJob job{};
     job.frames = frames; job.cropped = cropped;
     job.n = n; job.W = W; job.H = H; job.R = 1; job.C = 1;
+    job.oW = oW; job.oH = oH;
     job.px = px;
     job.kernel_ms = kernel_ms;
     job.warp = false;
@@ -558,7 +577,7 @@ static int crop_resize_host(const char* name, Px px, const uint8_t* const* frame
 int mf_crop_resize_u8c3_host_frames(const uint8_t* const* frames, uint8_t* const* cropped, int n, int W, int H, int left, int top,
                                     int right, int bottom, float* kernel_ms)
 {
-    return crop_resize_host("mf_crop_resize_u8c3_host_frames", Px::U8C3, frames, cropped, n, W, H, left, top, right, bottom, kernel_ms);
+    return crop_resize_host("mf_crop_resize_u8c3_host_frames", Px::U8C3, frames, cropped, n, W, H, left, top, right, bottom, W, H, kernel_ms);
 }
 
 int mf_warp_u8c1_host_frames(const uint8_t* const* frames, uint8_t* const* out, const double* unstab, const double* stab, int n,
@@ -581,7 +600,43 @@ int mf_warp_crop_u8c1_host_frames(const uint8_t* const* frames, uint8_t* const* 
 int mf_crop_resize_u8c1_host_frames(const uint8_t* const* frames, uint8_t* const* cropped, int n, int W, int H, int left, int top,
                                     int right, int bottom, float* kernel_ms)
 {
-    return crop_resize_host("mf_crop_resize_u8c1_host_frames", Px::U8C1, frames, cropped, n, W, H, left, top, right, bottom, kernel_ms);
+    return crop_resize_host("mf_crop_resize_u8c1_host_frames", Px::U8C1, frames, cropped, n, W, H, left, top, right, bottom, W, H, kernel_ms);
+}
+
+int mf_warp_crop_to_u8c3_host_frames(const uint8_t* const* frames, uint8_t* const* out, uint8_t* const* cropped, const double* unstab,
+                                     const double* stab, int n, int W, int H, int R, int C, const uint8_t border_bgr[3], int out_W, int out_H,
+                                     int32_t* crop, int32_t bounds[4], float* kernel_ms)
+{
+    const char* name = "mf_warp_crop_to_u8c3_host_frames";
+    if (!cropped || !bounds) { set_error("%s: null pointer", name); return MF_ERR_INVALID_ARG; }
+    if (const int rc = check_host_args(name, frames, out, cropped, unstab, stab, n, W, H, R, C, border_bgr, crop)) return rc;
+    if (const int rc = check_out_size(name, out_W, out_H)) return rc;
+    return warp_host_frames(frames, out, cropped, unstab, stab, n, W, H, R, C, border_bgr, crop, bounds, kernel_ms, Px::U8C3, out_W, out_H, name);
+}
+
+int mf_crop_resize_to_u8c3_host_frames(const uint8_t* const* frames, uint8_t* const* cropped, int n, int W, int H, int left, int top,
+                                       int right, int bottom, int out_W, int out_H, float* kernel_ms)
+{
+    return crop_resize_host("mf_crop_resize_to_u8c3_host_frames", Px::U8C3, frames, cropped, n, W, H, left, top, right, bottom, out_W, out_H,
+                            kernel_ms);
+}
+
+int mf_warp_crop_to_u8c1_host_frames(const uint8_t* const* frames, uint8_t* const* out, uint8_t* const* cropped, const double* unstab,
+                                     const double* stab, int n, int W, int H, int R, int C, uint8_t border, int out_W, int out_H,
+                                     int32_t* crop, int32_t bounds[4], float* kernel_ms)
+{
+    const char* name = "mf_warp_crop_to_u8c1_host_frames";
+    if (!cropped || !bounds) { set_error("%s: null pointer", name); return MF_ERR_INVALID_ARG; }
+    if (const int rc = check_host_args(name, frames, out, cropped, unstab, stab, n, W, H, R, C, &border, crop)) return rc;
+    if (const int rc = check_out_size(name, out_W, out_H)) return rc;
+    return warp_host_frames(frames, out, cropped, unstab, stab, n, W, H, R, C, &border, crop, bounds, kernel_ms, Px::U8C1, out_W, out_H, name);
+}
+
+int mf_crop_resize_to_u8c1_host_frames(const uint8_t* const* frames, uint8_t* const* cropped, int n, int W, int H, int left, int top,
+                                       int right, int bottom, int out_W, int out_H, float* kernel_ms)
+{
+    return crop_resize_host("mf_crop_resize_to_u8c1_host_frames", Px::U8C1, frames, cropped, n, W, H, left, top, right, bottom, out_W, out_H,
+                            kernel_ms);
 }
 
 int mf_host_cache_release(void)

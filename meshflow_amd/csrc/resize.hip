@@ -14,6 +14,7 @@
 // 12-byte store), the two source rows of an output row staged in LDS, v_dot2_u32_u16 for the horizontal pass.
 // Memory-bound in principle (2*H*W*3 bytes per frame).
 #include "mf_common.h"
+#include "resize_u8.h"
 
 namespace mf {
 
@@ -41,113 +42,6 @@ __global__ __launch_bounds__(256) void resize_tables_kernel(int cw, int ch, int 
         const int sy0 = min(max(sy, 0), ch - 1), sy1 = min(max(sy + 1, 0), ch - 1);
         ytab[i].ofs = sy0 | (sy1 << 16);
         ytab[i].w = (uint32_t)b0 | ((uint32_t)b1 << 16);
-    }
-}
-
-// B | G << 8 | R << 16 of the pixel at byte offset o; the 4-byte load of the very last pixel of the stack is
-// shifted back by one byte instead of running past the allocation.
-__device__ __forceinline__ uint32_t load_bgr(const uint8_t* __restrict__ frame, uint32_t o, size_t limit)
-{
-    uint32_t v;
-    if ((size_t)o + 4 <= limit) {
-        __builtin_memcpy(&v, frame + o, 4);
-    } else if (o != 0) {
-        __builtin_memcpy(&v, frame + o - 1, 4);
-        v >>= 8;
-    } else {                                             // a stack of ONE pixel: nothing in front of it either
-        v = (uint32_t)frame[0] | (uint32_t)frame[1] << 8 | (uint32_t)frame[2] << 16;
-    }
-    return v & 0xFFFFFFu;
-}
-
-typedef unsigned short ushort2_t __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ uint32_t udot2(uint32_t a, uint32_t b, uint32_t c)
-{
-    return __builtin_amdgcn_udot2(__builtin_bit_cast(ushort2_t, a), __builtin_bit_cast(ushort2_t, b), c, false);
-}
-
-constexpr int kRowPitch = 800;        // bytes of one staged source row in LDS: 50 chunks of 16 bytes (256 output px + slack)
-
-// Workgroup = 8 output rows x 256 pixels; wavefront = kRows consecutive rows; lane = 4 consecutive pixels per row (one
-// 12-byte store each).
-// The two source rows of an output row are shared by all its pixels: the wavefront copies the span it needs of both
-// (<= 800 bytes each, from the dword holding the first tap) into LDS with two global->LDS 16-byte loads per lane and
-// takes the taps from there (three dword reads per pixel and row + v_alignbyte for the 3-byte-pixel misalignment).
-// That replaces eight unaligned 8-byte loads per lane, whose instruction count -- not bytes -- bounded the first version.
-// High 32 bits of the product of two 24-bit values (v_mul_hi_u32_u24).
-__device__ __forceinline__ uint32_t mulhi_u24(uint32_t a, uint32_t b)
-{
-    return (uint32_t)(((unsigned long long)(a & 0xFFFFFFu) * (unsigned long long)(b & 0xFFFFFFu)) >> 32);
-}
-
-constexpr int kRows = 8;              // output rows per wavefront
-constexpr int kWaves = 4;             // wavefronts per workgroup (they never cooperate)
-constexpr int kSrcRows = kRows + 1;   // source rows a wavefront stages: _crop_frames only ever scales UP (the crop lies inside the frame), so
-                                      // consecutive output rows advance by at most one source row
-
-// The horizontal pass of ONE staged source row for the lane's four pixels: t = S[sx] a0 + S[sx+1] a1 per channel (v_dot2_u32_u16 with
-// the weights pre-scaled by 16: T = 16 t < 2^24), returned as T & ~255 = 256 (t >> 4), what the vertical pass multiplies.  The taps
-// are byte loads with immediate offsets: ds_read_u8 puts S[sx] into the low byte of one register, ds_read_u8_d16_hi S[sx+1] into
-// bits 16-23 of another (with SRAM ECC a d16 load zeroes the other half of its destination: check_d16_zero_fill), one v_or_b32 joins
-// them.  All 24 loads and their wait sit in ONE asm block: nothing can be scheduled between issue and wait.
-__device__ __forceinline__ void hpass_row(const uint32_t (&at)[4], const uint32_t (&w)[4], uint32_t (&T)[4][3])
-{
-    uint32_t lo[4][3], hi[4][3];
-    asm volatile("ds_read_u8 %0, %24 offset:0\n\tds_read_u8_d16_hi %1, %24 offset:3\n\t"
-                 "ds_read_u8 %2, %24 offset:1\n\tds_read_u8_d16_hi %3, %24 offset:4\n\t"
-                 "ds_read_u8 %4, %24 offset:2\n\tds_read_u8_d16_hi %5, %24 offset:5\n\t"
-                 "ds_read_u8 %6, %25 offset:0\n\tds_read_u8_d16_hi %7, %25 offset:3\n\t"
-                 "ds_read_u8 %8, %25 offset:1\n\tds_read_u8_d16_hi %9, %25 offset:4\n\t"
-                 "ds_read_u8 %10, %25 offset:2\n\tds_read_u8_d16_hi %11, %25 offset:5\n\t"
-                 "ds_read_u8 %12, %26 offset:0\n\tds_read_u8_d16_hi %13, %26 offset:3\n\t"
-                 "ds_read_u8 %14, %26 offset:1\n\tds_read_u8_d16_hi %15, %26 offset:4\n\t"
-                 "ds_read_u8 %16, %26 offset:2\n\tds_read_u8_d16_hi %17, %26 offset:5\n\t"
-                 "ds_read_u8 %18, %27 offset:0\n\tds_read_u8_d16_hi %19, %27 offset:3\n\t"
-                 "ds_read_u8 %20, %27 offset:1\n\tds_read_u8_d16_hi %21, %27 offset:4\n\t"
-                 "ds_read_u8 %22, %27 offset:2\n\tds_read_u8_d16_hi %23, %27 offset:5\n\t"
-                 "s_waitcnt lgkmcnt(0)"
-                 : "=&v"(lo[0][0]), "=&v"(hi[0][0]), "=&v"(lo[0][1]), "=&v"(hi[0][1]), "=&v"(lo[0][2]), "=&v"(hi[0][2]),
-                   "=&v"(lo[1][0]), "=&v"(hi[1][0]), "=&v"(lo[1][1]), "=&v"(hi[1][1]), "=&v"(lo[1][2]), "=&v"(hi[1][2]),
-                   "=&v"(lo[2][0]), "=&v"(hi[2][0]), "=&v"(lo[2][1]), "=&v"(hi[2][1]), "=&v"(lo[2][2]), "=&v"(hi[2][2]),
-                   "=&v"(lo[3][0]), "=&v"(hi[3][0]), "=&v"(lo[3][1]), "=&v"(hi[3][1]), "=&v"(lo[3][2]), "=&v"(hi[3][2])
-                 : "v"(at[0]), "v"(at[1]), "v"(at[2]), "v"(at[3]) : "memory");
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) T[j][c] = udot2(lo[j][c] | hi[j][c], w[j], 0u) & ~255u;
-}
-
-// The vertical pass + store of one output row: out = (((b0 (t0 >> 4)) >> 16) + ((b1 (t1 >> 4)) >> 16) + 2) >> 2, each product's
-// high half by one v_mul_hi_u32_u24 of (256 b) and (256 (t >> 4)).  No saturation needed: each weight pair sums to 2048 +- 1 (two
-// cvRound of complementary fractions), so t <= 255 * 2049, t >> 4 <= 32655 and the two high halves sum to at most
-// 2049 * 32655 / 65536 < 1021, i.e. (sum + 2) >> 2 <= 255 -- cv2's saturate_cast never triggers either.
-__device__ __forceinline__ void vpass_store(const uint32_t (&T0)[4][3], const uint32_t (&T1)[4][3], uint32_t b0s, uint32_t b1s,
-                                            uint8_t* __restrict__ dst, uint32_t o, int x0, int W)
-{
-    uint32_t px[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const uint32_t vB = (mulhi_u24(b0s, T0[j][0]) + mulhi_u24(b1s, T1[j][0]) + 2u) >> 2;
-        const uint32_t vG = (mulhi_u24(b0s, T0[j][1]) + mulhi_u24(b1s, T1[j][1]) + 2u) >> 2;
-        const uint32_t vR = (mulhi_u24(b0s, T0[j][2]) + mulhi_u24(b1s, T1[j][2]) + 2u) >> 2;
-        px[j] = vB | (vG << 8) | (vR << 16);
-    }
-    if (x0 + 3 < W) {
-        uint3 d;
-        d.x = px[0] | (px[1] << 24);
-        d.y = (px[1] >> 8) | (px[2] << 16);
-        d.z = (px[2] >> 16) | (px[3] << 8);
-        if ((W & 3) == 0) *reinterpret_cast<uint3*>(dst + o) = d;
-        else __builtin_memcpy(dst + o, &d, 12);                  // (a row of W % 4 != 0 starts anywhere: one unaligned 12-byte store)
-    } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-            if (x0 + j < W) {
-                dst[o + 3 * j + 0] = (uint8_t)(px[j]);
-                dst[o + 3 * j + 1] = (uint8_t)(px[j] >> 8);
-                dst[o + 3 * j + 2] = (uint8_t)(px[j] >> 16);
-            }
     }
 }
 
@@ -292,15 +186,20 @@ __global__ __launch_bounds__(64 * kWaves) void resize_kernel(const uint8_t* __re
 
 size_t crop_resize_workspace_bytes(int W, int H) { return (size_t)(W + H) * sizeof(ResizeTab); }
 
+// resize_tables_kernel's tables of a cw x ch crop scaled to oW x oH (oW x-entries, then oH y-entries) in `work`
+static int launch_resize_tables_to(int cw, int ch, int oW, int oH, void* work, hipStream_t st)
+{
+    const double scale_x = 1.0 / ((double)oW / (double)cw), scale_y = 1.0 / ((double)oH / (double)ch);
+    ResizeTab* xtab = (ResizeTab*)work;
+    ResizeTab* ytab = xtab + oW;
+    const int m = oW > oH ? oW : oH;
+    hipLaunchKernelGGL(resize_tables_kernel, dim3((m + 255) / 256), dim3(256), 0, st, cw, ch, oW, oH, scale_x, scale_y, xtab, ytab);
+    return hip_fail(hipGetLastError(), "resize_tables_kernel launch");
+}
+
 static int launch_resize_tables(int W, int H, int left, int top, int right, int bottom, void* work, hipStream_t st)
 {
-    const int cw = right - left + 1, ch = bottom - top + 1;
-    const double scale_x = 1.0 / ((double)W / (double)cw), scale_y = 1.0 / ((double)H / (double)ch);
-    ResizeTab* xtab = (ResizeTab*)work;
-    ResizeTab* ytab = xtab + W;
-    const int m = W > H ? W : H;
-    hipLaunchKernelGGL(resize_tables_kernel, dim3((m + 255) / 256), dim3(256), 0, st, cw, ch, W, H, scale_x, scale_y, xtab, ytab);
-    return hip_fail(hipGetLastError(), "resize_tables_kernel launch");
+    return launch_resize_tables_to(right - left + 1, bottom - top + 1, W, H, work, st);
 }
 
 int launch_crop_resize(Px px, const void* frames, void* out, int n, int W, int H, int left, int top, int right, int bottom,
@@ -334,6 +233,42 @@ int launch_crop_resize(Px px, const void* frames, void* out, int n, int W, int H
     hipLaunchKernelGGL(resize_kernel, dim3(order.per_xcd * 8u), dim3(64 * kWaves), 0, st, (const uint8_t*)frames, (uint8_t*)out, n, W, H, left, top,
                        cw, xtab, ytab, order);
     return hip_fail(hipGetLastError(), "resize_kernel launch");
+}
+
+int launch_crop_resize_to(Px px, const void* frames, void* out, int n, int W, int H, int left, int top, int right, int bottom, int oW, int oH,
+                          void* work, hipStream_t st)
+{
+    const char* name = px_name(px);
+    if (n <= 0 || W < 1 || H < 1 || W > 32767 || H > 32767) {
+        set_error("mf_crop_resize_to_%s: unsupported shape n=%d W=%d H=%d", name, n, W, H);
+        return MF_ERR_INVALID_ARG;
+    }
+    if (oW < 1 || oH < 1 || oW > 32767 || oH > 32767) {
+        set_error("mf_crop_resize_to_%s: unsupported output size %dx%d (1 .. 32,767 each)", name, oW, oH);
+        return MF_ERR_INVALID_ARG;
+    }
+    if (left < 0 || top < 0 || right >= W || bottom >= H || right < left || bottom < top) {
+        set_error("mf_crop_resize_to_%s: empty or out-of-frame crop rectangle (%d, %d, %d, %d) for %dx%d (cv2.resize would "
+                  "fail on an empty source)", name, left, top, right, bottom, W, H);
+        return MF_ERR_INVALID_ARG;
+    }
+    const int cw = right - left + 1, ch = bottom - top + 1;
+    const bool up = oW >= cw && oH >= ch;
+    // tiles: 256 output pixels of kWaves x (the instantiation's rows) output rows (u8c1: resize_c1.hip's; u16c3: one row)
+    const int tile_rows = resize_to_tile_rows(px, up);
+    TileOrder order;
+    if (!make_tile_order((oW + 255) / 256, (oH + tile_rows - 1) / tile_rows, n, order)) {
+        set_error("mf_crop_resize_to_%s: too many tiles", name);
+        return MF_ERR_INVALID_ARG;
+    }
+    if (oW == W && oH == H)                                          // the same size: today's call, byte for byte
+        return launch_crop_resize(px, frames, out, n, W, H, left, top, right, bottom, work, st);
+    if (px == Px::U8C3)
+        if (const int rc = check_d16_zero_fill(st)) return rc;
+    if (px == Px::U16C3)
+        return launch_resize16_to((const uint16_t*)frames, (uint16_t*)out, W, H, left, top, right, bottom, oW, oH, order, work, st);
+    if (const int rc = launch_resize_tables_to(cw, ch, oW, oH, work, st)) return rc;
+    return launch_resize8_to(px, (const uint8_t*)frames, (uint8_t*)out, n, W, H, left, top, cw, oW, oH, up, work, order, st);
 }
 
 }  // namespace mf

@@ -13,10 +13,6 @@
 
 namespace mf {
 
-// x: ofs = sx (clamped into the crop), f = its fraction (0 where clamped);  y: ofs = sy0 | sy1 << 16 (clipped rows), f = the fraction
-struct Resize16Tab { int32_t ofs; float f; };
-static_assert(sizeof(Resize16Tab) == 8, "the 8-bit call's workspace holds the tables");
-
 __global__ __launch_bounds__(256) void resize16_tables_kernel(int cw, int ch, int W, int H, double scale_x, double scale_y,
                                                               Resize16Tab* __restrict__ xtab, Resize16Tab* __restrict__ ytab)
 {
@@ -95,6 +91,21 @@ int launch_resize16(const uint16_t* frames, uint16_t* out, int W, int H, int lef
     if (rc != MF_OK) return rc;
     hipLaunchKernelGGL(resize16_kernel, dim3(order.per_xcd * 8u), dim3(256), 0, st, frames, out, W, H, left, top, cw, xtab, ytab, order);
     return hip_fail(hipGetLastError(), "resize16_kernel launch");
+}
+
+// launch_crop_resize_to's launches for uint16 frames (shape, output size, rectangle and tile count already checked there)
+int launch_resize16_to(const uint16_t* frames, uint16_t* out, int W, int H, int left, int top, int right, int bottom, int oW, int oH,
+                       const TileOrder& order, void* work, hipStream_t st)
+{
+    const int cw = right - left + 1, ch = bottom - top + 1;
+    const double scale_x = 1.0 / ((double)oW / (double)cw), scale_y = 1.0 / ((double)oH / (double)ch);
+    Resize16Tab* xtab = (Resize16Tab*)work;
+    Resize16Tab* ytab = xtab + oW;
+    const int m = oW > oH ? oW : oH;
+    hipLaunchKernelGGL(resize16_tables_kernel, dim3((m + 255) / 256), dim3(256), 0, st, cw, ch, oW, oH, scale_x, scale_y, xtab, ytab);
+    int rc = hip_fail(hipGetLastError(), "resize16_tables_kernel launch");
+    if (rc != MF_OK) return rc;
+    return launch_resize16_to_kernel(frames, out, W, H, left, top, cw, oW, oH, 2 * oW == cw && 2 * oH == ch, xtab, ytab, order, st);
 }
 
 }  // namespace mf

@@ -41,11 +41,11 @@ def _border_samples(ctype, top, count):
 
 
 # One row per pixel format of the device path: the frames it takes and the C calls that serve them (include/meshflow_hip.h).
-PixelFormat = collections.namedtuple('PixelFormat', 'dtype channels border warp warp_bounds warp_clip crop_resize')
+PixelFormat = collections.namedtuple('PixelFormat', 'dtype channels border warp warp_bounds warp_clip crop_resize crop_resize_to')
 
 
 def _row(name, dtype, channels, ctype, top):
-    calls = (getattr(_lib_, f'mf_{op}_{name}') for op in ('warp', 'warp_bounds', 'warp_clip', 'crop_resize'))
+    calls = (getattr(_lib_, f'mf_{op}_{name}') for op in ('warp', 'warp_bounds', 'warp_clip', 'crop_resize', 'crop_resize_to'))
     return PixelFormat(dtype, channels, _border_samples(ctype, top, channels), *calls)
 
 
@@ -250,15 +250,41 @@ def crop_reduce(crop, W, H):
     return bounds
 
 
-def crop_resize(frames, bounds, out=None):
+def check_output_size(size, name='size'):
+    """A (width, height) output size -- cv2.resize's dsize order -- as two Python ints in 1 .. 32,767; ValueError otherwise."""
+    try:
+        w, h = size
+    except (TypeError, ValueError):
+        raise ValueError(f'{name} must be (width, height), got {size!r}') from None
+    for v in (w, h):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or not 1 <= int(v) <= 32767:
+            raise ValueError(f'{name} must be two ints in 1 .. 32767 (width, height), got {size!r}')
+    return int(w), int(h)
+
+
+def crop_resize(frames, bounds, out=None, size=None):
     """Crop to the inclusive (left, top, right, bottom) and resize back to (W, H): mfs.py:1111-1157.  frames: uint8 or uint16 (uint16:
-    cv2.resize's float path, mf_crop_resize_u16c3), or (n, H, W) uint8 (mf_crop_resize_u8c1); the output has the input's dtype and shape."""
+    cv2.resize's float path, mf_crop_resize_u16c3), or (n, H, W) uint8 (mf_crop_resize_u8c1); the output has the input's dtype and shape.
+    size=(width, height) (cv2.resize's dsize order) scales the crop to that size instead (mf_crop_resize_to_*): the output is then
+    (n, height, width[, 3]), and so must `out` be; size == (W, H) is the default call."""
     fmt = _frames_format(frames)
     n, H, W = frames.shape[:3]
     left, top, right, bottom = (int(v) for v in bounds)
-    out = _out_for(frames, fmt, out)
-    work = torch.empty(_lib_.mf_crop_resize_workspace_bytes(W, H), dtype=torch.uint8, device=frames.device)
-    _lib.check(fmt.crop_resize(_ptr(frames), _ptr(out), n, W, H, left, top, right, bottom, _ptr(work), _stream()))
+    if size is None:
+        out = _out_for(frames, fmt, out)
+        work = torch.empty(_lib_.mf_crop_resize_workspace_bytes(W, H), dtype=torch.uint8, device=frames.device)
+        _lib.check(fmt.crop_resize(_ptr(frames), _ptr(out), n, W, H, left, top, right, bottom, _ptr(work), _stream()))
+        return out
+    oW, oH = check_output_size(size)
+    shape = (n, oH, oW) + tuple(frames.shape[3:])
+    if out is None:
+        out = torch.empty(shape, dtype=frames.dtype, device=frames.device)
+    else:
+        _need(out, fmt.dtype, 'out')
+        if tuple(out.shape) != shape:
+            raise ValueError(f'out must have shape {shape} for size {(oW, oH)}, got {tuple(out.shape)}')
+    work = torch.empty(_lib_.mf_crop_resize_workspace_bytes(oW, oH), dtype=torch.uint8, device=frames.device)
+    _lib.check(fmt.crop_resize_to(_ptr(frames), _ptr(out), n, W, H, left, top, right, bottom, oW, oH, _ptr(work), _stream()))
     return out
 
 

@@ -35,26 +35,30 @@ def _torch_device_of(self):
     return dev
 
 
-# The host-frame C calls (csrc/hostpipe.hip) by HostClip.channels: warp, warp + _crop_frames, _crop_frames alone
-_HOST_CALLS = {3: ('mf_warp_u8c3_host_frames', 'mf_warp_crop_u8c3_host_frames', 'mf_crop_resize_u8c3_host_frames'),
-               1: ('mf_warp_u8c1_host_frames', 'mf_warp_crop_u8c1_host_frames', 'mf_crop_resize_u8c1_host_frames')}
+# The host-frame C calls (csrc/hostpipe.hip) by HostClip.channels: warp, warp + _crop_frames, _crop_frames alone, and the last two to a
+# caller-chosen output size
+_HOST_CALLS = {3: ('mf_warp_u8c3_host_frames', 'mf_warp_crop_u8c3_host_frames', 'mf_crop_resize_u8c3_host_frames',
+                   'mf_warp_crop_to_u8c3_host_frames', 'mf_crop_resize_to_u8c3_host_frames'),
+               1: ('mf_warp_u8c1_host_frames', 'mf_warp_crop_u8c1_host_frames', 'mf_crop_resize_u8c1_host_frames',
+                   'mf_warp_crop_to_u8c1_host_frames', 'mf_crop_resize_to_u8c1_host_frames')}
 
 
-def _warp_host_c(self, clip, unstab, stab, crop=False, keep_uncropped=True):
+def _warp_host_c(self, clip, unstab, stab, crop=False, keep_uncropped=True, output_size=None):
     """Host frames in -> host frames out through the C ABI's own chunked pipeline (csrc/hostpipe.hip:
     `mf_warp_u8c3_host_frames`, upload / kernel / download threads below Python, GIL released for the whole call).
     Grey clips (HostClip.channels == 1) take the u8c1 twins of these calls and come back as (F, H, W) arrays.
     Returns (stabilized frames (F, H, W, 3) uint8 array, clip-level crop bounds as np.int64 (left, top, right,
     bottom), mfs.py:1103-1106).  crop=True: `mf_warp_crop_u8c3_host_frames` -- the same pipeline followed by `_crop_frames`
     (mfs.py:159, 1111-1157) on the device; returns (stabilized frames or None when keep_uncropped is False, bounds,
-    cropped + resized frames (F, H, W, 3))."""
+    cropped + resized frames (F, H, W, 3)); output_size=(width, height) resizes the crop to that size instead
+    (`mf_warp_crop_to_u8c3_host_frames`: (F, height, width, 3))."""
     import ctypes
     import torch
     from . import _lib, ops, pipeline
     dev = self._torch_device()
     n, H, W = clip.num_frames, clip.height, clip.width
     frames = [clip.array[i] for i in range(n)] if clip.array is not None else clip.frames      # (validated by HostClip, every one of them)
-    warp_fn, warp_crop_fn, _ = (getattr(_lib.lib, name) for name in _HOST_CALLS[clip.channels])
+    warp_fn, warp_crop_fn, _, warp_crop_to_fn, _ = (getattr(_lib.lib, name) for name in _HOST_CALLS[clip.channels])
     fb = H * W * clip.channels
     want_out = keep_uncropped or not crop
     out = np.empty((n,) + clip.frame_shape, dtype=np.uint8) if want_out else None
@@ -72,10 +76,15 @@ def _warp_host_c(self, clip, unstab, stab, crop=False, keep_uncropped=True):
             bounds = (np.int64(per_frame[:, 0].max()), np.int64(per_frame[:, 1].max()),
                       np.int64(per_frame[:, 2].min()), np.int64(per_frame[:, 3].min()))
             return out, bounds
-        cropped = np.empty((n,) + clip.frame_shape, dtype=np.uint8)
-        pcrop = (ctypes.c_void_p * n)(*[cropped.ctypes.data + i * fb for i in range(n)])
+        oW, oH = output_size if output_size is not None else (W, H)
+        cropped = np.empty((n, oH, oW) + clip.frame_shape[2:], dtype=np.uint8)
+        fbc = oH * oW * clip.channels
+        pcrop = (ctypes.c_void_p * n)(*[cropped.ctypes.data + i * fbc for i in range(n)])
         rect = (ctypes.c_int32 * 4)()
-        _lib.check(warp_crop_fn(pin, pout, pcrop, *args, rect, None))
+        if output_size is None:
+            _lib.check(warp_crop_fn(pin, pout, pcrop, *args, rect, None))
+        else:
+            _lib.check(warp_crop_to_fn(pin, pout, pcrop, *args[:-1], oW, oH, args[-1], rect, None))
     return out, tuple(np.int64(v) for v in rect), cropped
 
 
@@ -229,7 +238,7 @@ class MeshFlowStabilizer:
 
     def stabilize_clip(self, unstabilized_frames, vertex_unstabilized_displacements_by_frame_index, homographies,
                        adaptive_weights_definition=ADAPTIVE_WEIGHTS_DEFINITION_ORIGINAL, crop=False,
-                       keep_uncropped=True, chunk_frames=16, io_threads=3):
+                       keep_uncropped=True, chunk_frames=16, io_threads=3, output_size=None):
         """The hot path of `stabilize` (mfs.py:150-159, 162) on in-memory inputs, with ONE host->device and ONE
         device->host pass over the frames (the two private methods below each pay their own, like any drop-in
         for NumPy-in / NumPy-out methods must).  The passes are chunked and overlapped with each other and with
@@ -241,10 +250,16 @@ class MeshFlowStabilizer:
         and, with crop=True, a fifth item: the cropped + resized frames (`_crop_frames`, mfs.py:159), produced
         on the device from the stabilized frames in the same pipeline once the clip-level rectangle is known
         (`mf_warp_crop_u8c3_host_frames`); keep_uncropped=False then never brings the uncropped stabilized frames back
-        (the reference only uses the cropped ones afterwards) and returns None for them."""
+        (the reference only uses the cropped ones afterwards) and returns None for them.  output_size=(width, height) (cv2.resize's
+        dsize order; needs crop=True) makes the fifth item the crop resized to that size instead of (W, H)
+        (`mf_warp_crop_to_u8c3_host_frames`); bounds, vertex paths and stability score do not change."""
         import torch
-        from . import pipeline
+        from . import ops, pipeline
         self._check_definition(adaptive_weights_definition)
+        if output_size is not None:
+            if not crop:
+                raise ValueError('output_size needs crop=True: it is the size of the cropped frames')
+            output_size = ops.check_output_size(output_size, 'output_size')
         if chunk_frames != 16 or io_threads != 3:
             import warnings
             warnings.warn('stabilize_clip: chunk_frames / io_threads are ignored since the frames travel through the C pipeline '
@@ -273,7 +288,7 @@ class MeshFlowStabilizer:
         scorer = threading.Thread(target=scoring, name='mf-score')
         scorer.start()
         try:
-            res = _warp_host_c(self, clip, unstab, stab, crop=crop, keep_uncropped=keep_uncropped)
+            res = _warp_host_c(self, clip, unstab, stab, crop=crop, keep_uncropped=keep_uncropped, output_size=output_size)
         finally:
             scorer.join()
         if 'error' in score:
@@ -352,27 +367,34 @@ class MeshFlowStabilizer:
         ops.vertex_motion_check(status)
         return d_disp.cpu().numpy(), d_vel.cpu().numpy()
 
-    def _crop_frames(self, uncropped_frames, crop_boundaries, chunk_frames=16, io_threads=3):
+    def _crop_frames(self, uncropped_frames, crop_boundaries, chunk_frames=16, io_threads=3, output_size=None):
         """mfs.py:1111-1157: crop to the inclusive bounds and resize back to (W, H) (cv2.resize, INTER_LINEAR).
         Host frames in, host frames out through the C ABI's ring of chunk buffers (`mf_crop_resize_u8c3_host_frames`,
         csrc/hostpipe.hip): upload, resize and download of the chunks all overlap, below Python.
+        output_size=(width, height) (cv2.resize's dsize order) resizes to that size instead: cv2.resize(crop, output_size)
+        (`mf_crop_resize_to_u8c3_host_frames`).
         (`chunk_frames` / `io_threads` are kept for callers of earlier versions; the C pipeline has its own, MF_PIPE_*.)"""
         import ctypes
         import torch
-        from . import _lib, pipeline
+        from . import _lib, ops, pipeline
+        if output_size is not None:
+            output_size = ops.check_output_size(output_size, 'output_size')
         dev = _torch_device_of(self)
         n = len(uncropped_frames)
         clip = pipeline.HostClip(uncropped_frames, n)
         H, W = clip.height, clip.width
         frames = [clip.array[i] for i in range(n)] if clip.array is not None else clip.frames       # (every frame validated by HostClip)
         left, top, right, bottom = (int(v) for v in crop_boundaries)
-        out = np.empty((n,) + clip.frame_shape, dtype=np.uint8)
-        fb = H * W * clip.channels
+        oW, oH = output_size if output_size is not None else (W, H)
+        out = np.empty((n, oH, oW) + clip.frame_shape[2:], dtype=np.uint8)
+        fb = oH * oW * clip.channels
         pin = (ctypes.c_void_p * n)(*[f.ctypes.data for f in frames])
         pout = (ctypes.c_void_p * n)(*[out.ctypes.data + i * fb for i in range(n)])
-        fn = getattr(_lib.lib, _HOST_CALLS[clip.channels][2])
         with torch.cuda.device(dev):
-            _lib.check(fn(pin, pout, n, W, H, left, top, right, bottom, None))
+            if output_size is None:
+                _lib.check(getattr(_lib.lib, _HOST_CALLS[clip.channels][2])(pin, pout, n, W, H, left, top, right, bottom, None))
+            else:
+                _lib.check(getattr(_lib.lib, _HOST_CALLS[clip.channels][4])(pin, pout, n, W, H, left, top, right, bottom, oW, oH, None))
         return list(out)
 
     def compute_scores(self, frame_width, frame_height, vertex_unstabilized_displacements_by_frame_index,

@@ -1,0 +1,180 @@
+"""-m gpu: crop-resize to a caller-chosen output size on the device -- mf_crop_resize_to_u8c3 / _u16c3 / _u8c1 and
+ops.crop_resize(size=...) -- equal, sample for sample, to cv2.resize(crop, (out_W, out_H)) INTER_LINEAR as the oracle restates it
+(oracle.meshflow_oracle.resize_linear_u8; grey = channel 0 of that on the frame repeated three times; uint16: tests/cv16_model.py's float
+path plus tests/cv16_area.py's exact-2x branch).  Upscale, downscale, mixed, 1-pixel crops and outputs, outputs larger than the frame,
+W % 4 != 0, unaligned stacks, many tiles, both sides of the staged / direct cut-over; the same size equals today's call byte for byte;
+every refusal leaves the output untouched."""
+import ctypes
+
+import numpy as np
+import pytest
+
+import cv16_area
+
+pytestmark = pytest.mark.gpu
+
+torch = pytest.importorskip('torch')
+
+from meshflow_amd import _lib, ops  # noqa: E402
+from oracle import meshflow_oracle as mo  # noqa: E402
+
+FORMATS = ('u8c3', 'u8c1', 'u16c3')
+
+
+@pytest.fixture(scope='module')
+def dev():
+    if not torch.cuda.is_available():
+        pytest.fail('no GPU visible: the -m gpu tests must run on an MI355X')
+    return torch.device('cuda:0')
+
+
+def frames_of(fmt, n, H, W, seed):
+    rng = np.random.default_rng(seed)
+    if fmt == 'u16c3':
+        return rng.integers(0, 65536, (n, H, W, 3), dtype=np.uint16)
+    return rng.integers(0, 256, (n, H, W, 3) if fmt == 'u8c3' else (n, H, W), dtype=np.uint8)
+
+
+def to_dev(a, dev):
+    a = np.ascontiguousarray(a)
+    t = torch.from_numpy(a.view(np.uint8)).to(dev)
+    return t.view(torch.uint16) if a.dtype == np.uint16 else t
+
+
+def to_np(t):
+    return t.contiguous().view(torch.uint8).cpu().numpy().view(np.uint16) if t.dtype == torch.uint16 else t.cpu().numpy()
+
+
+def reference(fmt, frames, rect, ow, oh):
+    l, t, r, b = rect
+    out = []
+    for f in frames:
+        crop = f[t:b + 1, l:r + 1]
+        if fmt == 'u8c3':
+            out.append(mo.resize_linear_u8(crop, ow, oh))
+        elif fmt == 'u8c1':
+            out.append(mo.resize_linear_u8(np.repeat(crop[..., None], 3, axis=2), ow, oh)[..., 0])
+        else:
+            out.append(cv16_area.resize_u16(crop, ow, oh))
+    return np.stack(out)
+
+
+# (n, H, W, rect, (out_W, out_H)): what each covers
+CASES = [
+    (3, 48, 64, (5, 3, 40, 30), (90, 70)),            # upscale, non-integer ratios
+    (3, 120, 200, (3, 5, 190, 110), (61, 37)),        # downscale, non-integer
+    (2, 160, 96, (10, 10, 50, 150), (120, 40)),       # up in x, down in y
+    (2, 96, 160, (10, 10, 150, 50), (40, 120)),       # down in x, up in y
+    (3, 90, 130, (1, 3, 120, 82), (60, 40)),          # exactly 2x down (u16: INTER_AREA's fast path)
+    (2, 95, 127, (2, 1, 121, 90), (40, 30)),          # exactly 3x down
+    (2, 33, 47, (4, 2, 40, 30), (1, 1)),              # 1 x 1 output
+    (2, 33, 47, (4, 2, 40, 30), (1, 37)),             # 1 x N
+    (2, 33, 47, (4, 2, 40, 30), (29, 1)),             # N x 1
+    (2, 21, 19, (5, 7, 5, 7), (17, 9)),               # 1-pixel crop
+    (2, 21, 19, (0, 7, 18, 7), (13, 5)),              # 1-row crop, down in x
+    (2, 30, 41, (0, 0, 40, 29), (301, 203)),          # output larger than the frame
+    (2, 31, 67, (3, 2, 66, 30), (129, 61)),           # W % 4 != 0 in and out
+    (2, 40, 700, (20, 0, 619, 39), (250, 20)),        # 2.4x in x: u8c3 staged
+    (2, 40, 1000, (10, 0, 684, 39), (250, 20)),       # 2.7x in x: just above the u8c3 cut-over
+    (2, 40, 900, (20, 0, 819, 39), (250, 20)),        # 3.2x in x: u8c3 direct, u8c1 staged
+    (2, 40, 1400, (20, 0, 1269, 39), (250, 20)),      # 5x in x: both direct
+    (1, 300, 1000, (0, 0, 999, 299), (97, 29)),       # ~10x down in both axes
+    (20, 64, 300, (7, 5, 290, 60), (700, 90)),        # many frames and tiles (XCD tile order), up
+    (20, 300, 520, (7, 5, 510, 290), (170, 150)),     # many frames, down
+]
+
+
+@pytest.mark.parametrize('fmt', FORMATS)
+@pytest.mark.parametrize('case', range(len(CASES)))
+def test_matches_cv2_resize_model(dev, fmt, case):
+    n, H, W, rect, (ow, oh) = CASES[case]
+    frames = frames_of(fmt, n, H, W, seed=100 + case)
+    got = ops.crop_resize(to_dev(frames, dev), rect, size=(ow, oh))
+    torch.cuda.synchronize()
+    assert tuple(got.shape) == (n, oh, ow) + frames.shape[3:]
+    want = reference(fmt, frames, rect, ow, oh)
+    g = to_np(got)
+    assert np.array_equal(g, want), (fmt, CASES[case], int((g != want).sum()))
+
+
+def test_u16_exact_2x_takes_the_area_branch(dev):
+    """The 2x case above is only a test of the area branch where the float path would differ: check that it does on these frames."""
+    from cv16_model import resize_linear_u16
+    n, H, W, (l, t, r, b), (ow, oh) = CASES[4]
+    frames = frames_of('u16c3', n, H, W, seed=104)
+    crop = frames[0, t:b + 1, l:r + 1]
+    assert not np.array_equal(cv16_area.area_fast_u16(crop), resize_linear_u16(crop, ow, oh))
+    got = to_np(ops.crop_resize(to_dev(frames, dev), (l, t, r, b), size=(ow, oh)))
+    assert np.array_equal(got[0], cv16_area.area_fast_u16(crop))
+
+
+@pytest.mark.parametrize('fmt', FORMATS)
+def test_same_size_is_todays_call(dev, fmt):
+    n, H, W = 4, 70, 99
+    frames = to_dev(frames_of(fmt, n, H, W, seed=5), dev)
+    for rect in ((3, 2, 90, 60), (0, 0, W - 1, H - 1), (10, 10, 10, 10)):
+        assert torch.equal(ops.crop_resize(frames, rect, size=(W, H)), ops.crop_resize(frames, rect))
+
+
+@pytest.mark.parametrize('fmt', FORMATS)
+def test_unaligned_stacks(dev, fmt):
+    """Frames and output at every misalignment a stack of this format can have (u8: 1-3 bytes, u16: 2 bytes), cut to end exactly at the
+    end of their allocation."""
+    n, H, W, rect = 3, 37, 53, (2, 3, 50, 33)
+    frames = frames_of(fmt, n, H, W, seed=9)
+    raw = np.ascontiguousarray(frames).view(np.uint8).reshape(-1)
+    step = 2 if fmt == 'u16c3' else 1
+    call = getattr(_lib.lib, f'mf_crop_resize_to_{fmt}')
+    for ow, oh in ((71, 45), (20, 11), (W, H)):
+        want = reference(fmt, frames, rect, ow, oh)
+        ob = want.nbytes
+        for mis in range(step, 4, step):
+            src = torch.empty(raw.size + mis, dtype=torch.uint8, device=dev)
+            src[mis:] = torch.from_numpy(raw).to(dev)
+            dst = torch.empty(ob + mis, dtype=torch.uint8, device=dev)
+            work = torch.empty(_lib.lib.mf_crop_resize_workspace_bytes(ow, oh), dtype=torch.uint8, device=dev)
+            rc = call(ctypes.c_void_p(src.data_ptr() + mis), ctypes.c_void_p(dst.data_ptr() + mis), n, W, H, *rect, ow, oh,
+                      ctypes.c_void_p(work.data_ptr()), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+            assert rc == 0, _lib.lib.mf_last_error()
+            torch.cuda.synchronize()
+            got = dst[mis:].cpu().numpy().view(want.dtype).reshape(want.shape)
+            assert np.array_equal(got, want), (fmt, ow, oh, mis)
+
+
+@pytest.mark.parametrize('fmt', FORMATS)
+def test_refusals_leave_the_output_untouched(dev, fmt):
+    n, H, W = 2, 30, 40
+    frames = to_dev(frames_of(fmt, n, H, W, seed=11), dev)
+    out = torch.full((4 * 1024 * 1024,), 0xA5, dtype=torch.uint8, device=dev)
+    work = torch.empty(_lib.lib.mf_crop_resize_workspace_bytes(32767, 32767), dtype=torch.uint8, device=dev)
+    call = getattr(_lib.lib, f'mf_crop_resize_to_{fmt}')
+    st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    F, O, Wk = (ctypes.c_void_p(t.data_ptr()) for t in (frames, out, work))
+    good = (n, W, H, 2, 3, 30, 20, 25, 15)
+    bad = [
+        (None, O, *good, Wk), (F, None, *good, Wk), (F, O, *good, None), (F, F, *good, Wk),                 # null / aliasing pointers
+        (F, O, n, W, H, 2, 3, 30, 20, 0, 15, Wk), (F, O, n, W, H, 2, 3, 30, 20, 25, 0, Wk),                 # output sizes
+        (F, O, n, W, H, 2, 3, 30, 20, 32768, 15, Wk), (F, O, n, W, H, 2, 3, 30, 20, 25, -1, Wk),
+        (F, O, n, W, H, 20, 3, 10, 20, 25, 15, Wk), (F, O, n, W, H, 2, 20, 30, 10, 25, 15, Wk),             # empty rectangles
+        (F, O, n, W, H, -1, 3, 30, 20, 25, 15, Wk), (F, O, n, W, H, 2, 3, W, 20, 25, 15, Wk),               # out of the frame
+        (F, O, n, W, H, 2, 3, 30, H, 25, 15, Wk),
+        (F, O, 0, W, H, 2, 3, 30, 20, 25, 15, Wk), (F, O, n, 0, H, 0, 0, 0, 0, 25, 15, Wk),                 # shapes
+        (F, O, 1 << 20, W, H, 2, 3, 30, 20, 32767, 32767, Wk),                                              # too many tiles
+    ]
+    for args in bad:
+        rc = call(*args, st)
+        assert rc == _lib.MF_ERR_INVALID_ARG, args
+        assert f'mf_crop_resize_to_{fmt}' in _lib.lib.mf_last_error().decode(), _lib.lib.mf_last_error()
+    torch.cuda.synchronize()
+    assert bool((out == 0xA5).all())
+
+
+def test_ops_size_checks(dev):
+    frames = to_dev(frames_of('u8c3', 2, 20, 30, seed=1), dev)
+    for size in ((0, 5), (5, 0), (32768, 5), (5.0, 5), (5,), 'ab', (True, 5), (5, 5, 5)):
+        with pytest.raises(ValueError):
+            ops.crop_resize(frames, (0, 0, 9, 9), size=size)
+    with pytest.raises(ValueError):
+        ops.crop_resize(frames, (0, 0, 9, 9), out=torch.empty((2, 20, 30, 3), dtype=torch.uint8, device=dev), size=(31, 20))
+    out = torch.empty((2, 7, 31, 3), dtype=torch.uint8, device=dev)
+    assert ops.crop_resize(frames, (0, 0, 9, 9), out=out, size=(31, 7)) is out
