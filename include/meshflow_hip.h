@@ -179,6 +179,24 @@ int mf_warp_clip_u8c1(const uint8_t* d_frames, uint8_t* d_out, const double* d_u
                       int R, int C, uint8_t border, void* d_table, int32_t* d_crop, int32_t* d_bounds, int32_t* d_status,
                       int chunks, void* prep_stream, void* stream);
 
+/* ---- the same warp for 4-channel uint8 frames (B G R A, or R G B A: the kernels do not care which colour comes first) ----
+ * d_frames, d_out: [n][H][W][4] uint8, any alignment (a 4-byte aligned clip gets the staged taps); all offsets are 64-bit.  cv2.remap's 8-bit
+ * path works per channel, so out[..., 0:3] is byte for byte mf_warp_u8c3 of frames[..., 0:3] with border (b, g, r), and out[..., 3] is
+ * byte for byte mf_warp_u8c1 of frames[..., 3] with border a; the ownership, coordinates, crop flags, clip rectangle and degenerate-mesh
+ * status are the uint8 BGR call's on the same table (d_crop / d_bounds identical).  border_bgra: {b, g, r, a} as given.  A caller that
+ * holds a 3-component border (cv::Scalar(b, g, r) pads to (b, g, r, 0), as the reference's color_outside_image_area_bgr does) passes
+ * a = 0: the area the warp uncovers then comes out with alpha 0, and with input alpha 255 the output alpha is 255 x coverage with the
+ * bilinear soft edge.  Limits: 2 <= W, H <= 32,767, R, C <= 64.  mf_warp_clip_u8c4 is mf_warp_clip_u8c3 (mfs.py:909-1108) with the same
+ * `chunks` / `prep_stream` semantics; it refuses what its warp would refuse before the cell table is launched.  Null pointers,
+ * d_frames == d_out and bad sizes return MF_ERR_INVALID_ARG before anything is launched. */
+int mf_warp_u8c4(const uint8_t* d_frames, uint8_t* d_out, const void* d_table, int n, int W, int H,
+                 int R, int C, const uint8_t border_bgra[4], int32_t* d_crop, void* stream);
+int mf_warp_bounds_u8c4(const uint8_t* d_frames, uint8_t* d_out, const void* d_table, int n, int W, int H,
+                        int R, int C, const uint8_t border_bgra[4], int32_t* d_crop, int32_t* d_bounds, void* stream);
+int mf_warp_clip_u8c4(const uint8_t* d_frames, uint8_t* d_out, const double* d_unstab, const double* d_stab, int n, int W, int H,
+                      int R, int C, const uint8_t border_bgra[4], void* d_table, int32_t* d_crop, int32_t* d_bounds, int32_t* d_status,
+                      int chunks, void* prep_stream, void* stream);
+
 /* Clip-level crop bounds (mfs.py:1103-1106): {max left, max top, min right, min bottom} over n frames.
  * d_bounds: [4] int32. */
 int mf_crop_reduce(const int32_t* d_crop, int n, int W, int H, int32_t* d_bounds, void* stream);
@@ -202,8 +220,13 @@ int mf_crop_resize_u16c3(const uint16_t* d_frames, uint16_t* d_out, int n, int W
  * refusals. */
 int mf_crop_resize_u8c1(const uint8_t* d_frames, uint8_t* d_out, int n, int W, int H, int left, int top, int right,
                         int bottom, void* d_work, void* stream);
+/* The same for 4-channel uint8 frames [n][H][W][4]: channels 0-2 of the output are mf_crop_resize_u8c3 of frames[..., 0:3], channel 3 is
+ * mf_crop_resize_u8c1 of frames[..., 3] (cv2.resize's 8-bit path works per channel; the same tables, the same workspace size).
+ * 1 <= W, H <= 32,767; the same refusals. */
+int mf_crop_resize_u8c4(const uint8_t* d_frames, uint8_t* d_out, int n, int W, int H, int left, int top, int right,
+                        int bottom, void* d_work, void* stream);
 /* _crop_frames to a caller-chosen output size: the same crop, scaled to out_W x out_H exactly like cv2.resize(crop, (out_W, out_H)) with
- * INTER_LINEAR, for the three formats above (u16c3: where the crop is exactly twice the output in both axes, cv::resize takes INTER_AREA's
+ * INTER_LINEAR, for the four formats above (u16c3: where the crop is exactly twice the output in both axes, cv::resize takes INTER_AREA's
  * fast path, (S00 + S01 + S10 + S11 + 2) >> 2, rounded half up; for 8-bit data that equals the bilinear result).  d_out holds
  * n * out_H * out_W * channels samples.  d_work: mf_crop_resize_workspace_bytes(out_W, out_H) bytes suffice (the tables have one entry per
  * OUTPUT column and row; no separate workspace call).  out_W, out_H == W, H is the call above, byte for byte.  Refused with
@@ -214,6 +237,8 @@ int mf_crop_resize_to_u8c3(const uint8_t* d_frames, uint8_t* d_out, int n, int W
 int mf_crop_resize_to_u16c3(const uint16_t* d_frames, uint16_t* d_out, int n, int W, int H, int left, int top, int right, int bottom,
                             int out_W, int out_H, void* d_work, void* stream);
 int mf_crop_resize_to_u8c1(const uint8_t* d_frames, uint8_t* d_out, int n, int W, int H, int left, int top, int right, int bottom,
+                           int out_W, int out_H, void* d_work, void* stream);
+int mf_crop_resize_to_u8c4(const uint8_t* d_frames, uint8_t* d_out, int n, int W, int H, int left, int top, int right, int bottom,
                            int out_W, int out_H, void* d_work, void* stream);
 
 /* ---- the row before the path: vertex-motion accumulation (mfs.py:236-452 from the matched features on) ----

@@ -151,6 +151,12 @@ int mf_warp_u8c1(const uint8_t* d_frames, uint8_t* d_out, const void* d_table, i
     return warp_entry("mf_warp_u8c1", Px::U8C1, d_frames, d_out, d_table, n, W, H, R, C, &border, d_crop, false, nullptr, stream);
 }
 
+int mf_warp_u8c4(const uint8_t* d_frames, uint8_t* d_out, const void* d_table, int n, int W, int H,
+                 int R, int C, const uint8_t border_bgra[4], int32_t* d_crop, void* stream)
+{
+    return warp_entry("mf_warp_u8c4", Px::U8C4, d_frames, d_out, d_table, n, W, H, R, C, border_bgra, d_crop, false, nullptr, stream);
+}
+
 int mf_crop_scan_f64(const void* d_table, int n, int W, int H, int R, int C, int32_t* d_crop, void* stream)
 {
     if (!d_table || !d_crop) { set_error("mf_crop_scan_f64: null pointer"); return MF_ERR_INVALID_ARG; }
@@ -187,6 +193,12 @@ int mf_warp_bounds_u8c1(const uint8_t* d_frames, uint8_t* d_out, const void* d_t
                         int R, int C, uint8_t border, int32_t* d_crop, int32_t* d_bounds, void* stream)
 {
     return warp_entry("mf_warp_bounds_u8c1", Px::U8C1, d_frames, d_out, d_table, n, W, H, R, C, &border, d_crop, true, d_bounds, stream);
+}
+
+int mf_warp_bounds_u8c4(const uint8_t* d_frames, uint8_t* d_out, const void* d_table, int n, int W, int H,
+                        int R, int C, const uint8_t border_bgra[4], int32_t* d_crop, int32_t* d_bounds, void* stream)
+{
+    return warp_entry("mf_warp_bounds_u8c4", Px::U8C4, d_frames, d_out, d_table, n, W, H, R, C, border_bgra, d_crop, true, d_bounds, stream);
 }
 
 int mf_crop_scan_bounds_f64(const void* d_table, int n, int W, int H, int R, int C, int32_t* d_crop, int32_t* d_bounds, void* stream)
@@ -227,6 +239,12 @@ int mf_crop_resize_u8c1(const uint8_t* d_frames, uint8_t* d_out, int n, int W, i
     return crop_resize_entry("mf_crop_resize_u8c1", Px::U8C1, d_frames, d_out, n, W, H, left, top, right, bottom, d_work, stream);
 }
 
+int mf_crop_resize_u8c4(const uint8_t* d_frames, uint8_t* d_out, int n, int W, int H, int left, int top, int right,
+                        int bottom, void* d_work, void* stream)
+{
+    return crop_resize_entry("mf_crop_resize_u8c4", Px::U8C4, d_frames, d_out, n, W, H, left, top, right, bottom, d_work, stream);
+}
+
 int mf_crop_resize_to_u8c3(const uint8_t* d_frames, uint8_t* d_out, int n, int W, int H, int left, int top, int right, int bottom,
                            int out_W, int out_H, void* d_work, void* stream)
 {
@@ -245,6 +263,13 @@ int mf_crop_resize_to_u8c1(const uint8_t* d_frames, uint8_t* d_out, int n, int W
                            int out_W, int out_H, void* d_work, void* stream)
 {
     return crop_resize_to_entry("mf_crop_resize_to_u8c1", Px::U8C1, d_frames, d_out, n, W, H, left, top, right, bottom, out_W, out_H, d_work,
+                                stream);
+}
+
+int mf_crop_resize_to_u8c4(const uint8_t* d_frames, uint8_t* d_out, int n, int W, int H, int left, int top, int right, int bottom,
+                           int out_W, int out_H, void* d_work, void* stream)
+{
+    return crop_resize_to_entry("mf_crop_resize_to_u8c4", Px::U8C4, d_frames, d_out, n, W, H, left, top, right, bottom, out_W, out_H, d_work,
                                 stream);
 }
 

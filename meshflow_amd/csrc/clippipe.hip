@@ -158,3 +158,11 @@ extern "C" int mf_warp_clip_u8c1(const uint8_t* d_frames, uint8_t* d_out, const 
     return warp_clip("mf_warp_clip_u8c1", Px::U8C1, d_frames, d_out, d_unstab, d_stab, n, W, H, R, C, &border, d_table, d_crop, d_bounds,
                      d_status, chunks, prep_stream, stream);
 }
+
+extern "C" int mf_warp_clip_u8c4(const uint8_t* d_frames, uint8_t* d_out, const double* d_unstab, const double* d_stab, int n, int W, int H,
+                                 int R, int C, const uint8_t border_bgra[4], void* d_table, int32_t* d_crop, int32_t* d_bounds,
+                                 int32_t* d_status, int chunks, void* prep_stream, void* stream)
+{
+    return warp_clip("mf_warp_clip_u8c4", Px::U8C4, d_frames, d_out, d_unstab, d_stab, n, W, H, R, C, border_bgra, d_table, d_crop, d_bounds,
+                     d_status, chunks, prep_stream, stream);
+}

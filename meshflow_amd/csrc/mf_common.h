@@ -222,15 +222,15 @@ inline bool make_tile_order(int tiles_x, int tiles_y, int n, TileOrder& o)
 
 
 
-// Pixel format of a frame stack: the _u8c3 / _u16c3 / _u8c1 calls of include/meshflow_hip.h.  Every layer takes the format as this one
-// parameter; a new format is a row here plus its kernels.
-enum class Px { U8C3, U16C3, U8C1 };
-constexpr int px_channels(Px p) { return p == Px::U8C1 ? 1 : 3; }
+// Pixel format of a frame stack: the _u8c3 / _u16c3 / _u8c1 / _u8c4 calls of include/meshflow_hip.h.  Every layer takes the format as this
+// one parameter; a new format is a row here plus its kernels.
+enum class Px { U8C3, U16C3, U8C1, U8C4 };
+constexpr int px_channels(Px p) { return p == Px::U8C1 ? 1 : p == Px::U8C4 ? 4 : 3; }
 constexpr int px_sample_bytes(Px p) { return p == Px::U16C3 ? 2 : 1; }
 constexpr int px_bytes(Px p) { return px_channels(p) * px_sample_bytes(p); }
-constexpr const char* px_name(Px p) { return p == Px::U8C3 ? "u8c3" : p == Px::U16C3 ? "u16c3" : "u8c1"; }
+constexpr const char* px_name(Px p) { return p == Px::U8C3 ? "u8c3" : p == Px::U16C3 ? "u16c3" : p == Px::U8C1 ? "u8c1" : "u8c4"; }
 // The border colour as the warp kernels take it, from the caller's px_channels(p) samples: B | G << 8 | R << 16 (u8c3),
-// B | G << 16 | R << 32 (u16c3), the byte (u8c1).
+// B | G << 16 | R << 32 (u16c3), the byte (u8c1), B | G << 8 | R << 16 | A << 24 (u8c4).
 inline uint64_t pack_border(Px p, const void* samples)
 {
     uint64_t v = 0;
@@ -268,6 +268,7 @@ struct WarpRange {
     const void* frames; void* out; int32_t* crop; int32_t* bounds; int m;
 };
 void launch_warp8c1_range(const WarpGeom& g, const WarpRange& r, int W, int H, int C, uint32_t border, bool stage, hipStream_t st);  // warp_c1.hip
+void launch_warp8c4_range(const WarpGeom& g, const WarpRange& r, int W, int H, int C, uint32_t border, bool stage, hipStream_t st);  // warp_c4.hip
 int launch_crop_scan(const TableView& tv, int n, int W, int H, int R, int C, int32_t* crop, hipStream_t st);
 int check_d16_zero_fill(hipStream_t st);          // warp.hip: one-time device check the byte-tap kernels rely on
 int launch_selftest_recip(unsigned long long n, unsigned long long seed, unsigned long long* d_mismatches, hipStream_t st);
@@ -289,6 +290,11 @@ int launch_resize16(const uint16_t* frames, uint16_t* out, int W, int H, int lef
                     void* work, hipStream_t st);
 int launch_resize8c1(const uint8_t* frames, uint8_t* out, int n, int W, int H, int left, int top, int cw, const void* work,
                      const TileOrder& order, hipStream_t st);
+// resize_c4.hip: the u8c4 kernels on resize.hip's tables (already built) for an oW x oH output (oW x oH == W x H: the same-size call; `up`: oW >=
+// cw and oH >= ch), and their tile rows
+int launch_resize8c4(const uint8_t* frames, uint8_t* out, int n, int W, int H, int left, int top, int cw, int oW, int oH, bool up,
+                     const void* work, const TileOrder& order, hipStream_t st);
+int resize8c4_tile_rows(bool up);
 // resize.hip: every check of a crop-resize call to an oW x oH output, then the format's tables and kernel (oW x oH == W x H: launch_crop_resize)
 int launch_crop_resize_to(Px px, const void* frames, void* out, int n, int W, int H, int left, int top, int right, int bottom, int oW, int oH,
                           void* work, hipStream_t st);

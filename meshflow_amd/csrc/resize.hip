@@ -217,7 +217,7 @@ int launch_crop_resize(Px px, const void* frames, void* out, int n, int W, int H
                   "fail on an empty source)", name, left, top, right, bottom, W, H);
         return MF_ERR_INVALID_ARG;
     }
-    // tiles: 256 pixels of kWaves * kRows output rows (resize16_kernel: of one row)
+    // tiles: 256 pixels of kWaves * kRows output rows (resize16_kernel: of one row; resize8c4_kernel's same-size instantiation: the same)
     const int tile_rows = px == Px::U16C3 ? 1 : kWaves * kRows;
     TileOrder order;
     if (!make_tile_order((W + 255) / 256, (H + tile_rows - 1) / tile_rows, n, order)) {
@@ -228,6 +228,7 @@ int launch_crop_resize(Px px, const void* frames, void* out, int n, int W, int H
     if (const int rc = launch_resize_tables(W, H, left, top, right, bottom, work, st)) return rc;
     const int cw = right - left + 1;
     if (px == Px::U8C1) return launch_resize8c1((const uint8_t*)frames, (uint8_t*)out, n, W, H, left, top, cw, work, order, st);
+    if (px == Px::U8C4) return launch_resize8c4((const uint8_t*)frames, (uint8_t*)out, n, W, H, left, top, cw, W, H, true, work, order, st);
     const ResizeTab* xtab = (const ResizeTab*)work;
     const ResizeTab* ytab = xtab + W;
     hipLaunchKernelGGL(resize_kernel, dim3(order.per_xcd * 8u), dim3(64 * kWaves), 0, st, (const uint8_t*)frames, (uint8_t*)out, n, W, H, left, top,
@@ -268,6 +269,8 @@ int launch_crop_resize_to(Px px, const void* frames, void* out, int n, int W, in
     if (px == Px::U16C3)
         return launch_resize16_to((const uint16_t*)frames, (uint16_t*)out, W, H, left, top, right, bottom, oW, oH, order, work, st);
     if (const int rc = launch_resize_tables_to(cw, ch, oW, oH, work, st)) return rc;
+    if (px == Px::U8C4)
+        return launch_resize8c4((const uint8_t*)frames, (uint8_t*)out, n, W, H, left, top, cw, oW, oH, up, work, order, st);
     return launch_resize8_to(px, (const uint8_t*)frames, (uint8_t*)out, n, W, H, left, top, cw, oW, oH, up, work, order, st);
 }
 

@@ -353,6 +353,7 @@ __global__ __launch_bounds__(256) void resize16_to_kernel(const uint16_t* __rest
 int resize_to_tile_rows(Px px, bool up)
 {
     if (px == Px::U16C3) return 1;
+    if (px == Px::U8C4) return resize8c4_tile_rows(up);
     if (px == Px::U8C1) return kWaves * (up ? kRows : kDown1Rows);
     return kWaves * (up ? kRows : kDownRows);
 }

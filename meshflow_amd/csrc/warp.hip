@@ -874,6 +874,154 @@ __device__ __forceinline__ void remap_store_u8c1(const float (&u)[4], const floa
     }
 }
 
+// ---- 4-channel uint8 frames: cv2.remap of CV_8UC4 -- the 8-bit fixed-point path of CV_8UC3 on four channels: channels 0-2 come out as the
+// u8c3 warp's, channel 3 as the u8c1 warp's on the alpha plane ------------------------------------------------------------------------------
+// The 4-byte window: the plan's STAGED window (cut for 3-byte pixels) re-cut for 4-byte pixels, with the grey window's words (GreyWindow: first
+// row, first column).  sy0 and bs as for the grey window; the first column is gx = min(bs / 3, W - MF_C4_COLS) >= sx0 - 1 (bs >= 3 sx0 - 3), and
+// MF_C4_COLS columns from there hold every tap the plan certifies (columns sx0 .. sx0 + 53 at most, or clamped to W - 1) while the copy never
+// leaves the frame (the window is taken only for frames of at least MF_C4_COLS columns).  A row is MF_C4_PITCH = 14 chunks of 16 bytes; 12 rows
+// (9 for COMPACT regions) are at most 168 chunks: three global->LDS loads per lane, 2,688 bytes of LDS.  A pixel's two horizontal taps are 8
+// contiguous dword-aligned bytes there.
+constexpr int MF_C4_COLS = 56;
+constexpr int MF_C4_PITCH = 4 * MF_C4_COLS;
+
+// The blend of one 4-byte pixel from its taps p00 / p01 (row iy, columns ix and ix + 1) and p10 / p11 (row iy + 1) at fixed-point coordinates
+// (sx, sy): per channel the two horizontal neighbours in the 16-bit halves of one register (one v_perm_b32 per tap row), both lerped vertically
+// at once, then v_dot2_u32_u16 horizontally with the weights scaled so that the rounded byte lands in byte 2 -- blend_pixel's arithmetic,
+// (sum w_k s_k + 2^14) >> 15 per channel.  Returns B | G << 8 | R << 16 | A << 24.
+__device__ __forceinline__ uint32_t blend_c4(uint32_t p00, uint32_t p01, uint32_t p10, uint32_t p11, uint32_t sx, uint32_t sy)
+{
+    const uint32_t fy = sy & 31u, wy = 32u - fy;
+    const uint32_t wq = umad24(sx & 31u, 0x3FFFC0u, 2048u);               // 64 (32 - fx) | 64 fx << 16
+    uint32_t o[4];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        const uint32_t sel = 0x0C040C00u + 0x00010001u * (uint32_t)c;     // byte c of the first tap, byte c of the second in bits 16-23
+        const uint32_t vc = umad24(__builtin_amdgcn_perm(p11, p10, sel), fy, __umul24(__builtin_amdgcn_perm(p01, p00, sel), wy));
+        o[c] = udot2(vc, wq, 32768u);
+    }
+    return __builtin_amdgcn_perm(o[1], o[0], 0x0C0C0602u) | __builtin_amdgcn_perm(o[3], o[2], 0x06020C0Cu);
+}
+
+// Footprint-level tail of the U8C4 instantiation of footprint_body: the lane's four pixels at source coordinates (u, v) -- taps, blend, crop
+// flags, one 16-byte store.  Deep-interior footprints take their taps from the 4-byte window in LDS when the plan staged one (`win.on`: two
+// dword-pair reads per pixel), else two 8-byte loads per pixel from the frame; the others take every tap at its position clamped into the frame
+// and replace outside taps by `border` (the whole B G R A word).  All frame offsets are 64-bit.
+__device__ __forceinline__ void remap_store_u8c4(const float (&u)[4], const float (&v)[4], uint32_t f, int x0, int y, bool active, int W, int H,
+                                                 const uint8_t* __restrict__ frames, uint8_t* __restrict__ out, uint32_t border,
+                                                 int32_t* __restrict__ crop, int32_t* __restrict__ clip, const GreyWindow& win,
+                                                 const uint8_t* s_win)
+{
+    const uint64_t frame_bytes = 4ull * (uint64_t)((uint32_t)W * (uint32_t)H);
+    const uint8_t* __restrict__ src = frames + (uint64_t)f * frame_bytes;
+    uint8_t* __restrict__ dst = out + (uint64_t)f * frame_bytes;
+    const int lane = threadIdx.x;
+    uint32_t bx[4], by[4];
+    fixed_point(u, v, bx, by);
+    uint32_t dxm = 0, dym = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        dxm = max(dxm, bx[j] - (0x4B400000u + 64u));
+        dym = max(dym, by[j] - (0x4B400000u + 64u));
+    }
+    // deep interior (as in footprint_body): 2 <= ix <= W-3 and 2 <= iy <= H-3 for all four pixels
+    const bool deep = W >= 5 && H >= 5 && dxm <= (uint32_t)(32 * (W - 3) + 31 - 64) && dym <= (uint32_t)(32 * (H - 3) + 31 - 64);
+    const bool fast = __ballot(active && !deep) == 0;
+    uint32_t o[4];                                                      // the lane's 4 output pixels
+    int c_left = 0, c_top = 0, c_right = W - 1, c_bottom = H - 1;
+    if (win.on) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // the 4-byte window has landed in LDS
+    if (active) {
+        if (fast && win.on) {
+            typedef const __attribute__((address_space(3))) uint32_t* lds_words_t;
+            const lds_words_t w = (lds_words_t)lds_ptr(s_win);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const uint32_t ix = __builtin_amdgcn_ubfe(bx[j], 5, 17), iy = __builtin_amdgcn_ubfe(by[j], 5, 17);
+                const uint32_t a = umad24(iy - win.row0, (uint32_t)(MF_C4_PITCH / 4), ix - win.col0);       // in dwords
+                o[j] = blend_c4(w[a], w[a + 1], w[a + MF_C4_PITCH / 4], w[a + MF_C4_PITCH / 4 + 1], bx[j], by[j]);
+            }
+        } else if (fast) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const uint32_t ix = __builtin_amdgcn_ubfe(bx[j], 5, 17), iy = __builtin_amdgcn_ubfe(by[j], 5, 17);
+                const uint8_t* __restrict__ p = src + 4ull * (uint64_t)(iy * (uint32_t)W + ix);
+                uint2 a, b;                                             // pixels ix and ix + 1 of rows iy and iy + 1
+                __builtin_memcpy(&a, p, 8);
+                __builtin_memcpy(&b, p + 4ull * (uint32_t)W, 8);
+                o[j] = blend_c4(a.x, a.y, b.x, b.y, bx[j], by[j]);
+            }
+        } else {
+            // frame borders, uncovered pixels (at (W+1, H+1)), crop flags, out-of-range coordinates
+            const float fWm1 = (float)(W - 1), fHm1 = (float)(H - 1);
+            uint32_t spread = 0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                spread = max(spread, max(bx[j] - (0x4B400000u - 0x200000u), by[j] - (0x4B400000u - 0x200000u)));
+            const bool narrow = __ballot(spread >= 0x400000u) == 0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float uu = u[j], vv = v[j];
+                const int x = x0 + j;
+                if (x < W) {                                            // crop-boundary scan, mfs.py:1075-1098 (exact: Sterbenz)
+                    if (fabsf(uu) < 1.0f) c_left = max(c_left, x);
+                    if (fabsf(uu - fWm1) < 1.0f) c_right = min(c_right, x);
+                    if (fabsf(vv) < 1.0f) c_top = max(c_top, y);
+                    if (fabsf(vv - fHm1) < 1.0f) c_bottom = min(c_bottom, y);
+                }
+                const int sxx = narrow ? (int)(bx[j] - 0x4B400000u) : cv_round_f32(uu * 32.0f);
+                const int syy = narrow ? (int)(by[j] - 0x4B400000u) : cv_round_f32(vv * 32.0f);
+                const int ix = sxx >> 5, iy = syy >> 5;                 // (saturation to int16 cannot change any decision below)
+                // (a 2 x 2 footprint wholly outside needs no special case: four border taps with weights summing to 1024 give the border)
+                const bool in_x0 = (unsigned)ix < (unsigned)W, in_x1 = (unsigned)(ix + 1) < (unsigned)W;
+                const bool in_y0 = (unsigned)iy < (unsigned)H, in_y1 = (unsigned)(iy + 1) < (unsigned)H;
+                const uint32_t cx0 = (uint32_t)min(max(ix, 0), W - 1), cx1 = (uint32_t)min(max(ix + 1, 0), W - 1);
+                const uint32_t r0 = (uint32_t)min(max(iy, 0), H - 1) * (uint32_t)W, r1 = (uint32_t)min(max(iy + 1, 0), H - 1) * (uint32_t)W;
+                uint32_t p00, p01, p10, p11;
+                __builtin_memcpy(&p00, src + 4ull * (r0 + cx0), 4);
+                __builtin_memcpy(&p01, src + 4ull * (r0 + cx1), 4);
+                __builtin_memcpy(&p10, src + 4ull * (r1 + cx0), 4);
+                __builtin_memcpy(&p11, src + 4ull * (r1 + cx1), 4);
+                o[j] = blend_c4(in_x0 && in_y0 ? p00 : border, in_x1 && in_y0 ? p01 : border, in_x0 && in_y1 ? p10 : border,
+                                in_x1 && in_y1 ? p11 : border, (uint32_t)sxx, (uint32_t)syy);
+            }
+        }
+    }
+    if (!fast) {
+        // crop bounds: wave reduction, then at most one atomic per bound and wavefront (per frame, mfs.py:1075-1098, and the clip-level
+        // rectangle, mfs.py:1103-1106)
+        const bool any = c_left != 0 || c_top != 0 || c_right != W - 1 || c_bottom != H - 1;
+        if (__ballot(any) != 0) {
+#pragma unroll
+            for (int off = 32; off >= 1; off >>= 1) {
+                c_left = max(c_left, __shfl_xor(c_left, off));
+                c_top = max(c_top, __shfl_xor(c_top, off));
+                c_right = min(c_right, __shfl_xor(c_right, off));
+                c_bottom = min(c_bottom, __shfl_xor(c_bottom, off));
+            }
+            if (lane == 0) {
+                if (c_left != 0) { atomicMax(&crop[4 * f + 0], c_left); atomicMax(&clip[0], c_left); }
+                if (c_top != 0) { atomicMax(&crop[4 * f + 1], c_top); atomicMax(&clip[1], c_top); }
+                if (c_right != W - 1) { atomicMin(&crop[4 * f + 2], c_right); atomicMin(&clip[2], c_right); }
+                if (c_bottom != H - 1) { atomicMin(&crop[4 * f + 3], c_bottom); atomicMin(&clip[3], c_bottom); }
+            }
+        }
+    }
+    if (active) {
+        uint8_t* __restrict__ d = dst + 4u * ((uint32_t)y * (uint32_t)W + (uint32_t)x0);
+        if (x0 + 3 < W) {                                               // 16 bytes: one store (16-byte aligned on an aligned stack)
+            const uint4 q = make_uint4(o[0], o[1], o[2], o[3]);
+            __builtin_memcpy(d, &q, 16);
+            // (the compiler would otherwise merge the stores of the three call sites in footprint_body into one shared dwordx3 store behind
+            // a dword store of each: it does not move code across an asm statement)
+            asm volatile("" ::: "memory");
+        } else {                                                        // (a loop: its stores do not merge with the 16-byte one)
+            const int m = W - x0;
+#pragma unroll 1
+            for (int j = 0; j < m; ++j) __builtin_memcpy(d + 4 * j, &o[j], 4);
+        }
+    }
+}
+
 // ---- EXPERIMENT builds only (tools/phase_profile.sh; nothing of this is in the product library) ------------------------------------
 // -DMF_EXP_SKIP=mask: TIMING-ONLY kernels in which the wavefronts of a path class return right after the plan test that selects
 // them (their output is garbage): 1 hot, 2 border, 4 pair, 8 multi, 16 everything else, 32 every wavefront right after the plan and
@@ -903,6 +1051,9 @@ __device__ unsigned long long mf_exp_phase[8];
 // PX = Px::U8C1: the same for single-channel uint8 frames (warp8c1_footprint): `frames` / `out` hold W H bytes per frame, the border is the
 // low byte of `border`, and the pixels go through remap_store_u8c1.  With STAGE (GREY_STAGE below) the plan's STAGED windows (not the
 // BORDER ones) are re-cut for 1-byte pixels (GreyWindow) and copied to LDS at the start, like warp_kernel's.
+// PX = Px::U8C4: the same for 4-channel uint8 frames (warp8c4_footprint): `frames` / `out` hold 4 W H bytes per frame, the border is the whole
+// `border` word, and the pixels go through remap_store_u8c4.  With STAGE (C4_STAGE below) the plan's STAGED windows (not the BORDER ones) are
+// re-cut for 4-byte pixels (MF_C4_COLS) and copied to LDS at the start; the hot and pair footprints take the grey warp's shortcuts.
 template <Px PX, bool STAGE, bool SCAN>
 __device__ __forceinline__ void footprint_body(const uint32_t f, const uint32_t t, const FootPlan* __restrict__ plan, const FootRegion* __restrict__ regions,
                                                const WarpGeom& g, const uint8_t* __restrict__ frames,
@@ -916,10 +1067,14 @@ __device__ __forceinline__ void footprint_body(const uint32_t f, const uint32_t 
     // BGR_STAGE: the uint8 BGR warp of a 4-byte aligned clip -- the staged window and the certified paths (hot, border, pair, multi)
     constexpr bool BGR_STAGE = PX == Px::U8C3 && STAGE && !SCAN;
     constexpr bool U16 = PX == Px::U16C3, GREY = PX == Px::U8C1, GREY_STAGE = GREY && STAGE;
+    // C4_STAGE: the 4-channel warp of a 4-byte aligned clip; WIN_STAGE: a re-cut window (grey or 4-byte) and the hot / pair shortcuts on it
+    constexpr bool C4 = PX == Px::U8C4, C4_STAGE = C4 && STAGE, WIN_STAGE = GREY_STAGE || C4_STAGE;
     // inverse homographies of the footprint's candidate cells: [entry][Hi0..Hi8, pad] (80-byte rows)
     __shared__ __attribute__((aligned(16))) double s_hi[1][9][10];                // row 8: the "no cell" matrix, see OWN_NONE
-    // source region of the footprint: MF_STAGE_ROWS rows of MF_STAGE_PITCH bytes (+ slack for the third dword of the last tap)
-    __shared__ __attribute__((aligned(16))) uint8_t s_src_all[SCAN ? 16 : LDS_WINDOW_PAD + LDS_WINDOW_BYTES + 64];
+    // source region of the footprint: MF_STAGE_ROWS rows of MF_STAGE_PITCH bytes (+ slack for the third dword of the last tap); the 4-byte
+    // window's MF_STAGE_ROWS rows of MF_C4_PITCH bytes for U8C4
+    __shared__ __attribute__((aligned(16))) uint8_t s_src_all[SCAN ? 16 : C4 ? LDS_WINDOW_PAD + MF_STAGE_ROWS * MF_C4_PITCH
+                                                                             : LDS_WINDOW_PAD + LDS_WINDOW_BYTES + 64];
     uint8_t* const s_src = &s_src_all[SCAN ? 0 : LDS_WINDOW_PAD];
     constexpr int wave = 0;
     MF_EXP_STAMP(exp_t0);
@@ -1047,6 +1202,32 @@ __device__ __forceinline__ void footprint_body(const uint32_t f, const uint32_t 
             }
         }
     }
+    if constexpr (C4_STAGE) {
+        // the plan's window re-cut for 4-byte pixels (MF_C4_COLS), issued before the coordinate work like the grey one: lane i fetches chunks
+        // i, 64 + i and 128 + i below 14 rows (row c / 14, bytes 16 (c % 14) ..) to LDS byte 16 c
+        if ((rg & (MF_REGION_STAGED | MF_REGION_BORDER)) == MF_REGION_STAGED && W >= MF_C4_COLS) {
+            const bool cmp = (rg & MF_REGION_COMPACT) != 0;
+            const uint32_t P = cmp ? (uint32_t)MF_COMPACT_PITCH : (uint32_t)MF_STAGE_PITCH, rows = cmp ? (uint32_t)MF_COMPACT_ROWS : (uint32_t)MF_STAGE_ROWS;
+            const uint32_t origin = rg & MF_REGION_ORIGIN_MASK, sbytes = src_dwords << 2;
+            const uint32_t sy0 = __builtin_amdgcn_readfirstlane((uint32_t)((float)(sbytes - origin) / (float)(3u * (uint32_t)W - P) + 0.5f));
+            const uint32_t bs = origin - P * sy0;
+            const uint32_t gx = min(bs / 3u, (uint32_t)W - (uint32_t)MF_C4_COLS);
+            gwin.on = true; gwin.row0 = sy0; gwin.col0 = gx;
+            const uint8_t* __restrict__ gbase = frames + (uint64_t)f * (4ull * (uint64_t)((uint32_t)W * (uint32_t)H)) + 4ull * (uint64_t)(sy0 * (uint32_t)W + gx);
+            constexpr uint32_t row_chunks = MF_C4_PITCH / 16;
+#pragma unroll
+            for (uint32_t c0 = 0; c0 < MF_STAGE_ROWS * row_chunks; c0 += 64) {
+                const uint32_t c = (uint32_t)lane + c0;
+                if (c < row_chunks * rows) {
+                    const uint32_t r = c / row_chunks;
+                    uint32_t o0 = umad24(r, 4u * (uint32_t)W, (c - row_chunks * r) << 4);
+                    asm("" : "+v"(o0));
+                    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gbase + o0),
+                                                     (__attribute__((address_space(3))) void*)(lds_ptr(&s_src[0]) + 16u * c0), 16, 0, 0);
+                }
+            }
+        }
+    }
     // (a wavefront must not END with its global->LDS copy in flight: on this stack that is a GPU memory access fault -- tools/phase_variant_check.py --
     // so the timing-only returns below wait for it; `MF_EXP_RETURN` = that wait + return)
 #define MF_EXP_RETURN do { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); return; } while (0)
@@ -1131,7 +1312,7 @@ __device__ __forceinline__ void footprint_body(const uint32_t f, const uint32_t 
         return;
     }
 
-    if constexpr (GREY_STAGE) {
+    if constexpr (WIN_STAGE) {
         if (gwin.on && (pv.x & (MF_PLAN_HOT << 16)) != 0) {
             // the HOT footprints of the grey warp (one IN cell, certified denominator, deep, staged): the hot path's coordinates -- the cheap
             // chain where the plan allows it (FAST64), else the trimmed-reciprocal one -- without the general path's ownership code
@@ -1139,12 +1320,13 @@ __device__ __forceinline__ void footprint_body(const uint32_t f, const uint32_t 
             float u[4], v[4];
             if (!((pv.x >> 16) & MF_PLAN_FAST64) || !cell_coords_fast(rec, xs0, yy, u, v))
                 cell_coords<false>(rec, xs0, yy, x0, 0xFu, u, v, true);
-            remap_store_u8c1(u, v, f, x0, y, true, W, H, frames, out, border, crop, clip, gwin, &s_src[0]);
+            if constexpr (C4) remap_store_u8c4(u, v, f, x0, y, true, W, H, frames, out, border, crop, clip, gwin, &s_src[0]);
+            else remap_store_u8c1(u, v, f, x0, y, true, W, H, frames, out, border, crop, clip, gwin, &s_src[0]);
             return;
         }
     }
     const cedge_t fedge = (cedge_t)(uintptr_t)(reinterpret_cast<const uint8_t*>(edges) + f * g.edge_frame_bytes);
-    if constexpr (GREY_STAGE) {
+    if constexpr (WIN_STAGE) {
         if (gwin.on && (pv.y & MF_PLAN_HOT) != 0) {
             // the PAIR footprints of the grey warp (two cells, certified denominators, deep, staged): warp_kernel's per-pixel pair form --
             // the later cell owns a pixel where its one mask edge passes (one fma), the other cell the rest, both matrices in LDS; a pixel
@@ -1184,7 +1366,8 @@ __device__ __forceinline__ void footprint_body(const uint32_t f, const uint32_t 
                     u[j] = (float)(((xs * h01.x + yy * h01.y) + h23.x) * iw);
                     v[j] = (float)(((xs * h23.y + yy * h45.x) + h45.y) * iw);
                 }
-                remap_store_u8c1(u, v, f, x0, y, true, W, H, frames, out, border, crop, clip, gwin, &s_src[0]);
+                if constexpr (C4) remap_store_u8c4(u, v, f, x0, y, true, W, H, frames, out, border, crop, clip, gwin, &s_src[0]);
+                else remap_store_u8c1(u, v, f, x0, y, true, W, H, frames, out, border, crop, clip, gwin, &s_src[0]);
                 return;
             }
         }
@@ -1758,6 +1941,10 @@ __device__ __forceinline__ void footprint_body(const uint32_t f, const uint32_t 
             remap_store_u8c1(u, v, f, x0, y, active, W, H, frames, out, border, crop, clip, gwin, &s_src[0]);
             return;
         }
+        if constexpr (C4) {
+            remap_store_u8c4(u, v, f, x0, y, active, W, H, frames, out, border, crop, clip, gwin, &s_src[0]);
+            return;
+        }
         // cv2.remap: 1/32-pixel fixed point (round half to even), bilinear gather, store.
         uint32_t bx[4], by[4];
         fixed_point(u, v, bx, by);
@@ -2197,7 +2384,7 @@ int launch_warp(Px px, const void* frames, void* out, const TableView& tv, int n
         if (v > 0 && (uint64_t)v < per_launch) per_launch = (uint64_t)v;
     }
     // staging reads dword-aligned 16-byte chunks: needs a 4-byte aligned clip (W % 4 == 0 is checked by the plan); the plan's windows
-    // are sized for 1- and 3-byte pixels, so uint16 frames never stage
+    // are re-cut for 1- and 4-byte pixels, not for 6-byte ones, so uint16 frames never stage
     const bool stage = px != Px::U16C3 && ((uintptr_t)frames & 3u) == 0;
     const size_t frame_bytes = (size_t)W * H * px_bytes(px);
     for (int f0 = 0; f0 < n; f0 += (int)per_launch) {
@@ -2208,6 +2395,8 @@ int launch_warp(Px px, const void* frames, void* out, const TableView& tv, int n
         const dim3 grid(g.per_xcd * 8u, (uint32_t)m);                  // one wavefront per 32 x 8 footprint
         if (px == Px::U8C1)
             launch_warp8c1_range(g, r, W, H, C, (uint32_t)border, stage, st);
+        else if (px == Px::U8C4)
+            launch_warp8c4_range(g, r, W, H, C, (uint32_t)border, stage, st);
         else if (px == Px::U16C3)
             hipLaunchKernelGGL(warp16_footprint, grid, dim3(64), 0, st, r.plan, r.regions, g, (const uint16_t*)r.frames, r.records, (uint16_t*)r.out,
                                r.edges, m, W, H, C, border, r.crop, r.bounds);
@@ -2218,7 +2407,8 @@ int launch_warp(Px px, const void* frames, void* out, const TableView& tv, int n
             hipLaunchKernelGGL(warp_kernel<false>, grid, dim3(64), 0, st, r.plan, r.regions, g, (const uint8_t*)r.frames, r.records, (uint8_t*)r.out,
                                r.edges, m, W, H, C, (uint32_t)border, r.crop, r.bounds);
     }
-    return hip_fail(hipGetLastError(), px == Px::U8C3 ? "warp_kernel launch" : px == Px::U16C3 ? "warp16_footprint launch" : "warp8c1_footprint launch");
+    return hip_fail(hipGetLastError(), px == Px::U8C3 ? "warp_kernel launch" : px == Px::U16C3 ? "warp16_footprint launch" :
+                                       px == Px::U8C1 ? "warp8c1_footprint launch" : "warp8c4_footprint launch");
 }
 
 int launch_crop_scan(const TableView& tv, int n, int W, int H, int R, int C, int32_t* crop, hipStream_t st)

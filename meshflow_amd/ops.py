@@ -33,9 +33,11 @@ def _need(t, dtype, name):
 
 def _border_samples(ctype, top, count):
     """Border colour -> what a C call takes: clamp(round(v), 0, top) of the first `count` components -- the value itself, not scaled to 16
-    bits (cv2.remap's saturate_cast of borderValue; a 1-channel image uses borderValue[0]) -- as an array, or one value for count 1."""
+    bits (cv2.remap's saturate_cast of borderValue; a 1-channel image uses borderValue[0]) -- as an array, or one value for count 1.  Missing
+    components are 0, as cv::Scalar pads them: a 3-component border gives a 4-channel frame alpha 0."""
     def convert(border_bgr):
         v = [int(np.clip(round(float(c)), 0, top)) for c in border_bgr[:count]]
+        v += [0] * (count - len(v))
         return (ctype * count)(*v) if count > 1 else ctype(v[0])
     return convert
 
@@ -51,24 +53,27 @@ def _row(name, dtype, channels, ctype, top):
 
 _FORMATS = (_row('u8c3', torch.uint8, 3, ctypes.c_uint8, 255),
             _row('u16c3', torch.uint16, 3, ctypes.c_uint16, 65535),   # cv2.remap's / cv2.resize's 16U arithmetic
-            _row('u8c1', torch.uint8, 1, ctypes.c_uint8, 255))        # channel 0 of the BGR result of the frames repeated
+            _row('u8c1', torch.uint8, 1, ctypes.c_uint8, 255),        # channel 0 of the BGR result of the frames repeated
+            _row('u8c4', torch.uint8, 4, ctypes.c_uint8, 255))        # the BGR result on channels 0-2, the u8c1 result on channel 3
 _FRAME_DTYPES = {f.dtype for f in _FORMATS}
 
 
 def pixel_format(dtype, shape):
-    """The format of frames of this dtype and shape: (n, H, W, 3) uint8 or uint16 BGR, or (n, H, W) uint8 single-channel.  Grey uint16
-    is refused naming its dtype; other shapes and dtypes raise ValueError."""
+    """The format of frames of this dtype and shape: (n, H, W, 3) uint8 or uint16 BGR, (n, H, W) uint8 single-channel, or (n, H, W, 4)
+    uint8 BGRA / RGBA.  Grey and 4-channel frames of another dtype are refused naming it; other shapes and dtypes raise ValueError."""
     if len(shape) == 3:
         channels = 1
-    elif len(shape) == 4 and shape[3] == 3:
-        channels = 3
+    elif len(shape) == 4 and shape[3] in (3, 4):
+        channels = shape[3]
     else:
-        raise ValueError('frames must be (n, H, W, 3), or (n, H, W) uint8')
+        raise ValueError('frames must be (n, H, W, 3), or (n, H, W) or (n, H, W, 4) uint8')
     for f in _FORMATS:
         if (f.dtype, f.channels) == (dtype, channels):
             return f
     if channels == 1:
         raise ValueError(f'single-channel frames must be uint8 (got {dtype}): (n, H, W) {dtype} frames are not supported')
+    if channels == 4:
+        raise ValueError(f'4-channel frames must be uint8 (got {dtype}): (n, H, W, 4) {dtype} frames are not supported')
     raise ValueError(f'frames must have dtype {torch.uint8}, got {dtype}')
 
 
@@ -79,11 +84,11 @@ def _frames_format(frames):
 
 
 def _out_for(frames, fmt, out):
-    """`out` (None: a new tensor) checked for `frames`; a single-channel one must have their shape."""
+    """`out` (None: a new tensor) checked for `frames`; a single-channel or 4-channel one must have their shape."""
     if out is None:
         return torch.empty_like(frames)
     _need(out, fmt.dtype, 'out')
-    if fmt.channels == 1 and out.shape != frames.shape:
+    if fmt.channels in (1, 4) and out.shape != frames.shape:
         raise ValueError('out must have the shape of frames')
     return out
 
@@ -182,7 +187,9 @@ def cell_table(unstab, stab, W, H, R, C, table=None, reset_status=True, bounds=N
 def warp(frames, table, border_bgr=(0, 0, 255), out=None, bounds=None):
     """Mesh warp + crop scan of n frames (mfs.py:1000-1100).  frames: (n, H, W, 3) uint8 or uint16 device tensor (uint16: cv2.remap's
     16U arithmetic, include/meshflow_hip.h mf_warp_u16c3; the crop values are those of the uint8 warp of the same table), or (n, H, W)
-    uint8 single-channel frames (mf_warp_u8c1: channel 0 of the BGR warp of the frames repeated, border byte = border_bgr[0]).
+    uint8 single-channel frames (mf_warp_u8c1: channel 0 of the BGR warp of the frames repeated, border byte = border_bgr[0]), or
+    (n, H, W, 4) uint8 BGRA / RGBA frames (mf_warp_u8c4: channels 0-2 as the BGR warp, channel 3 as the single-channel warp of the alpha
+    plane; border_bgr may have 4 components, a 3-component one gets alpha 0 -- the uncovered area comes out transparent).
     Returns the stabilized frames (the input's dtype); per-frame crop values accumulate in table.crop, the clip-level rectangle in
     `bounds` (the tensor `cell_table` was given) or, without one, in table.clip_bounds."""
     fmt = _frames_format(frames)
@@ -207,8 +214,8 @@ def warp_clip(frames, unstab, stab, table, border_bgr=(0, 0, 255), out=None, chu
     stream -- table, warp alone, rectangle (early on `prep_stream` when one is given).  Returns (stabilized frames,
     bounds): bounds = int32 {left, top, right, bottom} of the clip -- the caller's tensor when one is given, else table.bounds --,
     folded together by the kernels, final on the prep stream right after the tables' crop scan (and on the current stream after
-    the call); per-frame values in table.crop; table.status accumulates degenerate cells.  frames: uint8 or uint16, or (n, H, W) uint8
-    (see `warp`)."""
+    the call); per-frame values in table.crop; table.status accumulates degenerate cells.  frames: uint8 or uint16, (n, H, W) uint8 or
+    (n, H, W, 4) uint8 (see `warp`)."""
     fmt = _frames_format(frames)
     _need(unstab, torch.float64, 'unstab')
     _need(stab, torch.float64, 'stab')
@@ -264,9 +271,10 @@ def check_output_size(size, name='size'):
 
 def crop_resize(frames, bounds, out=None, size=None):
     """Crop to the inclusive (left, top, right, bottom) and resize back to (W, H): mfs.py:1111-1157.  frames: uint8 or uint16 (uint16:
-    cv2.resize's float path, mf_crop_resize_u16c3), or (n, H, W) uint8 (mf_crop_resize_u8c1); the output has the input's dtype and shape.
+    cv2.resize's float path, mf_crop_resize_u16c3), (n, H, W) uint8 (mf_crop_resize_u8c1) or (n, H, W, 4) uint8 (mf_crop_resize_u8c4: the
+    BGR result on channels 0-2, the single-channel one on channel 3); the output has the input's dtype and shape.
     size=(width, height) (cv2.resize's dsize order) scales the crop to that size instead (mf_crop_resize_to_*): the output is then
-    (n, height, width[, 3]), and so must `out` be; size == (W, H) is the default call."""
+    (n, height, width[, 3 or 4]), and so must `out` be; size == (W, H) is the default call."""
     fmt = _frames_format(frames)
     n, H, W = frames.shape[:3]
     left, top, right, bottom = (int(v) for v in bounds)

@@ -692,8 +692,10 @@ class MeshFlowStabilizer:
     def stabilize_resident(self, d_frames, d_disp, homographies, adaptive_weights_definition=ADAPTIVE_WEIGHTS_DEFINITION_ORIGINAL,
                            out=None, frame_range=None, inputs_ready=None, check=True, collective=False, warp_events=None,
                            jacobi_events=None):
-        """mfs.py:150-158 for a clip whose frames (n, H, W, 3) uint8 or uint16 -- or (n, H, W) uint8 grey -- and vertex displacements
-        (F, R+1, C+1, 2) float64 are RESIDENT in HBM (uint16 and grey frames: `ops.warp`; the sweep, tables and rectangle are the uint8 call's): Jacobi sweep -> cell tables -> warp + crop rectangle, nothing leaves the device, one call per clip, NO synchronisation:
+        """mfs.py:150-158 for a clip whose frames (n, H, W, 3) uint8 or uint16 -- or (n, H, W) uint8 grey, or (n, H, W, 4) uint8 BGRA / RGBA
+        -- and vertex displacements (F, R+1, C+1, 2) float64 are RESIDENT in HBM (uint16, grey and 4-channel frames: `ops.warp`; the sweep,
+        tables and rectangle are the uint8 call's; 4-channel frames get alpha 0 where the warp uncovers the frame, the 3-component
+        color_outside_image_area_bgr padded as cv::Scalar pads it): Jacobi sweep -> cell tables -> warp + crop rectangle, nothing leaves the device, one call per clip, NO synchronisation:
         calls issued back to back pipeline by themselves (the sweep runs on this object's prep stream, the next clip's beside this
         clip's cell table + plan; see `resident_chunks` for the other arrangement).
         frame_range = (lo, hi): d_frames holds frames lo..hi-1 of the clip (a frame-range shard; the sweep still covers all F);
