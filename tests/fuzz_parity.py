@@ -1,7 +1,9 @@
 """Randomised parity campaign: HIP kernels vs the C oracle on random geometries (bit-exact or bust).
 pixel='u8c3' (the default) draws the original stream; 'u16c3' and 'u8c1' run the same geometries on uint16 BGR frames (against
 tests/cv16_model.py) and single-channel frames (against channel 0 of the C oracle on the frame repeated three times), Jacobi cases skipped.
-Usage: python tests/fuzz_parity.py [cases] [seed] [case] [big|-] [u8c3|u16c3|u8c1]"""
+'u8c4' runs them on the BGR frames plus an alpha plane (its samples and its border value from a stream of their own): channels 0-2 against
+the oracle on the BGR frames, channel 3 against channel 0 of the oracle on the alpha plane repeated three times.
+Usage: python tests/fuzz_parity.py [cases] [seed] [case] [big|-] [u8c3|u16c3|u8c1|u8c4]"""
 import sys, os, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -16,7 +18,18 @@ def _pixel_frames(frames, pixel, case):
         return np.ascontiguousarray(frames[..., 0])
     if pixel == 'u16c3':
         return np.random.default_rng(case).integers(0, 65536, frames.shape, dtype=np.uint16)
+    if pixel == 'u8c4':
+        return np.concatenate([frames, _alpha_stream(case).integers(0, 256, frames.shape[:3] + (1,), dtype=np.uint8)], axis=-1)
     return frames
+
+
+def _alpha_stream(case):
+    """The stream of a u8c4 case's alpha plane and, after it, its alpha border value."""
+    return np.random.default_rng([case, 4])
+
+
+def _rgb(a):
+    return np.ascontiguousarray(np.repeat(a[..., None], 3, axis=-1))
 
 
 def _to_dev(a, dev):
@@ -33,7 +46,7 @@ def _to_np(t):
 
 def run(cases=200, seed0=0, only=-1, big=False, pixel='u8c3'):
     """Returns (number of mismatching cases, per-kind counts)."""
-    assert pixel in ('u8c3', 'u16c3', 'u8c1'), pixel
+    assert pixel in ('u8c3', 'u16c3', 'u8c1', 'u8c4'), pixel
     if pixel == 'u16c3':
         sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
         import cv16_model
@@ -67,6 +80,15 @@ def run(cases=200, seed0=0, only=-1, big=False, pixel='u8c3'):
             frames = _pixel_frames(frames, pixel, case)
             if pixel == 'u8c1':
                 want = want[..., 0]
+            elif pixel == 'u8c4':
+                s = _alpha_stream(case)
+                s.integers(0, 256, frames.shape[:3], dtype=np.uint8)       # (the alpha plane's draw)
+                a = int(s.integers(0, 256))
+                border = border + (a,)
+                want_a, crop_a, bad_a = clib.warp_clip(_rgb(frames[..., 3]), R, C, unstab, stab, border_bgr=(a, a, a), use_bbox=use_bbox or big,
+                                                       openmp=big)
+                assert bad_a == bad and (bad or np.array_equal(crop_a, want_crop))
+                want = np.concatenate([want, want_a[..., :1]], axis=-1)
             elif pixel == 'u16c3':
                 border = tuple(257 * b for b in border)
                 if bad == 0:
@@ -122,6 +144,10 @@ def run(cases=200, seed0=0, only=-1, big=False, pixel='u8c3'):
                 if pixel == 'u8c1':
                     want = np.ascontiguousarray(want[..., 0])
                     frames = _pixel_frames(frames, pixel, case)
+                elif pixel == 'u8c4':
+                    frames = _pixel_frames(frames, pixel, case)
+                    want_a = np.stack(mo.crop_frames(list(_rgb(frames[..., 3])), (l, tp, r, bt)))
+                    want = np.concatenate([want, want_a[..., :1]], axis=-1)
             got = _to_np(ops.crop_resize(_to_dev(frames, dev), (l, tp, r, bt)))
             ok = np.array_equal(got, want)
             stats['resize'] += 1

@@ -8,18 +8,24 @@ PLAN_BORDER = 0x1000
 REGION_STAGED = 0x80000000
 REGION_COMPACT = 0x20000000
 REGION_BORDER = 0x08000000
+REGION_ORIGIN_MASK = 0x007FFFFF
 GREY_PITCH = 80                 # the grey warp re-cuts a staged window only for frames of at least this many columns (warp.hip)
+C4_COLS = 56                    # the 4-channel warp's re-cut window: this many columns, frames of at least as many (warp.hip, MF_C4_COLS)
+STAGE_PITCH, COMPACT_PITCH = 160, 112       # the plan's staged windows: bytes per row, wide and COMPACT (mf_common.h)
 
 
-def plan_and_regions(buf, n, W, H, R, C):
-    """(plan uint32 (n * per_frame, 4), region flags uint32 (n * per_frame,)) of a table buffer (a device or host uint8 tensor)."""
+def plan_and_regions(buf, n, W, H, R, C, src=False):
+    """(plan uint32 (n * per_frame, 4), region flags uint32 (n * per_frame,)) of a table buffer (a device or host uint8 tensor); with
+    src=True also the region's second word, the window's first dword in its frame (uint32 (n * per_frame,))."""
     nfp = n * ((H + 7) // 8) * ((W + 31) // 32)
     nrec = n * R * C
     plan_off = (nrec * (32 * 8 + 8 + (16 + 12) * 4) + 15) & ~15
     raw = buf[plan_off:plan_off + 24 * nfp].cpu().numpy()
     plan = raw[:16 * nfp].view(np.uint32).reshape(nfp, 4)
-    region = raw[16 * nfp:].view(np.uint32).reshape(nfp, 2)[:, 0]
-    return plan, region
+    words = raw[16 * nfp:].view(np.uint32).reshape(nfp, 2)
+    if src:
+        return plan, words[:, 0], words[:, 1]
+    return plan, words[:, 0]
 
 
 def classes(plan, region):
@@ -52,4 +58,50 @@ def grey_paths(table, aligned=True):
         seen.add('w_mod4')
     if not aligned:
         seen.add('unaligned')
+    return seen
+
+
+def c4_window_columns(region, src_dwords, W):
+    """First column of the 4-byte window (warp.hip's C4_STAGE block) of each region, decoded as footprint_body does: origin = the low 23
+    bits, sy0 = (4 src_dwords - origin) / (3 W - P) + 1/2 in float32 (P = 160, or 112 for COMPACT), bs = origin - P sy0, and the column
+    gx = bs / 3 before the clamp to W - C4_COLS.  Meaningful only for STAGED regions."""
+    region = np.asarray(region, dtype=np.uint32)
+    src_dwords = np.asarray(src_dwords, dtype=np.uint32)
+    P = np.where((region & REGION_COMPACT) != 0, COMPACT_PITCH, STAGE_PITCH).astype(np.uint32)
+    origin = region & np.uint32(REGION_ORIGIN_MASK)
+    with np.errstate(over='ignore'):
+        num = ((src_dwords << np.uint32(2)) - origin).astype(np.float32)
+        den = (np.uint32(3 * W) - P).astype(np.float32)
+        sy0 = (num / den + np.float32(0.5)).astype(np.uint32)
+        bs = origin - P * sy0
+    return bs // np.uint32(3)
+
+
+def c4_paths(table, offset):
+    """The 4-channel warp paths (warp8c4_footprint) the frames of `table` take from a stack `offset` bytes into a buffer (None: an
+    allocation of its own, 16-byte aligned), as a set of names: 'window' / 'window_compact' (the 4-byte LDS window re-cut from a STAGED /
+    COMPACT window), 'hot_window' / 'pair_window' (those fast paths through it), 'window_clamped' (its first column clamped to
+    W - C4_COLS), 'staged_narrow' (a staged footprint in a frame narrower than C4_COLS), 'border_region' (a BORDER window: not re-cut),
+    'w_mod4' (W % 4 != 0), 'unaligned' (not 4-byte aligned: warp8c4_footprint<false>) and 'aligned4_not16' (STAGE on, the stack 4, 8 or
+    12 bytes past a 16-byte boundary)."""
+    W = table.W
+    plan, region, src = plan_and_regions(table.buf, table.n, W, table.H, table.R, table.C, src=True)
+    k = classes(plan, region)
+    aligned = offset is None or offset % 4 == 0
+    window = k['staged'] & ~k['border_window'] & (W >= C4_COLS) & aligned
+    clamped = np.zeros_like(window)
+    if window.any():
+        clamped[window] = c4_window_columns(region[window], src[window], W) > W - C4_COLS
+    seen = set()
+    for name, mask in (('window', window & ~k['compact']), ('window_compact', window & k['compact']), ('hot_window', window & k['hot']),
+                       ('pair_window', window & k['pair']), ('window_clamped', clamped), ('staged_narrow', k['staged'] & (W < C4_COLS)),
+                       ('border_region', k['border_window'])):
+        if mask.any():
+            seen.add(name)
+    if W % 4:
+        seen.add('w_mod4')
+    if not aligned:
+        seen.add('unaligned')
+    elif offset is not None and offset % 16:
+        seen.add('aligned4_not16')
     return seen

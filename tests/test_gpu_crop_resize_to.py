@@ -1,7 +1,8 @@
-"""-m gpu: crop-resize to a caller-chosen output size on the device -- mf_crop_resize_to_u8c3 / _u16c3 / _u8c1 and
+"""-m gpu: crop-resize to a caller-chosen output size on the device -- mf_crop_resize_to_u8c3 / _u16c3 / _u8c1 / _u8c4 and
 ops.crop_resize(size=...) -- equal, sample for sample, to cv2.resize(crop, (out_W, out_H)) INTER_LINEAR as the oracle restates it
-(oracle.meshflow_oracle.resize_linear_u8; grey = channel 0 of that on the frame repeated three times; uint16: tests/cv16_model.py's float
-path plus tests/cv16_area.py's exact-2x branch).  Upscale, downscale, mixed, 1-pixel crops and outputs, outputs larger than the frame,
+(oracle.meshflow_oracle.resize_linear_u8; grey = channel 0 of that on the frame repeated three times; 4-channel = that on B G R and
+channel 0 of it on the alpha plane repeated three times; uint16: tests/cv16_model.py's float path plus tests/cv16_area.py's exact-2x
+branch).  Upscale, downscale, mixed, 1-pixel crops and outputs, outputs larger than the frame,
 W % 4 != 0, unaligned stacks, many tiles, both sides of the staged / direct cut-over; the same size equals today's call byte for byte;
 every refusal leaves the output untouched."""
 import ctypes
@@ -18,7 +19,7 @@ torch = pytest.importorskip('torch')
 from meshflow_amd import _lib, ops  # noqa: E402
 from oracle import meshflow_oracle as mo  # noqa: E402
 
-FORMATS = ('u8c3', 'u8c1', 'u16c3')
+FORMATS = ('u8c3', 'u8c1', 'u16c3', 'u8c4')
 
 
 @pytest.fixture(scope='module')
@@ -32,7 +33,7 @@ def frames_of(fmt, n, H, W, seed):
     rng = np.random.default_rng(seed)
     if fmt == 'u16c3':
         return rng.integers(0, 65536, (n, H, W, 3), dtype=np.uint16)
-    return rng.integers(0, 256, (n, H, W, 3) if fmt == 'u8c3' else (n, H, W), dtype=np.uint8)
+    return rng.integers(0, 256, {'u8c3': (n, H, W, 3), 'u8c1': (n, H, W), 'u8c4': (n, H, W, 4)}[fmt], dtype=np.uint8)
 
 
 def to_dev(a, dev):
@@ -54,6 +55,9 @@ def reference(fmt, frames, rect, ow, oh):
             out.append(mo.resize_linear_u8(crop, ow, oh))
         elif fmt == 'u8c1':
             out.append(mo.resize_linear_u8(np.repeat(crop[..., None], 3, axis=2), ow, oh)[..., 0])
+        elif fmt == 'u8c4':
+            alpha = mo.resize_linear_u8(np.repeat(crop[..., 3:], 3, axis=2), ow, oh)[..., :1]
+            out.append(np.concatenate([mo.resize_linear_u8(np.ascontiguousarray(crop[..., :3]), ow, oh), alpha], axis=-1))
         else:
             out.append(cv16_area.resize_u16(crop, ow, oh))
     return np.stack(out)
@@ -178,3 +182,87 @@ def test_ops_size_checks(dev):
         ops.crop_resize(frames, (0, 0, 9, 9), out=torch.empty((2, 20, 30, 3), dtype=torch.uint8, device=dev), size=(31, 20))
     out = torch.empty((2, 7, 31, 3), dtype=torch.uint8, device=dev)
     assert ops.crop_resize(frames, (0, 0, 9, 9), out=out, size=(31, 7)) is out
+
+
+# ---- seeded random sweep ----------------------------------------------------------------------------------------------------------
+
+# scale_x = crop width / output width at which each format's down instantiation leaves its staged form for the direct one: the widest span
+# 256 output pixels can take, px (ceil(255 scale_x) + 3) bytes (+ slack), must fit its LDS row -- u8c3: kDownPitch 2048 (resize_to.hip,
+# slack 15), u8c1: kDown1Pitch 1024 (slack 3), u8c4: kDownPitch 2432 (resize_c4.hip).  As the largest ceil(255 scale_x) that still fits.
+# uint16 has one kernel (no staging): its draws sit at u8c3's.
+CUT_CEIL = {'u8c3': 674, 'u8c1': 1018, 'u8c4': 605, 'u16c3': 674}
+SWEEP_OFFSETS = {'u8c3': ((None, None), (1, 3), (2, 1), (3, 2)), 'u8c1': ((None, None), (1, 3), (2, 1), (3, 2)),
+                 'u8c4': ((None, None), (1, 3), (2, 1), (3, 2), (8, 12)), 'u16c3': ((None, None), (2, 2), (0, 2))}
+SWEEP_CLASSES = ('one', 'up', 'down2', 'down3', 'cut_below', 'cut_above', 'mixed', 'any')
+
+
+def at_offset(a, dev, offset):
+    """numpy stack -> device tensor of its dtype and shape: offset None = an allocation of exactly its bytes; else `offset` bytes into a
+    zeroed buffer with 16 bytes to spare."""
+    raw = np.ascontiguousarray(a).view(np.uint8).reshape(-1)
+    if offset is None:
+        t = torch.from_numpy(raw).to(dev)
+    else:
+        buf = torch.zeros(raw.size + 16, dtype=torch.uint8, device=dev)
+        t = buf[offset:offset + raw.size]
+        t.copy_(torch.from_numpy(raw).to(dev))
+        assert t.data_ptr() % 16 == offset % 16
+    return (t.view(torch.uint16) if a.dtype == np.uint16 else t).view(a.shape)
+
+
+def sweep_draw(rng, fmt):
+    """One draw: (n, H, W, crop width and height, (out_W, out_H), class).  The crop is placed by the caller."""
+    W, H, n = int(rng.integers(1, 301)), int(rng.integers(1, 201)), int(rng.integers(1, 4))
+    kind = SWEEP_CLASSES[int(rng.integers(0, len(SWEEP_CLASSES)))]
+    ri = lambda lo, hi: int(rng.integers(lo, hi + 1))                      # noqa: E731
+    cw, ch = ri(1, W), ri(1, H)
+    if kind == 'one':
+        size = [(1, 1), (1, ri(1, 4 * ch)), (ri(1, 4 * cw), 1)][ri(0, 2)]
+    elif kind == 'up':
+        size = (ri(cw, 4 * cw), ri(ch, 4 * ch))
+    elif kind in ('down2', 'down3') and min(W, H) >= int(kind[-1]):
+        k = int(kind[-1])
+        ow, oh = ri(1, W // k), ri(1, H // k)
+        cw, ch, size = k * ow, k * oh, (ow, oh)
+    elif kind in ('cut_below', 'cut_above'):
+        # the widest output whose crop still fits the frame, then the crop width on this side of the cut: ceil(255 cw / oW) <= CUT_CEIL
+        # just holds (below) or just fails (above)
+        top = CUT_CEIL[fmt]
+        ow = ri(1, max(1, (W - 1) * 255 // (top + 1)))
+        below = top * ow // 255
+        cw = min(W, max(1, below if kind == 'cut_below' else below + 1))
+        size = (ow, ri(1, 2 * ch))
+    elif kind == 'mixed':
+        size = (ri(cw, 4 * cw), ri(1, ch)) if rng.random() < 0.5 else (ri(1, cw), ri(ch, 4 * ch))
+    else:
+        size = (ri(1, 4 * cw), ri(1, 4 * ch))
+    return n, H, W, cw, ch, size, kind
+
+
+@pytest.mark.parametrize('fmt', FORMATS)
+def test_random_sweep(dev, fmt):
+    """Seeded draws of frames of 1-300 x 1-200, 1-3 frames, crops and output sizes of every class above: 1 x 1, 1 x N and N x 1; up to 4x up;
+    exactly 2x down (u16c3: the area branch) and 3x down; scale_x just below and just above the format's staged / direct cut-over; up in
+    one axis and down in the other.  Each draw resizes one crop placed at random and one in the last rows of the frame (where a
+    wavefront's last staged row ends past the stack and it takes the direct form), from every input / output offset of SWEEP_OFFSETS, the
+    aligned input an allocation that ends with the stack."""
+    rng = np.random.default_rng({'u8c3': 31, 'u8c1': 32, 'u16c3': 33, 'u8c4': 34}[fmt])
+    pairs = SWEEP_OFFSETS[fmt]
+    draws, kinds, cut = 300, set(), {'cut_below': 0, 'cut_above': 0}
+    for d in range(draws):
+        n, H, W, cw, ch, (ow, oh), kind = sweep_draw(rng, fmt)
+        frames = frames_of(fmt, n, H, W, seed=1000 * d + 7)
+        l = int(rng.integers(0, W - cw + 1))
+        rects = [(l, int(rng.integers(0, H - ch + 1))), (int(rng.integers(0, W - cw + 1)), H - ch)]
+        srcs = {si: at_offset(frames, dev, si) for si in {p[0] for p in pairs}}
+        for (l, t) in rects:
+            rect = (l, t, l + cw - 1, t + ch - 1)
+            want = reference(fmt, frames, rect, ow, oh)
+            for si, di in pairs:
+                out = None if di is None else at_offset(np.zeros_like(want), dev, di)
+                got = to_np(ops.crop_resize(srcs[si], rect, size=(ow, oh), out=out))
+                assert np.array_equal(got, want), (fmt, d, kind, (n, H, W), rect, (ow, oh), si, di, int((got != want).sum()))
+        kinds.add(kind)
+        if kind in cut:
+            cut[kind] += 1
+    assert kinds == set(SWEEP_CLASSES) and min(cut.values()) >= 10, (kinds, cut)
