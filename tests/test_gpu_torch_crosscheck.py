@@ -14,9 +14,14 @@ compare the HIP path with implementations that share NOTHING with it:
 cv2.remap quantises coordinates to 1/32 pixel and cv2.resize its weights to 11 bits, so the comparison allows 1 LSB (north_star's
 own bar) around the envelope of the float64 result over a 1/32-pixel neighbourhood; identity and integer shifts must be exact.
 It pins nothing (parity stays "partial": tests/test_cv2_crosscheck.py is the door to "green"), but a wrong reading of pixel
-centres, map direction, mesh-motion sign or border handling cannot pass it."""
+centres, map direction, mesh-motion sign or border handling cannot pass it.
+
+The helpers live in tests/second_opinion.py.  The tests of the second half judge all four formats and crop_resize(size=...) with that
+module's judge and constants, which were fixed on the CPU against the models (tests/test_second_opinion_models.py); none is defined here."""
 import numpy as np
 import pytest
+
+import second_opinion as so
 
 pytestmark = pytest.mark.gpu
 
@@ -32,50 +37,25 @@ def dev():
 
 
 def _grid(W, H, R, C):
-    """Mesh vertex pixel positions (mfs.py:881-906): ceil((W-1) col / C), ceil((H-1) row / R)."""
-    gx = np.array([np.ceil((W - 1) * (c / C)) for c in range(C + 1)])
-    gy = np.array([np.ceil((H - 1) * (r / R)) for r in range(R + 1)])
-    return gx, gy
+    return so.grid(W, H, R, C)
 
 
 def _smooth_frames(dev, n, H, W, seed=0):
     """Band-limited frames (sums of sinusoids, gradients of a few grey levels per pixel): uint8 (n, H, W, 3) on the device."""
-    y = torch.arange(H, dtype=torch.float64, device=dev)[None, :, None, None]
-    x = torch.arange(W, dtype=torch.float64, device=dev)[None, None, :, None]
-    c = torch.arange(3, dtype=torch.float64, device=dev)[None, None, None, :]
-    f = torch.arange(n, dtype=torch.float64, device=dev)[:, None, None, None] + seed
-    v = 128 + 60 * torch.sin(0.031 * x + 0.017 * y + 0.7 * c + 0.3 * f) + 50 * torch.cos(0.011 * x - 0.043 * y + 1.3 * c - 0.2 * f)
-    return v.round().clamp(0, 255).to(torch.uint8)
+    return so.smooth_planes('u8c3', n, H, W, seed, dev).to(torch.uint8)
 
 
 def _sample(frames, u, v):
     """grid_sample of uint8 frames (n, H, W, 3) at float64 source positions u, v (n, H, W) in PIXEL units -> float64 (n, H, W, 3)."""
-    n, H, W, _ = frames.shape
-    src = frames.permute(0, 3, 1, 2).to(torch.float64)
-    grid = torch.stack([2 * u / (W - 1) - 1, 2 * v / (H - 1) - 1], dim=-1)          # align_corners=True: -1 <-> pixel 0, +1 <-> pixel W-1
-    return F_.grid_sample(src, grid, mode='bilinear', padding_mode='zeros', align_corners=True).permute(0, 2, 3, 1)
+    return so.sample(frames.to(torch.float64), u, v)
 
 
-def _assert_within_envelope(got, frames, u, v, allow=1.0, skip=None):
-    """got (uint8) must lie within `allow` grey levels of the range the float64 bilinear sample takes over the 1/32-pixel bucket
-    around (u, v) (cv2.remap rounds 32 u, 32 v to integers)."""
-    lo = hi = None
-    for du in (-1 / 64, 0.0, 1 / 64):
-        for dv in (-1 / 64, 0.0, 1 / 64):
-            s = _sample(frames, u + du, v + dv)
-            lo = s if lo is None else torch.minimum(lo, s)
-            hi = s if hi is None else torch.maximum(hi, s)
-    g = got.to(torch.float64)
-    bad = (g < lo - allow - 0.5) | (g > hi + allow + 0.5)                           # (+0.5: rounding of the final value)
-    if skip is not None:
-        bad = bad & ~skip[..., None]
-    assert not bool(bad.any()), f'{int(bad.sum())} of {bad.numel()} values outside the envelope; worst {float(torch.maximum(lo - g, g - hi).max()):.2f}'
-    return float((g - _sample(frames, u, v)).abs().mean())
+_assert_within_envelope = so.legacy_assert_within_envelope
 
 
 def _hip_warp(dev, d_frames, R, C, unstab, stab, border=(0, 0, 0)):
     from meshflow_amd import ops
-    n, H, W, _ = d_frames.shape
+    n, H, W = d_frames.shape[:3]
     table = ops.cell_table(torch.from_numpy(np.ascontiguousarray(unstab)).to(dev), torch.from_numpy(np.ascontiguousarray(stab)).to(dev), W, H, R, C)
     out = ops.warp(d_frames, table, border)
     torch.cuda.synchronize()
@@ -84,9 +64,7 @@ def _hip_warp(dev, d_frames, R, C, unstab, stab, border=(0, 0, 0)):
 
 
 def _pixels(dev, n, H, W):
-    ys = torch.arange(H, dtype=torch.float64, device=dev)[None, :, None].expand(n, H, W)
-    xs = torch.arange(W, dtype=torch.float64, device=dev)[None, None, :].expand(n, H, W)
-    return xs, ys
+    return so.pixels(n, H, W, dev)
 
 
 @pytest.mark.parametrize('H,W,R,C', [(360, 640, 16, 16), (270, 484, 5, 7), (1080, 1920, 16, 16)])
@@ -219,3 +197,104 @@ def test_crop_resize_vs_interpolate(dev, H, W, rect):
     crop = noise[:, top:bottom + 1, left:right + 1].permute(0, 3, 1, 2).to(torch.float64)
     want = F_.interpolate(crop, size=(H, W), mode='bilinear', align_corners=False, antialias=False).permute(0, 2, 3, 1)
     assert float((got.to(torch.float64) - want).abs().max()) <= 1.0 + 1e-9
+
+
+# ---- the four formats and resize-to, judged by tests/second_opinion.py with its constants -------------------------------------------------
+# Every bound below lives in second_opinion.py and was fixed on the CPU against the models (tests/test_second_opinion_models.py).
+
+PLANES = {'smooth': so.smooth_planes, 'noise': so.noise_planes}
+SMALL_WARP = [c for c in so.WARP_CASES if c.kind != 'far']
+LARGE_WARP = so.WARP_CASES_1080P
+
+
+def _to_dev(fmt, planes, dev):
+    """float64 planes -> the device stack `ops` takes (uint16 moved as bytes)."""
+    a = np.ascontiguousarray(so.to_numpy(fmt, planes))
+    t = torch.from_numpy(a.view(np.uint8)).to(dev)
+    return t.view(torch.uint16) if a.dtype == np.uint16 else t
+
+
+def _to_planes(t, dev):
+    a = t.contiguous().view(torch.uint8).cpu().numpy().view(np.uint16) if t.dtype == torch.uint16 else t.cpu().numpy()
+    return so.to_planes(a, dev)
+
+
+def _kernel_warp(dev, fmt, planes, R, C, unstab, stab, border):
+    out, _ = _hip_warp(dev, _to_dev(fmt, planes, dev), R, C, unstab, stab, border)
+    return _to_planes(out, dev)
+
+
+def _kernel_warp_findings(dev, fmt, case, kind, border=(0, 0, 0), with_model=False):
+    """Like test_second_opinion_models.warp_case_findings with the kernel in the model's place; with_model: the model through the same
+    judge must give the same numbers."""
+    planes = PLANES[kind](fmt, case.n, case.H, case.W, case.seed, dev)
+    found = []
+    for setup in so.warp_setups(case, dev):
+        got = _kernel_warp(dev, fmt, planes, case.R, case.C, setup.unstab, setup.stab, border)
+        f = so.warp_findings(fmt, got, planes, setup, border)
+        found.append((f, so.warp_violations(fmt, f, setup, kind == 'smooth')))
+        if with_model:
+            import test_second_opinion_models as models
+            want = so.to_planes(models.model_warp(fmt, so.to_numpy(fmt, planes), case.R, case.C, setup.unstab, setup.stab, border), dev)
+            assert so.warp_findings(fmt, want, planes, setup, border) == f
+    return found
+
+
+@pytest.mark.parametrize('kind', ['smooth', 'noise'])
+@pytest.mark.parametrize('fmt', so.FORMATS)
+@pytest.mark.parametrize('case', SMALL_WARP + LARGE_WARP, ids=lambda c: f'{c.kind}-{c.H}x{c.W}-{c.R}')
+def test_warp_formats_vs_grid_sample(dev, case, fmt, kind):
+    """ops.warp in each format: identity and integer shifts exact, a global homography and real mesh motion inside the envelope, the mean
+    signed difference of uint16 within its bound; on the CPU-sized cases the model gives the same numbers."""
+    found = _kernel_warp_findings(dev, fmt, case, kind, with_model=case in SMALL_WARP)
+    assert not [v for _, vs in found for v in vs], found
+
+
+@pytest.mark.parametrize('fmt', so.FORMATS)
+def test_warp_borders_vs_grid_sample(dev, fmt):
+    """A non-black border per format: exactly the border far outside the mesh (uint16 (0, 0, 255) -> 255; u8c4 alpha 0 from 3 components,
+    the given alpha from 4), blended into the pixels next to the ring as the float64 sampler blends it."""
+    far = next(c for c in so.WARP_CASES if c.kind == 'far')
+    hom = next(c for c in so.WARP_CASES if c.kind == 'homography')
+    borders = [so.BORDERS[fmt]] + ([so.BORDERS['u8c4'][:3]] if fmt == 'u8c4' else [])
+    for border in borders:
+        for case in (far, hom):
+            found = _kernel_warp_findings(dev, fmt, case, 'smooth', border, with_model=True)
+            assert not [v for _, vs in found for v in vs], found
+
+
+def _kernel_resize_findings(dev, fmt, case, kind, same_size=False, with_model=False):
+    from meshflow_amd import ops
+    n, H, W, rect, (ow, oh) = case
+    planes = PLANES[kind](fmt, n, H, W, 9, dev)
+    frames = _to_dev(fmt, planes, dev)
+    out = ops.crop_resize(frames, rect) if same_size else ops.crop_resize(frames, rect, size=(ow, oh))
+    torch.cuda.synchronize()
+    got = _to_planes(out, dev)
+    assert tuple(got.shape[:3]) == (n, oh, ow)
+    f = so.resize_findings(fmt, got, planes, rect, ow, oh)
+    if with_model:
+        import test_second_opinion_models as models
+        want = so.to_planes(models.model_resize(fmt, so.to_numpy(fmt, planes), rect, ow, oh), dev)
+        assert so.resize_findings(fmt, want, planes, rect, ow, oh) == f
+    return f, so.resize_violations(fmt, f, rect, ow, oh, kind == 'smooth')
+
+
+@pytest.mark.parametrize('kind', ['smooth', 'noise'])
+@pytest.mark.parametrize('fmt', so.FORMATS)
+@pytest.mark.parametrize('case', range(len(so.RESIZE_CASES) + len(so.RESIZE_CASES_1080P)))
+def test_crop_resize_to_vs_interpolate(dev, case, fmt, kind):
+    """ops.crop_resize(size=...) in each format over the device suite's case list and 1080p downscales on both sides of every staged /
+    direct cut-over, against float64 `interpolate` of the crop."""
+    small = case < len(so.RESIZE_CASES)
+    f, violations = _kernel_resize_findings(dev, fmt, (so.RESIZE_CASES + so.RESIZE_CASES_1080P)[case], kind, with_model=small)
+    assert not violations, (f, violations)
+
+
+@pytest.mark.parametrize('fmt', so.FORMATS)
+def test_crop_resize_same_size_formats_vs_interpolate(dev, fmt):
+    """The call without `size` (back to the frame size) in each format, 1080p included."""
+    for n, H, W, rect in so.SAME_SIZE_CASES + so.SAME_SIZE_CASES_1080P:
+        for kind in ('smooth', 'noise'):
+            f, violations = _kernel_resize_findings(dev, fmt, (n, H, W, rect, (W, H)), kind, same_size=True, with_model=H < 1080)
+            assert not violations, (f, violations)
