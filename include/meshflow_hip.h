@@ -240,6 +240,25 @@ int mf_crop_resize_to_u8c1(const uint8_t* d_frames, uint8_t* d_out, int n, int W
                            int out_W, int out_H, void* d_work, void* stream);
 int mf_crop_resize_to_u8c4(const uint8_t* d_frames, uint8_t* d_out, int n, int W, int H, int left, int top, int right, int bottom,
                            int out_W, int out_H, void* d_work, void* stream);
+/* _crop_frames (mfs.py:1111-1157) from a rectangle that stays on the device: the call above with {left, top, right, bottom} read by the
+ * kernels from d_bounds ([4] int32 in device memory, e.g. what mf_warp_bounds_* / mf_warp_clip_* / mf_crop_reduce leave there) when they
+ * EXECUTE, in stream order.  The host never reads the rectangle and the call never synchronises (for u8c3, once the device has been probed:
+ * mf_set_device does that).  The same size: out_W = W, out_H = H.  For a usable rectangle d_out and the tables in d_work
+ * (mf_crop_resize_workspace_bytes(out_W, out_H) bytes) are byte for byte those of mf_crop_resize_to_* with the same four numbers.
+ * d_status: [1] int32 of the caller's, zeroed by the caller.  A rectangle that cannot be used -- right < left, bottom < top, a negative
+ * edge, right >= W or bottom >= H, the device twin of the MF_ERR_INVALID_ARG refusal above -- adds 1 to *d_status, once per call; every
+ * kernel of the call then returns before it reads a frame byte or writes a byte of d_out or d_work.  Nothing faults, whatever the 16
+ * bytes hold; the return value cannot tell (it is MF_OK), *d_status is read whenever the caller next synchronises.
+ * Refused on the host with MF_ERR_INVALID_ARG, nothing launched or written: null pointers (d_bounds and d_status included), d_frames ==
+ * d_out, n < 1, W, H, out_W or out_H outside 1 .. 32,767, too many tiles. */
+int mf_crop_resize_dev_u8c3(const uint8_t* d_frames, uint8_t* d_out, int n, int W, int H, const int32_t* d_bounds, int out_W, int out_H,
+                            void* d_work, int32_t* d_status, void* stream);
+int mf_crop_resize_dev_u16c3(const uint16_t* d_frames, uint16_t* d_out, int n, int W, int H, const int32_t* d_bounds, int out_W, int out_H,
+                             void* d_work, int32_t* d_status, void* stream);
+int mf_crop_resize_dev_u8c1(const uint8_t* d_frames, uint8_t* d_out, int n, int W, int H, const int32_t* d_bounds, int out_W, int out_H,
+                            void* d_work, int32_t* d_status, void* stream);
+int mf_crop_resize_dev_u8c4(const uint8_t* d_frames, uint8_t* d_out, int n, int W, int H, const int32_t* d_bounds, int out_W, int out_H,
+                            void* d_work, int32_t* d_status, void* stream);
 
 /* ---- the row before the path: vertex-motion accumulation (mfs.py:236-452 from the matched features on) ----
  * Replaces the Python loops of _get_vertex_nearby_feature_residual_velocities (mfs.py:365-452), the medians, global

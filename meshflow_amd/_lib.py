@@ -61,6 +61,10 @@ SIGNATURES = {
     'mf_warp_clip_u8c4': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
     'mf_crop_resize_u8c4': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     'mf_crop_resize_to_u8c4': (_i, [_vp, _vp] + [_i] * 9 + [_vp, _vp]),
+    'mf_crop_resize_dev_u8c3': (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp]),
+    'mf_crop_resize_dev_u16c3': (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp]),
+    'mf_crop_resize_dev_u8c1': (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp]),
+    'mf_crop_resize_dev_u8c4': (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp]),
     'mf_vertex_motion_workspace_bytes': (_sz, [_i, _i, _i, _i, _i]),
     'mf_vertex_motion_f64': (_i, [_vp, _vp, _vp, _vp] + [_i] * 9 + [_vp, _vp, _vp, _vp, _vp]),
     'mf_stability_score_f64': (_i, [_vp, _i, _i, _vp, _vp, _vp]),

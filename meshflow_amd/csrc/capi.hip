@@ -53,6 +53,14 @@ static int crop_resize_to_entry(const char* name, Px px, const void* d_frames, v
     return launch_crop_resize_to(px, d_frames, d_out, n, W, H, left, top, right, bottom, out_W, out_H, d_work, (hipStream_t)stream);
 }
 
+static int crop_resize_dev_entry(const char* name, Px px, const void* d_frames, void* d_out, int n, int W, int H, const int32_t* d_bounds,
+                                 int out_W, int out_H, void* d_work, int32_t* d_status, void* stream)
+{
+    if (!d_frames || !d_out || !d_bounds || !d_work || !d_status) { set_error("%s: null pointer", name); return MF_ERR_INVALID_ARG; }
+    if (d_frames == d_out) { set_error("%s: d_frames and d_out alias", name); return MF_ERR_INVALID_ARG; }
+    return launch_crop_resize_dev(px, d_frames, d_out, n, W, H, d_bounds, out_W, out_H, d_work, d_status, (hipStream_t)stream);
+}
+
 }  // namespace mf
 
 using namespace mf;
@@ -271,6 +279,30 @@ int mf_crop_resize_to_u8c4(const uint8_t* d_frames, uint8_t* d_out, int n, int W
 {
     return crop_resize_to_entry("mf_crop_resize_to_u8c4", Px::U8C4, d_frames, d_out, n, W, H, left, top, right, bottom, out_W, out_H, d_work,
                                 stream);
+}
+
+int mf_crop_resize_dev_u8c3(const uint8_t* d_frames, uint8_t* d_out, int n, int W, int H, const int32_t* d_bounds, int out_W, int out_H,
+                            void* d_work, int32_t* d_status, void* stream)
+{
+    return crop_resize_dev_entry("mf_crop_resize_dev_u8c3", Px::U8C3, d_frames, d_out, n, W, H, d_bounds, out_W, out_H, d_work, d_status, stream);
+}
+
+int mf_crop_resize_dev_u16c3(const uint16_t* d_frames, uint16_t* d_out, int n, int W, int H, const int32_t* d_bounds, int out_W, int out_H,
+                             void* d_work, int32_t* d_status, void* stream)
+{
+    return crop_resize_dev_entry("mf_crop_resize_dev_u16c3", Px::U16C3, d_frames, d_out, n, W, H, d_bounds, out_W, out_H, d_work, d_status, stream);
+}
+
+int mf_crop_resize_dev_u8c1(const uint8_t* d_frames, uint8_t* d_out, int n, int W, int H, const int32_t* d_bounds, int out_W, int out_H,
+                            void* d_work, int32_t* d_status, void* stream)
+{
+    return crop_resize_dev_entry("mf_crop_resize_dev_u8c1", Px::U8C1, d_frames, d_out, n, W, H, d_bounds, out_W, out_H, d_work, d_status, stream);
+}
+
+int mf_crop_resize_dev_u8c4(const uint8_t* d_frames, uint8_t* d_out, int n, int W, int H, const int32_t* d_bounds, int out_W, int out_H,
+                            void* d_work, int32_t* d_status, void* stream)
+{
+    return crop_resize_dev_entry("mf_crop_resize_dev_u8c4", Px::U8C4, d_frames, d_out, n, W, H, d_bounds, out_W, out_H, d_work, d_status, stream);
 }
 
 size_t mf_vertex_motion_workspace_bytes(int total_features, int max_per_pair, int P, int R, int C)

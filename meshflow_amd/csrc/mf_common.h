@@ -307,6 +307,14 @@ int launch_resize8_to(Px px, const uint8_t* frames, uint8_t* out, int n, int W, 
                       const void* work, const TileOrder& order, hipStream_t st);
 int launch_resize16_to_kernel(const uint16_t* frames, uint16_t* out, int W, int H, int left, int top, int cw, int oW, int oH, bool area,
                               const Resize16Tab* xtab, const Resize16Tab* ytab, const TileOrder& order, hipStream_t st);
+// resize_dev.hip: mf_crop_resize_dev_*: the host-side checks, then the tables and the kernels that read the rectangle from d_bounds
+// (resize_dev_c1.hip / resize_dev_c4.hip: the launches of the kernels that live there)
+int launch_crop_resize_dev(Px px, const void* frames, void* out, int n, int W, int H, const int32_t* d_bounds, int oW, int oH, void* work,
+                           int32_t* d_status, hipStream_t st);
+int launch_resize8c1_dev(const uint8_t* frames, uint8_t* out, int n, int W, int H, const int32_t* d_bounds, const ResizeTab* xtab,
+                         const ResizeTab* ytab, const TileOrder& order, hipStream_t st);
+int launch_resize8c4_dev(const uint8_t* frames, uint8_t* out, int n, int W, int H, const int32_t* d_bounds, int oW, int oH, bool up,
+                         const ResizeTab* xtab, const ResizeTab* ytab, const TileOrder& order, hipStream_t st);
 size_t vertex_motion_workspace_bytes(int total_features, int max_per_pair, int P, int R, int C);
 int launch_vertex_motion(const double* early, const double* late, const int32_t* offsets, const double* hom, int P,
                          int total_features, int max_per_pair, int W, int H, int R, int C, int ell_rows, int ell_cols,

@@ -15,14 +15,16 @@
 // Memory-bound in principle (2*H*W*3 bytes per frame).
 #include "mf_common.h"
 #include "resize_u8.h"
+#include "resize_rect.h"
 
 namespace mf {
 
 __device__ __forceinline__ int cv_round_pos(float v) { return (int)rintf(v); }
 
-__global__ __launch_bounds__(256) void resize_tables_kernel(int cw, int ch, int W, int H, double scale_x, double scale_y,
+__global__ __launch_bounds__(256) void resize_tables_kernel(MF_TABLES_ARGS,
                                                             ResizeTab* __restrict__ xtab, ResizeTab* __restrict__ ytab)
 {
+    MF_TABLES_LOAD(W, H)
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < W) {
         float fx = (float)(((double)i + 0.5) * scale_x - 0.5);
@@ -54,10 +56,11 @@ __global__ __launch_bounds__(256) void resize_tables_kernel(int cw, int ch, int 
 // instead of 16.  Anything that cannot be staged (a frame narrower than a chunk, the last rows of the stack, a call that scales down)
 // takes the direct path below, row by row.
 __global__ __launch_bounds__(64 * kWaves) void resize_kernel(const uint8_t* __restrict__ frames, uint8_t* __restrict__ out, int n,
-                                                     int W, int H, int left, int top, int cw,
+                                                     int W, int H, MF_RECT_ARGS,
                                                      const ResizeTab* __restrict__ xtab,
                                                      const ResizeTab* __restrict__ ytab, TileOrder order)
 {
+    MF_RECT_LOAD(W, H)
     __shared__ __attribute__((aligned(16))) uint8_t s_rows[kWaves][kSrcRows][kRowPitch + 16];
     int f, tile_y, tile_x;
     if (!order.decode(blockIdx.x, f, tile_y, tile_x)) return;
@@ -184,6 +187,7 @@ __global__ __launch_bounds__(64 * kWaves) void resize_kernel(const uint8_t* __re
     }
 }
 
+#ifndef MF_RESIZE_DEV          // (resize_dev.hip includes this file for the two kernels alone)
 size_t crop_resize_workspace_bytes(int W, int H) { return (size_t)(W + H) * sizeof(ResizeTab); }
 
 // resize_tables_kernel's tables of a cw x ch crop scaled to oW x oH (oW x-entries, then oH y-entries) in `work`
@@ -273,5 +277,6 @@ int launch_crop_resize_to(Px px, const void* frames, void* out, int n, int W, in
         return launch_resize8c4((const uint8_t*)frames, (uint8_t*)out, n, W, H, left, top, cw, oW, oH, up, work, order, st);
     return launch_resize8_to(px, (const uint8_t*)frames, (uint8_t*)out, n, W, H, left, top, cw, oW, oH, up, work, order, st);
 }
+#endif  // MF_RESIZE_DEV
 
 }  // namespace mf

@@ -10,12 +10,14 @@
 // mf_crop_resize_workspace_bytes(W, H) already sizes (8 bytes per column and per row); resize16_kernel: one thread per output pixel, a
 // workgroup per 256 pixels of an output row, taps straight from the frame (two 12-byte loads per pixel where sx + 1 is inside the crop).
 #include "mf_common.h"
+#include "resize_rect.h"
 
 namespace mf {
 
-__global__ __launch_bounds__(256) void resize16_tables_kernel(int cw, int ch, int W, int H, double scale_x, double scale_y,
+__global__ __launch_bounds__(256) void resize16_tables_kernel(MF_TABLES_ARGS,
                                                               Resize16Tab* __restrict__ xtab, Resize16Tab* __restrict__ ytab)
 {
+    MF_TABLES_LOAD(W, H)
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < W) {
         float fx = (float)(((double)i + 0.5) * scale_x - 0.5);
@@ -37,9 +39,10 @@ __global__ __launch_bounds__(256) void resize16_tables_kernel(int cw, int ch, in
 }
 
 __global__ __launch_bounds__(256) void resize16_kernel(const uint16_t* __restrict__ frames, uint16_t* __restrict__ out, int W, int H,
-                                                       int left, int top, int cw, const Resize16Tab* __restrict__ xtab,
+                                                       MF_RECT_ARGS, const Resize16Tab* __restrict__ xtab,
                                                        const Resize16Tab* __restrict__ ytab, TileOrder order)
 {
+    MF_RECT_LOAD(W, H)
     int f, y, tx;
     if (!order.decode(blockIdx.x, f, y, tx)) return;
     const int x = tx * 256 + (int)threadIdx.x;
@@ -77,6 +80,7 @@ __global__ __launch_bounds__(256) void resize16_kernel(const uint16_t* __restric
     d[2] = (uint16_t)o[2];
 }
 
+#ifndef MF_RESIZE_DEV          // (resize_dev.hip includes this file for the two kernels alone)
 // launch_crop_resize's launches for uint16 frames (shape, rectangle and tile count already checked there)
 int launch_resize16(const uint16_t* frames, uint16_t* out, int W, int H, int left, int top, int right, int bottom, const TileOrder& order,
                     void* work, hipStream_t st)
@@ -107,5 +111,6 @@ int launch_resize16_to(const uint16_t* frames, uint16_t* out, int W, int H, int 
     if (rc != MF_OK) return rc;
     return launch_resize16_to_kernel(frames, out, W, H, left, top, cw, oW, oH, 2 * oW == cw && 2 * oH == ch, xtab, ytab, order, st);
 }
+#endif  // MF_RESIZE_DEV
 
 }  // namespace mf

@@ -2,6 +2,7 @@
 // cv2.resize INTER_LINEAR.  The tables are resize.hip's (the same resize_tables_kernel, the same workspace, built by launch_crop_resize); this
 // translation unit adds only the kernel, so resize.hip's code object stays what it is (tools/isa_compare.py).
 #include "mf_common.h"
+#include "resize_rect.h"
 
 namespace mf {
 
@@ -31,10 +32,11 @@ constexpr int kSrcRows = kRows + 1;   // source rows a wavefront stages (_crop_f
 constexpr int kC1RowPitch = 272;      // 17 chunks: 258 bytes + up to 3 of misalignment in front
 
 __global__ __launch_bounds__(64 * kWaves) void resize8c1_kernel(const uint8_t* __restrict__ frames, uint8_t* __restrict__ out, int n,
-                                                        int W, int H, int left, int top, int cw,
+                                                        int W, int H, MF_RECT_ARGS,
                                                         const ResizeTab* __restrict__ xtab,
                                                         const ResizeTab* __restrict__ ytab, TileOrder order)
 {
+    MF_RECT_LOAD(W, H)
     __shared__ __attribute__((aligned(16))) uint8_t s_rows[kWaves][kSrcRows][kC1RowPitch];
     int f, tile_y, tile_x;
     if (!order.decode(blockIdx.x, f, tile_y, tile_x)) return;
@@ -129,6 +131,7 @@ __global__ __launch_bounds__(64 * kWaves) void resize8c1_kernel(const uint8_t* _
     }
 }
 
+#ifndef MF_RESIZE_DEV          // (resize_dev_c1.hip includes this file for the kernel alone)
 // launch_crop_resize's launch for single-channel frames (checks done and resize.hip's tables built there)
 int launch_resize8c1(const uint8_t* frames, uint8_t* out, int n, int W, int H, int left, int top, int cw, const void* work,
                      const TileOrder& order, hipStream_t st)
@@ -139,5 +142,6 @@ int launch_resize8c1(const uint8_t* frames, uint8_t* out, int n, int W, int H, i
                        order);
     return hip_fail(hipGetLastError(), "resize8c1_kernel launch");
 }
+#endif  // MF_RESIZE_DEV
 
 }  // namespace mf

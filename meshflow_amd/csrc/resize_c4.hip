@@ -4,6 +4,7 @@
 // the alpha plane.  The tables are resize.hip's (resize_tables_kernel, built by launch_crop_resize / launch_crop_resize_to for the output size);
 // this translation unit adds only the kernels, so the code objects of resize.hip and resize_to.hip stay what they are (tools/isa_compare.py).
 #include "mf_common.h"
+#include "resize_rect.h"
 
 #include <cmath>
 
@@ -69,10 +70,11 @@ __device__ __forceinline__ void store_c4(uint8_t* __restrict__ dst, uint32_t o, 
 // the direct form: four 4-byte loads per pixel at the clamped tap positions, nothing outside the frame stack read.
 template <int ROWS, int SLOTS, int PITCH, bool PAIRS>
 __global__ __launch_bounds__(64 * kWaves) void resize8c4_kernel(const uint8_t* __restrict__ frames, uint8_t* __restrict__ out, int n,
-                                                                int W, int H, int left, int top, int cw, int oW, int oH,
+                                                                int W, int H, MF_RECT_ARGS, int oW, int oH,
                                                                 const ResizeTab* __restrict__ xtab,
                                                                 const ResizeTab* __restrict__ ytab, TileOrder order)
 {
+    MF_RECT_LOAD(W, H)
     __shared__ __attribute__((aligned(16))) uint32_t s_rows[kWaves][SLOTS][PITCH > 0 ? PITCH / 4 : 1];
     int f, tile_y, tile_x;
     if (!order.decode(blockIdx.x, f, tile_y, tile_x)) return;
@@ -188,6 +190,7 @@ __global__ __launch_bounds__(64 * kWaves) void resize8c4_kernel(const uint8_t* _
     }
 }
 
+#ifndef MF_RESIZE_DEV          // (resize_dev_c4.hip includes this file for the kernel alone)
 int resize8c4_tile_rows(bool up) { return kWaves * (up ? kUpRows : kDownRows); }
 
 // launch_crop_resize's / launch_crop_resize_to's launch for 4-channel frames (checks done and resize.hip's tables for (oW, oH) built there)
@@ -210,5 +213,6 @@ int launch_resize8c4(const uint8_t* frames, uint8_t* out, int n, int W, int H, i
                            order);
     return hip_fail(hipGetLastError(), "resize8c4_kernel launch");
 }
+#endif  // MF_RESIZE_DEV
 
 }  // namespace mf

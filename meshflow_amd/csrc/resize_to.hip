@@ -5,6 +5,7 @@
 // (tools/isa_compare.py).
 #include "mf_common.h"
 #include "resize_u8.h"
+#include "resize_rect.h"
 
 #include <cmath>
 
@@ -31,6 +32,7 @@ constexpr int kDownRows = 2;                                   // output rows pe
 constexpr int kDownPitch = MF_RESIZE_TO_STAGE_BYTES;           // bytes of one staged source row (a multiple of 16)
 static_assert(kDownPitch % 16 == 0 && kDownPitch >= 16, "whole 16-byte chunks");
 
+#ifndef MF_RESIZE_DEV
 // Whether the widest span 256 output pixels of a cw -> oW row can take (3 (ceil(255 scale_x) + 3) bytes of `px_bytes`-byte pixels, with the
 // kernels' slack of `slack` bytes) fits `pitch`: the launchers pick the instantiation by it (each wavefront still checks its own span).
 static bool span_fits(int cw, int oW, int px_bytes, int slack, int pitch)
@@ -38,13 +40,15 @@ static bool span_fits(int cw, int oW, int px_bytes, int slack, int pitch)
     const double widest = (double)px_bytes * (std::ceil(255.0 * ((double)cw / (double)oW)) + 3.0);
     return widest + slack <= (double)pitch;
 }
+#endif
 
 template <int ROWS, int SLOTS, int PITCH, bool PAIRS>
 __global__ __launch_bounds__(64 * kWaves) void resize_to_kernel(const uint8_t* __restrict__ frames, uint8_t* __restrict__ out, int n,
-                                                                int W, int H, int left, int top, int cw, int oW, int oH,
+                                                                int W, int H, MF_RECT_ARGS, int oW, int oH,
                                                                 const ResizeTab* __restrict__ xtab,
                                                                 const ResizeTab* __restrict__ ytab, TileOrder order)
 {
+    MF_RECT_LOAD(W, H)
     __shared__ __attribute__((aligned(16))) uint8_t s_rows[kWaves][SLOTS][PITCH + 16];
     int f, tile_y, tile_x;
     if (!order.decode(blockIdx.x, f, tile_y, tile_x)) return;
@@ -190,10 +194,11 @@ constexpr int kC1RowPitch = 272;      // resize8c1_kernel's: 258 bytes + up to 3
 
 template <int ROWS, int SLOTS, int PITCH, bool PAIRS>
 __global__ __launch_bounds__(64 * kWaves) void resize8c1_to_kernel(const uint8_t* __restrict__ frames, uint8_t* __restrict__ out, int n,
-                                                                   int W, int H, int left, int top, int cw, int oW, int oH,
+                                                                   int W, int H, MF_RECT_ARGS, int oW, int oH,
                                                                    const ResizeTab* __restrict__ xtab,
                                                                    const ResizeTab* __restrict__ ytab, TileOrder order)
 {
+    MF_RECT_LOAD(W, H)
     __shared__ __attribute__((aligned(16))) uint8_t s_rows[kWaves][SLOTS][PITCH > 0 ? PITCH : 16];
     int f, tile_y, tile_x;
     if (!order.decode(blockIdx.x, f, tile_y, tile_x)) return;
@@ -304,10 +309,11 @@ __global__ __launch_bounds__(64 * kWaves) void resize8c1_to_kernel(const uint8_t
 // 16-bit form is (S00 + S01 + S10 + S11 + 2) >> 2 -- rounded half UP, where the float path would round the same quarter-sums half to even.
 // The tables there give sx = 2 dx, sy0 = 2 dy, sy1 = 2 dy + 1, so the four taps are the ones the float path reads.
 __global__ __launch_bounds__(256) void resize16_to_kernel(const uint16_t* __restrict__ frames, uint16_t* __restrict__ out, int W, int H,
-                                                          int left, int top, int cw, int oW, int oH, bool area,
+                                                          MF_RECT16_TO_ARGS,
                                                           const Resize16Tab* __restrict__ xtab, const Resize16Tab* __restrict__ ytab,
                                                           TileOrder order)
 {
+    MF_RECT16_TO_LOAD(W, H)
     int f, y, tx;
     if (!order.decode(blockIdx.x, f, y, tx)) return;
     const int x = tx * 256 + (int)threadIdx.x;
@@ -350,6 +356,7 @@ __global__ __launch_bounds__(256) void resize16_to_kernel(const uint16_t* __rest
     d[2] = (uint16_t)o[2];
 }
 
+#ifndef MF_RESIZE_DEV          // (resize_dev.hip includes this file for the three kernels alone)
 int resize_to_tile_rows(Px px, bool up)
 {
     if (px == Px::U16C3) return 1;
@@ -397,5 +404,6 @@ int launch_resize16_to_kernel(const uint16_t* frames, uint16_t* out, int W, int 
                        ytab, order);
     return hip_fail(hipGetLastError(), "resize16_to_kernel launch");
 }
+#endif  // MF_RESIZE_DEV
 
 }  // namespace mf

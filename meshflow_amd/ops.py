@@ -43,11 +43,11 @@ def _border_samples(ctype, top, count):
 
 
 # One row per pixel format of the device path: the frames it takes and the C calls that serve them (include/meshflow_hip.h).
-PixelFormat = collections.namedtuple('PixelFormat', 'dtype channels border warp warp_bounds warp_clip crop_resize crop_resize_to')
+PixelFormat = collections.namedtuple('PixelFormat', 'dtype channels border warp warp_bounds warp_clip crop_resize crop_resize_to crop_resize_dev')
 
 
 def _row(name, dtype, channels, ctype, top):
-    calls = (getattr(_lib_, f'mf_{op}_{name}') for op in ('warp', 'warp_bounds', 'warp_clip', 'crop_resize', 'crop_resize_to'))
+    calls = (getattr(_lib_, f'mf_{op}_{name}') for op in ('warp', 'warp_bounds', 'warp_clip', 'crop_resize', 'crop_resize_to', 'crop_resize_dev'))
     return PixelFormat(dtype, channels, _border_samples(ctype, top, channels), *calls)
 
 
@@ -294,6 +294,36 @@ def crop_resize(frames, bounds, out=None, size=None):
     work = torch.empty(_lib_.mf_crop_resize_workspace_bytes(oW, oH), dtype=torch.uint8, device=frames.device)
     _lib.check(fmt.crop_resize_to(_ptr(frames), _ptr(out), n, W, H, left, top, right, bottom, oW, oH, _ptr(work), _stream()))
     return out
+
+
+def crop_resize_resident(frames, bounds, out=None, size=None, status=None):
+    """`crop_resize` from a rectangle that stays on the device (mfs.py:1111-1157, mf_crop_resize_dev_*): `bounds` is a 4-element int32
+    DEVICE tensor {left, top, right, bottom} -- what `warp_clip` / `stabilize_resident` return -- that the kernels read when they execute,
+    in stream order; the host never reads it and the call never waits.  frames, out and size as in `crop_resize`; for a usable rectangle
+    the result is byte for byte `crop_resize(frames, tuple(bounds.tolist()), size=size)`.
+    Returns (cropped frames, status): status is an int32[1] device tensor -- the caller's (not reset here: it accumulates) or a new zeroed
+    one.  A rectangle that cannot be used (empty, a negative edge, outside the frame: what `crop_resize` raises ValueError for) adds 1 to
+    it and leaves `out` untouched; the caller reads it whenever it next synchronises."""
+    fmt = _frames_format(frames)
+    _need_bounds(bounds)
+    n, H, W = frames.shape[:3]
+    oW, oH = (W, H) if size is None else check_output_size(size)
+    shape = (n, oH, oW) + tuple(frames.shape[3:])
+    if out is None:
+        out = torch.empty(shape, dtype=frames.dtype, device=frames.device)
+    else:
+        _need(out, fmt.dtype, 'out')
+        if tuple(out.shape) != shape:
+            raise ValueError(f'out must have shape {shape} for size {(oW, oH)}, got {tuple(out.shape)}')
+    if status is None:
+        status = torch.zeros(1, dtype=torch.int32, device=frames.device)
+    else:
+        _need(status, torch.int32, 'status')
+        if status.numel() != 1:
+            raise ValueError('status must hold 1 int32')
+    work = torch.empty(_lib_.mf_crop_resize_workspace_bytes(oW, oH), dtype=torch.uint8, device=frames.device)
+    _lib.check(fmt.crop_resize_dev(_ptr(frames), _ptr(out), n, W, H, _ptr(bounds), oW, oH, _ptr(work), _ptr(status), _stream()))
+    return out, status
 
 
 def vertex_motion(early, late, offsets, homographies, max_per_pair, W, H, R, C, ellipse_rows, ellipse_cols):

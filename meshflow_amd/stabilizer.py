@@ -99,6 +99,18 @@ class DegenerateMeshError(ValueError):
         self.cells, self.clip_serial = cells, clip_serial
 
 
+class UnusableCropError(ValueError):
+    """The clip-level crop rectangle of a resident clip issued with crop=True cannot be used: it is empty (right < left or bottom < top:
+    the stabilised frames share no fully covered area) or leaves the frame -- where the reference's cv2.resize fails on an empty source
+    (mfs.py:1150-1155) and `ops.crop_resize` raises.  The clip's cropped frames are whatever the buffer held before; its uncropped frames,
+    rectangle and displacements are valid.  `clip_serial`: as for `DegenerateMeshError`."""
+
+    def __init__(self, clip_serial):
+        super().__init__(f'the crop rectangle of resident clip #{clip_serial} is empty or outside the frame (cv2.resize would fail on an '
+                         'empty source); its cropped frames are undefined')
+        self.clip_serial = clip_serial
+
+
 class MeshFlowStabilizer:
     ADAPTIVE_WEIGHTS_DEFINITION_ORIGINAL = 0
     ADAPTIVE_WEIGHTS_DEFINITION_FLIPPED = 1
@@ -510,15 +522,20 @@ class MeshFlowStabilizer:
     def _settle(slot):
         """The degenerate-mesh verdict of the clip that last used this table slot: waits for its 4-byte status read-back (issued behind
         that clip's warp on a stream of its own -- long finished when the slot comes up again two clips later) and raises if the clip had
-        cells without a homography.  The counter is cumulative per table; a slot remembers what it has seen."""
+        cells without a homography.  The counter is cumulative per table; a slot remembers what it has seen.  A clip issued with crop=True
+        brings its crop's status word along in the same read-back (the slot's second word): an unusable rectangle raises
+        UnusableCropError -- after the mesh verdict, which explains it more often than not."""
         pending, slot['pending'] = slot['pending'], None
         if pending is None:
             return
         pending['copied'].synchronize()
-        total = int(slot['host'][0])
+        total, crops = int(slot['host'][0]), int(slot['host'][1])
         bad, slot['seen'] = total - slot['seen'], total
+        empty, slot['crop_seen'] = crops - slot['crop_seen'], crops
         if bad and not pending['ignore']:
             raise DegenerateMeshError(bad, pending['serial'])
+        if empty and not pending['ignore']:
+            raise UnusableCropError(pending['serial'])
 
     def finish(self):
         """Waits for the verdict of every clip `stabilize_resident` has issued and not yet checked (it checks clip i when clip i + 2 is
@@ -563,7 +580,10 @@ class MeshFlowStabilizer:
                 torch.cuda.synchronize(dev)
                 st['tables'].popitem(last=False)
             pair = st['tables'][key] = [{'table': ops.CellTable(n, W, H, self.mesh_row_count, self.mesh_col_count, dev), 'free': None,
-                                         'pending': None, 'seen': 0, 'host': torch.zeros(1, dtype=torch.int32).pin_memory()} for _ in range(2)]
+                                         'pending': None, 'seen': 0, 'host': torch.zeros(2, dtype=torch.int32).pin_memory(),
+                                         # (crop=True: the slot's count of unusable crop rectangles, cumulative like the table's status;
+                                         # made by the first clip that crops, so that crop=False launches what it always did)
+                                         'crop_status': None, 'crop_seen': 0} for _ in range(2)]
         st['tables'].move_to_end(key)
         slot = pair[st['turn'] & 1]
         self._settle(slot)                                   # (raises BEFORE anything of the new clip is issued or any state changes)
@@ -611,10 +631,12 @@ class MeshFlowStabilizer:
         d_stab.record_stream(torch.cuda.current_stream(dev))      # allocated on the prep stream, handed to the caller's
         return d_stab
 
-    def _resident_warp(self, d_frames, d_unstab, d_stab, out=None, chunks=None, warp_events=None, check='deferred'):
+    def _resident_warp(self, d_frames, d_unstab, d_stab, out=None, chunks=None, warp_events=None, check='deferred', verdict=True):
         """Stages 2-4, mfs.py:909-1108, for the d_stab `_resident_jacobi` just produced.  Returns (stabilized frames, bounds, table):
         bounds = the clip-level rectangle in a 16-byte tensor of this clip's own (the kernels fold it together there), table.crop per
         frame (valid until the table's next turn, two clips on).
+        verdict=False leaves the status read-back to the caller, who issues it behind the crop (`_resident_verdict` with the returned
+        st['open'] = (slot, end event)).
         warp_events: two torch events recorded on the current stream in front of and behind the warp kernel(s) (bench.py's roofline)."""
         import torch
         from . import ops
@@ -674,25 +696,40 @@ class MeshFlowStabilizer:
             end = warp_events[1] if warp_events else torch.cuda.Event()
             end.record(main)
         slot['free'] = end
+        st['open'] = (slot, end)
+        if verdict:
+            self._resident_verdict(st, check)
+        return out, bounds, table
+
+    def _resident_verdict(self, st, check, cropped=False):
+        """Issues the status read-back of the clip `_resident_warp` has just queued (behind its warp; cropped=True: behind whatever is on
+        the current stream now, i.e. the clip's crop, whose status word then rides along) and, under check=True, waits for it."""
+        import torch
+        slot, end = st.pop('open')
+        table = slot['table']
+        if cropped:
+            end = torch.cuda.Event()
+            end.record(torch.cuda.current_stream(st['device']))
         # the degenerate-cell counter of this clip, 4 bytes into pinned memory on a stream of their own behind the warp: no marker on
         # the caller's stream, nobody waits -- `_settle` looks at it when this slot comes up again (or `finish()` does); check='never'
         # only keeps the slot's running total in step
         ss = st['status']
         ss.wait_event(end)
         with torch.cuda.stream(ss):
-            slot['host'].copy_(table.status, non_blocking=True)
+            slot['host'][:1].copy_(table.status, non_blocking=True)
+            if cropped:
+                slot['host'][1:].copy_(slot['crop_status'], non_blocking=True)
             copied = torch.cuda.Event()
             copied.record(ss)
         st['serial'] += 1
         slot['pending'] = {'copied': copied, 'serial': st['serial'], 'ignore': check == 'never' or check is False}
         if check is True or check == 'now':
             self._settle(slot)
-        return out, bounds, table
 
     def stabilize_resident(self, d_frames, d_disp, homographies, adaptive_weights_definition=ADAPTIVE_WEIGHTS_DEFINITION_ORIGINAL,
                            out=None, frame_range=None, inputs_ready=None, check=True, collective=False, warp_events=None,
-                           jacobi_events=None):
-        """mfs.py:150-158 for a clip whose frames (n, H, W, 3) uint8 or uint16 -- or (n, H, W) uint8 grey, or (n, H, W, 4) uint8 BGRA / RGBA
+                           jacobi_events=None, crop=False, output_size=None, cropped_out=None):
+        """mfs.py:150-158 (crop=True: mfs.py:150-162, `_crop_frames` included) for a clip whose frames (n, H, W, 3) uint8 or uint16 -- or (n, H, W) uint8 grey, or (n, H, W, 4) uint8 BGRA / RGBA
         -- and vertex displacements (F, R+1, C+1, 2) float64 are RESIDENT in HBM (uint16, grey and 4-channel frames: `ops.warp`; the sweep,
         tables and rectangle are the uint8 call's; 4-channel frames get alpha 0 where the warp uncovers the frame, the 3-component
         color_outside_image_area_bgr padded as cv::Scalar pads it): Jacobi sweep -> cell tables -> warp + crop rectangle, nothing leaves the device, one call per clip, NO synchronisation:
@@ -710,6 +747,16 @@ class MeshFlowStabilizer:
         of clip i is then looked at when clip i + 2 is issued (its table slot comes up again; BEFORE anything of the new clip is queued,
         which is then not issued) or by `finish()`, whichever comes first -- such a caller MUST end with `finish()`.  check='never'
         skips it.  Clips after a degenerate one are unaffected.
+        crop=True adds the reference's last step, `_crop_frames` (mfs.py:159, 1111-1157), on the device: the frames cropped to the
+        clip-level rectangle and scaled back to (W, H) -- or to output_size=(width, height), cv2.resize's dsize order, which needs
+        crop=True -- by kernels that read the rectangle from `bounds` themselves (`ops.crop_resize_resident`): the host never learns it and
+        never waits for it.  The call then returns (frames, bounds, d_stab, cropped); `cropped` (cropped_out if given: (n, height, width
+        [, channels]) of the frames' dtype) is valid in current-stream order.  With frame_range and collective=True the crop uses the
+        all-reduced rectangle.  A rectangle that cannot be used (empty: the stabilised frames share no covered area; cv2.resize would
+        fail on an empty source) leaves `cropped` unwritten and is reported like a degenerate mesh, by the same read-back: `UnusableCropError`
+        (a ValueError with the clip's serial number) from this call under check=True, two clips later or from `finish()` under
+        check='deferred', never under check='never'.  crop=False (the default) is the call as it always was: the same 3-tuple, the same
+        launches.
         warp_events / jacobi_events: pairs of torch events recorded around the warp kernel (caller's stream) and the sweep stage (prep
         stream) -- bench.py's roofline brackets.
         One host thread per stabilizer object here: the calls of a pipeline are ordered by construction (table slots take turns, the
@@ -718,6 +765,12 @@ class MeshFlowStabilizer:
         import torch
         from . import dist as mfdist, ops
         self._check_definition(adaptive_weights_definition)
+        if output_size is not None:
+            if not crop:
+                raise ValueError('output_size needs crop=True: it is the size of the cropped frames')
+            output_size = ops.check_output_size(output_size, 'output_size')
+        if cropped_out is not None and not crop:
+            raise ValueError('cropped_out needs crop=True')
         if check is False:
             check = 'never'
         F = d_disp.shape[0]
@@ -740,7 +793,8 @@ class MeshFlowStabilizer:
             return d_stab
 
         def warp_fn(lo_, hi_, d_stab):
-            frames, bounds, _ = self._resident_warp(d_frames, d_disp[lo_:hi_], d_stab[lo_:hi_], out=out, warp_events=warp_events, check=check)
+            frames, bounds, _ = self._resident_warp(d_frames, d_disp[lo_:hi_], d_stab[lo_:hi_], out=out, warp_events=warp_events, check=check,
+                                                    verdict=not crop)
             return frames, bounds
 
         on_prep = self.resident_chunks > 0 or self.resident_rectangle == 'early'       # the rectangle is final on the prep stream, early
@@ -760,7 +814,24 @@ class MeshFlowStabilizer:
                 bounds.record_stream(main)
             elif self.resident_chunks <= 0:
                 main.wait_event(st['scanned'])               # (the chunked arrangement joins the streams inside mf_warp_clip_u8c3)
-        return frames, bounds, d_stab
+        if not crop:
+            return frames, bounds, d_stab
+        # _crop_frames (mfs.py:159): behind the warp on the caller's stream, where the (all-reduced) rectangle is final by now; the kernels
+        # read it from `bounds`, so nothing here waits.  The clip's status read-back goes behind the crop and takes its status word along.
+        if n == 0:                                           # an empty shard: nothing to crop, no table slot, no verdict
+            oW, oH = output_size if output_size is not None else (W, H)
+            shape = (0, oH, oW) + tuple(d_frames.shape[3:])
+            if cropped_out is not None and tuple(cropped_out.shape) != shape:
+                raise ValueError(f'cropped_out must have shape {shape}, got {tuple(cropped_out.shape)}')
+            return frames, bounds, d_stab, (cropped_out if cropped_out is not None else d_frames.new_empty(shape))
+        slot = st['open'][0]
+        if slot['crop_status'] is None:
+            slot['crop_status'] = torch.zeros(1, dtype=torch.int32, device=dev)
+        try:
+            cropped, _ = ops.crop_resize_resident(frames, bounds, out=cropped_out, size=output_size, status=slot['crop_status'])
+        finally:
+            self._resident_verdict(st, check, cropped=True)
+        return frames, bounds, d_stab, cropped
 
     def _stabilized_frames_device(self, d_frames, d_unstab, d_stab, out=None, table=None):
         """d_frames: (n, H, W, 3) uint8; d_unstab/d_stab: (n, R+1, C+1, 2) float64, all in HBM.
