@@ -197,6 +197,24 @@ int mf_warp_clip_u8c4(const uint8_t* d_frames, uint8_t* d_out, const double* d_u
                       int R, int C, const uint8_t border_bgra[4], void* d_table, int32_t* d_crop, int32_t* d_bounds, int32_t* d_status,
                       int chunks, void* prep_stream, void* stream);
 
+/* ---- the warp's float32 coordinate maps instead of pixels (mfs.py:983-984, 1054-1061: frame_stabilized_x_y, what cv2.remap is given at
+ * mfs.py:1063-1069) ----
+ * d_maps: [count][H][W][2] float32, x first, 8-byte aligned (16-byte aligned stacks get 16-byte stores); all offsets are 64-bit.  For the
+ * frames first .. first + count - 1 of d_table (n, W, H, R, C describe the table, as for mf_crop_scan_f64) every output pixel gets the source
+ * coordinates the pixel warps sample at, bit for bit: owner = last cell in row-major order whose warped mask is non-zero (cells with a
+ * non-zero status own nothing), (u, v) = float32(((x m0 + y m1) + m2) (1/w)), float32(((x m3 + y m4) + m5) (1/w)) from that cell's
+ * inverse homography in float64, (0, 0) where |w| <= FLT_EPSILON (cv2.perspectiveTransform); a pixel NO cell owns holds
+ * (float32(W + 1), float32(H + 1)), the map template of mfs.py:983-984, which cv2.remap answers with the border colour.  No frame is read:
+ * a caller samples any layer that must move with the video -- labels, depth, float32 planes -- with a sampler of its own.  The four edge scans
+ * (mfs.py:1075-1098) of these frames are folded into d_crop (the table's [n][4] rows; rows outside the range are not touched) and the clip
+ * rectangle exactly as mf_warp_u8c3 does: running it before or after a pixel warp on the same table changes nothing.  mf_warp_maps_bounds_f32:
+ * the rectangle in the caller's d_bounds[4], as mf_warp_bounds_u8c3.  count == 0 is a no-op.  first < 0, count < 0, first + count > n, null
+ * pointers, a misaligned d_maps, bad sizes, W or H outside 2 .. 32,767 and R or C > 64 return MF_ERR_INVALID_ARG before anything is launched. */
+int mf_warp_maps_f32(const void* d_table, float* d_maps, int n, int W, int H, int R, int C, int first, int count, int32_t* d_crop,
+                     void* stream);
+int mf_warp_maps_bounds_f32(const void* d_table, float* d_maps, int n, int W, int H, int R, int C, int first, int count, int32_t* d_crop,
+                            int32_t* d_bounds, void* stream);
+
 /* Clip-level crop bounds (mfs.py:1103-1106): {max left, max top, min right, min bottom} over n frames.
  * d_bounds: [4] int32. */
 int mf_crop_reduce(const int32_t* d_crop, int n, int W, int H, int32_t* d_bounds, void* stream);

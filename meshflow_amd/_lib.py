@@ -61,6 +61,8 @@ SIGNATURES = {
     'mf_warp_clip_u8c4': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
     'mf_crop_resize_u8c4': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     'mf_crop_resize_to_u8c4': (_i, [_vp, _vp] + [_i] * 9 + [_vp, _vp]),
+    'mf_warp_maps_f32': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    'mf_warp_maps_bounds_f32': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     'mf_crop_resize_dev_u8c3': (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp]),
     'mf_crop_resize_dev_u16c3': (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp]),
     'mf_crop_resize_dev_u8c1': (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp]),

@@ -37,6 +37,24 @@ static int warp_entry(const char* name, Px px, const void* d_frames, void* d_out
     return launch_warp(px, d_frames, d_out, tv, n, W, H, R, C, pack_border(px, border), d_crop, (hipStream_t)stream);
 }
 
+// The checks of the two coordinate-map entries, then launch_warp's Px::MAPS launches on the table's frames first .. first + count - 1.
+static int warp_maps_entry(const char* name, const void* d_table, float* d_maps, int n, int W, int H, int R, int C, int first, int count,
+                           int32_t* d_crop, bool has_bounds, int32_t* d_bounds, void* stream)
+{
+    if (!d_table || !d_crop || (has_bounds && !d_bounds) || (count > 0 && !d_maps)) { set_error("%s: null pointer", name); return MF_ERR_INVALID_ARG; }
+    if (n <= 0 || R <= 0 || C <= 0) { set_error("%s: bad sizes", name); return MF_ERR_INVALID_ARG; }
+    if (first < 0 || count < 0 || first > n || count > n - first) {
+        set_error("%s: frames first=%d count=%d are not inside the table's n=%d", name, first, count, n);
+        return MF_ERR_INVALID_ARG;
+    }
+    if (((uintptr_t)d_maps & 7u) != 0) { set_error("%s: d_maps must be 8-byte aligned", name); return MF_ERR_INVALID_ARG; }
+    if (count == 0) return MF_OK;
+    TableView tv = table_view(const_cast<void*>(d_table), n, W, H, R, C);
+    if (has_bounds) tv.bounds = d_bounds;
+    return launch_warp(Px::MAPS, nullptr, d_maps, table_slice(tv, first, W, H, R, C), count, W, H, R, C, 0, d_crop + 4 * (size_t)first,
+                       (hipStream_t)stream);
+}
+
 static int crop_resize_entry(const char* name, Px px, const void* d_frames, void* d_out, int n, int W, int H, int left, int top, int right,
                              int bottom, void* d_work, void* stream)
 {
@@ -171,6 +189,17 @@ int mf_crop_scan_f64(const void* d_table, int n, int W, int H, int R, int C, int
     if (n <= 0 || R <= 0 || C <= 0) { set_error("mf_crop_scan_f64: bad sizes"); return MF_ERR_INVALID_ARG; }
     const TableView tv = table_view(const_cast<void*>(d_table), n, W, H, R, C);
     return launch_crop_scan(tv, n, W, H, R, C, d_crop, (hipStream_t)stream);
+}
+
+int mf_warp_maps_f32(const void* d_table, float* d_maps, int n, int W, int H, int R, int C, int first, int count, int32_t* d_crop, void* stream)
+{
+    return warp_maps_entry("mf_warp_maps_f32", d_table, d_maps, n, W, H, R, C, first, count, d_crop, false, nullptr, stream);
+}
+
+int mf_warp_maps_bounds_f32(const void* d_table, float* d_maps, int n, int W, int H, int R, int C, int first, int count, int32_t* d_crop,
+                            int32_t* d_bounds, void* stream)
+{
+    return warp_maps_entry("mf_warp_maps_bounds_f32", d_table, d_maps, n, W, H, R, C, first, count, d_crop, true, d_bounds, stream);
 }
 
 // ---- the same three calls with the clip-level rectangle in the CALLER's d_bounds[4] instead of inside the table blob ----

@@ -224,11 +224,16 @@ inline bool make_tile_order(int tiles_x, int tiles_y, int n, TileOrder& o)
 
 // Pixel format of a frame stack: the _u8c3 / _u16c3 / _u8c1 / _u8c4 calls of include/meshflow_hip.h.  Every layer takes the format as this
 // one parameter; a new format is a row here plus its kernels.
-enum class Px { U8C3, U16C3, U8C1, U8C4 };
-constexpr int px_channels(Px p) { return p == Px::U8C1 ? 1 : p == Px::U8C4 ? 4 : 3; }
-constexpr int px_sample_bytes(Px p) { return p == Px::U16C3 ? 2 : 1; }
+// Px::MAPS is no frame format: the warp that reads no frame and writes the float32 coordinate maps (u, v) themselves, [H][W][2] per
+// frame (mf_warp_maps_f32, warp_maps.hip) -- "2 channels of 4 bytes" as far as launch_warp's frame stride goes.
+enum class Px { U8C3, U16C3, U8C1, U8C4, MAPS };
+constexpr int px_channels(Px p) { return p == Px::U8C1 ? 1 : p == Px::U8C4 ? 4 : p == Px::MAPS ? 2 : 3; }
+constexpr int px_sample_bytes(Px p) { return p == Px::U16C3 ? 2 : p == Px::MAPS ? 4 : 1; }
 constexpr int px_bytes(Px p) { return px_channels(p) * px_sample_bytes(p); }
-constexpr const char* px_name(Px p) { return p == Px::U8C3 ? "u8c3" : p == Px::U16C3 ? "u16c3" : p == Px::U8C1 ? "u8c1" : "u8c4"; }
+constexpr const char* px_name(Px p)
+{
+    return p == Px::U8C3 ? "u8c3" : p == Px::U16C3 ? "u16c3" : p == Px::U8C1 ? "u8c1" : p == Px::U8C4 ? "u8c4" : "maps_f32";
+}
 // The border colour as the warp kernels take it, from the caller's px_channels(p) samples: B | G << 8 | R << 16 (u8c3),
 // B | G << 16 | R << 32 (u16c3), the byte (u8c1), B | G << 8 | R << 16 | A << 24 (u8c4).
 inline uint64_t pack_border(Px p, const void* samples)
@@ -269,6 +274,7 @@ struct WarpRange {
 };
 void launch_warp8c1_range(const WarpGeom& g, const WarpRange& r, int W, int H, int C, uint32_t border, bool stage, hipStream_t st);  // warp_c1.hip
 void launch_warp8c4_range(const WarpGeom& g, const WarpRange& r, int W, int H, int C, uint32_t border, bool stage, hipStream_t st);  // warp_c4.hip
+void launch_maps_range(const WarpGeom& g, const WarpRange& r, int W, int H, int C, hipStream_t st);  // warp_maps.hip (r.frames unused, r.out: float32 maps)
 int launch_crop_scan(const TableView& tv, int n, int W, int H, int R, int C, int32_t* crop, hipStream_t st);
 int check_d16_zero_fill(hipStream_t st);          // warp.hip: one-time device check the byte-tap kernels rely on
 int launch_selftest_recip(unsigned long long n, unsigned long long seed, unsigned long long* d_mismatches, hipStream_t st);

@@ -1022,6 +1022,27 @@ __device__ __forceinline__ void remap_store_u8c4(const float (&u)[4], const floa
     }
 }
 
+// ---- the coordinate maps themselves: frame_stabilized_x_y of mfs.py:1054-1061, the arrays cv2.remap gets at mfs.py:1063-1069 ------------
+// Footprint-level tail of the MAPS instantiation of footprint_body: the lane's four pixels' source coordinates (u, v) go to
+// maps[f][y][x0 + j] = {u, v} as they are -- float32 [H][W][2], x first; a pixel no cell owns holds (W+1, H+1) already (mfs.py:983-984).
+// The lane's four pixels are 32 contiguous bytes: two 16-byte stores where that address is 16-byte aligned (always, for an even W and an
+// aligned stack; every other row for an odd W), else 8 bytes per pixel, and per pixel too in the lane that overhangs the right edge
+// (x < W).  `maps` is 8-byte aligned at least; all offsets are 64-bit (300 frames of 1080p are 4.98 GB).
+__device__ __forceinline__ void maps_store_f32(const float (&u)[4], const float (&v)[4], uint32_t f, int x0, int y, bool active, int W, int H,
+                                               float* __restrict__ maps)
+{
+    if (!active) return;                                                // (y < H and x0 < W)
+    float* __restrict__ d = maps + 2ull * ((uint64_t)f * (uint64_t)((uint32_t)W * (uint32_t)H) + (uint64_t)((uint32_t)y * (uint32_t)W + (uint32_t)x0));
+    if (x0 + 3 < W && ((uintptr_t)d & 15u) == 0) {
+        *reinterpret_cast<float4*>(d) = make_float4(u[0], v[0], u[1], v[1]);
+        *reinterpret_cast<float4*>(d + 4) = make_float4(u[2], v[2], u[3], v[3]);
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (x0 + j < W) *reinterpret_cast<float2*>(d + 2 * j) = make_float2(u[j], v[j]);
+    }
+}
+
 // ---- EXPERIMENT builds only (tools/phase_profile.sh; nothing of this is in the product library) ------------------------------------
 // -DMF_EXP_SKIP=mask: TIMING-ONLY kernels in which the wavefronts of a path class return right after the plan test that selects
 // them (their output is garbage): 1 hot, 2 border, 4 pair, 8 multi, 16 everything else, 32 every wavefront right after the plan and
@@ -1054,6 +1075,9 @@ __device__ unsigned long long mf_exp_phase[8];
 // PX = Px::U8C4: the same for 4-channel uint8 frames (warp8c4_footprint): `frames` / `out` hold 4 W H bytes per frame, the border is the whole
 // `border` word, and the pixels go through remap_store_u8c4.  With STAGE (C4_STAGE below) the plan's STAGED windows (not the BORDER ones) are
 // re-cut for 4-byte pixels (MF_C4_COLS) and copied to LDS at the start; the hot and pair footprints take the grey warp's shortcuts.
+// PX = Px::MAPS: the coordinate maps instead of pixels (maps_footprint, warp_maps.hip): SCAN's body -- ownership, coordinates, the four edge
+// tests on every footprint -- plus the store of (u, v) (maps_store_f32): `frames` is unused, `out` points to float32 [n][H][W][2].  No window, no
+// taps, no border colour; the hot and pair footprints take the grey warp's shortcuts (they need no window here), everything else the general path.
 template <Px PX, bool STAGE, bool SCAN>
 __device__ __forceinline__ void footprint_body(const uint32_t f, const uint32_t t, const FootPlan* __restrict__ plan, const FootRegion* __restrict__ regions,
                                                const WarpGeom& g, const uint8_t* __restrict__ frames,
@@ -1069,13 +1093,15 @@ __device__ __forceinline__ void footprint_body(const uint32_t f, const uint32_t 
     constexpr bool U16 = PX == Px::U16C3, GREY = PX == Px::U8C1, GREY_STAGE = GREY && STAGE;
     // C4_STAGE: the 4-channel warp of a 4-byte aligned clip; WIN_STAGE: a re-cut window (grey or 4-byte) and the hot / pair shortcuts on it
     constexpr bool C4 = PX == Px::U8C4, C4_STAGE = C4 && STAGE, WIN_STAGE = GREY_STAGE || C4_STAGE;
+    constexpr bool MAPS = PX == Px::MAPS;
+    static_assert(!MAPS || (!STAGE && !SCAN), "the maps kernel reads no frame: nothing to stage");
     // inverse homographies of the footprint's candidate cells: [entry][Hi0..Hi8, pad] (80-byte rows)
     __shared__ __attribute__((aligned(16))) double s_hi[1][9][10];                // row 8: the "no cell" matrix, see OWN_NONE
     // source region of the footprint: MF_STAGE_ROWS rows of MF_STAGE_PITCH bytes (+ slack for the third dword of the last tap); the 4-byte
     // window's MF_STAGE_ROWS rows of MF_C4_PITCH bytes for U8C4
-    __shared__ __attribute__((aligned(16))) uint8_t s_src_all[SCAN ? 16 : C4 ? LDS_WINDOW_PAD + MF_STAGE_ROWS * MF_C4_PITCH
+    __shared__ __attribute__((aligned(16))) uint8_t s_src_all[SCAN || MAPS ? 16 : C4 ? LDS_WINDOW_PAD + MF_STAGE_ROWS * MF_C4_PITCH
                                                                              : LDS_WINDOW_PAD + LDS_WINDOW_BYTES + 64];
-    uint8_t* const s_src = &s_src_all[SCAN ? 0 : LDS_WINDOW_PAD];
+    uint8_t* const s_src = &s_src_all[SCAN || MAPS ? 0 : LDS_WINDOW_PAD];
     constexpr int wave = 0;
     MF_EXP_STAMP(exp_t0);
     const uint32_t ty = (__umulhi(t, g.div_m) + (t & g.div_pass)) >> g.div_s, tx = t - ty * g.nfx;
@@ -1312,22 +1338,24 @@ __device__ __forceinline__ void footprint_body(const uint32_t f, const uint32_t 
         return;
     }
 
-    if constexpr (WIN_STAGE) {
-        if (gwin.on && (pv.x & (MF_PLAN_HOT << 16)) != 0) {
+    if constexpr (WIN_STAGE || MAPS) {
+        if ((MAPS || gwin.on) && (pv.x & (MF_PLAN_HOT << 16)) != 0) {
             // the HOT footprints of the grey warp (one IN cell, certified denominator, deep, staged): the hot path's coordinates -- the cheap
             // chain where the plan allows it (FAST64), else the trimmed-reciprocal one -- without the general path's ownership code
             const crec_t rec = frec + (pv.x & 0xFFFu) * MF_CELL_DOUBLES;
             float u[4], v[4];
             if (!((pv.x >> 16) & MF_PLAN_FAST64) || !cell_coords_fast(rec, xs0, yy, u, v))
                 cell_coords<false>(rec, xs0, yy, x0, 0xFu, u, v, true);
-            if constexpr (C4) remap_store_u8c4(u, v, f, x0, y, true, W, H, frames, out, border, crop, clip, gwin, &s_src[0]);
+            // (MAPS: a hot footprint is whole and DEEP -- every lane stores, no pixel can pass a crop test)
+            if constexpr (MAPS) maps_store_f32(u, v, f, x0, y, true, W, H, reinterpret_cast<float*>(out));
+            else if constexpr (C4) remap_store_u8c4(u, v, f, x0, y, true, W, H, frames, out, border, crop, clip, gwin, &s_src[0]);
             else remap_store_u8c1(u, v, f, x0, y, true, W, H, frames, out, border, crop, clip, gwin, &s_src[0]);
             return;
         }
     }
     const cedge_t fedge = (cedge_t)(uintptr_t)(reinterpret_cast<const uint8_t*>(edges) + f * g.edge_frame_bytes);
-    if constexpr (WIN_STAGE) {
-        if (gwin.on && (pv.y & MF_PLAN_HOT) != 0) {
+    if constexpr (WIN_STAGE || MAPS) {
+        if ((MAPS || gwin.on) && (pv.y & MF_PLAN_HOT) != 0) {
             // the PAIR footprints of the grey warp (two cells, certified denominators, deep, staged): warp_kernel's per-pixel pair form --
             // the later cell owns a pixel where its one mask edge passes (one fma), the other cell the rest, both matrices in LDS; a pixel
             // inside the edge's float32 error band leaves the footprint to the general code
@@ -1366,7 +1394,8 @@ __device__ __forceinline__ void footprint_body(const uint32_t f, const uint32_t 
                     u[j] = (float)(((xs * h01.x + yy * h01.y) + h23.x) * iw);
                     v[j] = (float)(((xs * h23.y + yy * h45.x) + h45.y) * iw);
                 }
-                if constexpr (C4) remap_store_u8c4(u, v, f, x0, y, true, W, H, frames, out, border, crop, clip, gwin, &s_src[0]);
+                if constexpr (MAPS) maps_store_f32(u, v, f, x0, y, true, W, H, reinterpret_cast<float*>(out));
+                else if constexpr (C4) remap_store_u8c4(u, v, f, x0, y, true, W, H, frames, out, border, crop, clip, gwin, &s_src[0]);
                 else remap_store_u8c1(u, v, f, x0, y, true, W, H, frames, out, border, crop, clip, gwin, &s_src[0]);
                 return;
             }
@@ -1897,9 +1926,10 @@ __device__ __forceinline__ void footprint_body(const uint32_t f, const uint32_t 
             }
         }
 
-        if (SCAN) {
+        if (SCAN || MAPS) {
             // The crop-boundary scan alone, mfs.py:1075-1098 (the same tests as on the generic path below; there they run only when
-            // some pixel of the footprint is not deep inside the frame -- a pixel that is cannot pass any of them).
+            // some pixel of the footprint is not deep inside the frame -- a pixel that is cannot pass any of them).  MAPS: the same
+            // fold, then the coordinates themselves.
             int c_left = 0, c_top = 0, c_right = W - 1, c_bottom = H - 1;
             if (active) {
 #pragma unroll
@@ -1930,6 +1960,7 @@ __device__ __forceinline__ void footprint_body(const uint32_t f, const uint32_t 
                     if (c_bottom != H - 1) { atomicMin(&crop[4 * f + 3], c_bottom); atomicMin(&clip[3], c_bottom); }
                 }
             }
+            if constexpr (MAPS) maps_store_f32(u, v, f, x0, y, active, W, H, reinterpret_cast<float*>(out));
             return;
         }
         if constexpr (U16) {
@@ -2386,17 +2417,19 @@ int launch_warp(Px px, const void* frames, void* out, const TableView& tv, int n
     // staging reads dword-aligned 16-byte chunks: needs a 4-byte aligned clip (W % 4 == 0 is checked by the plan); the plan's windows
     // are re-cut for 1- and 4-byte pixels, not for 6-byte ones, so uint16 frames never stage
     const bool stage = px != Px::U16C3 && ((uintptr_t)frames & 3u) == 0;
-    const size_t frame_bytes = (size_t)W * H * px_bytes(px);
+    const size_t frame_bytes = (size_t)W * H * px_bytes(px);            // (Px::MAPS: `frames` is null and stays unused, `out` holds 8 W H bytes per frame)
     for (int f0 = 0; f0 < n; f0 += (int)per_launch) {
         const int m = n - f0 < (int)per_launch ? n - f0 : (int)per_launch;
         const WarpRange r{ tv.plan + (size_t)f0 * g.per_frame, tv.regions + (size_t)f0 * g.per_frame,
                            tv.records + (size_t)f0 * R * C * MF_CELL_DOUBLES, tv.edges + (size_t)f0 * R * C * MF_EDGE_FLOATS,
-                           (const uint8_t*)frames + f0 * frame_bytes, (uint8_t*)out + f0 * frame_bytes, crop + 4 * (size_t)f0, tv.bounds, m };
+                           frames ? (const uint8_t*)frames + f0 * frame_bytes : nullptr, (uint8_t*)out + f0 * frame_bytes, crop + 4 * (size_t)f0, tv.bounds, m };
         const dim3 grid(g.per_xcd * 8u, (uint32_t)m);                  // one wavefront per 32 x 8 footprint
         if (px == Px::U8C1)
             launch_warp8c1_range(g, r, W, H, C, (uint32_t)border, stage, st);
         else if (px == Px::U8C4)
             launch_warp8c4_range(g, r, W, H, C, (uint32_t)border, stage, st);
+        else if (px == Px::MAPS)
+            launch_maps_range(g, r, W, H, C, st);
         else if (px == Px::U16C3)
             hipLaunchKernelGGL(warp16_footprint, grid, dim3(64), 0, st, r.plan, r.regions, g, (const uint16_t*)r.frames, r.records, (uint16_t*)r.out,
                                r.edges, m, W, H, C, border, r.crop, r.bounds);
@@ -2408,7 +2441,7 @@ int launch_warp(Px px, const void* frames, void* out, const TableView& tv, int n
                                r.edges, m, W, H, C, (uint32_t)border, r.crop, r.bounds);
     }
     return hip_fail(hipGetLastError(), px == Px::U8C3 ? "warp_kernel launch" : px == Px::U16C3 ? "warp16_footprint launch" :
-                                       px == Px::U8C1 ? "warp8c1_footprint launch" : "warp8c4_footprint launch");
+                                       px == Px::U8C1 ? "warp8c1_footprint launch" : px == Px::U8C4 ? "warp8c4_footprint launch" : "maps_footprint launch");
 }
 
 int launch_crop_scan(const TableView& tv, int n, int W, int H, int R, int C, int32_t* crop, hipStream_t st)

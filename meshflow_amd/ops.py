@@ -249,6 +249,67 @@ def crop_scan(table, bounds=None):
     return table.crop
 
 
+def _maps_range(table, first, count):
+    """(first, count) of a `warp_maps` call as two ints inside the table's frames; count=None: up to the table's last frame."""
+    for name, v in (('first', first), ('count', count)):
+        if v is not None and (isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer))):
+            raise ValueError(f'{name} must be an int, got {v!r}')
+    first = int(first)
+    if not 0 <= first <= table.n:
+        raise ValueError(f'first={first} is not inside the cell table\'s {table.n} frames')
+    count = table.n - first if count is None else int(count)
+    if count < 0 or count > table.n - first:
+        raise ValueError(f'frames first={first} count={count} are not inside the cell table\'s {table.n} frames')
+    return first, count
+
+
+def warp_maps(table, first=0, count=None, out=None, bounds=None):
+    """The warp's float32 coordinate maps instead of pixels (mf_warp_maps_f32; the reference's frame_stabilized_x_y, mfs.py:1054-1061, which
+    it hands to cv2.remap at mfs.py:1063-1069): for the table's frames first .. first + count - 1 (count=None: up to the last) a
+    (count, H, W, 2) float32 tensor on the table's device, x first -- maps[f, y, x] = the source position (u, v) the pixel warps sample for
+    output pixel (x, y), bit for bit; a pixel no cell owns holds (W + 1, H + 1) (mfs.py:983-984), which lies outside every frame.  No frame is
+    read: sample any layer that has to move with the video (labels, depth, float32 planes) with a sampler of your own, e.g.
+    `torch.nn.functional.grid_sample(layer, maps_to_grid(maps))`.  A long clip can be walked through an `out` of a few frames.
+    The frames' crop values accumulate in table.crop (rows outside the range are not touched) and the clip-level rectangle in `bounds` /
+    table.clip_bounds exactly as `warp` does it; calling both on one table changes nothing."""
+    first, count = _maps_range(table, first, count)
+    shape = (count, table.H, table.W, 2)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=table.device)
+    else:
+        _need(out, torch.float32, 'out')
+        if tuple(out.shape) != shape:
+            raise ValueError(f'out must have shape {shape} for frames {first} .. {first + count - 1}, got {tuple(out.shape)}')
+        if out.device != torch.device(table.device):
+            raise ValueError(f'out must be on the cell table\'s device {table.device}, got {out.device}')
+    if bounds is None:
+        _lib.check(_lib_.mf_warp_maps_f32(_ptr(table.buf), _ptr(out), table.n, table.W, table.H, table.R, table.C, first, count,
+                                          _ptr(table.crop), _stream()))
+    else:
+        _need_bounds(bounds)
+        _lib.check(_lib_.mf_warp_maps_bounds_f32(_ptr(table.buf), _ptr(out), table.n, table.W, table.H, table.R, table.C, first, count,
+                                                 _ptr(table.crop), _ptr(bounds), _stream()))
+    return out
+
+
+def maps_to_grid(maps, align_corners=True):
+    """`warp_maps`' pixel coordinates (..., H, W, 2) as the normalised grid `torch.nn.functional.grid_sample` takes: 2 u / (W - 1) - 1 (and
+    the same in y with H) for align_corners=True -- pass the same flag to grid_sample --, (2 u + 1) / W - 1 otherwise.  Pixels no cell owns,
+    at (W + 1, H + 1), land outside [-1, 1]: padding_mode='zeros' leaves them empty.  Pure torch, on whatever device `maps` lives; float32 in,
+    float32 out.  A convenience and NOT bit-exact: the maps are the reference's own arrays, this division and grid_sample's arithmetic are
+    torch's."""
+    if not isinstance(maps, torch.Tensor) or not maps.is_floating_point() or maps.dim() < 3 or maps.shape[-1] != 2:
+        raise ValueError('maps must be a floating-point tensor of shape (..., H, W, 2)')
+    H, W = maps.shape[-3], maps.shape[-2]
+    if align_corners:
+        if W < 2 or H < 2:
+            raise ValueError('align_corners=True needs W, H >= 2')
+        scale = torch.tensor([2.0 / (W - 1), 2.0 / (H - 1)], dtype=maps.dtype, device=maps.device)
+        return maps * scale - 1.0
+    size = torch.tensor([float(W), float(H)], dtype=maps.dtype, device=maps.device)
+    return (2.0 * maps + 1.0) / size - 1.0
+
+
 def crop_reduce(crop, W, H):
     """Clip-level bounds (mfs.py:1103-1106): int32 tensor {left, top, right, bottom}."""
     _need(crop, torch.int32, 'crop')

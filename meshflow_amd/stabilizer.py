@@ -94,7 +94,8 @@ class DegenerateMeshError(ValueError):
     after the `stabilize_resident` call that issued it; `cells`: how many cells.  A ValueError, as before."""
 
     def __init__(self, cells, clip_serial):
-        super().__init__(f'{cells} degenerate mesh cell(s) in resident clip #{clip_serial}: no homography exists '
+        where = f' in resident clip #{clip_serial}' if clip_serial is not None else ''       # (None: `stabilization_maps`, no resident clip)
+        super().__init__(f'{cells} degenerate mesh cell(s){where}: no homography exists '
                          '(cv2.findHomography would return None); its frames are undefined')
         self.cells, self.clip_serial = cells, clip_serial
 
@@ -832,6 +833,28 @@ class MeshFlowStabilizer:
         finally:
             self._resident_verdict(st, check, cropped=True)
         return frames, bounds, d_stab, cropped
+
+    def stabilization_maps(self, d_disp, homographies, frame_width, frame_height,
+                           adaptive_weights_definition=ADAPTIVE_WEIGHTS_DEFINITION_ORIGINAL, first=0, count=None, out=None):
+        """The stabilisation's float32 coordinate maps without any frame: the Jacobi sweep (mfs.py:695-704) on d_disp -- (F, R+1, C+1, 2)
+        float64 unstabilized vertex displacements in HBM --, the cell table + plan of all F frames, then `ops.warp_maps` for the frames
+        first .. first + count - 1 (count=None: up to the last; `out`: a (count, H, W, 2) float32 tensor to fill).  Everything on torch's
+        current stream.  Returns (maps, bounds): maps[f, y, x] = the source position (u, v) `stabilize_resident` samples for output pixel
+        (x, y) of frame first + f, (W + 1, H + 1) where no cell owns the pixel; bounds = int32[4] device tensor {left, top, right, bottom},
+        the crop rectangle of the frames of the range (mfs.py:1075-1106).  A degenerate mesh raises `DegenerateMeshError` (clip_serial None)
+        here, synchronously, before the maps are written."""
+        import torch
+        from . import ops
+        self._check_definition(adaptive_weights_definition)
+        self._check_mesh_shape(d_disp, d_disp.shape[0])
+        W, H = int(frame_width), int(frame_height)
+        d_stab = self._stabilized_vertex_displacements_device(d_disp, W, H, adaptive_weights_definition, homographies)
+        bounds = torch.empty(4, dtype=torch.int32, device=d_disp.device)
+        table = ops.cell_table(d_disp, d_stab, W, H, self.mesh_row_count, self.mesh_col_count, bounds=bounds)
+        bad = int(table.status.item())
+        if bad:
+            raise DegenerateMeshError(bad, None)
+        return ops.warp_maps(table, first=first, count=count, out=out, bounds=bounds), bounds
 
     def _stabilized_frames_device(self, d_frames, d_unstab, d_stab, out=None, table=None):
         """d_frames: (n, H, W, 3) uint8; d_unstab/d_stab: (n, R+1, C+1, 2) float64, all in HBM.
