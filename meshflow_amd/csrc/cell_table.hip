@@ -540,7 +540,6 @@ __device__ __forceinline__ void plan_one_footprint(EdgeOf edge_of, HiOf hi_of, M
         // lie completely inside it
         const uint32_t bs = min((3u * (uint32_t)cx_lo) & ~3u, 3u * (uint32_t)W - (uint32_t)MF_STAGE_PITCH);
         const int last_col = (int)((bs + (uint32_t)MF_STAGE_PITCH - 3u) / 3u);
-#ifndef MF_NO_BORDER
         // BORDER window (mf_common.h): one candidate, certified denominator, whole footprint, not a deep one.  The taps of covered
         // pixels reach at most ONE pixel outside the frame (tx / ty ranges above: L >= 0, Rt <= W-1); what they reach there is painted
         // into the window by the kernel, which needs the bytes in front of / behind the window rows to be free.
@@ -561,7 +560,6 @@ __device__ __forceinline__ void plan_one_footprint(EdgeOf edge_of, HiOf hi_of, M
                 return;
             }
         }
-#endif
         const int sy0 = min(cy_lo, H - MF_STAGE_ROWS - 1);
         if (cx_hi <= last_col && cy_hi <= sy0 + MF_STAGE_ROWS - 1)
         {
@@ -573,7 +571,7 @@ __device__ __forceinline__ void plan_one_footprint(EdgeOf edge_of, HiOf hi_of, M
             bool certified = false;                  // one of the warp kernel's three certified shapes: hot, pair, multi
             region.flags_origin = MF_REGION_STAGED | (deep ? MF_REGION_DEEP : 0u) | (noflag ? MF_REGION_NOFLAG : 0u) | ((uint32_t)sy0 * MF_STAGE_PITCH + bs);
             region.src_dwords = ((uint32_t)sy0 * (3u * (uint32_t)W) + bs) >> 2;
-            // The premises of the warp kernel's cheap coordinate chain (warp.hip, cheap_quotients) for EVERY listed cell on this footprint:
+            // The premises of the warp kernel's cheap coordinate chain (warp_body.h, cheap_quotients) for EVERY listed cell on this footprint:
             // no cancellation in the numerators -- the sum of the magnitudes of a numerator's terms (largest at the far corner: x, y >= 0)
             // at most 8 x the numerator, which is u w >= umin wlo for every listed cell -- denominator terms bounded, denominator above
             // 0.52.  One test for the three paths that use it (hot, pair, multi).
@@ -583,7 +581,7 @@ __device__ __forceinline__ void plan_one_footprint(EdgeOf edge_of, HiOf hi_of, M
             if (deep && p.e[1] == (uint16_t)MF_PLAN_UNIT && (p.e[0] & (MF_PLAN_VALID | MF_PLAN_IN)) == (MF_PLAN_VALID | MF_PLAN_IN)) {
                 // FAST64: no cancellation in the numerators (sum of the terms' magnitudes at most 8 x the value, everywhere on
                 // the footprint: the former grows with x and y, the latter is smallest at a corner), denominator terms bounded --
-                // the premises of the warp kernel's error bound for its cheap coordinate chain (warp.hip, cell_coords_fast)
+                // the premises of the warp kernel's error bound for its cheap coordinate chain (warp_body.h, cell_coords_fast)
                 const bool fast64 = cheap_all;
                 p.e[1] = (uint16_t)(MF_PLAN_UNIT | MF_PLAN_HOT | (fast64 ? MF_PLAN_FAST64 : 0u));
                 certified = true;
@@ -604,10 +602,9 @@ __device__ __forceinline__ void plan_one_footprint(EdgeOf edge_of, HiOf hi_of, M
                 p.e[4] = (uint16_t)(p.e[4] | MF_PLAN_HOT | (fast ? MF_PLAN_MULTI_FAST : 0u) | ((uint32_t)(cnt - 1) << MF_PLAN_COUNT_SHIFT));
                 certified = true;
             }
-#ifndef MF_NO_COMPACT            // (A/B switch shared with warp.hip: both sides must agree on the window layout)
             // COMPACT window for the three certified shapes (hot, pair, multi -- all whole and interior): 9 rows x 112 bytes hold every tap of
             // every pixel whichever listed cell owns it (ix / iy ranges above: the corner values of EVERY listed cell) -> one global->LDS
-            // load instead of two, and the conflict-free lane -> row mapping of warp.hip.  (The mesh warp is continuous across cell edges --
+            // load instead of two, and the conflict-free lane -> row mapping of warp_body.h.  (The mesh warp is continuous across cell edges --
             // neighbouring cells share their vertices -- so a footprint on an edge needs no larger window than one inside a cell.)
             const uint32_t cbs = (3u * (uint32_t)ix_lo) & ~3u;
             if (certified && iy_hi - iy_lo + 1 <= MF_COMPACT_ROWS && 3u * (uint32_t)ix_hi + 3u <= cbs + MF_COMPACT_PITCH &&
@@ -617,7 +614,6 @@ __device__ __forceinline__ void plan_one_footprint(EdgeOf edge_of, HiOf hi_of, M
                 region.flags_origin = MF_REGION_STAGED | (deep ? MF_REGION_DEEP : 0u) | MF_REGION_NOFLAG | MF_REGION_COMPACT | ((uint32_t)iy_lo * MF_COMPACT_PITCH + cbs);
                 region.src_dwords = ((uint32_t)iy_lo * (3u * (uint32_t)W) + cbs) >> 2;
             }
-#endif
         }
     }
 }

@@ -59,7 +59,7 @@ __host__ __device__ inline int reach_parts(int R, int C) { return (R * C + 63) /
 // (bit 13: clear in every valid entry -- cell indices take bits 0-11 -- and in the raw row / column numbers of an overflow list, so
 // the kernel tests this one bit without looking at the rest of the list)
 #define MF_PLAN_HOT 0x2000u
-// ... and MF_PLAN_FAST64 (only with HOT) the premises of the warp kernel's cheap float64 coordinate chain (warp.hip,
+// ... and MF_PLAN_FAST64 (only with HOT) the premises of the warp kernel's cheap float64 coordinate chain (warp_body.h,
 // cell_coords_fast): at every pixel of the footprint |h0| x + |h1| y + |h2| <= 8 (h0 x + h1 y + h2), the same for the second row,
 // and |h6| x + |h7| y + |h8| <= 2.5.
 #define MF_PLAN_FAST64 0x0002u
@@ -109,7 +109,7 @@ struct alignas(8) FootRegion { uint32_t flags_origin, src_dwords; };
 // to check coverage): every tap of every pixel, whichever listed cell owns it, lies in MF_COMPACT_ROWS rows of MF_COMPACT_PITCH bytes
 // starting at the dword that holds column sx0 of row sy0 -- 63 chunks of 16 bytes, ONE global->LDS load per wavefront; origin and
 // src_dwords then refer to that layout (origin = MF_COMPACT_PITCH sy0 + bs).  The warp kernel maps lanes to footprint rows differently
-// on such a window (rows 0, 2, 4, 6 in lanes 0-31: no LDS bank conflicts at this pitch, warp.hip).
+// on such a window (rows 0, 2, 4, 6 in lanes 0-31: no LDS bank conflicts at this pitch, warp_body.h).
 #define MF_REGION_COMPACT 0x20000000u
 #define MF_COMPACT_PITCH 112
 // bit 28 = NOFLAG (with or without STAGED): no pixel of the footprint can pass one of the four crop-boundary tests of mfs.py:1075-1098
@@ -254,7 +254,7 @@ struct WarpGeom {
     uint32_t frame_bytes, row_bytes;             // 3 W H, 3 W
     uint32_t rec_frame_bytes, edge_frame_bytes;  // R C records / edge sets of one frame
     uint32_t cell_mul_x, cell_mul_y, mesh_cols, cell_last;   // the cell under a pixel of the UNWARPED grid: (mulhi(x, cell_mul_x), mulhi(y, cell_mul_y));
-                                                 // row length C; R C - 1 (the speculative matrix load of the hot path, warp.hip)
+                                                 // row length C; R C - 1 (the speculative matrix load of the hot path, warp_body.h)
 };
 
 // Launchers (defined next to their kernels).

@@ -1,9 +1,8 @@
 // Kernel 2b for single-channel uint8 frames (mf_warp_u8c1, mf_warp_clip_u8c1, the u8c1 host pipeline): footprint_body's GREY instantiation.
 // It lives in a translation unit of its own so that warp.hip's code object -- and with it every existing kernel, instruction for instruction
-// (tools/isa_compare.py) -- stays what it is: this file takes footprint_body and its helpers from warp.hip (MF_WARP_BODY_ONLY) and adds the
-// grey kernel and its range launch.  Design and measurements: DESIGN.md section 4.8.
-#define MF_WARP_BODY_ONLY 1
-#include "warp.hip"
+// (tools/isa_compare.py) -- stays what it is: this file takes footprint_body and its helpers from warp_body.h and adds the grey kernel and its
+// range launch.  Design and measurements: DESIGN.md section 4.8.
+#include "warp_body.h"
 
 namespace mf {
 

@@ -1,9 +1,8 @@
 // Kernel 2b for 4-channel uint8 frames (mf_warp_u8c4, mf_warp_clip_u8c4): footprint_body's U8C4 instantiation.  Like warp_c1.hip, a translation
 // unit of its own, so that warp.hip's code object -- and with it every existing kernel, instruction for instruction (tools/isa_compare.py) --
-// stays what it is: this file takes footprint_body and its helpers from warp.hip (MF_WARP_BODY_ONLY) and adds the 4-channel kernel and its range
-// launch.  Design and measurements: profiles/u8c4_design.md.
-#define MF_WARP_BODY_ONLY 1
-#include "warp.hip"
+// stays what it is: this file takes footprint_body and its helpers from warp_body.h and adds the 4-channel kernel and its range launch.
+// Design and measurements: profiles/u8c4_design.md.
+#include "warp_body.h"
 
 namespace mf {
 

@@ -2,10 +2,8 @@
 // coordinates (u, v) of every output pixel -- the reference's frame_stabilized_x_y, mfs.py:1054-1061, the arrays it hands to cv2.remap at
 // mfs.py:1063-1069 -- instead of sampling a frame with them.  Like warp_c1.hip and warp_c4.hip, a translation unit of its own, so that warp.hip's
 // code object -- and with it every existing kernel, instruction for instruction (tools/isa_compare.py) -- stays what it is: this file takes
-// footprint_body and its helpers from warp.hip (MF_WARP_BODY_ONLY) and adds the maps kernel and its range launch.  Design and measurements:
-// profiles/warp_maps.md.
-#define MF_WARP_BODY_ONLY 1
-#include "warp.hip"
+// footprint_body and its helpers from warp_body.h and adds the maps kernel and its range launch.  Design and measurements: profiles/warp_maps.md.
+#include "warp_body.h"
 
 namespace mf {
 

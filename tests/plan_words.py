@@ -9,8 +9,8 @@ REGION_STAGED = 0x80000000
 REGION_COMPACT = 0x20000000
 REGION_BORDER = 0x08000000
 REGION_ORIGIN_MASK = 0x007FFFFF
-GREY_PITCH = 80                 # the grey warp re-cuts a staged window only for frames of at least this many columns (warp.hip)
-C4_COLS = 56                    # the 4-channel warp's re-cut window: this many columns, frames of at least as many (warp.hip, MF_C4_COLS)
+GREY_PITCH = 80                 # the grey warp re-cuts a staged window only for frames of at least this many columns (warp_body.h)
+C4_COLS = 56                    # the 4-channel warp's re-cut window: this many columns, frames of at least as many (warp_body.h, MF_C4_COLS)
 STAGE_PITCH, COMPACT_PITCH = 160, 112       # the plan's staged windows: bytes per row, wide and COMPACT (mf_common.h)
 
 
@@ -62,7 +62,7 @@ def grey_paths(table, aligned=True):
 
 
 def c4_window_columns(region, src_dwords, W):
-    """First column of the 4-byte window (warp.hip's C4_STAGE block) of each region, decoded as footprint_body does: origin = the low 23
+    """First column of the 4-byte window (warp_body.h's C4_STAGE block) of each region, decoded as footprint_body does: origin = the low 23
     bits, sy0 = (4 src_dwords - origin) / (3 W - P) + 1/2 in float32 (P = 160, or 112 for COMPACT), bs = origin - P sy0, and the column
     gx = bs / 3 before the clamp to W - C4_COLS.  Meaningful only for STAGED regions."""
     region = np.asarray(region, dtype=np.uint32)

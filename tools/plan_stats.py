@@ -56,7 +56,7 @@ print(f'hot with the fast64 certificate {fast64.mean():.4f}')
 pf = (ne == 2) & ((plan[:, 2] & 0x6001) == 0x2001)
 pv_ = (ne == 2) & ((plan[:, 2] & 0x6003) == 0x2003)
 print(f'pair path with the fast certificate {pf.mean():.4f} (of which transposed lanes {pv_.mean():.4f})')
-# the warp kernel's own dispatch (warp.hip footprint_body, in its order)
+# the warp kernel's own dispatch (warp_body.h footprint_body, in its order)
 k_hot = (plan[:, 1] & 0x2000) != 0
 k_border = ~k_hot & ((regions & 0x08000000) != 0)          # one candidate, several, or none at all (MF_REGION_BORDER)
 k_pair = ~k_hot & ~k_border & ((plan[:, 2] & 0x2000) != 0) & ~overflow
