@@ -286,41 +286,34 @@ int launch_crop_resize(Px px, const void* frames, void* out, int n, int W, int H
 // resize_tables_kernel's tables (u8c3, u8c1) for the rectangle in `work` (W x-entries, then H y-entries; x: ofs = sx, w = 16 a0 | 16 a1 << 16
 // (pre-scaled, see resize_kernel);  y: ofs = sy0 | sy1 << 16, w = b0 | b1 << 16)
 struct ResizeTab { int32_t ofs; uint32_t w; };
-// resize16_tables_kernel's (resize16.hip): x: ofs = sx (clamped into the crop), f = its fraction (0 where clamped);  y: ofs = sy0 | sy1 << 16
+// resize16_tables_kernel's (resize16_body.h): x: ofs = sx (clamped into the crop), f = its fraction (0 where clamped);  y: ofs = sy0 | sy1 << 16
 // (clipped rows), f = the fraction
 struct Resize16Tab { int32_t ofs; float f; };
 static_assert(sizeof(Resize16Tab) == 8, "the 8-bit call's workspace holds the tables");
-// The kernel launches of the other formats, behind launch_crop_resize's checks: resize16.hip (its own tables in the same workspace),
-// resize_c1.hip (resize.hip's tables, already built)
-int launch_resize16(const uint16_t* frames, uint16_t* out, int W, int H, int left, int top, int right, int bottom, const TileOrder& order,
-                    void* work, hipStream_t st);
-int launch_resize8c1(const uint8_t* frames, uint8_t* out, int n, int W, int H, int left, int top, int cw, const void* work,
-                     const TileOrder& order, hipStream_t st);
-// resize_c4.hip: the u8c4 kernels on resize.hip's tables (already built) for an oW x oH output (oW x oH == W x H: the same-size call; `up`: oW >=
-// cw and oH >= ch), and their tile rows
-int launch_resize8c4(const uint8_t* frames, uint8_t* out, int n, int W, int H, int left, int top, int cw, int oW, int oH, bool up,
-                     const void* work, const TileOrder& order, hipStream_t st);
-int resize8c4_tile_rows(bool up);
 // resize.hip: every check of a crop-resize call to an oW x oH output, then the format's tables and kernel (oW x oH == W x H: launch_crop_resize)
 int launch_crop_resize_to(Px px, const void* frames, void* out, int n, int W, int H, int left, int top, int right, int bottom, int oW, int oH,
                           void* work, hipStream_t st);
-// ... and what it launches: the tables (resize.hip for u8c3 / u8c1, resize16.hip for u16c3), then the kernels of resize_to.hip (`up`: oW >= cw
-// and oH >= ch, which instantiation; resize_to_tile_rows output rows per tile)
-int launch_resize16_to(const uint16_t* frames, uint16_t* out, int W, int H, int left, int top, int right, int bottom, int oW, int oH,
-                       const TileOrder& order, void* work, hipStream_t st);
-int resize_to_tile_rows(Px px, bool up);
-int launch_resize8_to(Px px, const uint8_t* frames, uint8_t* out, int n, int W, int H, int left, int top, int cw, int oW, int oH, bool up,
-                      const void* work, const TileOrder& order, hipStream_t st);
+// What those two launch behind their checks (the host units of the kernel headers; `up`: oW >= cw and oH >= ch, which instantiation):
+// resize16.hip: resize16_body.h's tables of the cw x ch crop for oW x oH in the same workspace, then resize16_kernel (oW x oH == W x H) or,
+// through resize_to.hip's launch_resize16_to_kernel, resize16_to_kernel
+int launch_resize16(const uint16_t* frames, uint16_t* out, int W, int H, int left, int top, int cw, int ch, int oW, int oH,
+                    const TileOrder& order, void* work, hipStream_t st);
 int launch_resize16_to_kernel(const uint16_t* frames, uint16_t* out, int W, int H, int left, int top, int cw, int oW, int oH, bool area,
                               const Resize16Tab* xtab, const Resize16Tab* ytab, const TileOrder& order, hipStream_t st);
+// resize_c1.hip: resize8c1_kernel on resize.hip's tables (already built in `work`)
+int launch_resize8c1(const uint8_t* frames, uint8_t* out, int n, int W, int H, int left, int top, int cw, const void* work,
+                     const TileOrder& order, hipStream_t st);
+// resize_c4.hip: the u8c4 kernels on resize.hip's tables for an oW x oH output (oW x oH == W x H: the same-size call), and their tile rows
+int launch_resize8c4(const uint8_t* frames, uint8_t* out, int n, int W, int H, int left, int top, int cw, int oW, int oH, bool up,
+                     const void* work, const TileOrder& order, hipStream_t st);
+int resize8c4_tile_rows(bool up);
+// resize_to.hip: the u8c3 / u8c1 kernels to a chosen size on resize.hip's tables for (oW, oH), and every format's output rows per tile
+int launch_resize8_to(Px px, const uint8_t* frames, uint8_t* out, int n, int W, int H, int left, int top, int cw, int oW, int oH, bool up,
+                      const void* work, const TileOrder& order, hipStream_t st);
+int resize_to_tile_rows(Px px, bool up);
 // resize_dev.hip: mf_crop_resize_dev_*: the host-side checks, then the tables and the kernels that read the rectangle from d_bounds
-// (resize_dev_c1.hip / resize_dev_c4.hip: the launches of the kernels that live there)
 int launch_crop_resize_dev(Px px, const void* frames, void* out, int n, int W, int H, const int32_t* d_bounds, int oW, int oH, void* work,
                            int32_t* d_status, hipStream_t st);
-int launch_resize8c1_dev(const uint8_t* frames, uint8_t* out, int n, int W, int H, const int32_t* d_bounds, const ResizeTab* xtab,
-                         const ResizeTab* ytab, const TileOrder& order, hipStream_t st);
-int launch_resize8c4_dev(const uint8_t* frames, uint8_t* out, int n, int W, int H, const int32_t* d_bounds, int oW, int oH, bool up,
-                         const ResizeTab* xtab, const ResizeTab* ytab, const TileOrder& order, hipStream_t st);
 size_t vertex_motion_workspace_bytes(int total_features, int max_per_pair, int P, int R, int C);
 int launch_vertex_motion(const double* early, const double* late, const int32_t* offsets, const double* hom, int P,
                          int total_features, int max_per_pair, int W, int H, int R, int C, int ell_rows, int ell_cols,

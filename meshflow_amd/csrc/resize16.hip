@@ -1,116 +1,24 @@
-// Crop + bilinear resize of uint16 frames: _crop_frames (meshflowstabilizer.py:1111-1157, cv2.resize at :1150-1155) for CV_16UC3.
-//
-// cv2.resize INTER_LINEAR of 16-bit data (imgproc/resize.cpp: resizeGeneric_ with HResizeLinear<ushort, float, float, 1, ...> and
-// VResizeLinear<ushort, float, float, Cast<float, ushort>, ...>) is the float path: the index and fraction tables are the 8-bit ones
-// (resize.hip), but the coefficients stay float32 (1 - f, f) -- no x2048, no rounding --, and
-//   horizontal  t  = float(S[sx]) a0 + float(S[sx+1]) a1                  (float32, unfused)
-//   vertical    out = saturate_cast<ushort>(t0 b0 + t1 b1)                (float32, unfused, rounded half to even)
-// The one-tap branch of the horizontal pass (columns whose sx is the crop's last) gives S[sx] * 1 = S[sx] + S[sx+1] * 0: the same value.
-// resize16_tables_kernel builds the tables on the device in the float / double operations of resize_tables_kernel, in the workspace
-// mf_crop_resize_workspace_bytes(W, H) already sizes (8 bytes per column and per row); resize16_kernel: one thread per output pixel, a
-// workgroup per 256 pixels of an output row, taps straight from the frame (two 12-byte loads per pixel where sx + 1 is inside the crop).
-#include "mf_common.h"
-#include "resize_rect.h"
+// The uint16 launches of mf_crop_resize_u16c3 / mf_crop_resize_to_u16c3 behind resize.hip's checks: resize16_body.h's tables kernel, then
+// resize16_kernel (here) or resize16_to_kernel (resize_to.hip).
+#include "resize16_body.h"
 
 namespace mf {
 
-__global__ __launch_bounds__(256) void resize16_tables_kernel(MF_TABLES_ARGS,
-                                                              Resize16Tab* __restrict__ xtab, Resize16Tab* __restrict__ ytab)
+// launch_crop_resize's and launch_crop_resize_to's launches for uint16 frames (every check done there): the tables of the cw x ch crop scaled
+// to oW x oH (oW x-entries, then oH y-entries) in `work`, then the same-size kernel (oW x oH == W x H) or the one to a chosen size
+int launch_resize16(const uint16_t* frames, uint16_t* out, int W, int H, int left, int top, int cw, int ch, int oW, int oH,
+                    const TileOrder& order, void* work, hipStream_t st)
 {
-    MF_TABLES_LOAD(W, H)
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < W) {
-        float fx = (float)(((double)i + 0.5) * scale_x - 0.5);
-        int sx = (int)floorf(fx);
-        fx -= (float)sx;
-        if (sx < 0) { fx = 0.0f; sx = 0; }
-        if (sx >= cw - 1) { fx = 0.0f; sx = cw - 1; }
-        xtab[i].ofs = sx;
-        xtab[i].f = fx;
-    }
-    if (i < H) {
-        float fy = (float)(((double)i + 0.5) * scale_y - 0.5);
-        const int sy = (int)floorf(fy);
-        fy -= (float)sy;
-        const int sy0 = min(max(sy, 0), ch - 1), sy1 = min(max(sy + 1, 0), ch - 1);
-        ytab[i].ofs = sy0 | (sy1 << 16);
-        ytab[i].f = fy;
-    }
-}
-
-__global__ __launch_bounds__(256) void resize16_kernel(const uint16_t* __restrict__ frames, uint16_t* __restrict__ out, int W, int H,
-                                                       MF_RECT_ARGS, const Resize16Tab* __restrict__ xtab,
-                                                       const Resize16Tab* __restrict__ ytab, TileOrder order)
-{
-    MF_RECT_LOAD(W, H)
-    int f, y, tx;
-    if (!order.decode(blockIdx.x, f, y, tx)) return;
-    const int x = tx * 256 + (int)threadIdx.x;
-    if (x >= W) return;
-    const uint64_t frame_samples = 3ull * (uint64_t)((uint32_t)W * (uint32_t)H);
-    const uint16_t* __restrict__ src = frames + (uint64_t)f * frame_samples;
-    const Resize16Tab xt = xtab[x], yt = ytab[y];
-    const float a1 = xt.f, a0 = 1.0f - xt.f, b1 = yt.f, b0 = 1.0f - yt.f;
-    const uint32_t sx = (uint32_t)(left + xt.ofs);
-    const uint16_t* __restrict__ p0 = src + 3ull * (uint64_t)((uint32_t)(top + (yt.ofs & 0xFFFF)) * (uint32_t)W + sx);
-    const uint16_t* __restrict__ p1 = src + 3ull * (uint64_t)((uint32_t)(top + (yt.ofs >> 16)) * (uint32_t)W + sx);
-    float s0[6], s1[6];                                          // B G R of columns sx and sx + 1, rows sy0 and sy1
-    if (xt.ofs + 1 < cw) {
-        uint32_t a[3], b[3];
-        __builtin_memcpy(a, p0, 12);
-        __builtin_memcpy(b, p1, 12);
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            s0[2 * k] = (float)(a[k] & 0xFFFFu); s0[2 * k + 1] = (float)(a[k] >> 16);
-            s1[2 * k] = (float)(b[k] & 0xFFFFu); s1[2 * k + 1] = (float)(b[k] >> 16);
-        }
-    } else {                                                     // the crop's last column: a1 = 0, nothing to its right is read
-#pragma unroll
-        for (int c = 0; c < 3; ++c) { s0[c] = s0[3 + c] = (float)p0[c]; s1[c] = s1[3 + c] = (float)p1[c]; }
-    }
-    uint16_t* __restrict__ d = out + (uint64_t)f * frame_samples + 3ull * (uint64_t)((uint32_t)y * (uint32_t)W + (uint32_t)x);
-    uint32_t o[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const float t0 = s0[c] * a0 + s0[3 + c] * a1, t1 = s1[c] * a0 + s1[3 + c] * a1;
-        o[c] = min((uint32_t)rintf(t0 * b0 + t1 * b1), 65535u);
-    }
-    d[0] = (uint16_t)o[0];
-    d[1] = (uint16_t)o[1];
-    d[2] = (uint16_t)o[2];
-}
-
-#ifndef MF_RESIZE_DEV          // (resize_dev.hip includes this file for the two kernels alone)
-// launch_crop_resize's launches for uint16 frames (shape, rectangle and tile count already checked there)
-int launch_resize16(const uint16_t* frames, uint16_t* out, int W, int H, int left, int top, int right, int bottom, const TileOrder& order,
-                    void* work, hipStream_t st)
-{
-    const int cw = right - left + 1, ch = bottom - top + 1;
-    const double scale_x = 1.0 / ((double)W / (double)cw), scale_y = 1.0 / ((double)H / (double)ch);
-    Resize16Tab* xtab = (Resize16Tab*)work;
-    Resize16Tab* ytab = xtab + W;
-    const int m = W > H ? W : H;
-    hipLaunchKernelGGL(resize16_tables_kernel, dim3((m + 255) / 256), dim3(256), 0, st, cw, ch, W, H, scale_x, scale_y, xtab, ytab);
-    int rc = hip_fail(hipGetLastError(), "resize16_tables_kernel launch");
-    if (rc != MF_OK) return rc;
-    hipLaunchKernelGGL(resize16_kernel, dim3(order.per_xcd * 8u), dim3(256), 0, st, frames, out, W, H, left, top, cw, xtab, ytab, order);
-    return hip_fail(hipGetLastError(), "resize16_kernel launch");
-}
-
-// launch_crop_resize_to's launches for uint16 frames (shape, output size, rectangle and tile count already checked there)
-int launch_resize16_to(const uint16_t* frames, uint16_t* out, int W, int H, int left, int top, int right, int bottom, int oW, int oH,
-                       const TileOrder& order, void* work, hipStream_t st)
-{
-    const int cw = right - left + 1, ch = bottom - top + 1;
     const double scale_x = 1.0 / ((double)oW / (double)cw), scale_y = 1.0 / ((double)oH / (double)ch);
     Resize16Tab* xtab = (Resize16Tab*)work;
     Resize16Tab* ytab = xtab + oW;
     const int m = oW > oH ? oW : oH;
     hipLaunchKernelGGL(resize16_tables_kernel, dim3((m + 255) / 256), dim3(256), 0, st, cw, ch, oW, oH, scale_x, scale_y, xtab, ytab);
-    int rc = hip_fail(hipGetLastError(), "resize16_tables_kernel launch");
-    if (rc != MF_OK) return rc;
-    return launch_resize16_to_kernel(frames, out, W, H, left, top, cw, oW, oH, 2 * oW == cw && 2 * oH == ch, xtab, ytab, order, st);
+    if (const int rc = hip_fail(hipGetLastError(), "resize16_tables_kernel launch")) return rc;
+    if (oW != W || oH != H)
+        return launch_resize16_to_kernel(frames, out, W, H, left, top, cw, oW, oH, 2 * oW == cw && 2 * oH == ch, xtab, ytab, order, st);
+    hipLaunchKernelGGL(resize16_kernel, dim3(order.per_xcd * 8u), dim3(256), 0, st, frames, out, W, H, left, top, cw, xtab, ytab, order);
+    return hip_fail(hipGetLastError(), "resize16_kernel launch");
 }
-#endif  // MF_RESIZE_DEV
 
 }  // namespace mf

@@ -1,8 +1,8 @@
 // _crop_frames (mfs.py:1111-1157) from a rectangle that stays on the device: mf_crop_resize_dev_u8c3 / _u16c3 / _u8c1 / _u8c4.  The rectangle
 // {left, top, right, bottom} is the 16 bytes a warp's clip-level reduction left in device memory; the host never reads it, so these calls
-// never wait for the warp.  The kernels are the bodies of resize.hip, resize16.hip and resize_to.hip (here) and of resize_c1.hip / resize_c4.hip
-// (resize_dev_c1.hip, resize_dev_c4.hip) compiled a second time under MF_RESIZE_DEV (resize_rect.h): the rectangle is loaded instead of
-// passed, everything else is the same code, and the code objects of those five files stay what they are (tools/isa_compare.py).
+// never wait for the warp.  The kernels are the five kernel headers' (resize_body.h, resize16_body.h, resize_to_body.h, resize_c1_body.h,
+// resize_c4_body.h) compiled a second time, under MF_RESIZE_DEV (resize_rect.h) and other names: the rectangle is loaded instead of passed,
+// everything else is the same code.
 //
 // What the host still decides, from (W, H, oW, oH) alone:
 //   oW >= W and oH >= H (the same-size call included): the crop lies inside the frame, so this is an upscale whatever the rectangle -- the
@@ -19,31 +19,26 @@
 #define resize_to_kernel resize_to_dev_kernel
 #define resize8c1_to_kernel resize8c1_to_dev_kernel
 #define resize16_to_kernel resize16_to_dev_kernel
-#include "resize.hip"
-#include "resize16.hip"
-#include "resize_to.hip"
+#define resize8c1_kernel resize8c1_dev_kernel
+#define resize8c4_kernel resize_bgra_dev_kernel
+#include "resize_body.h"
+#include "resize16_body.h"
+#include "resize_to_body.h"
+#include "resize_c1_body.h"
+#include "resize_c4_body.h"
+#include "resize_checks.h"
 
 namespace mf {
 
 int launch_crop_resize_dev(Px px, const void* frames, void* out, int n, int W, int H, const int32_t* d_bounds, int oW, int oH, void* work,
                            int32_t* d_status, hipStream_t st)
 {
+    const char* const call = "mf_crop_resize_dev_";
     const char* name = px_name(px);
-    if (n <= 0 || W < 1 || H < 1 || W > 32767 || H > 32767) {
-        set_error("mf_crop_resize_dev_%s: unsupported shape n=%d W=%d H=%d", name, n, W, H);
-        return MF_ERR_INVALID_ARG;
-    }
-    if (oW < 1 || oH < 1 || oW > 32767 || oH > 32767) {
-        set_error("mf_crop_resize_dev_%s: unsupported output size %dx%d (1 .. 32,767 each)", name, oW, oH);
-        return MF_ERR_INVALID_ARG;
-    }
+    if (!resize_shape_ok(call, name, n, W, H) || !resize_out_size_ok(call, name, oW, oH)) return MF_ERR_INVALID_ARG;
     const bool up = oW >= W && oH >= H, same = oW == W && oH == H;
     TileOrder order;
-    const int tile_rows = resize_to_tile_rows(px, up);
-    if (!make_tile_order((oW + 255) / 256, (oH + tile_rows - 1) / tile_rows, n, order)) {
-        set_error("mf_crop_resize_dev_%s: too many tiles", name);
-        return MF_ERR_INVALID_ARG;
-    }
+    if (!resize_tiles_ok(call, name, oW, oH, resize_to_tile_rows(px, up), n, order)) return MF_ERR_INVALID_ARG;
     if (px == Px::U8C3)
         if (const int rc = check_d16_zero_fill(st)) return rc;
     const dim3 tab_grid(((oW > oH ? oW : oH) + 255) / 256), grid(order.per_xcd * 8u), block(64 * kWaves);
@@ -65,10 +60,20 @@ int launch_crop_resize_dev(Px px, const void* frames, void* out, int n, int W, i
     if (const int rc = hip_fail(hipGetLastError(), "resize_tables_dev_kernel launch")) return rc;
     const uint8_t* src = (const uint8_t*)frames;
     uint8_t* dst = (uint8_t*)out;
-    if (px == Px::U8C4) return launch_resize8c4_dev(src, dst, n, W, H, d_bounds, oW, oH, up, xtab, ytab, order, st);
+    if (px == Px::U8C4) {
+        if (up)
+            hipLaunchKernelGGL((resize8c4_kernel<kUpRows, kUpSlots, kUpPitch, false>), grid, block, 0, st, src, dst, n, W, H, d_bounds, oW, oH, xtab,
+                               ytab, order);
+        else
+            hipLaunchKernelGGL((resize8c4_kernel<kDown4Rows, 2 * kDown4Rows, kDown4Pitch, true>), grid, block, 0, st, src, dst, n, W, H, d_bounds,
+                               oW, oH, xtab, ytab, order);
+        return hip_fail(hipGetLastError(), "resize_bgra_dev_kernel launch");
+    }
     if (px == Px::U8C1) {
-        if (same)
-            return launch_resize8c1_dev(src, dst, n, W, H, d_bounds, xtab, ytab, order, st);
+        if (same) {
+            hipLaunchKernelGGL(resize8c1_kernel, grid, block, 0, st, src, dst, n, W, H, d_bounds, xtab, ytab, order);
+            return hip_fail(hipGetLastError(), "resize8c1_dev_kernel launch");
+        }
         if (up)
             hipLaunchKernelGGL((resize8c1_to_kernel<kRows, kSrcRows, kC1RowPitch, false>), grid, block, 0, st, src, dst, n, W, H, d_bounds, oW, oH,
                                xtab, ytab, order);

@@ -1,16 +1,16 @@
-// Where a crop-resize kernel gets its rectangle from.  The kernels of resize.hip, resize16.hip, resize_c1.hip, resize_c4.hip and resize_to.hip
-// take `left, top, cw` as launch arguments (MF_RECT_ARGS) -- the host knows the rectangle.  The translation units of the device-rectangle
-// calls (mf_crop_resize_dev_*: resize_dev.hip, resize_dev_c1.hip, resize_dev_c4.hip) define MF_RESIZE_DEV, rename the kernels and include those
-// files for the kernels alone: MF_RECT_ARGS is then a pointer to {left, top, right, bottom} in device memory and MF_RECT_LOAD, the first
-// statement of every body, reads it (four uniform dwords: one scalar 16-byte load per wavefront) and RETURNS if the rectangle cannot be
-// used, before the kernel has read a frame byte or written an output byte.  Without MF_RESIZE_DEV both macros leave the kernels exactly
-// what they were (tools/isa_compare.py).
+// Where a crop-resize kernel gets its rectangle from.  The kernel headers (resize_body.h, resize16_body.h, resize_c1_body.h, resize_c4_body.h,
+// resize_to_body.h) are written against these macros.  Included from resize.hip, resize16.hip, resize_c1.hip, resize_c4.hip and resize_to.hip,
+// their kernels take `left, top, cw` as launch arguments (MF_RECT_ARGS) -- the host knows the rectangle.  The translation unit of the
+// device-rectangle calls (mf_crop_resize_dev_*: resize_dev.hip) defines MF_RESIZE_DEV, renames the kernels and includes the same headers:
+// MF_RECT_ARGS is then a pointer to {left, top, right, bottom} in device memory and MF_RECT_LOAD, the first statement of every body, reads
+// it (four uniform dwords: one scalar 16-byte load per wavefront) and RETURNS if the rectangle cannot be used, before the kernel has read a
+// frame byte or written an output byte.  Without MF_RESIZE_DEV both macros leave the kernels exactly what they were (tools/isa_compare.py).
 #pragma once
 #include "mf_common.h"
 
 #ifdef MF_RESIZE_DEV
 namespace mf {
-// the device twin of launch_crop_resize's refusal: an empty rectangle or one that leaves the W x H frame
+// the device twin of resize_rect_ok (resize_checks.h): an empty rectangle or one that leaves the W x H frame
 __device__ __forceinline__ bool rect_usable(int left, int top, int right, int bottom, int W, int H)
 {
     return left >= 0 && top >= 0 && right < W && bottom < H && right >= left && bottom >= top;

@@ -1,4 +1,5 @@
-// The 8-bit BGR resize's device helpers (resize_kernel's, resize.hip), shared with the kernels to a caller-chosen output size (resize_to.hip).
+// The device helpers and tile constants every 8-bit crop-resize kernel shares (resize_body.h, resize_c1_body.h, resize_c4_body.h,
+// resize_to_body.h), each defined here once; the BGR row passes (hpass_row, vpass_store) are resize_kernel's and resize_to_kernel's.
 #pragma once
 #include "mf_common.h"
 
@@ -27,30 +28,28 @@ __device__ __forceinline__ uint32_t udot2(uint32_t a, uint32_t b, uint32_t c)
     return __builtin_amdgcn_udot2(__builtin_bit_cast(ushort2_t, a), __builtin_bit_cast(ushort2_t, b), c, false);
 }
 
-constexpr int kRowPitch = 800;        // bytes of one staged source row in LDS: 50 chunks of 16 bytes (256 output px + slack)
+// Tiles: a workgroup is kWaves wavefronts that never cooperate; a wavefront owns kRows consecutive output rows x 256 pixels, a lane 4
+// consecutive pixels per row.  _crop_frames only ever scales UP (the crop lies inside the frame), so consecutive output rows advance by at
+// most one source row and the kRows output rows read at most kSrcRows source rows.
+constexpr int kRows = 8;              // output rows per wavefront
+constexpr int kWaves = 4;             // wavefronts per workgroup
+constexpr int kSrcRows = kRows + 1;   // source rows a wavefront stages
+constexpr int kRowPitch = 800;        // u8c3: bytes of one staged source row in LDS, 50 chunks of 16 bytes (256 output px + slack)
+constexpr int kC1RowPitch = 272;      // u8c1: 17 chunks, 258 bytes + up to 3 of misalignment in front
 
-// Workgroup = 8 output rows x 256 pixels; wavefront = kRows consecutive rows; lane = 4 consecutive pixels per row (one
-// 12-byte store each).
-// The two source rows of an output row are shared by all its pixels: the wavefront copies the span it needs of both
-// (<= 800 bytes each, from the dword holding the first tap) into LDS with two global->LDS 16-byte loads per lane and
-// takes the taps from there (three dword reads per pixel and row + v_alignbyte for the 3-byte-pixel misalignment).
-// That replaces eight unaligned 8-byte loads per lane, whose instruction count -- not bytes -- bounded the first version.
 // High 32 bits of the product of two 24-bit values (v_mul_hi_u32_u24).
 __device__ __forceinline__ uint32_t mulhi_u24(uint32_t a, uint32_t b)
 {
     return (uint32_t)(((unsigned long long)(a & 0xFFFFFFu) * (unsigned long long)(b & 0xFFFFFFu)) >> 32);
 }
 
-constexpr int kRows = 8;              // output rows per wavefront
-constexpr int kWaves = 4;             // wavefronts per workgroup (they never cooperate)
-constexpr int kSrcRows = kRows + 1;   // source rows a wavefront stages: _crop_frames only ever scales UP (the crop lies inside the frame), so
-                                      // consecutive output rows advance by at most one source row
-
-// The horizontal pass of ONE staged source row for the lane's four pixels: t = S[sx] a0 + S[sx+1] a1 per channel (v_dot2_u32_u16 with
-// the weights pre-scaled by 16: T = 16 t < 2^24), returned as T & ~255 = 256 (t >> 4), what the vertical pass multiplies.  The taps
-// are byte loads with immediate offsets: ds_read_u8 puts S[sx] into the low byte of one register, ds_read_u8_d16_hi S[sx+1] into
-// bits 16-23 of another (with SRAM ECC a d16 load zeroes the other half of its destination: check_d16_zero_fill), one v_or_b32 joins
-// them.  All 24 loads and their wait sit in ONE asm block: nothing can be scheduled between issue and wait.
+// The horizontal pass of ONE staged source row for the lane's four pixels.  The wavefront has copied the span of the row it needs into LDS
+// (from the dword holding its first tap, 16-byte global->LDS chunks); at[j] is the LDS byte address of pixel j's first tap there.
+// t = S[sx] a0 + S[sx+1] a1 per channel (v_dot2_u32_u16 with the weights pre-scaled by 16: T = 16 t < 2^24), returned as
+// T & ~255 = 256 (t >> 4), what the vertical pass multiplies.  The taps are byte loads with immediate offsets: ds_read_u8 puts S[sx] into
+// the low byte of one register, ds_read_u8_d16_hi S[sx+1] into bits 16-23 of another (with SRAM ECC a d16 load zeroes the other half of its
+// destination: check_d16_zero_fill), one v_or_b32 joins them.  All 24 loads and their wait sit in ONE asm block: nothing can be scheduled
+// between issue and wait.
 __device__ __forceinline__ void hpass_row(const uint32_t (&at)[4], const uint32_t (&w)[4], uint32_t (&T)[4][3])
 {
     uint32_t lo[4][3], hi[4][3];

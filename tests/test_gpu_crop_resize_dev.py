@@ -258,6 +258,15 @@ def test_host_side_refusals_launch_nothing(dev, fmt):
     for args in bad:
         assert call(*args, stream()) == _lib.MF_ERR_INVALID_ARG, args
         assert f'mf_crop_resize_dev_{fmt}' in _lib.lib.mf_last_error().decode(), _lib.lib.mf_last_error()
+    # the whole text of one refusal of each kind (the strings the library has always given)
+    texts = [
+        ((F, O, n, W, 32768, B, 25, 15, Wk, S), f'mf_crop_resize_dev_{fmt}: unsupported shape n=2 W=40 H=32768'),
+        ((F, O, n, W, H, B, 25, -1, Wk, S), f'mf_crop_resize_dev_{fmt}: unsupported output size 25x-1 (1 .. 32,767 each)'),
+        ((F, O, 1 << 20, W, H, B, 32767, 32767, Wk, S), f'mf_crop_resize_dev_{fmt}: too many tiles'),
+    ]
+    for args, text in texts:
+        assert call(*args, stream()) == _lib.MF_ERR_INVALID_ARG, args
+        assert _lib.lib.mf_last_error().decode() == text
     # ops: `out` of the wrong shape, a host tensor, a wrong dtype or a wrong length as bounds, a bad size, a bad status
     good_out = torch.empty_like(frames)
     for kw in (dict(bounds=bounds, out=good_out, size=(25, 15)), dict(bounds=bounds, out=torch.empty_like(frames)[:1]),

@@ -169,6 +169,22 @@ def test_refusals_leave_the_output_untouched(dev, fmt):
         rc = call(*args, st)
         assert rc == _lib.MF_ERR_INVALID_ARG, args
         assert f'mf_crop_resize_to_{fmt}' in _lib.lib.mf_last_error().decode(), _lib.lib.mf_last_error()
+    # the whole text of one refusal of each kind, of this call and of the same-size call (the strings the library has always given)
+    same = getattr(_lib.lib, f'mf_crop_resize_{fmt}')
+    texts = [
+        (call, (F, O, 0, W, H, 2, 3, 30, 20, 25, 15, Wk), f'mf_crop_resize_to_{fmt}: unsupported shape n=0 W=40 H=30'),
+        (call, (F, O, n, W, H, 2, 3, 30, 20, 32768, 15, Wk), f'mf_crop_resize_to_{fmt}: unsupported output size 32768x15 (1 .. 32,767 each)'),
+        (call, (F, O, n, W, H, 20, 3, 10, 20, 25, 15, Wk), f'mf_crop_resize_to_{fmt}: empty or out-of-frame crop rectangle (20, 3, 10, 20) for '
+                                                           '40x30 (cv2.resize would fail on an empty source)'),
+        (call, (F, O, 1 << 20, W, H, 2, 3, 30, 20, 32767, 32767, Wk), f'mf_crop_resize_to_{fmt}: too many tiles'),
+        (same, (F, O, n, 0, H, 0, 0, 0, 0, Wk), f'mf_crop_resize_{fmt}: unsupported shape n=2 W=0 H=30'),
+        (same, (F, O, n, W, H, 2, 3, W, 20, Wk), f'mf_crop_resize_{fmt}: empty or out-of-frame crop rectangle (2, 3, 40, 20) for 40x30 '
+                                                 '(cv2.resize would fail on an empty source)'),
+        (same, (F, O, 1 << 20, 32767, 32767, 2, 3, 30, 20, Wk), f'mf_crop_resize_{fmt}: too many tiles'),
+    ]
+    for fn, args, text in texts:
+        assert fn(*args, st) == _lib.MF_ERR_INVALID_ARG, args
+        assert _lib.lib.mf_last_error().decode() == text
     torch.cuda.synchronize()
     assert bool((out == 0xA5).all())
 
@@ -187,8 +203,8 @@ def test_ops_size_checks(dev):
 # ---- seeded random sweep ----------------------------------------------------------------------------------------------------------
 
 # scale_x = crop width / output width at which each format's down instantiation leaves its staged form for the direct one: the widest span
-# 256 output pixels can take, px (ceil(255 scale_x) + 3) bytes (+ slack), must fit its LDS row -- u8c3: kDownPitch 2048 (resize_to.hip,
-# slack 15), u8c1: kDown1Pitch 1024 (slack 3), u8c4: kDownPitch 2432 (resize_c4.hip).  As the largest ceil(255 scale_x) that still fits.
+# 256 output pixels can take, px (ceil(255 scale_x) + 3) bytes (+ slack), must fit its LDS row -- u8c3: kDownPitch 2048 (resize_to_body.h,
+# slack 15), u8c1: kDown1Pitch 1024 (slack 3), u8c4: kDown4Pitch 2432 (resize_c4_body.h).  As the largest ceil(255 scale_x) that still fits.
 # uint16 has one kernel (no staging): its draws sit at u8c3's.
 CUT_CEIL = {'u8c3': 674, 'u8c1': 1018, 'u8c4': 605, 'u16c3': 674}
 SWEEP_OFFSETS = {'u8c3': ((None, None), (1, 3), (2, 1), (3, 2)), 'u8c1': ((None, None), (1, 3), (2, 1), (3, 2)),

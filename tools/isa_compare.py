@@ -3,12 +3,27 @@
 
     python tools/isa_compare.py base/libmeshflow_hip.so meshflow_amd/libmeshflow_hip.so
 
+A listing is compared up to and including its last s_endpgm.  What the assembler puts after it to fill the text section out (s_nop 0,
+s_code_end, objdump's '...' for a run of zeros) depends on which kernel comes last in its code object, not on the kernel, and is dropped;
+anything else after the last s_endpgm still counts.
+
 Exit status 0 when every kernel of the first library is unchanged."""
 import os
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import codeobj  # noqa: E402
+
+
+PADDING = ('s_nop 0', 's_code_end', '...')
+
+
+def strip_padding(lines):
+    """The listing without its end-of-text padding: cut after the last s_endpgm if every line behind it is padding, unchanged otherwise."""
+    last = max((i for i, l in enumerate(lines) if l == 's_endpgm'), default=None)
+    if last is None or any(l not in PADDING for l in lines[last + 1:]):
+        return lines
+    return lines[:last + 1]
 
 
 def listings(so_path):
@@ -18,7 +33,7 @@ def listings(so_path):
         dis = codeobj.disassemble(co)
         for name, md in codeobj.kernel_metadata(co).items():
             sym = md['symbol'][:-3] if md['symbol'].endswith('.kd') else md['symbol']
-            out[name] = dis.get(sym, [])
+            out[name] = strip_padding(dis.get(sym, []))
     return out
 
 
