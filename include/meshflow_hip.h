@@ -215,6 +215,46 @@ int mf_warp_maps_f32(const void* d_table, float* d_maps, int n, int W, int H, in
 int mf_warp_maps_bounds_f32(const void* d_table, float* d_maps, int n, int W, int H, int R, int C, int first, int count, int32_t* d_crop,
                             int32_t* d_bounds, void* stream);
 
+/* ---- side planes: what travels with a video without being a picture -- depth, disparity, flow components, confidence (float32), labels and
+ * masks (any element of 1, 2, 4 or 8 bytes) -- warped with the arrays the reference hands to cv2.remap at mfs.py:1063-1069 and cropped like
+ * _crop_frames (mfs.py:1111-1157), so that a plane moves exactly as its colour frame does.  Planes are [n][H][W], contiguous.
+ * mf_warp_plane_f32: cv2.remap(plane, map_x, map_y, INTER_LINEAR, BORDER_CONSTANT, borderValue = fill) on CV_32FC1 with the maps of
+ * mf_warp_maps_f32: sx = cvRound(32 u), ix = sat_short(sx >> 5), fx = sx & 31 (the 8-bit path's quantisation), BilinearTab_f's exact float32
+ * weights, t = ((S00 w0 + S01 w1) + S10 w2) + S11 w3 with every product and sum rounded on its own, out = t -- mf_warp_u16c3 on one channel
+ * without saturate_cast.  A 2 x 2 footprint wholly outside the plane gives fill exactly, otherwise each outside tap is fill inside the sum;
+ * a pixel no cell owns samples (W + 1, H + 1) and comes out as fill.  Non-finite samples get no special case.
+ * mf_warp_plane_nearest: cv2.remap(..., INTER_NEAREST, BORDER_CONSTANT) on elements of elem_bytes = 1, 2, 4 or 8 bytes: ix =
+ * sat_short(cvRound(u)), iy = sat_short(cvRound(v)), float32 coordinates rounded half to even; the element is copied as bits where
+ * 0 <= ix < W and 0 <= iy < H, otherwise the result is the low elem_bytes bytes of fill_bits.
+ * Both fold the four edge scans (mfs.py:1075-1098) into d_crop and the clip rectangle exactly as mf_warp_u8c3 does -- a caller that warps
+ * planes only gets the rectangle a frames caller gets; d_bounds (may be NULL): the rectangle in the caller's int32[4] as mf_warp_bounds_u8c3,
+ * else in the table's own words.  All offsets are 64-bit.  Nothing outside the planes' bytes is read.  Refused with MF_ERR_INVALID_ARG before
+ * anything is launched: null pointers, d_planes == d_out, n <= 0, W or H outside 2 .. 32,767, R or C outside 1 .. 64, an elem_bytes other
+ * than 1, 2, 4, 8, a d_planes or d_out that is not aligned to its element. */
+int mf_warp_plane_f32(const float* d_planes, float* d_out, const void* d_table, int n, int W, int H, int R, int C, float fill,
+                      int32_t* d_crop, int32_t* d_bounds, void* stream);
+int mf_warp_plane_nearest(const void* d_planes, void* d_out, const void* d_table, int n, int W, int H, int R, int C, int elem_bytes,
+                          uint64_t fill_bits, int32_t* d_crop, int32_t* d_bounds, void* stream);
+/* _crop_frames (mfs.py:1111-1157, cv2.resize at :1150-1155) for such planes: the inclusive rectangle scaled to out_W x out_H (the reference's
+ * own call: out_W, out_H = W, H); d_out holds n * out_H * out_W elements.
+ * mf_crop_resize_plane_f32: cv2.resize INTER_LINEAR on CV_32FC1 -- the index and fraction tables of mf_crop_resize_u8c3, float32 coefficients
+ * (1 - f, f), t = S[sx] a0 + S[sx+1] a1, out = t0 b0 + t1 b1, float32, unfused: mf_crop_resize_to_u16c3 without saturate_cast; a crop exactly
+ * twice the output in both axes takes INTER_AREA's fast path, (((S00 + S01) + S10) + S11) * 0.25f.
+ * mf_crop_resize_plane_nearest: cv2.resize INTER_NEAREST on elements of elem_bytes = 1, 2, 4 or 8 bytes: sx = min(floor(x * (1.0 / (out_W /
+ * crop_w))), crop_w - 1) in float64, the same for y, the element copied as bits.
+ * d_work: mf_crop_resize_workspace_bytes(out_W, out_H) bytes (the tables).  mf_crop_resize_dev_plane_*: the rectangle read by the kernels from
+ * d_bounds when they execute, d_status as in mf_crop_resize_dev_u8c3 -- an unusable rectangle adds 1 to *d_status and nothing is read or written.
+ * Refused with MF_ERR_INVALID_ARG before anything is launched: null pointers, d_planes == d_out, n <= 0, W, H, out_W or out_H outside
+ * 1 .. 32,767, too many tiles, a bad elem_bytes, misaligned planes, and (host rectangle) an empty or out-of-plane rectangle. */
+int mf_crop_resize_plane_f32(const float* d_planes, float* d_out, int n, int W, int H, int left, int top, int right, int bottom, int out_W,
+                             int out_H, void* d_work, void* stream);
+int mf_crop_resize_plane_nearest(const void* d_planes, void* d_out, int n, int W, int H, int left, int top, int right, int bottom, int out_W,
+                                 int out_H, int elem_bytes, void* d_work, void* stream);
+int mf_crop_resize_dev_plane_f32(const float* d_planes, float* d_out, int n, int W, int H, const int32_t* d_bounds, int out_W, int out_H,
+                                 void* d_work, int32_t* d_status, void* stream);
+int mf_crop_resize_dev_plane_nearest(const void* d_planes, void* d_out, int n, int W, int H, const int32_t* d_bounds, int out_W, int out_H,
+                                     int elem_bytes, void* d_work, int32_t* d_status, void* stream);
+
 /* Clip-level crop bounds (mfs.py:1103-1106): {max left, max top, min right, min bottom} over n frames.
  * d_bounds: [4] int32. */
 int mf_crop_reduce(const int32_t* d_crop, int n, int W, int H, int32_t* d_bounds, void* stream);

@@ -2,6 +2,7 @@
 // host-buffer convenience wrappers.  Declarations and reference citations: include/meshflow_hip.h.
 #include <stdarg.h>
 #include <stdio.h>
+#include <string.h>
 
 #include "mf_common.h"
 
@@ -53,6 +54,47 @@ static int warp_maps_entry(const char* name, const void* d_table, float* d_maps,
     if (has_bounds) tv.bounds = d_bounds;
     return launch_warp(Px::MAPS, nullptr, d_maps, table_slice(tv, first, W, H, R, C), count, W, H, R, C, 0, d_crop + 4 * (size_t)first,
                        (hipStream_t)stream);
+}
+
+// The element checks every plane entry shares: elem_bytes is 0 (the float32 calls) or 1, 2, 4, 8, and both pointers are aligned to the element
+static bool plane_elem_ok(const char* name, int elem_bytes, const void* d_planes, const void* d_out)
+{
+    if (elem_bytes != 0 && elem_bytes != 1 && elem_bytes != 2 && elem_bytes != 4 && elem_bytes != 8) {
+        set_error("%s: elem_bytes=%d (1, 2, 4 or 8)", name, elem_bytes);
+        return false;
+    }
+    const uintptr_t mask = (uintptr_t)(elem_bytes ? elem_bytes : 4) - 1u;
+    if ((((uintptr_t)d_planes | (uintptr_t)d_out) & mask) != 0) {
+        set_error("%s: d_planes and d_out must be aligned to their %d-byte elements", name, (int)mask + 1);
+        return false;
+    }
+    return true;
+}
+
+// The checks of the two plane warps, then launch_warp's Px::PLANE_* launches.  elem_bytes == 0: mf_warp_plane_f32 (fill: the float's bits).
+// d_bounds may be null: the clip-level rectangle then goes to the table's own four words, as in mf_warp_u8c3.
+static int warp_plane_entry(const char* name, int elem_bytes, const void* d_planes, void* d_out, const void* d_table, int n, int W, int H, int R,
+                            int C, uint64_t fill, int32_t* d_crop, int32_t* d_bounds, void* stream)
+{
+    if (!d_planes || !d_out || !d_table || !d_crop) { set_error("%s: null pointer", name); return MF_ERR_INVALID_ARG; }
+    if (d_planes == d_out) { set_error("%s: d_planes and d_out alias", name); return MF_ERR_INVALID_ARG; }
+    if (n <= 0 || R <= 0 || C <= 0) { set_error("%s: bad sizes", name); return MF_ERR_INVALID_ARG; }
+    if (!plane_elem_ok(name, elem_bytes, d_planes, d_out)) return MF_ERR_INVALID_ARG;
+    const Px px = elem_bytes == 0 ? Px::PLANE_F32 : elem_bytes == 1 ? Px::PLANE_N1 : elem_bytes == 2 ? Px::PLANE_N2 :
+                  elem_bytes == 4 ? Px::PLANE_N4 : Px::PLANE_N8;
+    TableView tv = table_view(const_cast<void*>(d_table), n, W, H, R, C);
+    if (d_bounds) tv.bounds = d_bounds;
+    return launch_warp(px, d_planes, d_out, tv, n, W, H, R, C, fill, d_crop, (hipStream_t)stream);
+}
+
+// The checks the four plane crop-resize entries share ahead of their launchers' (elem_bytes == 0: the float32 calls)
+static int crop_resize_plane_checks(const char* name, int elem_bytes, const void* d_planes, const void* d_out, const void* d_work, bool dev,
+                                    const void* d_bounds, const void* d_status)
+{
+    if (!d_planes || !d_out || !d_work || (dev && (!d_bounds || !d_status))) { set_error("%s: null pointer", name); return MF_ERR_INVALID_ARG; }
+    if (d_planes == d_out) { set_error("%s: d_planes and d_out alias", name); return MF_ERR_INVALID_ARG; }
+    if (!plane_elem_ok(name, elem_bytes, d_planes, d_out)) return MF_ERR_INVALID_ARG;
+    return MF_OK;
 }
 
 static int crop_resize_entry(const char* name, Px px, const void* d_frames, void* d_out, int n, int W, int H, int left, int top, int right,
@@ -202,6 +244,21 @@ int mf_warp_maps_bounds_f32(const void* d_table, float* d_maps, int n, int W, in
     return warp_maps_entry("mf_warp_maps_bounds_f32", d_table, d_maps, n, W, H, R, C, first, count, d_crop, true, d_bounds, stream);
 }
 
+int mf_warp_plane_f32(const float* d_planes, float* d_out, const void* d_table, int n, int W, int H, int R, int C, float fill,
+                      int32_t* d_crop, int32_t* d_bounds, void* stream)
+{
+    uint32_t bits;
+    memcpy(&bits, &fill, sizeof bits);
+    return warp_plane_entry("mf_warp_plane_f32", 0, d_planes, d_out, d_table, n, W, H, R, C, bits, d_crop, d_bounds, stream);
+}
+
+int mf_warp_plane_nearest(const void* d_planes, void* d_out, const void* d_table, int n, int W, int H, int R, int C, int elem_bytes,
+                          uint64_t fill_bits, int32_t* d_crop, int32_t* d_bounds, void* stream)
+{
+    if (elem_bytes == 0) elem_bytes = -1;           // (0 is warp_plane_entry's word for the float32 call)
+    return warp_plane_entry("mf_warp_plane_nearest", elem_bytes, d_planes, d_out, d_table, n, W, H, R, C, fill_bits, d_crop, d_bounds, stream);
+}
+
 // ---- the same three calls with the clip-level rectangle in the CALLER's d_bounds[4] instead of inside the table blob ----
 
 int mf_cell_table_bounds_f64(const double* d_unstab, const double* d_stab, int n, int W, int H, int R, int C,
@@ -332,6 +389,37 @@ int mf_crop_resize_dev_u8c4(const uint8_t* d_frames, uint8_t* d_out, int n, int 
                             void* d_work, int32_t* d_status, void* stream)
 {
     return crop_resize_dev_entry("mf_crop_resize_dev_u8c4", Px::U8C4, d_frames, d_out, n, W, H, d_bounds, out_W, out_H, d_work, d_status, stream);
+}
+
+int mf_crop_resize_plane_f32(const float* d_planes, float* d_out, int n, int W, int H, int left, int top, int right, int bottom, int out_W,
+                             int out_H, void* d_work, void* stream)
+{
+    if (const int rc = crop_resize_plane_checks("mf_crop_resize_plane_f32", 0, d_planes, d_out, d_work, false, nullptr, nullptr)) return rc;
+    return launch_crop_resize_plane(0, d_planes, d_out, n, W, H, left, top, right, bottom, out_W, out_H, d_work, (hipStream_t)stream);
+}
+
+int mf_crop_resize_plane_nearest(const void* d_planes, void* d_out, int n, int W, int H, int left, int top, int right, int bottom, int out_W,
+                                 int out_H, int elem_bytes, void* d_work, void* stream)
+{
+    if (elem_bytes == 0) elem_bytes = -1;
+    if (const int rc = crop_resize_plane_checks("mf_crop_resize_plane_nearest", elem_bytes, d_planes, d_out, d_work, false, nullptr, nullptr)) return rc;
+    return launch_crop_resize_plane(elem_bytes, d_planes, d_out, n, W, H, left, top, right, bottom, out_W, out_H, d_work, (hipStream_t)stream);
+}
+
+int mf_crop_resize_dev_plane_f32(const float* d_planes, float* d_out, int n, int W, int H, const int32_t* d_bounds, int out_W, int out_H,
+                                 void* d_work, int32_t* d_status, void* stream)
+{
+    if (const int rc = crop_resize_plane_checks("mf_crop_resize_dev_plane_f32", 0, d_planes, d_out, d_work, true, d_bounds, d_status)) return rc;
+    return launch_crop_resize_plane_dev(0, d_planes, d_out, n, W, H, d_bounds, out_W, out_H, d_work, d_status, (hipStream_t)stream);
+}
+
+int mf_crop_resize_dev_plane_nearest(const void* d_planes, void* d_out, int n, int W, int H, const int32_t* d_bounds, int out_W, int out_H,
+                                     int elem_bytes, void* d_work, int32_t* d_status, void* stream)
+{
+    if (elem_bytes == 0) elem_bytes = -1;
+    if (const int rc = crop_resize_plane_checks("mf_crop_resize_dev_plane_nearest", elem_bytes, d_planes, d_out, d_work, true, d_bounds, d_status))
+        return rc;
+    return launch_crop_resize_plane_dev(elem_bytes, d_planes, d_out, n, W, H, d_bounds, out_W, out_H, d_work, d_status, (hipStream_t)stream);
 }
 
 size_t mf_vertex_motion_workspace_bytes(int total_features, int max_per_pair, int P, int R, int C)

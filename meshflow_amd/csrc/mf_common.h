@@ -226,13 +226,21 @@ inline bool make_tile_order(int tiles_x, int tiles_y, int n, TileOrder& o)
 // one parameter; a new format is a row here plus its kernels.
 // Px::MAPS is no frame format: the warp that reads no frame and writes the float32 coordinate maps (u, v) themselves, [H][W][2] per
 // frame (mf_warp_maps_f32, warp_maps.hip) -- "2 channels of 4 bytes" as far as launch_warp's frame stride goes.
-enum class Px { U8C3, U16C3, U8C1, U8C4, MAPS };
-constexpr int px_channels(Px p) { return p == Px::U8C1 ? 1 : p == Px::U8C4 ? 4 : p == Px::MAPS ? 2 : 3; }
-constexpr int px_sample_bytes(Px p) { return p == Px::U16C3 ? 2 : p == Px::MAPS ? 4 : 1; }
+// Px::PLANE_*: no picture either -- the side planes [n][H][W] that travel with a video (mf_warp_plane_f32, mf_warp_plane_nearest,
+// warp_planes.hip): float32 sampled like cv2.remap INTER_LINEAR of CV_32FC1, or elements of 1, 2, 4 or 8 bytes copied as bits like
+// INTER_NEAREST.  One channel of px_sample_bytes bytes; the pixel calls (launch_crop_resize*, the clip and host pipelines) never see them.
+enum class Px { U8C3, U16C3, U8C1, U8C4, MAPS, PLANE_F32, PLANE_N1, PLANE_N2, PLANE_N4, PLANE_N8 };
+constexpr bool px_is_plane(Px p) { return p == Px::PLANE_F32 || p == Px::PLANE_N1 || p == Px::PLANE_N2 || p == Px::PLANE_N4 || p == Px::PLANE_N8; }
+constexpr int px_channels(Px p) { return p == Px::U8C1 || px_is_plane(p) ? 1 : p == Px::U8C4 ? 4 : p == Px::MAPS ? 2 : 3; }
+constexpr int px_sample_bytes(Px p)
+{
+    return p == Px::U16C3 || p == Px::PLANE_N2 ? 2 : p == Px::MAPS || p == Px::PLANE_F32 || p == Px::PLANE_N4 ? 4 : p == Px::PLANE_N8 ? 8 : 1;
+}
 constexpr int px_bytes(Px p) { return px_channels(p) * px_sample_bytes(p); }
 constexpr const char* px_name(Px p)
 {
-    return p == Px::U8C3 ? "u8c3" : p == Px::U16C3 ? "u16c3" : p == Px::U8C1 ? "u8c1" : p == Px::U8C4 ? "u8c4" : "maps_f32";
+    return p == Px::U8C3 ? "u8c3" : p == Px::U16C3 ? "u16c3" : p == Px::U8C1 ? "u8c1" : p == Px::U8C4 ? "u8c4" : p == Px::MAPS ? "maps_f32" :
+           p == Px::PLANE_F32 ? "plane_f32" : "plane_nearest";
 }
 // The border colour as the warp kernels take it, from the caller's px_channels(p) samples: B | G << 8 | R << 16 (u8c3),
 // B | G << 16 | R << 32 (u16c3), the byte (u8c1), B | G << 8 | R << 16 | A << 24 (u8c4).
@@ -275,6 +283,7 @@ struct WarpRange {
 void launch_warp8c1_range(const WarpGeom& g, const WarpRange& r, int W, int H, int C, uint32_t border, bool stage, hipStream_t st);  // warp_c1.hip
 void launch_warp8c4_range(const WarpGeom& g, const WarpRange& r, int W, int H, int C, uint32_t border, bool stage, hipStream_t st);  // warp_c4.hip
 void launch_maps_range(const WarpGeom& g, const WarpRange& r, int W, int H, int C, hipStream_t st);  // warp_maps.hip (r.frames unused, r.out: float32 maps)
+void launch_plane_range(Px px, const WarpGeom& g, const WarpRange& r, int W, int H, int C, uint64_t fill, hipStream_t st);  // warp_planes.hip (fill: the element's bits)
 int launch_crop_scan(const TableView& tv, int n, int W, int H, int R, int C, int32_t* crop, hipStream_t st);
 int check_d16_zero_fill(hipStream_t st);          // warp.hip: one-time device check the byte-tap kernels rely on
 int launch_selftest_recip(unsigned long long n, unsigned long long seed, unsigned long long* d_mismatches, hipStream_t st);
@@ -314,6 +323,12 @@ int resize_to_tile_rows(Px px, bool up);
 // resize_dev.hip: mf_crop_resize_dev_*: the host-side checks, then the tables and the kernels that read the rectangle from d_bounds
 int launch_crop_resize_dev(Px px, const void* frames, void* out, int n, int W, int H, const int32_t* d_bounds, int oW, int oH, void* work,
                            int32_t* d_status, hipStream_t st);
+// resize_planes.hip / resize_planes_dev.hip: mf_crop_resize_plane_* and mf_crop_resize_dev_plane_* -- every check of the call, the tables,
+// the kernel.  elem_bytes == 0: the float32 linear call; 1, 2, 4, 8: the nearest one on elements of that size.
+int launch_crop_resize_plane(int elem_bytes, const void* planes, void* out, int n, int W, int H, int left, int top, int right, int bottom,
+                             int oW, int oH, void* work, hipStream_t st);
+int launch_crop_resize_plane_dev(int elem_bytes, const void* planes, void* out, int n, int W, int H, const int32_t* d_bounds, int oW, int oH,
+                                 void* work, int32_t* d_status, hipStream_t st);
 size_t vertex_motion_workspace_bytes(int total_features, int max_per_pair, int P, int R, int C);
 int launch_vertex_motion(const double* early, const double* late, const int32_t* offsets, const double* hom, int P,
                          int total_features, int max_per_pair, int W, int H, int R, int C, int ell_rows, int ell_cols,

@@ -981,6 +981,189 @@ __device__ __forceinline__ void maps_store_f32(const float (&u)[4], const float 
     }
 }
 
+// ---- side planes [n][H][W]: what travels with a video without being a picture (depth, flow, labels, masks) ---------------------------
+// Crop bounds of a tail that scans every pixel itself: wave reduction, then at most one atomic per bound and wavefront (per frame,
+// mfs.py:1075-1098, and the clip-level rectangle, mfs.py:1103-1106) -- remap_store_u16's fold.
+__device__ __forceinline__ void plane_crop_fold(int c_left, int c_top, int c_right, int c_bottom, uint32_t f, int W, int H,
+                                                int32_t* __restrict__ crop, int32_t* __restrict__ clip)
+{
+    const bool any = c_left != 0 || c_top != 0 || c_right != W - 1 || c_bottom != H - 1;
+    if (__ballot(any) == 0) return;
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        c_left = max(c_left, __shfl_xor(c_left, off));
+        c_top = max(c_top, __shfl_xor(c_top, off));
+        c_right = min(c_right, __shfl_xor(c_right, off));
+        c_bottom = min(c_bottom, __shfl_xor(c_bottom, off));
+    }
+    if (threadIdx.x == 0) {
+        if (c_left != 0) { atomicMax(&crop[4 * f + 0], c_left); atomicMax(&clip[0], c_left); }
+        if (c_top != 0) { atomicMax(&crop[4 * f + 1], c_top); atomicMax(&clip[1], c_top); }
+        if (c_right != W - 1) { atomicMin(&crop[4 * f + 2], c_right); atomicMin(&clip[2], c_right); }
+        if (c_bottom != H - 1) { atomicMin(&crop[4 * f + 3], c_bottom); atomicMin(&clip[3], c_bottom); }
+    }
+}
+
+// Footprint-level tail of the PLANE_F32 instantiation of footprint_body: cv2.remap INTER_LINEAR / BORDER_CONSTANT of CV_32FC1
+// (remapBilinear<Cast<float, float>, RemapNoVec, float>) -- remap_store_u16 on one float32 channel without saturate_cast: the 8-bit map
+// quantisation, BilinearTab_f's exact weights, t = ((S00 w0 + S01 w1) + S10 w2) + S11 w3 with every product and sum rounded on its own,
+// out = t.  Deep-interior footprints take each pixel's two tap rows as one 8-byte load apiece (4-byte aligned); the others take every tap at
+// its position clamped into the plane and replace outside taps by `fill`, and a 2 x 2 footprint wholly outside gives `fill` itself.  Nothing
+// outside the plane's bytes is read.  The lane's four results are 16 contiguous bytes: one 16-byte store where that address is 16-byte
+// aligned, else 4 bytes per pixel, and per pixel too in the lane that overhangs the right edge (maps_store_f32's rule).  All offsets are
+// 64-bit.
+__device__ __forceinline__ void remap_store_plane_f32(const float (&u)[4], const float (&v)[4], uint32_t f, int x0, int y, bool active, int W, int H,
+                                                      const float* __restrict__ planes, float* __restrict__ out, float fill,
+                                                      int32_t* __restrict__ crop, int32_t* __restrict__ clip)
+{
+    const uint64_t plane_elems = (uint64_t)((uint32_t)W * (uint32_t)H);
+    const float* __restrict__ src = planes + (uint64_t)f * plane_elems;
+    uint32_t bx[4], by[4];
+    fixed_point(u, v, bx, by);
+    uint32_t dxm = 0, dym = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        dxm = max(dxm, bx[j] - (0x4B400000u + 64u));
+        dym = max(dym, by[j] - (0x4B400000u + 64u));
+    }
+    // deep interior (as in footprint_body): 2 <= ix <= W-3 and 2 <= iy <= H-3 for all four pixels
+    const bool deep = W >= 5 && H >= 5 && dxm <= (uint32_t)(32 * (W - 3) + 31 - 64) && dym <= (uint32_t)(32 * (H - 3) + 31 - 64);
+    const bool fast = __ballot(active && !deep) == 0;
+    float o[4] = { fill, fill, fill, fill };
+    int c_left = 0, c_top = 0, c_right = W - 1, c_bottom = H - 1;
+    if (active) {
+        if (fast) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const uint32_t ix = __builtin_amdgcn_ubfe(bx[j], 5, 17), iy = __builtin_amdgcn_ubfe(by[j], 5, 17);
+                const float* __restrict__ p0 = src + (uint64_t)(iy * (uint32_t)W + ix);
+                float a[2], b[2];                                       // S00 S01 of row iy, S10 S11 of row iy + 1
+                __builtin_memcpy(a, p0, 8);
+                __builtin_memcpy(b, p0 + (uint32_t)W, 8);
+                const float ax = (float)(bx[j] & 31u) * 0.03125f, ay = (float)(by[j] & 31u) * 0.03125f;
+                const float ax0 = 1.0f - ax, ay0 = 1.0f - ay;
+                o[j] = ((a[0] * (ay0 * ax0) + a[1] * (ay0 * ax)) + b[0] * (ay * ax0)) + b[1] * (ay * ax);
+            }
+        } else {
+            // plane borders, uncovered pixels (at (W+1, H+1)), crop flags, out-of-range coordinates
+            const float fWm1 = (float)(W - 1), fHm1 = (float)(H - 1);
+            uint32_t spread = 0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                spread = max(spread, max(bx[j] - (0x4B400000u - 0x200000u), by[j] - (0x4B400000u - 0x200000u)));
+            const bool narrow = __ballot(spread >= 0x400000u) == 0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float uu = u[j], vv = v[j];
+                const int x = x0 + j;
+                if (x < W) {                                            // crop-boundary scan, mfs.py:1075-1098 (exact: Sterbenz)
+                    if (fabsf(uu) < 1.0f) c_left = max(c_left, x);
+                    if (fabsf(uu - fWm1) < 1.0f) c_right = min(c_right, x);
+                    if (fabsf(vv) < 1.0f) c_top = max(c_top, y);
+                    if (fabsf(vv - fHm1) < 1.0f) c_bottom = min(c_bottom, y);
+                }
+                const int sxx = narrow ? (int)(bx[j] - 0x4B400000u) : cv_round_f32(uu * 32.0f);
+                const int syy = narrow ? (int)(by[j] - 0x4B400000u) : cv_round_f32(vv * 32.0f);
+                const int ix = sxx >> 5, iy = syy >> 5;                 // (saturation to int16 cannot change any decision below)
+                if (ix >= W || ix + 1 < 0 || iy >= H || iy + 1 < 0) continue;       // the 2 x 2 footprint lies wholly outside: fill
+                const bool in_x0 = (unsigned)ix < (unsigned)W, in_x1 = (unsigned)(ix + 1) < (unsigned)W;
+                const bool in_y0 = (unsigned)iy < (unsigned)H, in_y1 = (unsigned)(iy + 1) < (unsigned)H;
+                const uint32_t cx0 = (uint32_t)min(max(ix, 0), W - 1), cx1 = (uint32_t)min(max(ix + 1, 0), W - 1);
+                const uint32_t r0 = (uint32_t)min(max(iy, 0), H - 1) * (uint32_t)W, r1 = (uint32_t)min(max(iy + 1, 0), H - 1) * (uint32_t)W;
+                const float q00 = src[(uint64_t)(r0 + cx0)], q01 = src[(uint64_t)(r0 + cx1)];
+                const float q10 = src[(uint64_t)(r1 + cx0)], q11 = src[(uint64_t)(r1 + cx1)];
+                const float s00 = in_x0 && in_y0 ? q00 : fill, s01 = in_x1 && in_y0 ? q01 : fill;
+                const float s10 = in_x0 && in_y1 ? q10 : fill, s11 = in_x1 && in_y1 ? q11 : fill;
+                const float ax = (float)(sxx & 31) * 0.03125f, ay = (float)(syy & 31) * 0.03125f;
+                const float ax0 = 1.0f - ax, ay0 = 1.0f - ay;
+                o[j] = ((s00 * (ay0 * ax0) + s01 * (ay0 * ax)) + s10 * (ay * ax0)) + s11 * (ay * ax);
+            }
+        }
+    }
+    if (!fast) plane_crop_fold(c_left, c_top, c_right, c_bottom, f, W, H, crop, clip);
+    if (active) {
+        float* __restrict__ d = out + (uint64_t)f * plane_elems + (uint64_t)((uint32_t)y * (uint32_t)W + (uint32_t)x0);
+        if (x0 + 3 < W && ((uintptr_t)d & 15u) == 0) {
+            *reinterpret_cast<float4*>(d) = make_float4(o[0], o[1], o[2], o[3]);
+            // (as in remap_store_u8c4: the compiler would otherwise split this store into a dword every path shares and a dwordx3; it does
+            // not move code across an asm statement)
+            asm volatile("" ::: "memory");
+        } else {                                                        // (a loop: its stores do not merge with the 16-byte one)
+            const int m = min(4, W - x0);
+#pragma unroll 1
+            for (int j = 0; j < m; ++j) d[j] = j == 0 ? o[0] : j == 1 ? o[1] : j == 2 ? o[2] : o[3];      // (selects: o stays in registers)
+        }
+    }
+}
+
+// Footprint-level tail of the PLANE_N* instantiations: cv2.remap INTER_NEAREST / BORDER_CONSTANT on elements of ES = 1, 2, 4 or 8 bytes
+// (remapNearest): ix = sat_short(cvRound(u)), iy = sat_short(cvRound(v)) -- float32 coordinates rounded half to even; the saturation cannot
+// change the inside test, W and H are below 32,768 --, the element copied as bits where 0 <= ix < W and 0 <= iy < H, `fill` (the element's
+// bit pattern) otherwise.  Every load goes to the position clamped into the plane.  SCAN: the four crop tests on every pixel (the general
+// path; a hot or pair footprint is certified DEEP, no pixel of it can pass one).  The lane's four elements are 4 ES contiguous bytes: stores of
+// min(4 ES, 16) bytes where the address is aligned to that, else per element, and per element in the lane that overhangs the right edge.
+template <int ES> struct PlaneElem;
+template <> struct PlaneElem<1> { typedef uint8_t type; };
+template <> struct PlaneElem<2> { typedef uint16_t type; };
+template <> struct PlaneElem<4> { typedef uint32_t type; };
+template <> struct PlaneElem<8> { typedef uint64_t type; };
+template <int ES, bool SCAN>
+__device__ __forceinline__ void remap_store_plane_nearest(const float (&u)[4], const float (&v)[4], uint32_t f, int x0, int y, bool active, int W,
+                                                          int H, const uint8_t* __restrict__ planes, uint8_t* __restrict__ out, uint64_t fill,
+                                                          int32_t* __restrict__ crop, int32_t* __restrict__ clip)
+{
+    typedef typename PlaneElem<ES>::type T;
+    const uint64_t plane_elems = (uint64_t)((uint32_t)W * (uint32_t)H);
+    const T* __restrict__ src = reinterpret_cast<const T*>(planes) + (uint64_t)f * plane_elems;
+    const float fWm1 = (float)(W - 1), fHm1 = (float)(H - 1);
+    T o[4];
+    int c_left = 0, c_top = 0, c_right = W - 1, c_bottom = H - 1;
+    if (active) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const float uu = u[j], vv = v[j];
+            const int x = x0 + j;
+            if (SCAN && x < W) {                                        // crop-boundary scan, mfs.py:1075-1098 (exact: Sterbenz)
+                if (fabsf(uu) < 1.0f) c_left = max(c_left, x);
+                if (fabsf(uu - fWm1) < 1.0f) c_right = min(c_right, x);
+                if (fabsf(vv) < 1.0f) c_top = max(c_top, y);
+                if (fabsf(vv - fHm1) < 1.0f) c_bottom = min(c_bottom, y);
+            }
+            const int ix = cv_round_f32(uu), iy = cv_round_f32(vv);
+            const bool inside = (unsigned)ix < (unsigned)W && (unsigned)iy < (unsigned)H;
+            const uint32_t cx = (uint32_t)min(max(ix, 0), W - 1), cy = (uint32_t)min(max(iy, 0), H - 1);
+            const T s = src[(uint64_t)(cy * (uint32_t)W + cx)];
+            o[j] = inside ? s : (T)fill;
+        }
+    }
+    if (SCAN) plane_crop_fold(c_left, c_top, c_right, c_bottom, f, W, H, crop, clip);
+    if (active) {
+        T* __restrict__ d = reinterpret_cast<T*>(out) + (uint64_t)f * plane_elems + (uint64_t)((uint32_t)y * (uint32_t)W + (uint32_t)x0);
+        constexpr uint32_t VB = 4 * ES < 16 ? 4 * ES : 16;              // the widest store the lane's 4 ES bytes fill
+        if (x0 + 3 < W && ((uintptr_t)d & (VB - 1u)) == 0) {
+            __builtin_memcpy(__builtin_assume_aligned(d, VB), o, 4 * ES);
+            asm volatile("" ::: "memory");                              // (keeps the wide store whole, as in remap_store_plane_f32)
+        } else {                                                        // (a loop: its stores do not merge with the wide one)
+            const int m = min(4, W - x0);
+#pragma unroll 1
+            for (int j = 0; j < m; ++j) d[j] = j == 0 ? o[0] : j == 1 ? o[1] : j == 2 ? o[2] : o[3];      // (selects: o stays in registers)
+        }
+    }
+}
+
+// The planes' tail by format (`fill`: the element's bit pattern in the low bytes; float32 bits for PLANE_F32)
+template <Px PX, bool SCAN>
+__device__ __forceinline__ void remap_store_plane(const float (&u)[4], const float (&v)[4], uint32_t f, int x0, int y, bool active, int W, int H,
+                                                  const uint8_t* __restrict__ planes, uint8_t* __restrict__ out, uint64_t fill,
+                                                  int32_t* __restrict__ crop, int32_t* __restrict__ clip)
+{
+    if constexpr (PX == Px::PLANE_F32)
+        remap_store_plane_f32(u, v, f, x0, y, active, W, H, reinterpret_cast<const float*>(planes), reinterpret_cast<float*>(out),
+                              __uint_as_float((uint32_t)fill), crop, clip);
+    else
+        remap_store_plane_nearest<px_sample_bytes(PX), SCAN>(u, v, f, x0, y, active, W, H, planes, out, fill, crop, clip);
+}
+
 // PX: the pixel format.  STAGE: the clip is 4-byte aligned, so the plan's STAGED windows can be copied by 16-byte global->LDS loads (always
 // the case for buffers from hipMalloc / torch; the other instantiation ignores the windows).
 // SCAN: the crop-boundary scan ALONE (crop_scan_kernel, warp.hip): the same ownership and coordinate code for footprint t of frame f,
@@ -998,6 +1181,9 @@ __device__ __forceinline__ void maps_store_f32(const float (&u)[4], const float 
 // PX = Px::MAPS: the coordinate maps instead of pixels (maps_footprint, warp_maps.hip): SCAN's body -- ownership, coordinates, the four edge
 // tests on every footprint -- plus the store of (u, v) (maps_store_f32): `frames` is unused, `out` points to float32 [n][H][W][2].  No window, no
 // taps, no border colour; the hot and pair footprints take the grey warp's shortcuts (they need no window here), everything else the general path.
+// PX = Px::PLANE_*: the side planes (plane_footprint, warp_planes.hip): `frames` / `out` hold W H elements of px_sample_bytes(PX) bytes per
+// frame, `border16` is the fill value's bit pattern, and the pixels go through remap_store_plane -- taps from global memory like the uint16
+// warp (the plan's windows are cut for 3-byte pixels), the hot and pair shortcuts like the maps (they need no window), the general path for the rest.
 template <Px PX, bool STAGE, bool SCAN>
 __device__ __forceinline__ void footprint_body(const uint32_t f, const uint32_t t, const FootPlan* __restrict__ plan, const FootRegion* __restrict__ regions,
                                                const WarpGeom& g, const uint8_t* __restrict__ frames,
@@ -1015,13 +1201,16 @@ __device__ __forceinline__ void footprint_body(const uint32_t f, const uint32_t 
     constexpr bool C4 = PX == Px::U8C4, C4_STAGE = C4 && STAGE, WIN_STAGE = GREY_STAGE || C4_STAGE;
     constexpr bool MAPS = PX == Px::MAPS;
     static_assert(!MAPS || (!STAGE && !SCAN), "the maps kernel reads no frame: nothing to stage");
+    // NOWIN: the instantiations that take the hot and pair shortcuts without a window (the maps read no frame, the planes tap global memory)
+    constexpr bool PLANE = px_is_plane(PX), NOWIN = MAPS || PLANE;
+    static_assert(!PLANE || (!STAGE && !SCAN), "the plane warps take their taps from global memory");
     // inverse homographies of the footprint's candidate cells: [entry][Hi0..Hi8, pad] (80-byte rows)
     __shared__ __attribute__((aligned(16))) double s_hi[1][9][10];                // row 8: the "no cell" matrix, see OWN_NONE
     // source region of the footprint: MF_STAGE_ROWS rows of MF_STAGE_PITCH bytes (+ slack for the third dword of the last tap); the 4-byte
     // window's MF_STAGE_ROWS rows of MF_C4_PITCH bytes for U8C4
-    __shared__ __attribute__((aligned(16))) uint8_t s_src_all[SCAN || MAPS ? 16 : C4 ? LDS_WINDOW_PAD + MF_STAGE_ROWS * MF_C4_PITCH
+    __shared__ __attribute__((aligned(16))) uint8_t s_src_all[SCAN || NOWIN ? 16 : C4 ? LDS_WINDOW_PAD + MF_STAGE_ROWS * MF_C4_PITCH
                                                                              : LDS_WINDOW_PAD + LDS_WINDOW_BYTES + 64];
-    uint8_t* const s_src = &s_src_all[SCAN || MAPS ? 0 : LDS_WINDOW_PAD];
+    uint8_t* const s_src = &s_src_all[SCAN || NOWIN ? 0 : LDS_WINDOW_PAD];
     constexpr int wave = 0;
     const uint32_t ty = (__umulhi(t, g.div_m) + (t & g.div_pass)) >> g.div_s, tx = t - ty * g.nfx;
     const int xa = (int)(tx * (uint32_t)FOOT_W), ya = (int)(ty * (uint32_t)FOOT_H);
@@ -1195,8 +1384,8 @@ __device__ __forceinline__ void footprint_body(const uint32_t f, const uint32_t 
         return;
     }
 
-    if constexpr (WIN_STAGE || MAPS) {
-        if ((MAPS || gwin.on) && (pv.x & (MF_PLAN_HOT << 16)) != 0) {
+    if constexpr (WIN_STAGE || NOWIN) {
+        if ((NOWIN || gwin.on) && (pv.x & (MF_PLAN_HOT << 16)) != 0) {
             // the HOT footprints of the grey warp (one IN cell, certified denominator, deep, staged): the hot path's coordinates -- the cheap
             // chain where the plan allows it (FAST64), else the trimmed-reciprocal one -- without the general path's ownership code
             const crec_t rec = frec + (pv.x & 0xFFFu) * MF_CELL_DOUBLES;
@@ -1205,14 +1394,15 @@ __device__ __forceinline__ void footprint_body(const uint32_t f, const uint32_t 
                 cell_coords<false>(rec, xs0, yy, x0, 0xFu, u, v, true);
             // (MAPS: a hot footprint is whole and DEEP -- every lane stores, no pixel can pass a crop test)
             if constexpr (MAPS) maps_store_f32(u, v, f, x0, y, true, W, H, reinterpret_cast<float*>(out));
+            else if constexpr (PLANE) remap_store_plane<PX, false>(u, v, f, x0, y, true, W, H, frames, out, border16, crop, clip);
             else if constexpr (C4) remap_store_u8c4(u, v, f, x0, y, true, W, H, frames, out, border, crop, clip, gwin, &s_src[0]);
             else remap_store_u8c1(u, v, f, x0, y, true, W, H, frames, out, border, crop, clip, gwin, &s_src[0]);
             return;
         }
     }
     const cedge_t fedge = (cedge_t)(uintptr_t)(reinterpret_cast<const uint8_t*>(edges) + f * g.edge_frame_bytes);
-    if constexpr (WIN_STAGE || MAPS) {
-        if ((MAPS || gwin.on) && (pv.y & MF_PLAN_HOT) != 0) {
+    if constexpr (WIN_STAGE || NOWIN) {
+        if ((NOWIN || gwin.on) && (pv.y & MF_PLAN_HOT) != 0) {
             // the PAIR footprints of the grey warp (two cells, certified denominators, deep, staged): warp_kernel's per-pixel pair form --
             // the later cell owns a pixel where its one mask edge passes (one fma), the other cell the rest, both matrices in LDS; a pixel
             // inside the edge's float32 error band leaves the footprint to the general code
@@ -1252,6 +1442,7 @@ __device__ __forceinline__ void footprint_body(const uint32_t f, const uint32_t 
                     v[j] = (float)(((xs * h23.y + yy * h45.x) + h45.y) * iw);
                 }
                 if constexpr (MAPS) maps_store_f32(u, v, f, x0, y, true, W, H, reinterpret_cast<float*>(out));
+                else if constexpr (PLANE) remap_store_plane<PX, false>(u, v, f, x0, y, true, W, H, frames, out, border16, crop, clip);
                 else if constexpr (C4) remap_store_u8c4(u, v, f, x0, y, true, W, H, frames, out, border, crop, clip, gwin, &s_src[0]);
                 else remap_store_u8c1(u, v, f, x0, y, true, W, H, frames, out, border, crop, clip, gwin, &s_src[0]);
                 return;
@@ -1813,6 +2004,10 @@ __device__ __forceinline__ void footprint_body(const uint32_t f, const uint32_t 
         if constexpr (U16) {
             remap_store_u16(u, v, f, x0, y, active, W, H, reinterpret_cast<const uint16_t*>(frames), reinterpret_cast<uint16_t*>(out), border16,
                             crop, clip);
+            return;
+        }
+        if constexpr (PLANE) {
+            remap_store_plane<PX, true>(u, v, f, x0, y, active, W, H, frames, out, border16, crop, clip);
             return;
         }
         if constexpr (GREY) {

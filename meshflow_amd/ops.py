@@ -387,6 +387,112 @@ def crop_resize_resident(frames, bounds, out=None, size=None, status=None):
     return out, status
 
 
+def _need_planes(planes, interpolation, name='planes'):
+    """Check a stack of side planes for `warp_planes` / `crop_resize_planes`: a contiguous (n, H, W) device tensor, float32 for 'linear',
+    any dtype of 1, 2, 4 or 8 bytes for 'nearest' (moved as bytes: nothing depends on torch kernels for the dtype).  Returns the C call's
+    elem_bytes (0: the float32 linear call)."""
+    if interpolation not in ('linear', 'nearest'):
+        raise ValueError(f"interpolation must be 'linear' or 'nearest', got {interpolation!r}")
+    if not isinstance(planes, torch.Tensor) or not planes.is_cuda:
+        raise ValueError(f'{name} must be a CUDA/HIP torch tensor')
+    if planes.dim() != 3:
+        raise ValueError(f'{name} must be (n, H, W) planes, got shape {tuple(planes.shape)}')
+    if not planes.is_contiguous():
+        raise ValueError(f'{name} must be contiguous')
+    if interpolation == 'linear':
+        if planes.dtype != torch.float32:
+            raise ValueError(f"'linear' planes must be {torch.float32}, got {planes.dtype} (labels and masks: interpolation='nearest')")
+        return 0
+    if planes.is_complex() or planes.element_size() not in (1, 2, 4, 8):
+        raise ValueError(f"'nearest' planes must have elements of 1, 2, 4 or 8 bytes, got {planes.dtype}")
+    return planes.element_size()
+
+
+def _fill_bits(fill, dtype):
+    """`fill` cast to dtype, as the bit pattern of one element (an int below 2^64)."""
+    one = torch.tensor([fill], dtype=dtype)
+    return int.from_bytes(one.view(torch.uint8).numpy().tobytes(), 'little')
+
+
+def _planes_out(planes, shape, out):
+    if out is None:
+        return torch.empty(shape, dtype=planes.dtype, device=planes.device)
+    _need(out, planes.dtype, 'out')
+    if tuple(out.shape) != tuple(shape):
+        raise ValueError(f'out must have shape {tuple(shape)}, got {tuple(out.shape)}')
+    if out.device != planes.device:
+        raise ValueError(f'out must be on the planes\' device {planes.device}, got {out.device}')
+    return out
+
+
+def warp_planes(planes, table, interpolation='linear', fill=0, out=None, bounds=None):
+    """The mesh warp of side planes -- what travels with a video without being a picture: depth, disparity, flow components, confidence
+    (float32, 'linear') or labels and masks ('nearest') -- sampled at the positions the pixel warps of the same table sample
+    (mf_warp_plane_f32 / mf_warp_plane_nearest; the arrays the reference hands to cv2.remap at mfs.py:1063-1069).  planes: a contiguous
+    (n, H, W) device tensor, n == table.n.  'linear': float32, cv2.remap INTER_LINEAR on CV_32FC1 -- the maps quantised to 1/32 pixel exactly
+    as for the colour frames, no rounding or saturation of the result.  'nearest': any dtype of 1, 2, 4 or 8 bytes (bool, (u)int8 ... int64,
+    float16, bfloat16, float32, float64), cv2.remap INTER_NEAREST, the element copied as bits.  Where the source lies outside the plane, and
+    where no cell owns the pixel, the result is `fill` cast to the planes' dtype.  The frames' crop values accumulate in table.crop and the
+    clip-level rectangle in `bounds` / table.clip_bounds exactly as `warp` does it, so a planes-only caller gets the rectangle a frames caller
+    gets.  Returns the warped planes (the input's dtype and shape)."""
+    es = _need_planes(planes, interpolation)
+    n, H, W = planes.shape
+    if (n, W, H) != (table.n, table.W, table.H):
+        raise ValueError(f'planes {tuple(planes.shape)} do not match the cell table (n, H, W) = {(table.n, table.H, table.W)}')
+    out = _planes_out(planes, planes.shape, out)
+    if bounds is not None:
+        _need_bounds(bounds)
+    bptr = _ptr(bounds) if bounds is not None else None
+    if es == 0:
+        _lib.check(_lib_.mf_warp_plane_f32(_ptr(planes), _ptr(out), _ptr(table.buf), n, W, H, table.R, table.C, float(fill),
+                                           _ptr(table.crop), bptr, _stream()))
+    else:
+        _lib.check(_lib_.mf_warp_plane_nearest(_ptr(planes), _ptr(out), _ptr(table.buf), n, W, H, table.R, table.C, es,
+                                               _fill_bits(fill, planes.dtype), _ptr(table.crop), bptr, _stream()))
+    return out
+
+
+def crop_resize_planes(planes, bounds, interpolation='linear', size=None, out=None, status=None):
+    """`crop_resize` for side planes (mfs.py:1111-1157 on a plane; mf_crop_resize_plane_* / mf_crop_resize_dev_plane_*): crop to the inclusive
+    {left, top, right, bottom} and scale to `size` = (width, height), by default back to (W, H).  planes and interpolation as in
+    `warp_planes`: 'linear' is cv2.resize INTER_LINEAR on CV_32FC1 (a crop exactly twice the output in both axes takes INTER_AREA's fast
+    path, as cv2 does), 'nearest' cv2.resize INTER_NEAREST with the element copied as bits.  bounds: a 4-tuple the host knows, or an int32[4]
+    DEVICE tensor (what `warp_clip`, `stabilize_resident`, `stabilized_planes` return) that the kernels read when they execute -- the host
+    never reads it and the call never waits; the bytes are the same.  status (device rectangle only): as in `crop_resize_resident` -- an
+    int32[1] device tensor, the caller's (it accumulates) or a new zeroed one, that an unusable rectangle adds 1 to, leaving `out` untouched.
+    Returns the planes (n, height, width), or (planes, status) for a device rectangle."""
+    es = _need_planes(planes, interpolation)
+    n, H, W = planes.shape
+    oW, oH = (W, H) if size is None else check_output_size(size)
+    resident = isinstance(bounds, torch.Tensor)
+    if resident:
+        _need_bounds(bounds)
+    elif status is not None:
+        raise ValueError('status belongs to a device rectangle: a host rectangle is checked when the call is made')
+    out = _planes_out(planes, (n, oH, oW), out)
+    work = torch.empty(_lib_.mf_crop_resize_workspace_bytes(oW, oH), dtype=torch.uint8, device=planes.device)
+    if not resident:
+        left, top, right, bottom = (int(v) for v in bounds)
+        if es == 0:
+            _lib.check(_lib_.mf_crop_resize_plane_f32(_ptr(planes), _ptr(out), n, W, H, left, top, right, bottom, oW, oH, _ptr(work), _stream()))
+        else:
+            _lib.check(_lib_.mf_crop_resize_plane_nearest(_ptr(planes), _ptr(out), n, W, H, left, top, right, bottom, oW, oH, es, _ptr(work),
+                                                          _stream()))
+        return out
+    if status is None:
+        status = torch.zeros(1, dtype=torch.int32, device=planes.device)
+    else:
+        _need(status, torch.int32, 'status')
+        if status.numel() != 1:
+            raise ValueError('status must hold 1 int32')
+    if es == 0:
+        _lib.check(_lib_.mf_crop_resize_dev_plane_f32(_ptr(planes), _ptr(out), n, W, H, _ptr(bounds), oW, oH, _ptr(work), _ptr(status), _stream()))
+    else:
+        _lib.check(_lib_.mf_crop_resize_dev_plane_nearest(_ptr(planes), _ptr(out), n, W, H, _ptr(bounds), oW, oH, es, _ptr(work), _ptr(status),
+                                                          _stream()))
+    return out, status
+
+
 def vertex_motion(early, late, offsets, homographies, max_per_pair, W, H, R, C, ellipse_rows, ellipse_cols):
     """Vertex velocities and their running sum from matched features (mfs.py:236-452 after the tracker).
     early/late: (K_total, 2) float64 device tensors; offsets: (P+1,) int32; homographies: (P, 3, 3) float64.

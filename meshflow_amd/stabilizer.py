@@ -856,9 +856,41 @@ class MeshFlowStabilizer:
             raise DegenerateMeshError(bad, None)
         return ops.warp_maps(table, first=first, count=count, out=out, bounds=bounds), bounds
 
+    def stabilized_planes(self, d_planes, d_disp, homographies, interpolation='linear', fill=0, crop=False, output_size=None, out=None,
+                          adaptive_weights_definition=ADAPTIVE_WEIGHTS_DEFINITION_ORIGINAL):
+        """Side planes of a clip -- depth, flow, confidence (float32, 'linear') or labels and masks ('nearest', any dtype of 1, 2, 4 or 8
+        bytes) -- moved exactly as `stabilize_resident` moves its colour frames, without any frame: the Jacobi sweep (mfs.py:695-704) on
+        d_disp, the cell table + plan of all F frames, then `ops.warp_planes` on d_planes (F, H, W); like `stabilization_maps`, everything
+        on torch's current stream.  crop=True: `ops.crop_resize_planes` from the clip rectangle as the warp left it on the device (it never
+        visits the host), scaled to output_size = (width, height), by default back to (W, H) (mfs.py:1111-1157).  `out`: the tensor to fill
+        (the cropped planes with crop=True).  Returns (planes, bounds): bounds = int32[4] device tensor {left, top, right, bottom}, the
+        rectangle `stabilization_maps` returns for the same inputs.  A degenerate mesh raises `DegenerateMeshError` (clip_serial None) here,
+        synchronously, before a plane is written.  (A caller that moves frames AND planes keeps one table: `_stabilized_frames_device`.)"""
+        import torch
+        from . import ops
+        self._check_definition(adaptive_weights_definition)
+        self._check_mesh_shape(d_disp, d_disp.shape[0])
+        if output_size is not None and not crop:
+            raise ValueError('output_size belongs to crop=True')
+        ops._need_planes(d_planes, interpolation, 'd_planes')
+        H, W = int(d_planes.shape[1]), int(d_planes.shape[2])
+        d_stab = self._stabilized_vertex_displacements_device(d_disp, W, H, adaptive_weights_definition, homographies)
+        bounds = torch.empty(4, dtype=torch.int32, device=d_disp.device)
+        table = ops.cell_table(d_disp, d_stab, W, H, self.mesh_row_count, self.mesh_col_count, bounds=bounds)
+        bad = int(table.status.item())
+        if bad:
+            raise DegenerateMeshError(bad, None)
+        if not crop:
+            return ops.warp_planes(d_planes, table, interpolation, fill, out=out, bounds=bounds), bounds
+        warped = ops.warp_planes(d_planes, table, interpolation, fill, bounds=bounds)
+        cropped, _ = ops.crop_resize_planes(warped, bounds, interpolation, size=output_size, out=out)
+        return cropped, bounds
+
     def _stabilized_frames_device(self, d_frames, d_unstab, d_stab, out=None, table=None):
         """d_frames: (n, H, W, 3) uint8; d_unstab/d_stab: (n, R+1, C+1, 2) float64, all in HBM.
-        Returns (stabilized frames (n, H, W, 3) uint8, per-frame crop values (n, 4) int32), in HBM."""
+        Returns (stabilized frames (n, H, W, 3) uint8, per-frame crop values (n, 4) int32), in HBM.
+        table: a `CellTable` to (re)build for this clip instead of a new one -- the caller keeps it, and `ops.warp_planes(planes, table)`
+        then moves the clip's side planes through the very table its frames went through, without a second cell table or plan."""
         from . import ops
         n, H, W, _ = d_frames.shape
         table = ops.cell_table(d_unstab, d_stab, W, H, self.mesh_row_count, self.mesh_col_count, table=table)

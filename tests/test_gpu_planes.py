@@ -1,0 +1,416 @@
+"""-m gpu: the side planes of a video -- `ops.warp_planes`, `ops.crop_resize_planes`, `MeshFlowStabilizer.stabilized_planes` over
+mf_warp_plane_* / mf_crop_resize_plane_* / mf_crop_resize_dev_plane_*.
+
+Every equality is bit for bit (uint8 / uint16 / uint32 / uint64 views); there is no tolerance anywhere.  The references: tests/planes_model.py
+applied to the reference's own maps (tests/cv16_model.warp_maps: the C oracle, on the CPU), the merged uint16 kernels on integer-valued planes,
+and a gather on `ops.warp_maps` for the label planes.  The geometries are tests/test_gpu_warp_maps.py's kinds at 64 x 48 .. 160 x 96, with
+2 x 2 and 3 x 4 meshes, one odd width and one frame at the 2-pixel limit."""
+import os
+import sys
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+torch = pytest.importorskip('torch')
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import cv16_model  # noqa: E402
+import planes_model  # noqa: E402
+
+UINT = {1: np.uint8, 2: np.uint16, 4: np.uint32, 8: np.uint64}
+SIGNED = {1: np.uint8, 2: np.int16, 4: np.int32, 8: np.int64}          # what torch.from_numpy takes for the same bytes
+# fill values per element size, as the dtype's own number and as its bits; the random data below never holds them
+FILL = {1: (231, 231), 2: (-4083, 0xF00D), 4: (-559038737, 0xDEADBEEF), 8: (-81985529216486896, 0xFEDCBA9876543210)}
+DATA_TOP = {1: 200, 2: 60000, 4: 2 ** 31, 8: 2 ** 63}
+FILL_F32 = -777.25
+
+
+@pytest.fixture(scope='module')
+def dev():
+    if not torch.cuda.is_available():
+        pytest.fail('no GPU visible: the -m gpu tests must run on an MI355X')
+    return torch.device('cuda:0')
+
+
+def dev64(a, dev):
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev)
+
+
+def motion(F, H, W, R, C, seed, jitter, kind):
+    from meshflow_amd import synthetic
+    from oracle import meshflow_oracle as mo
+    if kind == 'shift':                            # large global translation: wide border rings, many uncovered pixels
+        disp, hom = synthetic.motion(F, R, C, seed=seed, translation_sigma=12.0, jitter_sigma=jitter)
+    else:
+        disp, hom = synthetic.motion(F, R, C, seed=seed, jitter_sigma=jitter)
+    return disp, hom, mo.stabilized_vertex_displacements(W, H, 0, disp, hom, 3, 10)
+
+
+def table_for(dev, case, bounds=None):
+    from meshflow_amd import ops
+    return ops.cell_table(dev64(case['disp'], dev), dev64(case['stab'], dev), case['W'], case['H'], case['R'], case['C'], bounds=bounds)
+
+
+# F, H, W, R, C, jitter, kind, seed, tiny
+GEOMETRIES = {
+    '64x48_2x2': (2, 48, 64, 2, 2, 3.0, 'shift', 50, False),
+    '100x72_3x5': (3, 72, 100, 3, 5, 6.0, 'jitter', 75, False),
+    '131x97_4x6_oddW': (3, 97, 131, 4, 6, 4.0, 'shift', 101, False),      # odd W: the overhanging lane, rows that are not 16-byte aligned
+    '160x96_3x4': (2, 96, 160, 3, 4, 3.0, 'jitter', 99, False),
+    '9x2_1x2_tiny': (3, 2, 9, 1, 2, 0.3, 'jitter', 12, True),             # the 2-pixel limit: below one footprint, no deep pixel
+}
+_CASES = {}
+
+
+def case_for(name):
+    """The geometry's motion, its maps from the C oracle, random planes and the planes model's results: computed once, shared, never changed."""
+    if name in _CASES:
+        return _CASES[name]
+    F, H, W, R, C, jitter, kind, seed, tiny = GEOMETRIES[name]
+    disp, hom, stab = motion(F, H, W, R, C, seed, jitter, kind)
+    mx = np.empty((F, H, W), np.float32)
+    my = np.empty((F, H, W), np.float32)
+    for f in range(F):
+        mx[f], my[f], _, bad = cv16_model.warp_maps(W, H, R, C, disp[f], stab[f])
+        assert bad == 0
+    rng = np.random.default_rng(seed)
+    planes = (rng.normal(0, 1000.0, (F, H, W))).astype(np.float32)
+    ints = rng.integers(0, 65536, (F, H, W)).astype(np.float32)
+    labels = {es: rng.integers(0, DATA_TOP[es], (F, H, W), dtype=np.uint64).astype(UINT[es]) for es in UINT}
+    c = dict(F=F, H=H, W=W, R=R, C=C, tiny=tiny, disp=disp, hom=hom, stab=stab, mx=mx, my=my, planes=planes, ints=ints, labels=labels)
+    c['linear'] = np.stack([planes_model.remap_linear_f32(planes[f], mx[f], my[f], FILL_F32) for f in range(F)])
+    c['nearest'] = {es: np.stack([planes_model.remap_nearest(labels[es][f], mx[f], my[f], FILL[es][1]) for f in range(F)]) for es in UINT}
+    for a in (mx, my, planes, ints, c['linear'], *labels.values(), *c['nearest'].values()):
+        a.setflags(write=False)
+    _CASES[name] = c
+    return c
+
+
+def to_dev(a, dev):
+    """A NumPy plane stack on the device, unsigned element types as the signed torch dtype of the same bytes."""
+    a = np.ascontiguousarray(a)
+    if a.dtype.kind == 'u' and a.dtype.itemsize > 1:
+        a = a.view(SIGNED[a.dtype.itemsize])
+    return torch.from_numpy(a).to(dev)
+
+
+def raw(t):
+    """The tensor's bytes on the host, as unsigned integers of the element's size."""
+    a = t.detach().cpu().contiguous()
+    return a.view(torch.uint8).numpy().view(UINT[t.element_size()]).reshape(tuple(t.shape))
+
+
+def same_bits(got, want):
+    want = np.ascontiguousarray(want)
+    return np.array_equal(raw(got), want.view(UINT[want.dtype.itemsize]))
+
+
+@pytest.mark.parametrize('name', list(GEOMETRIES))
+def test_warp_equals_the_planes_model(dev, name):
+    from meshflow_amd import ops
+    c = case_for(name)
+    W, H = c['W'], c['H']
+    unowned = (c['mx'] == np.float32(W + 1)) & (c['my'] == np.float32(H + 1))
+    # partly outside: an owned pixel whose 2 x 2 taps straddle the plane's edge
+    sx, sy = np.rint(c['mx'] * np.float32(32)).astype(np.int64) >> 5, np.rint(c['my'] * np.float32(32)).astype(np.int64) >> 5
+    whole_out = (sx >= W) | (sx + 1 < 0) | (sy >= H) | (sy + 1 < 0)
+    partly = ~unowned & ~whole_out & ((sx < 0) | (sx + 1 >= W) | (sy < 0) | (sy + 1 >= H))
+    print(name, 'unowned', int(unowned.sum()), 'partly outside', int(partly.sum()), 'of', unowned.size)
+    if not c['tiny']:
+        assert unowned.any() and partly.any() and (~unowned & ~partly & ~whole_out).any(), 'the case cannot fail on borders'
+        assert np.all(c['linear'][unowned] == np.float32(FILL_F32)) and np.any(c['linear'][partly] != np.float32(FILL_F32))
+    table = table_for(dev, c)
+    got = ops.warp_planes(to_dev(c['planes'], dev), table, 'linear', fill=FILL_F32)
+    torch.cuda.synchronize()
+    table.check()
+    assert got.dtype == torch.float32 and tuple(got.shape) == c['planes'].shape
+    diff = raw(got) != c['linear'].view(np.uint32)
+    assert not diff.any(), (int(diff.sum()), np.argwhere(diff)[:5].tolist())
+    for es in UINT:
+        planes = to_dev(c['labels'][es], dev)
+        got = ops.warp_planes(planes, table, 'nearest', fill=FILL[es][0])
+        assert got.dtype == planes.dtype
+        diff = raw(got) != c['nearest'][es]
+        assert not diff.any(), (es, int(diff.sum()), np.argwhere(diff)[:5].tolist())
+        if not c['tiny']:
+            assert (c['nearest'][es] == FILL[es][1]).any() and not (c['labels'][es] == FILL[es][1]).any()
+    # the default interpolation is 'linear', the default fill 0
+    assert torch.equal(ops.warp_planes(to_dev(c['planes'], dev), table, fill=FILL_F32), ops.warp_planes(to_dev(c['planes'], dev), table, 'linear', FILL_F32))
+    zero = ops.warp_planes(to_dev(c['labels'][4], dev), table, 'nearest')
+    assert np.array_equal(raw(zero)[unowned], np.zeros(int(unowned.sum()), np.uint32))
+
+
+@pytest.mark.parametrize('name', list(GEOMETRIES))
+def test_linear_warp_equals_the_uint16_kernel(dev, name):
+    """Integer-valued float32 planes in 0 .. 65,535: rint(clamp(warp_planes)) is channel 0 of `ops.warp` on the uint16 BGR stack of the plane,
+    the same fill in the border."""
+    from meshflow_amd import ops
+    c = case_for(name)
+    fill = 40000
+    table = table_for(dev, c)
+    got = ops.warp_planes(to_dev(c['ints'], dev), table, 'linear', fill=fill).cpu().numpy()
+    stack = np.repeat(c['ints'].astype(np.uint16)[..., None], 3, axis=3).view(np.int16)
+    want = ops.warp(torch.from_numpy(stack).to(dev).view(torch.uint16), table, (fill, fill, fill))
+    want = want.view(torch.int16).cpu().numpy().view(np.uint16)[..., 0]
+    assert np.array_equal(np.clip(np.rint(got.astype(np.float64)), 0, 65535).astype(np.uint16), want)
+    if not c['tiny']:
+        assert (want == fill).any() and (want != fill).any()
+
+
+@pytest.mark.parametrize('name', list(GEOMETRIES))
+def test_nearest_warp_equals_a_gather_on_the_maps(dev, name):
+    """An independent route through a kernel proven against the oracle: maps.round(), inside test, gather, fill -- INTEGRATION.md's recipe."""
+    from meshflow_amd import ops
+    c = case_for(name)
+    F, H, W = c['F'], c['H'], c['W']
+    table = table_for(dev, c)
+    maps = ops.warp_maps(table)
+    idx = maps.round().long()
+    ix, iy = idx[..., 0], idx[..., 1]
+    inside = (ix >= 0) & (ix < W) & (iy >= 0) & (iy < H)
+    flat = (iy.clamp(0, H - 1) * W + ix.clamp(0, W - 1)).view(F, -1)
+    for es in UINT:
+        labels = to_dev(c['labels'][es], dev)
+        want = torch.where(inside, labels.view(F, -1).gather(1, flat).view(F, H, W), torch.full_like(labels, FILL[es][0]))
+        got = ops.warp_planes(labels, table, 'nearest', fill=FILL[es][0])
+        assert np.array_equal(raw(got), raw(want)), es
+    # dtypes torch has few kernels for travel as bytes: bfloat16, float16, bool, float64
+    bits16 = to_dev(c['labels'][2], dev)
+    for dt in (torch.bfloat16, torch.float16):
+        got = ops.warp_planes(bits16.view(dt), table, 'nearest', fill=1.5)
+        want = ops.warp_planes(bits16, table, 'nearest', fill=int(torch.tensor([1.5], dtype=dt).view(torch.int16)))
+        assert got.dtype == dt and torch.equal(got.view(torch.int16), want)
+    flags = to_dev(c['labels'][1] & 1, dev)
+    got = ops.warp_planes(flags.view(torch.bool), table, 'nearest', fill=True)
+    assert got.dtype == torch.bool and torch.equal(got.view(torch.uint8), ops.warp_planes(flags, table, 'nearest', fill=1))
+    bits64 = to_dev(c['labels'][8], dev)
+    got = ops.warp_planes(bits64.view(torch.float64), table, 'nearest', fill=-2.5)
+    assert torch.equal(got.view(torch.int64), ops.warp_planes(bits64, table, 'nearest', fill=int(torch.tensor([-2.5], dtype=torch.float64).view(torch.int64))))
+
+
+@pytest.mark.parametrize('name', ['100x72_3x5', '131x97_4x6_oddW', '9x2_1x2_tiny'])
+@pytest.mark.parametrize('mode,es', [('linear', 4), ('nearest', 1), ('nearest', 8)])
+def test_crop_fold(dev, name, mode, es):
+    """After `warp_planes` alone on a fresh table, table.crop and the rectangle are what `ops.crop_scan` gives for that table."""
+    from meshflow_amd import ops
+    c = case_for(name)
+    planes = to_dev(c['planes'] if mode == 'linear' else c['labels'][es], dev)
+    scan = table_for(dev, c)
+    ops.crop_scan(scan)
+    t = table_for(dev, c)
+    ops.warp_planes(planes, t, mode, fill=3)
+    bounds = torch.empty(4, dtype=torch.int32, device=dev)
+    tb = table_for(dev, c, bounds=bounds)
+    ops.warp_planes(planes, tb, mode, fill=3, bounds=bounds)
+    torch.cuda.synchronize()
+    assert torch.equal(t.crop, scan.crop) and torch.equal(t.clip_bounds, scan.clip_bounds)
+    assert torch.equal(tb.crop, scan.crop) and torch.equal(bounds, scan.clip_bounds)
+    if not c['tiny']:
+        defaults = torch.tensor([0, 0, c['W'] - 1, c['H'] - 1], dtype=torch.int32, device=dev)
+        assert not torch.equal(scan.crop, defaults.expand(c['F'], 4)), 'the geometry sets no crop value: nothing compared'
+
+
+def guarded(dev, like, lead):
+    """A buffer full of the sentinel byte 0xA5 with a view of `like`'s shape and dtype that starts `lead` elements in; (buffer, view)."""
+    es, size = like.element_size(), like.numel()
+    buf = torch.full(((lead + size + 16) * es,), 0xA5, dtype=torch.uint8, device=dev)
+    return buf, buf[lead * es:(lead + size) * es].view(like.dtype).view(like.shape)
+
+
+def guards_intact(buf, like, lead):
+    es, size = like.element_size(), like.numel()
+    return bool((buf[:lead * es] == 0xA5).all()) and bool((buf[(lead + size) * es:] == 0xA5).all())
+
+
+@pytest.mark.parametrize('name', ['131x97_4x6_oddW', '64x48_2x2'])
+@pytest.mark.parametrize('lead', [1, 3])
+def test_sentinel_padded_buffers(dev, name, lead):
+    """Views that start 1 and 3 elements into sentinel-filled buffers, the input and the output independently: the same results, and not a
+    byte outside the view changes."""
+    from meshflow_amd import ops
+    c = case_for(name)
+    table = table_for(dev, c)
+    for mode, planes, fill in [('linear', to_dev(c['planes'], dev), FILL_F32)] + [('nearest', to_dev(c['labels'][es], dev), FILL[es][0]) for es in UINT]:
+        want = ops.warp_planes(planes, table, mode, fill=fill)
+        ibuf, iview = guarded(dev, planes, lead)
+        iview.copy_(planes)
+        obuf, oview = guarded(dev, planes, lead)
+        assert iview.data_ptr() % 16 != 0 and iview.is_contiguous()
+        got_in = ops.warp_planes(iview, table, mode, fill=fill)                       # offset input, aligned output
+        got_out = ops.warp_planes(planes, table, mode, fill=fill, out=oview)         # aligned input, offset output
+        torch.cuda.synchronize()
+        assert got_out.data_ptr() == oview.data_ptr()
+        assert np.array_equal(raw(got_in), raw(want)) and np.array_equal(raw(oview), raw(want)), (mode, planes.dtype)
+        assert guards_intact(ibuf, planes, lead) and guards_intact(obuf, planes, lead) and np.array_equal(raw(iview), raw(planes))
+        # ... and the crop-resize from and into such views
+        rect = (3, 2, c['W'] - 5, c['H'] - 4)
+        want = ops.crop_resize_planes(planes, rect, mode)
+        got_in = ops.crop_resize_planes(iview, rect, mode)
+        obuf, oview = guarded(dev, planes, lead)
+        ops.crop_resize_planes(planes, rect, mode, out=oview)
+        torch.cuda.synchronize()
+        assert np.array_equal(raw(got_in), raw(want)) and np.array_equal(raw(oview), raw(want)) and guards_intact(obuf, planes, lead)
+
+
+RECT_H, RECT_W, RECT = 50, 77, (3, 4, 70, 45)                      # a 68 x 42 crop of 77 x 50 planes
+SIZES = {'same': None, 'up': (131, 90), 'down': (31, 17), 'half': (34, 21), 'mixed': (100, 20)}
+
+
+@pytest.mark.parametrize('size', list(SIZES))
+def test_crop_resize_equals_the_model(dev, size):
+    from meshflow_amd import ops
+    rng = np.random.default_rng(17)
+    n, H, W = 2, RECT_H, RECT_W
+    size_ = SIZES[size]
+    oW, oH = size_ or (W, H)
+    planes = rng.normal(0, 1000.0, (n, H, W)).astype(np.float32)
+    ints = rng.integers(0, 65536, (n, H, W)).astype(np.float32)
+    d_rect = torch.tensor(RECT, dtype=torch.int32, device=dev)
+    want = planes_model.crop_planes(planes, RECT, 'linear', size_)
+    got = ops.crop_resize_planes(to_dev(planes, dev), RECT, 'linear', size=size_)
+    got_dev, status = ops.crop_resize_planes(to_dev(planes, dev), d_rect, 'linear', size=size_)
+    assert tuple(got.shape) == (n, oH, oW) and got.dtype == torch.float32
+    assert same_bits(got, want) and torch.equal(got.view(torch.int32), got_dev.view(torch.int32)) and int(status.item()) == 0
+    for es in UINT:
+        labels = rng.integers(0, DATA_TOP[es], (n, H, W), dtype=np.uint64).astype(UINT[es])
+        want = planes_model.crop_planes(labels, RECT, 'nearest', size_)
+        got = ops.crop_resize_planes(to_dev(labels, dev), RECT, 'nearest', size=size_)
+        got_dev, status = ops.crop_resize_planes(to_dev(labels, dev), d_rect, 'nearest', size=size_)
+        assert got.dtype == to_dev(labels, dev).dtype and same_bits(got, want), es
+        assert np.array_equal(raw(got), raw(got_dev)) and int(status.item()) == 0
+    # integer-valued planes: the merged uint16 kernel after saturate_u16, away from the exact-2x case (where 16-bit data rounds half up in
+    # integers, tests/cv16_area.py, and float32 data takes the float sum)
+    got = ops.crop_resize_planes(to_dev(ints, dev), RECT, 'linear', size=size_).cpu().numpy()
+    if size != 'half':
+        stack = np.repeat(ints.astype(np.uint16)[..., None], 3, axis=3).view(np.int16)
+        want = ops.crop_resize(torch.from_numpy(stack).to(dev).view(torch.uint16), RECT, size=size_)
+        want = want.view(torch.int16).cpu().numpy().view(np.uint16)[..., 0]
+        assert np.array_equal(cv16_model.saturate_u16(got), want)
+    else:
+        assert 2 * oW == RECT[2] - RECT[0] + 1 and 2 * oH == RECT[3] - RECT[1] + 1
+        assert same_bits(torch.from_numpy(got), planes_model.crop_planes(ints, RECT, 'linear', size_))
+
+
+def test_empty_device_rectangle_sets_status(dev):
+    """An empty or out-of-plane device rectangle: status += 1 and `out` untouched, as `crop_resize_resident` does it; a host one raises."""
+    from meshflow_amd import ops
+    n, H, W = 2, 20, 33
+    planes = torch.from_numpy(np.random.default_rng(3).normal(0, 1, (n, H, W)).astype(np.float32)).to(dev)
+    frames = torch.zeros((n, H, W, 3), dtype=torch.uint8, device=dev)
+    for rect in ((9, 3, 8, 10), (0, 0, W, H - 1), (-1, 0, 5, 5)):
+        d_rect = torch.tensor(rect, dtype=torch.int32, device=dev)
+        _, want_status = ops.crop_resize_resident(frames, d_rect)
+        for mode, p in (('linear', planes), ('nearest', planes.view(torch.int32)), ('nearest', (planes > 0))):
+            out = torch.full_like(p, 1)
+            status = torch.zeros(1, dtype=torch.int32, device=dev)
+            got, st = ops.crop_resize_planes(p, d_rect, mode, out=out, status=status)
+            got, st = ops.crop_resize_planes(p, d_rect, mode, out=out, status=status, size=(W, H))
+            torch.cuda.synchronize()
+            assert st.data_ptr() == status.data_ptr() and int(status.item()) == 2 * int(want_status.item()) == 2
+            assert torch.equal(out, torch.full_like(p, 1))
+            with pytest.raises(ValueError):
+                ops.crop_resize_planes(p, rect, mode)
+
+
+def test_stabilized_planes(dev, monkeypatch):
+    from meshflow_amd import ops, synthetic
+    from meshflow_amd.stabilizer import DegenerateMeshError, MeshFlowStabilizer
+    F, H, W, R, C = 8, 64, 96, 3, 4
+    disp, hom = synthetic.motion(F, R, C, seed=71, jitter_sigma=2.0)
+    s = MeshFlowStabilizer(mesh_row_count=R, mesh_col_count=C, temporal_smoothing_radius=4, optimization_num_iterations=15, device='cuda:0')
+    rng = np.random.default_rng(8)
+    depth = torch.from_numpy(rng.normal(5, 2, (F, H, W)).astype(np.float32)).to(dev)
+    labels = torch.from_numpy(rng.integers(0, 50, (F, H, W)).astype(np.int64)).to(dev)
+    maps, maps_bounds = s.stabilization_maps(dev64(disp, dev), hom, W, H)
+    stab = s._get_stabilized_vertex_displacements(F, [np.zeros((H, W, 3), np.uint8)] * F, s.ADAPTIVE_WEIGHTS_DEFINITION_ORIGINAL, disp, hom)
+    for planes, mode, fill in ((depth, 'linear', -1.0), (labels, 'nearest', -1)):
+        table = ops.cell_table(dev64(disp, dev), dev64(stab, dev), W, H, R, C)
+        warped = ops.warp_planes(planes, table, mode, fill=fill)
+        got, b = s.stabilized_planes(planes, dev64(disp, dev), hom, mode, fill)
+        torch.cuda.synchronize()
+        assert np.array_equal(raw(got), raw(warped))
+        assert b.dtype == torch.int32 and torch.equal(b, maps_bounds) and torch.equal(b, table.clip_bounds)
+        rect = tuple(b.tolist())
+        assert rect != (0, 0, W - 1, H - 1)
+        for size in (None, (61, 40)):
+            want = ops.crop_resize_planes(warped, rect, mode, size=size)
+            got, b2 = s.stabilized_planes(planes, dev64(disp, dev), hom, mode, fill, crop=True, output_size=size)
+            assert np.array_equal(raw(got), raw(want)) and torch.equal(b2, maps_bounds)
+        out = torch.empty_like(planes)
+        got, _ = s.stabilized_planes(planes, dev64(disp, dev), hom, mode, fill, crop=True, out=out)
+        assert got.data_ptr() == out.data_ptr() and np.array_equal(raw(out), raw(ops.crop_resize_planes(warped, rect, mode)))
+    with pytest.raises(ValueError):
+        s.stabilized_planes(depth, dev64(disp, dev), hom, output_size=(10, 10))
+    # a degenerate mesh: the sweep's result replaced by displacements that put vertex (0, 1) of frame 1 onto vertex (0, 0)
+    flat = np.zeros((F, R + 1, C + 1, 2))
+    collapsed = flat.copy()
+    collapsed[1, 0, 1] = [-W / C, 0.0]
+    monkeypatch.setattr(s, '_stabilized_vertex_displacements_device', lambda *a, **k: dev64(collapsed, dev))
+    out = torch.full_like(depth, 7.0)
+    with pytest.raises(DegenerateMeshError) as e:
+        s.stabilized_planes(depth, dev64(flat, dev), hom, out=out)
+    assert e.value.cells >= 1 and e.value.clip_serial is None
+    torch.cuda.synchronize()
+    assert bool((out == 7.0).all())
+
+
+def test_python_refusals(dev):
+    from meshflow_amd import ops
+    c = case_for('64x48_2x2')
+    F, H, W = c['F'], c['H'], c['W']
+    table = table_for(dev, c)
+    f32 = to_dev(c['planes'], dev)
+    crop0 = table.crop.clone()
+    rect = (1, 1, W - 2, H - 2)
+    with pytest.raises(ValueError, match='int32'):                                   # 'linear' on a non-float32 plane
+        ops.warp_planes(f32.view(torch.int32), table, 'linear')
+    with pytest.raises(ValueError, match='float64'):
+        ops.crop_resize_planes(f32.double(), rect, 'linear')
+    with pytest.raises(ValueError, match='complex64'):                               # no 1/2/4/8-byte element to copy
+        ops.warp_planes(torch.zeros((F, H, W), dtype=torch.complex64, device=dev), table, 'nearest')
+    with pytest.raises(ValueError, match='complex64'):
+        ops.crop_resize_planes(torch.zeros((F, H, W), dtype=torch.complex64, device=dev), rect, 'nearest')
+    with pytest.raises(ValueError, match='complex128'):
+        ops.warp_planes(torch.zeros((F, H, W), dtype=torch.complex128, device=dev), table, 'nearest')
+    for mode in ('linear', 'nearest'):
+        with pytest.raises(ValueError, match='shape'):                               # (n, H, W, 1)
+            ops.warp_planes(f32[..., None], table, mode)
+        with pytest.raises(ValueError, match='shape'):
+            ops.crop_resize_planes(f32[..., None], rect, mode)
+        with pytest.raises(ValueError, match='cell table'):                          # n != table.n
+            ops.warp_planes(f32[:1], table, mode)
+        with pytest.raises(ValueError, match='cell table'):
+            ops.warp_planes(f32.transpose(1, 2).contiguous(), table, mode)
+        with pytest.raises(ValueError, match='contiguous'):
+            ops.warp_planes(torch.zeros((F, H, 2 * W), dtype=torch.float32, device=dev)[..., ::2], table, mode)
+        with pytest.raises(ValueError, match='contiguous'):
+            ops.crop_resize_planes(torch.zeros((F, H, 2 * W), dtype=torch.float32, device=dev)[..., ::2], rect, mode)
+        for bad in (torch.zeros((F, H, W), dtype=torch.float64, device=dev), torch.zeros((F, H, W + 1), dtype=torch.float32, device=dev),
+                    torch.zeros((F, H, 2 * W), dtype=torch.float32, device=dev)[..., ::2], np.zeros((F, H, W), np.float32)):
+            with pytest.raises(ValueError):
+                ops.warp_planes(f32, table, mode, out=bad)
+            with pytest.raises(ValueError):
+                ops.crop_resize_planes(f32, rect, mode, out=bad)
+        with pytest.raises(ValueError):
+            ops.crop_resize_planes(f32, rect, mode, size=(31, 17), out=torch.zeros((F, 31, 17), dtype=torch.float32, device=dev))
+        with pytest.raises(ValueError):
+            ops.warp_planes(f32, table, mode, bounds=torch.zeros(3, dtype=torch.int32, device=dev))
+        with pytest.raises(ValueError):
+            ops.crop_resize_planes(f32, torch.zeros(4, dtype=torch.int64, device=dev), mode)
+        with pytest.raises(ValueError):
+            ops.crop_resize_planes(f32, rect, mode, status=torch.zeros(1, dtype=torch.int32, device=dev))
+        with pytest.raises(ValueError):
+            ops.crop_resize_planes(f32, rect, mode, size=(0, 5))
+    with pytest.raises(ValueError):
+        ops.warp_planes(f32, table, 'cubic')
+    with pytest.raises(ValueError):
+        ops.warp_planes(f32.cpu(), table)
+    torch.cuda.synchronize()
+    assert torch.equal(table.crop, crop0)
+    # the pixel operators still refuse what they refused: these planes are no frames
+    with pytest.raises(ValueError):
+        ops.warp(f32, table)
+    with pytest.raises(ValueError):
+        ops.crop_resize(f32, rect)
