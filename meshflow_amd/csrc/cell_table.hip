@@ -571,7 +571,7 @@ __device__ __forceinline__ void plan_one_footprint(EdgeOf edge_of, HiOf hi_of, M
             bool certified = false;                  // one of the warp kernel's three certified shapes: hot, pair, multi
             region.flags_origin = MF_REGION_STAGED | (deep ? MF_REGION_DEEP : 0u) | (noflag ? MF_REGION_NOFLAG : 0u) | ((uint32_t)sy0 * MF_STAGE_PITCH + bs);
             region.src_dwords = ((uint32_t)sy0 * (3u * (uint32_t)W) + bs) >> 2;
-            // The premises of the warp kernel's cheap coordinate chain (warp_body.h, cheap_quotients) for EVERY listed cell on this footprint:
+            // The premises of the warp kernel's cheap coordinate chain (warp_coords.h, cheap_quotients) for EVERY listed cell on this footprint:
             // no cancellation in the numerators -- the sum of the magnitudes of a numerator's terms (largest at the far corner: x, y >= 0)
             // at most 8 x the numerator, which is u w >= umin wlo for every listed cell -- denominator terms bounded, denominator above
             // 0.52.  One test for the three paths that use it (hot, pair, multi).
@@ -581,7 +581,7 @@ __device__ __forceinline__ void plan_one_footprint(EdgeOf edge_of, HiOf hi_of, M
             if (deep && p.e[1] == (uint16_t)MF_PLAN_UNIT && (p.e[0] & (MF_PLAN_VALID | MF_PLAN_IN)) == (MF_PLAN_VALID | MF_PLAN_IN)) {
                 // FAST64: no cancellation in the numerators (sum of the terms' magnitudes at most 8 x the value, everywhere on
                 // the footprint: the former grows with x and y, the latter is smallest at a corner), denominator terms bounded --
-                // the premises of the warp kernel's error bound for its cheap coordinate chain (warp_body.h, cell_coords_fast)
+                // the premises of the warp kernel's error bound for its cheap coordinate chain (warp_coords.h, cell_coords_fast)
                 const bool fast64 = cheap_all;
                 p.e[1] = (uint16_t)(MF_PLAN_UNIT | MF_PLAN_HOT | (fast64 ? MF_PLAN_FAST64 : 0u));
                 certified = true;

@@ -59,7 +59,7 @@ __host__ __device__ inline int reach_parts(int R, int C) { return (R * C + 63) /
 // (bit 13: clear in every valid entry -- cell indices take bits 0-11 -- and in the raw row / column numbers of an overflow list, so
 // the kernel tests this one bit without looking at the rest of the list)
 #define MF_PLAN_HOT 0x2000u
-// ... and MF_PLAN_FAST64 (only with HOT) the premises of the warp kernel's cheap float64 coordinate chain (warp_body.h,
+// ... and MF_PLAN_FAST64 (only with HOT) the premises of the warp kernel's cheap float64 coordinate chain (warp_coords.h,
 // cell_coords_fast): at every pixel of the footprint |h0| x + |h1| y + |h2| <= 8 (h0 x + h1 y + h2), the same for the second row,
 // and |h6| x + |h7| y + |h8| <= 2.5.
 #define MF_PLAN_FAST64 0x0002u
@@ -171,6 +171,13 @@ inline TableView table_view(void* blob, int n, int W, int H, int R, int C)
     v.grid = v.reach + (size_t)n * reach_parts(R, C) * 4;
     v.bounds = v.grid + (R + C + 2);
     return v;
+}
+
+// a.lo * b.lo + a.hi * b.hi + c on 16-bit halves (v_dot2_u32_u16): the horizontal lerp of the warp's and the crop-resize's uint8 blends
+__device__ __forceinline__ uint32_t udot2(uint32_t a, uint32_t b, uint32_t c)
+{
+    typedef unsigned short us2 __attribute__((ext_vector_type(2)));
+    return __builtin_amdgcn_udot2(__builtin_bit_cast(us2, a), __builtin_bit_cast(us2, b), c, false);
 }
 
 // n / d for n < 2^31 as (n * m) >> (32 + s), m = ceil(2^(31 + ceil(log2 d)) / d): exact because the excess m d - 2^p is below

@@ -21,13 +21,6 @@ __device__ __forceinline__ uint32_t load_bgr(const uint8_t* __restrict__ frame, 
     return v & 0xFFFFFFu;
 }
 
-typedef unsigned short ushort2_t __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ uint32_t udot2(uint32_t a, uint32_t b, uint32_t c)
-{
-    return __builtin_amdgcn_udot2(__builtin_bit_cast(ushort2_t, a), __builtin_bit_cast(ushort2_t, b), c, false);
-}
-
 // Tiles: a workgroup is kWaves wavefronts that never cooperate; a wavefront owns kRows consecutive output rows x 256 pixels, a lane 4
 // consecutive pixels per row.  _crop_frames only ever scales UP (the crop lies inside the frame), so consecutive output rows advance by at
 // most one source row and the kRows output rows read at most kSrcRows source rows.

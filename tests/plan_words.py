@@ -9,8 +9,8 @@ REGION_STAGED = 0x80000000
 REGION_COMPACT = 0x20000000
 REGION_BORDER = 0x08000000
 REGION_ORIGIN_MASK = 0x007FFFFF
-GREY_PITCH = 80                 # the grey warp re-cuts a staged window only for frames of at least this many columns (warp_body.h)
-C4_COLS = 56                    # the 4-channel warp's re-cut window: this many columns, frames of at least as many (warp_body.h, MF_C4_COLS)
+GREY_PITCH = 80                 # the grey warp re-cuts a staged window only for frames of at least this many columns (warp_tails.h, MF_C1_PITCH)
+C4_COLS = 56                    # the 4-channel warp's re-cut window: this many columns, frames of at least as many (warp_tails.h, MF_C4_COLS)
 STAGE_PITCH, COMPACT_PITCH = 160, 112       # the plan's staged windows: bytes per row, wide and COMPACT (mf_common.h)
 
 

@@ -105,7 +105,7 @@ def test_resize_identity_and_2x_upscale():
 
 
 def test_fast_blend_rounds_inside_its_samples():
-    """The premise of the unclamped fast blend in warp.hip's remap_store_u16: the float32 chain ((s00 w0 + s01 w1) + s10 w2) + s11 w3
+    """The premise of the unclamped fast blend in warp_tails.h's remap_store_u16: the float32 chain ((s00 w0 + s01 w1) + s10 w2) + s11 w3
     rounds (half to even) into [min, max] of its four samples, so saturate_cast's clamp to 65535 never acts there.  Every (fx, fy) of
     the 32 x 32 weight table, every quadruple of samples from {0, 1, 65533, 65534, 65535}; a change of the blend order that breaks the
     premise fails here first."""

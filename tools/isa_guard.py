@@ -4,12 +4,12 @@ the instruction listing of one execution path of it (what used to be hand-kept u
     python tools/isa_guard.py [lib.so]                       checks; prints resources and what was verified; exit code 1 on a violation
     python tools/isa_guard.py [lib.so] --walk NNTN...        + every instruction a wavefront issues on ONE path: T / N per conditional branch met
 
-Why.  Two places in csrc/warp_body.h issue loads the COMPILER DOES NOT KNOW ABOUT:
-  * the speculative matrix load -- `s_load_dwordx16` + `s_load_dwordx2` from inline asm at the top of the kernel.  Scalar loads return
+Why.  Two places in the warp kernel's source issue loads the COMPILER DOES NOT KNOW ABOUT:
+  * the speculative matrix load (csrc/warp_body.h, footprint_body) -- `s_load_dwordx16` + `s_load_dwordx2` from inline asm at the top of the kernel.  Scalar loads return
     out of order and nothing tracks these two, so on EVERY path from them an `s_waitcnt lgkmcnt(0)` must come before the first instruction
     that WRITES one of their destination registers -- otherwise the late load overwrites the new value (round 5: about one corrupted
     launch in 200 in an instantiation where the registers were dead and had been handed to the plan words' loads).
-  * the byte taps -- runs of `ds_read_u8` / `ds_read_u8_d16_hi` inside one asm statement that ends with its own `s_waitcnt lgkmcnt(0)`: a
+  * the byte taps (csrc/warp_taps_u8c3.h) -- runs of `ds_read_u8` / `ds_read_u8_d16_hi` inside one asm statement that ends with its own `s_waitcnt lgkmcnt(0)`: a
     run must reach that wait with nothing but tap loads in between.
 And the kernel's occupancy rests on three numbers: zero scratch, <= 64 VGPRs (8 wavefronts per SIMD), <= 80 SGPRs (8 one-wavefront
 workgroups per CU, MI355X_MICROARCH.md).  A hipcc bump can break any of these silently; this turns it into a failing CPU test."""
