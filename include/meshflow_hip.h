@@ -222,7 +222,10 @@ int mf_warp_maps_bounds_f32(const void* d_table, float* d_maps, int n, int W, in
  * mf_warp_maps_f32: sx = cvRound(32 u), ix = sat_short(sx >> 5), fx = sx & 31 (the 8-bit path's quantisation), BilinearTab_f's exact float32
  * weights, t = ((S00 w0 + S01 w1) + S10 w2) + S11 w3 with every product and sum rounded on its own, out = t -- mf_warp_u16c3 on one channel
  * without saturate_cast.  A 2 x 2 footprint wholly outside the plane gives fill exactly, otherwise each outside tap is fill inside the sum;
- * a pixel no cell owns samples (W + 1, H + 1) and comes out as fill.  Non-finite samples get no special case.
+ * a pixel no cell owns samples (W + 1, H + 1) and comes out as fill.  Every operation is an IEEE binary32 operation rounded on its own,
+ * subnormals are kept, and no sample's value is looked at: all four products are always formed, so a tap of +-Inf or NaN with weight 0 gives
+ * NaN (0 * Inf) and with a positive weight +-Inf or NaN; an outside tap is fill inside the sum (an infinite fill with weight 0: NaN); a footprint
+ * wholly outside and an unowned pixel carry fill's own bits (-0.0 stays -0.0, a NaN fill gives a NaN).  A NaN's sign and payload are unspecified.
  * mf_warp_plane_nearest: cv2.remap(..., INTER_NEAREST, BORDER_CONSTANT) on elements of elem_bytes = 1, 2, 4 or 8 bytes: ix =
  * sat_short(cvRound(u)), iy = sat_short(cvRound(v)), float32 coordinates rounded half to even; the element is copied as bits where
  * 0 <= ix < W and 0 <= iy < H, otherwise the result is the low elem_bytes bytes of fill_bits.
@@ -239,7 +242,12 @@ int mf_warp_plane_nearest(const void* d_planes, void* d_out, const void* d_table
  * own call: out_W, out_H = W, H); d_out holds n * out_H * out_W elements.
  * mf_crop_resize_plane_f32: cv2.resize INTER_LINEAR on CV_32FC1 -- the index and fraction tables of mf_crop_resize_u8c3, float32 coefficients
  * (1 - f, f), t = S[sx] a0 + S[sx+1] a1, out = t0 b0 + t1 b1, float32, unfused: mf_crop_resize_to_u16c3 without saturate_cast; a crop exactly
- * twice the output in both axes takes INTER_AREA's fast path, (((S00 + S01) + S10) + S11) * 0.25f.
+ * twice the output in both axes takes INTER_AREA's fast path, (((S00 + S01) + S10) + S11) * 0.25f, in that order (the first sum may overflow).
+ * On non-finite samples, signed zeros and subnormals (kept, never flushed) it is cv::resize's code path by path: the output columns whose sx was
+ * clamped to the crop's last column are HResizeLinear's one-tap tail t = S[crop_w - 1] (an infinity there stays an infinity; the columns
+ * clamped on the left stay two-tap, S[0] * 1 + S[1] * 0), the vertical pass always has two taps (a row of weight 0 that holds an infinity
+ * gives NaN), and a crop of the output's own size is cv::resize's copy: the samples' bits, -0.0 and NaN payloads included, host and device
+ * rectangle alike.  Integer-valued and finite non-negative data cannot tell these from the plain two-tap arithmetic.
  * mf_crop_resize_plane_nearest: cv2.resize INTER_NEAREST on elements of elem_bytes = 1, 2, 4 or 8 bytes: sx = min(floor(x * (1.0 / (out_W /
  * crop_w))), crop_w - 1) in float64, the same for y, the element copied as bits.
  * d_work: mf_crop_resize_workspace_bytes(out_W, out_H) bytes (the tables).  mf_crop_resize_dev_plane_*: the rectangle read by the kernels from

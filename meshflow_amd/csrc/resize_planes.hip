@@ -25,7 +25,7 @@ int launch_crop_resize_plane(int elem_bytes, const void* planes, void* out, int 
     switch (elem_bytes) {
     case 0:
         hipLaunchKernelGGL(plane_resize_f32, grid, block, 0, st, (const float*)planes, (float*)out, W, H, left, top, cw, oW, oH,
-                           2 * oW == cw && 2 * oH == ch, xtab, ytab, order);
+                           plane_f32_path(cw, ch, oW, oH), xtab, ytab, order);
         break;
     case 1:
         hipLaunchKernelGGL(plane_resize_nearest<uint8_t>, grid, block, 0, st, (const uint8_t*)planes, (uint8_t*)out, W, H, left, top, cw, oW, oH,

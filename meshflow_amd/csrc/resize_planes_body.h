@@ -4,9 +4,14 @@
 //
 // float32, INTER_LINEAR (resize.cpp: HResizeLinear<float, float, float> + VResizeLinear<float, float, float, Cast<float, float>>): resize16_body.h
 // without saturate_cast -- the 8-bit index and fraction tables, float32 coefficients (1 - f, f),
-//   horizontal  t   = S[sx] a0 + S[sx+1] a1                               (float32, unfused)
-//   vertical    out = t0 b0 + t1 b1                                       (float32, unfused)
-// and, where the crop is exactly twice the output in both axes, INTER_AREA's fast path in its scalar order, (((S00 + S01) + S10) + S11) * 0.25f.
+//   horizontal  t   = S[sx] a0 + S[sx+1] a1                               (float32, unfused; the columns left of xmax)
+//               t   = S[cw-1]                                             (HResizeLinear's one-tap tail S * 1.0f from xmax on: the columns whose
+//                                                                          sx was clamped to the crop's last column -- no product with 0, so an
+//                                                                          infinity there stays an infinity)
+//   vertical    out = t0 b0 + t1 b1                                       (float32, unfused, always two taps)
+// where the crop is exactly twice the output in both axes, INTER_AREA's fast path in its scalar order, (((S00 + S01) + S10) + S11) * 0.25f,
+// and where the crop has the output's own size, cv::resize's `dsize == ssize` copy: the sample's bits (-0.0, NaN payloads), no arithmetic.
+// Nothing looks at a sample's value; subnormals are kept (the build flushes nothing); a weight of 0 does not exclude a tap.
 // Elements of 1, 2, 4 or 8 bytes, INTER_NEAREST (resizeNN): sx = min(floor(x * (1.0 / (oW / cw))), cw - 1) in float64, the same for y, and
 // the element copied as bits.
 // plane_resize_tables builds either pair of tables on the device in the workspace mf_crop_resize_workspace_bytes(oW, oH) sizes (8 bytes per
@@ -17,6 +22,21 @@
 #include "resize_rect.h"
 
 namespace mf {
+
+// which of cv::resize's three INTER_LINEAR routes a float32 crop of cw x ch takes to oW x oH
+enum PlanePath : int { PLANE_PATH_LINEAR = 0, PLANE_PATH_AREA = 1, PLANE_PATH_COPY = 2 };
+__host__ __device__ __forceinline__ int plane_f32_path(int cw, int ch, int oW, int oH)
+{
+    return cw == oW && ch == oH ? PLANE_PATH_COPY : 2 * oW == cw && 2 * oH == ch ? PLANE_PATH_AREA : PLANE_PATH_LINEAR;
+}
+// the host knows the rectangle and passes the route; a device rectangle decides it in the kernel (wavefront-uniform)
+#ifdef MF_RESIZE_DEV
+#define MF_PLANE_PATH_ARG
+#define MF_PLANE_PATH_LOAD const int path = plane_f32_path(cw, ch, oW, oH);
+#else
+#define MF_PLANE_PATH_ARG int path,
+#define MF_PLANE_PATH_LOAD
+#endif
 
 // nearest == 0: resize16_tables_kernel's tables (x: ofs = sx clamped into the crop, f = its fraction, 0 where clamped;  y: ofs = sy0 | sy1 << 16
 // of the clipped rows, f = the fraction);  nearest != 0: ofs = the one source column / row, f = 0
@@ -49,12 +69,14 @@ __global__ __launch_bounds__(256) void plane_resize_tables(MF_TABLES_ARGS, int n
     }
 }
 
-// `area`: 2 oW == cw and 2 oH == ch (the tables there give sx = 2 dx, sy0 = 2 dy, sy1 = 2 dy + 1: the four taps of the 2 x 2 block)
+// `path`: plane_f32_path.  PLANE_PATH_AREA: the tables give sx = 2 dx, sy0 = 2 dy, sy1 = 2 dy + 1, the four taps of the 2 x 2 block;
+// PLANE_PATH_COPY: they give sx = dx, sy0 = dy, and s0[0] is the sample itself
 __global__ __launch_bounds__(256) void plane_resize_f32(const float* __restrict__ planes, float* __restrict__ out, int W, int H,
-                                                        MF_RECT16_TO_ARGS, const Resize16Tab* __restrict__ xtab,
+                                                        MF_RECT_ARGS, int oW, int oH, MF_PLANE_PATH_ARG const Resize16Tab* __restrict__ xtab,
                                                         const Resize16Tab* __restrict__ ytab, TileOrder order)
 {
-    MF_RECT16_TO_LOAD(W, H)
+    MF_RECT_LOAD(W, H)
+    MF_PLANE_PATH_LOAD
     int f, y, tx;
     if (!order.decode(blockIdx.x, f, y, tx)) return;
     const int x = tx * 256 + (int)threadIdx.x;
@@ -66,18 +88,21 @@ __global__ __launch_bounds__(256) void plane_resize_f32(const float* __restrict_
     const float* __restrict__ p0 = src + (uint64_t)((uint32_t)(top + (yt.ofs & 0xFFFF)) * (uint32_t)W + sx);
     const float* __restrict__ p1 = src + (uint64_t)((uint32_t)(top + (yt.ofs >> 16)) * (uint32_t)W + sx);
     float s0[2], s1[2];                                          // columns sx and sx + 1 of rows sy0 and sy1
-    if (xt.ofs + 1 < cw) {
+    const bool two = xt.ofs + 1 < cw;                            // false from xmax on: the crop's last column, nothing to its right is read
+    if (two) {
         __builtin_memcpy(s0, p0, 8);
         __builtin_memcpy(s1, p1, 8);
-    } else {                                                     // the crop's last column: a1 = 0, nothing to its right is read
+    } else {
         s0[0] = s0[1] = p0[0];
         s1[0] = s1[1] = p1[0];
     }
     float o;
-    if (area) {
+    if (path == PLANE_PATH_COPY) {
+        o = s0[0];
+    } else if (path == PLANE_PATH_AREA) {
         o = (((s0[0] + s0[1]) + s1[0]) + s1[1]) * 0.25f;
     } else {
-        const float t0 = s0[0] * a0 + s0[1] * a1, t1 = s1[0] * a0 + s1[1] * a1;
+        const float t0 = two ? s0[0] * a0 + s0[1] * a1 : s0[0], t1 = two ? s1[0] * a0 + s1[1] * a1 : s1[0];      // (selects, no product with 0)
         o = t0 * b0 + t1 * b1;
     }
     out[(uint64_t)f * (uint64_t)((uint32_t)oW * (uint32_t)oH) + (uint64_t)((uint32_t)y * (uint32_t)oW + (uint32_t)x)] = o;
