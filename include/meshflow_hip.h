@@ -263,6 +263,29 @@ int mf_crop_resize_dev_plane_f32(const float* d_planes, float* d_out, int n, int
 int mf_crop_resize_dev_plane_nearest(const void* d_planes, void* d_out, int n, int W, int H, const int32_t* d_bounds, int out_W, int out_H,
                                      int elem_bytes, void* d_work, int32_t* d_status, void* stream);
 
+/* ---- NV12 clips: the 4:2:0 surfaces hardware decoders and encoders exchange -- a full-resolution luma plane and one interleaved
+ * half-resolution chroma plane -- warped from ONE cell table with the arrays the reference hands to cv2.remap at mfs.py:1063-1069, without a
+ * conversion to BGR and back.  A clip is two contiguous stacks: d_y [n][H][W] uint8 and d_uv [n][H/2][W/2][2] uint8, U first; W and H are even,
+ * 2 .. 32,767.  (Pitched surfaces and surfaces that keep a frame's two planes together are not taken: one plane stack per pointer.)
+ * Luma: d_out_y is byte for byte mf_warp_u8c1 of d_y with border border_yuv[0] -- that very launch; the per-frame crop values in d_crop, the
+ * clip rectangle and the ownership are that call's.
+ * Chroma: chroma is DEFINED as sited at the even luma sample: output chroma sample (cx, cy) of frame f takes the float32 map (u, v) of luma
+ * pixel (2 cx, 2 cy) -- exactly what mf_warp_maps_f32 returns for it, (W + 1, H + 1) for a pixel no cell owns included --, halves it in float32
+ * (uc = u * 0.5f, vc = v * 0.5f: exact) and applies cv2.remap's 8-bit fixed-point INTER_LINEAR with BORDER_CONSTANT to the (H/2, W/2)
+ * two-channel plane: sx = cvRound(32 uc), ix = sat_short(sx >> 5), fx = sx & 31 (the same in y), weights from the 2^15 table, out = (sum w s +
+ * 2^14) >> 15 per channel.  A 2 x 2 tap footprint wholly outside the plane gives (border_yuv[1], border_yuv[2]), otherwise each outside tap is
+ * that border sample inside the sum; an unowned pixel halves to ((W + 1) / 2, (H + 1) / 2), which lies outside the plane.  U and V never mix.
+ * (No quarter-pixel correction for left- or centre-sited chroma is applied.)  The chroma launch follows the luma launch on the same stream; it
+ * reads nothing outside the plane's bytes and touches neither d_crop nor the rectangle.  All plane offsets are 64-bit.
+ * border_yuv: {Y, U, V} as given; BT.601 limited-range red, the reference's default BGR (0, 0, 255), is (81, 90, 240).
+ * mf_warp_bounds_nv12: the rectangle in the caller's d_bounds[4], as mf_warp_bounds_u8c1.
+ * Refused with MF_ERR_INVALID_ARG before anything is launched: null pointers, n <= 0, any two of the four planes overlapping, an odd W or H, W
+ * or H outside 2 .. 32,767, R or C outside 1 .. 64, a d_uv or d_out_uv that is not 2-byte aligned. */
+int mf_warp_nv12(const uint8_t* d_y, const uint8_t* d_uv, uint8_t* d_out_y, uint8_t* d_out_uv, const void* d_table, int n, int W, int H,
+                 int R, int C, const uint8_t border_yuv[3], int32_t* d_crop, void* stream);
+int mf_warp_bounds_nv12(const uint8_t* d_y, const uint8_t* d_uv, uint8_t* d_out_y, uint8_t* d_out_uv, const void* d_table, int n, int W, int H,
+                        int R, int C, const uint8_t border_yuv[3], int32_t* d_crop, int32_t* d_bounds, void* stream);
+
 /* Clip-level crop bounds (mfs.py:1103-1106): {max left, max top, min right, min bottom} over n frames.
  * d_bounds: [4] int32. */
 int mf_crop_reduce(const int32_t* d_crop, int n, int W, int H, int32_t* d_bounds, void* stream);

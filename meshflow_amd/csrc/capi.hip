@@ -56,6 +56,37 @@ static int warp_maps_entry(const char* name, const void* d_table, float* d_maps,
                        (hipStream_t)stream);
 }
 
+// The checks of the two NV12 entries, then the grey warp of the luma planes (launch_warp's Px::U8C1 launches, unchanged) and the chroma launches
+// behind it on the same stream.  has_bounds: the clip-level rectangle goes to the caller's d_bounds instead of the table's.
+static int warp_nv12_entry(const char* name, const uint8_t* d_y, const uint8_t* d_uv, uint8_t* d_out_y, uint8_t* d_out_uv, const void* d_table,
+                           int n, int W, int H, int R, int C, const uint8_t* border_yuv, int32_t* d_crop, bool has_bounds, int32_t* d_bounds,
+                           void* stream)
+{
+    if (!d_y || !d_uv || !d_out_y || !d_out_uv || !d_table || !border_yuv || !d_crop || (has_bounds && !d_bounds)) {
+        set_error("%s: null pointer", name);
+        return MF_ERR_INVALID_ARG;
+    }
+    if (n <= 0) { set_error("%s: bad sizes", name); return MF_ERR_INVALID_ARG; }
+    if (W < 2 || H < 2 || W > 32767 || H > 32767) { set_error("%s: W=%d H=%d outside 2 .. 32,767", name, W, H); return MF_ERR_INVALID_ARG; }
+    if ((W | H) & 1) { set_error("%s: an NV12 frame has an even W and H, got W=%d H=%d", name, W, H); return MF_ERR_INVALID_ARG; }
+    if (R < 1 || C < 1 || R > 64 || C > 64) { set_error("%s: mesh R=%d C=%d outside 1 .. 64", name, R, C); return MF_ERR_INVALID_ARG; }
+    if ((((uintptr_t)d_uv | (uintptr_t)d_out_uv) & 1u) != 0) { set_error("%s: d_uv and d_out_uv must be 2-byte aligned", name); return MF_ERR_INVALID_ARG; }
+    // no two of the four plane stacks may share a byte
+    const size_t y_bytes = (size_t)n * W * H, uv_bytes = (size_t)n * nv12_uv_frame_bytes(W, H);
+    const struct { uintptr_t at; size_t bytes; const char* what; } pl[4] = {
+        { (uintptr_t)d_y, y_bytes, "d_y" }, { (uintptr_t)d_uv, uv_bytes, "d_uv" }, { (uintptr_t)d_out_y, y_bytes, "d_out_y" }, { (uintptr_t)d_out_uv, uv_bytes, "d_out_uv" } };
+    for (int i = 0; i < 4; ++i)
+        for (int j = i + 1; j < 4; ++j)
+            if (pl[i].at < pl[j].at + pl[j].bytes && pl[j].at < pl[i].at + pl[i].bytes) {
+                set_error("%s: %s and %s alias", name, pl[i].what, pl[j].what);
+                return MF_ERR_INVALID_ARG;
+            }
+    TableView tv = table_view(const_cast<void*>(d_table), n, W, H, R, C);
+    if (has_bounds) tv.bounds = d_bounds;
+    if (const int rc = launch_warp(Px::U8C1, d_y, d_out_y, tv, n, W, H, R, C, pack_border(Px::U8C1, border_yuv), d_crop, (hipStream_t)stream)) return rc;
+    return launch_warp(Px::NV12_UV, d_uv, d_out_uv, tv, n, W, H, R, C, pack_border(Px::NV12_UV, border_yuv + 1), d_crop, (hipStream_t)stream);
+}
+
 // The element checks every plane entry shares: elem_bytes is 0 (the float32 calls) or 1, 2, 4, 8, and both pointers are aligned to the element
 static bool plane_elem_ok(const char* name, int elem_bytes, const void* d_planes, const void* d_out)
 {
@@ -257,6 +288,18 @@ int mf_warp_plane_nearest(const void* d_planes, void* d_out, const void* d_table
 {
     if (elem_bytes == 0) elem_bytes = -1;           // (0 is warp_plane_entry's word for the float32 call)
     return warp_plane_entry("mf_warp_plane_nearest", elem_bytes, d_planes, d_out, d_table, n, W, H, R, C, fill_bits, d_crop, d_bounds, stream);
+}
+
+int mf_warp_nv12(const uint8_t* d_y, const uint8_t* d_uv, uint8_t* d_out_y, uint8_t* d_out_uv, const void* d_table, int n, int W, int H,
+                 int R, int C, const uint8_t border_yuv[3], int32_t* d_crop, void* stream)
+{
+    return warp_nv12_entry("mf_warp_nv12", d_y, d_uv, d_out_y, d_out_uv, d_table, n, W, H, R, C, border_yuv, d_crop, false, nullptr, stream);
+}
+
+int mf_warp_bounds_nv12(const uint8_t* d_y, const uint8_t* d_uv, uint8_t* d_out_y, uint8_t* d_out_uv, const void* d_table, int n, int W, int H,
+                        int R, int C, const uint8_t border_yuv[3], int32_t* d_crop, int32_t* d_bounds, void* stream)
+{
+    return warp_nv12_entry("mf_warp_bounds_nv12", d_y, d_uv, d_out_y, d_out_uv, d_table, n, W, H, R, C, border_yuv, d_crop, true, d_bounds, stream);
 }
 
 // ---- the same three calls with the clip-level rectangle in the CALLER's d_bounds[4] instead of inside the table blob ----

@@ -236,9 +236,12 @@ inline bool make_tile_order(int tiles_x, int tiles_y, int n, TileOrder& o)
 // Px::PLANE_*: no picture either -- the side planes [n][H][W] that travel with a video (mf_warp_plane_f32, mf_warp_plane_nearest,
 // warp_planes.hip): float32 sampled like cv2.remap INTER_LINEAR of CV_32FC1, or elements of 1, 2, 4 or 8 bytes copied as bits like
 // INTER_NEAREST.  One channel of px_sample_bytes bytes; the pixel calls (launch_crop_resize*, the clip and host pipelines) never see them.
-enum class Px { U8C3, U16C3, U8C1, U8C4, MAPS, PLANE_F32, PLANE_N1, PLANE_N2, PLANE_N4, PLANE_N8 };
+// Px::NV12_UV: the interleaved half-resolution chroma plane of an NV12 clip (mf_warp_nv12, warp_nv12.hip): [n][H/2][W/2] pixels of two bytes,
+// U first, sampled at half the luma coordinates of the even luma pixels.  W and H stay the LUMA frame's everywhere (the cell table's); only
+// launch_warp's frame stride (nv12_uv_frame_bytes) and the kernel's tail know the plane's own size.  The luma plane is a Px::U8C1 stack.
+enum class Px { U8C3, U16C3, U8C1, U8C4, MAPS, PLANE_F32, PLANE_N1, PLANE_N2, PLANE_N4, PLANE_N8, NV12_UV };
 constexpr bool px_is_plane(Px p) { return p == Px::PLANE_F32 || p == Px::PLANE_N1 || p == Px::PLANE_N2 || p == Px::PLANE_N4 || p == Px::PLANE_N8; }
-constexpr int px_channels(Px p) { return p == Px::U8C1 || px_is_plane(p) ? 1 : p == Px::U8C4 ? 4 : p == Px::MAPS ? 2 : 3; }
+constexpr int px_channels(Px p) { return p == Px::U8C1 || px_is_plane(p) ? 1 : p == Px::U8C4 ? 4 : p == Px::MAPS || p == Px::NV12_UV ? 2 : 3; }
 constexpr int px_sample_bytes(Px p)
 {
     return p == Px::U16C3 || p == Px::PLANE_N2 ? 2 : p == Px::MAPS || p == Px::PLANE_F32 || p == Px::PLANE_N4 ? 4 : p == Px::PLANE_N8 ? 8 : 1;
@@ -247,10 +250,12 @@ constexpr int px_bytes(Px p) { return px_channels(p) * px_sample_bytes(p); }
 constexpr const char* px_name(Px p)
 {
     return p == Px::U8C3 ? "u8c3" : p == Px::U16C3 ? "u16c3" : p == Px::U8C1 ? "u8c1" : p == Px::U8C4 ? "u8c4" : p == Px::MAPS ? "maps_f32" :
-           p == Px::PLANE_F32 ? "plane_f32" : "plane_nearest";
+           p == Px::PLANE_F32 ? "plane_f32" : p == Px::NV12_UV ? "nv12_uv" : "plane_nearest";
 }
+// bytes of one frame's chroma plane of an NV12 clip of W x H luma pixels (W, H even): (W / 2) (H / 2) pixels of 2 bytes
+constexpr size_t nv12_uv_frame_bytes(int W, int H) { return (size_t)(W / 2) * (size_t)(H / 2) * 2u; }
 // The border colour as the warp kernels take it, from the caller's px_channels(p) samples: B | G << 8 | R << 16 (u8c3),
-// B | G << 16 | R << 32 (u16c3), the byte (u8c1), B | G << 8 | R << 16 | A << 24 (u8c4).
+// B | G << 16 | R << 32 (u16c3), the byte (u8c1), B | G << 8 | R << 16 | A << 24 (u8c4), U | V << 8 (nv12_uv).
 inline uint64_t pack_border(Px p, const void* samples)
 {
     uint64_t v = 0;
@@ -291,6 +296,7 @@ void launch_warp8c1_range(const WarpGeom& g, const WarpRange& r, int W, int H, i
 void launch_warp8c4_range(const WarpGeom& g, const WarpRange& r, int W, int H, int C, uint32_t border, bool stage, hipStream_t st);  // warp_c4.hip
 void launch_maps_range(const WarpGeom& g, const WarpRange& r, int W, int H, int C, hipStream_t st);  // warp_maps.hip (r.frames unused, r.out: float32 maps)
 void launch_plane_range(Px px, const WarpGeom& g, const WarpRange& r, int W, int H, int C, uint64_t fill, hipStream_t st);  // warp_planes.hip (fill: the element's bits)
+void launch_nv12_chroma_range(const WarpGeom& g, const WarpRange& r, int W, int H, int C, uint32_t border_uv, hipStream_t st);  // warp_nv12.hip (r.crop, r.bounds unused)
 int launch_crop_scan(const TableView& tv, int n, int W, int H, int R, int C, int32_t* crop, hipStream_t st);
 int check_d16_zero_fill(hipStream_t st);          // warp.hip: one-time device check the byte-tap kernels rely on
 int launch_selftest_recip(unsigned long long n, unsigned long long seed, unsigned long long* d_mismatches, hipStream_t st);

@@ -1,4 +1,4 @@
-// What the warp translation units share (warp.hip, warp_c1.hip, warp_c4.hip, warp_maps.hip, warp_planes.hip): footprint_body and the blocks its
+// What the warp translation units share (warp.hip, warp_c1.hip, warp_c4.hip, warp_maps.hip, warp_planes.hip, warp_nv12.hip): footprint_body and the blocks its
 // paths share.  The constants and the coordinate code are in warp_coords.h, the uint8 BGR taps and blend in warp_taps_u8c3.h, the other
 // formats' tails in warp_tails.h; the units include this header only.  The design note is at the head of warp.hip.
 #ifndef MF_WARP_BODY_H
@@ -98,6 +98,7 @@ __device__ __forceinline__ void store_tail(const float (&u)[4], const float (&v)
                                            int32_t* __restrict__ crop, int32_t* __restrict__ clip, const GreyWindow& win, const uint8_t* s_win)
 {
     if constexpr (PX == Px::MAPS) maps_store_f32(u, v, f, x0, y, active, W, H, reinterpret_cast<float*>(out));
+    else if constexpr (PX == Px::NV12_UV) remap_store_nv12_uv(u, v, f, x0, y, active, W, H, frames, out, border);
     else if constexpr (px_is_plane(PX)) remap_store_plane<PX, SCAN>(u, v, f, x0, y, active, W, H, frames, out, border16, crop, clip);
     else if constexpr (PX == Px::U16C3)
         remap_store_u16(u, v, f, x0, y, active, W, H, reinterpret_cast<const uint16_t*>(frames), reinterpret_cast<uint16_t*>(out), border16, crop, clip);
@@ -132,6 +133,10 @@ __device__ __forceinline__ void store_bgr4(uint8_t* __restrict__ dst, int W, int
 // PX = Px::PLANE_*: the side planes (plane_footprint, warp_planes.hip): `frames` / `out` hold W H elements of px_sample_bytes(PX) bytes per
 // frame, `border16` is the fill value's bit pattern, and the pixels go through remap_store_plane -- taps from global memory like the uint16
 // warp (the plan's windows are cut for 3-byte pixels), the hot and pair shortcuts like the maps (they need no window), the general path for the rest.
+// PX = Px::NV12_UV: the chroma plane of an NV12 clip (nv12_chroma_footprint, warp_nv12.hip) on the LUMA frame's plan: W, H, the footprints, the
+// ownership and the coordinates are the luma frame's -- the maps kernel's paths, so (u, v) are its values bit for bit --, `frames` / `out` hold
+// (W / 2) (H / 2) pixels of two bytes per frame, the border is U | V << 8 in `border`, and the pixels go through remap_store_nv12_uv, which halves
+// the coordinates of the even luma pixels.  Taps from global memory; `crop` / `clip` are never touched (null: the luma launch owns them).
 template <Px PX, bool STAGE, bool SCAN>
 __device__ __forceinline__ void footprint_body(const uint32_t f, const uint32_t t, const FootPlan* __restrict__ plan, const FootRegion* __restrict__ regions,
                                                const WarpGeom& g, const uint8_t* __restrict__ frames,
@@ -150,8 +155,8 @@ __device__ __forceinline__ void footprint_body(const uint32_t f, const uint32_t 
     constexpr bool MAPS = PX == Px::MAPS;
     static_assert(!MAPS || (!STAGE && !SCAN), "the maps kernel reads no frame: nothing to stage");
     // NOWIN: the instantiations that take the hot and pair shortcuts without a window (the maps read no frame, the planes tap global memory)
-    constexpr bool PLANE = px_is_plane(PX), NOWIN = MAPS || PLANE;
-    static_assert(!PLANE || (!STAGE && !SCAN), "the plane warps take their taps from global memory");
+    constexpr bool PLANE = px_is_plane(PX), NV12 = PX == Px::NV12_UV, NOWIN = MAPS || PLANE || NV12;
+    static_assert(!(PLANE || NV12) || (!STAGE && !SCAN), "the plane and chroma warps take their taps from global memory");
     // inverse homographies of the footprint's candidate cells: [entry][Hi0..Hi8, pad] (80-byte rows)
     __shared__ __attribute__((aligned(16))) double s_hi[1][9][10];                // row 8: the "no cell" matrix, see OWN_NONE
     // source region of the footprint: MF_STAGE_ROWS rows of MF_STAGE_PITCH bytes (+ slack for the third dword of the last tap); the 4-byte

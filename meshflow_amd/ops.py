@@ -452,6 +452,62 @@ def warp_planes(planes, table, interpolation='linear', fill=0, out=None, bounds=
     return out
 
 
+# BT.601 limited-range red: what the reference's default border, BGR (0, 0, 255), is in Y, U, V
+NV12_BORDER_RED = (81, 90, 240)
+_nv12_border = _border_samples(ctypes.c_uint8, 255, 3)
+
+
+def _nv12_plane(t, name, shape, device):
+    """One plane stack of an NV12 clip: a contiguous uint8 device tensor of exactly `shape` on `device` (None: wherever it is)."""
+    _need(t, torch.uint8, name)
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError(f'{name} must have shape {tuple(shape)}, got {tuple(t.shape)}')
+    if device is not None and t.device != device:
+        raise ValueError(f'{name} must be on the device of y, {device}, got {t.device}')
+
+
+def warp_nv12(y, uv, table, border_yuv=NV12_BORDER_RED, out=None, bounds=None):
+    """The mesh warp of an NV12 clip -- the 4:2:0 surfaces decoders and encoders exchange -- from one cell table, without a conversion to BGR and
+    back (mf_warp_nv12; the arrays the reference hands to cv2.remap at mfs.py:1063-1069).  y: (n, H, W) uint8 luma, uv: (n, H/2, W/2, 2) uint8
+    interleaved chroma, U first; both contiguous device tensors, W and H even, n == table.n.  (Pitched surfaces, or one tensor that holds a
+    frame's two planes together, are not taken: one plane stack per tensor.)
+    Luma is byte for byte `warp(y, table, (border_yuv[0],))` -- that very launch: the per-frame crop values in table.crop and the clip-level
+    rectangle in `bounds` / table.clip_bounds are its.  Chroma is DEFINED as sited at the even luma sample: output chroma sample (cx, cy) takes
+    `warp_maps(table)[f, 2 cy, 2 cx]`, halves it in float32 and samples the (H/2, W/2) two-channel plane like cv2.remap's 8-bit INTER_LINEAR with
+    BORDER_CONSTANT; where the source lies outside the plane, and where no cell owns the luma pixel, the result is (border_yuv[1], border_yuv[2]).
+    No quarter-pixel correction for left- or centre-sited chroma is applied.
+    border_yuv: (Y, U, V), each clamp(round(v), 0, 255).  The default (81, 90, 240) is BT.601 limited-range red, i.e. the reference's default
+    BGR (0, 0, 255).  out: an (out_y, out_uv) pair to fill.  Returns (out_y, out_uv)."""
+    _need(y, torch.uint8, 'y')
+    if y.dim() != 3:
+        raise ValueError(f'y must be (n, H, W) luma planes, got shape {tuple(y.shape)}')
+    n, H, W = (int(v) for v in y.shape)
+    if W % 2 or H % 2:
+        raise ValueError(f'an NV12 frame has an even width and height, got W={W} H={H}')
+    _nv12_plane(uv, 'uv', (n, H // 2, W // 2, 2), y.device)
+    if (n, W, H) != (table.n, table.W, table.H):
+        raise ValueError(f'y {tuple(y.shape)} does not match the cell table (n, H, W) = {(table.n, table.H, table.W)}')
+    if len(border_yuv) != 3:
+        raise ValueError(f'border_yuv must be (Y, U, V), got {border_yuv!r}')
+    if out is None:
+        out_y, out_uv = torch.empty_like(y), torch.empty_like(uv)
+    else:
+        if not isinstance(out, (tuple, list)) or len(out) != 2:
+            raise ValueError('out must be a pair (out_y, out_uv)')
+        out_y, out_uv = out
+        _nv12_plane(out_y, 'out_y', y.shape, y.device)
+        _nv12_plane(out_uv, 'out_uv', uv.shape, y.device)
+    border = _nv12_border(border_yuv)
+    if bounds is None:
+        _lib.check(_lib_.mf_warp_nv12(_ptr(y), _ptr(uv), _ptr(out_y), _ptr(out_uv), _ptr(table.buf), n, W, H, table.R, table.C, border,
+                                      _ptr(table.crop), _stream()))
+    else:
+        _need_bounds(bounds)
+        _lib.check(_lib_.mf_warp_bounds_nv12(_ptr(y), _ptr(uv), _ptr(out_y), _ptr(out_uv), _ptr(table.buf), n, W, H, table.R, table.C, border,
+                                             _ptr(table.crop), _ptr(bounds), _stream()))
+    return out_y, out_uv
+
+
 def crop_resize_planes(planes, bounds, interpolation='linear', size=None, out=None, status=None):
     """`crop_resize` for side planes (mfs.py:1111-1157 on a plane; mf_crop_resize_plane_* / mf_crop_resize_dev_plane_*): crop to the inclusive
     {left, top, right, bottom} and scale to `size` = (width, height), by default back to (W, H).  planes and interpolation as in

@@ -886,6 +886,33 @@ class MeshFlowStabilizer:
         cropped, _ = ops.crop_resize_planes(warped, bounds, interpolation, size=output_size, out=out)
         return cropped, bounds
 
+    def stabilized_nv12(self, d_y, d_uv, d_disp, homographies, border_yuv=(81, 90, 240), out=None,
+                        adaptive_weights_definition=ADAPTIVE_WEIGHTS_DEFINITION_ORIGINAL):
+        """An NV12 clip that a decoder left in device memory -- d_y (F, H, W) uint8 luma, d_uv (F, H/2, W/2, 2) uint8 interleaved chroma, U
+        first -- stabilized without ever becoming BGR: the Jacobi sweep (mfs.py:695-704) on d_disp, the cell table + plan of all F frames, then
+        `ops.warp_nv12`; like `stabilized_planes`, everything on torch's current stream.  Luma moves exactly as a grey clip does, chroma is
+        sampled at half the luma coordinates of the even luma pixels (`ops.warp_nv12` has the definition).  border_yuv: (Y, U, V) of the
+        uncovered area, by default BT.601 limited-range red (81, 90, 240) -- the reference's default BGR (0, 0, 255).  out: an
+        (out_y, out_uv) pair to fill.  Returns (out_y, out_uv, bounds): bounds = int32[4] device tensor {left, top, right, bottom}, the
+        rectangle `stabilization_maps` returns for the same inputs.  A degenerate mesh raises `DegenerateMeshError` (clip_serial None) here,
+        synchronously, before a plane is written."""
+        import torch
+        from . import ops
+        self._check_definition(adaptive_weights_definition)
+        self._check_mesh_shape(d_disp, d_disp.shape[0])
+        ops._need(d_y, torch.uint8, 'd_y')
+        if d_y.dim() != 3:
+            raise ValueError(f'd_y must be (F, H, W) luma planes, got shape {tuple(d_y.shape)}')
+        H, W = int(d_y.shape[1]), int(d_y.shape[2])
+        d_stab = self._stabilized_vertex_displacements_device(d_disp, W, H, adaptive_weights_definition, homographies)
+        bounds = torch.empty(4, dtype=torch.int32, device=d_disp.device)
+        table = ops.cell_table(d_disp, d_stab, W, H, self.mesh_row_count, self.mesh_col_count, bounds=bounds)
+        bad = int(table.status.item())
+        if bad:
+            raise DegenerateMeshError(bad, None)
+        out_y, out_uv = ops.warp_nv12(d_y, d_uv, table, border_yuv, out=out, bounds=bounds)
+        return out_y, out_uv, bounds
+
     def _stabilized_frames_device(self, d_frames, d_unstab, d_stab, out=None, table=None):
         """d_frames: (n, H, W, 3) uint8; d_unstab/d_stab: (n, R+1, C+1, 2) float64, all in HBM.
         Returns (stabilized frames (n, H, W, 3) uint8, per-frame crop values (n, 4) int32), in HBM.
