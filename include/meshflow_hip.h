@@ -348,6 +348,30 @@ int mf_crop_resize_dev_u8c1(const uint8_t* d_frames, uint8_t* d_out, int n, int 
                             void* d_work, int32_t* d_status, void* stream);
 int mf_crop_resize_dev_u8c4(const uint8_t* d_frames, uint8_t* d_out, int n, int W, int H, const int32_t* d_bounds, int out_W, int out_H,
                             void* d_work, int32_t* d_status, void* stream);
+/* _crop_frames (mfs.py:1111-1157) for an NV12 clip -- d_y [n][H][W], d_uv [n][H/2][W/2][2], U first, as mf_warp_nv12 takes them -- to d_out_y
+ * [n][out_H][out_W] and d_out_uv [n][out_H/2][out_W/2][2], without a conversion to BGR and back.  W, H, out_W and out_H are even, 2 .. 32,767;
+ * the rectangle is inclusive, in luma pixels, of any parity.  DEFINED here, modelled on cv2.resize, not pinned (like mf_warp_nv12's chroma).
+ * Luma: d_out_y is byte for byte mf_crop_resize_to_u8c1 of d_y (mf_crop_resize_dev_u8c1 for the device rectangle) -- that very launch.
+ * Chroma is sited at the even luma sample: output chroma sample cx sits on output luma pixel 2 cx, and its source is that pixel's luma source
+ * position, made absolute in the frame and halved.  With cw = right - left + 1, scale_x = 1.0 / ((double)out_W / (double)cw) (the luma tables'
+ * value), c1 = right >> 1 and c0 = min((left + 1) >> 1, c1) -- the chroma samples whose siting luma pixel lies inside the crop --:
+ *   fc = (float)(((double)left + (((double)(2 cx) + 0.5) * scale_x - 0.5)) * 0.5);  s = floor(fc);  f = fc - (float)s
+ *   s < c0 -> (s, f) = (c0, 0);  s >= c1 -> (c1, 0);  a0 = cvRound((1 - f) * 2048), a1 = cvRound(f * 2048)
+ * the y axis the same with top, bottom, out_H and cy, except that (as in cv2) the two row indices are clipped to [r0, r1] and the weights kept.
+ * Then mf_crop_resize_u8c3's two passes per channel: t = S[s] a0 + S[s+1] a1, out = (((b0 (t0 >> 4)) >> 16) + ((b1 (t1 >> 4)) >> 16) + 2) >> 2.
+ * U and V never mix; no INTER_AREA special case.  Nothing outside columns c0 .. c1 and rows r0 .. r1 of the frame's own chroma plane influences
+ * the result, and no byte outside the d_uv stack is read.  The full-frame rectangle at out_W x out_H == W x H is a copy of d_uv.
+ * d_work: mf_crop_resize_nv12_workspace_bytes(out_W, out_H) bytes (the luma tables, then the chroma tables).  The luma launch goes first, then
+ * chroma, on the same stream.  mf_crop_resize_dev_nv12: the rectangle read from d_bounds when the kernels execute; one that cannot be used adds
+ * exactly 1 to *d_status and leaves both outputs and the workspace untouched (d_status as in mf_crop_resize_dev_u8c3).
+ * Refused with MF_ERR_INVALID_ARG before anything is launched: null pointers, n <= 0, any two of the four plane stacks overlapping, an odd W, H,
+ * out_W or out_H or one outside 2 .. 32,767, a d_uv or d_out_uv that is not 2-byte aligned, too many tiles, and (host rectangle) an empty or
+ * out-of-frame rectangle. */
+size_t mf_crop_resize_nv12_workspace_bytes(int out_W, int out_H);
+int mf_crop_resize_nv12(const uint8_t* d_y, const uint8_t* d_uv, uint8_t* d_out_y, uint8_t* d_out_uv, int n, int W, int H, int left, int top,
+                        int right, int bottom, int out_W, int out_H, void* d_work, void* stream);
+int mf_crop_resize_dev_nv12(const uint8_t* d_y, const uint8_t* d_uv, uint8_t* d_out_y, uint8_t* d_out_uv, int n, int W, int H,
+                            const int32_t* d_bounds, int out_W, int out_H, void* d_work, int32_t* d_status, void* stream);
 
 /* ---- the row before the path: vertex-motion accumulation (mfs.py:236-452 from the matched features on) ----
  * Replaces the Python loops of _get_vertex_nearby_feature_residual_velocities (mfs.py:365-452), the medians, global

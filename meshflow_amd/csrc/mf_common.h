@@ -342,6 +342,15 @@ int launch_crop_resize_plane(int elem_bytes, const void* planes, void* out, int 
                              int oW, int oH, void* work, hipStream_t st);
 int launch_crop_resize_plane_dev(int elem_bytes, const void* planes, void* out, int n, int W, int H, const int32_t* d_bounds, int oW, int oH,
                                  void* work, int32_t* d_status, hipStream_t st);
+// resize_uv.hip / resize_uv_dev.hip: the chroma half of mf_crop_resize_nv12 / mf_crop_resize_dev_nv12 (W, H, oW, oH and the rectangle are the
+// LUMA frame's; `tabs`: the chroma tables' part of the workspace, behind the luma tables) -- resize_uv_body.h's tables, then its kernel.  The
+// calls' checks are capi.hip's; resize_uv_tile_order: the kernel's tiles (false: too many).
+size_t crop_resize_nv12_workspace_bytes(int oW, int oH);
+bool resize_uv_tile_order(int oW, int oH, int n, TileOrder& order);
+int launch_resize_uv(const uint8_t* uv, uint8_t* out_uv, int W, int H, int left, int top, int right, int bottom, int oW, int oH, void* tabs,
+                     const TileOrder& order, hipStream_t st);
+int launch_resize_uv_dev(const uint8_t* uv, uint8_t* out_uv, int W, int H, const int32_t* d_bounds, int oW, int oH, void* tabs,
+                         const TileOrder& order, hipStream_t st);
 size_t vertex_motion_workspace_bytes(int total_features, int max_per_pair, int P, int R, int C);
 int launch_vertex_motion(const double* early, const double* late, const int32_t* offsets, const double* hom, int P,
                          int total_features, int max_per_pair, int W, int H, int R, int C, int ell_rows, int ell_cols,

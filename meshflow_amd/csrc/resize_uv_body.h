@@ -1,0 +1,143 @@
+// Crop + resize of the interleaved chroma plane of an NV12 clip: uv [n][H/2][W/2][2] uint8, U first, to out_uv [n][oH/2][oW/2][2] -- the chroma
+// half of mf_crop_resize_nv12 / mf_crop_resize_dev_nv12 (the luma half is the u8c1 crop-resize as it is).  W, H, oW, oH and the rectangle
+// {left, top, right, bottom} (inclusive, any parity) are the LUMA frame's everywhere.
+//
+// Chroma is sited at the even luma sample, as in the NV12 warp: output chroma sample cx sits on output luma pixel 2 cx; its source is that
+// pixel's luma source position (cv2.resize's, resize_body.h), made absolute in the frame and halved:
+//   scale = 1 / ((double)oW / cw)                                              (the luma tables' own value)
+//   fc = float((left + ((2 cx + 0.5) scale - 0.5)) 0.5);  s = floor(fc);  f = fc - s
+//   c1 = right >> 1,  c0 = min((left + 1) >> 1, c1)                            (the chroma samples whose siting luma pixel lies in the crop)
+//   x axis: s < c0 -> (c0, 0);  s >= c1 -> (c1, 0)        y axis: the two row indices are clipped to [r0, r1] instead, the weights kept
+//   weights  a0 = cvRound((1 - f) 2048), a1 = cvRound(f 2048)
+//   horizontal  t   = S[s] a0 + S[s+1] a1                                      per channel; U and V never mix
+//   vertical    out = (((b0 (t0 >> 4)) >> 16) + ((b1 (t1 >> 4)) >> 16) + 2) >> 2
+// chroma_tables_kernel builds the oW/2 + oH/2 entries on the device (the offsets are ABSOLUTE chroma columns and rows of the plane), for the
+// host rectangle too: the tables depend on the parity of left and top, and both paths are one code.  chroma_resize_kernel applies them: a lane
+// owns 4 consecutive chroma samples of a row (one 8-byte store), a wavefront 256 samples x kUvRows rows; taps straight from the plane, no LDS.
+// Where s + 1 <= c1 the two taps of a row are ONE 4-byte load at 2-byte alignment (U0 V0 U1 V1), split by v_perm_b32 and blended by
+// v_dot2_u32_u16 / v_mul_hi_u32_u24 as resize_u8.h does it; where s == c1 (a1 == 0) only the 2-byte sample is read, so nothing right of column
+// c1 -- and never a byte behind the stack -- is touched.
+// Device code only, written against resize_rect.h's macros: resize_uv.hip compiles it with the rectangle as launch arguments, resize_uv_dev.hip
+// a second time under MF_RESIZE_DEV and other names, with the rectangle read from device memory.  An unusable device rectangle: both kernels
+// return before they read or write anything; *d_status is the luma tables kernel's to raise, once per call.
+#ifndef MF_RESIZE_UV_BODY_H
+#define MF_RESIZE_UV_BODY_H
+#include "mf_common.h"
+#include "resize_u8.h"
+#include "resize_rect.h"
+
+namespace mf {
+
+constexpr int kUvRows = 4;            // output chroma rows per wavefront
+
+// the tables kernel needs all four edges (MF_RECT_ARGS carries left, top, cw only)
+#ifdef MF_RESIZE_DEV
+#define MF_UV_TABLES_ARGS const int32_t* __restrict__ d_bounds, int frame_W, int frame_H
+#define MF_UV_TABLES_LOAD MF_RECT_LOAD(frame_W, frame_H)
+#else
+#define MF_UV_TABLES_ARGS int left, int top, int rect_right, int rect_bottom
+#define MF_UV_TABLES_LOAD const int cw = rect_right - left + 1, ch = rect_bottom - top + 1;
+#endif
+
+// x: ofs = s (absolute chroma column, clamped into c0 .. c1), w = 16 a0 | 16 a1 << 16;  y: ofs = sy0 | sy1 << 16 (absolute chroma rows, clipped
+// into r0 .. r1), w = b0 | b1 << 16 -- resize_tables_kernel's layout
+__global__ __launch_bounds__(256) void chroma_tables_kernel(MF_UV_TABLES_ARGS, int oW, int oH, ResizeTab* __restrict__ xtab,
+                                                            ResizeTab* __restrict__ ytab)
+{
+    MF_UV_TABLES_LOAD
+    const double scale_x = 1.0 / ((double)oW / (double)cw), scale_y = 1.0 / ((double)oH / (double)ch);
+    const int c1 = rect_right >> 1, c0 = min((left + 1) >> 1, c1);
+    const int r1 = rect_bottom >> 1, r0 = min((top + 1) >> 1, r1);
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < (oW >> 1)) {
+        float fx = (float)(((double)left + (((double)(2 * i) + 0.5) * scale_x - 0.5)) * 0.5);
+        int sx = (int)floorf(fx);
+        fx -= (float)sx;
+        if (sx < c0) { fx = 0.0f; sx = c0; }
+        if (sx >= c1) { fx = 0.0f; sx = c1; }
+        const int a0 = (int)rintf((1.0f - fx) * 2048.0f), a1 = (int)rintf(fx * 2048.0f);
+        xtab[i].ofs = sx;
+        xtab[i].w = ((uint32_t)a0 << 4) | ((uint32_t)a1 << 20);
+    }
+    if (i < (oH >> 1)) {
+        float fy = (float)(((double)top + (((double)(2 * i) + 0.5) * scale_y - 0.5)) * 0.5);
+        const int sy = (int)floorf(fy);
+        fy -= (float)sy;
+        const int b0 = (int)rintf((1.0f - fy) * 2048.0f), b1 = (int)rintf(fy * 2048.0f);
+        const int sy0 = min(max(sy, r0), r1), sy1 = min(max(sy + 1, r0), r1);
+        ytab[i].ofs = sy0 | (sy1 << 16);
+        ytab[i].w = (uint32_t)b0 | ((uint32_t)b1 << 16);
+    }
+}
+
+// U0 | V0 << 8 | U1 << 16 | V1 << 24 of samples s and s + 1 at p (two), or U0 | V0 << 8 of sample s alone
+__device__ __forceinline__ uint32_t load_uv_taps(const uint8_t* __restrict__ p, bool two)
+{
+    uint32_t v;
+    if (two) __builtin_memcpy(&v, __builtin_assume_aligned(p, 2), 4);
+    else v = *reinterpret_cast<const uint16_t*>(p);
+    return v;
+}
+
+__global__ __launch_bounds__(64 * kWaves) void chroma_resize_kernel(const uint8_t* __restrict__ uv, uint8_t* __restrict__ out, int W, int H,
+                                                                    MF_RECT_ARGS, int oW, int oH, const ResizeTab* __restrict__ xtab,
+                                                                    const ResizeTab* __restrict__ ytab, TileOrder order)
+{
+    MF_RECT_LOAD(W, H)
+    (void)top;                                                    // (the tables hold absolute rows)
+    int f, tile_y, tile_x;
+    if (!order.decode(blockIdx.x, f, tile_y, tile_x)) return;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const int CW = W >> 1, CH = H >> 1, oCW = oW >> 1, oCH = oH >> 1;
+    const int ya = (tile_y * kWaves + wave) * kUvRows;
+    const int x0 = tile_x * 256 + lane * 4;
+    if (ya >= oCH || x0 >= oCW) return;
+    const int c1 = (left + cw - 1) >> 1;                           // the crop's last chroma column: nothing to its right is read
+    const uint8_t* __restrict__ src = uv + (uint64_t)f * (2ull * (uint64_t)((uint32_t)CW * (uint32_t)CH));
+    uint8_t* __restrict__ dst = out + (uint64_t)f * (2ull * (uint64_t)((uint32_t)oCW * (uint32_t)oCH));
+    uint32_t at[4], w[4];
+    bool two[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const ResizeTab xt = xtab[min(x0 + j, oCW - 1)];
+        at[j] = 2u * (uint32_t)xt.ofs;
+        w[j] = xt.w;
+        two[j] = xt.ofs < c1;
+    }
+#pragma unroll
+    for (int q = 0; q < kUvRows; ++q) {
+        const int y = ya + q;
+        if (y >= oCH) break;
+        const ResizeTab yt = ytab[y];
+        const uint32_t b0s = (yt.w & 0xFFFFu) << 8, b1s = (yt.w >> 16) << 8;
+        const uint8_t* __restrict__ p0 = src + (uint32_t)(yt.ofs & 0xFFFF) * (uint32_t)CW * 2u;       // (a plane is below 2^30 bytes)
+        const uint8_t* __restrict__ p1 = src + (uint32_t)(yt.ofs >> 16) * (uint32_t)CW * 2u;
+        uint32_t px[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const uint32_t v0 = load_uv_taps(p0 + at[j], two[j]), v1 = load_uv_taps(p1 + at[j], two[j]);
+            const uint32_t U0 = udot2(__builtin_amdgcn_perm(0u, v0, 0x0C020C00u), w[j], 0u) & ~255u;
+            const uint32_t U1 = udot2(__builtin_amdgcn_perm(0u, v1, 0x0C020C00u), w[j], 0u) & ~255u;
+            const uint32_t V0 = udot2(__builtin_amdgcn_perm(0u, v0, 0x0C030C01u), w[j], 0u) & ~255u;
+            const uint32_t V1 = udot2(__builtin_amdgcn_perm(0u, v1, 0x0C030C01u), w[j], 0u) & ~255u;
+            const uint32_t u = (mulhi_u24(b0s, U0) + mulhi_u24(b1s, U1) + 2u) >> 2;
+            const uint32_t v = (mulhi_u24(b0s, V0) + mulhi_u24(b1s, V1) + 2u) >> 2;
+            px[j] = u | (v << 8);
+        }
+        uint8_t* __restrict__ d = dst + ((uint32_t)y * (uint32_t)oCW + (uint32_t)x0) * 2u;
+        if (x0 + 3 < oCW) {
+            uint2 o;
+            o.x = px[0] | (px[1] << 16);
+            o.y = px[2] | (px[3] << 16);
+            __builtin_memcpy(__builtin_assume_aligned(d, 2), &o, 8);
+        } else {                                                  // a row end of oW/2 % 4 != 0 samples
+#pragma unroll
+            for (int j = 0; j < 3; ++j)
+                if (x0 + j < oCW) reinterpret_cast<uint16_t*>(d)[j] = (uint16_t)px[j];
+        }
+    }
+}
+
+}  // namespace mf
+
+#endif  // MF_RESIZE_UV_BODY_H

@@ -887,17 +887,23 @@ class MeshFlowStabilizer:
         return cropped, bounds
 
     def stabilized_nv12(self, d_y, d_uv, d_disp, homographies, border_yuv=(81, 90, 240), out=None,
-                        adaptive_weights_definition=ADAPTIVE_WEIGHTS_DEFINITION_ORIGINAL):
+                        adaptive_weights_definition=ADAPTIVE_WEIGHTS_DEFINITION_ORIGINAL, crop=False, output_size=None):
         """An NV12 clip that a decoder left in device memory -- d_y (F, H, W) uint8 luma, d_uv (F, H/2, W/2, 2) uint8 interleaved chroma, U
         first -- stabilized without ever becoming BGR: the Jacobi sweep (mfs.py:695-704) on d_disp, the cell table + plan of all F frames, then
         `ops.warp_nv12`; like `stabilized_planes`, everything on torch's current stream.  Luma moves exactly as a grey clip does, chroma is
         sampled at half the luma coordinates of the even luma pixels (`ops.warp_nv12` has the definition).  border_yuv: (Y, U, V) of the
-        uncovered area, by default BT.601 limited-range red (81, 90, 240) -- the reference's default BGR (0, 0, 255).  out: an
-        (out_y, out_uv) pair to fill.  Returns (out_y, out_uv, bounds): bounds = int32[4] device tensor {left, top, right, bottom}, the
-        rectangle `stabilization_maps` returns for the same inputs.  A degenerate mesh raises `DegenerateMeshError` (clip_serial None) here,
-        synchronously, before a plane is written."""
+        uncovered area, by default BT.601 limited-range red (81, 90, 240) -- the reference's default BGR (0, 0, 255).  crop=True: the warp
+        goes into temporaries and `ops.crop_resize_nv12` crops them from the clip rectangle as the warp left it on the device (the host never
+        reads it), scaled to output_size = (width, height), even, by default back to (W, H) (mfs.py:1111-1157).  out: an (out_y, out_uv)
+        pair to fill (the cropped pair with crop=True).  Returns (out_y, out_uv, bounds): bounds = int32[4] device tensor {left, top, right,
+        bottom}, the rectangle `stabilization_maps` returns for the same inputs.  A degenerate mesh raises `DegenerateMeshError`
+        (clip_serial None) here, synchronously, before a plane is written."""
         import torch
         from . import ops
+        if output_size is not None:
+            if not crop:
+                raise ValueError('output_size belongs to crop=True')
+            ops._even_output_size(output_size, 'output_size')
         self._check_definition(adaptive_weights_definition)
         self._check_mesh_shape(d_disp, d_disp.shape[0])
         ops._need(d_y, torch.uint8, 'd_y')
@@ -910,7 +916,11 @@ class MeshFlowStabilizer:
         bad = int(table.status.item())
         if bad:
             raise DegenerateMeshError(bad, None)
-        out_y, out_uv = ops.warp_nv12(d_y, d_uv, table, border_yuv, out=out, bounds=bounds)
+        if not crop:
+            out_y, out_uv = ops.warp_nv12(d_y, d_uv, table, border_yuv, out=out, bounds=bounds)
+            return out_y, out_uv, bounds
+        warped_y, warped_uv = ops.warp_nv12(d_y, d_uv, table, border_yuv, bounds=bounds)
+        out_y, out_uv, _ = ops.crop_resize_nv12(warped_y, warped_uv, bounds, size=output_size, out=out)
         return out_y, out_uv, bounds
 
     def _stabilized_frames_device(self, d_frames, d_unstab, d_stab, out=None, table=None):
