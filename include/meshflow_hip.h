@@ -286,6 +286,32 @@ int mf_warp_nv12(const uint8_t* d_y, const uint8_t* d_uv, uint8_t* d_out_y, uint
 int mf_warp_bounds_nv12(const uint8_t* d_y, const uint8_t* d_uv, uint8_t* d_out_y, uint8_t* d_out_uv, const void* d_table, int n, int W, int H,
                         int R, int C, const uint8_t border_yuv[3], int32_t* d_crop, int32_t* d_bounds, void* stream);
 
+/* ---- P010 clips: the 4:2:0 layout with 16-bit samples that hardware decoders write for 10-bit and HDR video, warped from ONE cell table like an
+ * NV12 clip, without a conversion to 3-channel uint16 and back.  A clip is two contiguous stacks: d_y [n][H][W] uint16 and d_uv
+ * [n][H/2][W/2][2] uint16, U first; W and H are even, 2 .. 32,767.  Samples are plain 16-bit numbers, 0 .. 65,535: P010, P012 and P016 differ
+ * only in how many low bits a producer leaves zero, so this one entry serves all three.  The OUTPUT's low bits carry the blend's fraction --
+ * nothing is masked; a consumer that needs them zero masks them itself.  (Pitched surfaces and surfaces that keep a frame's two planes
+ * together are not taken: one plane stack per pointer.)
+ * Luma: d_out_y is, bit for bit, channel 0 of mf_warp_u16c3 applied to the clip stack(Y, Y, Y) with border (b, b, b), b = border_yuv[0]:
+ * cv2.remap INTER_LINEAR / BORDER_CONSTANT of CV_16UC1 -- the 8-bit map quantisation (sx = cvRound(32 u), ix = sx >> 5, fx = sx & 31), the
+ * float32 BilinearTab_f weights, the chain ((S00 w0 + S01 w1) + S10 w2) + S11 w3 with every product and sum rounded on its own, then
+ * saturate_cast<ushort>; a 2 x 2 footprint wholly outside the frame gives the border sample itself.  The per-frame crop values in d_crop, the
+ * clip rectangle and the degenerate-cell status are written by this launch and are exactly what mf_warp_u16c3 (and mf_warp_u8c1) writes on
+ * the same table.
+ * Chroma: sited at the even luma sample, as for NV12: output chroma sample (cx, cy) of frame f takes the float32 map (u, v) of luma pixel
+ * (2 cx, 2 cy) -- exactly what mf_warp_maps_f32 returns for it, (W + 1, H + 1) for a pixel no cell owns included --, halves it in float32 (exact)
+ * and applies the CV_16U arithmetic above per channel on the (H/2, W/2) two-channel plane with border (border_yuv[1], border_yuv[2]).  U and V
+ * never mix.  The chroma launch follows the luma launch on the same stream; it reads nothing outside the plane's bytes and touches neither
+ * d_crop nor the rectangle.  All plane offsets are 64-bit.
+ * border_yuv: {Y, U, V} as given; BT.601 limited-range red at 10 bits in P010's high bits is (81 << 8, 90 << 8, 240 << 8) = (20736, 23040, 61440).
+ * mf_warp_bounds_p010: the rectangle in the caller's d_bounds[4], as mf_warp_bounds_u16c3.
+ * Refused with MF_ERR_INVALID_ARG before anything is launched: null pointers, n <= 0, any two of the four planes overlapping, an odd W or H, W
+ * or H outside 2 .. 32,767, R or C outside 1 .. 64, a plane pointer that is not 2-byte aligned. */
+int mf_warp_p010(const uint16_t* d_y, const uint16_t* d_uv, uint16_t* d_out_y, uint16_t* d_out_uv, const void* d_table, int n, int W, int H,
+                 int R, int C, const uint16_t border_yuv[3], int32_t* d_crop, void* stream);
+int mf_warp_bounds_p010(const uint16_t* d_y, const uint16_t* d_uv, uint16_t* d_out_y, uint16_t* d_out_uv, const void* d_table, int n, int W, int H,
+                        int R, int C, const uint16_t border_yuv[3], int32_t* d_crop, int32_t* d_bounds, void* stream);
+
 /* Clip-level crop bounds (mfs.py:1103-1106): {max left, max top, min right, min bottom} over n frames.
  * d_bounds: [4] int32. */
 int mf_crop_reduce(const int32_t* d_crop, int n, int W, int H, int32_t* d_bounds, void* stream);

@@ -88,6 +88,40 @@ static int warp_nv12_entry(const char* name, const uint8_t* d_y, const uint8_t* 
     return launch_warp(Px::NV12_UV, d_uv, d_out_uv, tv, n, W, H, R, C, pack_border(Px::NV12_UV, border_yuv + 1), d_crop, (hipStream_t)stream);
 }
 
+// The checks of the two P010 entries (warp_nv12_entry's, on uint16 planes), then the luma launches (Px::U16C1) and the chroma launches behind them
+// on the same stream.  has_bounds: the clip-level rectangle goes to the caller's d_bounds instead of the table's.
+static int warp_p010_entry(const char* name, const uint16_t* d_y, const uint16_t* d_uv, uint16_t* d_out_y, uint16_t* d_out_uv, const void* d_table,
+                           int n, int W, int H, int R, int C, const uint16_t* border_yuv, int32_t* d_crop, bool has_bounds, int32_t* d_bounds,
+                           void* stream)
+{
+    if (!d_y || !d_uv || !d_out_y || !d_out_uv || !d_table || !border_yuv || !d_crop || (has_bounds && !d_bounds)) {
+        set_error("%s: null pointer", name);
+        return MF_ERR_INVALID_ARG;
+    }
+    if (n <= 0) { set_error("%s: bad sizes", name); return MF_ERR_INVALID_ARG; }
+    if (W < 2 || H < 2 || W > 32767 || H > 32767) { set_error("%s: W=%d H=%d outside 2 .. 32,767", name, W, H); return MF_ERR_INVALID_ARG; }
+    if ((W | H) & 1) { set_error("%s: a P010 frame has an even W and H, got W=%d H=%d", name, W, H); return MF_ERR_INVALID_ARG; }
+    if (R < 1 || C < 1 || R > 64 || C > 64) { set_error("%s: mesh R=%d C=%d outside 1 .. 64", name, R, C); return MF_ERR_INVALID_ARG; }
+    if ((((uintptr_t)d_y | (uintptr_t)d_uv | (uintptr_t)d_out_y | (uintptr_t)d_out_uv) & 1u) != 0) {
+        set_error("%s: d_y, d_uv, d_out_y and d_out_uv must be 2-byte aligned", name);
+        return MF_ERR_INVALID_ARG;
+    }
+    // no two of the four plane stacks may share a byte
+    const size_t y_bytes = (size_t)n * W * H * 2u, uv_bytes = (size_t)n * p010_uv_frame_bytes(W, H);
+    const struct { uintptr_t at; size_t bytes; const char* what; } pl[4] = {
+        { (uintptr_t)d_y, y_bytes, "d_y" }, { (uintptr_t)d_uv, uv_bytes, "d_uv" }, { (uintptr_t)d_out_y, y_bytes, "d_out_y" }, { (uintptr_t)d_out_uv, uv_bytes, "d_out_uv" } };
+    for (int i = 0; i < 4; ++i)
+        for (int j = i + 1; j < 4; ++j)
+            if (pl[i].at < pl[j].at + pl[j].bytes && pl[j].at < pl[i].at + pl[i].bytes) {
+                set_error("%s: %s and %s alias", name, pl[i].what, pl[j].what);
+                return MF_ERR_INVALID_ARG;
+            }
+    TableView tv = table_view(const_cast<void*>(d_table), n, W, H, R, C);
+    if (has_bounds) tv.bounds = d_bounds;
+    if (const int rc = launch_warp(Px::U16C1, d_y, d_out_y, tv, n, W, H, R, C, pack_border(Px::U16C1, border_yuv), d_crop, (hipStream_t)stream)) return rc;
+    return launch_warp(Px::P010_UV, d_uv, d_out_uv, tv, n, W, H, R, C, pack_border(Px::P010_UV, border_yuv + 1), d_crop, (hipStream_t)stream);
+}
+
 // The element checks every plane entry shares: elem_bytes is 0 (the float32 calls) or 1, 2, 4, 8, and both pointers are aligned to the element
 static bool plane_elem_ok(const char* name, int elem_bytes, const void* d_planes, const void* d_out)
 {
@@ -348,6 +382,18 @@ int mf_warp_bounds_nv12(const uint8_t* d_y, const uint8_t* d_uv, uint8_t* d_out_
                         int R, int C, const uint8_t border_yuv[3], int32_t* d_crop, int32_t* d_bounds, void* stream)
 {
     return warp_nv12_entry("mf_warp_bounds_nv12", d_y, d_uv, d_out_y, d_out_uv, d_table, n, W, H, R, C, border_yuv, d_crop, true, d_bounds, stream);
+}
+
+int mf_warp_p010(const uint16_t* d_y, const uint16_t* d_uv, uint16_t* d_out_y, uint16_t* d_out_uv, const void* d_table, int n, int W, int H,
+                 int R, int C, const uint16_t border_yuv[3], int32_t* d_crop, void* stream)
+{
+    return warp_p010_entry("mf_warp_p010", d_y, d_uv, d_out_y, d_out_uv, d_table, n, W, H, R, C, border_yuv, d_crop, false, nullptr, stream);
+}
+
+int mf_warp_bounds_p010(const uint16_t* d_y, const uint16_t* d_uv, uint16_t* d_out_y, uint16_t* d_out_uv, const void* d_table, int n, int W, int H,
+                        int R, int C, const uint16_t border_yuv[3], int32_t* d_crop, int32_t* d_bounds, void* stream)
+{
+    return warp_p010_entry("mf_warp_bounds_p010", d_y, d_uv, d_out_y, d_out_uv, d_table, n, W, H, R, C, border_yuv, d_crop, true, d_bounds, stream);
 }
 
 // ---- the same three calls with the clip-level rectangle in the CALLER's d_bounds[4] instead of inside the table blob ----

@@ -1,5 +1,5 @@
 // The tails of footprint_body's other formats (device only, included through warp_body.h): the lane's four pixels at source coordinates
-// (u, v) -- taps, blend, crop flags, store -- for uint16 BGR, grey, 4-channel uint8, the coordinate maps, the side planes and NV12 chroma.
+// (u, v) -- taps, blend, crop flags, store -- for uint16 BGR, grey, 4-channel uint8, the coordinate maps, the side planes, NV12 chroma and the two planes of a P010 clip.
 #ifndef MF_WARP_TAILS_H
 #define MF_WARP_TAILS_H
 #include "warp_coords.h"
@@ -583,6 +583,171 @@ __device__ __forceinline__ void remap_store_nv12_uv(const float (&u)[4], const f
         } else {
             const uint16_t w2 = (uint16_t)o[0];
             __builtin_memcpy(d, &w2, 2);
+        }
+    }
+}
+
+// ---- the planes of a P010 / P012 / P016 clip: cv2.remap's CV_16U arithmetic (blend16 at the head of this file) on one and on two channels ----
+// Footprint-level tail of the U16C1 instantiation of footprint_body: remap_store_u16 on one channel -- out is, bit for bit, channel 0 of
+// remap_store_u16 on the plane repeated three times.  Deep-interior footprints (every tap two pixels inside the frame, no crop flag possible)
+// take each pixel's two tap rows as one 4-byte load apiece (the frame may be only 2-byte aligned: unaligned dword loads) and blend pixels
+// 0 + 1 and 2 + 3 pairwise; the others take every tap at its position clamped into the frame and replace outside taps by `border`, and a
+// 2 x 2 footprint wholly outside the frame gives `border` itself.  The four crop tests and crop_fold as in remap_store_u16.  The lane's four
+// samples go out as one 8-byte store where all four lie inside the row.  All offsets are 64-bit.
+__device__ __forceinline__ void remap_store_u16c1(const float (&u)[4], const float (&v)[4], uint32_t f, int x0, int y, bool active, int W, int H,
+                                                  const uint16_t* __restrict__ frames, uint16_t* __restrict__ out, uint32_t border,
+                                                  int32_t* __restrict__ crop, int32_t* __restrict__ clip)
+{
+    const uint64_t frame_samples = (uint64_t)((uint32_t)W * (uint32_t)H);
+    const uint16_t* __restrict__ src = frames + (uint64_t)f * frame_samples;
+    uint16_t* __restrict__ dst = out + (uint64_t)f * frame_samples;
+    uint32_t bx[4], by[4];
+    fixed_point(u, v, bx, by);
+    const bool deep = deep_interior(bx, by, W, H);
+    const bool fast = __ballot(active && !deep) == 0;
+    uint32_t o[4];                                                      // the lane's 4 output samples
+    int c_left = 0, c_top = 0, c_right = W - 1, c_bottom = H - 1;
+    if (active) {
+        if (fast) {
+            float sv[4][4];                                             // taps as float, [pixel][S00, S01, S10, S11]
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const uint32_t ix = __builtin_amdgcn_ubfe(bx[j], 5, 17), iy = __builtin_amdgcn_ubfe(by[j], 5, 17);
+                const uint16_t* __restrict__ p0 = src + (uint64_t)(iy * (uint32_t)W + ix);
+                uint32_t a, b;                                          // S00 | S01 << 16 of row iy, S10 | S11 << 16 of row iy + 1
+                __builtin_memcpy(&a, p0, 4);
+                __builtin_memcpy(&b, p0 + (uint32_t)W, 4);
+                sv[j][0] = (float)(a & 0xFFFFu); sv[j][1] = (float)(a >> 16);
+                sv[j][2] = (float)(b & 0xFFFFu); sv[j][3] = (float)(b >> 16);
+            }
+#pragma unroll
+            for (int j = 0; j < 4; j += 2) {
+                const f32x2 ax = f32x2{ (float)(bx[j] & 31u), (float)(bx[j + 1] & 31u) } * 0.03125f;
+                const f32x2 ay = f32x2{ (float)(by[j] & 31u), (float)(by[j + 1] & 31u) } * 0.03125f;
+                const f32x2 ax0 = 1.0f - ax, ay0 = 1.0f - ay;
+                const f32x2 t = blend16x2(f32x2{ sv[j][0], sv[j + 1][0] }, f32x2{ sv[j][1], sv[j + 1][1] }, f32x2{ sv[j][2], sv[j + 1][2] },
+                                          f32x2{ sv[j][3], sv[j + 1][3] }, ay0 * ax0, ay0 * ax, ay * ax0, ay * ax);
+                o[j] = (uint32_t)rintf(t.x);                            // (no clamp: rint(t) <= 65535 here, see remap_store_u16)
+                o[j + 1] = (uint32_t)rintf(t.y);
+            }
+        } else {
+            // frame borders, uncovered pixels (at (W+1, H+1)), crop flags, out-of-range coordinates
+            const float fWm1 = (float)(W - 1), fHm1 = (float)(H - 1);
+            const bool narrow = narrow_coords(bx, by);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float uu = u[j], vv = v[j];
+                const int x = x0 + j;
+                if (x < W) {                                            // crop-boundary scan, mfs.py:1075-1098 (exact: Sterbenz)
+                    if (fabsf(uu) < 1.0f) c_left = max(c_left, x);
+                    if (fabsf(uu - fWm1) < 1.0f) c_right = min(c_right, x);
+                    if (fabsf(vv) < 1.0f) c_top = max(c_top, y);
+                    if (fabsf(vv - fHm1) < 1.0f) c_bottom = min(c_bottom, y);
+                }
+                const int sxx = fixed_coord(narrow, bx[j], uu), syy = fixed_coord(narrow, by[j], vv);
+                const int ix = sxx >> 5, iy = syy >> 5;                 // (saturation to int16 cannot change any decision below)
+                o[j] = border;
+                if (ix >= W || ix + 1 < 0 || iy >= H || iy + 1 < 0) continue;       // the 2 x 2 footprint lies wholly outside: the border sample
+                const ClampedTaps t = clamped_taps(ix, iy, W, H);
+                const uint32_t q00 = src[(uint64_t)(t.r0 + t.cx0)], q01 = src[(uint64_t)(t.r0 + t.cx1)];
+                const uint32_t q10 = src[(uint64_t)(t.r1 + t.cx0)], q11 = src[(uint64_t)(t.r1 + t.cx1)];
+                const uint32_t s00 = t.in_x0 && t.in_y0 ? q00 : border, s01 = t.in_x1 && t.in_y0 ? q01 : border;
+                const uint32_t s10 = t.in_x0 && t.in_y1 ? q10 : border, s11 = t.in_x1 && t.in_y1 ? q11 : border;
+                const float ax = (float)(sxx & 31) * 0.03125f, ay = (float)(syy & 31) * 0.03125f;
+                const float ax0 = 1.0f - ax, ay0 = 1.0f - ay;
+                o[j] = blend16((float)s00, (float)s01, (float)s10, (float)s11, ay0 * ax0, ay0 * ax, ay * ax0, ay * ax);
+            }
+        }
+    }
+    if (!fast) crop_fold(c_left, c_top, c_right, c_bottom, f, W, H, crop, clip);
+    if (active) {
+        uint16_t* __restrict__ d = dst + (uint64_t)((uint32_t)y * (uint32_t)W + (uint32_t)x0);
+        if (x0 + 3 < W) {                                               // 8 bytes at a 2-byte aligned address: one unaligned store
+            const uint2 q = make_uint2(o[0] | (o[1] << 16), o[2] | (o[3] << 16));
+            __builtin_memcpy(d, &q, 8);
+            asm volatile("" ::: "memory");                              // (keeps the store whole across footprint_body's three call sites, as in remap_store_u8c4)
+        } else {                                                        // (a loop: its stores do not merge with the 8-byte one)
+            const int m = W - x0;
+#pragma unroll 1
+            for (int j = 0; j < m; ++j) d[j] = (uint16_t)(j == 0 ? o[0] : j == 1 ? o[1] : j == 2 ? o[2] : o[3]);   // (selects: o stays in registers)
+        }
+    }
+}
+
+// Footprint-level tail of the P010_UV instantiation of footprint_body: remap_store_nv12_uv's lane mapping and coordinates -- a lane of an even
+// row emits chroma samples (x0 / 2, y / 2) and (x0 / 2 + 1, y / 2) from its luma pixels 0 and 2 at half their (u, v), halved in float32
+// (exact) -- with the CV_16U arithmetic on the (H / 2, W / 2) plane of 4-byte pixels.  A tap is one 4-byte word, U | V << 16; the pair goes
+// through blend16x2 with the sample's four weights computed once, so U and V never mix.  Deep-interior footprints (wave-uniform) fetch a tap
+// row's two words as one 8-byte load (the plane may be only 2-byte aligned: unaligned loads); the others take every tap as a 4-byte load at
+// its position clamped into the plane and replace outside taps by `border` (U | V << 16), and a 2 x 2 footprint wholly outside the plane
+// -- an unowned pixel's, at ((W + 1) / 2, (H + 1) / 2), among them -- gives `border` itself.  Nothing outside the plane's bytes is read, no
+// crop value is touched (the luma launch owns them), and the lane's two samples go out as one 8-byte store (4 bytes in the lane that holds the
+// last sample of a row with W % 4 == 2).  All plane offsets are 64-bit.
+__device__ __forceinline__ void remap_store_p010_uv(const float (&u)[4], const float (&v)[4], uint32_t f, int x0, int y, bool active, int W, int H,
+                                                    const uint16_t* __restrict__ planes, uint16_t* __restrict__ out, uint32_t border)
+{
+    const int Wc = W >> 1, Hc = H >> 1;
+    const uint64_t plane_samples = 2ull * (uint64_t)((uint32_t)Wc * (uint32_t)Hc);
+    const uint16_t* __restrict__ src = planes + (uint64_t)f * plane_samples;
+    const bool emit = active && (y & 1) == 0;                           // (x0 is a multiple of 4: pixels 0 and 2 are even columns)
+    const bool two = x0 + 2 < W;                                        // (the lane's second sample exists)
+    // the lane's two samples twice over, so that the four-pixel helpers of warp_coords.h serve (the duplicates fold away)
+    const float h0 = u[0] * 0.5f, g0 = v[0] * 0.5f, h1 = two ? u[2] * 0.5f : h0, g1 = two ? v[2] * 0.5f : g0;
+    const float uc[4] = { h0, h1, h0, h1 }, vc[4] = { g0, g1, g0, g1 };
+    uint32_t bx[4], by[4];
+    fixed_point(uc, vc, bx, by);
+    const bool deep = deep_interior(bx, by, Wc, Hc);
+    const bool fast = __ballot(emit && !deep) == 0;
+    uint32_t o[2];                                                      // the lane's two output pixels, U | V << 16
+    if (emit) {
+        if (fast) {
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const uint32_t ix = __builtin_amdgcn_ubfe(bx[j], 5, 17), iy = __builtin_amdgcn_ubfe(by[j], 5, 17);
+                const uint16_t* __restrict__ p = src + 2ull * (uint64_t)(iy * (uint32_t)Wc + ix);
+                uint2 a, b;                                             // pixels ix and ix + 1 of rows iy and iy + 1
+                __builtin_memcpy(&a, p, 8);
+                __builtin_memcpy(&b, p + 2u * (uint32_t)Wc, 8);
+                const float ax = (float)(bx[j] & 31u) * 0.03125f, ay = (float)(by[j] & 31u) * 0.03125f;
+                const float ax0 = 1.0f - ax, ay0 = 1.0f - ay;
+                const float w0 = ay0 * ax0, w1 = ay0 * ax, w2 = ay * ax0, w3 = ay * ax;
+                const f32x2 t = blend16x2(f32x2{ (float)(a.x & 0xFFFFu), (float)(a.x >> 16) }, f32x2{ (float)(a.y & 0xFFFFu), (float)(a.y >> 16) },
+                                          f32x2{ (float)(b.x & 0xFFFFu), (float)(b.x >> 16) }, f32x2{ (float)(b.y & 0xFFFFu), (float)(b.y >> 16) },
+                                          f32x2{ w0, w0 }, f32x2{ w1, w1 }, f32x2{ w2, w2 }, f32x2{ w3, w3 });
+                o[j] = (uint32_t)rintf(t.x) | ((uint32_t)rintf(t.y) << 16);         // (no clamp: rint(t) <= 65535 here, see remap_store_u16)
+            }
+        } else {
+            // plane borders, uncovered pixels, out-of-range coordinates
+            const bool narrow = narrow_coords(bx, by);
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const int sxx = fixed_coord(narrow, bx[j], uc[j]), syy = fixed_coord(narrow, by[j], vc[j]);
+                const int ix = sxx >> 5, iy = syy >> 5;                 // (saturation to int16 cannot change any decision below)
+                o[j] = border;
+                if (ix >= Wc || ix + 1 < 0 || iy >= Hc || iy + 1 < 0) continue;     // the 2 x 2 footprint lies wholly outside: the border pixel
+                const ClampedTaps t = clamped_taps(ix, iy, Wc, Hc);
+                uint32_t p00, p01, p10, p11;
+                __builtin_memcpy(&p00, src + 2ull * (uint64_t)(t.r0 + t.cx0), 4);
+                __builtin_memcpy(&p01, src + 2ull * (uint64_t)(t.r0 + t.cx1), 4);
+                __builtin_memcpy(&p10, src + 2ull * (uint64_t)(t.r1 + t.cx0), 4);
+                __builtin_memcpy(&p11, src + 2ull * (uint64_t)(t.r1 + t.cx1), 4);
+                p00 = t.in_x0 && t.in_y0 ? p00 : border; p01 = t.in_x1 && t.in_y0 ? p01 : border;
+                p10 = t.in_x0 && t.in_y1 ? p10 : border; p11 = t.in_x1 && t.in_y1 ? p11 : border;
+                const float ax = (float)(sxx & 31) * 0.03125f, ay = (float)(syy & 31) * 0.03125f;
+                const float ax0 = 1.0f - ax, ay0 = 1.0f - ay;
+                const float w0 = ay0 * ax0, w1 = ay0 * ax, w2 = ay * ax0, w3 = ay * ax;
+                const f32x2 t2 = blend16x2(f32x2{ (float)(p00 & 0xFFFFu), (float)(p00 >> 16) }, f32x2{ (float)(p01 & 0xFFFFu), (float)(p01 >> 16) },
+                                           f32x2{ (float)(p10 & 0xFFFFu), (float)(p10 >> 16) }, f32x2{ (float)(p11 & 0xFFFFu), (float)(p11 >> 16) },
+                                           f32x2{ w0, w0 }, f32x2{ w1, w1 }, f32x2{ w2, w2 }, f32x2{ w3, w3 });
+                o[j] = min((uint32_t)rintf(t2.x), 65535u) | (min((uint32_t)rintf(t2.y), 65535u) << 16);      // saturate_cast<ushort>, as blend16
+            }
+        }
+        uint16_t* __restrict__ d = out + (uint64_t)f * plane_samples + 2ull * (uint64_t)((uint32_t)(y >> 1) * (uint32_t)Wc + (uint32_t)(x0 >> 1));
+        if (two) {                                                      // 8 bytes at a 2-byte aligned address: one unaligned store
+            const uint2 q = make_uint2(o[0], o[1]);
+            __builtin_memcpy(d, &q, 8);
+        } else {
+            __builtin_memcpy(d, &o[0], 4);
         }
     }
 }

@@ -457,9 +457,10 @@ NV12_BORDER_RED = (81, 90, 240)
 _nv12_border = _border_samples(ctypes.c_uint8, 255, 3)
 
 
-def _nv12_plane(t, name, shape, device):
-    """One plane stack of an NV12 clip: a contiguous uint8 device tensor of exactly `shape` on `device` (None: wherever it is)."""
-    _need(t, torch.uint8, name)
+def _nv12_plane(t, name, shape, device, dtype=torch.uint8):
+    """One plane stack of an NV12 clip (dtype=torch.uint16: of a P010 clip): a contiguous device tensor of that dtype and of exactly `shape`
+    on `device` (None: wherever it is)."""
+    _need(t, dtype, name)
     if tuple(t.shape) != tuple(shape):
         raise ValueError(f'{name} must have shape {tuple(shape)}, got {tuple(t.shape)}')
     if device is not None and t.device != device:
@@ -504,6 +505,54 @@ def warp_nv12(y, uv, table, border_yuv=NV12_BORDER_RED, out=None, bounds=None):
     else:
         _need_bounds(bounds)
         _lib.check(_lib_.mf_warp_bounds_nv12(_ptr(y), _ptr(uv), _ptr(out_y), _ptr(out_uv), _ptr(table.buf), n, W, H, table.R, table.C, border,
+                                             _ptr(table.crop), _ptr(bounds), _stream()))
+    return out_y, out_uv
+
+
+# BT.601 limited-range red at 10 bits, in P010's high bits: NV12_BORDER_RED << 8
+P010_BORDER_RED = (81 << 8, 90 << 8, 240 << 8)
+_p010_border = _border_samples(ctypes.c_uint16, 65535, 3)
+
+
+def warp_p010(y, uv, table, border_yuv=P010_BORDER_RED, out=None, bounds=None):
+    """The mesh warp of a P010 clip -- the 4:2:0 layout with 16-bit samples that hardware decoders write for 10-bit and HDR video -- from one
+    cell table, without a conversion to 3-channel uint16 and back (mf_warp_p010).  y: (n, H, W) uint16 luma, uv: (n, H/2, W/2, 2) uint16
+    interleaved chroma, U first; both contiguous device tensors, W and H even, n == table.n.  Samples are plain 16-bit numbers, 0 .. 65535:
+    P010, P012 and P016 differ only in how many low bits a producer leaves zero, so this call serves all three -- and the OUTPUT's low bits
+    carry the blend's fraction: nothing is masked.  (Pitched surfaces, or one tensor that holds a frame's two planes together, are not taken.)
+    Luma is bit for bit channel 0 of `warp(stack(y, y, y), table, (b, b, b))`, b = border_yuv[0] -- cv2.remap's CV_16U arithmetic on one
+    channel; the per-frame crop values in table.crop and the clip-level rectangle in `bounds` / table.clip_bounds are that call's.  Chroma is
+    sited at the even luma sample, as in `warp_nv12`: output chroma sample (cx, cy) takes `warp_maps(table)[f, 2 cy, 2 cx]`, halves it in
+    float32 and samples the (H/2, W/2) two-channel plane with the same CV_16U arithmetic per channel; where the source lies outside the plane,
+    and where no cell owns the luma pixel, the result is (border_yuv[1], border_yuv[2]).
+    border_yuv: (Y, U, V), each clamp(round(v), 0, 65535).  The default (20736, 23040, 61440) is BT.601 limited-range red at 10 bits in P010's
+    high bits.  out: an (out_y, out_uv) pair to fill.  Returns (out_y, out_uv)."""
+    _need(y, torch.uint16, 'y')
+    if y.dim() != 3:
+        raise ValueError(f'y must be (n, H, W) luma planes, got shape {tuple(y.shape)}')
+    n, H, W = (int(v) for v in y.shape)
+    if W % 2 or H % 2:
+        raise ValueError(f'a P010 frame has an even width and height, got W={W} H={H}')
+    _nv12_plane(uv, 'uv', (n, H // 2, W // 2, 2), y.device, torch.uint16)
+    if (n, W, H) != (table.n, table.W, table.H):
+        raise ValueError(f'y {tuple(y.shape)} does not match the cell table (n, H, W) = {(table.n, table.H, table.W)}')
+    if len(border_yuv) != 3:
+        raise ValueError(f'border_yuv must be (Y, U, V), got {border_yuv!r}')
+    if out is None:
+        out_y, out_uv = torch.empty_like(y), torch.empty_like(uv)
+    else:
+        if not isinstance(out, (tuple, list)) or len(out) != 2:
+            raise ValueError('out must be a pair (out_y, out_uv)')
+        out_y, out_uv = out
+        _nv12_plane(out_y, 'out_y', y.shape, y.device, torch.uint16)
+        _nv12_plane(out_uv, 'out_uv', uv.shape, y.device, torch.uint16)
+    border = _p010_border(border_yuv)
+    if bounds is None:
+        _lib.check(_lib_.mf_warp_p010(_ptr(y), _ptr(uv), _ptr(out_y), _ptr(out_uv), _ptr(table.buf), n, W, H, table.R, table.C, border,
+                                      _ptr(table.crop), _stream()))
+    else:
+        _need_bounds(bounds)
+        _lib.check(_lib_.mf_warp_bounds_p010(_ptr(y), _ptr(uv), _ptr(out_y), _ptr(out_uv), _ptr(table.buf), n, W, H, table.R, table.C, border,
                                              _ptr(table.crop), _ptr(bounds), _stream()))
     return out_y, out_uv
 

@@ -923,6 +923,35 @@ class MeshFlowStabilizer:
         out_y, out_uv, _ = ops.crop_resize_nv12(warped_y, warped_uv, bounds, size=output_size, out=out)
         return out_y, out_uv, bounds
 
+    def stabilized_p010(self, d_y, d_uv, d_disp, homographies, border_yuv=(81 << 8, 90 << 8, 240 << 8), out=None,
+                        adaptive_weights_definition=ADAPTIVE_WEIGHTS_DEFINITION_ORIGINAL, crop=False, output_size=None):
+        """`stabilized_nv12` for a P010 clip -- d_y (F, H, W) uint16 luma, d_uv (F, H/2, W/2, 2) uint16 interleaved chroma, U first, what a
+        decoder writes for 10-bit and HDR video (P012 and P016 alike) -- stabilized without ever becoming 3-channel uint16: the Jacobi sweep
+        (mfs.py:695-704) on d_disp, the cell table + plan of all F frames, then `ops.warp_p010` (which has the definition), everything on
+        torch's current stream.  border_yuv: (Y, U, V) of the uncovered area, by default BT.601 limited-range red at 10 bits in P010's high
+        bits, (20736, 23040, 61440).  There is no crop path yet: crop=True or an output_size raises ValueError.  out: an (out_y, out_uv) pair
+        to fill.  Returns (out_y, out_uv, bounds): bounds = int32[4] device tensor {left, top, right, bottom}, the rectangle
+        `stabilization_maps` returns for the same inputs.  A degenerate mesh raises `DegenerateMeshError` (clip_serial None) here,
+        synchronously, before a plane is written."""
+        import torch
+        from . import ops
+        if crop or output_size is not None:
+            raise ValueError('crop-resize of 16-bit 4:2:0 clips is not built yet: stabilized_p010 takes neither crop=True nor output_size')
+        self._check_definition(adaptive_weights_definition)
+        self._check_mesh_shape(d_disp, d_disp.shape[0])
+        ops._need(d_y, torch.uint16, 'd_y')
+        if d_y.dim() != 3:
+            raise ValueError(f'd_y must be (F, H, W) luma planes, got shape {tuple(d_y.shape)}')
+        H, W = int(d_y.shape[1]), int(d_y.shape[2])
+        d_stab = self._stabilized_vertex_displacements_device(d_disp, W, H, adaptive_weights_definition, homographies)
+        bounds = torch.empty(4, dtype=torch.int32, device=d_disp.device)
+        table = ops.cell_table(d_disp, d_stab, W, H, self.mesh_row_count, self.mesh_col_count, bounds=bounds)
+        bad = int(table.status.item())
+        if bad:
+            raise DegenerateMeshError(bad, None)
+        out_y, out_uv = ops.warp_p010(d_y, d_uv, table, border_yuv, out=out, bounds=bounds)
+        return out_y, out_uv, bounds
+
     def _stabilized_frames_device(self, d_frames, d_unstab, d_stab, out=None, table=None):
         """d_frames: (n, H, W, 3) uint8; d_unstab/d_stab: (n, R+1, C+1, 2) float64, all in HBM.
         Returns (stabilized frames (n, H, W, 3) uint8, per-frame crop values (n, 4) int32), in HBM.
