@@ -398,6 +398,35 @@ int mf_crop_resize_nv12(const uint8_t* d_y, const uint8_t* d_uv, uint8_t* d_out_
                         int right, int bottom, int out_W, int out_H, void* d_work, void* stream);
 int mf_crop_resize_dev_nv12(const uint8_t* d_y, const uint8_t* d_uv, uint8_t* d_out_y, uint8_t* d_out_uv, int n, int W, int H,
                             const int32_t* d_bounds, int out_W, int out_H, void* d_work, int32_t* d_status, void* stream);
+/* _crop_frames (mfs.py:1111-1157) for a P010 clip -- d_y [n][H][W] uint16, d_uv [n][H/2][W/2][2] uint16, U first, as mf_warp_p010 takes them -- to
+ * d_out_y [n][out_H][out_W] and d_out_uv [n][out_H/2][out_W/2][2], without a conversion to 3-channel uint16 and back.  W, H, out_W and out_H are
+ * even, 2 .. 32,767; the rectangle is inclusive, in luma pixels, of any parity.  Samples are plain 16-bit numbers; nothing is masked.  DEFINED
+ * here, modelled on cv2.resize (OpenCV 4.5-4.10), not pinned.
+ * Luma: d_out_y is, bit for bit, channel 0 of mf_crop_resize_to_u16c3 (mf_crop_resize_dev_u16c3 for the device rectangle) applied to the clip
+ * stack(Y, Y, Y): cv2.resize INTER_LINEAR of CV_16UC1 -- that call's tables for (out_W, out_H), float32 weights (1 - f, f),
+ * t = float(S[sx]) a0 + float(S[sx+1]) a1, out = min(rint(t0 b0 + t1 b1), 65535), every product and sum rounded on its own; where
+ * 2 out_W == cw and 2 out_H == ch, INTER_AREA's (S00 + S01 + S10 + S11 + 2) >> 2 instead.
+ * Chroma is sited at the even luma sample, exactly as for mf_crop_resize_nv12: with cw = right - left + 1,
+ * scale_x = 1.0 / ((double)out_W / (double)cw), c1 = right >> 1 and c0 = min((left + 1) >> 1, c1):
+ *   fc = (float)(((double)left + (((double)(2 cx) + 0.5) * scale_x - 0.5)) * 0.5);  s = floor(fc);  f = fc - (float)s
+ *   s < c0 -> (s, f) = (c0, 0);  s >= c1 -> (c1, 0)
+ * the y axis the same with top, bottom, out_H and cy, except that the two row indices are clipped to [r0, r1] and the fraction kept.  Then the
+ * 16-bit float arithmetic above per channel with the float32 weights (1 - f, f) -- no 2048 quantisation.  U and V never mix.  Chroma has NO
+ * area branch: at exactly 2x down an even `left` gives f = 0.25, not a box, so chroma takes the float path everywhere.  Nothing outside columns
+ * c0 .. c1 and rows r0 .. r1 of the frame's own chroma plane influences the result, and no byte outside the d_uv stack is read (where s == c1
+ * only that one sample is loaded).  The full-frame rectangle at out_W x out_H == W x H is a copy of both planes.
+ * d_work: mf_crop_resize_p010_workspace_bytes(out_W, out_H) bytes (the luma tables, mf_crop_resize_workspace_bytes(out_W, out_H), then
+ * out_W/2 + out_H/2 chroma entries of 8 bytes).  The luma launch goes first, then chroma, on the same stream.  mf_crop_resize_dev_p010: the
+ * rectangle read from d_bounds when the kernels execute; one that cannot be used adds exactly 1 to *d_status, once per call, and leaves both
+ * outputs and the workspace untouched (d_status as in mf_crop_resize_dev_u16c3).
+ * Refused with MF_ERR_INVALID_ARG before anything is launched: null pointers, n <= 0, any two of the four plane stacks overlapping, an odd W, H,
+ * out_W or out_H or one outside 2 .. 32,767, a plane pointer that is not 2-byte aligned, too many tiles, and (host rectangle) an empty or
+ * out-of-frame rectangle. */
+size_t mf_crop_resize_p010_workspace_bytes(int out_W, int out_H);
+int mf_crop_resize_p010(const uint16_t* d_y, const uint16_t* d_uv, uint16_t* d_out_y, uint16_t* d_out_uv, int n, int W, int H, int left, int top,
+                        int right, int bottom, int out_W, int out_H, void* d_work, void* stream);
+int mf_crop_resize_dev_p010(const uint16_t* d_y, const uint16_t* d_uv, uint16_t* d_out_y, uint16_t* d_out_uv, int n, int W, int H,
+                            const int32_t* d_bounds, int out_W, int out_H, void* d_work, int32_t* d_status, void* stream);
 
 /* ---- the row before the path: vertex-motion accumulation (mfs.py:236-452 from the matched features on) ----
  * Replaces the Python loops of _get_vertex_nearby_feature_residual_velocities (mfs.py:365-452), the medians, global

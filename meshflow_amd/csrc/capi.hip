@@ -234,6 +234,49 @@ static int crop_resize_nv12_entry(bool dev, const uint8_t* d_y, const uint8_t* d
     return launch_resize_uv(d_uv, d_out_uv, W, H, left, top, right, bottom, oW, oH, tabs, order, st);
 }
 
+// The checks of the two P010 crop-resize entries (crop_resize_nv12_entry's, on uint16 planes) -- all of them ahead of the first launch --, then
+// the luma tables, the luma kernel, the chroma tables and the chroma kernel on the same stream (resize_hdr.hip / resize_hdr_dev.hip).  dev:
+// mf_crop_resize_dev_p010 (the rectangle in d_bounds, left .. bottom unused).
+static int crop_resize_p010_entry(bool dev, const uint16_t* d_y, const uint16_t* d_uv, uint16_t* d_out_y, uint16_t* d_out_uv, int n, int W, int H,
+                                  int left, int top, int right, int bottom, const int32_t* d_bounds, int oW, int oH, void* d_work,
+                                  int32_t* d_status, void* stream)
+{
+    const char* const call = dev ? "mf_crop_resize_dev_" : "mf_crop_resize_";
+    const char* const fmt = "p010";
+    if (!d_y || !d_uv || !d_out_y || !d_out_uv || !d_work || (dev && (!d_bounds || !d_status))) {
+        set_error("%s%s: null pointer", call, fmt);
+        return MF_ERR_INVALID_ARG;
+    }
+    if (n <= 0) { set_error("%s%s: bad sizes n=%d", call, fmt, n); return MF_ERR_INVALID_ARG; }
+    if (W < 2 || H < 2 || W > 32767 || H > 32767) { set_error("%s%s: W=%d H=%d outside 2 .. 32,767", call, fmt, W, H); return MF_ERR_INVALID_ARG; }
+    if (oW < 2 || oH < 2 || oW > 32767 || oH > 32767) {
+        set_error("%s%s: unsupported output size %dx%d (2 .. 32,767 each)", call, fmt, oW, oH);
+        return MF_ERR_INVALID_ARG;
+    }
+    if ((W | H) & 1) { set_error("%s%s: a P010 frame has an even W and H, got W=%d H=%d", call, fmt, W, H); return MF_ERR_INVALID_ARG; }
+    if ((oW | oH) & 1) { set_error("%s%s: a P010 output has an even size, got %dx%d", call, fmt, oW, oH); return MF_ERR_INVALID_ARG; }
+    if ((((uintptr_t)d_y | (uintptr_t)d_uv | (uintptr_t)d_out_y | (uintptr_t)d_out_uv) & 1u) != 0) {
+        set_error("%s%s: d_y, d_uv, d_out_y and d_out_uv must be 2-byte aligned", call, fmt);
+        return MF_ERR_INVALID_ARG;
+    }
+    // no two of the four plane stacks may share a byte
+    const struct { uintptr_t at; size_t bytes; const char* what; } pl[4] = {
+        { (uintptr_t)d_y, (size_t)n * W * H * 2u, "d_y" }, { (uintptr_t)d_uv, (size_t)n * p010_uv_frame_bytes(W, H), "d_uv" },
+        { (uintptr_t)d_out_y, (size_t)n * oW * oH * 2u, "d_out_y" }, { (uintptr_t)d_out_uv, (size_t)n * p010_uv_frame_bytes(oW, oH), "d_out_uv" } };
+    for (int i = 0; i < 4; ++i)
+        for (int j = i + 1; j < 4; ++j)
+            if (pl[i].at < pl[j].at + pl[j].bytes && pl[j].at < pl[i].at + pl[i].bytes) {
+                set_error("%s%s: %s and %s alias", call, fmt, pl[i].what, pl[j].what);
+                return MF_ERR_INVALID_ARG;
+            }
+    if (!dev && !resize_rect_ok(call, fmt, left, top, right, bottom, W, H)) return MF_ERR_INVALID_ARG;
+    TileOrder luma, chroma;
+    if (!resize_hdr_tile_orders(oW, oH, n, luma, chroma)) { set_error("%s%s: too many tiles", call, fmt); return MF_ERR_INVALID_ARG; }
+    hipStream_t st = (hipStream_t)stream;
+    if (dev) return launch_resize_hdr_dev(d_y, d_uv, d_out_y, d_out_uv, W, H, d_bounds, oW, oH, d_work, d_status, luma, chroma, st);
+    return launch_resize_hdr(d_y, d_uv, d_out_y, d_out_uv, W, H, left, top, right, bottom, oW, oH, d_work, luma, chroma, st);
+}
+
 }  // namespace mf
 
 using namespace mf;
@@ -544,6 +587,24 @@ int mf_crop_resize_dev_nv12(const uint8_t* d_y, const uint8_t* d_uv, uint8_t* d_
                             const int32_t* d_bounds, int out_W, int out_H, void* d_work, int32_t* d_status, void* stream)
 {
     return crop_resize_nv12_entry(true, d_y, d_uv, d_out_y, d_out_uv, n, W, H, 0, 0, 0, 0, d_bounds, out_W, out_H, d_work, d_status, stream);
+}
+
+size_t mf_crop_resize_p010_workspace_bytes(int out_W, int out_H)
+{
+    return (out_W > 0 && out_H > 0) ? crop_resize_p010_workspace_bytes(out_W, out_H) : 0;
+}
+
+int mf_crop_resize_p010(const uint16_t* d_y, const uint16_t* d_uv, uint16_t* d_out_y, uint16_t* d_out_uv, int n, int W, int H, int left, int top,
+                        int right, int bottom, int out_W, int out_H, void* d_work, void* stream)
+{
+    return crop_resize_p010_entry(false, d_y, d_uv, d_out_y, d_out_uv, n, W, H, left, top, right, bottom, nullptr, out_W, out_H, d_work, nullptr,
+                                  stream);
+}
+
+int mf_crop_resize_dev_p010(const uint16_t* d_y, const uint16_t* d_uv, uint16_t* d_out_y, uint16_t* d_out_uv, int n, int W, int H,
+                            const int32_t* d_bounds, int out_W, int out_H, void* d_work, int32_t* d_status, void* stream)
+{
+    return crop_resize_p010_entry(true, d_y, d_uv, d_out_y, d_out_uv, n, W, H, 0, 0, 0, 0, d_bounds, out_W, out_H, d_work, d_status, stream);
 }
 
 int mf_crop_resize_plane_f32(const float* d_planes, float* d_out, int n, int W, int H, int left, int top, int right, int bottom, int out_W,

@@ -364,6 +364,18 @@ int launch_resize_uv(const uint8_t* uv, uint8_t* out_uv, int W, int H, int left,
                      const TileOrder& order, hipStream_t st);
 int launch_resize_uv_dev(const uint8_t* uv, uint8_t* out_uv, int W, int H, const int32_t* d_bounds, int oW, int oH, void* tabs,
                          const TileOrder& order, hipStream_t st);
+// resize16.hip / resize_dev.hip: resize16_tables_kernel's / resize16_tables_dev_kernel's tables for (oW, oH) in `work`, on their own
+int launch_resize16_tables(int cw, int ch, int oW, int oH, void* work, hipStream_t st);
+int launch_resize16_tables_dev(const int32_t* d_bounds, int W, int H, int oW, int oH, void* work, int32_t* d_status, hipStream_t st);
+// resize_hdr.hip / resize_hdr_dev.hip: mf_crop_resize_p010 / mf_crop_resize_dev_p010 behind capi.hip's checks (W, H, oW, oH and the rectangle are
+// the LUMA frame's; `work`: the luma tables, then the chroma tables) -- the luma tables above, resize_hdr_body.h's luma kernel, its chroma
+// tables and its chroma kernel.  resize_hdr_tile_orders: the two kernels' tiles (false: too many).
+size_t crop_resize_p010_workspace_bytes(int oW, int oH);
+bool resize_hdr_tile_orders(int oW, int oH, int n, TileOrder& luma, TileOrder& chroma);
+int launch_resize_hdr(const uint16_t* y, const uint16_t* uv, uint16_t* out_y, uint16_t* out_uv, int W, int H, int left, int top, int right,
+                      int bottom, int oW, int oH, void* work, const TileOrder& luma, const TileOrder& chroma, hipStream_t st);
+int launch_resize_hdr_dev(const uint16_t* y, const uint16_t* uv, uint16_t* out_y, uint16_t* out_uv, int W, int H, const int32_t* d_bounds, int oW,
+                          int oH, void* work, int32_t* d_status, const TileOrder& luma, const TileOrder& chroma, hipStream_t st);
 size_t vertex_motion_workspace_bytes(int total_features, int max_per_pair, int P, int R, int C);
 int launch_vertex_motion(const double* early, const double* late, const int32_t* offsets, const double* hom, int P,
                          int total_features, int max_per_pair, int W, int H, int R, int C, int ell_rows, int ell_cols,

@@ -30,6 +30,17 @@
 
 namespace mf {
 
+// resize16_tables_dev_kernel's tables for (oW, oH) in `work` (an unusable rectangle adds 1 to *d_status): launch_crop_resize_dev's uint16 tables,
+// and the luma tables of mf_crop_resize_dev_p010 (resize_hdr_dev.hip)
+int launch_resize16_tables_dev(const int32_t* d_bounds, int W, int H, int oW, int oH, void* work, int32_t* d_status, hipStream_t st)
+{
+    Resize16Tab* xtab = (Resize16Tab*)work;
+    Resize16Tab* ytab = xtab + oW;
+    hipLaunchKernelGGL(resize16_tables_kernel, dim3(((oW > oH ? oW : oH) + 255) / 256), dim3(256), 0, st, d_bounds, W, H, oW, oH, d_status, xtab,
+                       ytab);
+    return hip_fail(hipGetLastError(), "resize16_tables_dev_kernel launch");
+}
+
 int launch_crop_resize_dev(Px px, const void* frames, void* out, int n, int W, int H, const int32_t* d_bounds, int oW, int oH, void* work,
                            int32_t* d_status, hipStream_t st)
 {
@@ -45,8 +56,7 @@ int launch_crop_resize_dev(Px px, const void* frames, void* out, int n, int W, i
     if (px == Px::U16C3) {
         Resize16Tab* xtab = (Resize16Tab*)work;
         Resize16Tab* ytab = xtab + oW;
-        hipLaunchKernelGGL(resize16_tables_kernel, tab_grid, dim3(256), 0, st, d_bounds, W, H, oW, oH, d_status, xtab, ytab);
-        if (const int rc = hip_fail(hipGetLastError(), "resize16_tables_dev_kernel launch")) return rc;
+        if (const int rc = launch_resize16_tables_dev(d_bounds, W, H, oW, oH, work, d_status, st)) return rc;
         if (same)
             hipLaunchKernelGGL(resize16_kernel, grid, dim3(256), 0, st, (const uint16_t*)frames, (uint16_t*)out, W, H, d_bounds, xtab, ytab, order);
         else

@@ -37,6 +37,10 @@ __device__ __forceinline__ bool rect_usable(int left, int top, int right, int bo
     }                                                                                                                   \
     const int cw = rect_right - left + 1, ch = rect_bottom - top + 1;                                                   \
     const double scale_x = 1.0 / ((double)(W) / (double)cw), scale_y = 1.0 / ((double)(H) / (double)ch);
+// the chroma tables kernels (resize_uv_body.h, resize_hdr_body.h) need all four edges (MF_RECT_ARGS carries left, top, cw only); they raise no
+// status: the luma tables kernel in front of them has
+#define MF_UV_TABLES_ARGS const int32_t* __restrict__ d_bounds, int frame_W, int frame_H
+#define MF_UV_TABLES_LOAD MF_RECT_LOAD(frame_W, frame_H)
 #else
 #define MF_RECT_ARGS int left, int top, int cw
 #define MF_RECT_LOAD(W, H)
@@ -44,4 +48,6 @@ __device__ __forceinline__ bool rect_usable(int left, int top, int right, int bo
 #define MF_RECT16_TO_LOAD(W, H)
 #define MF_TABLES_ARGS int cw, int ch, int W, int H, double scale_x, double scale_y
 #define MF_TABLES_LOAD(W, H)
+#define MF_UV_TABLES_ARGS int left, int top, int rect_right, int rect_bottom
+#define MF_UV_TABLES_LOAD const int cw = rect_right - left + 1, ch = rect_bottom - top + 1;
 #endif

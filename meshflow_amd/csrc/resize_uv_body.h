@@ -30,15 +30,6 @@ namespace mf {
 
 constexpr int kUvRows = 4;            // output chroma rows per wavefront
 
-// the tables kernel needs all four edges (MF_RECT_ARGS carries left, top, cw only)
-#ifdef MF_RESIZE_DEV
-#define MF_UV_TABLES_ARGS const int32_t* __restrict__ d_bounds, int frame_W, int frame_H
-#define MF_UV_TABLES_LOAD MF_RECT_LOAD(frame_W, frame_H)
-#else
-#define MF_UV_TABLES_ARGS int left, int top, int rect_right, int rect_bottom
-#define MF_UV_TABLES_LOAD const int cw = rect_right - left + 1, ch = rect_bottom - top + 1;
-#endif
-
 // x: ofs = s (absolute chroma column, clamped into c0 .. c1), w = 16 a0 | 16 a1 << 16;  y: ofs = sy0 | sy1 << 16 (absolute chroma rows, clipped
 // into r0 .. r1), w = b0 | b1 << 16 -- resize_tables_kernel's layout
 __global__ __launch_bounds__(256) void chroma_tables_kernel(MF_UV_TABLES_ARGS, int oW, int oH, ResizeTab* __restrict__ xtab,

@@ -618,6 +618,61 @@ def crop_resize_nv12(y, uv, bounds, size=None, out=None, status=None):
     return out_y, out_uv, status
 
 
+def crop_resize_p010(y, uv, bounds, size=None, out=None, status=None):
+    """`crop_resize_nv12` for a P010 clip (mfs.py:1111-1157 without a conversion to 3-channel uint16 and back; mf_crop_resize_p010 /
+    mf_crop_resize_dev_p010): crop to the inclusive {left, top, right, bottom} -- in luma pixels, of any parity -- and scale to `size` = (width,
+    height), even, by default back to (W, H).  y, uv as in `warp_p010`: uint16, plain 16-bit numbers, nothing masked.  bounds: a 4-tuple the
+    host knows, or an int32[4] DEVICE tensor (what `stabilized_p010` returns) that the kernels read when they execute -- the host never reads
+    it and the call never waits; the bits are the same.
+    Luma is bit for bit channel 0 of `crop_resize(stack(y, y, y), bounds, size=size)` (`crop_resize_resident` for a device rectangle):
+    cv2.resize's float path on CV_16UC1, and INTER_AREA's (S00 + S01 + S10 + S11 + 2) >> 2 where the crop is exactly twice the output in both
+    axes.  Chroma is sited at the even luma sample with `crop_resize_nv12`'s positions and clamps and the same float arithmetic per channel,
+    weights (1 - f, f) in float32 -- no 2048 quantisation and no area branch (include/meshflow_hip.h has every expression).  The full frame at
+    its own size is a copy.
+    out: an (out_y, out_uv) pair to fill.  status (device rectangle only): as in `crop_resize_resident` -- an int32[1] device tensor, the
+    caller's (it accumulates) or a new zeroed one, that an unusable rectangle adds exactly 1 to, leaving both outputs untouched.
+    Returns (out_y, out_uv), or (out_y, out_uv, status) for a device rectangle."""
+    _need(y, torch.uint16, 'y')
+    if y.dim() != 3:
+        raise ValueError(f'y must be (n, H, W) luma planes, got shape {tuple(y.shape)}')
+    n, H, W = (int(v) for v in y.shape)
+    if W % 2 or H % 2:
+        raise ValueError(f'a P010 frame has an even width and height, got W={W} H={H}')
+    _nv12_plane(uv, 'uv', (n, H // 2, W // 2, 2), y.device, torch.uint16)
+    oW, oH = (W, H) if size is None else _even_output_size(size)
+    resident = isinstance(bounds, torch.Tensor)
+    if resident:
+        _need_bounds(bounds)
+    elif status is not None:
+        raise ValueError('status belongs to a device rectangle: a host rectangle is checked when the call is made')
+    y_shape, uv_shape = (n, oH, oW), (n, oH // 2, oW // 2, 2)
+    if out is None:
+        out_y = torch.empty(y_shape, dtype=torch.uint16, device=y.device)
+        out_uv = torch.empty(uv_shape, dtype=torch.uint16, device=y.device)
+    else:
+        if not isinstance(out, (tuple, list)) or len(out) != 2:
+            raise ValueError('out must be a pair (out_y, out_uv)')
+        out_y, out_uv = out
+        _nv12_plane(out_y, 'out_y', y_shape, y.device, torch.uint16)
+        _nv12_plane(out_uv, 'out_uv', uv_shape, y.device, torch.uint16)
+    if resident:
+        if status is None:
+            status = torch.zeros(1, dtype=torch.int32, device=y.device)
+        else:
+            _need(status, torch.int32, 'status')
+            if status.numel() != 1:
+                raise ValueError('status must hold 1 int32')
+    work = torch.empty(_lib_.mf_crop_resize_p010_workspace_bytes(oW, oH), dtype=torch.uint8, device=y.device)
+    if not resident:
+        left, top, right, bottom = (int(v) for v in bounds)
+        _lib.check(_lib_.mf_crop_resize_p010(_ptr(y), _ptr(uv), _ptr(out_y), _ptr(out_uv), n, W, H, left, top, right, bottom, oW, oH, _ptr(work),
+                                             _stream()))
+        return out_y, out_uv
+    _lib.check(_lib_.mf_crop_resize_dev_p010(_ptr(y), _ptr(uv), _ptr(out_y), _ptr(out_uv), n, W, H, _ptr(bounds), oW, oH, _ptr(work),
+                                             _ptr(status), _stream()))
+    return out_y, out_uv, status
+
+
 def crop_resize_planes(planes, bounds, interpolation='linear', size=None, out=None, status=None):
     """`crop_resize` for side planes (mfs.py:1111-1157 on a plane; mf_crop_resize_plane_* / mf_crop_resize_dev_plane_*): crop to the inclusive
     {left, top, right, bottom} and scale to `size` = (width, height), by default back to (W, H).  planes and interpolation as in

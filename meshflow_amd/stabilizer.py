@@ -929,14 +929,16 @@ class MeshFlowStabilizer:
         decoder writes for 10-bit and HDR video (P012 and P016 alike) -- stabilized without ever becoming 3-channel uint16: the Jacobi sweep
         (mfs.py:695-704) on d_disp, the cell table + plan of all F frames, then `ops.warp_p010` (which has the definition), everything on
         torch's current stream.  border_yuv: (Y, U, V) of the uncovered area, by default BT.601 limited-range red at 10 bits in P010's high
-        bits, (20736, 23040, 61440).  There is no crop path yet: crop=True or an output_size raises ValueError.  out: an (out_y, out_uv) pair
+        bits, (20736, 23040, 61440).  This call does not crop: crop=True or an output_size raises ValueError, and `stabilized_p010_cropped` is the
+        call that crops and scales.  out: an (out_y, out_uv) pair
         to fill.  Returns (out_y, out_uv, bounds): bounds = int32[4] device tensor {left, top, right, bottom}, the rectangle
         `stabilization_maps` returns for the same inputs.  A degenerate mesh raises `DegenerateMeshError` (clip_serial None) here,
         synchronously, before a plane is written."""
         import torch
         from . import ops
         if crop or output_size is not None:
-            raise ValueError('crop-resize of 16-bit 4:2:0 clips is not built yet: stabilized_p010 takes neither crop=True nor output_size')
+            raise ValueError('crop-resize of 16-bit 4:2:0 clips is not built yet into stabilized_p010, which takes neither crop=True nor '
+                             'output_size: call stabilized_p010_cropped')
         self._check_definition(adaptive_weights_definition)
         self._check_mesh_shape(d_disp, d_disp.shape[0])
         ops._need(d_y, torch.uint16, 'd_y')
@@ -950,6 +952,35 @@ class MeshFlowStabilizer:
         if bad:
             raise DegenerateMeshError(bad, None)
         out_y, out_uv = ops.warp_p010(d_y, d_uv, table, border_yuv, out=out, bounds=bounds)
+        return out_y, out_uv, bounds
+
+    def stabilized_p010_cropped(self, d_y, d_uv, d_disp, homographies, border_yuv=(81 << 8, 90 << 8, 240 << 8), out=None,
+                                adaptive_weights_definition=ADAPTIVE_WEIGHTS_DEFINITION_ORIGINAL, output_size=None):
+        """`stabilized_p010` followed by the reference's last step, _crop_frames (mfs.py:1111-1157), without the clip ever becoming 3-channel
+        uint16: the cell table + plan of all F frames, `ops.warp_p010` into temporaries, then `ops.crop_resize_p010` from the clip rectangle
+        as the warp left it on the device (the host never reads it), scaled to output_size = (width, height), even, by default back to
+        (W, H); everything on torch's current stream.  d_y, d_uv, d_disp, homographies and border_yuv as in `stabilized_p010`.  out: an
+        (out_y, out_uv) pair of the OUTPUT's size to fill.  Returns (out_y, out_uv, bounds): the cropped pair and the int32[4] device
+        tensor {left, top, right, bottom} `stabilized_p010` returns for the same inputs.  A degenerate mesh raises `DegenerateMeshError`
+        (clip_serial None) here, synchronously, before a plane is written."""
+        import torch
+        from . import ops
+        if output_size is not None:
+            ops._even_output_size(output_size, 'output_size')
+        self._check_definition(adaptive_weights_definition)
+        self._check_mesh_shape(d_disp, d_disp.shape[0])
+        ops._need(d_y, torch.uint16, 'd_y')
+        if d_y.dim() != 3:
+            raise ValueError(f'd_y must be (F, H, W) luma planes, got shape {tuple(d_y.shape)}')
+        H, W = int(d_y.shape[1]), int(d_y.shape[2])
+        d_stab = self._stabilized_vertex_displacements_device(d_disp, W, H, adaptive_weights_definition, homographies)
+        bounds = torch.empty(4, dtype=torch.int32, device=d_disp.device)
+        table = ops.cell_table(d_disp, d_stab, W, H, self.mesh_row_count, self.mesh_col_count, bounds=bounds)
+        bad = int(table.status.item())
+        if bad:
+            raise DegenerateMeshError(bad, None)
+        warped_y, warped_uv = ops.warp_p010(d_y, d_uv, table, border_yuv, bounds=bounds)
+        out_y, out_uv, _ = ops.crop_resize_p010(warped_y, warped_uv, bounds, size=output_size, out=out)
         return out_y, out_uv, bounds
 
     def _stabilized_frames_device(self, d_frames, d_unstab, d_stab, out=None, table=None):
