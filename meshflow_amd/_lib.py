@@ -13,6 +13,7 @@ MF_ERR_INVALID_ARG = -1
 MF_ERR_HIP = -2
 MF_ERR_DEGENERATE = -3
 CELL_DOUBLES = 32
+TRACK_MIN_SUBFRAME, TRACK_MAX_PER_SUBFRAME, TRACK_OVERFLOW = 2, 16384, 1
 CELL_OFF_M, CELL_OFF_HI, CELL_OFF_RECT, CELL_OFF_BBOX, CELL_OFF_STATUS = 0, 9, 18, 22, 26
 
 _vp = ctypes.c_void_p
@@ -83,6 +84,9 @@ SIGNATURES = {
     'mf_crop_resize_p010_workspace_bytes': (_sz, [_i, _i]),
     'mf_crop_resize_p010': (_i, [_vp, _vp, _vp, _vp] + [_i] * 9 + [_vp, _vp]),
     'mf_crop_resize_dev_p010': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp]),
+    'mf_track_workspace_bytes': (_sz, [_i] * 6),
+    'mf_fast_corners_u8': (_i, [_vp] + [_i] * 7 + [_vp] * 5),
+    'mf_lk_track_u8': (_i, [_vp, _vp] + [_i] * 6 + [_vp] * 6),
     'mf_vertex_motion_workspace_bytes': (_sz, [_i, _i, _i, _i, _i]),
     'mf_vertex_motion_f64': (_i, [_vp, _vp, _vp, _vp] + [_i] * 9 + [_vp, _vp, _vp, _vp, _vp]),
     'mf_stability_score_f64': (_i, [_vp, _i, _i, _vp, _vp, _vp]),

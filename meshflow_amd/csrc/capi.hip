@@ -6,6 +6,7 @@
 
 #include "mf_common.h"
 #include "resize_checks.h"
+#include "track.h"
 
 namespace mf {
 
@@ -275,6 +276,39 @@ static int crop_resize_p010_entry(bool dev, const uint16_t* d_y, const uint16_t*
     hipStream_t st = (hipStream_t)stream;
     if (dev) return launch_resize_hdr_dev(d_y, d_uv, d_out_y, d_out_uv, W, H, d_bounds, oW, oH, d_work, d_status, luma, chroma, st);
     return launch_resize_hdr(d_y, d_uv, d_out_y, d_out_uv, W, H, left, top, right, bottom, oW, oH, d_work, luma, chroma, st);
+}
+
+// Every check the tracker's calls share (include/meshflow_hip.h); the geometry on success.
+static int track_checks(const char* name, int n, int W, int H, int sub_rows, int sub_cols, int max_per, track::Geom& g)
+{
+    if (W < 1 || H < 1 || W > 32767 || H > 32767) { set_error("%s: W and H must be in 1 .. 32,767 (got %d x %d)", name, W, H); return MF_ERR_INVALID_ARG; }
+    if (sub_rows < 1 || sub_cols < 1 || sub_rows > H || sub_cols > W) {
+        set_error("%s: sub_rows must be in 1 .. H and sub_cols in 1 .. W (got %d x %d for %d x %d)", name, sub_rows, sub_cols, W, H);
+        return MF_ERR_INVALID_ARG;
+    }
+    g = track::make_geom(W, H, sub_rows, sub_cols);
+    const int last_w = W - (g.ncols - 1) * g.sub_w, last_h = H - (g.nrows - 1) * g.sub_h;
+    if (last_w < MF_TRACK_MIN_SUBFRAME || last_h < MF_TRACK_MIN_SUBFRAME) {
+        set_error("%s: sub-frame below the minimum: the smallest is %d x %d, every sub-frame must be at least %d x %d", name, last_w, last_h,
+                  MF_TRACK_MIN_SUBFRAME, MF_TRACK_MIN_SUBFRAME);
+        return MF_ERR_INVALID_ARG;
+    }
+    if (max_per < 1 || max_per > MF_TRACK_MAX_PER_SUBFRAME) {
+        set_error("%s: max_per_subframe must be in 1 .. %d (got %d)", name, MF_TRACK_MAX_PER_SUBFRAME, max_per);
+        return MF_ERR_INVALID_ARG;
+    }
+    if (n < 1 || 2ll * n * g.ncols * g.nrows > 65535) {
+        set_error("%s: n must be at least 1 with 2 * n * sub-frames <= 65,535 (got n = %d, %d sub-frames): too many for one call", name, n,
+                  g.ncols * g.nrows);
+        return MF_ERR_INVALID_ARG;
+    }
+    return MF_OK;
+}
+
+static bool overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes)
+{
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x < y + b_bytes && y < x + a_bytes;
 }
 
 }  // namespace mf
@@ -636,6 +670,58 @@ int mf_crop_resize_dev_plane_nearest(const void* d_planes, void* d_out, int n, i
     if (const int rc = crop_resize_plane_checks("mf_crop_resize_dev_plane_nearest", elem_bytes, d_planes, d_out, d_work, true, d_bounds, d_status))
         return rc;
     return launch_crop_resize_plane_dev(elem_bytes, d_planes, d_out, n, W, H, d_bounds, out_W, out_H, d_work, d_status, (hipStream_t)stream);
+}
+
+size_t mf_track_workspace_bytes(int n_pairs, int W, int H, int sub_rows, int sub_cols, int max_per_subframe)
+{
+    track::Geom g;
+    if (track_checks("mf_track_workspace_bytes", n_pairs, W, H, sub_rows, sub_cols, max_per_subframe, g)) return 0;
+    const size_t mask = align16(track_mask_bytes(g, n_pairs)), pyramid = track_pyramid_bytes(g, n_pairs);
+    return mask > pyramid ? mask : pyramid;
+}
+
+int mf_fast_corners_u8(const uint8_t* d_grey, int n, int W, int H, int sub_rows, int sub_cols, int max_per_subframe, int threshold,
+                       float* d_points, int32_t* d_counts, int32_t* d_status, void* d_work, void* stream)
+{
+    const char* name = "mf_fast_corners_u8";
+    if (!d_grey || !d_points || !d_counts || !d_status || !d_work) { set_error("%s: null pointer", name); return MF_ERR_INVALID_ARG; }
+    track::Geom g;
+    if (const int rc = track_checks(name, n, W, H, sub_rows, sub_cols, max_per_subframe, g)) return rc;
+    if (threshold < 1 || threshold > 254) { set_error("%s: threshold must be in 1 .. 254 (got %d)", name, threshold); return MF_ERR_INVALID_ARG; }
+    if (((uintptr_t)d_points & 7) || ((uintptr_t)d_counts & 3) || ((uintptr_t)d_status & 3)) {
+        set_error("%s: d_points must be 8-byte aligned, d_counts and d_status 4-byte aligned", name);
+        return MF_ERR_INVALID_ARG;
+    }
+    const size_t slots = (size_t)n * g.ncols * g.nrows, frames = (size_t)n * W * H;
+    if (overlap(d_grey, frames, d_points, slots * max_per_subframe * 8) || overlap(d_grey, frames, d_counts, slots * 4) ||
+        overlap(d_grey, frames, d_status, slots * 4) || overlap(d_grey, frames, d_work, track_mask_bytes(g, n))) {
+        set_error("%s: the frames alias an output or the workspace", name);
+        return MF_ERR_INVALID_ARG;
+    }
+    return launch_fast_corners(d_grey, n, g, max_per_subframe, threshold, d_points, d_counts, d_status, d_work, (hipStream_t)stream);
+}
+
+int mf_lk_track_u8(const uint8_t* d_early, const uint8_t* d_late, int n_pairs, int W, int H, int sub_rows, int sub_cols,
+                   int max_per_subframe, const float* d_points, const int32_t* d_counts, float* d_moved, uint8_t* d_found, void* d_work,
+                   void* stream)
+{
+    const char* name = "mf_lk_track_u8";
+    if (!d_early || !d_late || !d_points || !d_counts || !d_moved || !d_found || !d_work) { set_error("%s: null pointer", name); return MF_ERR_INVALID_ARG; }
+    track::Geom g;
+    if (const int rc = track_checks(name, n_pairs, W, H, sub_rows, sub_cols, max_per_subframe, g)) return rc;
+    if (((uintptr_t)d_points & 7) || ((uintptr_t)d_moved & 7) || ((uintptr_t)d_counts & 3)) {
+        set_error("%s: d_points and d_moved must be 8-byte aligned, d_counts 4-byte aligned", name);
+        return MF_ERR_INVALID_ARG;
+    }
+    const size_t slots = (size_t)n_pairs * g.ncols * g.nrows, frames = (size_t)n_pairs * W * H;
+    for (const uint8_t* stack : {d_early, d_late})
+        if (overlap(stack, frames, d_moved, slots * max_per_subframe * 8) || overlap(stack, frames, d_found, slots * max_per_subframe) ||
+            overlap(stack, frames, d_work, track_pyramid_bytes(g, n_pairs))) {
+            set_error("%s: the frames alias an output or the workspace", name);
+            return MF_ERR_INVALID_ARG;
+        }
+    if (const int rc = launch_pyramid(d_early, d_late, n_pairs, g, d_work, (hipStream_t)stream)) return rc;
+    return launch_lk_levels(d_early, d_late, n_pairs, g, max_per_subframe, d_points, d_counts, d_moved, d_found, d_work, (hipStream_t)stream);
 }
 
 size_t mf_vertex_motion_workspace_bytes(int total_features, int max_per_pair, int P, int R, int C)

@@ -1,0 +1,19 @@
+// The device tracker's launchers (track_fast.hip, track_pyr.hip, track_lk.hip) behind capi.hip's checks.
+#pragma once
+#include "mf_common.h"
+#include "track_body.h"
+
+namespace mf {
+
+// bytes of the mask of corner flags (FAST) and of pyramid levels 1-3 of both stacks (LK); the workspace is the larger of the two
+size_t track_mask_bytes(const track::Geom& g, int n);
+size_t track_pyramid_bytes(const track::Geom& g, int n_pairs);
+// where pyramid level `level` (1-3) starts in the workspace, and the pitch and height of one of its 2 * n_pairs * S sub-images
+size_t track_level_offset(const track::Geom& g, int n_pairs, int level);
+int launch_fast_corners(const uint8_t* grey, int n, const track::Geom& g, int max_per, int threshold, float* points, int32_t* counts,
+                        int32_t* status, void* work, hipStream_t st);
+int launch_pyramid(const uint8_t* early, const uint8_t* late, int n_pairs, const track::Geom& g, void* work, hipStream_t st);
+int launch_lk_levels(const uint8_t* early, const uint8_t* late, int n_pairs, const track::Geom& g, int max_per, const float* points,
+                     const int32_t* counts, float* moved, uint8_t* found, const void* work, hipStream_t st);
+
+}  // namespace mf

@@ -141,3 +141,139 @@ def pack_features(features_by_pair):
     offsets = np.cumsum([0] + counts).astype(np.int32)
     cat = lambda parts: np.ascontiguousarray(np.concatenate(parts)) if parts else np.zeros((0, 2))
     return cat(early), cat(late), offsets, max(counts, default=0)
+
+
+# ---- the host finisher of the device tracker (tracker.py): outlier rejection and the homography, mfs.py:524-526 and 569-574 ----
+# cv2.findHomography cannot be restated here: its RANSAC draws samples from OpenCV's own random generator, and both of its modes end with a
+# Levenberg-Marquardt refinement.  This is a documented deviation, like the mesh-based cropping ratio above: samples of 4 come from
+# `synthetic.hash32` counters (the same on every platform), degenerate samples are skipped, the number of iterations follows cv2's adaptive
+# formula (RANSACUpdateNumIters), the mask is the best sample's consensus set, and every fit is a normalised DLT in float64.  There is NO
+# Levenberg-Marquardt refinement.
+
+def _points(a, name):
+    a = np.asarray(a, dtype=np.float64)
+    if a.ndim == 3 and a.shape[1:] == (1, 2):
+        a = a[:, 0, :]
+    if a.ndim != 2 or a.shape[1] != 2:
+        raise ValueError(f'{name} must be (K, 2) or (K, 1, 2) points, got shape {a.shape}')
+    return a
+
+
+def _collinear(p):
+    """All points of p (K, 2) on one line (or fewer than 3 distinct): the second singular value of the centred points vanishes."""
+    c = p - p.mean(axis=0)
+    sv = np.linalg.svd(c, compute_uv=False)
+    return len(sv) < 2 or sv[1] <= 1e-9 * max(sv[0], 1.0)
+
+
+def _matched_points(early, late, caller):
+    early, late = _points(early, 'early'), _points(late, 'late')
+    if early.shape != late.shape:
+        raise ValueError(f'{caller}: early and late must hold the same number of points')
+    if len(early) < 4:
+        raise ValueError(f'{caller}: a homography needs at least 4 point pairs, got {len(early)}')
+    if _collinear(early) or _collinear(late):
+        raise ValueError(f'{caller}: all points lie on one line: no homography is determined')
+    return early, late
+
+
+def _normalisation(p):
+    """Hartley's similarity: centroid to the origin, mean distance sqrt(2)."""
+    c = p.mean(axis=0)
+    d = np.sqrt(((p - c) ** 2).sum(axis=1)).mean()
+    s = math.sqrt(2.0) / d if d > 0 else 1.0
+    return np.array([[s, 0.0, -s * c[0]], [0.0, s, -s * c[1]], [0.0, 0.0, 1.0]])
+
+
+def _dlt(early, late):
+    """Normalised DLT: the 3 x 3 matrix (h22 = 1) that minimises the algebraic error, or None where it has h22 = 0."""
+    te, tl = _normalisation(early), _normalisation(late)
+    e = early * te[0, 0] + te[:2, 2]
+    l = late * tl[0, 0] + tl[:2, 2]
+    k = len(e)
+    a = np.zeros((2 * k, 9))
+    a[0::2, 0:2], a[0::2, 2] = e, 1.0
+    a[0::2, 6:8], a[0::2, 8] = -l[:, :1] * e, -l[:, 0]
+    a[1::2, 3:5], a[1::2, 5] = e, 1.0
+    a[1::2, 6:8], a[1::2, 8] = -l[:, 1:] * e, -l[:, 1]
+    h = np.linalg.svd(a)[2][-1].reshape(3, 3)
+    h = np.linalg.inv(tl) @ h @ te
+    if abs(h[2, 2]) <= 1e-12 * np.abs(h).max():
+        return None
+    return h / h[2, 2]
+
+
+def _reprojection_sq(h, early, late):
+    w = early @ h[2, :2] + h[2, 2]
+    with np.errstate(divide='ignore', invalid='ignore'):
+        x = (early @ h[0, :2] + h[0, 2]) / w
+        y = (early @ h[1, :2] + h[1, 2]) / w
+    err = (x - late[:, 0]) ** 2 + (y - late[:, 1]) ** 2
+    return np.where(np.isfinite(err), err, np.inf)
+
+
+def _degenerate_sample(p):
+    """cv2's checkSubset for 4 points: three of them on one line."""
+    for i, j, k in ((0, 1, 2), (0, 1, 3), (0, 2, 3), (1, 2, 3)):
+        d1, d2 = p[j] - p[i], p[k] - p[i]
+        if abs(d1[0] * d2[1] - d1[1] * d2[0]) <= 1.1920929e-07 * (abs(d1).sum() + abs(d2).sum()):
+            return True
+    return False
+
+
+def _ransac_iterations(confidence, outlier_ratio, max_iters):
+    """cv::RANSACUpdateNumIters for 4-point models."""
+    p = min(max(confidence, 0.0), 1.0)
+    ep = min(max(outlier_ratio, 0.0), 1.0)
+    tiny = 2.2250738585072014e-308
+    num = max(1.0 - p, tiny)
+    denom = 1.0 - (1.0 - ep) ** 4
+    if denom < tiny:
+        return 0
+    num, denom = math.log(num), math.log(denom)
+    return max_iters if denom >= 0 or -num >= max_iters * (-denom) else int(round(num / denom))
+
+
+def ransac_inliers(early, late, threshold=3.0, confidence=0.995, max_iters=2000, seed=0):
+    """The boolean inlier mask that stands in for cv2.findHomography(early, late, method=cv2.RANSAC)[1] (mfs.py:569-572): see the note above.
+    ValueError for fewer than 4 pairs or points that all lie on one line.  The same inputs give the same mask on every platform's float64."""
+    from . import synthetic
+    early, late = _matched_points(early, late, 'ransac_inliers')
+    k = len(early)
+    best, best_count = np.zeros(k, dtype=bool), 0
+    iterations, counter, it = int(max_iters), 0, 0
+    draws = np.zeros(0, dtype=np.int64)
+    while it < iterations:
+        it += 1
+        sample = []
+        while len(sample) < 4:                                   # four DISTINCT indices from consecutive hash counters
+            if counter == len(draws):
+                draws = np.concatenate([draws, synthetic.hash32(np.arange(counter, counter + 1024), seed) % k])
+            i = int(draws[counter])
+            counter += 1
+            if i not in sample:
+                sample.append(i)
+        if _degenerate_sample(early[sample]) or _degenerate_sample(late[sample]):
+            continue
+        h = _dlt(early[sample], late[sample])
+        if h is None:
+            continue
+        mask = _reprojection_sq(h, early, late) <= threshold * threshold
+        count = int(mask.sum())
+        if count > max(best_count, 3):
+            best, best_count = mask, count
+            iterations = min(iterations, _ransac_iterations(confidence, (k - count) / k, int(max_iters)))
+    if best_count < 4:
+        raise ValueError('ransac_inliers: no sample of 4 pairs had 4 inliers within %g pixels' % threshold)
+    return best
+
+
+def lsq_homography(early, late):
+    """The least-squares homography that stands in for cv2.findHomography(early, late)[0] (mfs.py:524-526): a normalised DLT over all pairs
+    in float64, h22 = 1, no Levenberg-Marquardt refinement (cv2 refines its own linear estimate; the two agree where the pairs fit a
+    homography).  ValueError for fewer than 4 pairs or points that all lie on one line."""
+    early, late = _matched_points(early, late, 'lsq_homography')
+    h = _dlt(early, late)
+    if h is None:
+        raise ValueError('lsq_homography: the fitted matrix sends the origin to infinity')
+    return h

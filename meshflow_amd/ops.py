@@ -714,6 +714,77 @@ def crop_resize_planes(planes, bounds, interpolation='linear', size=None, out=No
     return out, status
 
 
+def track_subframe_grid(W, H, sub_rows, sub_cols):
+    """(sub_w, sub_h, columns, rows) of the sub-frame grid of mfs.py:493-504: ceil-sized sub-frames, possibly fewer than sub_rows x sub_cols.
+    Sub-frame s = column * rows + row (left outer, top inner) starts at (column * sub_w, row * sub_h)."""
+    sub_rows, sub_cols = int(sub_rows), int(sub_cols)
+    if sub_rows < 1 or sub_cols < 1 or sub_rows > H or sub_cols > W:
+        raise ValueError(f'sub_rows must be in 1 .. H and sub_cols in 1 .. W (got {sub_rows} x {sub_cols} for {W} x {H})')
+    sub_w, sub_h = -(-W // sub_cols), -(-H // sub_rows)
+    return sub_w, sub_h, -(-W // sub_w), -(-H // sub_h)
+
+
+def _need_grey(t, name):
+    _need(t, torch.uint8, name)
+    if t.dim() != 3 or t.shape[0] < 1:
+        raise ValueError(f'{name} must have shape (n, H, W): one-channel uint8 images (got {tuple(t.shape)})')
+
+
+def _track_work(n, W, H, sub_rows, sub_cols, max_per_subframe, device):
+    size = _lib_.mf_track_workspace_bytes(n, W, H, sub_rows, sub_cols, max_per_subframe)
+    if size == 0:                                  # outside the limits: let the call itself say which
+        size = 16
+    return torch.empty(size, dtype=torch.uint8, device=device)
+
+
+def fast_corners(grey, sub_rows, sub_cols, max_per_subframe=1024, threshold=10):
+    """FAST corners (cv2.FastFeatureDetector_create() defaults: TYPE_9_16, non-maximum suppression) of every sub-frame of every image of a
+    (n, H, W) uint8 stack, each sub-frame an image of its own (mfs.py:505-516, 613).  Returns (points (n, S, max_per_subframe, 2) float32 --
+    (x, y) relative to the sub-frame, row-major order, zeros behind a sub-frame's corners --, counts (n, S) int32 -- the TRUE number of
+    corners --, status (n, S) int32 -- bit _lib.TRACK_OVERFLOW where the count exceeds max_per_subframe and only the first ones were kept).
+    S and the sub-frames' order: `track_subframe_grid`."""
+    _need_grey(grey, 'grey')
+    n, H, W = grey.shape
+    _, _, cols, rows = track_subframe_grid(W, H, sub_rows, sub_cols)
+    max_per_subframe = int(max_per_subframe)
+    if not 1 <= max_per_subframe <= _lib.TRACK_MAX_PER_SUBFRAME:
+        raise ValueError(f'max_per_subframe must be in 1 .. {_lib.TRACK_MAX_PER_SUBFRAME} (got {max_per_subframe})')
+    dev = grey.device
+    points = torch.zeros((n, cols * rows, max_per_subframe, 2), dtype=torch.float32, device=dev)
+    counts = torch.empty((n, cols * rows), dtype=torch.int32, device=dev)
+    status = torch.empty((n, cols * rows), dtype=torch.int32, device=dev)
+    work = _track_work(n, W, H, int(sub_rows), int(sub_cols), max_per_subframe, dev)
+    _lib.check(_lib_.mf_fast_corners_u8(_ptr(grey), n, W, H, int(sub_rows), int(sub_cols), max_per_subframe, int(threshold), _ptr(points),
+                                        _ptr(counts), _ptr(status), _ptr(work), _stream()))
+    return points, counts, status
+
+
+def lk_track(early, late, points, counts, sub_rows, sub_cols):
+    """Pyramidal Lucas-Kanade (cv2.calcOpticalFlowPyrLK defaults) of `fast_corners`' points from the (n, H, W) uint8 stack `early` into `late`,
+    sub-frame by sub-frame.  Returns (moved (n, S, max_per_subframe, 2) float32, found (n, S, max_per_subframe) uint8 = cv2's status), zeros
+    behind a sub-frame's corners.  The adjacent pairs of a clip: early = clip[:-1], late = clip[1:]."""
+    _need_grey(early, 'early')
+    _need_grey(late, 'late')
+    if early.shape != late.shape or early.device != late.device:
+        raise ValueError(f'early and late must have the same shape and device (got {tuple(early.shape)} and {tuple(late.shape)})')
+    n, H, W = early.shape
+    _, _, cols, rows = track_subframe_grid(W, H, sub_rows, sub_cols)
+    _need(points, torch.float32, 'points')
+    _need(counts, torch.int32, 'counts')
+    if points.dim() != 4 or points.shape[:2] != (n, cols * rows) or points.shape[3] != 2 or points.shape[2] < 1:
+        raise ValueError(f'points must have shape (n, S, max_per_subframe, 2) = ({n}, {cols * rows}, *, 2), got {tuple(points.shape)}')
+    if counts.shape != (n, cols * rows):
+        raise ValueError(f'counts must have shape (n, S) = ({n}, {cols * rows}), got {tuple(counts.shape)}')
+    max_per_subframe = points.shape[2]
+    dev = early.device
+    moved = torch.zeros((n, cols * rows, max_per_subframe, 2), dtype=torch.float32, device=dev)
+    found = torch.zeros((n, cols * rows, max_per_subframe), dtype=torch.uint8, device=dev)
+    work = _track_work(n, W, H, int(sub_rows), int(sub_cols), max_per_subframe, dev)
+    _lib.check(_lib_.mf_lk_track_u8(_ptr(early), _ptr(late), n, W, H, int(sub_rows), int(sub_cols), max_per_subframe, _ptr(points),
+                                    _ptr(counts), _ptr(moved), _ptr(found), _ptr(work), _stream()))
+    return moved, found
+
+
 def vertex_motion(early, late, offsets, homographies, max_per_pair, W, H, R, C, ellipse_rows, ellipse_cols):
     """Vertex velocities and their running sum from matched features (mfs.py:236-452 after the tracker).
     early/late: (K_total, 2) float64 device tensors; offsets: (P+1,) int32; homographies: (P, 3, 3) float64.

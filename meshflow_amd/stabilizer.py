@@ -237,6 +237,32 @@ class MeshFlowStabilizer:
         return self._get_unstabilized_vertex_displacements_from_features(
             num_frames, frame_width, frame_height, [(e, l) for e, l, _ in tracked], homographies)
 
+    def device_tracker(self, max_per_subframe=1024):
+        """The tracker that needs no OpenCV (tracker.py): FAST + LK as HIP kernels, outlier step and homography in NumPy."""
+        from . import tracker
+        return tracker.DeviceTracker(self.mesh_outlier_subframe_row_count, self.mesh_outlier_subframe_col_count,
+                                     self.homography_min_number_corresponding_features, self._torch_device(), max_per_subframe)
+
+    def estimate_motion(self, d_grey, chunk_pairs=32, max_per_subframe=1024):
+        """mfs.py:236-284 for a clip that is already on the device: `d_grey` (F, H, W) uint8 -- grey frames or the luma plane of an NV12
+        clip -- through `device_tracker()` and `_get_unstabilized_vertex_displacements_from_features`.  Returns (d_disp (F, R+1, C+1, 2)
+        float64 device tensor, homographies (F, 3, 3) float64 with the identity last, mfs.py:273-274): what `stabilize_resident`,
+        `stabilized_nv12`, `stabilized_p010` and `stabilized_planes` take.  ValueError where a pair cannot be tracked, as in
+        `_get_unstabilized_vertex_displacements_and_homographies`."""
+        import torch
+        tracked = self.device_tracker(max_per_subframe).track_clip(d_grey, chunk_pairs)
+        num_frames, frame_height, frame_width = d_grey.shape
+        homographies = np.empty((num_frames, 3, 3))
+        homographies[-1] = np.identity(3)                                                   # mfs.py:274
+        for t, (_, _, h) in enumerate(tracked):
+            if h is None:
+                raise ValueError(f'fewer than {self.homography_min_number_corresponding_features} features could be '
+                                 f'tracked from frame {t} to frame {t + 1}')
+            homographies[t] = h
+        disp, homographies = self._get_unstabilized_vertex_displacements_from_features(
+            num_frames, frame_width, frame_height, [(e, l) for e, l, _ in tracked], homographies)
+        return torch.from_numpy(disp).to(self._torch_device()), homographies
+
     def _compute_cropping_ratio_and_distortion_score(self, num_frames, unstabilized_frames, cropped_frames):
         """mfs.py:1160-1212."""
         from . import frontend_cv2

@@ -1,0 +1,100 @@
+"""The tracker on the device: `frontend_cv2.Tracker`'s interface (mfs.py:455-629) without OpenCV.
+
+FAST corners and pyramidal LK of every sub-frame run as HIP kernels (`ops.fast_corners`, `ops.lk_track`, csrc/track_*.hip; bit for bit
+tests/track_model.py).  The outlier step per sub-frame and the homography over the survivors are a few thousand points per pair and run
+on the host in NumPy (`host.ransac_inliers`, `host.lsq_homography`) -- deterministic stand-ins for cv2.findHomography, NOT restatements of
+it (host.py says why).  Input is one-channel uint8 only: grey frames or the luma plane of an NV12 clip.  A BGR clip needs a luma plane first,
+e.g. `(bgr.float() @ torch.tensor([0.114, 0.587, 0.299], device=bgr.device)).round().clamp(0, 255).to(torch.uint8)` (cv2's BGR2GRAY up to
+its 14-bit fixed point); the reference itself hands BGR sub-frames to cv2, where FAST sees BGR2GRAY and LK tracks three channels."""
+import numpy as np
+
+from . import host
+
+
+def finish_pair(grid, points, counts, moved, found, min_features):
+    """mfs.py:510-528 and 564-629 after the two cv2 calls, for ONE frame pair: `grid` = ops.track_subframe_grid(...), points / moved
+    (S, max, 2) float32, counts (S,), found (S, max) as NumPy arrays.  Returns (early, late, homography) -- (K, 1, 2) float64 features in
+    frame coordinates -- or (None, None, None)."""
+    sub_w, sub_h, _, rows = grid
+    early_parts, late_parts = [], []
+    for s in range(points.shape[0]):
+        k = min(int(counts[s]), points.shape[1])
+        if k < min_features:                                             # mfs.py:614
+            continue
+        keep = found[s, :k].astype(bool)
+        early, late = points[s, :k][keep], moved[s, :k][keep]
+        if len(early) < min_features:                                    # mfs.py:626
+            continue
+        try:
+            inliers = host.ransac_inliers(early, late)
+        except ValueError:                                               # fewer than 4 pairs, collinear points, no consensus: cv2 returns no mask
+            continue
+        offset = [(s // rows) * sub_w, (s % rows) * sub_h]
+        # adding the (int, int) offset promotes the float32 coordinates to float64, as in mfs.py:578
+        early_parts.append(early[inliers][:, np.newaxis, :] + offset)
+        late_parts.append(late[inliers][:, np.newaxis, :] + offset)
+    if not early_parts:        # the reference dies in np.concatenate here; like frontend_cv2.Tracker we report the pair as untrackable
+        return None, None, None
+    early, late = np.concatenate(early_parts), np.concatenate(late_parts)
+    if len(early) < min_features:                                        # mfs.py:521
+        return None, None, None
+    try:
+        homography = host.lsq_homography(early, late)
+    except ValueError:
+        return None, None, None
+    return early, late, homography
+
+
+class DeviceTracker:
+    """FAST + LK on the device, RANSAC + homography on the host, with the stabilizer's sub-frame grid and minimum feature count."""
+
+    def __init__(self, subframe_rows, subframe_cols, min_features, device='cuda:0', max_per_subframe=1024, threshold=10):
+        self.subframe_rows = int(subframe_rows)
+        self.subframe_cols = int(subframe_cols)
+        self.min_features = min_features
+        self.device = device
+        self.max_per_subframe = int(max_per_subframe)
+        self.threshold = int(threshold)
+
+    def _device_stack(self, frames, name):
+        import torch
+        if not isinstance(frames, torch.Tensor):
+            frames = torch.from_numpy(np.ascontiguousarray(np.stack([np.asarray(f) for f in frames])))
+        if frames.dtype != torch.uint8 or frames.dim() != 3:
+            raise ValueError(f'{name} must be one-channel uint8 frames (n, H, W), got {frames.dtype} {tuple(frames.shape)}: the device tracker '
+                             f'takes grey or luma only')
+        return frames.to(self.device).contiguous()
+
+    def track_stacks(self, d_early, d_late, chunk_pairs=32):
+        """[(early, late, homography) or (None, None, None)] for the pairs (d_early[i], d_late[i]) of two (n, H, W) uint8 device stacks,
+        `chunk_pairs` pairs per launch so that outputs and workspace stay bounded."""
+        from . import ops
+        if d_early.shape != d_late.shape:
+            raise ValueError('early and late stacks must have the same shape')
+        n, H, W = d_early.shape
+        grid = ops.track_subframe_grid(W, H, self.subframe_rows, self.subframe_cols)
+        chunk_pairs = max(1, min(int(chunk_pairs), 65535 // (2 * grid[2] * grid[3])))
+        out = []
+        for lo in range(0, n, chunk_pairs):
+            e, l = d_early[lo:lo + chunk_pairs], d_late[lo:lo + chunk_pairs]
+            points, counts, _ = ops.fast_corners(e, self.subframe_rows, self.subframe_cols, self.max_per_subframe, self.threshold)
+            moved, found = ops.lk_track(e, l, points, counts, self.subframe_rows, self.subframe_cols)
+            points, counts, moved, found = (t.cpu().numpy() for t in (points, counts, moved, found))
+            out.extend(finish_pair(grid, points[i], counts[i], moved[i], found[i], self.min_features) for i in range(len(points)))
+        return out
+
+    def track_clip(self, d_grey, chunk_pairs=32):
+        """The adjacent pairs (t, t + 1) of a resident (F, H, W) uint8 clip: F - 1 results."""
+        d_grey = self._device_stack(d_grey, 'd_grey')
+        if d_grey.shape[0] < 2:
+            raise ValueError('a clip needs at least 2 frames')
+        return self.track_stacks(d_grey[:-1], d_grey[1:], chunk_pairs)
+
+    def track_pair(self, early_frame, late_frame):
+        """(early_features, late_features, homography) of one frame pair, or (None, None, None) -- mfs.py:492-528."""
+        return self.track_pairs([early_frame], [late_frame])[0]
+
+    def track_pairs(self, first_frames, second_frames, workers=None, chunk_pairs=32):
+        """track_pair over many independent pairs, in order (`workers` is accepted for frontend_cv2.Tracker's signature and unused)."""
+        return self.track_stacks(self._device_stack(first_frames, 'first_frames'), self._device_stack(second_frames, 'second_frames'),
+                                 chunk_pairs)
