@@ -432,7 +432,7 @@ int mf_crop_resize_dev_p010(const uint16_t* d_y, const uint16_t* d_uv, uint16_t*
  * What the reference asks of cv2.FastFeatureDetector_create().detect and cv2.calcOpticalFlowPyrLK (their defaults), for one-channel uint8
  * images ONLY (grey clips, NV12 luma): bit for bit what tests/track_model.py computes, which restates OpenCV 4.5-4.10 with the five sums of
  * an LK window taken exactly in integers and rounded to float32 once (cv2 accumulates them in float32 in a SIMD-dependent order).  The
- * RANSAC outlier step and the homography are the caller's (meshflow_amd/host.py).
+ * RANSAC outlier step and the homography are the caller's (meshflow_amd/host.py; the outlier step also as mf_ransac_inliers_f32 below).
  * Sub-frames: as at mfs.py:493-504 a W x H frame is cut into sub-frames of ceil(W / sub_cols) x ceil(H / sub_rows) pixels, the last column /
  * row smaller; there are S = ceil(W / sub_w) * ceil(H / sub_h) of them (possibly fewer than sub_rows * sub_cols), numbered left outer, top
  * inner.  EACH SUB-FRAME IS AN IMAGE OF ITS OWN: FAST's 3-pixel margin, the pyramid's and the derivative's borders fall at its edges, and
@@ -460,6 +460,43 @@ int mf_fast_corners_u8(const uint8_t* d_grey, int n, int W, int H, int sub_rows,
 int mf_lk_track_u8(const uint8_t* d_early, const uint8_t* d_late, int n_pairs, int W, int H, int sub_rows, int sub_cols,
                    int max_per_subframe, const float* d_points, const int32_t* d_counts, float* d_moved, uint8_t* d_found, void* d_work,
                    void* stream);
+
+/* ---- between the two: outlier rejection per sub-frame and the packing of the survivors (mfs.py:564-579, 614, 626; 521, 578) ----
+ * What the reference asks of cv2.findHomography(..., method=cv2.RANSAC)[1] per sub-frame, as a specification of its own that a kernel can
+ * equal: bit for bit tests/ransac_model.py (stateless hash sampling, cv2's degenerate-sample test, a closed-form 4-point fit in float64, a
+ * division-free error test, three times cv2's adaptive iteration count, the best sample's consensus set as the mask; that file lists
+ * where it deviates from cv2 and from meshflow_amd/host.py's ransac_inliers).  The homography over the survivors stays with the caller
+ * (host.lsq_homography).
+ * Layouts: d_points, d_moved [n_pairs][S][max_per_subframe][2] float32, d_counts [n_pairs][S] int32 and d_found [n_pairs][S][max_per_subframe]
+ * uint8 as mf_fast_corners_u8 / mf_lk_track_u8 leave them (counts above max_per_subframe are read as max_per_subframe, negative ones as 0).
+ * mf_ransac_inliers_f32: the candidates of a sub-frame are its points i < count with d_found != 0, k of them.  d_inlier [n_pairs][S]
+ * [max_per_subframe] uint8: 1 for the candidates in the consensus set of the best hypothesis, 0 everywhere else (every entry is written).
+ * d_info [n_pairs][S][4] int32: {status, k, inliers, iterations run}; status MF_RANSAC_OK, MF_RANSAC_TOO_FEW (count, k below min_features
+ * -- mfs.py:614, 626 -- or k < 4; no iteration runs) or MF_RANSAC_NO_CONSENSUS (no sample had 4 inliers; collinear or identical points end
+ * here after max_iters skipped iterations): the sub-frame then contributes nothing, which is what the caller of cv2 does with a None mask.
+ * d_work: mf_ransac_workspace_bytes(...) bytes, 16-byte aligned: the compacted candidates of sub-frames that hold more than 1,024 of them (16
+ * bytes for max_per_subframe <= 1,024); 0 for arguments outside the limits.
+ * mf_track_gather_f64: per pair the inliers of the sub-frames with status MF_RANSAC_OK, sub-frame order outer, point order inner, as float64
+ * (x, y) = float32 coordinate + the sub-frame's integer offset (column * sub_w, row * sub_h) (mfs.py:578: exact), back to back in d_early,
+ * d_late [total][2] -- capacity n_pairs * S * max_per_subframe pairs -- with d_offsets [n_pairs + 1] int32: the layout mf_vertex_motion_f64
+ * takes.  A pair with fewer than min_features survivors (mfs.py:521) gets an empty range and MF_TRACK_PAIR_TOO_FEW in d_pair_status
+ * [n_pairs] int32, 0 otherwise.  No atomics: the order is part of the contract.  S = the sub-frames of W x H cut sub_rows x sub_cols.
+ * Limits (MF_ERR_INVALID_ARG, nothing launched): n_pairs >= 1 and S >= 1 with 2 * n_pairs * S <= 65,535; max_per_subframe in 1 ..
+ * MF_TRACK_MAX_PER_SUBFRAME; the tracker's limits on W, H, sub_rows, sub_cols; threshold finite and > 0; 0 < confidence < 1; max_iters in
+ * 1 .. MF_RANSAC_MAX_ITERS; min_features >= 1; null pointers; float and int arrays 8- / 4-byte aligned; outputs that overlap inputs or each other.
+ * Both calls are asynchronous on `stream`. */
+#define MF_RANSAC_OK 0
+#define MF_RANSAC_TOO_FEW 1
+#define MF_RANSAC_NO_CONSENSUS 2
+#define MF_RANSAC_MAX_ITERS 65536
+#define MF_TRACK_PAIR_TOO_FEW 1
+size_t mf_ransac_workspace_bytes(int n_pairs, int S, int max_per_subframe);
+int mf_ransac_inliers_f32(const float* d_points, const float* d_moved, const int32_t* d_counts, const uint8_t* d_found, int n_pairs, int S,
+                          int max_per_subframe, int min_features, double threshold, double confidence, int max_iters, uint32_t seed,
+                          uint8_t* d_inlier, int32_t* d_info, void* d_work, void* stream);
+int mf_track_gather_f64(const float* d_points, const float* d_moved, const uint8_t* d_inlier, const int32_t* d_info, int n_pairs, int W, int H,
+                        int sub_rows, int sub_cols, int max_per_subframe, int min_features, double* d_early, double* d_late,
+                        int32_t* d_offsets, int32_t* d_pair_status, void* stream);
 
 /* ---- the row before the path: vertex-motion accumulation (mfs.py:236-452 from the matched features on) ----
  * Replaces the Python loops of _get_vertex_nearby_feature_residual_velocities (mfs.py:365-452), the medians, global

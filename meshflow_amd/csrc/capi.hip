@@ -724,6 +724,93 @@ int mf_lk_track_u8(const uint8_t* d_early, const uint8_t* d_late, int n_pairs, i
     return launch_lk_levels(d_early, d_late, n_pairs, g, max_per_subframe, d_points, d_counts, d_moved, d_found, d_work, (hipStream_t)stream);
 }
 
+// The checks mf_ransac_inliers_f32 and its workspace size share: the sizes only.
+static int ransac_size_checks(const char* name, int n_pairs, int S, int max_per)
+{
+    if (max_per < 1 || max_per > MF_TRACK_MAX_PER_SUBFRAME) {
+        set_error("%s: max_per_subframe must be in 1 .. %d (got %d)", name, MF_TRACK_MAX_PER_SUBFRAME, max_per);
+        return MF_ERR_INVALID_ARG;
+    }
+    if (n_pairs < 1 || S < 1 || 2ll * n_pairs * S > 65535) {
+        set_error("%s: n_pairs and S must be at least 1 with 2 * n_pairs * S <= 65,535 (got n_pairs = %d, S = %d): too many for one call", name,
+                  n_pairs, S);
+        return MF_ERR_INVALID_ARG;
+    }
+    return MF_OK;
+}
+
+size_t mf_ransac_workspace_bytes(int n_pairs, int S, int max_per_subframe)
+{
+    if (ransac_size_checks("mf_ransac_workspace_bytes", n_pairs, S, max_per_subframe)) return 0;
+    return ransac_workspace_bytes(n_pairs, S, max_per_subframe);
+}
+
+int mf_ransac_inliers_f32(const float* d_points, const float* d_moved, const int32_t* d_counts, const uint8_t* d_found, int n_pairs, int S,
+                          int max_per_subframe, int min_features, double threshold, double confidence, int max_iters, uint32_t seed,
+                          uint8_t* d_inlier, int32_t* d_info, void* d_work, void* stream)
+{
+    const char* name = "mf_ransac_inliers_f32";
+    if (!d_points || !d_moved || !d_counts || !d_found || !d_inlier || !d_info || !d_work) { set_error("%s: null pointer", name); return MF_ERR_INVALID_ARG; }
+    if (const int rc = ransac_size_checks(name, n_pairs, S, max_per_subframe)) return rc;
+    if (min_features < 1) { set_error("%s: min_features must be at least 1 (got %d)", name, min_features); return MF_ERR_INVALID_ARG; }
+    if (!(threshold > 0.0) || !(threshold - threshold == 0.0)) { set_error("%s: threshold must be finite and > 0 (got %g)", name, threshold); return MF_ERR_INVALID_ARG; }
+    if (!(confidence > 0.0 && confidence < 1.0)) { set_error("%s: confidence must be in (0, 1) (got %g)", name, confidence); return MF_ERR_INVALID_ARG; }
+    if (max_iters < 1 || max_iters > MF_RANSAC_MAX_ITERS) {
+        set_error("%s: max_iters must be in 1 .. %d (got %d)", name, MF_RANSAC_MAX_ITERS, max_iters);
+        return MF_ERR_INVALID_ARG;
+    }
+    if (((uintptr_t)d_points & 7) || ((uintptr_t)d_moved & 7) || ((uintptr_t)d_counts & 3) || ((uintptr_t)d_info & 3) || ((uintptr_t)d_work & 15)) {
+        set_error("%s: d_points and d_moved must be 8-byte aligned, d_counts and d_info 4-byte aligned, d_work 16-byte aligned", name);
+        return MF_ERR_INVALID_ARG;
+    }
+    const size_t slots = (size_t)n_pairs * S, features = slots * max_per_subframe;
+    const struct { const void* at; size_t bytes; } in[4] = {{d_points, features * 8}, {d_moved, features * 8}, {d_counts, slots * 4}, {d_found, features}},
+                                                   out[3] = {{d_inlier, features}, {d_info, slots * 16},
+                                                             {d_work, ransac_workspace_bytes(n_pairs, S, max_per_subframe)}};
+    for (const auto& i : in)
+        for (const auto& o : out)
+            if (overlap(i.at, i.bytes, o.at, o.bytes)) { set_error("%s: an input aliases an output or the workspace", name); return MF_ERR_INVALID_ARG; }
+    for (int a = 0; a < 3; ++a)
+        for (int b = a + 1; b < 3; ++b)
+            if (overlap(out[a].at, out[a].bytes, out[b].at, out[b].bytes)) {
+                set_error("%s: two of d_inlier, d_info and d_work alias", name);
+                return MF_ERR_INVALID_ARG;
+            }
+    return launch_ransac(d_points, d_moved, d_counts, d_found, n_pairs, S, max_per_subframe, min_features, threshold, confidence, max_iters, seed,
+                         d_inlier, d_info, d_work, (hipStream_t)stream);
+}
+
+int mf_track_gather_f64(const float* d_points, const float* d_moved, const uint8_t* d_inlier, const int32_t* d_info, int n_pairs, int W, int H,
+                        int sub_rows, int sub_cols, int max_per_subframe, int min_features, double* d_early, double* d_late,
+                        int32_t* d_offsets, int32_t* d_pair_status, void* stream)
+{
+    const char* name = "mf_track_gather_f64";
+    if (!d_points || !d_moved || !d_inlier || !d_info || !d_early || !d_late || !d_offsets || !d_pair_status) {
+        set_error("%s: null pointer", name);
+        return MF_ERR_INVALID_ARG;
+    }
+    track::Geom g;
+    if (const int rc = track_checks(name, n_pairs, W, H, sub_rows, sub_cols, max_per_subframe, g)) return rc;
+    if (min_features < 1) { set_error("%s: min_features must be at least 1 (got %d)", name, min_features); return MF_ERR_INVALID_ARG; }
+    if (((uintptr_t)d_points & 7) || ((uintptr_t)d_moved & 7) || ((uintptr_t)d_early & 7) || ((uintptr_t)d_late & 7) || ((uintptr_t)d_info & 3) ||
+        ((uintptr_t)d_offsets & 3) || ((uintptr_t)d_pair_status & 3)) {
+        set_error("%s: d_points, d_moved, d_early and d_late must be 8-byte aligned, d_info, d_offsets and d_pair_status 4-byte aligned", name);
+        return MF_ERR_INVALID_ARG;
+    }
+    const size_t slots = (size_t)n_pairs * g.ncols * g.nrows, features = slots * max_per_subframe;
+    const struct { const void* at; size_t bytes; } in[4] = {{d_points, features * 8}, {d_moved, features * 8}, {d_inlier, features}, {d_info, slots * 16}},
+                                                   out[4] = {{d_early, features * 16}, {d_late, features * 16}, {d_offsets, ((size_t)n_pairs + 1) * 4},
+                                                             {d_pair_status, (size_t)n_pairs * 4}};
+    for (const auto& i : in)
+        for (const auto& o : out)
+            if (overlap(i.at, i.bytes, o.at, o.bytes)) { set_error("%s: an input aliases an output", name); return MF_ERR_INVALID_ARG; }
+    for (int a = 0; a < 4; ++a)
+        for (int b = a + 1; b < 4; ++b)
+            if (overlap(out[a].at, out[a].bytes, out[b].at, out[b].bytes)) { set_error("%s: two outputs alias", name); return MF_ERR_INVALID_ARG; }
+    return launch_track_gather(d_points, d_moved, d_inlier, d_info, n_pairs, g, max_per_subframe, min_features, d_early, d_late, d_offsets,
+                               d_pair_status, (hipStream_t)stream);
+}
+
 size_t mf_vertex_motion_workspace_bytes(int total_features, int max_per_pair, int P, int R, int C)
 {
     if (total_features < 0 || max_per_pair < 0 || P < 0 || R <= 0 || C <= 0) return 0;

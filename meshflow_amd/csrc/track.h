@@ -1,7 +1,8 @@
-// The device tracker's launchers (track_fast.hip, track_pyr.hip, track_lk.hip) behind capi.hip's checks.
+// The device tracker's launchers (track_fast.hip, track_pyr.hip, track_lk.hip, track_ransac.hip) behind capi.hip's checks.
 #pragma once
 #include "mf_common.h"
 #include "track_body.h"
+#include "ransac_body.h"
 
 namespace mf {
 
@@ -15,5 +16,13 @@ int launch_fast_corners(const uint8_t* grey, int n, const track::Geom& g, int ma
 int launch_pyramid(const uint8_t* early, const uint8_t* late, int n_pairs, const track::Geom& g, void* work, hipStream_t st);
 int launch_lk_levels(const uint8_t* early, const uint8_t* late, int n_pairs, const track::Geom& g, int max_per, const float* points,
                      const int32_t* counts, float* moved, uint8_t* found, const void* work, hipStream_t st);
+// track_ransac.hip: the outlier step per sub-frame (workspace: the compacted candidates of sub-frames beyond ransac::STAGED) and the gather
+// of the survivors into mf_vertex_motion_f64's layout
+size_t ransac_workspace_bytes(int n_pairs, int S, int max_per);
+int launch_ransac(const float* points, const float* moved, const int32_t* counts, const uint8_t* found, int n_pairs, int S, int max_per,
+                  int min_features, double threshold, double confidence, int max_iters, uint32_t seed, uint8_t* inlier, int32_t* info, void* work,
+                  hipStream_t st);
+int launch_track_gather(const float* points, const float* moved, const uint8_t* inlier, const int32_t* info, int n_pairs, const track::Geom& g,
+                        int max_per, int min_features, double* early, double* late, int32_t* offsets, int32_t* pair_status, hipStream_t st);
 
 }  // namespace mf

@@ -785,6 +785,70 @@ def lk_track(early, late, points, counts, sub_rows, sub_cols):
     return moved, found
 
 
+def _need_tracks(points, moved, name):
+    """points / moved (n, S, max_per_subframe, 2) float32 on one device: (n, S, max_per_subframe)."""
+    _need(points, torch.float32, 'points')
+    _need(moved, torch.float32, 'moved')
+    if points.dim() != 4 or points.shape[3] != 2 or min(points.shape[:3]) < 1:
+        raise ValueError(f'{name}: points must have shape (n, S, max_per_subframe, 2), got {tuple(points.shape)}')
+    if moved.shape != points.shape or moved.device != points.device:
+        raise ValueError(f'{name}: moved must have the shape and device of points (got {tuple(moved.shape)} and {tuple(points.shape)})')
+    return tuple(points.shape[:3])
+
+
+def _need_like(t, dtype, shape, device, what, name):
+    _need(t, dtype, what)
+    if tuple(t.shape) != tuple(shape) or t.device != device:
+        raise ValueError(f'{name}: {what} must have shape {tuple(shape)} on the device of points (got {tuple(t.shape)})')
+
+
+def ransac_inliers(points, counts, moved, found, min_features=4, threshold=3.0, confidence=0.995, max_iters=2000, seed=0):
+    """The outlier step per sub-frame on the device (mfs.py:564-579, 614, 626), bit for bit tests/ransac_model.py: `fast_corners`' points and
+    counts, `lk_track`'s moved and found.  Returns (inlier (n, S, max_per_subframe) uint8 -- 1 for the candidates in the best hypothesis'
+    consensus set --, info (n, S, 4) int32 -- (status, candidates, inliers, iterations run), status _lib.RANSAC_OK / RANSAC_TOO_FEW /
+    RANSAC_NO_CONSENSUS)."""
+    name = 'ransac_inliers'
+    n, S, max_per_subframe = _need_tracks(points, moved, name)
+    dev = points.device
+    _need_like(counts, torch.int32, (n, S), dev, 'counts', name)
+    _need_like(found, torch.uint8, (n, S, max_per_subframe), dev, 'found', name)
+    seed = int(seed)
+    if not 0 <= seed < 1 << 32:
+        raise ValueError(f'{name}: seed must be in 0 .. 2^32 - 1 (got {seed})')
+    inlier = torch.empty((n, S, max_per_subframe), dtype=torch.uint8, device=dev)
+    info = torch.empty((n, S, 4), dtype=torch.int32, device=dev)
+    size = _lib_.mf_ransac_workspace_bytes(n, S, max_per_subframe)
+    work = torch.empty(size if size else 16, dtype=torch.uint8, device=dev)      # (0: outside the limits -- let the call itself say which)
+    _lib.check(_lib_.mf_ransac_inliers_f32(_ptr(points), _ptr(moved), _ptr(counts), _ptr(found), n, S, max_per_subframe, int(min_features),
+                                           float(threshold), float(confidence), int(max_iters), seed, _ptr(inlier), _ptr(info), _ptr(work),
+                                           _stream()))
+    return inlier, info
+
+
+def gather_inliers(points, moved, inlier, info, W, H, sub_rows, sub_cols, min_features):
+    """The survivors of `ransac_inliers` packed per pair as `host.pack_features` packs `tracker.finish_pair`'s (mfs.py:521, 578): sub-frame
+    order outer, point order inner, float64 frame coordinates.  Returns (early (K_total, 2) float64, late, offsets (n + 1,) int32, pair_status
+    (n,) int32 -- _lib.TRACK_PAIR_TOO_FEW where a pair has fewer than min_features survivors: its range is empty): what `vertex_motion` takes.
+    Reads offsets[-1] to size the result, so it waits for the stream."""
+    name = 'gather_inliers'
+    n, S, max_per_subframe = _need_tracks(points, moved, name)
+    dev = points.device
+    _, _, cols, rows = track_subframe_grid(W, H, sub_rows, sub_cols)
+    if cols * rows != S:
+        raise ValueError(f'{name}: {W} x {H} cut {sub_rows} x {sub_cols} has {cols * rows} sub-frames, points has {S}')
+    _need_like(inlier, torch.uint8, (n, S, max_per_subframe), dev, 'inlier', name)
+    _need_like(info, torch.int32, (n, S, 4), dev, 'info', name)
+    early = torch.empty((n * S * max_per_subframe, 2), dtype=torch.float64, device=dev)
+    late = torch.empty_like(early)
+    offsets = torch.empty(n + 1, dtype=torch.int32, device=dev)
+    pair_status = torch.empty(n, dtype=torch.int32, device=dev)
+    _lib.check(_lib_.mf_track_gather_f64(_ptr(points), _ptr(moved), _ptr(inlier), _ptr(info), n, int(W), int(H), int(sub_rows), int(sub_cols),
+                                         max_per_subframe, int(min_features), _ptr(early), _ptr(late), _ptr(offsets), _ptr(pair_status),
+                                         _stream()))
+    total = int(offsets[-1].item())
+    return early[:total], late[:total], offsets, pair_status
+
+
 def vertex_motion(early, late, offsets, homographies, max_per_pair, W, H, R, C, ellipse_rows, ellipse_cols):
     """Vertex velocities and their running sum from matched features (mfs.py:236-452 after the tracker).
     early/late: (K_total, 2) float64 device tensors; offsets: (P+1,) int32; homographies: (P, 3, 3) float64.
