@@ -498,6 +498,37 @@ int mf_track_gather_f64(const float* d_points, const float* d_moved, const uint8
                         int sub_rows, int sub_cols, int max_per_subframe, int min_features, double* d_early, double* d_late,
                         int32_t* d_offsets, int32_t* d_pair_status, void* stream);
 
+/* ---- the homography over a pair's survivors (mfs.py:524-526) ----
+ * What the reference asks of cv2.findHomography(early, late)[0] per pair, as a specification of its own that a kernel can equal:
+ * bit for bit tests/homography_model.py (Hartley's similarity exactly as meshflow_amd/host.py's _normalisation defines it, the 9 x 9 normal matrix
+ * of the DLT rows from 24 sums -- the 2K x 9 matrix is never formed --, its smallest eigenvector by cyclic Jacobi rotations, the way back
+ * in closed form, h22 = 1; that file lists where it deviates from host.lsq_homography and from cv2: no Levenberg-Marquardt refinement, no
+ * SVD).  Every sum over a pair's points has ONE order, the same for every launch: 256 strided partial sums from +0.0, a halving tree per
+ * 64 of them, (w0 + w1) + (w2 + w3).  No atomics: the order is part of the contract.
+ * Layouts: d_early, d_late [K_total][2] float64 and d_offsets [n_pairs + 1] int32 as mf_track_gather_f64 leaves them and
+ * mf_vertex_motion_f64 takes them.  A pair whose range is not 0 <= d_offsets[p] <= d_offsets[p + 1] <= K_total is read as empty: no load
+ * leaves d_early / d_late whatever d_offsets holds.  d_h [n_pairs][9] float64, row-major, what mf_vertex_motion_f64 takes as d_hom.
+ * d_info [n_pairs][4] int32: {status, K, sweeps run, index of the chosen eigenvalue}.  d_diag [n_pairs][8] float64: {early scale, late
+ * scale, early centroid x, y, late centroid x, y, smallest eigenvalue, second smallest}: a mismatch against the model names its stage.
+ * Refusals per pair -- d_h is then the IDENTITY, so that later stages stay defined until the caller has looked, and d_diag is 0 where
+ * undefined --: MF_HFIT_TOO_FEW (K < 4), MF_HFIT_COLLINEAR (either cloud on one line or one point: the smaller eigenvalue of its centred
+ * second moments <= 1e-18 max(larger, 1); non-finite coordinates end here too), MF_HFIT_AT_INFINITY (|h22| <= 1e-12 max |h|, host.py's
+ * test) and MF_HFIT_NOT_CONVERGED (a rotation in each of 30 sweeps: never expected).
+ * d_work: mf_homography_fit_workspace_bytes(n_pairs) bytes, 8-byte aligned: 24 doubles per pair between the two kernels; 0 for n_pairs
+ * outside the limits.
+ * Limits (MF_ERR_INVALID_ARG, nothing launched): n_pairs in 0 .. 32,767 (the tracker's own: 2 * n_pairs * S <= 65,535), K_total >= 0; null
+ * pointers (d_early and d_late may be null where K_total is 0); float64 and int32 arrays 8- / 4-byte aligned; outputs that overlap inputs,
+ * the workspace or each other.  n_pairs == 0 succeeds and launches nothing.  Asynchronous on `stream`. */
+#define MF_HFIT_OK 0
+#define MF_HFIT_TOO_FEW 1
+#define MF_HFIT_COLLINEAR 2
+#define MF_HFIT_AT_INFINITY 3
+#define MF_HFIT_NOT_CONVERGED 4
+#define MF_HFIT_MAX_PAIRS 32767
+size_t mf_homography_fit_workspace_bytes(int n_pairs);
+int mf_homography_fit_f64(const double* d_early, const double* d_late, const int32_t* d_offsets, int n_pairs, int K_total, double* d_h,
+                          int32_t* d_info, double* d_diag, void* d_work, void* stream);
+
 /* ---- the row before the path: vertex-motion accumulation (mfs.py:236-452 from the matched features on) ----
  * Replaces the Python loops of _get_vertex_nearby_feature_residual_velocities (mfs.py:365-452), the medians, global
  * motion and median blur of _get_unstabilized_vertex_velocities (mfs.py:316-362, everything after the tracker call)

@@ -811,6 +811,46 @@ int mf_track_gather_f64(const float* d_points, const float* d_moved, const uint8
                                d_pair_status, (hipStream_t)stream);
 }
 
+size_t mf_homography_fit_workspace_bytes(int n_pairs)
+{
+    if (n_pairs < 0 || n_pairs > hfit::MAX_PAIRS) return 0;
+    return hfit_workspace_bytes(n_pairs);
+}
+
+int mf_homography_fit_f64(const double* d_early, const double* d_late, const int32_t* d_offsets, int n_pairs, int K_total, double* d_h,
+                          int32_t* d_info, double* d_diag, void* d_work, void* stream)
+{
+    const char* name = "mf_homography_fit_f64";
+    if (n_pairs < 0 || K_total < 0) { set_error("%s: n_pairs and K_total must not be negative (got %d, %d)", name, n_pairs, K_total); return MF_ERR_INVALID_ARG; }
+    if (n_pairs > hfit::MAX_PAIRS) {
+        set_error("%s: n_pairs must be at most %d, the tracker's own limit (got %d): too many for one call", name, hfit::MAX_PAIRS, n_pairs);
+        return MF_ERR_INVALID_ARG;
+    }
+    if (!d_offsets || !d_h || !d_info || !d_diag || !d_work || (K_total > 0 && (!d_early || !d_late))) {
+        set_error("%s: null pointer", name);
+        return MF_ERR_INVALID_ARG;
+    }
+    if (((uintptr_t)d_early & 7) || ((uintptr_t)d_late & 7) || ((uintptr_t)d_h & 7) || ((uintptr_t)d_diag & 7) || ((uintptr_t)d_work & 7) ||
+        ((uintptr_t)d_offsets & 3) || ((uintptr_t)d_info & 3)) {
+        set_error("%s: d_early, d_late, d_h, d_diag and d_work must be 8-byte aligned, d_offsets and d_info 4-byte aligned", name);
+        return MF_ERR_INVALID_ARG;
+    }
+    const size_t P = (size_t)n_pairs, features = (size_t)K_total;
+    const struct { const void* at; size_t bytes; } in[3] = {{d_early, features * 16}, {d_late, features * 16}, {d_offsets, (P + 1) * 4}},
+                                                   out[4] = {{d_h, P * 72}, {d_info, P * 16}, {d_diag, P * 64}, {d_work, hfit_workspace_bytes(n_pairs)}};
+    for (const auto& i : in)
+        for (const auto& o : out)
+            if (overlap(i.at, i.bytes, o.at, o.bytes)) { set_error("%s: an input aliases an output or the workspace", name); return MF_ERR_INVALID_ARG; }
+    for (int a = 0; a < 4; ++a)
+        for (int b = a + 1; b < 4; ++b)
+            if (overlap(out[a].at, out[a].bytes, out[b].at, out[b].bytes)) {
+                set_error("%s: two of d_h, d_info, d_diag and d_work alias", name);
+                return MF_ERR_INVALID_ARG;
+            }
+    if (n_pairs == 0) return MF_OK;
+    return launch_homography_fit(d_early, d_late, d_offsets, n_pairs, K_total, d_h, d_info, d_diag, d_work, (hipStream_t)stream);
+}
+
 size_t mf_vertex_motion_workspace_bytes(int total_features, int max_per_pair, int P, int R, int C)
 {
     if (total_features < 0 || max_per_pair < 0 || P < 0 || R <= 0 || C <= 0) return 0;

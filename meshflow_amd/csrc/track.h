@@ -1,8 +1,9 @@
-// The device tracker's launchers (track_fast.hip, track_pyr.hip, track_lk.hip, track_ransac.hip) behind capi.hip's checks.
+// The device tracker's launchers (track_fast.hip, track_pyr.hip, track_lk.hip, track_ransac.hip, track_fit.hip) behind capi.hip's checks.
 #pragma once
 #include "mf_common.h"
 #include "track_body.h"
 #include "ransac_body.h"
+#include "hfit_body.h"
 
 namespace mf {
 
@@ -24,5 +25,9 @@ int launch_ransac(const float* points, const float* moved, const int32_t* counts
                   hipStream_t st);
 int launch_track_gather(const float* points, const float* moved, const uint8_t* inlier, const int32_t* info, int n_pairs, const track::Geom& g,
                         int max_per, int min_features, double* early, double* late, int32_t* offsets, int32_t* pair_status, hipStream_t st);
+// track_fit.hip: the homography over each pair's packed survivors (workspace: the 23 sums of each pair's normal matrix between its two kernels)
+size_t hfit_workspace_bytes(int n_pairs);
+int launch_homography_fit(const double* early, const double* late, const int32_t* offsets, int n_pairs, int K_total, double* hom, int32_t* info,
+                          double* diag, void* work, hipStream_t st);
 
 }  // namespace mf

@@ -148,7 +148,9 @@ def pack_features(features_by_pair):
 # Levenberg-Marquardt refinement.  This is a documented deviation, like the mesh-based cropping ratio above: samples of 4 come from
 # `synthetic.hash32` counters (the same on every platform), degenerate samples are skipped, the number of iterations follows cv2's adaptive
 # formula (RANSACUpdateNumIters), the mask is the best sample's consensus set, and every fit is a normalised DLT in float64.  There is NO
-# Levenberg-Marquardt refinement.
+# Levenberg-Marquardt refinement.  `lsq_homography` is the specification of the tracker's fit='host' mode; fit='device' (`ops.fit_homographies`)
+# has its own, tests/homography_model.py -- the same similarity and the same algebraic error through the 9 x 9 normal matrix instead of an
+# SVD -- and nothing here changes for it.
 
 def _points(a, name):
     a = np.asarray(a, dtype=np.float64)

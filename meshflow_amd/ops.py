@@ -849,6 +849,41 @@ def gather_inliers(points, moved, inlier, info, W, H, sub_rows, sub_cols, min_fe
     return early[:total], late[:total], offsets, pair_status
 
 
+def fit_homographies(early, late, offsets):
+    """The homography over each pair's packed survivors on the device (mfs.py:524-526), bit for bit tests/homography_model.py -- a
+    specification of its own, not `host.lsq_homography`: the two minimise the same algebraic error in the same normalised coordinates and
+    differ by rounding.  early / late (K_total, 2) float64 and offsets (P + 1,) int32 as `gather_inliers` leaves them.  Returns
+    (homographies (P, 3, 3) float64 -- what `vertex_motion` takes --, info (P, 4) int32 -- (status, K, sweeps run, index of the chosen
+    eigenvalue), status _lib.HFIT_OK / HFIT_TOO_FEW / HFIT_COLLINEAR / HFIT_AT_INFINITY / HFIT_NOT_CONVERGED --, diag (P, 8) float64 -- the
+    two scales, the two centroids, the smallest and second smallest eigenvalue).  A pair that is not HFIT_OK gets the identity.  Runs on
+    torch's current stream and does not wait for it: `fit_check` does."""
+    name = 'fit_homographies'
+    _need(early, torch.float64, 'early')
+    _need(late, torch.float64, 'late')
+    _need(offsets, torch.int32, 'offsets')
+    if early.dim() != 2 or early.shape[1] != 2 or late.shape != early.shape or late.device != early.device:
+        raise ValueError(f'{name}: early and late must be (K_total, 2) points on one device, got {tuple(early.shape)} and {tuple(late.shape)}')
+    if offsets.dim() != 1 or offsets.numel() < 1 or offsets.device != early.device:
+        raise ValueError(f'{name}: offsets must have shape (P + 1,) on the device of early, got {tuple(offsets.shape)}')
+    P, K, dev = offsets.numel() - 1, early.shape[0], early.device
+    homographies = torch.empty((P, 3, 3), dtype=torch.float64, device=dev)
+    info = torch.empty((P, 4), dtype=torch.int32, device=dev)
+    diag = torch.empty((P, 8), dtype=torch.float64, device=dev)
+    size = _lib_.mf_homography_fit_workspace_bytes(P)
+    work = torch.empty(size if size else 16, dtype=torch.uint8, device=dev)      # (0: outside the limits -- let the call itself say which)
+    # (an empty tensor has no address; the call takes null features where K_total is 0, and every output of P == 0 is empty as well)
+    held = [t if t.numel() else torch.empty(16, dtype=torch.uint8, device=dev) for t in (homographies, info, diag)]
+    _lib.check(_lib_.mf_homography_fit_f64(_ptr(early) if K else None, _ptr(late) if K else None, _ptr(offsets), P, K, _ptr(held[0]), _ptr(held[1]),
+                                           _ptr(held[2]), _ptr(work), _stream()))
+    return homographies, info, diag
+
+
+def fit_check(info):
+    """The first pair of `fit_homographies`' info whose status is not _lib.HFIT_OK, or None.  Waits for the stream."""
+    bad = torch.nonzero(info[:, 0] != _lib.HFIT_OK)
+    return int(bad[0].item()) if bad.numel() else None
+
+
 def vertex_motion(early, late, offsets, homographies, max_per_pair, W, H, R, C, ellipse_rows, ellipse_cols):
     """Vertex velocities and their running sum from matched features (mfs.py:236-452 after the tracker).
     early/late: (K_total, 2) float64 device tensors; offsets: (P+1,) int32; homographies: (P, 3, 3) float64.

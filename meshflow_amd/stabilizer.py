@@ -237,26 +237,42 @@ class MeshFlowStabilizer:
         return self._get_unstabilized_vertex_displacements_from_features(
             num_frames, frame_width, frame_height, [(e, l) for e, l, _ in tracked], homographies)
 
-    def device_tracker(self, max_per_subframe=1024, outliers='host'):
-        """The tracker that needs no OpenCV (tracker.py): FAST + LK as HIP kernels, the homography in NumPy, the outlier step in NumPy
-        (outliers='host') or as a HIP kernel (outliers='device')."""
+    def device_tracker(self, max_per_subframe=1024, outliers='host', fit='host'):
+        """The tracker that needs no OpenCV (tracker.py): FAST + LK as HIP kernels, the outlier step in NumPy (outliers='host') or as a HIP
+        kernel (outliers='device'), the homography in NumPy (fit='host') or as HIP kernels (fit='device', with outliers='device' only)."""
         from . import tracker
-        tracker.check_outliers(outliers)
+        tracker.check_fit(fit, tracker.check_outliers(outliers))
         return tracker.DeviceTracker(self.mesh_outlier_subframe_row_count, self.mesh_outlier_subframe_col_count,
                                      self.homography_min_number_corresponding_features, self._torch_device(), max_per_subframe,
-                                     outliers=outliers)
+                                     outliers=outliers, fit=fit)
 
-    def estimate_motion(self, d_grey, chunk_pairs=32, max_per_subframe=1024, outliers='host'):
+    def estimate_motion(self, d_grey, chunk_pairs=32, max_per_subframe=1024, outliers='host', fit='host'):
         """mfs.py:236-284 for a clip that is already on the device: `d_grey` (F, H, W) uint8 -- grey frames or the luma plane of an NV12
         clip -- through `device_tracker()` and `_get_unstabilized_vertex_displacements_from_features`.  Returns (d_disp (F, R+1, C+1, 2)
         float64 device tensor, homographies (F, 3, 3) float64 with the identity last, mfs.py:273-274): what `stabilize_resident`,
         `stabilized_nv12`, `stabilized_p010` and `stabilized_planes` take.  ValueError where a pair cannot be tracked, as in
         `_get_unstabilized_vertex_displacements_and_homographies`.  outliers='device': the outlier step runs on the device as well
         (`ops.ransac_inliers`, tests/ransac_model.py), the packed features go straight to `ops.vertex_motion` and d_disp never visits the
-        host; only the survivors come down, for the one homography fit per pair."""
+        host; only the survivors come down, for the one homography fit per pair.  fit='device' (with outliers='device'): that fit runs on the
+        device too (`ops.fit_homographies`, tests/homography_model.py -- within rounding of the host fit), its homographies go to
+        `ops.vertex_motion` as they are, and all that comes down is the (F - 1, 9) matrices and their (F - 1, 4) records."""
         import torch
         from . import ops, tracker
-        if tracker.check_outliers(outliers) == 'device':
+        if tracker.check_fit(fit, tracker.check_outliers(outliers)) == 'device':
+            d_early, d_late, d_offsets, kmax, d_hom, d_info = self.device_tracker(max_per_subframe, outliers, fit).track_clip_resident(d_grey, chunk_pairs)
+            num_frames, frame_height, frame_width = d_grey.shape
+            d_disp, _, status = ops.vertex_motion(d_early, d_late, d_offsets, d_hom, kmax, frame_width, frame_height, self.mesh_row_count,
+                                                  self.mesh_col_count, self.feature_ellipse_row_count, self.feature_ellipse_col_count)
+            t = ops.fit_check(d_info)
+            if t is not None:
+                raise ValueError(f'fewer than {self.homography_min_number_corresponding_features} features could be '
+                                 f'tracked from frame {t} to frame {t + 1}')
+            ops.vertex_motion_check(status)
+            homographies = np.empty((num_frames, 3, 3))
+            homographies[:-1] = d_hom.cpu().numpy()
+            homographies[-1] = np.identity(3)                                               # mfs.py:274
+            return d_disp, homographies
+        if outliers == 'device':
             tracked, (d_early, d_late, d_offsets, kmax) = self.device_tracker(max_per_subframe, outliers).track_clip_packed(d_grey, chunk_pairs)
         else:
             tracked = self.device_tracker(max_per_subframe).track_clip(d_grey, chunk_pairs)
