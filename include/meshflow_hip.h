@@ -529,6 +529,26 @@ size_t mf_homography_fit_workspace_bytes(int n_pairs);
 int mf_homography_fit_f64(const double* d_early, const double* d_late, const int32_t* d_offsets, int n_pairs, int K_total, double* d_h,
                           int32_t* d_info, double* d_diag, void* d_work, void* stream);
 
+/* ---- the scores from tracked features: cropping ratio and distortion score (mfs.py:1196-1212 after the tracker) ----
+ * The reference tracks (unstabilized frame t, cropped frame t) and reads two numbers off each homography: 1 / (h00 h11), and the ratio of
+ * the two largest eigenvalue magnitudes of its affine part; the clip's cropping ratio is the float32 mean of the first, its distortion
+ * score the float32 MINIMUM of the second (the code's choice at mfs.py:1212; its docstring says "greatest").  Bit for bit
+ * tests/scores_model.py: the eigenvalues of the 2 x 2 block in closed form from float64 + - * / and sqrt (not np.linalg.eigvals, which no
+ * kernel equals bit for bit; the two agree within one float32 ulp, tests/test_scores_model.py), IEEE throughout -- a zero h00 h11 gives an
+ * infinity, nothing is refused -- and every float32 NaN is the quiet NaN 0x7FC00000.
+ * d_h [pairs][9] float64, row-major, as mf_homography_fit_f64 leaves them.  d_info: that call's record [pairs][4] int32, or null.  With a
+ * record only the pairs whose status is MF_HFIT_OK are scored (a refused pair holds the identity, which is no measurement); without one,
+ * all are.  d_pair_scores [pairs][2] float32: {ratio, distortion} of each pair, two NaNs where it was not scored.  d_scores float[2]:
+ * {cropping_ratio, distortion_score}, two NaNs where no pair was scored; the distortion score is a NaN where any scored pair's is.
+ * d_record int32[2]: {pairs scored, the first pair that was not scored or -1}.
+ * The mean is float32(sum / count) with the float64 sum in ONE order, the homography fit's: 256 strided partial sums from +0.0, a halving
+ * tree per 64 of them, (w0 + w1) + (w2 + w3); the minimum folds in the same order.  No atomics.  One launch of one 256-lane workgroup.
+ * Limits (MF_ERR_INVALID_ARG, nothing launched): 1 <= pairs <= MF_SCORES_MAX_PAIRS (1,048,576); null pointers other than d_info; d_h
+ * 8-byte and the other arrays 4-byte aligned; outputs that overlap inputs or each other.  Asynchronous on `stream`. */
+#define MF_SCORES_MAX_PAIRS 1048576
+int mf_feature_scores_f64(const double* d_h, const int32_t* d_info, int pairs, float* d_pair_scores, float* d_scores, int32_t* d_record,
+                          void* stream);
+
 /* ---- the row before the path: vertex-motion accumulation (mfs.py:236-452 from the matched features on) ----
  * Replaces the Python loops of _get_vertex_nearby_feature_residual_velocities (mfs.py:365-452), the medians, global
  * motion and median blur of _get_unstabilized_vertex_velocities (mfs.py:316-362, everything after the tracker call)

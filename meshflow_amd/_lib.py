@@ -16,6 +16,7 @@ CELL_DOUBLES = 32
 TRACK_MIN_SUBFRAME, TRACK_MAX_PER_SUBFRAME, TRACK_OVERFLOW = 2, 16384, 1
 RANSAC_OK, RANSAC_TOO_FEW, RANSAC_NO_CONSENSUS, RANSAC_MAX_ITERS, TRACK_PAIR_TOO_FEW = 0, 1, 2, 65536, 1
 HFIT_OK, HFIT_TOO_FEW, HFIT_COLLINEAR, HFIT_AT_INFINITY, HFIT_NOT_CONVERGED, HFIT_MAX_PAIRS = 0, 1, 2, 3, 4, 32767
+SCORES_MAX_PAIRS = 1 << 20
 CELL_OFF_M, CELL_OFF_HI, CELL_OFF_RECT, CELL_OFF_BBOX, CELL_OFF_STATUS = 0, 9, 18, 22, 26
 
 _vp = ctypes.c_void_p
@@ -94,6 +95,7 @@ SIGNATURES = {
     'mf_track_gather_f64': (_i, [_vp] * 4 + [_i] * 7 + [_vp] * 5),
     'mf_homography_fit_workspace_bytes': (_sz, [_i]),
     'mf_homography_fit_f64': (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    'mf_feature_scores_f64': (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp]),
     'mf_vertex_motion_workspace_bytes': (_sz, [_i, _i, _i, _i, _i]),
     'mf_vertex_motion_f64': (_i, [_vp, _vp, _vp, _vp] + [_i] * 9 + [_vp, _vp, _vp, _vp, _vp]),
     'mf_stability_score_f64': (_i, [_vp, _i, _i, _vp, _vp, _vp]),

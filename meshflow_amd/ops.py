@@ -884,6 +884,39 @@ def fit_check(info):
     return int(bad[0].item()) if bad.numel() else None
 
 
+def feature_scores(homographies, info=None):
+    """The cropping ratio and the distortion score of a clip from its per-frame (unstabilized -> cropped) homographies on the device
+    (mfs.py:1196-1212 after the tracker), bit for bit tests/scores_model.py -- the eigenvalues of the affine part in closed form, not
+    np.linalg.eigvals; the two agree within one float32 ulp.  homographies (P, 3, 3) float64 and info (P, 4) int32 as `fit_homographies`
+    returns them: with info only the pairs whose status is _lib.HFIT_OK are scored, without it all are.  Returns (scores (2,) float32 --
+    (cropping_ratio, distortion_score), two NaNs where no pair was scored --, per_pair (P, 2) float32 -- each pair's (ratio, distortion),
+    NaNs where it was not scored --, record (2,) int32 -- (pairs scored, the first pair that was not scored or -1)).  One launch on torch's
+    current stream; does not wait for it: `feature_scores_check` does."""
+    name = 'feature_scores'
+    _need(homographies, torch.float64, 'homographies')
+    if homographies.dim() != 3 or tuple(homographies.shape[1:]) != (3, 3):
+        raise ValueError(f'{name}: homographies must have shape (P, 3, 3), got {tuple(homographies.shape)}')
+    P, dev = homographies.shape[0], homographies.device
+    if info is not None:
+        _need(info, torch.int32, 'info')
+        if tuple(info.shape) != (P, 4) or info.device != dev:
+            raise ValueError(f'{name}: info must have shape ({P}, 4) on the device of homographies, got {tuple(info.shape)}')
+    if P < 1:
+        raise ValueError(f'{name}: no pair to score (homographies has shape {tuple(homographies.shape)})')
+    scores = torch.empty(2, dtype=torch.float32, device=dev)
+    per_pair = torch.empty((P, 2), dtype=torch.float32, device=dev)
+    record = torch.empty(2, dtype=torch.int32, device=dev)
+    _lib.check(_lib_.mf_feature_scores_f64(_ptr(homographies), _ptr(info) if info is not None else None, P, _ptr(per_pair), _ptr(scores),
+                                           _ptr(record), _stream()))
+    return scores, per_pair, record
+
+
+def feature_scores_check(record):
+    """The first pair `feature_scores` did not score (its record's second word), or None.  Waits for the stream."""
+    first = int(record[1].item())
+    return None if first < 0 else first
+
+
 def vertex_motion(early, late, offsets, homographies, max_per_pair, W, H, R, C, ellipse_rows, ellipse_cols):
     """Vertex velocities and their running sum from matched features (mfs.py:236-452 after the tracker).
     early/late: (K_total, 2) float64 device tensors; offsets: (P+1,) int32; homographies: (P, 3, 3) float64.

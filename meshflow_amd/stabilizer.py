@@ -301,6 +301,62 @@ class MeshFlowStabilizer:
         return frontend_cv2.cropping_and_distortion(self._tracker(), unstabilized_frames[:num_frames],
                                                     cropped_frames[:num_frames])
 
+    def cropping_and_distortion_resident(self, d_unstabilized, d_cropped, chunk_pairs=32, max_per_subframe=1024):
+        """mfs.py:1160-1212 for two resident (F, H, W) uint8 stacks of equal shape -- grey frames or luma planes, the unstabilized clip and
+        its stabilized, cropped version scaled back to the clip's own size -- without OpenCV: `device_tracker(max_per_subframe, 'device',
+        'device').track_stacks_resident` on the pairs (unstabilized[t], cropped[t]), then `ops.feature_scores` with the fit's record
+        (tests/scores_model.py: within one float32 ulp per frame of the reference's np.linalg.eigvals formulation).  Returns
+        (cropping_ratio, distortion_score) as np.float32 -- the float32 mean and the float32 MINIMUM, the reference's choices.  Where the
+        tracker fits no homography for a frame the reference dies with a TypeError on None; this raises a ValueError that names the frame.
+        Everything runs on torch's current stream; the call waits for it once, for the 8-byte record and the two scores."""
+        import torch
+        from . import ops
+        for t, name in ((d_unstabilized, 'd_unstabilized'), (d_cropped, 'd_cropped')):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() != 3:
+                raise ValueError(f'{name} must be a one-channel uint8 tensor (F, H, W): the device tracker takes grey or luma only')
+        if d_unstabilized.shape != d_cropped.shape:
+            raise ValueError(f"the feature scores need the crop at the clip's own size: the unstabilized stack is "
+                             f'{tuple(d_unstabilized.shape)}, the cropped one {tuple(d_cropped.shape)} (crop without output_size)')
+        tracker = self.device_tracker(max_per_subframe, 'device', 'device')
+        tracked = tracker.track_stacks_resident(tracker._device_stack(d_unstabilized, 'd_unstabilized'),
+                                                tracker._device_stack(d_cropped, 'd_cropped'), chunk_pairs)
+        scores, _, record = ops.feature_scores(tracked[4], tracked[5])
+        t = ops.feature_scores_check(record)
+        if t is not None:
+            raise ValueError(f'fewer than {self.homography_min_number_corresponding_features} features could be tracked from unstabilized '
+                             f'frame {t} to cropped frame {t}')
+        cropping_ratio, distortion_score = scores.cpu().numpy()
+        return cropping_ratio, distortion_score
+
+    def stabilize_scored(self, clip, adaptive_weights_definition=ADAPTIVE_WEIGHTS_DEFINITION_ORIGINAL, chunk_pairs=32, max_per_subframe=1024):
+        """The reference's stabilize() between decoder and encoder (mfs.py:140-169) for a resident clip, without OpenCV: `clip` is an
+        (F, H, W) uint8 grey tensor or an NV12 pair (d_y (F, H, W), d_uv (F, H/2, W/2, 2)).  In order: `estimate_motion(luma,
+        outliers='device', fit='device')`; `stabilize_resident(crop=True)` for grey or `stabilized_nv12(crop=True)` for NV12;
+        `cropping_and_distortion_resident(luma, cropped luma)`; `_compute_stability_score_device` on the stabilized vertex paths.  Returns
+        (the cropped clip in the input's form, (cropping_ratio, distortion_score, stability_score)) -- the reference's order, mfs.py:169;
+        the first two np.float32, the third a float.  Every ValueError of those calls is this one's."""
+        nv12 = isinstance(clip, (tuple, list))
+        if nv12:
+            if len(clip) != 2:
+                raise ValueError('an NV12 clip is the pair (d_y, d_uv)')
+            d_y, d_uv = clip
+            luma = d_y
+        else:
+            luma = clip
+        d_disp, homographies = self.estimate_motion(luma, chunk_pairs, max_per_subframe, outliers='device', fit='device')
+        if nv12:
+            out_y, out_uv, _ = self.stabilized_nv12(d_y, d_uv, d_disp, homographies, adaptive_weights_definition=adaptive_weights_definition,
+                                                    crop=True)
+            # stabilized_nv12 keeps its paths to itself; the sweep is deterministic, so a second one yields the same bytes
+            d_stab = self._stabilized_vertex_displacements_device(d_disp, int(d_y.shape[2]), int(d_y.shape[1]), adaptive_weights_definition,
+                                                                  homographies)
+            cropped, cropped_luma = (out_y, out_uv), out_y
+        else:
+            _, _, d_stab, cropped = self.stabilize_resident(luma, d_disp, homographies, adaptive_weights_definition, crop=True)
+            cropped_luma = cropped
+        cropping_ratio, distortion_score = self.cropping_and_distortion_resident(luma, cropped_luma, chunk_pairs, max_per_subframe)
+        return cropped, (cropping_ratio, distortion_score, self._compute_stability_score_device(d_stab))
+
     def _write_stabilized_video(self, output_path, num_frames, frames_per_second, codec, stabilized_frames):
         """mfs.py:1290-1322."""
         from . import frontend_cv2
