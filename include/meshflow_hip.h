@@ -549,6 +549,26 @@ int mf_homography_fit_f64(const double* d_early, const double* d_late, const int
 int mf_feature_scores_f64(const double* d_h, const int32_t* d_info, int pairs, float* d_pair_scores, float* d_scores, int32_t* d_record,
                           void* stream);
 
+/* ---- the luma of a colour or 16-bit clip: what the tracker calls above take (cv2's conversion in front of FAST, mfs.py:505-516) ----
+ * d_src: a contiguous stack of n frames of H x W pixels; d_dst: [n][H][W] uint8.  Bit for bit tests/luma_model.py, integers only:
+ *   mf_luma_u8c3   [n][H][W][3] uint8 BGR:   (b 3735 + g 19235 + r 9798 + 16384) >> 15 -- OpenCV's 8U COLOR_BGR2GRAY, 15-bit coefficients
+ *                  that sum to 32768
+ *   mf_luma_u8c4   [n][H][W][4] uint8 BGRA:  the same on channels 0-2; channel 3 is ignored (COLOR_BGRA2GRAY)
+ *   mf_luma_u16c3  [n][H][W][3] uint16 BGR:  y16 = (b 1868 + g 9617 + r 4899 + 8192) >> 14 -- OpenCV's 16U path, 14-bit coefficients that sum
+ *                  to 16384 --, then y16 >> 8
+ *   mf_luma_u16    [n][H][W] uint16:       y >> 8 -- the luma plane of a P010 / P012 / P016 clip, whose samples are MSB-aligned
+ * red_first = 1 swaps the roles of channels 0 and 2 (COLOR_RGB2GRAY / RGBA).  A 16-bit value becomes a byte by TRUNCATION (>> 8, no
+ * rounding): cv2's FAST takes no 16-bit image, so this rule is the library's own, one rule for BGR and for P010.  The constants are restated
+ * from OpenCV 4.5-4.10; tests/test_cv2_luma_crosscheck.py compares them with cv2 where there is one.
+ * One launch per 2^28 pixels over the flat pixel stream, 64-bit pixel indices (n * W * H may exceed 2^32).  d_src and d_dst may start at any byte
+ * (a uint16 source: at any even byte); 16-byte accesses are used where the addresses allow them, narrower ones elsewhere.
+ * Limits (MF_ERR_INVALID_ARG, nothing launched): null pointers; n < 1; W or H outside 1 .. 32,767; red_first outside {0, 1}; a uint16 source
+ * at an odd address; a destination that overlaps the source.  Asynchronous on `stream`. */
+int mf_luma_u8c3(const void* d_src, int n, int W, int H, int red_first, uint8_t* d_dst, void* stream);
+int mf_luma_u8c4(const void* d_src, int n, int W, int H, int red_first, uint8_t* d_dst, void* stream);
+int mf_luma_u16c3(const void* d_src, int n, int W, int H, int red_first, uint8_t* d_dst, void* stream);
+int mf_luma_u16(const void* d_src, int n, int W, int H, uint8_t* d_dst, void* stream);
+
 /* ---- the row before the path: vertex-motion accumulation (mfs.py:236-452 from the matched features on) ----
  * Replaces the Python loops of _get_vertex_nearby_feature_residual_velocities (mfs.py:365-452), the medians, global
  * motion and median blur of _get_unstabilized_vertex_velocities (mfs.py:316-362, everything after the tracker call)

@@ -96,6 +96,10 @@ SIGNATURES = {
     'mf_homography_fit_workspace_bytes': (_sz, [_i]),
     'mf_homography_fit_f64': (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     'mf_feature_scores_f64': (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    'mf_luma_u8c3': (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
+    'mf_luma_u8c4': (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
+    'mf_luma_u16c3': (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
+    'mf_luma_u16': (_i, [_vp, _i, _i, _i, _vp, _vp]),
     'mf_vertex_motion_workspace_bytes': (_sz, [_i, _i, _i, _i, _i]),
     'mf_vertex_motion_f64': (_i, [_vp, _vp, _vp, _vp] + [_i] * 9 + [_vp, _vp, _vp, _vp, _vp]),
     'mf_stability_score_f64': (_i, [_vp, _i, _i, _vp, _vp, _vp]),

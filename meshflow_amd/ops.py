@@ -730,6 +730,56 @@ def _need_grey(t, name):
         raise ValueError(f'{name} must have shape (n, H, W): one-channel uint8 images (got {tuple(t.shape)})')
 
 
+LUMA_MAX_DIM = 32767
+# (dtype, dimensions, channels) of a clip `luma` converts -> (its C call, whether the call takes red_first)
+_LUMA_CALLS = {(torch.uint8, 4, 3): (_lib_.mf_luma_u8c3, True), (torch.uint8, 4, 4): (_lib_.mf_luma_u8c4, True),
+               (torch.uint16, 4, 3): (_lib_.mf_luma_u16c3, True), (torch.uint16, 3, 1): (_lib_.mf_luma_u16, False)}
+
+
+def luma_source(frames):
+    """The key of `_LUMA_CALLS` for a clip `luma` converts, or None: (n, H, W, 3) uint8 / uint16, (n, H, W, 4) uint8, (n, H, W) uint16."""
+    if not isinstance(frames, torch.Tensor) or frames.dim() not in (3, 4):
+        return None
+    key = (frames.dtype, frames.dim(), int(frames.shape[3]) if frames.dim() == 4 else 1)
+    return key if key in _LUMA_CALLS else None
+
+
+def luma(frames, red_first=False, out=None):
+    """The luma of a resident clip as a (n, H, W) uint8 stack -- what `fast_corners`, `lk_track` and the device tracker take -- bit for bit
+    tests/luma_model.py.  frames: (n, H, W, 3) uint8 BGR or (n, H, W, 4) uint8 BGRA (OpenCV's 8U COLOR_BGR2GRAY: (b*3735 + g*19235 + r*9798
+    + 16384) >> 15; alpha is ignored), (n, H, W, 3) uint16 BGR (OpenCV's 16U arithmetic, then the high byte) or (n, H, W) uint16, the luma
+    plane of a P010 clip (the high byte); 16-bit values are truncated, not rounded.  red_first: channel 0 is red (RGB / RGBA).  A (n, H, W)
+    uint8 stack is luma already and is refused: pass it on as it is.  out: a contiguous (n, H, W) uint8 tensor on the device of frames that
+    does not overlap them.  One launch per 2^28 pixels on torch's current stream; does not wait for it."""
+    name = 'luma'
+    if not isinstance(frames, torch.Tensor):
+        raise ValueError(f'{name}: frames must be a CUDA/HIP torch tensor')
+    if frames.dtype == torch.uint8 and frames.dim() == 3:
+        raise ValueError(f'{name}: a (n, H, W) uint8 stack is already luma: pass it to the tracker as it is')
+    key = luma_source(frames)
+    if key is None:
+        raise ValueError(f'{name}: frames must be (n, H, W, 3) uint8 or uint16, (n, H, W, 4) uint8 or (n, H, W) uint16 '
+                         f'(got {tuple(frames.shape)} {frames.dtype})')
+    n, H, W = (int(v) for v in frames.shape[:3])
+    if n < 1 or not 1 <= H <= LUMA_MAX_DIM or not 1 <= W <= LUMA_MAX_DIM:
+        raise ValueError(f'{name}: frames need n >= 1 and H, W in 1 .. {LUMA_MAX_DIM} (got {tuple(frames.shape)})')
+    if red_first not in (False, True):
+        raise ValueError(f'{name}: red_first must be False or True (got {red_first!r})')
+    call, takes_order = _LUMA_CALLS[key]
+    if red_first and not takes_order:
+        raise ValueError(f'{name}: red_first has no meaning for a one-channel (n, H, W) uint16 plane')
+    _need(frames, frames.dtype, 'frames')
+    if out is None:
+        out = torch.empty((n, H, W), dtype=torch.uint8, device=frames.device)
+    else:
+        _need(out, torch.uint8, 'out')
+        if tuple(out.shape) != (n, H, W) or out.device != frames.device:
+            raise ValueError(f'{name}: out must have shape {(n, H, W)} on the device of frames (got {tuple(out.shape)} on {out.device})')
+    order = (int(bool(red_first)),) if takes_order else ()
+    _lib.check(call(_ptr(frames), n, W, H, *order, _ptr(out), _stream()))
+    return out
+
+
 def _track_work(n, W, H, sub_rows, sub_cols, max_per_subframe, device):
     size = _lib_.mf_track_workspace_bytes(n, W, H, sub_rows, sub_cols, max_per_subframe)
     if size == 0:                                  # outside the limits: let the call itself say which

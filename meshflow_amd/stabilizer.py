@@ -246,7 +246,7 @@ class MeshFlowStabilizer:
                                      self.homography_min_number_corresponding_features, self._torch_device(), max_per_subframe,
                                      outliers=outliers, fit=fit)
 
-    def estimate_motion(self, d_grey, chunk_pairs=32, max_per_subframe=1024, outliers='host', fit='host'):
+    def estimate_motion(self, d_grey, chunk_pairs=32, max_per_subframe=1024, outliers='host', fit='host', red_first=False):
         """mfs.py:236-284 for a clip that is already on the device: `d_grey` (F, H, W) uint8 -- grey frames or the luma plane of an NV12
         clip -- through `device_tracker()` and `_get_unstabilized_vertex_displacements_from_features`.  Returns (d_disp (F, R+1, C+1, 2)
         float64 device tensor, homographies (F, 3, 3) float64 with the identity last, mfs.py:273-274): what `stabilize_resident`,
@@ -255,9 +255,14 @@ class MeshFlowStabilizer:
         (`ops.ransac_inliers`, tests/ransac_model.py), the packed features go straight to `ops.vertex_motion` and d_disp never visits the
         host; only the survivors come down, for the one homography fit per pair.  fit='device' (with outliers='device'): that fit runs on the
         device too (`ops.fit_homographies`, tests/homography_model.py -- within rounding of the host fit), its homographies go to
-        `ops.vertex_motion` as they are, and all that comes down is the (F - 1, 9) matrices and their (F - 1, 4) records."""
+        `ops.vertex_motion` as they are, and all that comes down is the (F - 1, 9) matrices and their (F - 1, 4) records.
+        A clip that is not luma yet -- (F, H, W, 3) uint8 or uint16 BGR, (F, H, W, 4) uint8 BGRA, or the (F, H, W) uint16 luma plane of a P010
+        clip -- goes through `ops.luma` first (tests/luma_model.py; red_first: channel 0 is red) and is tracked as that uint8
+        stack; a uint8 (F, H, W) stack takes the same launches as ever."""
         import torch
         from . import ops, tracker
+        if ops.luma_source(d_grey) is not None:
+            d_grey = ops.luma(d_grey, red_first)
         if tracker.check_fit(fit, tracker.check_outliers(outliers)) == 'device':
             d_early, d_late, d_offsets, kmax, d_hom, d_info = self.device_tracker(max_per_subframe, outliers, fit).track_clip_resident(d_grey, chunk_pairs)
             num_frames, frame_height, frame_width = d_grey.shape
@@ -328,32 +333,45 @@ class MeshFlowStabilizer:
         cropping_ratio, distortion_score = scores.cpu().numpy()
         return cropping_ratio, distortion_score
 
-    def stabilize_scored(self, clip, adaptive_weights_definition=ADAPTIVE_WEIGHTS_DEFINITION_ORIGINAL, chunk_pairs=32, max_per_subframe=1024):
+    def stabilize_scored(self, clip, adaptive_weights_definition=ADAPTIVE_WEIGHTS_DEFINITION_ORIGINAL, chunk_pairs=32, max_per_subframe=1024,
+                         red_first=False):
         """The reference's stabilize() between decoder and encoder (mfs.py:140-169) for a resident clip, without OpenCV: `clip` is an
-        (F, H, W) uint8 grey tensor or an NV12 pair (d_y (F, H, W), d_uv (F, H/2, W/2, 2)).  In order: `estimate_motion(luma,
-        outliers='device', fit='device')`; `stabilize_resident(crop=True)` for grey or `stabilized_nv12(crop=True)` for NV12;
-        `cropping_and_distortion_resident(luma, cropped luma)`; `_compute_stability_score_device` on the stabilized vertex paths.  Returns
-        (the cropped clip in the input's form, (cropping_ratio, distortion_score, stability_score)) -- the reference's order, mfs.py:169;
-        the first two np.float32, the third a float.  Every ValueError of those calls is this one's."""
-        nv12 = isinstance(clip, (tuple, list))
-        if nv12:
+        (F, H, W) uint8 grey tensor, (F, H, W, 3) uint8 or uint16 BGR frames, (F, H, W, 4) uint8 BGRA frames (red_first: RGB / RGBA), an NV12
+        pair (d_y (F, H, W), d_uv (F, H/2, W/2, 2)) of uint8 or a P010 pair of the same shapes of uint16 -- the pair's dtype tells the two
+        apart.  In order: the clip's luma (itself for grey and NV12, `ops.luma` otherwise); `estimate_motion(luma, outliers='device',
+        fit='device')`; `stabilize_resident(crop=True)` on the frames, `stabilized_nv12(crop=True)` or `stabilized_p010_cropped` on the
+        pair; the luma of the cropped clip in the same way; `cropping_and_distortion_resident(luma, cropped luma)`;
+        `_compute_stability_score_device` on the stabilized vertex paths.  Returns (the cropped clip in the input's form,
+        (cropping_ratio, distortion_score, stability_score)) -- the reference's order, mfs.py:169; the first two np.float32, the third a
+        float.  Every ValueError of those calls is this one's."""
+        import torch
+        from . import ops
+        pair = isinstance(clip, (tuple, list))
+        if pair:
             if len(clip) != 2:
-                raise ValueError('an NV12 clip is the pair (d_y, d_uv)')
+                raise ValueError('an NV12 or P010 clip is the pair (d_y, d_uv)')
             d_y, d_uv = clip
-            luma = d_y
+            deep = isinstance(d_y, torch.Tensor) and d_y.dtype == torch.uint16
+            luma = ops.luma(d_y) if deep else d_y
         else:
-            luma = clip
+            if isinstance(clip, torch.Tensor) and clip.dtype == torch.uint16 and clip.dim() == 3:
+                raise ValueError('a (F, H, W) uint16 stack is the luma plane of a P010 clip: pass the pair (d_y, d_uv)')
+            luma = ops.luma(clip, red_first) if ops.luma_source(clip) is not None else clip
         d_disp, homographies = self.estimate_motion(luma, chunk_pairs, max_per_subframe, outliers='device', fit='device')
-        if nv12:
-            out_y, out_uv, _ = self.stabilized_nv12(d_y, d_uv, d_disp, homographies, adaptive_weights_definition=adaptive_weights_definition,
-                                                    crop=True)
-            # stabilized_nv12 keeps its paths to itself; the sweep is deterministic, so a second one yields the same bytes
+        if pair:
+            if deep:
+                out_y, out_uv, _ = self.stabilized_p010_cropped(d_y, d_uv, d_disp, homographies,
+                                                                adaptive_weights_definition=adaptive_weights_definition)
+            else:
+                out_y, out_uv, _ = self.stabilized_nv12(d_y, d_uv, d_disp, homographies,
+                                                        adaptive_weights_definition=adaptive_weights_definition, crop=True)
+            # neither call hands out its paths; the sweep is deterministic, so a second one yields the same bytes
             d_stab = self._stabilized_vertex_displacements_device(d_disp, int(d_y.shape[2]), int(d_y.shape[1]), adaptive_weights_definition,
                                                                   homographies)
-            cropped, cropped_luma = (out_y, out_uv), out_y
+            cropped, cropped_luma = (out_y, out_uv), ops.luma(out_y) if deep else out_y
         else:
-            _, _, d_stab, cropped = self.stabilize_resident(luma, d_disp, homographies, adaptive_weights_definition, crop=True)
-            cropped_luma = cropped
+            _, _, d_stab, cropped = self.stabilize_resident(clip, d_disp, homographies, adaptive_weights_definition, crop=True)
+            cropped_luma = cropped if luma is clip else ops.luma(cropped, red_first)
         cropping_ratio, distortion_score = self.cropping_and_distortion_resident(luma, cropped_luma, chunk_pairs, max_per_subframe)
         return cropped, (cropping_ratio, distortion_score, self._compute_stability_score_device(d_stab))
 
