@@ -58,42 +58,42 @@ static int warp_maps_entry(const char* name, const void* d_table, float* d_maps,
                        (hipStream_t)stream);
 }
 
-// The checks of the two NV12 entries, then the grey warp of the luma planes (launch_warp's Px::U8C1 launches, unchanged) and the chroma launches
-// behind it on the same stream.  has_bounds: the clip-level rectangle goes to the caller's d_bounds instead of the table's.
-static int warp_nv12_entry(const char* name, const uint8_t* d_y, const uint8_t* d_uv, uint8_t* d_out_y, uint8_t* d_out_uv, const void* d_table,
-                           int n, int W, int H, int R, int C, const uint8_t* border_yuv, int32_t* d_crop, bool has_bounds, int32_t* d_bounds,
-                           void* stream)
+// A 4:2:0 format with a luma plane stack and an interleaved half-resolution chroma one: NV12 (uint8 samples) and P010 (uint16 samples)
+struct Fmt420 {
+    int bytes;              // of a sample: 1 or 2
+    const char* noun;       // with its article, for the messages
+    Px luma, chroma;        // launch_warp's formats of the two plane stacks
+};
+constexpr Fmt420 kNv12 = { 1, "an NV12", Px::U8C1, Px::NV12_UV }, kP010 = { 2, "a P010", Px::U16C1, Px::P010_UV };
+
+// The plane stacks of a 4:2:0 call, n frames of W x H in and of oW x oH out: aligned to 2 bytes -- the chroma pair of an NV12 clip, all four of a
+// P010 clip -- and no two of them share a byte
+static bool planes_420_ok(const char* name, const Fmt420& f, const void* d_y, const void* d_uv, const void* d_out_y, const void* d_out_uv, int n, int W,
+                          int H, int oW, int oH)
 {
-    if (!d_y || !d_uv || !d_out_y || !d_out_uv || !d_table || !border_yuv || !d_crop || (has_bounds && !d_bounds)) {
-        set_error("%s: null pointer", name);
-        return MF_ERR_INVALID_ARG;
-    }
-    if (n <= 0) { set_error("%s: bad sizes", name); return MF_ERR_INVALID_ARG; }
-    if (W < 2 || H < 2 || W > 32767 || H > 32767) { set_error("%s: W=%d H=%d outside 2 .. 32,767", name, W, H); return MF_ERR_INVALID_ARG; }
-    if ((W | H) & 1) { set_error("%s: an NV12 frame has an even W and H, got W=%d H=%d", name, W, H); return MF_ERR_INVALID_ARG; }
-    if (R < 1 || C < 1 || R > 64 || C > 64) { set_error("%s: mesh R=%d C=%d outside 1 .. 64", name, R, C); return MF_ERR_INVALID_ARG; }
-    if ((((uintptr_t)d_uv | (uintptr_t)d_out_uv) & 1u) != 0) { set_error("%s: d_uv and d_out_uv must be 2-byte aligned", name); return MF_ERR_INVALID_ARG; }
-    // no two of the four plane stacks may share a byte
-    const size_t y_bytes = (size_t)n * W * H, uv_bytes = (size_t)n * nv12_uv_frame_bytes(W, H);
+    const size_t b = (size_t)f.bytes;
     const struct { uintptr_t at; size_t bytes; const char* what; } pl[4] = {
-        { (uintptr_t)d_y, y_bytes, "d_y" }, { (uintptr_t)d_uv, uv_bytes, "d_uv" }, { (uintptr_t)d_out_y, y_bytes, "d_out_y" }, { (uintptr_t)d_out_uv, uv_bytes, "d_out_uv" } };
+        { (uintptr_t)d_y, (size_t)n * W * H * b, "d_y" }, { (uintptr_t)d_uv, (size_t)n * nv12_uv_frame_bytes(W, H) * b, "d_uv" },
+        { (uintptr_t)d_out_y, (size_t)n * oW * oH * b, "d_out_y" }, { (uintptr_t)d_out_uv, (size_t)n * nv12_uv_frame_bytes(oW, oH) * b, "d_out_uv" } };
+    if ((((b == 2 ? pl[0].at | pl[2].at : 0) | pl[1].at | pl[3].at) & 1u) != 0) {
+        set_error("%s: %s must be 2-byte aligned", name, b == 2 ? "d_y, d_uv, d_out_y and d_out_uv" : "d_uv and d_out_uv");
+        return false;
+    }
     for (int i = 0; i < 4; ++i)
         for (int j = i + 1; j < 4; ++j)
             if (pl[i].at < pl[j].at + pl[j].bytes && pl[j].at < pl[i].at + pl[i].bytes) {
                 set_error("%s: %s and %s alias", name, pl[i].what, pl[j].what);
-                return MF_ERR_INVALID_ARG;
+                return false;
             }
-    TableView tv = table_view(const_cast<void*>(d_table), n, W, H, R, C);
-    if (has_bounds) tv.bounds = d_bounds;
-    if (const int rc = launch_warp(Px::U8C1, d_y, d_out_y, tv, n, W, H, R, C, pack_border(Px::U8C1, border_yuv), d_crop, (hipStream_t)stream)) return rc;
-    return launch_warp(Px::NV12_UV, d_uv, d_out_uv, tv, n, W, H, R, C, pack_border(Px::NV12_UV, border_yuv + 1), d_crop, (hipStream_t)stream);
+    return true;
 }
 
-// The checks of the two P010 entries (warp_nv12_entry's, on uint16 planes), then the luma launches (Px::U16C1) and the chroma launches behind them
-// on the same stream.  has_bounds: the clip-level rectangle goes to the caller's d_bounds instead of the table's.
-static int warp_p010_entry(const char* name, const uint16_t* d_y, const uint16_t* d_uv, uint16_t* d_out_y, uint16_t* d_out_uv, const void* d_table,
-                           int n, int W, int H, int R, int C, const uint16_t* border_yuv, int32_t* d_crop, bool has_bounds, int32_t* d_bounds,
-                           void* stream)
+// The checks of the four NV12 and P010 warp entries, then the warp of the luma planes (launch_warp's f.luma launches: the grey warp, unchanged, for
+// NV12) and the chroma launches behind it on the same stream.  border_yuv: three samples of f.bytes each.  has_bounds: the clip-level rectangle
+// goes to the caller's d_bounds instead of the table's.
+static int warp_420_entry(const char* name, const Fmt420& f, const void* d_y, const void* d_uv, void* d_out_y, void* d_out_uv, const void* d_table,
+                          int n, int W, int H, int R, int C, const void* border_yuv, int32_t* d_crop, bool has_bounds, int32_t* d_bounds,
+                          void* stream)
 {
     if (!d_y || !d_uv || !d_out_y || !d_out_uv || !d_table || !border_yuv || !d_crop || (has_bounds && !d_bounds)) {
         set_error("%s: null pointer", name);
@@ -101,26 +101,14 @@ static int warp_p010_entry(const char* name, const uint16_t* d_y, const uint16_t
     }
     if (n <= 0) { set_error("%s: bad sizes", name); return MF_ERR_INVALID_ARG; }
     if (W < 2 || H < 2 || W > 32767 || H > 32767) { set_error("%s: W=%d H=%d outside 2 .. 32,767", name, W, H); return MF_ERR_INVALID_ARG; }
-    if ((W | H) & 1) { set_error("%s: a P010 frame has an even W and H, got W=%d H=%d", name, W, H); return MF_ERR_INVALID_ARG; }
+    if ((W | H) & 1) { set_error("%s: %s frame has an even W and H, got W=%d H=%d", name, f.noun, W, H); return MF_ERR_INVALID_ARG; }
     if (R < 1 || C < 1 || R > 64 || C > 64) { set_error("%s: mesh R=%d C=%d outside 1 .. 64", name, R, C); return MF_ERR_INVALID_ARG; }
-    if ((((uintptr_t)d_y | (uintptr_t)d_uv | (uintptr_t)d_out_y | (uintptr_t)d_out_uv) & 1u) != 0) {
-        set_error("%s: d_y, d_uv, d_out_y and d_out_uv must be 2-byte aligned", name);
-        return MF_ERR_INVALID_ARG;
-    }
-    // no two of the four plane stacks may share a byte
-    const size_t y_bytes = (size_t)n * W * H * 2u, uv_bytes = (size_t)n * p010_uv_frame_bytes(W, H);
-    const struct { uintptr_t at; size_t bytes; const char* what; } pl[4] = {
-        { (uintptr_t)d_y, y_bytes, "d_y" }, { (uintptr_t)d_uv, uv_bytes, "d_uv" }, { (uintptr_t)d_out_y, y_bytes, "d_out_y" }, { (uintptr_t)d_out_uv, uv_bytes, "d_out_uv" } };
-    for (int i = 0; i < 4; ++i)
-        for (int j = i + 1; j < 4; ++j)
-            if (pl[i].at < pl[j].at + pl[j].bytes && pl[j].at < pl[i].at + pl[i].bytes) {
-                set_error("%s: %s and %s alias", name, pl[i].what, pl[j].what);
-                return MF_ERR_INVALID_ARG;
-            }
+    if (!planes_420_ok(name, f, d_y, d_uv, d_out_y, d_out_uv, n, W, H, W, H)) return MF_ERR_INVALID_ARG;
     TableView tv = table_view(const_cast<void*>(d_table), n, W, H, R, C);
     if (has_bounds) tv.bounds = d_bounds;
-    if (const int rc = launch_warp(Px::U16C1, d_y, d_out_y, tv, n, W, H, R, C, pack_border(Px::U16C1, border_yuv), d_crop, (hipStream_t)stream)) return rc;
-    return launch_warp(Px::P010_UV, d_uv, d_out_uv, tv, n, W, H, R, C, pack_border(Px::P010_UV, border_yuv + 1), d_crop, (hipStream_t)stream);
+    const void* const border_uv = (const char*)border_yuv + f.bytes;
+    if (const int rc = launch_warp(f.luma, d_y, d_out_y, tv, n, W, H, R, C, pack_border(f.luma, border_yuv), d_crop, (hipStream_t)stream)) return rc;
+    return launch_warp(f.chroma, d_uv, d_out_uv, tv, n, W, H, R, C, pack_border(f.chroma, border_uv), d_crop, (hipStream_t)stream);
 }
 
 // The element checks every plane entry shares: elem_bytes is 0 (the float32 calls) or 1, 2, 4, 8, and both pointers are aligned to the element
@@ -188,94 +176,48 @@ static int crop_resize_dev_entry(const char* name, Px px, const void* d_frames, 
     return launch_crop_resize_dev(px, d_frames, d_out, n, W, H, d_bounds, out_W, out_H, d_work, d_status, (hipStream_t)stream);
 }
 
-// The checks of the two NV12 crop-resize entries -- all of them ahead of the first launch, under the call's own name --, then the luma call as it
-// is (launch_crop_resize_to / launch_crop_resize_dev on Px::U8C1) and the chroma launches behind it on the same stream.  dev:
-// mf_crop_resize_dev_nv12 (the rectangle in d_bounds, left .. bottom unused).
-static int crop_resize_nv12_entry(bool dev, const uint8_t* d_y, const uint8_t* d_uv, uint8_t* d_out_y, uint8_t* d_out_uv, int n, int W, int H,
-                                  int left, int top, int right, int bottom, const int32_t* d_bounds, int oW, int oH, void* d_work,
-                                  int32_t* d_status, void* stream)
+// The checks of the four NV12 and P010 crop-resize entries -- all of them ahead of the first launch, under the call's own name `name` --, then
+// the format's launches on one stream.  NV12: the luma call as it is (launch_crop_resize_to / launch_crop_resize_dev on Px::U8C1) and the chroma
+// launches behind it.  P010: the luma tables, the luma kernel, the chroma tables and the chroma kernel (resize_hdr.hip / resize_hdr_dev.hip).
+// dev: an mf_crop_resize_dev_* call (the rectangle in d_bounds, left .. bottom unused).
+static int crop_resize_420_entry(const char* name, const Fmt420& f, bool dev, const void* d_y, const void* d_uv, void* d_out_y, void* d_out_uv,
+                                 int n, int W, int H, int left, int top, int right, int bottom, const int32_t* d_bounds, int oW, int oH,
+                                 void* d_work, int32_t* d_status, void* stream)
 {
-    const char* const call = dev ? "mf_crop_resize_dev_" : "mf_crop_resize_";
-    const char* const fmt = "nv12";
     if (!d_y || !d_uv || !d_out_y || !d_out_uv || !d_work || (dev && (!d_bounds || !d_status))) {
-        set_error("%s%s: null pointer", call, fmt);
+        set_error("%s: null pointer", name);
         return MF_ERR_INVALID_ARG;
     }
-    if (n <= 0) { set_error("%s%s: bad sizes n=%d", call, fmt, n); return MF_ERR_INVALID_ARG; }
-    if (W < 2 || H < 2 || W > 32767 || H > 32767) { set_error("%s%s: W=%d H=%d outside 2 .. 32,767", call, fmt, W, H); return MF_ERR_INVALID_ARG; }
+    if (n <= 0) { set_error("%s: bad sizes n=%d", name, n); return MF_ERR_INVALID_ARG; }
+    if (W < 2 || H < 2 || W > 32767 || H > 32767) { set_error("%s: W=%d H=%d outside 2 .. 32,767", name, W, H); return MF_ERR_INVALID_ARG; }
     if (oW < 2 || oH < 2 || oW > 32767 || oH > 32767) {
-        set_error("%s%s: unsupported output size %dx%d (2 .. 32,767 each)", call, fmt, oW, oH);
+        set_error("%s: unsupported output size %dx%d (2 .. 32,767 each)", name, oW, oH);
         return MF_ERR_INVALID_ARG;
     }
-    if ((W | H) & 1) { set_error("%s%s: an NV12 frame has an even W and H, got W=%d H=%d", call, fmt, W, H); return MF_ERR_INVALID_ARG; }
-    if ((oW | oH) & 1) { set_error("%s%s: an NV12 output has an even size, got %dx%d", call, fmt, oW, oH); return MF_ERR_INVALID_ARG; }
-    if ((((uintptr_t)d_uv | (uintptr_t)d_out_uv) & 1u) != 0) { set_error("%s%s: d_uv and d_out_uv must be 2-byte aligned", call, fmt); return MF_ERR_INVALID_ARG; }
-    // no two of the four plane stacks may share a byte
-    const struct { uintptr_t at; size_t bytes; const char* what; } pl[4] = {
-        { (uintptr_t)d_y, (size_t)n * W * H, "d_y" }, { (uintptr_t)d_uv, (size_t)n * nv12_uv_frame_bytes(W, H), "d_uv" },
-        { (uintptr_t)d_out_y, (size_t)n * oW * oH, "d_out_y" }, { (uintptr_t)d_out_uv, (size_t)n * nv12_uv_frame_bytes(oW, oH), "d_out_uv" } };
-    for (int i = 0; i < 4; ++i)
-        for (int j = i + 1; j < 4; ++j)
-            if (pl[i].at < pl[j].at + pl[j].bytes && pl[j].at < pl[i].at + pl[i].bytes) {
-                set_error("%s%s: %s and %s alias", call, fmt, pl[i].what, pl[j].what);
-                return MF_ERR_INVALID_ARG;
-            }
-    if (!dev && !resize_rect_ok(call, fmt, left, top, right, bottom, W, H)) return MF_ERR_INVALID_ARG;
+    if ((W | H) & 1) { set_error("%s: %s frame has an even W and H, got W=%d H=%d", name, f.noun, W, H); return MF_ERR_INVALID_ARG; }
+    if ((oW | oH) & 1) { set_error("%s: %s output has an even size, got %dx%d", name, f.noun, oW, oH); return MF_ERR_INVALID_ARG; }
+    if (!planes_420_ok(name, f, d_y, d_uv, d_out_y, d_out_uv, n, W, H, oW, oH)) return MF_ERR_INVALID_ARG;
+    if (!dev && !resize_rect_ok(name, "", left, top, right, bottom, W, H)) return MF_ERR_INVALID_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    if (f.bytes == 2) {
+        const uint16_t* const y = (const uint16_t*)d_y, * const uv = (const uint16_t*)d_uv;
+        uint16_t* const out_y = (uint16_t*)d_out_y, * const out_uv = (uint16_t*)d_out_uv;
+        TileOrder luma, chroma;
+        if (!resize_hdr_tile_orders(oW, oH, n, luma, chroma)) { set_error("%s: too many tiles", name); return MF_ERR_INVALID_ARG; }
+        if (dev) return launch_resize_hdr_dev(y, uv, out_y, out_uv, W, H, d_bounds, oW, oH, d_work, d_status, luma, chroma, st);
+        return launch_resize_hdr(y, uv, out_y, out_uv, W, H, left, top, right, bottom, oW, oH, d_work, luma, chroma, st);
+    }
     // the luma call's tiles at their smallest (the `down` instantiation's rows: the most tiles any of its paths counts), then chroma's
     TileOrder luma_order, order;
-    if (!resize_tiles_ok(call, fmt, oW, oH, resize_to_tile_rows(Px::U8C1, false), n, luma_order)) return MF_ERR_INVALID_ARG;
-    if (!resize_uv_tile_order(oW, oH, n, order)) { set_error("%s%s: too many tiles", call, fmt); return MF_ERR_INVALID_ARG; }
+    if (!resize_tiles_ok(name, "", oW, oH, resize_to_tile_rows(Px::U8C1, false), n, luma_order)) return MF_ERR_INVALID_ARG;
+    if (!resize_uv_tile_order(oW, oH, n, order)) { set_error("%s: too many tiles", name); return MF_ERR_INVALID_ARG; }
     void* const tabs = (char*)d_work + crop_resize_workspace_bytes(oW, oH);
-    hipStream_t st = (hipStream_t)stream;
     if (dev) {
         if (const int rc = launch_crop_resize_dev(Px::U8C1, d_y, d_out_y, n, W, H, d_bounds, oW, oH, d_work, d_status, st)) return rc;
-        return launch_resize_uv_dev(d_uv, d_out_uv, W, H, d_bounds, oW, oH, tabs, order, st);
+        return launch_resize_uv_dev((const uint8_t*)d_uv, (uint8_t*)d_out_uv, W, H, d_bounds, oW, oH, tabs, order, st);
     }
     if (const int rc = launch_crop_resize_to(Px::U8C1, d_y, d_out_y, n, W, H, left, top, right, bottom, oW, oH, d_work, st)) return rc;
-    return launch_resize_uv(d_uv, d_out_uv, W, H, left, top, right, bottom, oW, oH, tabs, order, st);
-}
-
-// The checks of the two P010 crop-resize entries (crop_resize_nv12_entry's, on uint16 planes) -- all of them ahead of the first launch --, then
-// the luma tables, the luma kernel, the chroma tables and the chroma kernel on the same stream (resize_hdr.hip / resize_hdr_dev.hip).  dev:
-// mf_crop_resize_dev_p010 (the rectangle in d_bounds, left .. bottom unused).
-static int crop_resize_p010_entry(bool dev, const uint16_t* d_y, const uint16_t* d_uv, uint16_t* d_out_y, uint16_t* d_out_uv, int n, int W, int H,
-                                  int left, int top, int right, int bottom, const int32_t* d_bounds, int oW, int oH, void* d_work,
-                                  int32_t* d_status, void* stream)
-{
-    const char* const call = dev ? "mf_crop_resize_dev_" : "mf_crop_resize_";
-    const char* const fmt = "p010";
-    if (!d_y || !d_uv || !d_out_y || !d_out_uv || !d_work || (dev && (!d_bounds || !d_status))) {
-        set_error("%s%s: null pointer", call, fmt);
-        return MF_ERR_INVALID_ARG;
-    }
-    if (n <= 0) { set_error("%s%s: bad sizes n=%d", call, fmt, n); return MF_ERR_INVALID_ARG; }
-    if (W < 2 || H < 2 || W > 32767 || H > 32767) { set_error("%s%s: W=%d H=%d outside 2 .. 32,767", call, fmt, W, H); return MF_ERR_INVALID_ARG; }
-    if (oW < 2 || oH < 2 || oW > 32767 || oH > 32767) {
-        set_error("%s%s: unsupported output size %dx%d (2 .. 32,767 each)", call, fmt, oW, oH);
-        return MF_ERR_INVALID_ARG;
-    }
-    if ((W | H) & 1) { set_error("%s%s: a P010 frame has an even W and H, got W=%d H=%d", call, fmt, W, H); return MF_ERR_INVALID_ARG; }
-    if ((oW | oH) & 1) { set_error("%s%s: a P010 output has an even size, got %dx%d", call, fmt, oW, oH); return MF_ERR_INVALID_ARG; }
-    if ((((uintptr_t)d_y | (uintptr_t)d_uv | (uintptr_t)d_out_y | (uintptr_t)d_out_uv) & 1u) != 0) {
-        set_error("%s%s: d_y, d_uv, d_out_y and d_out_uv must be 2-byte aligned", call, fmt);
-        return MF_ERR_INVALID_ARG;
-    }
-    // no two of the four plane stacks may share a byte
-    const struct { uintptr_t at; size_t bytes; const char* what; } pl[4] = {
-        { (uintptr_t)d_y, (size_t)n * W * H * 2u, "d_y" }, { (uintptr_t)d_uv, (size_t)n * p010_uv_frame_bytes(W, H), "d_uv" },
-        { (uintptr_t)d_out_y, (size_t)n * oW * oH * 2u, "d_out_y" }, { (uintptr_t)d_out_uv, (size_t)n * p010_uv_frame_bytes(oW, oH), "d_out_uv" } };
-    for (int i = 0; i < 4; ++i)
-        for (int j = i + 1; j < 4; ++j)
-            if (pl[i].at < pl[j].at + pl[j].bytes && pl[j].at < pl[i].at + pl[i].bytes) {
-                set_error("%s%s: %s and %s alias", call, fmt, pl[i].what, pl[j].what);
-                return MF_ERR_INVALID_ARG;
-            }
-    if (!dev && !resize_rect_ok(call, fmt, left, top, right, bottom, W, H)) return MF_ERR_INVALID_ARG;
-    TileOrder luma, chroma;
-    if (!resize_hdr_tile_orders(oW, oH, n, luma, chroma)) { set_error("%s%s: too many tiles", call, fmt); return MF_ERR_INVALID_ARG; }
-    hipStream_t st = (hipStream_t)stream;
-    if (dev) return launch_resize_hdr_dev(d_y, d_uv, d_out_y, d_out_uv, W, H, d_bounds, oW, oH, d_work, d_status, luma, chroma, st);
-    return launch_resize_hdr(d_y, d_uv, d_out_y, d_out_uv, W, H, left, top, right, bottom, oW, oH, d_work, luma, chroma, st);
+    return launch_resize_uv((const uint8_t*)d_uv, (uint8_t*)d_out_uv, W, H, left, top, right, bottom, oW, oH, tabs, order, st);
 }
 
 // Every check the tracker's calls share (include/meshflow_hip.h); the geometry on success.
@@ -452,25 +394,27 @@ int mf_warp_plane_nearest(const void* d_planes, void* d_out, const void* d_table
 int mf_warp_nv12(const uint8_t* d_y, const uint8_t* d_uv, uint8_t* d_out_y, uint8_t* d_out_uv, const void* d_table, int n, int W, int H,
                  int R, int C, const uint8_t border_yuv[3], int32_t* d_crop, void* stream)
 {
-    return warp_nv12_entry("mf_warp_nv12", d_y, d_uv, d_out_y, d_out_uv, d_table, n, W, H, R, C, border_yuv, d_crop, false, nullptr, stream);
+    return warp_420_entry("mf_warp_nv12", kNv12, d_y, d_uv, d_out_y, d_out_uv, d_table, n, W, H, R, C, border_yuv, d_crop, false, nullptr, stream);
 }
 
 int mf_warp_bounds_nv12(const uint8_t* d_y, const uint8_t* d_uv, uint8_t* d_out_y, uint8_t* d_out_uv, const void* d_table, int n, int W, int H,
                         int R, int C, const uint8_t border_yuv[3], int32_t* d_crop, int32_t* d_bounds, void* stream)
 {
-    return warp_nv12_entry("mf_warp_bounds_nv12", d_y, d_uv, d_out_y, d_out_uv, d_table, n, W, H, R, C, border_yuv, d_crop, true, d_bounds, stream);
+    return warp_420_entry("mf_warp_bounds_nv12", kNv12, d_y, d_uv, d_out_y, d_out_uv, d_table, n, W, H, R, C, border_yuv, d_crop, true, d_bounds,
+                          stream);
 }
 
 int mf_warp_p010(const uint16_t* d_y, const uint16_t* d_uv, uint16_t* d_out_y, uint16_t* d_out_uv, const void* d_table, int n, int W, int H,
                  int R, int C, const uint16_t border_yuv[3], int32_t* d_crop, void* stream)
 {
-    return warp_p010_entry("mf_warp_p010", d_y, d_uv, d_out_y, d_out_uv, d_table, n, W, H, R, C, border_yuv, d_crop, false, nullptr, stream);
+    return warp_420_entry("mf_warp_p010", kP010, d_y, d_uv, d_out_y, d_out_uv, d_table, n, W, H, R, C, border_yuv, d_crop, false, nullptr, stream);
 }
 
 int mf_warp_bounds_p010(const uint16_t* d_y, const uint16_t* d_uv, uint16_t* d_out_y, uint16_t* d_out_uv, const void* d_table, int n, int W, int H,
                         int R, int C, const uint16_t border_yuv[3], int32_t* d_crop, int32_t* d_bounds, void* stream)
 {
-    return warp_p010_entry("mf_warp_bounds_p010", d_y, d_uv, d_out_y, d_out_uv, d_table, n, W, H, R, C, border_yuv, d_crop, true, d_bounds, stream);
+    return warp_420_entry("mf_warp_bounds_p010", kP010, d_y, d_uv, d_out_y, d_out_uv, d_table, n, W, H, R, C, border_yuv, d_crop, true, d_bounds,
+                          stream);
 }
 
 // ---- the same three calls with the clip-level rectangle in the CALLER's d_bounds[4] instead of inside the table blob ----
@@ -613,14 +557,15 @@ size_t mf_crop_resize_nv12_workspace_bytes(int out_W, int out_H)
 int mf_crop_resize_nv12(const uint8_t* d_y, const uint8_t* d_uv, uint8_t* d_out_y, uint8_t* d_out_uv, int n, int W, int H, int left, int top,
                         int right, int bottom, int out_W, int out_H, void* d_work, void* stream)
 {
-    return crop_resize_nv12_entry(false, d_y, d_uv, d_out_y, d_out_uv, n, W, H, left, top, right, bottom, nullptr, out_W, out_H, d_work, nullptr,
-                                  stream);
+    return crop_resize_420_entry("mf_crop_resize_nv12", kNv12, false, d_y, d_uv, d_out_y, d_out_uv, n, W, H, left, top, right, bottom, nullptr, out_W,
+                                 out_H, d_work, nullptr, stream);
 }
 
 int mf_crop_resize_dev_nv12(const uint8_t* d_y, const uint8_t* d_uv, uint8_t* d_out_y, uint8_t* d_out_uv, int n, int W, int H,
                             const int32_t* d_bounds, int out_W, int out_H, void* d_work, int32_t* d_status, void* stream)
 {
-    return crop_resize_nv12_entry(true, d_y, d_uv, d_out_y, d_out_uv, n, W, H, 0, 0, 0, 0, d_bounds, out_W, out_H, d_work, d_status, stream);
+    return crop_resize_420_entry("mf_crop_resize_dev_nv12", kNv12, true, d_y, d_uv, d_out_y, d_out_uv, n, W, H, 0, 0, 0, 0, d_bounds, out_W, out_H,
+                                 d_work, d_status, stream);
 }
 
 size_t mf_crop_resize_p010_workspace_bytes(int out_W, int out_H)
@@ -631,14 +576,15 @@ size_t mf_crop_resize_p010_workspace_bytes(int out_W, int out_H)
 int mf_crop_resize_p010(const uint16_t* d_y, const uint16_t* d_uv, uint16_t* d_out_y, uint16_t* d_out_uv, int n, int W, int H, int left, int top,
                         int right, int bottom, int out_W, int out_H, void* d_work, void* stream)
 {
-    return crop_resize_p010_entry(false, d_y, d_uv, d_out_y, d_out_uv, n, W, H, left, top, right, bottom, nullptr, out_W, out_H, d_work, nullptr,
-                                  stream);
+    return crop_resize_420_entry("mf_crop_resize_p010", kP010, false, d_y, d_uv, d_out_y, d_out_uv, n, W, H, left, top, right, bottom, nullptr, out_W,
+                                 out_H, d_work, nullptr, stream);
 }
 
 int mf_crop_resize_dev_p010(const uint16_t* d_y, const uint16_t* d_uv, uint16_t* d_out_y, uint16_t* d_out_uv, int n, int W, int H,
                             const int32_t* d_bounds, int out_W, int out_H, void* d_work, int32_t* d_status, void* stream)
 {
-    return crop_resize_p010_entry(true, d_y, d_uv, d_out_y, d_out_uv, n, W, H, 0, 0, 0, 0, d_bounds, out_W, out_H, d_work, d_status, stream);
+    return crop_resize_420_entry("mf_crop_resize_dev_p010", kP010, true, d_y, d_uv, d_out_y, d_out_uv, n, W, H, 0, 0, 0, 0, d_bounds, out_W, out_H,
+                                 d_work, d_status, stream);
 }
 
 int mf_crop_resize_plane_f32(const float* d_planes, float* d_out, int n, int W, int H, int left, int top, int right, int bottom, int out_W,

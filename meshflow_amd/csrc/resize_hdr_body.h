@@ -10,10 +10,8 @@
 // where sx + 1 < cw a sample's two taps of a row are ONE 4-byte load at 2-byte alignment, on the crop's last column only the 2-byte sample
 // is read (a1 = 0 there).
 //
-// Chroma is sited at the even luma sample with resize_uv_body.h's positions and clamps --
-//   scale = 1 / ((double)oW / cw);  fc = float((left + ((2 cx + 0.5) scale - 0.5)) 0.5);  s = floor(fc);  f = fc - s
-//   c1 = right >> 1,  c0 = min((left + 1) >> 1, c1);   x: s < c0 -> (c0, 0), s >= c1 -> (c1, 0);   y: both rows clipped to [r0, r1], f kept
-// -- and the 16-bit float arithmetic above per channel with the weights (1 - f, f) as they are: no 2048 quantisation, and NO area branch (at
+// Chroma is sited at the even luma sample (chroma_siting.h has the positions and clamps: column s and fraction f per output sample) and takes
+// the 16-bit float arithmetic above per channel with the weights (1 - f, f) as they are: no 2048 quantisation, and NO area branch (at
 // exactly 2x down an even `left` gives f = 0.25, not a box).  U and V never mix.  hdr_uv_tables_kernel builds the oW/2 + oH/2 Resize16Tab
 // entries on the device, for the host rectangle too (x: ofs = the ABSOLUTE clamped chroma column, f;  y: ofs = sy0 | sy1 << 16, absolute rows,
 // f).  hdr_uv_resize_kernel: a tap is one 4-byte word U | V << 16; a lane owns 4 consecutive chroma samples of a row (one 16-byte store), a
@@ -26,6 +24,7 @@
 #ifndef MF_RESIZE_HDR_BODY_H
 #define MF_RESIZE_HDR_BODY_H
 #include "mf_common.h"
+#include "chroma_siting.h"
 #include "resize_u8.h"
 #include "resize_rect.h"
 
@@ -102,30 +101,28 @@ __global__ __launch_bounds__(64 * kWaves) void hdr_luma_resize_kernel(const uint
     }
 }
 
-// chroma_tables_kernel's positions and clamps (resize_uv_body.h) with the fractions kept as float32
+// chroma_siting.h's positions with the fractions kept as float32
 __global__ __launch_bounds__(256) void hdr_uv_tables_kernel(MF_UV_TABLES_ARGS, int oW, int oH, Resize16Tab* __restrict__ xtab,
                                                             Resize16Tab* __restrict__ ytab)
 {
     MF_UV_TABLES_LOAD
     const double scale_x = 1.0 / ((double)oW / (double)cw), scale_y = 1.0 / ((double)oH / (double)ch);
-    const int c1 = rect_right >> 1, c0 = min((left + 1) >> 1, c1);
-    const int r1 = rect_bottom >> 1, r0 = min((top + 1) >> 1, r1);
+    int c0, c1, r0, r1;
+    chroma_site_range(left, rect_right, c0, c1);
+    chroma_site_range(top, rect_bottom, r0, r1);
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < (oW >> 1)) {
-        float fx = (float)(((double)left + (((double)(2 * i) + 0.5) * scale_x - 0.5)) * 0.5);
-        int sx = (int)floorf(fx);
-        fx -= (float)sx;
-        if (sx < c0) { fx = 0.0f; sx = c0; }
-        if (sx >= c1) { fx = 0.0f; sx = c1; }
+        float fx;
+        int sx;
+        chroma_site_x(i, left, scale_x, c0, c1, sx, fx);
         xtab[i].ofs = sx;
         xtab[i].f = fx;
     }
     if (i < (oH >> 1)) {
-        float fy = (float)(((double)top + (((double)(2 * i) + 0.5) * scale_y - 0.5)) * 0.5);
-        const int sy = (int)floorf(fy);
-        fy -= (float)sy;
-        const int sy0 = min(max(sy, r0), r1), sy1 = min(max(sy + 1, r0), r1);
-        ytab[i].ofs = sy0 | (sy1 << 16);
+        float fy;
+        int sy;
+        chroma_site(i, top, scale_y, sy, fy);
+        ytab[i].ofs = chroma_site_rows(sy, r0, r1);
         ytab[i].f = fy;
     }
 }

@@ -2,12 +2,7 @@
 // half of mf_crop_resize_nv12 / mf_crop_resize_dev_nv12 (the luma half is the u8c1 crop-resize as it is).  W, H, oW, oH and the rectangle
 // {left, top, right, bottom} (inclusive, any parity) are the LUMA frame's everywhere.
 //
-// Chroma is sited at the even luma sample, as in the NV12 warp: output chroma sample cx sits on output luma pixel 2 cx; its source is that
-// pixel's luma source position (cv2.resize's, resize_body.h), made absolute in the frame and halved:
-//   scale = 1 / ((double)oW / cw)                                              (the luma tables' own value)
-//   fc = float((left + ((2 cx + 0.5) scale - 0.5)) 0.5);  s = floor(fc);  f = fc - s
-//   c1 = right >> 1,  c0 = min((left + 1) >> 1, c1)                            (the chroma samples whose siting luma pixel lies in the crop)
-//   x axis: s < c0 -> (c0, 0);  s >= c1 -> (c1, 0)        y axis: the two row indices are clipped to [r0, r1] instead, the weights kept
+// Chroma is sited at the even luma sample (chroma_siting.h has the positions and clamps: column s and fraction f per output sample), then
 //   weights  a0 = cvRound((1 - f) 2048), a1 = cvRound(f 2048)
 //   horizontal  t   = S[s] a0 + S[s+1] a1                                      per channel; U and V never mix
 //   vertical    out = (((b0 (t0 >> 4)) >> 16) + ((b1 (t1 >> 4)) >> 16) + 2) >> 2
@@ -23,6 +18,7 @@
 #ifndef MF_RESIZE_UV_BODY_H
 #define MF_RESIZE_UV_BODY_H
 #include "mf_common.h"
+#include "chroma_siting.h"
 #include "resize_u8.h"
 #include "resize_rect.h"
 
@@ -37,26 +33,24 @@ __global__ __launch_bounds__(256) void chroma_tables_kernel(MF_UV_TABLES_ARGS, i
 {
     MF_UV_TABLES_LOAD
     const double scale_x = 1.0 / ((double)oW / (double)cw), scale_y = 1.0 / ((double)oH / (double)ch);
-    const int c1 = rect_right >> 1, c0 = min((left + 1) >> 1, c1);
-    const int r1 = rect_bottom >> 1, r0 = min((top + 1) >> 1, r1);
+    int c0, c1, r0, r1;
+    chroma_site_range(left, rect_right, c0, c1);
+    chroma_site_range(top, rect_bottom, r0, r1);
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < (oW >> 1)) {
-        float fx = (float)(((double)left + (((double)(2 * i) + 0.5) * scale_x - 0.5)) * 0.5);
-        int sx = (int)floorf(fx);
-        fx -= (float)sx;
-        if (sx < c0) { fx = 0.0f; sx = c0; }
-        if (sx >= c1) { fx = 0.0f; sx = c1; }
+        float fx;
+        int sx;
+        chroma_site_x(i, left, scale_x, c0, c1, sx, fx);
         const int a0 = (int)rintf((1.0f - fx) * 2048.0f), a1 = (int)rintf(fx * 2048.0f);
         xtab[i].ofs = sx;
         xtab[i].w = ((uint32_t)a0 << 4) | ((uint32_t)a1 << 20);
     }
     if (i < (oH >> 1)) {
-        float fy = (float)(((double)top + (((double)(2 * i) + 0.5) * scale_y - 0.5)) * 0.5);
-        const int sy = (int)floorf(fy);
-        fy -= (float)sy;
+        float fy;
+        int sy;
+        chroma_site(i, top, scale_y, sy, fy);
         const int b0 = (int)rintf((1.0f - fy) * 2048.0f), b1 = (int)rintf(fy * 2048.0f);
-        const int sy0 = min(max(sy, r0), r1), sy1 = min(max(sy + 1, r0), r1);
-        ytab[i].ofs = sy0 | (sy1 << 16);
+        ytab[i].ofs = chroma_site_rows(sy, r0, r1);
         ytab[i].w = (uint32_t)b0 | ((uint32_t)b1 << 16);
     }
 }

@@ -330,6 +330,26 @@ def check_output_size(size, name='size'):
     return int(w), int(h)
 
 
+def _device_rectangle(bounds, status):
+    """Whether `bounds` is a device rectangle (an int32[4] tensor, checked) and not four host numbers; only a device rectangle takes `status`."""
+    if isinstance(bounds, torch.Tensor):
+        _need_bounds(bounds)
+        return True
+    if status is not None:
+        raise ValueError('status belongs to a device rectangle: a host rectangle is checked when the call is made')
+    return False
+
+
+def _status_for(status, device):
+    """The status word of a device-rectangle call: the caller's int32[1] device tensor, checked, or a new zeroed one on `device`."""
+    if status is None:
+        return torch.zeros(1, dtype=torch.int32, device=device)
+    _need(status, torch.int32, 'status')
+    if status.numel() != 1:
+        raise ValueError('status must hold 1 int32')
+    return status
+
+
 def crop_resize(frames, bounds, out=None, size=None):
     """Crop to the inclusive (left, top, right, bottom) and resize back to (W, H): mfs.py:1111-1157.  frames: uint8 or uint16 (uint16:
     cv2.resize's float path, mf_crop_resize_u16c3), (n, H, W) uint8 (mf_crop_resize_u8c1) or (n, H, W, 4) uint8 (mf_crop_resize_u8c4: the
@@ -376,12 +396,7 @@ def crop_resize_resident(frames, bounds, out=None, size=None, status=None):
         _need(out, fmt.dtype, 'out')
         if tuple(out.shape) != shape:
             raise ValueError(f'out must have shape {shape} for size {(oW, oH)}, got {tuple(out.shape)}')
-    if status is None:
-        status = torch.zeros(1, dtype=torch.int32, device=frames.device)
-    else:
-        _need(status, torch.int32, 'status')
-        if status.numel() != 1:
-            raise ValueError('status must hold 1 int32')
+    status = _status_for(status, frames.device)
     work = torch.empty(_lib_.mf_crop_resize_workspace_bytes(oW, oH), dtype=torch.uint8, device=frames.device)
     _lib.check(fmt.crop_resize_dev(_ptr(frames), _ptr(out), n, W, H, _ptr(bounds), oW, oH, _ptr(work), _ptr(status), _stream()))
     return out, status
@@ -454,17 +469,75 @@ def warp_planes(planes, table, interpolation='linear', fill=0, out=None, bounds=
 
 # BT.601 limited-range red: what the reference's default border, BGR (0, 0, 255), is in Y, U, V
 NV12_BORDER_RED = (81, 90, 240)
+# ... at 10 bits, in P010's high bits: NV12_BORDER_RED << 8
+P010_BORDER_RED = (81 << 8, 90 << 8, 240 << 8)
+
+# One row per 4:2:0 format -- a luma plane stack and a half-resolution interleaved chroma one --: the samples, the format's noun in the
+# messages and the C calls that serve it.
+_Format420 = collections.namedtuple('_Format420', 'dtype noun border warp warp_bounds crop_resize crop_resize_dev workspace_bytes')
+
+
+def _row_420(name, dtype, noun, border):
+    calls = (getattr(_lib_, f'mf_{op}_{name}') for op in ('warp', 'warp_bounds', 'crop_resize', 'crop_resize_dev'))
+    return _Format420(dtype, noun, border, *calls, getattr(_lib_, f'mf_crop_resize_{name}_workspace_bytes'))
+
+
 _nv12_border = _border_samples(ctypes.c_uint8, 255, 3)
+_p010_border = _border_samples(ctypes.c_uint16, 65535, 3)
+_NV12 = _row_420('nv12', torch.uint8, 'an NV12', _nv12_border)
+_P010 = _row_420('p010', torch.uint16, 'a P010', _p010_border)        # P012 and P016 alike: plain 16-bit samples
 
 
-def _nv12_plane(t, name, shape, device, dtype=torch.uint8):
-    """One plane stack of an NV12 clip (dtype=torch.uint16: of a P010 clip): a contiguous device tensor of that dtype and of exactly `shape`
-    on `device` (None: wherever it is)."""
+def _plane_420(t, name, shape, device, dtype):
+    """One plane stack of a 4:2:0 clip: a contiguous device tensor of that dtype and of exactly `shape` on `device`."""
     _need(t, dtype, name)
     if tuple(t.shape) != tuple(shape):
         raise ValueError(f'{name} must have shape {tuple(shape)}, got {tuple(t.shape)}')
-    if device is not None and t.device != device:
+    if t.device != device:
         raise ValueError(f'{name} must be on the device of y, {device}, got {t.device}')
+
+
+def _need_420(fmt, y, uv):
+    """Check the (y, uv) pair of a clip of format `fmt`; returns (n, H, W) of the luma stack."""
+    _need(y, fmt.dtype, 'y')
+    if y.dim() != 3:
+        raise ValueError(f'y must be (n, H, W) luma planes, got shape {tuple(y.shape)}')
+    n, H, W = (int(v) for v in y.shape)
+    if W % 2 or H % 2:
+        raise ValueError(f'{fmt.noun} frame has an even width and height, got W={W} H={H}')
+    _plane_420(uv, 'uv', (n, H // 2, W // 2, 2), y.device, fmt.dtype)
+    return n, H, W
+
+
+def _out_420(fmt, y, y_shape, uv_shape, out):
+    """`out` (None: a new pair) checked as an (out_y, out_uv) pair of these shapes beside `y`."""
+    if out is None:
+        return torch.empty(y_shape, dtype=fmt.dtype, device=y.device), torch.empty(uv_shape, dtype=fmt.dtype, device=y.device)
+    if not isinstance(out, (tuple, list)) or len(out) != 2:
+        raise ValueError('out must be a pair (out_y, out_uv)')
+    out_y, out_uv = out
+    _plane_420(out_y, 'out_y', y_shape, y.device, fmt.dtype)
+    _plane_420(out_uv, 'out_uv', uv_shape, y.device, fmt.dtype)
+    return out_y, out_uv
+
+
+def _warp_420(fmt, y, uv, table, border_yuv, out, bounds):
+    """`warp_nv12` / `warp_p010`: the checks, then the format's C call."""
+    n, H, W = _need_420(fmt, y, uv)
+    if (n, W, H) != (table.n, table.W, table.H):
+        raise ValueError(f'y {tuple(y.shape)} does not match the cell table (n, H, W) = {(table.n, table.H, table.W)}')
+    if len(border_yuv) != 3:
+        raise ValueError(f'border_yuv must be (Y, U, V), got {border_yuv!r}')
+    out_y, out_uv = _out_420(fmt, y, y.shape, uv.shape, out)
+    border = fmt.border(border_yuv)
+    if bounds is None:
+        _lib.check(fmt.warp(_ptr(y), _ptr(uv), _ptr(out_y), _ptr(out_uv), _ptr(table.buf), n, W, H, table.R, table.C, border, _ptr(table.crop),
+                            _stream()))
+    else:
+        _need_bounds(bounds)
+        _lib.check(fmt.warp_bounds(_ptr(y), _ptr(uv), _ptr(out_y), _ptr(out_uv), _ptr(table.buf), n, W, H, table.R, table.C, border,
+                                   _ptr(table.crop), _ptr(bounds), _stream()))
+    return out_y, out_uv
 
 
 def warp_nv12(y, uv, table, border_yuv=NV12_BORDER_RED, out=None, bounds=None):
@@ -479,39 +552,7 @@ def warp_nv12(y, uv, table, border_yuv=NV12_BORDER_RED, out=None, bounds=None):
     No quarter-pixel correction for left- or centre-sited chroma is applied.
     border_yuv: (Y, U, V), each clamp(round(v), 0, 255).  The default (81, 90, 240) is BT.601 limited-range red, i.e. the reference's default
     BGR (0, 0, 255).  out: an (out_y, out_uv) pair to fill.  Returns (out_y, out_uv)."""
-    _need(y, torch.uint8, 'y')
-    if y.dim() != 3:
-        raise ValueError(f'y must be (n, H, W) luma planes, got shape {tuple(y.shape)}')
-    n, H, W = (int(v) for v in y.shape)
-    if W % 2 or H % 2:
-        raise ValueError(f'an NV12 frame has an even width and height, got W={W} H={H}')
-    _nv12_plane(uv, 'uv', (n, H // 2, W // 2, 2), y.device)
-    if (n, W, H) != (table.n, table.W, table.H):
-        raise ValueError(f'y {tuple(y.shape)} does not match the cell table (n, H, W) = {(table.n, table.H, table.W)}')
-    if len(border_yuv) != 3:
-        raise ValueError(f'border_yuv must be (Y, U, V), got {border_yuv!r}')
-    if out is None:
-        out_y, out_uv = torch.empty_like(y), torch.empty_like(uv)
-    else:
-        if not isinstance(out, (tuple, list)) or len(out) != 2:
-            raise ValueError('out must be a pair (out_y, out_uv)')
-        out_y, out_uv = out
-        _nv12_plane(out_y, 'out_y', y.shape, y.device)
-        _nv12_plane(out_uv, 'out_uv', uv.shape, y.device)
-    border = _nv12_border(border_yuv)
-    if bounds is None:
-        _lib.check(_lib_.mf_warp_nv12(_ptr(y), _ptr(uv), _ptr(out_y), _ptr(out_uv), _ptr(table.buf), n, W, H, table.R, table.C, border,
-                                      _ptr(table.crop), _stream()))
-    else:
-        _need_bounds(bounds)
-        _lib.check(_lib_.mf_warp_bounds_nv12(_ptr(y), _ptr(uv), _ptr(out_y), _ptr(out_uv), _ptr(table.buf), n, W, H, table.R, table.C, border,
-                                             _ptr(table.crop), _ptr(bounds), _stream()))
-    return out_y, out_uv
-
-
-# BT.601 limited-range red at 10 bits, in P010's high bits: NV12_BORDER_RED << 8
-P010_BORDER_RED = (81 << 8, 90 << 8, 240 << 8)
-_p010_border = _border_samples(ctypes.c_uint16, 65535, 3)
+    return _warp_420(_NV12, y, uv, table, border_yuv, out, bounds)
 
 
 def warp_p010(y, uv, table, border_yuv=P010_BORDER_RED, out=None, bounds=None):
@@ -527,34 +568,7 @@ def warp_p010(y, uv, table, border_yuv=P010_BORDER_RED, out=None, bounds=None):
     and where no cell owns the luma pixel, the result is (border_yuv[1], border_yuv[2]).
     border_yuv: (Y, U, V), each clamp(round(v), 0, 65535).  The default (20736, 23040, 61440) is BT.601 limited-range red at 10 bits in P010's
     high bits.  out: an (out_y, out_uv) pair to fill.  Returns (out_y, out_uv)."""
-    _need(y, torch.uint16, 'y')
-    if y.dim() != 3:
-        raise ValueError(f'y must be (n, H, W) luma planes, got shape {tuple(y.shape)}')
-    n, H, W = (int(v) for v in y.shape)
-    if W % 2 or H % 2:
-        raise ValueError(f'a P010 frame has an even width and height, got W={W} H={H}')
-    _nv12_plane(uv, 'uv', (n, H // 2, W // 2, 2), y.device, torch.uint16)
-    if (n, W, H) != (table.n, table.W, table.H):
-        raise ValueError(f'y {tuple(y.shape)} does not match the cell table (n, H, W) = {(table.n, table.H, table.W)}')
-    if len(border_yuv) != 3:
-        raise ValueError(f'border_yuv must be (Y, U, V), got {border_yuv!r}')
-    if out is None:
-        out_y, out_uv = torch.empty_like(y), torch.empty_like(uv)
-    else:
-        if not isinstance(out, (tuple, list)) or len(out) != 2:
-            raise ValueError('out must be a pair (out_y, out_uv)')
-        out_y, out_uv = out
-        _nv12_plane(out_y, 'out_y', y.shape, y.device, torch.uint16)
-        _nv12_plane(out_uv, 'out_uv', uv.shape, y.device, torch.uint16)
-    border = _p010_border(border_yuv)
-    if bounds is None:
-        _lib.check(_lib_.mf_warp_p010(_ptr(y), _ptr(uv), _ptr(out_y), _ptr(out_uv), _ptr(table.buf), n, W, H, table.R, table.C, border,
-                                      _ptr(table.crop), _stream()))
-    else:
-        _need_bounds(bounds)
-        _lib.check(_lib_.mf_warp_bounds_p010(_ptr(y), _ptr(uv), _ptr(out_y), _ptr(out_uv), _ptr(table.buf), n, W, H, table.R, table.C, border,
-                                             _ptr(table.crop), _ptr(bounds), _stream()))
-    return out_y, out_uv
+    return _warp_420(_P010, y, uv, table, border_yuv, out, bounds)
 
 
 def _even_output_size(size, name='size'):
@@ -563,6 +577,24 @@ def _even_output_size(size, name='size'):
     if oW % 2 or oH % 2:
         raise ValueError(f'an NV12 output has an even width and height, got {name}={(oW, oH)}')
     return oW, oH
+
+
+def _crop_resize_420(fmt, y, uv, bounds, size, out, status):
+    """`crop_resize_nv12` / `crop_resize_p010`: the checks, then the format's C call for a host or a device rectangle."""
+    n, H, W = _need_420(fmt, y, uv)
+    oW, oH = (W, H) if size is None else _even_output_size(size)
+    resident = _device_rectangle(bounds, status)
+    out_y, out_uv = _out_420(fmt, y, (n, oH, oW), (n, oH // 2, oW // 2, 2), out)
+    if resident:
+        status = _status_for(status, y.device)
+    work = torch.empty(fmt.workspace_bytes(oW, oH), dtype=torch.uint8, device=y.device)
+    if not resident:
+        left, top, right, bottom = (int(v) for v in bounds)
+        _lib.check(fmt.crop_resize(_ptr(y), _ptr(uv), _ptr(out_y), _ptr(out_uv), n, W, H, left, top, right, bottom, oW, oH, _ptr(work), _stream()))
+        return out_y, out_uv
+    _lib.check(fmt.crop_resize_dev(_ptr(y), _ptr(uv), _ptr(out_y), _ptr(out_uv), n, W, H, _ptr(bounds), oW, oH, _ptr(work), _ptr(status),
+                                   _stream()))
+    return out_y, out_uv, status
 
 
 def crop_resize_nv12(y, uv, bounds, size=None, out=None, status=None):
@@ -577,45 +609,7 @@ def crop_resize_nv12(y, uv, bounds, size=None, out=None, status=None):
     out: an (out_y, out_uv) pair to fill.  status (device rectangle only): as in `crop_resize_resident` -- an int32[1] device tensor, the
     caller's (it accumulates) or a new zeroed one, that an unusable rectangle adds exactly 1 to, leaving both outputs untouched.
     Returns (out_y, out_uv), or (out_y, out_uv, status) for a device rectangle."""
-    _need(y, torch.uint8, 'y')
-    if y.dim() != 3:
-        raise ValueError(f'y must be (n, H, W) luma planes, got shape {tuple(y.shape)}')
-    n, H, W = (int(v) for v in y.shape)
-    if W % 2 or H % 2:
-        raise ValueError(f'an NV12 frame has an even width and height, got W={W} H={H}')
-    _nv12_plane(uv, 'uv', (n, H // 2, W // 2, 2), y.device)
-    oW, oH = (W, H) if size is None else _even_output_size(size)
-    resident = isinstance(bounds, torch.Tensor)
-    if resident:
-        _need_bounds(bounds)
-    elif status is not None:
-        raise ValueError('status belongs to a device rectangle: a host rectangle is checked when the call is made')
-    y_shape, uv_shape = (n, oH, oW), (n, oH // 2, oW // 2, 2)
-    if out is None:
-        out_y = torch.empty(y_shape, dtype=torch.uint8, device=y.device)
-        out_uv = torch.empty(uv_shape, dtype=torch.uint8, device=y.device)
-    else:
-        if not isinstance(out, (tuple, list)) or len(out) != 2:
-            raise ValueError('out must be a pair (out_y, out_uv)')
-        out_y, out_uv = out
-        _nv12_plane(out_y, 'out_y', y_shape, y.device)
-        _nv12_plane(out_uv, 'out_uv', uv_shape, y.device)
-    if resident:
-        if status is None:
-            status = torch.zeros(1, dtype=torch.int32, device=y.device)
-        else:
-            _need(status, torch.int32, 'status')
-            if status.numel() != 1:
-                raise ValueError('status must hold 1 int32')
-    work = torch.empty(_lib_.mf_crop_resize_nv12_workspace_bytes(oW, oH), dtype=torch.uint8, device=y.device)
-    if not resident:
-        left, top, right, bottom = (int(v) for v in bounds)
-        _lib.check(_lib_.mf_crop_resize_nv12(_ptr(y), _ptr(uv), _ptr(out_y), _ptr(out_uv), n, W, H, left, top, right, bottom, oW, oH, _ptr(work),
-                                             _stream()))
-        return out_y, out_uv
-    _lib.check(_lib_.mf_crop_resize_dev_nv12(_ptr(y), _ptr(uv), _ptr(out_y), _ptr(out_uv), n, W, H, _ptr(bounds), oW, oH, _ptr(work),
-                                             _ptr(status), _stream()))
-    return out_y, out_uv, status
+    return _crop_resize_420(_NV12, y, uv, bounds, size, out, status)
 
 
 def crop_resize_p010(y, uv, bounds, size=None, out=None, status=None):
@@ -632,45 +626,7 @@ def crop_resize_p010(y, uv, bounds, size=None, out=None, status=None):
     out: an (out_y, out_uv) pair to fill.  status (device rectangle only): as in `crop_resize_resident` -- an int32[1] device tensor, the
     caller's (it accumulates) or a new zeroed one, that an unusable rectangle adds exactly 1 to, leaving both outputs untouched.
     Returns (out_y, out_uv), or (out_y, out_uv, status) for a device rectangle."""
-    _need(y, torch.uint16, 'y')
-    if y.dim() != 3:
-        raise ValueError(f'y must be (n, H, W) luma planes, got shape {tuple(y.shape)}')
-    n, H, W = (int(v) for v in y.shape)
-    if W % 2 or H % 2:
-        raise ValueError(f'a P010 frame has an even width and height, got W={W} H={H}')
-    _nv12_plane(uv, 'uv', (n, H // 2, W // 2, 2), y.device, torch.uint16)
-    oW, oH = (W, H) if size is None else _even_output_size(size)
-    resident = isinstance(bounds, torch.Tensor)
-    if resident:
-        _need_bounds(bounds)
-    elif status is not None:
-        raise ValueError('status belongs to a device rectangle: a host rectangle is checked when the call is made')
-    y_shape, uv_shape = (n, oH, oW), (n, oH // 2, oW // 2, 2)
-    if out is None:
-        out_y = torch.empty(y_shape, dtype=torch.uint16, device=y.device)
-        out_uv = torch.empty(uv_shape, dtype=torch.uint16, device=y.device)
-    else:
-        if not isinstance(out, (tuple, list)) or len(out) != 2:
-            raise ValueError('out must be a pair (out_y, out_uv)')
-        out_y, out_uv = out
-        _nv12_plane(out_y, 'out_y', y_shape, y.device, torch.uint16)
-        _nv12_plane(out_uv, 'out_uv', uv_shape, y.device, torch.uint16)
-    if resident:
-        if status is None:
-            status = torch.zeros(1, dtype=torch.int32, device=y.device)
-        else:
-            _need(status, torch.int32, 'status')
-            if status.numel() != 1:
-                raise ValueError('status must hold 1 int32')
-    work = torch.empty(_lib_.mf_crop_resize_p010_workspace_bytes(oW, oH), dtype=torch.uint8, device=y.device)
-    if not resident:
-        left, top, right, bottom = (int(v) for v in bounds)
-        _lib.check(_lib_.mf_crop_resize_p010(_ptr(y), _ptr(uv), _ptr(out_y), _ptr(out_uv), n, W, H, left, top, right, bottom, oW, oH, _ptr(work),
-                                             _stream()))
-        return out_y, out_uv
-    _lib.check(_lib_.mf_crop_resize_dev_p010(_ptr(y), _ptr(uv), _ptr(out_y), _ptr(out_uv), n, W, H, _ptr(bounds), oW, oH, _ptr(work),
-                                             _ptr(status), _stream()))
-    return out_y, out_uv, status
+    return _crop_resize_420(_P010, y, uv, bounds, size, out, status)
 
 
 def crop_resize_planes(planes, bounds, interpolation='linear', size=None, out=None, status=None):
@@ -685,11 +641,7 @@ def crop_resize_planes(planes, bounds, interpolation='linear', size=None, out=No
     es = _need_planes(planes, interpolation)
     n, H, W = planes.shape
     oW, oH = (W, H) if size is None else check_output_size(size)
-    resident = isinstance(bounds, torch.Tensor)
-    if resident:
-        _need_bounds(bounds)
-    elif status is not None:
-        raise ValueError('status belongs to a device rectangle: a host rectangle is checked when the call is made')
+    resident = _device_rectangle(bounds, status)
     out = _planes_out(planes, (n, oH, oW), out)
     work = torch.empty(_lib_.mf_crop_resize_workspace_bytes(oW, oH), dtype=torch.uint8, device=planes.device)
     if not resident:
@@ -700,12 +652,7 @@ def crop_resize_planes(planes, bounds, interpolation='linear', size=None, out=No
             _lib.check(_lib_.mf_crop_resize_plane_nearest(_ptr(planes), _ptr(out), n, W, H, left, top, right, bottom, oW, oH, es, _ptr(work),
                                                           _stream()))
         return out
-    if status is None:
-        status = torch.zeros(1, dtype=torch.int32, device=planes.device)
-    else:
-        _need(status, torch.int32, 'status')
-        if status.numel() != 1:
-            raise ValueError('status must hold 1 int32')
+    status = _status_for(status, planes.device)
     if es == 0:
         _lib.check(_lib_.mf_crop_resize_dev_plane_f32(_ptr(planes), _ptr(out), n, W, H, _ptr(bounds), oW, oH, _ptr(work), _ptr(status), _stream()))
     else:

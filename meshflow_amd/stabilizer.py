@@ -966,6 +966,20 @@ class MeshFlowStabilizer:
             self._resident_verdict(st, check, cropped=True)
         return frames, bounds, d_stab, cropped
 
+    def _checked_table(self, d_disp, W, H, adaptive_weights_definition, homographies):
+        """What the frameless calls below start with, on torch's current stream: the Jacobi sweep on d_disp, then the cell table + plan of all
+        its frames with a fresh clip rectangle.  Returns (table, bounds); waits for the table's status and raises `DegenerateMeshError`
+        (clip_serial None) before anything has been warped."""
+        import torch
+        from . import ops
+        d_stab = self._stabilized_vertex_displacements_device(d_disp, W, H, adaptive_weights_definition, homographies)
+        bounds = torch.empty(4, dtype=torch.int32, device=d_disp.device)
+        table = ops.cell_table(d_disp, d_stab, W, H, self.mesh_row_count, self.mesh_col_count, bounds=bounds)
+        bad = int(table.status.item())
+        if bad:
+            raise DegenerateMeshError(bad, None)
+        return table, bounds
+
     def stabilization_maps(self, d_disp, homographies, frame_width, frame_height,
                            adaptive_weights_definition=ADAPTIVE_WEIGHTS_DEFINITION_ORIGINAL, first=0, count=None, out=None):
         """The stabilisation's float32 coordinate maps without any frame: the Jacobi sweep (mfs.py:695-704) on d_disp -- (F, R+1, C+1, 2)
@@ -975,17 +989,11 @@ class MeshFlowStabilizer:
         (x, y) of frame first + f, (W + 1, H + 1) where no cell owns the pixel; bounds = int32[4] device tensor {left, top, right, bottom},
         the crop rectangle of the frames of the range (mfs.py:1075-1106).  A degenerate mesh raises `DegenerateMeshError` (clip_serial None)
         here, synchronously, before the maps are written."""
-        import torch
         from . import ops
         self._check_definition(adaptive_weights_definition)
         self._check_mesh_shape(d_disp, d_disp.shape[0])
         W, H = int(frame_width), int(frame_height)
-        d_stab = self._stabilized_vertex_displacements_device(d_disp, W, H, adaptive_weights_definition, homographies)
-        bounds = torch.empty(4, dtype=torch.int32, device=d_disp.device)
-        table = ops.cell_table(d_disp, d_stab, W, H, self.mesh_row_count, self.mesh_col_count, bounds=bounds)
-        bad = int(table.status.item())
-        if bad:
-            raise DegenerateMeshError(bad, None)
+        table, bounds = self._checked_table(d_disp, W, H, adaptive_weights_definition, homographies)
         return ops.warp_maps(table, first=first, count=count, out=out, bounds=bounds), bounds
 
     def stabilized_planes(self, d_planes, d_disp, homographies, interpolation='linear', fill=0, crop=False, output_size=None, out=None,
@@ -998,7 +1006,6 @@ class MeshFlowStabilizer:
         (the cropped planes with crop=True).  Returns (planes, bounds): bounds = int32[4] device tensor {left, top, right, bottom}, the
         rectangle `stabilization_maps` returns for the same inputs.  A degenerate mesh raises `DegenerateMeshError` (clip_serial None) here,
         synchronously, before a plane is written.  (A caller that moves frames AND planes keeps one table: `_stabilized_frames_device`.)"""
-        import torch
         from . import ops
         self._check_definition(adaptive_weights_definition)
         self._check_mesh_shape(d_disp, d_disp.shape[0])
@@ -1006,17 +1013,34 @@ class MeshFlowStabilizer:
             raise ValueError('output_size belongs to crop=True')
         ops._need_planes(d_planes, interpolation, 'd_planes')
         H, W = int(d_planes.shape[1]), int(d_planes.shape[2])
-        d_stab = self._stabilized_vertex_displacements_device(d_disp, W, H, adaptive_weights_definition, homographies)
-        bounds = torch.empty(4, dtype=torch.int32, device=d_disp.device)
-        table = ops.cell_table(d_disp, d_stab, W, H, self.mesh_row_count, self.mesh_col_count, bounds=bounds)
-        bad = int(table.status.item())
-        if bad:
-            raise DegenerateMeshError(bad, None)
+        table, bounds = self._checked_table(d_disp, W, H, adaptive_weights_definition, homographies)
         if not crop:
             return ops.warp_planes(d_planes, table, interpolation, fill, out=out, bounds=bounds), bounds
         warped = ops.warp_planes(d_planes, table, interpolation, fill, bounds=bounds)
         cropped, _ = ops.crop_resize_planes(warped, bounds, interpolation, size=output_size, out=out)
         return cropped, bounds
+
+    def _stabilized_420(self, fmt, d_y, d_uv, d_disp, homographies, border_yuv, out, adaptive_weights_definition, crop, output_size):
+        """`stabilized_nv12`, `stabilized_p010` and `stabilized_p010_cropped` for the 4:2:0 format `fmt` (a row of ops.py): the argument checks,
+        `_checked_table`, the warp and, with crop=True, the crop-resize of the warped temporaries from the rectangle on the device."""
+        from . import ops
+        if output_size is not None:
+            if not crop:
+                raise ValueError('output_size belongs to crop=True')
+            ops._even_output_size(output_size, 'output_size')
+        self._check_definition(adaptive_weights_definition)
+        self._check_mesh_shape(d_disp, d_disp.shape[0])
+        ops._need(d_y, fmt.dtype, 'd_y')
+        if d_y.dim() != 3:
+            raise ValueError(f'd_y must be (F, H, W) luma planes, got shape {tuple(d_y.shape)}')
+        H, W = int(d_y.shape[1]), int(d_y.shape[2])
+        table, bounds = self._checked_table(d_disp, W, H, adaptive_weights_definition, homographies)
+        if not crop:
+            out_y, out_uv = ops._warp_420(fmt, d_y, d_uv, table, border_yuv, out, bounds)
+            return out_y, out_uv, bounds
+        warped_y, warped_uv = ops._warp_420(fmt, d_y, d_uv, table, border_yuv, None, bounds)
+        out_y, out_uv, _ = ops._crop_resize_420(fmt, warped_y, warped_uv, bounds, output_size, out, None)
+        return out_y, out_uv, bounds
 
     def stabilized_nv12(self, d_y, d_uv, d_disp, homographies, border_yuv=(81, 90, 240), out=None,
                         adaptive_weights_definition=ADAPTIVE_WEIGHTS_DEFINITION_ORIGINAL, crop=False, output_size=None):
@@ -1030,30 +1054,8 @@ class MeshFlowStabilizer:
         pair to fill (the cropped pair with crop=True).  Returns (out_y, out_uv, bounds): bounds = int32[4] device tensor {left, top, right,
         bottom}, the rectangle `stabilization_maps` returns for the same inputs.  A degenerate mesh raises `DegenerateMeshError`
         (clip_serial None) here, synchronously, before a plane is written."""
-        import torch
         from . import ops
-        if output_size is not None:
-            if not crop:
-                raise ValueError('output_size belongs to crop=True')
-            ops._even_output_size(output_size, 'output_size')
-        self._check_definition(adaptive_weights_definition)
-        self._check_mesh_shape(d_disp, d_disp.shape[0])
-        ops._need(d_y, torch.uint8, 'd_y')
-        if d_y.dim() != 3:
-            raise ValueError(f'd_y must be (F, H, W) luma planes, got shape {tuple(d_y.shape)}')
-        H, W = int(d_y.shape[1]), int(d_y.shape[2])
-        d_stab = self._stabilized_vertex_displacements_device(d_disp, W, H, adaptive_weights_definition, homographies)
-        bounds = torch.empty(4, dtype=torch.int32, device=d_disp.device)
-        table = ops.cell_table(d_disp, d_stab, W, H, self.mesh_row_count, self.mesh_col_count, bounds=bounds)
-        bad = int(table.status.item())
-        if bad:
-            raise DegenerateMeshError(bad, None)
-        if not crop:
-            out_y, out_uv = ops.warp_nv12(d_y, d_uv, table, border_yuv, out=out, bounds=bounds)
-            return out_y, out_uv, bounds
-        warped_y, warped_uv = ops.warp_nv12(d_y, d_uv, table, border_yuv, bounds=bounds)
-        out_y, out_uv, _ = ops.crop_resize_nv12(warped_y, warped_uv, bounds, size=output_size, out=out)
-        return out_y, out_uv, bounds
+        return self._stabilized_420(ops._NV12, d_y, d_uv, d_disp, homographies, border_yuv, out, adaptive_weights_definition, crop, output_size)
 
     def stabilized_p010(self, d_y, d_uv, d_disp, homographies, border_yuv=(81 << 8, 90 << 8, 240 << 8), out=None,
                         adaptive_weights_definition=ADAPTIVE_WEIGHTS_DEFINITION_ORIGINAL, crop=False, output_size=None):
@@ -1066,25 +1068,11 @@ class MeshFlowStabilizer:
         to fill.  Returns (out_y, out_uv, bounds): bounds = int32[4] device tensor {left, top, right, bottom}, the rectangle
         `stabilization_maps` returns for the same inputs.  A degenerate mesh raises `DegenerateMeshError` (clip_serial None) here,
         synchronously, before a plane is written."""
-        import torch
         from . import ops
         if crop or output_size is not None:
             raise ValueError('crop-resize of 16-bit 4:2:0 clips is not built yet into stabilized_p010, which takes neither crop=True nor '
                              'output_size: call stabilized_p010_cropped')
-        self._check_definition(adaptive_weights_definition)
-        self._check_mesh_shape(d_disp, d_disp.shape[0])
-        ops._need(d_y, torch.uint16, 'd_y')
-        if d_y.dim() != 3:
-            raise ValueError(f'd_y must be (F, H, W) luma planes, got shape {tuple(d_y.shape)}')
-        H, W = int(d_y.shape[1]), int(d_y.shape[2])
-        d_stab = self._stabilized_vertex_displacements_device(d_disp, W, H, adaptive_weights_definition, homographies)
-        bounds = torch.empty(4, dtype=torch.int32, device=d_disp.device)
-        table = ops.cell_table(d_disp, d_stab, W, H, self.mesh_row_count, self.mesh_col_count, bounds=bounds)
-        bad = int(table.status.item())
-        if bad:
-            raise DegenerateMeshError(bad, None)
-        out_y, out_uv = ops.warp_p010(d_y, d_uv, table, border_yuv, out=out, bounds=bounds)
-        return out_y, out_uv, bounds
+        return self._stabilized_420(ops._P010, d_y, d_uv, d_disp, homographies, border_yuv, out, adaptive_weights_definition, False, None)
 
     def stabilized_p010_cropped(self, d_y, d_uv, d_disp, homographies, border_yuv=(81 << 8, 90 << 8, 240 << 8), out=None,
                                 adaptive_weights_definition=ADAPTIVE_WEIGHTS_DEFINITION_ORIGINAL, output_size=None):
@@ -1095,25 +1083,8 @@ class MeshFlowStabilizer:
         (out_y, out_uv) pair of the OUTPUT's size to fill.  Returns (out_y, out_uv, bounds): the cropped pair and the int32[4] device
         tensor {left, top, right, bottom} `stabilized_p010` returns for the same inputs.  A degenerate mesh raises `DegenerateMeshError`
         (clip_serial None) here, synchronously, before a plane is written."""
-        import torch
         from . import ops
-        if output_size is not None:
-            ops._even_output_size(output_size, 'output_size')
-        self._check_definition(adaptive_weights_definition)
-        self._check_mesh_shape(d_disp, d_disp.shape[0])
-        ops._need(d_y, torch.uint16, 'd_y')
-        if d_y.dim() != 3:
-            raise ValueError(f'd_y must be (F, H, W) luma planes, got shape {tuple(d_y.shape)}')
-        H, W = int(d_y.shape[1]), int(d_y.shape[2])
-        d_stab = self._stabilized_vertex_displacements_device(d_disp, W, H, adaptive_weights_definition, homographies)
-        bounds = torch.empty(4, dtype=torch.int32, device=d_disp.device)
-        table = ops.cell_table(d_disp, d_stab, W, H, self.mesh_row_count, self.mesh_col_count, bounds=bounds)
-        bad = int(table.status.item())
-        if bad:
-            raise DegenerateMeshError(bad, None)
-        warped_y, warped_uv = ops.warp_p010(d_y, d_uv, table, border_yuv, bounds=bounds)
-        out_y, out_uv, _ = ops.crop_resize_p010(warped_y, warped_uv, bounds, size=output_size, out=out)
-        return out_y, out_uv, bounds
+        return self._stabilized_420(ops._P010, d_y, d_uv, d_disp, homographies, border_yuv, out, adaptive_weights_definition, True, output_size)
 
     def _stabilized_frames_device(self, d_frames, d_unstab, d_stab, out=None, table=None):
         """d_frames: (n, H, W, 3) uint8; d_unstab/d_stab: (n, R+1, C+1, 2) float64, all in HBM.
