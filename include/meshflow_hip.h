@@ -587,6 +587,41 @@ int mf_vertex_motion_f64(const double* d_early, const double* d_late, const int3
                          int ellipse_rows, int ellipse_cols, float* d_velocities, double* d_displacements,
                          void* d_work, int32_t* d_status, void* stream);
 
+/* ---- online path smoothing: blocks of frames pushed in, a sliding window per frame, zero latency ----
+ * The reference has the offline optimisation only (mfs.py:632-710); this is a specification of the project's own, bit for bit
+ * tests/online_model.py.  Per series s of S = (R+1)(C+1)*2, frames numbered from 0 since the session began, `seen` of them before this call:
+ *   path     C_0 = 0, C_t = C_{t-1} + (double)v_t: the sequential float64 running sum of mf_vertex_motion_f64's d_displacements, formed
+ *            here from the velocities and the one carried C -- a stream pushed in blocks of any sizes yields the bits of one block
+ *   window   xi has newest frame xi and covers Phi = [max(0, xi - window + 1), xi]; taps w_d = exp(-((3 / omega) d)^2), 1 <= d <= omega,
+ *            made on the host (d_taps [omega] float64, d_taps[d - 1] = w_d); no d = 0 tap
+ *   weights  lam_t for t < xi is the adaptive weight of pair (t -> t + 1), known once frame t + 1 has arrived; lam_xi = lam_newest, the
+ *            weight of the identity homography (what the reference gives its last frame, mfs.py:273-274, 757)
+ *   start    x_t = q_t, window xi - 1's solution, for t < xi; x_xi = C_xi + (q_{xi-1} - C_{xi-1}); x_0 = C_0 in window 0
+ *   sweep    `iters` times, every t of Phi: acc = sum w_|d| x_{t+d} and sw = sum w_|d| over d = -omega .. omega ascending, without d = 0
+ *            and every t + d outside Phi, both from 0.0, a rounded multiply then a rounded add per term (no fma);
+ *            x'_t = ((C_t + beta q_t) + (2 lam_t) acc) / ((1 + beta) + (2 lam_t) sw) for t < xi and
+ *            x'_xi = (C_xi + (2 lam_xi) acc) / (1.0 + (2 lam_xi) sw) -- the newest frame has no q --, IEEE division
+ *   result   P_xi = x_xi after the last sweep; the whole x is window xi + 1's q
+ * One block of n new frames: d_vel [n][S] float32, row i the velocity of the pair that ENDS at new frame i (mf_vertex_motion_f64's
+ * d_velocities); d_lam_known [n] float64, entry i the weight of the frame BEFORE new frame i.  Row 0 / entry 0 are not read when seen is 0.
+ * d_c_out, d_p_out [n][S] float64: C and P of the new frames, mf_jacobi_f64's [F][S] layout.
+ * State, updated in place, zeroed by the caller before the first call (seen = 0 reads none of it): d_c_state, d_q_state [window - 1][S]
+ * and d_lam_state [window - 1] float64; afterwards row j holds frame seen + n - (window - 1) + j, zeros where that frame does not exist,
+ * and the last row of d_lam_state holds lam_newest.  The caller adds n to `seen`.
+ * The n windows run in order inside ONE launch of one wavefront per series (frame t in lane t mod window; x in 1 KB of LDS); a second,
+ * 64-lane launch behind it shifts d_lam_state, which every wavefront of the first reads.  No atomics; a second call on the same inputs
+ * gives the same bytes; a non-finite value stays in its series.
+ * Limits (MF_ERR_INVALID_ARG, nothing launched): n >= 1, S >= 1; window in 2 .. MF_ONLINE_MAX_WINDOW; omega in 1 .. MF_ONLINE_MAX_OMEGA;
+ * iters in 1 .. MF_ONLINE_MAX_ITERS; beta and lam_newest finite and >= 0; seen >= 0; null pointers; d_vel 4-byte and every float64 array
+ * 8-byte aligned; outputs that overlap inputs, the state or each other; state arrays that overlap inputs or each other.
+ * Asynchronous on `stream`. */
+#define MF_ONLINE_MAX_WINDOW 64
+#define MF_ONLINE_MAX_OMEGA 64
+#define MF_ONLINE_MAX_ITERS 1000
+int mf_online_smooth_f64(const float* d_vel, const double* d_lam_known, const double* d_taps, int n, int S, int omega, int window, int iters,
+                         double beta, double lam_newest, int64_t seen, double* d_c_state, double* d_q_state, double* d_lam_state,
+                         double* d_c_out, double* d_p_out, void* stream);
+
 /* ---- stability score (mfs.py:1216-1259) of device-resident vertex paths ----
  * d_stab: [F][S] float64 as for mf_jacobi_f64 (S = V*2: x and y of every vertex interleaved).  Per series the fraction of
  * the velocity profile's spectral energy that sits in DFT bins 1..5 (five direct sums + Parseval for the total);

@@ -817,6 +817,57 @@ int mf_vertex_motion_f64(const double* d_early, const double* d_late, const int3
                                 ellipse_rows, ellipse_cols, d_velocities, d_displacements, d_work, d_status, (hipStream_t)stream);
 }
 
+int mf_online_smooth_f64(const float* d_vel, const double* d_lam_known, const double* d_taps, int n, int S, int omega, int window, int iters,
+                         double beta, double lam_newest, int64_t seen, double* d_c_state, double* d_q_state, double* d_lam_state,
+                         double* d_c_out, double* d_p_out, void* stream)
+{
+    const char* name = "mf_online_smooth_f64";
+    if (n < 1 || S < 1) { set_error("%s: n and S must be at least 1 (got %d, %d)", name, n, S); return MF_ERR_INVALID_ARG; }
+    if (window < 2 || window > MF_ONLINE_MAX_WINDOW) {
+        set_error("%s: window must be in 2 .. %d (got %d)", name, MF_ONLINE_MAX_WINDOW, window);
+        return MF_ERR_INVALID_ARG;
+    }
+    if (omega < 1 || omega > MF_ONLINE_MAX_OMEGA) { set_error("%s: omega must be in 1 .. %d (got %d)", name, MF_ONLINE_MAX_OMEGA, omega); return MF_ERR_INVALID_ARG; }
+    if (iters < 1 || iters > MF_ONLINE_MAX_ITERS) { set_error("%s: iters must be in 1 .. %d (got %d)", name, MF_ONLINE_MAX_ITERS, iters); return MF_ERR_INVALID_ARG; }
+    if (!(beta >= 0.0) || !(beta - beta == 0.0)) { set_error("%s: beta must be finite and >= 0 (got %g)", name, beta); return MF_ERR_INVALID_ARG; }
+    if (!(lam_newest >= 0.0) || !(lam_newest - lam_newest == 0.0)) {
+        set_error("%s: lam_newest must be finite and >= 0 (got %g)", name, lam_newest);
+        return MF_ERR_INVALID_ARG;
+    }
+    if (seen < 0) { set_error("%s: seen must not be negative (got %lld)", name, (long long)seen); return MF_ERR_INVALID_ARG; }
+    if (!d_vel || !d_lam_known || !d_taps || !d_c_state || !d_q_state || !d_lam_state || !d_c_out || !d_p_out) {
+        set_error("%s: null pointer", name);
+        return MF_ERR_INVALID_ARG;
+    }
+    if (((uintptr_t)d_vel & 3) || ((uintptr_t)d_lam_known & 7) || ((uintptr_t)d_taps & 7) || ((uintptr_t)d_c_state & 7) || ((uintptr_t)d_q_state & 7) ||
+        ((uintptr_t)d_lam_state & 7) || ((uintptr_t)d_c_out & 7) || ((uintptr_t)d_p_out & 7)) {
+        set_error("%s: d_vel must be 4-byte aligned, every float64 array 8-byte aligned", name);
+        return MF_ERR_INVALID_ARG;
+    }
+    const size_t rows = (size_t)n, series = (size_t)S, held = (size_t)window - 1;
+    const struct { const void* at; size_t bytes; } in[3] = {{d_vel, rows * series * 4}, {d_lam_known, rows * 8}, {d_taps, (size_t)omega * 8}},
+                                                   state[3] = {{d_c_state, held * series * 8}, {d_q_state, held * series * 8}, {d_lam_state, held * 8}},
+                                                   out[2] = {{d_c_out, rows * series * 8}, {d_p_out, rows * series * 8}};
+    for (const auto& o : out) {
+        for (const auto& i : in)
+            if (overlap(i.at, i.bytes, o.at, o.bytes)) { set_error("%s: an output aliases an input", name); return MF_ERR_INVALID_ARG; }
+        for (const auto& q : state)
+            if (overlap(q.at, q.bytes, o.at, o.bytes)) { set_error("%s: an output aliases the state", name); return MF_ERR_INVALID_ARG; }
+    }
+    if (overlap(out[0].at, out[0].bytes, out[1].at, out[1].bytes)) { set_error("%s: d_c_out and d_p_out alias", name); return MF_ERR_INVALID_ARG; }
+    for (int a = 0; a < 3; ++a) {                           // (the state is updated in place while the inputs are still being read)
+        for (const auto& i : in)
+            if (overlap(i.at, i.bytes, state[a].at, state[a].bytes)) { set_error("%s: the state aliases an input", name); return MF_ERR_INVALID_ARG; }
+        for (int b = a + 1; b < 3; ++b)
+            if (overlap(state[a].at, state[a].bytes, state[b].at, state[b].bytes)) {
+                set_error("%s: two of the state arrays alias", name);
+                return MF_ERR_INVALID_ARG;
+            }
+    }
+    return launch_online_smooth(d_vel, d_lam_known, d_taps, n, S, omega, window, iters, beta, lam_newest, (long long)seen, d_c_state, d_q_state,
+                                d_lam_state, d_c_out, d_p_out, (hipStream_t)stream);
+}
+
 int mf_stability_score_f64(const double* d_stab, int F, int S, double* d_series, double* d_score, void* stream)
 {
     if (!d_stab || !d_series || !d_score) { set_error("mf_stability_score_f64: null pointer"); return MF_ERR_INVALID_ARG; }

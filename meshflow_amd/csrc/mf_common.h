@@ -380,6 +380,10 @@ size_t vertex_motion_workspace_bytes(int total_features, int max_per_pair, int P
 int launch_vertex_motion(const double* early, const double* late, const int32_t* offsets, const double* hom, int P,
                          int total_features, int max_per_pair, int W, int H, int R, int C, int ell_rows, int ell_cols,
                          float* vel, double* disp, void* work, int32_t* status, hipStream_t st);
+// online_smooth.hip: mf_online_smooth_f64 behind capi.hip's checks
+int launch_online_smooth(const float* vel, const double* lam_known, const double* taps, int n, int S, int omega, int L, int iters,
+                         double beta, double lam_newest, long long seen, double* c_state, double* q_state, double* lam_state,
+                         double* c_out, double* p_out, hipStream_t st);
 int launch_selftest_sqrt(unsigned long long n, unsigned long long seed, unsigned long long* d_mismatches, hipStream_t st);
 int launch_stability_score(const double* stab, int F, int S, double* ratio, double* score, hipStream_t st);
 int launch_crop_reduce(const int32_t* crop, int n, int W, int H, int32_t* bounds, hipStream_t st);

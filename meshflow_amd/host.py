@@ -60,6 +60,15 @@ def jacobi_band_coefficients(num_frames, frame_width, frame_height, definition, 
     return taps, lam, np.reciprocal(on)             # mfs.py:873
 
 
+def online_taps(omega):
+    """The online smoother's taps (include/meshflow_hip.h, mf_online_smooth_f64): w(d) for d = 1 .. omega, the offline band's formula
+    without its centre."""
+    omega = int(omega)
+    if omega < 1:
+        raise ValueError('omega must be >= 1')
+    return np.exp(-np.square((3 / omega) * np.arange(1, omega + 1)))
+
+
 def vertex_x_y(frame_width, frame_height, mesh_rows, mesh_cols):
     """mfs.py:881-906: (V, 1, 2) float32 vertex pixel coordinates."""
     xs = [math.ceil((frame_width - 1) * (col / mesh_cols)) for col in range(mesh_cols + 1)]

@@ -1,0 +1,162 @@
+"""Online stabilization: frames pushed in as they arrive, every frame out again at once (`MeshFlowStabilizer.online_session`).
+
+The offline path needs a whole clip twice: `ops.jacobi` smooths every vertex path over all its frames, and the crop rectangle is a clip-level
+reduction.  A session replaces the first by `ops.online_smooth` -- a sliding window that ends at the newest frame (include/meshflow_hip.h,
+mf_online_smooth_f64; tests/online_model.py) -- and the second by a rectangle fixed in advance from `crop_margin`.  Everything else is the
+offline path's own: `ops.luma`, the device tracker with the outlier step and the fit on the device, `ops.vertex_motion`, `ops.cell_table`,
+the format's warp and crop-resize.  What a session carries between pushes: the previous push's last luma frame and an `ops.OnlineState`."""
+import collections
+import math
+
+import numpy as np
+
+from . import host
+
+# What `push` reports beside its frames.  first: the session's index of the push's first frame; d_unstab, d_stab: (n, R+1, C+1, 2) float64
+# device tensors, the unstabilized and the stabilized vertex paths; rectangle: the fixed crop (left, top, right, bottom), inclusive, in
+# `ops.crop_resize`'s convention; covered: (n,) bool device tensor, True where the frame's own crop values (`CellTable.crop`, mfs.py:1075-1098)
+# contain the rectangle -- False says the margin was too small for that frame and border colour shows --; lost: the session's indices of the
+# frames whose pair (frame - 1 -> frame) could not be fitted.
+OnlineReport = collections.namedtuple('OnlineReport', 'first d_unstab d_stab rectangle covered lost')
+
+
+def margin_rectangle(crop_margin, W, H):
+    """The fixed rectangle of a W x H frame: left = floor(m (W - 1)), right = (W - 1) - left, the same vertically; inclusive edges, any
+    parity (`ops.crop_resize_nv12` takes the rectangle in luma pixels of any parity, so a 4:2:0 pair needs no other)."""
+    left, top = math.floor(crop_margin * (W - 1)), math.floor(crop_margin * (H - 1))
+    right, bottom = (W - 1) - left, (H - 1) - top
+    if right - left + 1 < 2 or bottom - top + 1 < 2:
+        raise ValueError(f'crop_margin={crop_margin} leaves fewer than 2 x 2 pixels of a {W} x {H} frame')
+    return left, top, right, bottom
+
+
+class OnlineSession:
+    """One stream of frames through `stabilizer`.  Made by `MeshFlowStabilizer.online_session`, which documents the keywords."""
+
+    def __init__(self, stabilizer, window=40, iters=10, beta=1.0, crop_margin=0.08, output_size=None,
+                 adaptive_weights_definition=host.ADAPTIVE_WEIGHTS_DEFINITION_ORIGINAL, chunk_pairs=32, max_per_subframe=1024, red_first=False,
+                 on_lost='hold'):
+        from . import _lib
+        stabilizer._check_definition(adaptive_weights_definition)
+        omega = int(stabilizer.temporal_smoothing_radius)
+        if not 2 <= int(window) <= _lib.ONLINE_MAX_WINDOW:
+            raise ValueError(f'window must be in 2 .. {_lib.ONLINE_MAX_WINDOW} frames (got {window})')
+        if not 1 <= omega <= _lib.ONLINE_MAX_OMEGA:
+            raise ValueError(f'an online session needs temporal_smoothing_radius in 1 .. {_lib.ONLINE_MAX_OMEGA} (got {omega})')
+        if not 1 <= int(iters) <= _lib.ONLINE_MAX_ITERS:
+            raise ValueError(f'iters must be in 1 .. {_lib.ONLINE_MAX_ITERS} (got {iters})')
+        if not (math.isfinite(beta) and beta >= 0):
+            raise ValueError(f'beta must be finite and >= 0 (got {beta})')
+        if not (isinstance(crop_margin, (int, float)) and 0 <= crop_margin < 0.5):
+            raise ValueError(f'crop_margin must lie in [0, 0.5) (got {crop_margin!r})')
+        if on_lost not in ('hold', 'raise'):
+            raise ValueError(f"on_lost must be 'hold' or 'raise' (got {on_lost!r})")
+        self.stabilizer, self.window, self.omega, self.iters, self.beta = stabilizer, int(window), omega, int(iters), float(beta)
+        self.crop_margin, self.output_size, self.definition = crop_margin, output_size, adaptive_weights_definition
+        self.chunk_pairs, self.red_first, self.on_lost = chunk_pairs, red_first, on_lost
+        self.device = stabilizer._torch_device()
+        self.tracker = stabilizer.device_tracker(max_per_subframe, 'device', 'device')
+        self.form = None              # (pair?, dtype, frame shape) of the first push; the rectangle and the state follow from it
+        self.rectangle = self.state = self._last_luma = self._taps = self._lam_newest = None
+
+    @property
+    def seen(self):
+        return self.state.seen if self.state is not None else 0
+
+    def reset(self):
+        """Forget every frame pushed so far (a caller that knows of a cut): the next push starts a path at frame 0, as a fresh session's
+        does.  The frame size and form stay."""
+        if self.state is not None:
+            self.state.reset()
+        self._last_luma = None
+
+    def _luma_of(self, frames):
+        """(form, luma (n, H, W) uint8) of a push, in any form `stabilize_scored` takes."""
+        import torch
+        from . import ops
+        if isinstance(frames, (tuple, list)):
+            if len(frames) != 2:
+                raise ValueError('an NV12 or P010 clip is the pair (d_y, d_uv)')
+            d_y, d_uv = frames
+            fmt = ops._P010 if isinstance(d_y, torch.Tensor) and d_y.dtype == torch.uint16 else ops._NV12
+            ops._need_420(fmt, d_y, d_uv)
+            return (True, d_y.dtype, tuple(d_y.shape[1:])), (ops.luma(d_y) if fmt is ops._P010 else d_y)
+        if isinstance(frames, torch.Tensor) and frames.dtype == torch.uint16 and frames.dim() == 3:
+            raise ValueError('a (n, H, W) uint16 stack is the luma plane of a P010 clip: pass the pair (d_y, d_uv)')
+        ops._frames_format(frames)
+        return (False, frames.dtype, tuple(frames.shape[1:])), (ops.luma(frames, self.red_first) if ops.luma_source(frames) is not None else frames)
+
+    def _start(self, form, H, W):
+        import torch
+        from . import ops
+        pair = form[0]
+        if self.output_size is not None:
+            self.output_size = (ops._even_output_size if pair else ops.check_output_size)(self.output_size, 'output_size')
+        rectangle = margin_rectangle(self.crop_margin, W, H)
+        s = self.stabilizer
+        self.state = ops.OnlineState((s.mesh_row_count + 1) * (s.mesh_col_count + 1) * 2, self.window, self.device)
+        self._taps = torch.from_numpy(host.online_taps(self.omega)).to(self.device)
+        # the weight of the newest frame: the identity homography's under the chosen definition (mfs.py:273-274, 757)
+        self._lam_newest = float(host.adaptive_weights(1, W, H, self.definition, np.identity(3)[None])[0])
+        self.form, self.rectangle = form, rectangle
+
+    def push(self, frames):
+        """One or more new frames -- a stack (n, ...) in any form `stabilize_scored` takes, on the session's device -- in; returns
+        (the same n frames stabilized and cropped, in the input's form, `OnlineReport`)."""
+        import torch
+        from . import _lib, ops
+        s = self.stabilizer
+        form, luma = self._luma_of(frames)
+        n, H, W = (int(v) for v in luma.shape)
+        if n < 1:
+            raise ValueError('push needs at least one frame')
+        if self.form is None:
+            self._start(form, H, W)
+        elif form != self.form:
+            raise ValueError(f'this session takes {self.form[1]} frames of shape {self.form[2]}{" as (d_y, d_uv) pairs" if self.form[0] else ""}; '
+                             f'got {form[1]} frames of shape {form[2]}{" as a pair" if form[0] else ""}')
+        R, C, S, first = s.mesh_row_count, s.mesh_col_count, self.state.S, self.state.seen
+        # pairs: (the frame kept from the previous push -> new frame 0), then the adjacent new frames
+        stack, k0 = (luma, 1) if self._last_luma is None else (torch.cat([self._last_luma[None], luma]), 0)
+        vel = torch.zeros((n, S), dtype=torch.float32, device=self.device)
+        lam_known = np.full(n, self._lam_newest)
+        lost = []
+        if stack.shape[0] >= 2:
+            early, late, offsets, kmax, d_hom, d_info = self.tracker.track_stacks_resident(stack[:-1], stack[1:], self.chunk_pairs)
+            _, d_vel, status = ops.vertex_motion(early, late, offsets, d_hom, kmax, W, H, R, C, s.feature_ellipse_row_count,
+                                                 s.feature_ellipse_col_count)
+            homographies, info = d_hom.cpu().numpy(), d_info.cpu().numpy()          # (the one wait of a push beyond the tracker's own)
+            ops.vertex_motion_check(status)
+            bad = np.nonzero(info[:, 0] != _lib.HFIT_OK)[0]
+            if bad.size and self.on_lost == 'raise':
+                t = first + k0 + int(bad[0]) - 1
+                raise ValueError(f'fewer than {s.homography_min_number_corresponding_features} features could be '
+                                 f'tracked from frame {t} to frame {t + 1}')
+            d_vel = d_vel.reshape(-1, S)
+            if bad.size:
+                # 'hold': no motion for such a pair.  The fit left the identity there, whose weight is lam_newest's; an empty feature range
+                # gives a zero velocity by itself (oracle/motion_oracle.py), a refused fit over a non-empty range does not
+                d_vel = d_vel.index_fill(0, torch.from_numpy(bad).to(self.device), 0.0)
+                lost = [first + k0 + int(b) for b in bad]
+            vel[k0:] = d_vel
+            lam_known[k0:] = host.adaptive_weights(len(homographies), W, H, self.definition, homographies)
+        c, p = ops.online_smooth(vel, torch.from_numpy(lam_known).to(self.device), self.state, self._taps, self.omega, self.iters, self.beta,
+                                 self._lam_newest)
+        self._last_luma = luma[-1].clone()
+        table = ops.cell_table(c, p, W, H, R, C)
+        left, top, right, bottom = self.rectangle
+        whole = (left, top, right, bottom) == (0, 0, W - 1, H - 1) and self.output_size in (None, (W, H))
+        if form[0]:
+            fmt = ops._P010 if form[1] == torch.uint16 else ops._NV12
+            out = ops._warp_420(fmt, frames[0], frames[1], table, ops.P010_BORDER_RED if fmt is ops._P010 else ops.NV12_BORDER_RED, None, None)
+            if not whole:
+                out = ops._crop_resize_420(fmt, out[0], out[1], self.rectangle, self.output_size, None, None)
+        else:
+            out = ops.warp(frames, table, s.color_outside_image_area_bgr)
+            if not whole:
+                out = ops.crop_resize(out, self.rectangle, size=self.output_size)
+        table.check()
+        crop = table.crop
+        covered = (crop[:, 0] <= left) & (crop[:, 1] <= top) & (crop[:, 2] >= right) & (crop[:, 3] >= bottom)
+        shape = (n, R + 1, C + 1, 2)
+        return out, OnlineReport(first, c.view(shape), p.view(shape), self.rectangle, covered, lost)

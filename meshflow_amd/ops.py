@@ -943,6 +943,60 @@ def vertex_motion_check(status):
         raise ValueError('math domain error')          # what math.sqrt raises at mfs.py:444
 
 
+class OnlineState:
+    """What `online_smooth` carries from block to block (include/meshflow_hip.h, mf_online_smooth_f64): the last L - 1 frames of the
+    unstabilized path `c`, of the previous window's solution `q` -- both (L - 1, S) float64 -- and of the weights `lam` (L - 1,), on
+    `device`, plus `seen`, the frames pushed so far.  `reset()` empties it."""
+
+    def __init__(self, S, L, device):
+        S, L = int(S), int(L)
+        if S < 1 or not 2 <= L <= _lib.ONLINE_MAX_WINDOW:
+            raise ValueError(f'OnlineState: S must be at least 1 and L in 2 .. {_lib.ONLINE_MAX_WINDOW} (got S={S}, L={L})')
+        self.S, self.L = S, L
+        self.c = torch.zeros((L - 1, S), dtype=torch.float64, device=device)
+        self.device = self.c.device                       # (with its index: 'cuda' is the current device)
+        self.q = torch.zeros((L - 1, S), dtype=torch.float64, device=self.device)
+        self.lam = torch.zeros(L - 1, dtype=torch.float64, device=self.device)
+        self.seen = 0
+
+    def reset(self):
+        for t in (self.c, self.q, self.lam):
+            t.zero_()
+        self.seen = 0
+
+
+def online_smooth(vel, lam_known, state, taps, omega, iters, beta, lam_newest):
+    """One block of n new frames through the online smoother (mf_online_smooth_f64, bit for bit tests/online_model.py): every frame is
+    smoothed over the window of `state.L` frames that ends at it.  vel: (n, S) or (n, R+1, C+1, 2) float32 device tensor, row i the vertex
+    velocity of the pair that ends at new frame i (`vertex_motion`'s velocities); lam_known: (n,) float64, entry i the adaptive weight of
+    the frame before new frame i; row 0 / entry 0 are not read while the state is empty.  taps: (omega,) float64, `host.online_taps`.
+    Returns (c, p): the unstabilized and the stabilized path of the n frames, (n, S) float64; `state` is updated in place.  Runs on
+    torch's current stream and does not wait for it."""
+    name = 'online_smooth'
+    if not isinstance(state, OnlineState):
+        raise ValueError(f'{name}: state must be an OnlineState')
+    _need(vel, torch.float32, 'vel')
+    _need(lam_known, torch.float64, 'lam_known')
+    _need(taps, torch.float64, 'taps')
+    n = vel.shape[0] if vel.dim() else 0
+    if n < 1 or vel.numel() != n * state.S:
+        raise ValueError(f'{name}: vel must hold (n, {state.S}) velocities with n >= 1, got {tuple(vel.shape)}')
+    if tuple(lam_known.shape) != (n,):
+        raise ValueError(f'{name}: lam_known must have shape ({n},), got {tuple(lam_known.shape)}')
+    if tuple(taps.shape) != (int(omega),):
+        raise ValueError(f'{name}: taps must have shape ({int(omega)},), got {tuple(taps.shape)}')
+    for t, what in ((vel, 'vel'), (lam_known, 'lam_known'), (taps, 'taps')):
+        if t.device != state.device:
+            raise ValueError(f'{name}: {what} must be on the device of the state, {state.device}, got {t.device}')
+    c = torch.empty((n, state.S), dtype=torch.float64, device=state.device)
+    p = torch.empty((n, state.S), dtype=torch.float64, device=state.device)
+    _lib.check(_lib_.mf_online_smooth_f64(_ptr(vel), _ptr(lam_known), _ptr(taps), n, state.S, int(omega), state.L, int(iters), float(beta),
+                                          float(lam_newest), state.seen, _ptr(state.c), _ptr(state.q), _ptr(state.lam), _ptr(c), _ptr(p),
+                                          _stream()))
+    state.seen += n
+    return c, p
+
+
 def stability_score(stab):
     """Stability score (mfs.py:1216-1259) of device-resident paths: (F, R+1, C+1, 2) or (F, S) float64 tensor ->
     (score (1,) float64 tensor, per-series fractions (S,))."""

@@ -375,6 +375,33 @@ class MeshFlowStabilizer:
         cropping_ratio, distortion_score = self.cropping_and_distortion_resident(luma, cropped_luma, chunk_pairs, max_per_subframe)
         return cropped, (cropping_ratio, distortion_score, self._compute_stability_score_device(d_stab))
 
+    def online_session(self, window=40, iters=10, beta=1.0, crop_margin=0.08, output_size=None,
+                       adaptive_weights_definition=ADAPTIVE_WEIGHTS_DEFINITION_ORIGINAL, chunk_pairs=32, max_per_subframe=1024, red_first=False,
+                       on_lost='hold'):
+        """Stabilization of a stream whose end nobody has seen -- a capture card, a decoder's ring, a clip longer than HBM: an
+        `online.OnlineSession` whose `push(frames)` takes one or more new frames in any form `stabilize_scored` takes and returns
+        (those frames stabilized and cropped, in the input's form, `online.OnlineReport`) at once, with zero latency.  The reference has no
+        such path; the arithmetic is the library's own (include/meshflow_hip.h, mf_online_smooth_f64; tests/online_model.py).
+        Per push: `ops.luma` where the frames are not luma yet; the pairs (the previous push's last frame -> the first new one, then the
+        adjacent new ones) through `device_tracker(max_per_subframe, 'device', 'device').track_stacks_resident(early, late, chunk_pairs)`;
+        their velocities from `ops.vertex_motion` (its running sum is ignored: the smoother keeps its own across pushes); their weights from
+        `host.adaptive_weights` on the homographies, which come down with the fit's record -- the one wait of a push beyond the tracker's
+        own --; `ops.online_smooth` over a window of `window` frames (2 .. 64) that ends at each new frame, radius
+        `temporal_smoothing_radius` (1 .. 64), `iters` sweeps, `beta` the pull towards the previous window's solution;
+        `ops.cell_table(c, p, ...)`; the format's warp; the format's crop-resize to a FIXED rectangle: left = floor(crop_margin (W - 1)),
+        right = (W - 1) - left, the same vertically (crop_margin in [0, 0.5), at least 2 x 2 pixels left, else ValueError; 0 returns the warp
+        uncropped), scaled back to the frame size or to output_size = (width, height).  The report says per frame whether the rectangle
+        was `covered`.  on_lost: a pair the tracker cannot fit is zero motion and listed in the report's `lost` ('hold'), or today's
+        ValueError with the session unchanged ('raise').  `reset()` empties the session's memory at a cut.  Frame size and form are fixed
+        by the first push; a later mismatch is a ValueError."""
+        from . import online
+        return online.OnlineSession(self, window, iters, beta, crop_margin, output_size, adaptive_weights_definition, chunk_pairs,
+                                    max_per_subframe, red_first, on_lost)
+
+    def stabilize_online(self, clip, **session):
+        """One `online_session(**session)` and one push of the whole clip: (stabilized and cropped clip, `online.OnlineReport`)."""
+        return self.online_session(**session).push(clip)
+
     def _write_stabilized_video(self, output_path, num_frames, frames_per_second, codec, stabilized_frames):
         """mfs.py:1290-1322."""
         from . import frontend_cv2
