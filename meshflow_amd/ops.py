@@ -549,7 +549,8 @@ def warp_nv12(y, uv, table, border_yuv=NV12_BORDER_RED, out=None, bounds=None):
     rectangle in `bounds` / table.clip_bounds are its.  Chroma is DEFINED as sited at the even luma sample: output chroma sample (cx, cy) takes
     `warp_maps(table)[f, 2 cy, 2 cx]`, halves it in float32 and samples the (H/2, W/2) two-channel plane like cv2.remap's 8-bit INTER_LINEAR with
     BORDER_CONSTANT; where the source lies outside the plane, and where no cell owns the luma pixel, the result is (border_yuv[1], border_yuv[2]).
-    No quarter-pixel correction for left- or centre-sited chroma is applied.
+    No quarter-pixel correction for left- or centre-sited chroma is applied.  (That the definition registers chroma on luma is checked by the
+    tests' `second_opinion` module: a float64 sampler of both planes, and a ramp on which chroma must equal the luma of its even pixel.)
     border_yuv: (Y, U, V), each clamp(round(v), 0, 255).  The default (81, 90, 240) is BT.601 limited-range red, i.e. the reference's default
     BGR (0, 0, 255).  out: an (out_y, out_uv) pair to fill.  Returns (out_y, out_uv)."""
     return _warp_420(_NV12, y, uv, table, border_yuv, out, bounds)
@@ -565,7 +566,8 @@ def warp_p010(y, uv, table, border_yuv=P010_BORDER_RED, out=None, bounds=None):
     channel; the per-frame crop values in table.crop and the clip-level rectangle in `bounds` / table.clip_bounds are that call's.  Chroma is
     sited at the even luma sample, as in `warp_nv12`: output chroma sample (cx, cy) takes `warp_maps(table)[f, 2 cy, 2 cx]`, halves it in
     float32 and samples the (H/2, W/2) two-channel plane with the same CV_16U arithmetic per channel; where the source lies outside the plane,
-    and where no cell owns the luma pixel, the result is (border_yuv[1], border_yuv[2]).
+    and where no cell owns the luma pixel, the result is (border_yuv[1], border_yuv[2]).  (Checked for consistency with luma by the tests'
+    `second_opinion` module, as for `warp_nv12`.)
     border_yuv: (Y, U, V), each clamp(round(v), 0, 65535).  The default (20736, 23040, 61440) is BT.601 limited-range red at 10 bits in P010's
     high bits.  out: an (out_y, out_uv) pair to fill.  Returns (out_y, out_uv)."""
     return _warp_420(_P010, y, uv, table, border_yuv, out, bounds)
@@ -606,6 +608,8 @@ def crop_resize_nv12(y, uv, bounds, size=None, out=None, status=None):
     DEFINED as sited at the even luma sample: output chroma sample cx takes the luma source position of output luma pixel 2 cx, made absolute in
     the frame and halved, clamped to the chroma samples whose siting luma pixel lies inside the crop, and cv2.resize's 8-bit INTER_LINEAR
     arithmetic per channel (include/meshflow_hip.h has every expression).  The full frame at its own size is a copy.
+    (The definition's consistency with luma -- positions, parity, clamp range -- is checked by the tests' `second_opinion` module against
+    float64 positions of its own.)
     out: an (out_y, out_uv) pair to fill.  status (device rectangle only): as in `crop_resize_resident` -- an int32[1] device tensor, the
     caller's (it accumulates) or a new zeroed one, that an unusable rectangle adds exactly 1 to, leaving both outputs untouched.
     Returns (out_y, out_uv), or (out_y, out_uv, status) for a device rectangle."""
@@ -622,7 +626,7 @@ def crop_resize_p010(y, uv, bounds, size=None, out=None, status=None):
     cv2.resize's float path on CV_16UC1, and INTER_AREA's (S00 + S01 + S10 + S11 + 2) >> 2 where the crop is exactly twice the output in both
     axes.  Chroma is sited at the even luma sample with `crop_resize_nv12`'s positions and clamps and the same float arithmetic per channel,
     weights (1 - f, f) in float32 -- no 2048 quantisation and no area branch (include/meshflow_hip.h has every expression).  The full frame at
-    its own size is a copy.
+    its own size is a copy.  (Checked for consistency with luma by the tests' `second_opinion` module, as for `crop_resize_nv12`.)
     out: an (out_y, out_uv) pair to fill.  status (device rectangle only): as in `crop_resize_resident` -- an int32[1] device tensor, the
     caller's (it accumulates) or a new zeroed one, that an unusable rectangle adds exactly 1 to, leaving both outputs untouched.
     Returns (out_y, out_uv), or (out_y, out_uv, status) for a device rectangle."""

@@ -22,6 +22,21 @@ its 1080p cases; the slack ladder was 0, 1/16, 1/8, 1/4, 1/2, 1, 2, 4 ulp, the c
   resize u8c3 / u8c1 / u8c4| 0                  | 0        | 0.818 LSB                   | 1                    | 1.0
   resize u16c3             | 1/2 ulp (<= 640 and| 1 ulp    | 0.504 LSB                   | 0.5195               | 1.0
                            |  1080p alike)      |          |                             |                      |
+  warp u8c2 (NV12 chroma) | 0                  | 0        | 0.500 LSB                   | 1                    | homography >= 0.993,
+  warp u16c2 (P010 chroma) | 1/2 ulp (1080p     | 2 ulp    | 0.489 LSB                   | 0.5195 (the same ten |  1080p 0.997, odd shifts
+                           |  noise, 32 x 32    |          |                             |  roundings, counted  |  0.996, 1/32 shift 0.989;
+                           |  mesh; 1/4 ulp on  |          |                             |  at VALUE_ALLOW)     |  mesh 0.859
+                           |  16 x 16; 0 <= 640)|          |                             |                      |
+  resize u8c2              | 0                  | 0        | 0.813 LSB                   | 1                    | 1.0
+  resize u16c2             | 1/2 ulp (<= 640 and| 1 ulp    | 0.505 LSB (0.519 at 1/2 ulp)| 0.5195               | 1.0
+                           |  1080p alike)      |          |                             |                      |
+  The chroma rows were measured on WARP_CASES_420 plus both 1080p homographies, and on RESIZE_CASES_420 plus the 1080p and same-size
+  cases, against tests/nv12_model.py, p010_model.py, nv12_crop_model.py and p010_crop_model.py alone; ulps are counted at the chroma
+  plane's extent (the resize positions are absolute in that plane).  Distances at slack 0 on 1080p noise: warp 0.81 LSB (16 x 16 mesh) and
+  1.62 LSB (32 x 32) from the box, resize 2.97 LSB.  The warp constant is u16c3's by derivation, not by the ladder (which would give 1 ulp):
+  the chroma maps are the luma maps halved exactly and the chroma extent's ulp is half the luma extent's, so the same half ulp of the map
+  and half ulp of the vertices arrive, counted in the same unit.  Chroma mean signed difference (P010, smooth, two frames shifted by
+  (6 14/32, -2 22/32), 130,140 values): +0.00019 LSB; truncation moves it to -0.50.
   2 ulp at 1080p is 2^-12 px, far below the caps (1/64 px warp, 2^-10 px resize) beyond which a bucket taken by floor would pass.
   The uint16 allowance is derived, not measured: 0.5 for the final rounding and ten float32 roundings of values below 65,536 (half an ulp,
   2^-9, each: seven in the remap's four products and three sums, nine in the resize's two passes and its 1 - f) -- the measurement agrees.
@@ -48,6 +63,14 @@ half to even): both lie within 0.5 LSB of the float64 value, so the envelope pas
 float64 sampler can say which of the two OpenCV takes -- that case is left out of the mean check and the branch stays unchecked here.
 Nor can it see the last bit of the 8-bit fixed-point paths (1 LSB allowance), the painter order on cell seams (mesh cases judge cell
 interiors only), or who paints the one-pixel ring outside the frame's edge.
+For 4:2:0 chroma it cannot see who owns the ring either, and that ring is wider: a chroma sample whose siting luma pixel has its source
+outside the frame may be the border outright or a blend, anywhere within one chroma pixel (two luma pixels) of the plane's edge
+(`chroma_ring`); under a shift by (5 7/32, -3 11/32) every chroma coordinate is a tie of the 1/32 bucket, so which way cvRound breaks ties
+is invisible to the envelope there and the chroma mean is taken on a sixteenths shift instead.  In the crop-resize the x axis zeroes its
+fraction where it clamps and the y axis keeps it on two rows clipped to one: both are the value at the clamped position, so which of the
+two a kernel does cannot be told, nor should it.  A clamp range one sample too wide shows only where the extra sample differs (noise, or
+a steep frame) and only in the one or two edge samples that clamp (on 8-bit smooth frames by 0.8 LSB: noise is the case that counts).
+Every wrong 4:2:0 model of tests/test_second_opinion_models.py is rejected; none had to be listed here.
 """
 import collections
 import math
@@ -60,6 +83,13 @@ F_ = torch.nn.functional
 FORMATS = ('u8c3', 'u16c3', 'u8c1', 'u8c4')
 CHANNELS = {'u8c3': 3, 'u16c3': 3, 'u8c1': 1, 'u8c4': 4}
 TOP = {'u8c3': 255, 'u16c3': 65535, 'u8c1': 255, 'u8c4': 255}
+# 4:2:0: a luma plane and an interleaved (U, V) plane of half the size in each axis, each judged as a format of its own.  NV12 luma is the
+# u8c1 launch; P010 luma is channel 0 of u16c3 bit for bit, so it is a one-channel plane with u16c3's constants (the arithmetic is per channel)
+FORMATS_420 = ('nv12', 'p010')
+LUMA_OF = {'nv12': 'u8c1', 'p010': 'u16c1'}
+CHROMA_OF = {'nv12': 'u8c2', 'p010': 'u16c2'}
+CHANNELS.update({'u16c1': 1, 'u8c2': 2, 'u16c2': 2})
+TOP.update({'u16c1': 65535, 'u8c2': 255, 'u16c2': 65535})
 
 # ---- the constants (how each was fixed: the table above) ------------------------------------------------------------------------------
 
@@ -71,7 +101,14 @@ WARP_EPS_CAP = 1.0 / 64              # px: a slack beyond these could no longer 
 RESIZE_EPS_CAP = 2.0 ** -10
 HALF_ULP_U16 = 2.0 ** -9             # half a float32 ulp of a value in [32768, 65536)
 VALUE_ALLOW = {'u8c3': 1.0, 'u16c3': 0.5 + 10 * HALF_ULP_U16, 'u8c1': 1.0, 'u8c4': 1.0}             # LSB of the format
-MEAN_SIGNED_VALUES = 100000          # the mean signed difference is judged on at least this many values
+# the chroma planes (the table's 4:2:0 rows; ulps are counted at the chroma plane's extent) and P010 luma (u16c3's, per channel).  The
+# u16c2 allowance is u16c3's because the count is: the warp is cv16_model.remap_bilinear_u16c3 itself (seven roundings), and
+# p010_crop_model.blend rounds three times per horizontal tap pair (two products, one sum), three times in the vertical pass, and once in
+# each 1 - f that reaches a value -- ten at the most
+WARP_EPS_ULPS.update({'u16c1': WARP_EPS_ULPS['u16c3'], 'u8c2': 0.0, 'u16c2': 2.0})
+RESIZE_EPS_ULPS.update({'u16c1': RESIZE_EPS_ULPS['u16c3'], 'u8c2': 0.0, 'u16c2': 1.0})
+VALUE_ALLOW.update({'u16c1': VALUE_ALLOW['u16c3'], 'u8c2': 1.0, 'u16c2': 0.5 + 10 * HALF_ULP_U16})
+MEAN_SIGNED_VALUES = 100000         # the mean signed difference is judged on at least this many values
 MEAN_SIGNED_BOUND = 3 * math.sqrt(1.0 / 12) / math.sqrt(MEAN_SIGNED_VALUES)                         # 3 standard errors: 0.00274 LSB
 SHARE_GLOBAL = 0.97                  # global-homography and resize cases judge at least this share of their pixels
 SHARE_MESH = 0.60                    # mesh-motion cases (cell interiors only)
@@ -143,6 +180,35 @@ SAME_SIZE_CASES_1080P = [(1, 1080, 1920, (17, 9, 1899, 1071))]
 # a non-black border per format; u16c3: the default, which must come out as 255, not 65,535
 BORDERS = {'u8c3': (11, 122, 233), 'u16c3': (0, 0, 255), 'u8c1': (77,), 'u8c4': (11, 122, 233, 44)}
 
+# ---- the 4:2:0 case table -----------------------------------------------------------------------------------------------------------------
+
+BORDERS_YUV = {'nv12': (19, 203, 77), 'p010': (4921, 52107, 19733)}      # (Y, U, V), all three different: a border from the wrong component shows
+# a shift by multiples of 1/16 luma px: halved it is a multiple of 1/32 chroma px, so chroma has no bucket error either (THIRTYSECONDS_SHIFT
+# halves to odd multiples of 1/64 chroma px, every one a rounding tie of the bucket: the true P010 chroma mean comes out at -0.25 LSB there)
+SIXTEENTHS_SHIFT = (6 + 14 / 32, -2 - 22 / 32)
+# the warp cases (every size is even already) and the chroma mean-signed case: two frames, 65,340 chroma values each
+WARP_CASES_420 = WARP_CASES + [WarpCase('sixteenths', 2, 270, 484, 5, 7, 8)]
+
+
+def _even(v):
+    return v + v % 2
+
+
+def _resize_cases_420():
+    """RESIZE_CASES with the frame and the output made even (odd numbers go up by one; the rectangle stays) and at most two frames; a
+    100 x 72 frame with both parities of every edge of the rectangle; one-pixel crops on an odd column and row and on the frame's last pixel."""
+    cases = [(min(n, 2), _even(H), _even(W), rect, (_even(ow), _even(oh))) for n, H, W, rect, (ow, oh) in RESIZE_CASES]
+    for k in range(16):
+        rect = (10 + (k & 1), 6 + (k >> 1 & 1), 80 + (k >> 2 & 1), 60 + (k >> 3 & 1))
+        cases.append((1, 72, 100, rect, ((46, 90)[k & 1], (34, 80)[k >> 1 & 1])))      # down and up, non-integer ratios
+    cases += [(2, 72, 100, (37, 21, 37, 21), (18, 10)), (2, 72, 100, (99, 71, 99, 71), (6, 4)), (2, 72, 100, (98, 70, 99, 71), (10, 8)),
+              (2, 72, 100, (0, 0, 99, 71), (100, 72))]                    # ..., the last 2 x 2 pixels, the whole frame at its own size
+    return cases
+
+
+RESIZE_CASES_420 = _resize_cases_420()
+PARITY_CASE_420 = next(c for c in RESIZE_CASES_420 if c[1:3] == (72, 100) and c[3][0] % 2 and c[3][1] % 2)   # odd left, odd top
+
 
 # ---- frames ---------------------------------------------------------------------------------------------------------------------------
 
@@ -166,9 +232,9 @@ def noise_planes(fmt, n, H, W, seed=0, device='cpu'):
 
 
 def to_numpy(fmt, planes):
-    """Planes -> the NumPy stack a model takes: (n, H, W, 3 or 4) uint8 / uint16, or (n, H, W) uint8."""
-    a = planes.cpu().numpy().astype(np.uint16 if fmt == 'u16c3' else np.uint8)
-    return a[..., 0] if fmt == 'u8c1' else a
+    """Planes -> the NumPy stack a model takes: (n, H, W, 2, 3 or 4) uint8 / uint16, or (n, H, W) for one channel."""
+    a = planes.cpu().numpy().astype(np.uint16 if TOP[fmt] > 255 else np.uint8)
+    return a[..., 0] if CHANNELS[fmt] == 1 else a
 
 
 def to_planes(a, device='cpu'):
@@ -354,15 +420,18 @@ def _box_points(p, half):
     return p - half, torch.where((k - p).abs() < half, k, p), p + half
 
 
-def envelope(planes, u, v, half, border=None, clamp=False):
+def envelope(planes, u, v, half, border=None, clamp=False, lim=None):
     """(lo, hi): the range the bilinear sample takes over the box [u +- half] x [v +- half].  The sample is bilinear inside each source
     cell, so on every piece of the box its extremes sit at the piece's corners: the box's own corners and, where an integer line crosses
-    it, the points on that line -- 3 x 3 samples, exact for half < 0.5, nothing missed between them."""
+    it, the points on that line -- 3 x 3 samples, exact for half < 0.5, nothing missed between them.  clamp: the box is clamped to the
+    plane, or to `lim` = ((x0, x1), (y0, y1)) inside it."""
+    if clamp and lim is None:
+        lim = ((0, planes.shape[2] - 1), (0, planes.shape[1] - 1))
     lo = hi = None
     for pu in _box_points(u, half):
         for pv in _box_points(v, half):
             if clamp:
-                pu, pv = pu.clamp(0, planes.shape[2] - 1), pv.clamp(0, planes.shape[1] - 1)
+                pu, pv = pu.clamp(*lim[0]), pv.clamp(*lim[1])
             s = sample(planes, pu, pv, border, clamp)
             lo = s if lo is None else torch.minimum(lo, s)
             hi = s if hi is None else torch.maximum(hi, s)
@@ -395,10 +464,10 @@ def judge_warp(fmt, got, planes, u, v, border, judged=None, eps=None, allow=None
     return judge(got, sample(planes, u, v, b), lo, hi, VALUE_ALLOW[fmt] if allow is None else allow, judged)
 
 
-def far_mismatches(fmt, got, u, v, border):
+def far_mismatches(fmt, got, u, v, border, far=None):
     """(values well outside the frame that are not the border value exactly, number of such pixels)."""
     H, W = got.shape[1:3]
-    far = far_outside(u, v, H, W)
+    far = far_outside(u, v, H, W) if far is None else far
     return int((got[far] != border_planes(fmt, border, got.device)).sum()), int(far.sum())
 
 
@@ -437,7 +506,8 @@ def legacy_assert_within_envelope(got, frames, u, v, allow=1.0, skip=None):
 
 # ---- cases -> what to judge -----------------------------------------------------------------------------------------------------------
 
-WarpSetup = collections.namedtuple('WarpSetup', 'label unstab stab u v judged exact min_share')
+# far: which samples must be the border exactly (None: `far_outside` of (u, v))
+WarpSetup = collections.namedtuple('WarpSetup', 'label unstab stab u v judged exact min_share far', defaults=(None,))
 
 
 def warp_setups(case, device='cpu'):
@@ -449,11 +519,11 @@ def warp_setups(case, device='cpu'):
         for dx, dy in shifts:                                           # content moves by (+dx, +dy): the map is (x - dx, y - dy)
             unstab, stab = shift_motion(n, R, C, dx, dy)
             yield WarpSetup(f'{case.kind}{(dx, dy)}', unstab, stab, xs - dx, ys - dy, None, True, 1.0)
-    elif case.kind == 'thirtyseconds':
-        dx, dy = THIRTYSECONDS_SHIFT
+    elif case.kind in ('thirtyseconds', 'sixteenths'):
+        dx, dy = THIRTYSECONDS_SHIFT if case.kind == 'thirtyseconds' else SIXTEENTHS_SHIFT
         unstab, stab = shift_motion(n, R, C, dx, dy)
         u, v = xs - dx, ys - dy
-        yield WarpSetup('thirtyseconds', unstab, stab, u, v, ~border_ring(u, v, H, W), False, SHARE_GLOBAL)
+        yield WarpSetup(case.kind, unstab, stab, u, v, ~border_ring(u, v, H, W), False, SHARE_GLOBAL)
     elif case.kind == 'homography':
         unstab, stab, G = homography_motion(n, H, W, R, C, case.seed)
         u, v = source_map(inverse(G, device), n, H, W, device)
@@ -476,7 +546,7 @@ def warp_findings(fmt, got, planes, setup, border, eps=None, allow=None):
     else:
         vd = judge_warp(fmt, got, planes, setup.u, setup.v, border, setup.judged, eps, allow)
         worst, share, mean_signed, values = vd.worst, vd.share, vd.mean_signed, vd.values
-    far_bad, far_pixels = far_mismatches(fmt, got, setup.u, setup.v, border)
+    far_bad, far_pixels = far_mismatches(fmt, got, setup.u, setup.v, border, setup.far)
     return dict(label=setup.label, worst=worst, share=share, mean_signed=mean_signed, values=values, far_bad=far_bad, far_pixels=far_pixels)
 
 
@@ -493,7 +563,7 @@ def warp_violations(fmt, f, setup, smooth):
         out.append(f"{f['label']}: {f['far_bad']} values far outside the frame are not the border value")
     if setup.label.startswith('far') and not f['far_pixels']:
         out.append(f"{f['label']}: no pixel far outside the frame")
-    if fmt == 'u16c3' and smooth and setup.label == 'thirtyseconds':
+    if smooth and TOP[fmt] == 65535 and setup.label == ('sixteenths' if CHANNELS[fmt] == 2 else 'thirtyseconds'):
         if f['values'] < MEAN_SIGNED_VALUES:
             out.append(f"{f['label']}: {f['values']} values, too few for the mean signed difference")
         if abs(f['mean_signed']) > MEAN_SIGNED_BOUND:
@@ -525,3 +595,153 @@ def resize_violations(fmt, f, rect, out_w, out_h, smooth):
     if mean_signed_applies(fmt, rect, out_w, out_h, f['values'], smooth) and abs(f['mean_signed']) > MEAN_SIGNED_BOUND:
         out.append(f"mean signed difference {f['mean_signed']:+.5f} LSB, bound {MEAN_SIGNED_BOUND:.5f}")
     return out
+
+
+# ---- 4:2:0: the chroma planes ---------------------------------------------------------------------------------------------------------
+# Nothing below takes a position, a clamp range or a parity rule from a model: a chroma sample (cx, cy) is said to sit on luma pixel
+# (2 cx, 2 cy) -- the definition under test -- and everything else follows from the float64 luma positions above, halved.
+
+def planes_420(fmt, kind, n, H, W, seed=0, device='cpu'):
+    """(y (n, H, W, 1), uv (n, H/2, W/2, 2)) float64 planes, kind 'smooth' or 'noise'; the chroma planes have their own phases and draws."""
+    make = {'smooth': smooth_planes, 'noise': noise_planes}[kind]
+    return make(LUMA_OF[fmt], n, H, W, seed, device), make(CHROMA_OF[fmt], n, H // 2, W // 2, seed + 17, device)
+
+
+def chroma_ring(u, v, H, W):
+    """Chroma samples a sampler of the chroma plane cannot judge, from the luma source (u, v) of their siting pixel: that source lies
+    outside [0, W-1] x [0, H-1] -- no cell owns the pixel for certain, so the sample may be the border outright -- while the halved
+    position still lies within a chroma pixel of the plane, (-1, Wc) x (-1, Hc), where the sampler blends the plane with the border.  The
+    blend zone is one CHROMA pixel wide, two luma pixels: the luma ring is not this ring."""
+    outside = (u < 0) | (u > W - 1) | (v < 0) | (v > H - 1)
+    return outside & (u / 2 > -1) & (u / 2 < W // 2) & (v / 2 > -1) & (v / 2 < H // 2)
+
+
+def chroma_far_outside(uc, vc, Hc, Wc):
+    """Chroma samples whose source lies well outside the chroma plane: the (U, V) border exactly."""
+    return (uc < -1.5) | (uc > Wc + 0.5) | (vc < -1.5) | (vc > Hc + 0.5)
+
+
+def chroma_setup(setup, H, W):
+    """The chroma plane's setup from the luma frame's: the source of the even luma pixels, halved; judged where luma is judged, less the
+    chroma ring.  Exact only where every halved position is an integer (identity, shifts even in both axes): an odd shift moves chroma by
+    half a chroma pixel, which is judged by the envelope like any other motion."""
+    ul, vl = setup.u[:, ::2, ::2], setup.v[:, ::2, ::2]
+    uc, vc = ul / 2, vl / 2
+    exact = bool(setup.exact and ((uc == uc.round()) & (vc == vc.round())).all())
+    judged = ~chroma_ring(ul, vl, H, W) if setup.judged is None else setup.judged[:, ::2, ::2] & ~chroma_ring(ul, vl, H, W)
+    return WarpSetup(setup.label, setup.unstab, setup.stab, uc, vc, None if exact else judged, exact,
+                     1.0 if exact else min(setup.min_share, SHARE_GLOBAL), chroma_far_outside(uc, vc, H // 2, W // 2))
+
+
+def chroma_axis(lo, hi, out_len, device='cpu'):
+    """One axis of the chroma crop-resize, float64: the position in the chroma plane of each of the out_len / 2 output chroma samples and
+    the clamp range (c0, c1).  Output chroma sample c sits on output luma pixel 2 c, whose source in the frame is lo + (2 c + 0.5) cw / out
+    - 0.5; halved, that is its place among the chroma samples.  c0 .. c1 are the chroma samples whose own luma pixel (even) lies in
+    lo .. hi; a one-pixel crop on an odd pixel has none and takes the sample that covers it."""
+    cw = hi - lo + 1
+    c0, c1 = -(-lo // 2), hi // 2
+    if c0 > c1:
+        c0 = c1 = lo // 2
+    c = torch.arange(out_len // 2, dtype=torch.float64, device=device)
+    return ((lo + ((2 * c + 0.5) * (cw / out_len) - 0.5)) / 2).clamp(c0, c1), (c0, c1)
+
+
+def judge_resize_chroma(fmt, got, uv, rect, out_w, out_h, eps=None, allow=None):
+    """The chroma crop-resize's verdict: the WHOLE chroma plane sampled at the clamped absolute positions; the envelope is resize_eps (in
+    ulps of the chroma plane's extent: the positions are absolute) around them, clamped to the same range.  A clamped position is all
+    there is to either clamp: two taps clipped to one row give that row whatever the fraction."""
+    left, top, right, bottom = rect
+    n, Hc, Wc = uv.shape[:3]
+    px, limx = chroma_axis(left, right, out_w, uv.device)
+    py, limy = chroma_axis(top, bottom, out_h, uv.device)
+    u = px[None, None, :].expand(n, out_h // 2, out_w // 2)
+    v = py[None, :, None].expand(n, out_h // 2, out_w // 2)
+    centre = sample(uv, u, v, None, clamp=True)
+    lo, hi = envelope(uv, u, v, resize_eps(fmt, Hc, Wc, eps), None, clamp=True, lim=(limx, limy))
+    lo, hi = torch.minimum(lo, centre), torch.maximum(hi, centre)
+    return judge(got, centre, lo, hi, VALUE_ALLOW[fmt] if allow is None else allow)
+
+
+def resize_chroma_findings(fmt, got, uv, rect, out_w, out_h, eps=None, allow=None):
+    vd = judge_resize_chroma(fmt, got, uv, rect, out_w, out_h, eps, allow)
+    return dict(worst=vd.worst, share=vd.share, mean_signed=vd.mean_signed, values=vd.values, agree=0.0)
+
+
+def warp_findings_420(fmt, got_y, got_uv, y, uv, setup, border_yuv, smooth=False):
+    """A warped pair judged whole: (luma findings, chroma findings, violations of either)."""
+    H, W = y.shape[1:3]
+    cs = chroma_setup(setup, H, W)
+    fy = warp_findings(LUMA_OF[fmt], got_y, y, setup, border_yuv[:1])
+    fc = warp_findings(CHROMA_OF[fmt], got_uv, uv, cs, border_yuv[1:])
+    return fy, fc, ['luma ' + s for s in warp_violations(LUMA_OF[fmt], fy, setup, smooth)] + \
+        ['chroma ' + s for s in warp_violations(CHROMA_OF[fmt], fc, cs, smooth)]
+
+
+def resize_findings_420(fmt, got_y, got_uv, y, uv, rect, out_w, out_h):
+    fy = resize_findings(LUMA_OF[fmt], got_y, y, rect, out_w, out_h)
+    fc = resize_chroma_findings(CHROMA_OF[fmt], got_uv, uv, rect, out_w, out_h)
+    return fy, fc, ['luma ' + s for s in resize_violations(LUMA_OF[fmt], fy, rect, out_w, out_h, False)] + \
+        ['chroma ' + s for s in resize_violations(CHROMA_OF[fmt], fc, rect, out_w, out_h, False)]
+
+
+# ---- 4:2:0: registration of chroma on luma, without a model of siting -----------------------------------------------------------------
+# A linear ramp with integer slopes, y = a + sx x + sy y, and uv[cy, cx, k] = ramp(2 cx, 2 cy) + offset[k].  Bilinear sampling of a linear
+# function returns the function, so whatever the motion out_uv[cy, cx, k] - offset[k] and out_y[2 cy, 2 cx] are the same number ramp(u, v),
+# each read through its own coordinate error and its own rounding.  Chroma sited anywhere else is off by its distance times the slope.
+
+RAMP = {'nv12': dict(a=5, sx=3, sy=1, offsets=(0, 7)), 'p010': dict(a=200, sx=100, sy=60, offsets=(0, 500))}
+# the warp case of each format: 8 bits need a frame narrow enough for a slope of 3 (5 + 3 * 63 + 47 + 7 = 248): a luma pixel is 4 LSB
+REGISTRATION_WARP = {'nv12': WarpCase('homography', 2, 48, 64, 4, 6, 2), 'p010': WarpCase('homography', 2, 270, 484, 5, 7, 2)}
+# (n, H, W, rect, size): odd left and top, a non-integer ratio, inside the ramp's range
+REGISTRATION_RESIZE = {'nv12': (1, 48, 64, (5, 3, 58, 44), (40, 30)), 'p010': (1, 270, 484, (41, 31, 443, 238), (300, 170))}
+
+
+def ramp_420(fmt, n, H, W, device='cpu'):
+    r = RAMP[fmt]
+    xs, ys = pixels(n, H, W, device)
+    y = (r['a'] + r['sx'] * xs + r['sy'] * ys)[..., None]
+    uv = torch.cat([y[:, ::2, ::2] + o for o in r['offsets']], dim=-1)
+    assert float(uv.max()) <= TOP[LUMA_OF[fmt]]
+    return y, uv
+
+
+def _registration_gap(fmt, got_y, got_uv, inside):
+    off = torch.tensor(RAMP[fmt]['offsets'], dtype=torch.float64, device=got_y.device)
+    gap = ((got_uv - off) - got_y[:, ::2, ::2]).abs() * inside[..., None]
+    return float(gap.max()), int(inside.sum())
+
+
+def registration_warp(fmt, got_y, got_uv, setup):
+    """(worst |chroma - luma at the even pixel| in LSB, samples compared, bound) of a warped ramp.  Compared where every tap of both
+    lies inside the frame (the luma source within [1, W - 3] x [1, H - 3]): against the border nothing is linear.
+    Bound: the luma bucket moves the source by up to 1/64 luma px per axis, the chroma bucket by 1/64 chroma px = 1/32 luma px; each side
+    then rounds once (0.5 LSB), in float32 for 16 bits (VALUE_ALLOW), with 2^15 fixed-point weights for 8 bits (four taps, each weight
+    within 2^-16 of its value, on taps that differ by at most sx + sy: below 0.001 LSB)."""
+    H, W = got_y.shape[1:3]
+    u, v = setup.u[:, ::2, ::2], setup.v[:, ::2, ::2]
+    inside = (u >= 1) & (u <= W - 3) & (v >= 1) & (v <= H - 3)
+    if setup.judged is not None:
+        inside = inside & setup.judged[:, ::2, ::2]
+    r = RAMP[fmt]
+    value = VALUE_ALLOW[CHROMA_OF[fmt]] if fmt == 'p010' else 0.5 + 0.001
+    eps = warp_eps(LUMA_OF[fmt], H, W) + 2 * warp_eps(CHROMA_OF[fmt], H // 2, W // 2)
+    return (*_registration_gap(fmt, got_y, got_uv, inside), (r['sx'] + r['sy']) * (1 / 64 + 1 / 32 + eps) + 2 * value)
+
+
+def registration_resize(fmt, got_y, got_uv, H, W, rect, out_w, out_h):
+    """The same for a crop-resize, on the samples that neither the luma rule (the position clamped to the crop) nor the chroma rule (clamped
+    to c0 .. c1) clamps, decided here from the float64 positions.  Bound: no bucket, the float32 position alone (resize_eps, at most
+    RESIZE_EPS_CAP) times the slope, and each side's value error: 16 bits VALUE_ALLOW; 8 bits between -(0.5 + 0.25 + 0.25 + 1/32) and
+    +0.5 of the float64 value (the final rounding; two products truncated to quarter LSBs; the >> 4 of both rows and the 11-bit weights
+    on taps 3 LSB apart) -- the same one-sided range on both sides, so their difference stays below its width."""
+    left, top, right, bottom = rect
+    r = RAMP[fmt]
+    keep = []
+    for lo, hi, out_len in ((left, right, out_w), (top, bottom, out_h)):
+        c = torch.arange(out_len // 2, dtype=torch.float64, device=got_y.device)
+        p = lo + (2 * c + 0.5) * ((hi - lo + 1) / out_len) - 0.5                     # luma source of output luma pixel 2 c, absolute
+        pc, (c0, c1) = chroma_axis(lo, hi, out_len, got_y.device)
+        keep.append((p >= lo) & (p <= hi) & (p / 2 >= c0) & (p / 2 <= c1) & (pc == p / 2))
+    inside = (keep[1][:, None] & keep[0][None, :])[None].expand(got_uv.shape[:3])
+    value = 2 * VALUE_ALLOW[CHROMA_OF[fmt]] if fmt == 'p010' else 1.0 + 0.5 + 1 / 32
+    return (*_registration_gap(fmt, got_y, got_uv, inside), (r['sx'] + r['sy']) * 3 * RESIZE_EPS_CAP + value)

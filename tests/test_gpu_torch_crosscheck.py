@@ -17,7 +17,8 @@ It pins nothing (parity stays "partial": tests/test_cv2_crosscheck.py is the doo
 centres, map direction, mesh-motion sign or border handling cannot pass it.
 
 The helpers live in tests/second_opinion.py.  The tests of the second half judge all four formats and crop_resize(size=...) with that
-module's judge and constants, which were fixed on the CPU against the models (tests/test_second_opinion_models.py); none is defined here."""
+module's judge and constants, which were fixed on the CPU against the models (tests/test_second_opinion_models.py); none is defined here.
+The last part does the same for the NV12 and P010 calls, chroma included, and registers chroma on luma with a ramp."""
 import numpy as np
 import pytest
 
@@ -298,3 +299,134 @@ def test_crop_resize_same_size_formats_vs_interpolate(dev, fmt):
         for kind in ('smooth', 'noise'):
             f, violations = _kernel_resize_findings(dev, fmt, (n, H, W, rect, (W, H)), kind, same_size=True, with_model=H < 1080)
             assert not violations, (f, violations)
+
+
+# ---- NV12 and P010: the pair judged whole, chroma by the chroma rows of tests/second_opinion.py ----------------------------------------------
+# Luma as u8c1 / as a one-channel 16-bit plane with u16c3's constants; chroma as the two-channel plane at the even luma pixels' positions
+# halved (warp) or at the absolute float64 positions (crop-resize).  Proven on the CPU models first, like everything above.
+
+WARP_420 = so.WARP_CASES_420 + [so.WARP_CASES_1080P[0]]
+RESIZE_420 = so.RESIZE_CASES_420 + so.RESIZE_CASES_1080P
+
+
+def _pair_to_dev(fmt, y, uv, dev):
+    return _to_dev(so.LUMA_OF[fmt], y, dev), _to_dev(so.CHROMA_OF[fmt], uv, dev)
+
+
+def _kernel_warp_420(dev, fmt, y, uv, case, setup, border):
+    """(out_y, out_uv) of ops.warp_nv12 / ops.warp_p010 as device tensors."""
+    from meshflow_amd import ops
+    d_y, d_uv = _pair_to_dev(fmt, y, uv, dev)
+    table = ops.cell_table(torch.from_numpy(np.ascontiguousarray(setup.unstab)).to(dev), torch.from_numpy(np.ascontiguousarray(setup.stab)).to(dev),
+                           case.W, case.H, case.R, case.C)
+    out_y, out_uv = {'nv12': ops.warp_nv12, 'p010': ops.warp_p010}[fmt](d_y, d_uv, table, border)
+    torch.cuda.synchronize()
+    table.check()
+    return out_y, out_uv
+
+
+def _same_bits(t, a):
+    got = t.contiguous().view(torch.uint8).cpu().numpy().view(a.dtype).reshape(a.shape)
+    return np.array_equal(got, a), (int((got != a).sum()), np.argwhere(got != a)[:5].tolist())
+
+
+def _warp_420_findings(dev, fmt, case, kind, with_model, planes=None):
+    """[(luma findings, chroma findings, violations)] per setup; with_model: the model's planes equal the kernel's bit for bit and go
+    through the judge to the same numbers."""
+    import test_second_opinion_models as models
+    border = so.BORDERS_YUV[fmt]
+    y, uv = planes or so.planes_420(fmt, kind, case.n, case.H, case.W, case.seed, dev)
+    found = []
+    for setup in so.warp_setups(case, dev):
+        out_y, out_uv = _kernel_warp_420(dev, fmt, y, uv, case, setup, border)
+        f = so.warp_findings_420(fmt, _to_planes(out_y, dev), _to_planes(out_uv, dev), y, uv, setup, border, kind == 'smooth')
+        print(fmt, case.kind, f'{case.H}x{case.W}', kind, 'luma', {k: f[0][k] for k in ('label', 'worst', 'share')}, 'chroma',
+              {k: f[1][k] for k in ('worst', 'share', 'mean_signed', 'far_bad', 'far_pixels')})
+        found.append(f)
+        if with_model:
+            want_y, want_uv = models.model_warp_420(fmt, so.to_numpy(so.LUMA_OF[fmt], y), so.to_numpy(so.CHROMA_OF[fmt], uv), case, setup, border)
+            same_y, same_uv = _same_bits(out_y, want_y), _same_bits(out_uv, want_uv)
+            assert same_y[0] and same_uv[0], (setup.label, 'luma', same_y[1], 'chroma', same_uv[1])
+            assert so.warp_findings_420(fmt, so.to_planes(want_y, dev), so.to_planes(want_uv, dev), y, uv, setup, border, kind == 'smooth') == f
+    return found
+
+
+@pytest.mark.parametrize('kind', ['smooth', 'noise'])
+@pytest.mark.parametrize('fmt', so.FORMATS_420)
+@pytest.mark.parametrize('case', WARP_420, ids=lambda c: f'{c.kind}-{c.H}x{c.W}-{c.R}')
+def test_warp_420_vs_grid_sample(dev, case, fmt, kind):
+    """ops.warp_nv12 / ops.warp_p010 with a (Y, U, V) border whose components all differ: luma and chroma exact under identity and even
+    shifts, inside their envelopes otherwise, exactly the border far outside, the P010 chroma mean within its bound; up to 360 x 640 the
+    kernel's planes are the model's bit for bit."""
+    found = _warp_420_findings(dev, fmt, case, kind, with_model=case.H < 1080)
+    assert not [v for _, _, vs in found for v in vs], found
+    if case.kind == 'far':
+        assert found[0][1]['far_pixels'] > 250
+
+
+@pytest.mark.parametrize('fmt', so.FORMATS_420)
+def test_warp_420_is_the_model_at_1080p(dev, fmt):
+    """One 1080p noise frame under a homography: both planes bit for bit the model's."""
+    case = so.WARP_CASES_1080P[0]
+    found = _warp_420_findings(dev, fmt, case, 'noise', with_model=True)
+    assert not [v for _, _, vs in found for v in vs], found
+
+
+def _resize_420_findings(dev, fmt, case, kind, same_size=False, planes=None):
+    """(luma findings, chroma findings, violations), the kernel's planes bit for bit the model's and the model judged to the same numbers."""
+    from meshflow_amd import ops
+    import test_second_opinion_models as models
+    n, H, W, rect, (ow, oh) = case
+    y, uv = planes or so.planes_420(fmt, kind, n, H, W, 9, dev)
+    d_y, d_uv = _pair_to_dev(fmt, y, uv, dev)
+    call = {'nv12': ops.crop_resize_nv12, 'p010': ops.crop_resize_p010}[fmt]
+    out_y, out_uv = call(d_y, d_uv, rect) if same_size else call(d_y, d_uv, rect, size=(ow, oh))
+    torch.cuda.synchronize()
+    assert tuple(out_y.shape) == (n, oh, ow) and tuple(out_uv.shape) == (n, oh // 2, ow // 2, 2)
+    f = so.resize_findings_420(fmt, _to_planes(out_y, dev), _to_planes(out_uv, dev), y, uv, rect, ow, oh)
+    print(fmt, f'{H}x{W}', rect, (ow, oh), kind, 'luma', f[0]['worst'], 'chroma', f[1]['worst'])
+    want_y, want_uv = models.model_resize_420(fmt, so.to_numpy(so.LUMA_OF[fmt], y), so.to_numpy(so.CHROMA_OF[fmt], uv), rect, (ow, oh))
+    same_y, same_uv = _same_bits(out_y, want_y), _same_bits(out_uv, want_uv)
+    assert same_y[0] and same_uv[0], ('luma', same_y[1], 'chroma', same_uv[1])
+    assert so.resize_findings_420(fmt, so.to_planes(want_y, dev), so.to_planes(want_uv, dev), y, uv, rect, ow, oh) == f
+    return (out_y, out_uv), f
+
+
+@pytest.mark.parametrize('kind', ['smooth', 'noise'])
+@pytest.mark.parametrize('fmt', so.FORMATS_420)
+@pytest.mark.parametrize('case', range(len(RESIZE_420)))
+def test_crop_resize_420_vs_float64_positions(dev, case, fmt, kind):
+    """ops.crop_resize_nv12 / ops.crop_resize_p010 over the 4:2:0 table (every parity of every edge, one-pixel crops) and the 1080p
+    downscales on both sides of every staged / direct cut-over: luma against `interpolate` of the crop, chroma against the whole chroma
+    plane sampled at the absolute float64 positions; bit for bit the model at every size."""
+    _, f = _resize_420_findings(dev, fmt, RESIZE_420[case], kind)
+    assert not f[2], f
+
+
+@pytest.mark.parametrize('fmt', so.FORMATS_420)
+def test_crop_resize_420_same_size_vs_float64_positions(dev, fmt):
+    """The call without `size`, 1080p included."""
+    for n, H, W, rect in so.SAME_SIZE_CASES + so.SAME_SIZE_CASES_1080P:
+        _, f = _resize_420_findings(dev, fmt, (n, H, W, rect, (W, H)), 'noise', same_size=True)
+        assert not f[2], f
+
+
+@pytest.mark.parametrize('fmt', so.FORMATS_420)
+def test_ramp_registration_of_the_kernels(dev, fmt):
+    """Chroma registered on luma without a model of siting: on a linear ramp out_uv[cy, cx] is out_y[2 cy, 2 cx] (less the channel's
+    offset) within the bound derived in second_opinion.registration_warp / registration_resize, under a homography and under a crop with
+    an odd left and top.  Chroma sited at the odd luma sample is off by sx + sy LSB, several times the bound."""
+    case = so.REGISTRATION_WARP[fmt]
+    y, uv = so.ramp_420(fmt, case.n, case.H, case.W, dev)
+    setup = next(so.warp_setups(case, dev))
+    out_y, out_uv = _kernel_warp_420(dev, fmt, y, uv, case, setup, so.BORDERS_YUV[fmt])
+    worst, compared, bound = so.registration_warp(fmt, _to_planes(out_y, dev), _to_planes(out_uv, dev), setup)
+    print(fmt, 'warp', worst, compared, bound)
+    assert worst <= bound and compared > 0.8 * case.n * case.H * case.W / 4
+    assert so.RAMP[fmt]['sx'] + so.RAMP[fmt]['sy'] > 3 * bound
+    n, H, W, rect, (ow, oh) = so.REGISTRATION_RESIZE[fmt]
+    planes = so.ramp_420(fmt, n, H, W, dev)
+    (out_y, out_uv), _ = _resize_420_findings(dev, fmt, so.REGISTRATION_RESIZE[fmt], 'ramp', planes=planes)
+    worst, compared, bound = so.registration_resize(fmt, _to_planes(out_y, dev), _to_planes(out_uv, dev), H, W, rect, ow, oh)
+    print(fmt, 'resize', worst, compared, bound)
+    assert worst <= bound and compared >= n * (ow // 2 - 2) * (oh // 2 - 2)
