@@ -1,6 +1,10 @@
 """The NV12 test cases, made on the CPU: geometry, motion, the reference's maps (C oracle), random planes, the model's result
 (tests/nv12_model.py) and the luma reference -- computed once per case, shared, never changed.  Before any kernel result is looked at, every
-non-tiny case is checked to hold all three classes of chroma samples: border, partly outside and deep interior."""
+non-tiny case is checked to hold all three classes of chroma samples: border, partly outside and deep interior.
+
+Those are classes of TAPS.  They say nothing about which footprint path of the kernel produced a sample: the frames stop at 128 x 96 with cells
+of 20 to 33 pixels under a 32-pixel footprint, so hot and pair footprints are few or absent here.  The plan classes and the tail's two forms
+are counted and compared in tests/test_gpu_footprint_paths.py on tests/footprint_cases.py's geometries."""
 import glob
 import os
 

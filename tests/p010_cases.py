@@ -2,7 +2,8 @@
 that every non-tiny case holds border, partly-outside and deep-interior chroma samples), with uint16 planes drawn over the whole 0 .. 65535
 range -- products of 16-bit samples and 10-bit weights need 26 bits and must round; 8-bit-sized samples would hide a fused or reordered chain
 -- and the model's result (tests/p010_model.py), computed once per case, shared, never changed.  Before any kernel result is looked at, every
-non-tiny case is also checked to hold all three classes of LUMA samples."""
+non-tiny case is also checked to hold all three classes of LUMA samples.  (Classes of taps, as in tests/nv12_cases.py: which footprint path
+produced a sample -- hot, pair, the general code; the fast or the clamped tail -- is tests/test_gpu_footprint_paths.py's business.)"""
 import zlib
 
 import numpy as np

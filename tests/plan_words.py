@@ -5,6 +5,11 @@ import numpy as np
 PLAN_HOT = 0x2000
 PLAN_VALID = 0x4000
 PLAN_BORDER = 0x1000
+PLAN_FAST64 = 0x0002            # in entry 1, only with PLAN_HOT: the cheap float64 coordinate chain is allowed (MF_PLAN_FAST64)
+PLAN_OVERFLOW = 0xFFFF          # entry 7: more than 8 candidate cells, entries 0-3 hold the cell range (MF_PLAN_OVERFLOW)
+FOOT_W, FOOT_H = 32, 8          # MF_FOOT_W, MF_FOOT_H
+# footprint_class_map's labels, in the order of their codes
+CLASS_NAMES = ('hot_fast64', 'hot_plain', 'pair', 'multi', 'border', 'overflow', 'other')
 REGION_STAGED = 0x80000000
 REGION_COMPACT = 0x20000000
 REGION_BORDER = 0x08000000
@@ -29,14 +34,46 @@ def plan_and_regions(buf, n, W, H, R, C, src=False):
 
 
 def classes(plan, region):
-    """Boolean masks per footprint: hot / pair / border (the plan's classes, as tools/class_census.py counts them) and the region's
-    staged / compact / border-window flags."""
-    x, y = plan[:, 0], plan[:, 1]
+    """Boolean masks per footprint: hot / pair / border (the plan's classes, as tools/class_census.py counts them), multi (MF_PLAN_HOT in
+    the first edge-code word, entry 4, and none of the three), overflow (entry 7 is 0xFFFF: the first four entries then hold a cell range,
+    whose numbers never carry bit 12 or 13), hot_fast64 (MF_PLAN_FAST64 next to MF_PLAN_HOT in entry 1) and the region's staged / compact /
+    border-window flags."""
+    x, y, z, w = plan[:, 0], plan[:, 1], plan[:, 2], plan[:, 3]
     hot = ((x >> 16) & PLAN_HOT) != 0
     border = (((x >> 16) & (PLAN_VALID | PLAN_BORDER)) == PLAN_BORDER) & ~hot
     pair = ((y & PLAN_HOT) != 0) & ~hot & ~border
-    return dict(hot=hot, pair=pair, border=border, staged=(region & REGION_STAGED) != 0, compact=(region & REGION_COMPACT) != 0,
-                border_window=(region & REGION_BORDER) != 0)
+    multi = ((z & PLAN_HOT) != 0) & ~hot & ~pair & ~border
+    return dict(hot=hot, pair=pair, border=border, multi=multi, overflow=(w >> 16) == PLAN_OVERFLOW,
+                hot_fast64=hot & (((x >> 16) & PLAN_FAST64) != 0),
+                staged=(region & REGION_STAGED) != 0, compact=(region & REGION_COMPACT) != 0, border_window=(region & REGION_BORDER) != 0)
+
+
+def entry_counts(plan):
+    """Candidate cells per footprint as footprint_body's general path counts them: the leading entries that carry bit 14 (0 for an empty list
+    and for an overflow list, whose first four entries are row and column numbers)."""
+    valid = (np.ascontiguousarray(plan).view(np.uint16).reshape(-1, 8) & PLAN_VALID) != 0
+    return np.cumprod(valid, axis=1).sum(axis=1)
+
+
+def footprint_class_map(table):
+    """One label per footprint of `table` (an ops.CellTable after ops.cell_table), uint8 (n, ceil(H / 8), ceil(W / 32)) of indices into
+    CLASS_NAMES: footprint t of frame f is row t // nfx, column t % nfx (footprint_body's ty, tx).  The classes in the order the warps that
+    take the shortcuts without a window test them (warp_body.h, NOWIN): hot -- split by MF_PLAN_FAST64 --, then pair; border, multi and
+    overflow lists go through the general path there, 'other' is every remaining list (one uncertified cell, five to eight cells, none)."""
+    nfy, nfx = (table.H + FOOT_H - 1) // FOOT_H, (table.W + FOOT_W - 1) // FOOT_W
+    plan, region = plan_and_regions(table.buf, table.n, table.W, table.H, table.R, table.C)
+    k = classes(plan, region)
+    label = np.full(plan.shape[0], CLASS_NAMES.index('other'), np.uint8)
+    for name, mask in (('overflow', k['overflow']), ('multi', k['multi']), ('border', k['border']), ('pair', k['pair']),
+                       ('hot_plain', k['hot'] & ~k['hot_fast64']), ('hot_fast64', k['hot_fast64'])):
+        label[mask] = CLASS_NAMES.index(name)
+    return label.reshape(table.n, nfy, nfx)
+
+
+def per_pixel(footprint_map, H, W):
+    """A per-footprint array (n, ceil(H / 8), ceil(W / 32)) expanded to the luma pixels (n, H, W) its footprints hold.  The chroma sample
+    (cx, cy) of a 4:2:0 plane belongs to luma pixel (2 cx, 2 cy): per_pixel(...)[:, ::2, ::2]."""
+    return np.repeat(np.repeat(np.asarray(footprint_map), FOOT_H, axis=1), FOOT_W, axis=2)[:, :H, :W]
 
 
 def grey_paths(table, aligned=True):

@@ -4,7 +4,11 @@ mf_warp_plane_* / mf_crop_resize_plane_* / mf_crop_resize_dev_plane_*.
 Every equality is bit for bit (uint8 / uint16 / uint32 / uint64 views); there is no tolerance anywhere.  The references: tests/planes_model.py
 applied to the reference's own maps (tests/cv16_model.warp_maps: the C oracle, on the CPU), the merged uint16 kernels on integer-valued planes,
 and a gather on `ops.warp_maps` for the label planes.  The geometries are tests/test_gpu_warp_maps.py's kinds at 64 x 48 .. 160 x 96, with
-2 x 2 and 3 x 4 meshes, one odd width and one frame at the 2-pixel limit."""
+2 x 2 and 3 x 4 meshes, one odd width and one frame at the 2-pixel limit.
+
+These geometries are chosen for the calls' edges -- sizes, alignments, sample classes --, not for the kernel's footprint paths: two of the five
+have W % 4 != 0 and can hold no hot or pair footprint at all, and nothing here says which plan class produced a sample.  The paths (hot with
+either coordinate chain, pair, multi, border, overflow, each under both tail forms) are held in tests/test_gpu_footprint_paths.py."""
 import os
 import sys
 

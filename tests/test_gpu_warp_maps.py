@@ -72,12 +72,10 @@ def table_for(dev, disp, stab, H, W, R, C, bounds=None):
 
 
 def class_counts(table):
-    """Footprints per plan class: hot / pair / border as tests/plan_words.py decodes them, multi = the short lists of coded edges that
-    carry MF_PLAN_HOT in their first edge-code word (csrc/mf_common.h) and are none of the others."""
+    """Footprints per plan class: hot / pair / multi / border as tests/plan_words.py decodes them."""
     plan, region = plan_words.plan_and_regions(table.buf, table.n, table.W, table.H, table.R, table.C)
     k = plan_words.classes(plan, region)
-    multi = ((plan[:, 2] & plan_words.PLAN_HOT) != 0) & ~k['hot'] & ~k['pair'] & ~k['border']
-    return {'hot': int(k['hot'].sum()), 'pair': int(k['pair'].sum()), 'multi': int(multi.sum()), 'border': int(k['border'].sum())}
+    return {name: int(k[name].sum()) for name in ('hot', 'pair', 'multi', 'border')}
 
 
 # F, H, W, R, C, jitter, kind, seed.  Every case leaves pixels no cell owns (asserted): the stabilised mesh never covers the whole frame here.
