@@ -622,6 +622,27 @@ int mf_online_smooth_f64(const float* d_vel, const double* d_lam_known, const do
                          double beta, double lam_newest, int64_t seen, double* d_c_state, double* d_q_state, double* d_lam_state,
                          double* d_c_out, double* d_p_out, void* stream);
 
+/* ---- scene cuts: a per-frame signature of tile histograms of luma, and the distance of adjacent signatures ----
+ * The reference has nothing of the kind; this is a specification of the project's own, bit for bit tests/cuts_model.py, integers only -- any
+ * order of summation gives the same bytes.
+ *   signature  of an H x W uint8 frame: 4 x 4 tiles; tile row i covers rows [floor(i H / 4), floor((i + 1) H / 4)), tile columns split W the
+ *              same way (a tile is empty where H < 4 or W < 4); 16 counters per tile, counter b = the number of the tile's pixels with
+ *              value >> 4 == b; layout [tile_row][tile_col][bin], MF_CUT_COUNTERS = 256 int32 per frame, which sum to H W
+ *   distance   D(a, b) = the sum over the 256 counters of |a - b|, 0 .. 2 H W; with W, H <= 32,767 that is below 2^31
+ *   decision   the caller's, on the host: frame t starts a new shot iff D_t > floor(threshold * 2 H W) (meshflow_amd/ops.py, find_cuts)
+ * mf_frame_signature_u8: d_luma is a contiguous [n][H][W] uint8 stack that may start at any byte (16-byte loads where the address allows,
+ * narrower ones elsewhere); d_sig [n][256] int32 is OVERWRITTEN -- the call clears it itself (a memset on `stream`), then one launch per 2^20
+ * workgroups adds every strip of a tile to it with integer atomic adds, which commute: a second call gives the same bytes.  Pixel indices are
+ * 64-bit (n * W * H may exceed 2^32).
+ * mf_cut_distance_i32: d_dist [n] int32; d_dist[0] = D(d_sig_prev, d_sig[0]) where d_sig_prev ([256] int32) is given, else 0;
+ * d_dist[i] = D(d_sig[i - 1], d_sig[i]) for the rest.  One launch, no atomics.
+ * Limits (MF_ERR_INVALID_ARG, nothing launched): null pointers other than d_sig_prev; n < 1; W or H outside 1 .. MF_CUT_MAX_DIM (32,767);
+ * d_sig, d_dist or d_sig_prev not 4-byte aligned; an output that overlaps an input.  Asynchronous on `stream`. */
+#define MF_CUT_COUNTERS 256
+#define MF_CUT_MAX_DIM 32767
+int mf_frame_signature_u8(const uint8_t* d_luma, int n, int W, int H, int32_t* d_sig, void* stream);
+int mf_cut_distance_i32(const int32_t* d_sig_prev, const int32_t* d_sig, int n, int32_t* d_dist, void* stream);
+
 /* ---- stability score (mfs.py:1216-1259) of device-resident vertex paths ----
  * d_stab: [F][S] float64 as for mf_jacobi_f64 (S = V*2: x and y of every vertex interleaved).  Per series the fraction of
  * the velocity profile's spectral energy that sits in DFT bins 1..5 (five direct sums + Parseval for the total);

@@ -868,6 +868,40 @@ int mf_online_smooth_f64(const float* d_vel, const double* d_lam_known, const do
                                 d_lam_state, d_c_out, d_p_out, (hipStream_t)stream);
 }
 
+int mf_frame_signature_u8(const uint8_t* d_luma, int n, int W, int H, int32_t* d_sig, void* stream)
+{
+    const char* name = "mf_frame_signature_u8";
+    if (!d_luma || !d_sig) { set_error("%s: null pointer", name); return MF_ERR_INVALID_ARG; }
+    if (n < 1) { set_error("%s: n must be at least 1 (got %d)", name, n); return MF_ERR_INVALID_ARG; }
+    if (W < 1 || W > MF_CUT_MAX_DIM || H < 1 || H > MF_CUT_MAX_DIM) {
+        set_error("%s: W and H must be in 1 .. %d (got %d x %d)", name, MF_CUT_MAX_DIM, W, H);
+        return MF_ERR_INVALID_ARG;
+    }
+    if ((uintptr_t)d_sig & 3) { set_error("%s: d_sig must be 4-byte aligned", name); return MF_ERR_INVALID_ARG; }
+    if (overlap(d_luma, (size_t)n * (size_t)W * (size_t)H, d_sig, (size_t)n * MF_CUT_COUNTERS * 4)) {
+        set_error("%s: d_sig overlaps the frames", name);
+        return MF_ERR_INVALID_ARG;
+    }
+    return launch_frame_signature(d_luma, n, W, H, d_sig, (hipStream_t)stream);
+}
+
+int mf_cut_distance_i32(const int32_t* d_sig_prev, const int32_t* d_sig, int n, int32_t* d_dist, void* stream)
+{
+    const char* name = "mf_cut_distance_i32";
+    if (!d_sig || !d_dist) { set_error("%s: null pointer", name); return MF_ERR_INVALID_ARG; }
+    if (n < 1) { set_error("%s: n must be at least 1 (got %d)", name, n); return MF_ERR_INVALID_ARG; }
+    if (((uintptr_t)d_sig_prev & 3) || ((uintptr_t)d_sig & 3) || ((uintptr_t)d_dist & 3)) {
+        set_error("%s: d_sig_prev, d_sig and d_dist must be 4-byte aligned", name);
+        return MF_ERR_INVALID_ARG;
+    }
+    if (overlap(d_sig, (size_t)n * MF_CUT_COUNTERS * 4, d_dist, (size_t)n * 4) ||
+        (d_sig_prev && overlap(d_sig_prev, MF_CUT_COUNTERS * 4, d_dist, (size_t)n * 4))) {
+        set_error("%s: d_dist overlaps a signature", name);
+        return MF_ERR_INVALID_ARG;
+    }
+    return launch_cut_distance(d_sig_prev, d_sig, n, d_dist, (hipStream_t)stream);
+}
+
 int mf_stability_score_f64(const double* d_stab, int F, int S, double* d_series, double* d_score, void* stream)
 {
     if (!d_stab || !d_series || !d_score) { set_error("mf_stability_score_f64: null pointer"); return MF_ERR_INVALID_ARG; }

@@ -4,7 +4,9 @@ The offline path needs a whole clip twice: `ops.jacobi` smooths every vertex pat
 reduction.  A session replaces the first by `ops.online_smooth` -- a sliding window that ends at the newest frame (include/meshflow_hip.h,
 mf_online_smooth_f64; tests/online_model.py) -- and the second by a rectangle fixed in advance from `crop_margin`.  Everything else is the
 offline path's own: `ops.luma`, the device tracker with the outlier step and the fit on the device, `ops.vertex_motion`, `ops.cell_table`,
-the format's warp and crop-resize.  What a session carries between pushes: the previous push's last luma frame and an `ops.OnlineState`."""
+the format's warp and crop-resize.  What a session carries between pushes: the previous push's last luma frame, an `ops.OnlineState` and --
+with on_cut='reset' -- that frame's scene-cut signature (`ops.find_cuts`; tests/cuts_model.py), by which a push finds the cuts in its frames
+and restarts the path at each."""
 import collections
 import math
 
@@ -30,13 +32,34 @@ def margin_rectangle(crop_margin, W, H):
     return left, top, right, bottom
 
 
+def luma_of(frames, red_first=False):
+    """(form, luma (n, H, W) uint8) of a clip in any form `stabilize_scored` takes; form = (pair?, dtype, frame shape)."""
+    import torch
+    from . import ops
+    if isinstance(frames, (tuple, list)):
+        if len(frames) != 2:
+            raise ValueError('an NV12 or P010 clip is the pair (d_y, d_uv)')
+        d_y, d_uv = frames
+        fmt = ops._P010 if isinstance(d_y, torch.Tensor) and d_y.dtype == torch.uint16 else ops._NV12
+        ops._need_420(fmt, d_y, d_uv)
+        return (True, d_y.dtype, tuple(d_y.shape[1:])), (ops.luma(d_y) if fmt is ops._P010 else d_y)
+    if isinstance(frames, torch.Tensor) and frames.dtype == torch.uint16 and frames.dim() == 3:
+        raise ValueError('a (n, H, W) uint16 stack is the luma plane of a P010 clip: pass the pair (d_y, d_uv)')
+    ops._frames_format(frames)
+    return (False, frames.dtype, tuple(frames.shape[1:])), (ops.luma(frames, red_first) if ops.luma_source(frames) is not None else frames)
+
+
+def _part(frames, lo, hi):
+    return tuple(p[lo:hi] for p in frames) if isinstance(frames, (tuple, list)) else frames[lo:hi]
+
+
 class OnlineSession:
     """One stream of frames through `stabilizer`.  Made by `MeshFlowStabilizer.online_session`, which documents the keywords."""
 
     def __init__(self, stabilizer, window=40, iters=10, beta=1.0, crop_margin=0.08, output_size=None,
                  adaptive_weights_definition=host.ADAPTIVE_WEIGHTS_DEFINITION_ORIGINAL, chunk_pairs=32, max_per_subframe=1024, red_first=False,
-                 on_lost='hold'):
-        from . import _lib
+                 on_lost='hold', on_cut='ignore', cut_threshold=0.30):
+        from . import _lib, ops
         stabilizer._check_definition(adaptive_weights_definition)
         omega = int(stabilizer.temporal_smoothing_radius)
         if not 2 <= int(window) <= _lib.ONLINE_MAX_WINDOW:
@@ -51,40 +74,34 @@ class OnlineSession:
             raise ValueError(f'crop_margin must lie in [0, 0.5) (got {crop_margin!r})')
         if on_lost not in ('hold', 'raise'):
             raise ValueError(f"on_lost must be 'hold' or 'raise' (got {on_lost!r})")
+        if on_cut not in ('ignore', 'reset'):
+            raise ValueError(f"on_cut must be 'ignore' or 'reset' (got {on_cut!r})")
+        self.on_cut, self.cut_threshold = on_cut, ops.check_cut_threshold(cut_threshold, 'cut_threshold')
         self.stabilizer, self.window, self.omega, self.iters, self.beta = stabilizer, int(window), omega, int(iters), float(beta)
         self.crop_margin, self.output_size, self.definition = crop_margin, output_size, adaptive_weights_definition
         self.chunk_pairs, self.red_first, self.on_lost = chunk_pairs, red_first, on_lost
         self.device = stabilizer._torch_device()
         self.tracker = stabilizer.device_tracker(max_per_subframe, 'device', 'device')
         self.form = None              # (pair?, dtype, frame shape) of the first push; the rectangle and the state follow from it
-        self.rectangle = self.state = self._last_luma = self._taps = self._lam_newest = None
+        self.rectangle = self.state = self._last_luma = self._last_sig = self._taps = self._lam_newest = None
+        # shots: the shots begun so far (the first frame, every frame after a `reset()`, every cut found); last_cuts: the indices, relative to
+        # the last push, of its frames that started a shot, and last_cut_distances: that push's (n,) int32 distances -- on_cut='reset' only
+        self.shots, self.last_cuts, self.last_cut_distances = 0, [], None
 
     @property
     def seen(self):
         return self.state.seen if self.state is not None else 0
 
     def reset(self):
-        """Forget every frame pushed so far (a caller that knows of a cut): the next push starts a path at frame 0, as a fresh session's
-        does.  The frame size and form stay."""
+        """Forget every frame pushed so far (a caller that knows of a cut; on_cut='reset' calls it at the cuts it finds): the next push starts
+        a path at frame 0, as a fresh session's does, and its first frame is no cut.  The frame size and form stay."""
         if self.state is not None:
             self.state.reset()
-        self._last_luma = None
+        self._last_luma = self._last_sig = None
 
     def _luma_of(self, frames):
         """(form, luma (n, H, W) uint8) of a push, in any form `stabilize_scored` takes."""
-        import torch
-        from . import ops
-        if isinstance(frames, (tuple, list)):
-            if len(frames) != 2:
-                raise ValueError('an NV12 or P010 clip is the pair (d_y, d_uv)')
-            d_y, d_uv = frames
-            fmt = ops._P010 if isinstance(d_y, torch.Tensor) and d_y.dtype == torch.uint16 else ops._NV12
-            ops._need_420(fmt, d_y, d_uv)
-            return (True, d_y.dtype, tuple(d_y.shape[1:])), (ops.luma(d_y) if fmt is ops._P010 else d_y)
-        if isinstance(frames, torch.Tensor) and frames.dtype == torch.uint16 and frames.dim() == 3:
-            raise ValueError('a (n, H, W) uint16 stack is the luma plane of a P010 clip: pass the pair (d_y, d_uv)')
-        ops._frames_format(frames)
-        return (False, frames.dtype, tuple(frames.shape[1:])), (ops.luma(frames, self.red_first) if ops.luma_source(frames) is not None else frames)
+        return luma_of(frames, self.red_first)
 
     def _start(self, form, H, W):
         import torch
@@ -102,10 +119,13 @@ class OnlineSession:
 
     def push(self, frames):
         """One or more new frames -- a stack (n, ...) in any form `stabilize_scored` takes, on the session's device -- in; returns
-        (the same n frames stabilized and cropped, in the input's form, `OnlineReport`)."""
+        (the same n frames stabilized and cropped, in the input's form, `OnlineReport`).  on_cut='reset': the frames are scored first
+        (`ops.find_cuts` against the signature of the last frame pushed: two small launches and one wait for n integers), the block is
+        split at every cut and each part pushed as a plain session would, with `reset()` before each part that begins at a cut -- the pair
+        across a cut is never tracked --; the parts' frames and reports come back joined: `first` is the first part's, d_unstab, d_stab and
+        covered are concatenated, `lost` is concatenated in each part's own numbering."""
         import torch
-        from . import _lib, ops
-        s = self.stabilizer
+        from . import ops
         form, luma = self._luma_of(frames)
         n, H, W = (int(v) for v in luma.shape)
         if n < 1:
@@ -115,6 +135,51 @@ class OnlineSession:
         elif form != self.form:
             raise ValueError(f'this session takes {self.form[1]} frames of shape {self.form[2]}{" as (d_y, d_uv) pairs" if self.form[0] else ""}; '
                              f'got {form[1]} frames of shape {form[2]}{" as a pair" if form[0] else ""}')
+        if self.on_cut == 'ignore':
+            return self._push_part(frames, form, luma)
+        cuts, distances, sig = ops.find_cuts(luma, self.cut_threshold, self._last_sig)
+        if not cuts:
+            result = self._push_part(frames, form, luma)
+        else:
+            starts = sorted({0, *cuts}) + [n]
+            # on_lost='raise' promises the session as it was: a part may fail after an earlier one, or a reset, has changed it
+            saved = self._snapshot() if self.on_lost == 'raise' else None
+            try:
+                parts = []
+                for lo, hi in zip(starts[:-1], starts[1:]):
+                    if lo in cuts:
+                        self.reset()
+                    parts.append(self._push_part(_part(frames, lo, hi), form, luma[lo:hi]))
+            except ValueError:
+                if saved is not None:
+                    self._restore(saved)
+                raise
+            if len(parts) == 1:
+                result = parts[0]
+            else:
+                outs, reports = [p[0] for p in parts], [p[1] for p in parts]
+                out = tuple(torch.cat([o[i] for o in outs]) for i in range(2)) if form[0] else torch.cat(outs)
+                result = out, OnlineReport(reports[0].first, torch.cat([r.d_unstab for r in reports]), torch.cat([r.d_stab for r in reports]),
+                                           self.rectangle, torch.cat([r.covered for r in reports]), [t for r in reports for t in r.lost])
+        self._last_sig, self.last_cuts, self.last_cut_distances = sig, cuts, distances
+        return result
+
+    def _snapshot(self):
+        st = self.state
+        return (st.c.clone(), st.q.clone(), st.lam.clone(), st.seen), self._last_luma, self._last_sig, self.shots
+
+    def _restore(self, saved):
+        (c, q, lam, seen), self._last_luma, self._last_sig, self.shots = saved
+        st = self.state
+        st.c.copy_(c), st.q.copy_(q), st.lam.copy_(lam)
+        st.seen = seen
+
+    def _push_part(self, frames, form, luma):
+        """A run of frames of one shot through the session: (frames out, `OnlineReport`)."""
+        import torch
+        from . import _lib, ops
+        s = self.stabilizer
+        n, H, W = (int(v) for v in luma.shape)
         R, C, S, first = s.mesh_row_count, s.mesh_col_count, self.state.S, self.state.seen
         # pairs: (the frame kept from the previous push -> new frame 0), then the adjacent new frames
         stack, k0 = (luma, 1) if self._last_luma is None else (torch.cat([self._last_luma[None], luma]), 0)
@@ -143,6 +208,7 @@ class OnlineSession:
         c, p = ops.online_smooth(vel, torch.from_numpy(lam_known).to(self.device), self.state, self._taps, self.omega, self.iters, self.beta,
                                  self._lam_newest)
         self._last_luma = luma[-1].clone()
+        self.shots += int(first == 0)
         table = ops.cell_table(c, p, W, H, R, C)
         left, top, right, bottom = self.rectangle
         whole = (left, top, right, bottom) == (0, 0, W - 1, H - 1) and self.output_size in (None, (W, H))

@@ -5,6 +5,7 @@ hands raw device pointers to libmeshflow_hip.so through the C ABI (`_lib.py`) on
 stream, so torch.cuda events and synchronisation see the kernels."""
 import collections
 import ctypes
+import math
 
 import numpy as np
 import torch
@@ -999,6 +1000,68 @@ def online_smooth(vel, lam_known, state, taps, omega, iters, beta, lam_newest):
                                           _stream()))
     state.seen += n
     return c, p
+
+
+CUT_THRESHOLD = 0.30            # a design choice, not a value tuned on footage (profiles/cuts.md)
+
+
+def check_cut_threshold(threshold, name='threshold'):
+    """`threshold` as a float: a finite number in [0, 1], else ValueError."""
+    if isinstance(threshold, bool) or not isinstance(threshold, (int, float, np.integer, np.floating)) or not 0.0 <= float(threshold) <= 1.0:
+        raise ValueError(f'{name} must be a finite number in [0, 1] (got {threshold!r})')           # (a NaN fails both comparisons)
+    return float(threshold)
+
+
+def cut_bound(threshold, W, H):
+    """The largest distance of two W x H frames that is not a cut: floor(threshold * 2 H W)."""
+    return math.floor(float(threshold) * (2 * int(H) * int(W)))
+
+
+def frame_signatures(d_luma):
+    """The scene-cut signature of every frame of a (n, H, W) uint8 luma stack on the device: a (n, 256) int32 device tensor, bit for bit
+    tests/cuts_model.py -- 4 x 4 tiles, 16 counters of value >> 4 per tile, [tile_row][tile_col][bin] (include/meshflow_hip.h,
+    mf_frame_signature_u8).  On torch's current stream; does not wait for it."""
+    name = 'frame_signatures'
+    _need(d_luma, torch.uint8, 'd_luma')
+    if d_luma.dim() != 3:
+        raise ValueError(f'{name}: d_luma must have shape (n, H, W): one-channel uint8 images (got {tuple(d_luma.shape)})')
+    n, H, W = (int(v) for v in d_luma.shape)
+    if n < 1 or not 1 <= H <= _lib.CUT_MAX_DIM or not 1 <= W <= _lib.CUT_MAX_DIM:
+        raise ValueError(f'{name}: d_luma needs n >= 1 and H, W in 1 .. {_lib.CUT_MAX_DIM} (got {tuple(d_luma.shape)})')
+    sig = torch.empty((n, _lib.CUT_COUNTERS), dtype=torch.int32, device=d_luma.device)
+    _lib.check(_lib_.mf_frame_signature_u8(_ptr(d_luma), n, W, H, _ptr(sig), _stream()))
+    return sig
+
+
+def cut_distances(d_sig, d_prev=None):
+    """The distance of every signature of d_sig, (n, 256) int32 on the device, from the one before it: a (n,) int32 device tensor, entry i the
+    sum over the 256 counters of |d_sig[i] - d_sig[i - 1]|; entry 0 is measured from d_prev, a (256,) int32 signature, and is 0 without one
+    (mf_cut_distance_i32).  On torch's current stream; does not wait for it."""
+    name = 'cut_distances'
+    _need(d_sig, torch.int32, 'd_sig')
+    if d_sig.dim() != 2 or d_sig.shape[0] < 1 or d_sig.shape[1] != _lib.CUT_COUNTERS:
+        raise ValueError(f'{name}: d_sig must have shape (n, {_lib.CUT_COUNTERS}) with n >= 1 (got {tuple(d_sig.shape)})')
+    if d_prev is not None:
+        _need(d_prev, torch.int32, 'd_prev')
+        if tuple(d_prev.shape) != (_lib.CUT_COUNTERS,) or d_prev.device != d_sig.device:
+            raise ValueError(f'{name}: d_prev must have shape ({_lib.CUT_COUNTERS},) on the device of d_sig (got {tuple(d_prev.shape)} on {d_prev.device})')
+    n = int(d_sig.shape[0])
+    dist = torch.empty(n, dtype=torch.int32, device=d_sig.device)
+    _lib.check(_lib_.mf_cut_distance_i32(_ptr(d_prev) if d_prev is not None else None, _ptr(d_sig), n, _ptr(dist), _stream()))
+    return dist
+
+
+def find_cuts(d_luma, threshold=CUT_THRESHOLD, d_prev=None):
+    """Where the shots of a (n, H, W) uint8 luma stack on the device begin: (the indices i, relative to the stack, of the frames with
+    distance[i] > floor(threshold * 2 H W); the distances as a NumPy (n,) int32 array; the last frame's signature, a (256,) int32 device
+    tensor -- the next block's d_prev).  Frame 0 is measured from d_prev, the signature of the frame before the stack, and is never a cut
+    without one.  threshold: a finite number in [0, 1]; at 1.0 nothing is a cut.  The decision is made on the host from the integers,
+    which are handed out so that a caller can apply a rule of their own.  Two launches; the one wait is for the n distances."""
+    threshold = check_cut_threshold(threshold)
+    sig = frame_signatures(d_luma)
+    dist = cut_distances(sig, d_prev).cpu().numpy()
+    bound = cut_bound(threshold, d_luma.shape[2], d_luma.shape[1])
+    return [int(i) for i in np.nonzero(dist.astype(np.int64) > bound)[0]], dist, sig[-1]
 
 
 def stability_score(stab):

@@ -377,7 +377,7 @@ class MeshFlowStabilizer:
 
     def online_session(self, window=40, iters=10, beta=1.0, crop_margin=0.08, output_size=None,
                        adaptive_weights_definition=ADAPTIVE_WEIGHTS_DEFINITION_ORIGINAL, chunk_pairs=32, max_per_subframe=1024, red_first=False,
-                       on_lost='hold'):
+                       on_lost='hold', on_cut='ignore', cut_threshold=0.30):
         """Stabilization of a stream whose end nobody has seen -- a capture card, a decoder's ring, a clip longer than HBM: an
         `online.OnlineSession` whose `push(frames)` takes one or more new frames in any form `stabilize_scored` takes and returns
         (those frames stabilized and cropped, in the input's form, `online.OnlineReport`) at once, with zero latency.  The reference has no
@@ -392,11 +392,29 @@ class MeshFlowStabilizer:
         right = (W - 1) - left, the same vertically (crop_margin in [0, 0.5), at least 2 x 2 pixels left, else ValueError; 0 returns the warp
         uncropped), scaled back to the frame size or to output_size = (width, height).  The report says per frame whether the rectangle
         was `covered`.  on_lost: a pair the tracker cannot fit is zero motion and listed in the report's `lost` ('hold'), or today's
-        ValueError with the session unchanged ('raise').  `reset()` empties the session's memory at a cut.  Frame size and form are fixed
-        by the first push; a later mismatch is a ValueError."""
+        ValueError with the session unchanged ('raise').  `reset()` empties the session's memory at a cut.  on_cut: 'ignore' leaves cuts
+        to the caller -- no launch, wait or byte differs from a session without the keyword --; 'reset' scores every push's frames first
+        (`ops.find_cuts`: the tile-histogram distance of tests/cuts_model.py to the frame before, a cut where it exceeds
+        floor(cut_threshold * 2 H W); cut_threshold a finite number in [0, 1], 0.30 by design, not tuned on footage), splits the block at
+        every cut and calls `reset()` before each part that begins at one, so the pair across a cut is never tracked; the session's
+        `last_cuts`, `last_cut_distances` and `shots` say what it found.  Frame size and form are fixed by the first push; a later
+        mismatch is a ValueError."""
         from . import online
         return online.OnlineSession(self, window, iters, beta, crop_margin, output_size, adaptive_weights_definition, chunk_pairs,
-                                    max_per_subframe, red_first, on_lost)
+                                    max_per_subframe, red_first, on_lost, on_cut, cut_threshold)
+
+    def find_cuts(self, clip, threshold=0.30, red_first=False):
+        """Where the shots of a resident clip begin: the list of frame indices t in 1 .. F-1 whose tile-histogram distance to frame t - 1
+        (`ops.find_cuts`, tests/cuts_model.py) exceeds floor(threshold * 2 H W).  `clip` in any form `stabilize_scored` takes; its luma comes
+        the way a session's does (`online.luma_of`; red_first: RGB / RGBA).  threshold: a finite number in [0, 1], 0.30 by design, not
+        tuned on footage; at 1.0 nothing is a cut.  For splitting a clip before `estimate_motion` / `stabilize_scored`, which track across
+        a cut like across any pair."""
+        from . import online, ops
+        threshold = ops.check_cut_threshold(threshold)
+        if red_first not in (False, True):
+            raise ValueError(f'red_first must be False or True (got {red_first!r})')
+        _, luma = online.luma_of(clip, red_first)
+        return ops.find_cuts(luma, threshold)[0]
 
     def stabilize_online(self, clip, **session):
         """One `online_session(**session)` and one push of the whole clip: (stabilized and cropped clip, `online.OnlineReport`)."""

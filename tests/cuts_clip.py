@@ -1,0 +1,43 @@
+"""What the scene-cut tests share, restated here so that no test module imports another: scene A, the ten 128 x 96 frames of
+tests/test_gpu_online_session.py's `grey_clip()` (canvas seed 21); scene B, the same ten offsets cut from another canvas (seed 77) made darker
+by 60 levels; and the clips with cuts made of the two."""
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import tracker_clip  # noqa: E402
+from tracker_clip import SHIFTS  # noqa: E402
+
+W, H = 128, 96
+MORE_SHIFTS = ((-3, 2), (2, -4), (-5, 3), (4, 1))
+
+
+def _cut_from(big):
+    ox, oy, frames = 20, 20, []
+    for dx, dy in ((0, 0),) + SHIFTS + MORE_SHIFTS:
+        ox, oy = ox - dx, oy - dy
+        frames.append(np.ascontiguousarray(big[oy:oy + H, ox:ox + W]))
+    return np.stack(frames)
+
+
+def scene_a():
+    return _cut_from(tracker_clip.canvas(140, 170, 21, boxes=160))
+
+
+def scene_b():
+    big = tracker_clip.canvas(140, 170, 77, boxes=160).astype(np.int64) - 60
+    return _cut_from(np.clip(big, 0, 255).astype(np.uint8))
+
+
+def one_cut():
+    """M = A[:5] + B[5:]: a cut at frame 5."""
+    a, b = scene_a(), scene_b()
+    return np.concatenate([a[:5], b[5:]])
+
+
+def two_cuts():
+    """M2 = A[:3] + B[3:7] + A[7:]: cuts at frames 3 and 7."""
+    a, b = scene_a(), scene_b()
+    return np.concatenate([a[:3], b[3:7], a[7:]])
