@@ -643,6 +643,38 @@ int mf_online_smooth_f64(const float* d_vel, const double* d_lam_known, const do
 int mf_frame_signature_u8(const uint8_t* d_luma, int n, int W, int H, int32_t* d_sig, void* stream);
 int mf_cut_distance_i32(const int32_t* d_sig_prev, const int32_t* d_sig, int n, int32_t* d_dist, void* stream);
 
+/* ---- path limit: scale a frame's correction so that the mesh still covers a fixed crop rectangle ----
+ * The reference has nothing of the kind (its rectangle is a reduction over the whole clip, mfs.py:1103-1106); this is a specification of the
+ * project's own, bit for bit tests/path_limit_model.py: float64, the operations in the stated order, each rounded by itself, no fma.
+ * d_unstab, d_stab [n][S] float64, S = (R+1)(C+1)*2: the unstabilized path c and the stabilized path p in mf_cell_table_f64's layout.  The
+ * warp puts vertex v at g_v + (p_v - c_v), g the integer vertex grid of mfs.py:881-906 as mf_cell_table_f64 forms it.
+ *   candidate  k in 1 .. steps (K) has f = (double)k / (double)K; vertex v lies at g_v + f * d_v, d_v = p_v - c_v
+ *   polygon    the mesh's perimeter, B = 2 (R + C) vertices: row 0 from column 0 to C-1; column C from row 0 to R-1; row R from column C down
+ *              to 1; column 0 from row R down to 1; edge e joins vertex e to vertex (e + 1) mod B.  Interior vertices play no part
+ *   rectangle  (left, top, right, bottom) inclusive, mf_crop_resize_u8c3's convention, widened: x0 = left - guard, x1 = right + guard,
+ *              y0 = top - guard, y1 = bottom + guard; centre cx = (x0 + x1) * 0.5, cy alike
+ *   passes     candidate k passes iff (a) every edge (A, B) is clear of the rectangle -- its bounding box is disjoint from it
+ *              (min(ax,bx) > x1, or max(ax,bx) < x0, or the same in y; min(a,b) = a < b ? a : b, max(a,b) = a > b ? a : b), or the cross
+ *              products (bx-ax)*(py-ay) - (by-ay)*(px-ax) of the four corners are all > 0, or all < 0 -- and (b) the crossing number of the
+ *              centre's rightward ray is odd: an edge counts iff (ay > cy) != (by > cy) and s = (bx-ax)*(cy-ay) - (by-ay)*(cx-ax) has the
+ *              sign of by - ay.  Every predicate is affirmative: a NaN makes none true
+ *   k_raw_t    the largest k such that every candidate 1 .. k passes; candidate 0 is never tested
+ *   k_t        min(k_raw_t, k_{t-1} + rise), k_{-1} = *d_k_prev clamped to 0 .. K, or K where d_k_prev is null: the drop is immediate, the
+ *              recovery slew-limited; evaluated as min(K, min_i (k_raw_{t-i} + rise * i), k_prev + rise * (t + 1)) over i <= 63
+ *   path       d_out row t = p_t bit for bit when k_t == K, c_t bit for bit when k_t == 0, else c + f * (p - c) with f = (double)k_t / (double)K
+ * d_k_raw, d_k [n] int32 and d_out [n][S] float64 are outputs.  Two launches on `stream`, one 64-lane workgroup per frame each: the first
+ * stages the boundary in LDS (32 bytes per vertex) and lane j tests candidate j + 1, a ballot gives k_raw; the second takes an integer
+ * minimum over the 64 terms and writes the path.  d_k_prev is read on the device, never by the host; the call never waits.  No atomics; a
+ * second call on the same inputs gives the same bytes.
+ * Limits (MF_ERR_INVALID_ARG, nothing launched): n < 1; R or C < 1; 2 (R + C) > MF_PATH_LIMIT_MAX_BOUNDARY; W or H < 2; a rectangle that is
+ * not 0 <= left <= right <= W-1 and 0 <= top <= bottom <= H-1; steps outside 1 .. MF_PATH_LIMIT_MAX_STEPS; rise outside 1 .. steps; guard
+ * negative or not finite; a null pointer other than d_k_prev; a float64 array not 8-byte or an int32 array not 4-byte aligned; an output that
+ * overlaps an input or another output.  Asynchronous on `stream`. */
+#define MF_PATH_LIMIT_MAX_STEPS 64
+#define MF_PATH_LIMIT_MAX_BOUNDARY 1024
+int mf_path_limit_f64(const double* d_unstab, const double* d_stab, int n, int W, int H, int R, int C, int left, int top, int right, int bottom,
+                      double guard, int steps, int rise, const int32_t* d_k_prev, int32_t* d_k_raw, int32_t* d_k, double* d_out, void* stream);
+
 /* ---- stability score (mfs.py:1216-1259) of device-resident vertex paths ----
  * d_stab: [F][S] float64 as for mf_jacobi_f64 (S = V*2: x and y of every vertex interleaved).  Per series the fraction of
  * the velocity profile's spectral energy that sits in DFT bins 1..5 (five direct sums + Parseval for the total);

@@ -19,6 +19,7 @@ HFIT_OK, HFIT_TOO_FEW, HFIT_COLLINEAR, HFIT_AT_INFINITY, HFIT_NOT_CONVERGED, HFI
 SCORES_MAX_PAIRS = 1 << 20
 ONLINE_MAX_WINDOW, ONLINE_MAX_OMEGA, ONLINE_MAX_ITERS = 64, 64, 1000
 CUT_COUNTERS, CUT_MAX_DIM = 256, 32767
+PATH_LIMIT_MAX_STEPS, PATH_LIMIT_MAX_BOUNDARY = 64, 1024
 CELL_OFF_M, CELL_OFF_HI, CELL_OFF_RECT, CELL_OFF_BBOX, CELL_OFF_STATUS = 0, 9, 18, 22, 26
 
 _vp = ctypes.c_void_p
@@ -107,6 +108,7 @@ SIGNATURES = {
     'mf_online_smooth_f64': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, ctypes.c_double, ctypes.c_double, ctypes.c_int64] + [_vp] * 6),
     'mf_frame_signature_u8': (_i, [_vp, _i, _i, _i, _vp, _vp]),
     'mf_cut_distance_i32': (_i, [_vp, _vp, _i, _vp, _vp]),
+    'mf_path_limit_f64': (_i, [_vp, _vp] + [_i] * 9 + [ctypes.c_double, _i, _i] + [_vp] * 5),
     'mf_stability_score_f64': (_i, [_vp, _i, _i, _vp, _vp, _vp]),
     'mf_selftest_sqrt': (_i, [ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),
     'mf_selftest_recip': (_i, [ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),

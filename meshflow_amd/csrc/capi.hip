@@ -902,6 +902,45 @@ int mf_cut_distance_i32(const int32_t* d_sig_prev, const int32_t* d_sig, int n, 
     return launch_cut_distance(d_sig_prev, d_sig, n, d_dist, (hipStream_t)stream);
 }
 
+int mf_path_limit_f64(const double* d_unstab, const double* d_stab, int n, int W, int H, int R, int C, int left, int top, int right, int bottom,
+                      double guard, int steps, int rise, const int32_t* d_k_prev, int32_t* d_k_raw, int32_t* d_k, double* d_out, void* stream)
+{
+    const char* name = "mf_path_limit_f64";
+    if (n < 1) { set_error("%s: n must be at least 1 (got %d)", name, n); return MF_ERR_INVALID_ARG; }
+    if (R < 1 || C < 1 || (long long)R + (long long)C > MF_PATH_LIMIT_MAX_BOUNDARY / 2) {
+        set_error("%s: mesh R=%d C=%d: each at least 1 with 2 (R + C) <= %d boundary vertices", name, R, C, MF_PATH_LIMIT_MAX_BOUNDARY);
+        return MF_ERR_INVALID_ARG;
+    }
+    if (W < 2 || H < 2) { set_error("%s: W and H must be at least 2 (got %d x %d)", name, W, H); return MF_ERR_INVALID_ARG; }
+    if (!(0 <= left && left <= right && right <= W - 1 && 0 <= top && top <= bottom && bottom <= H - 1)) {
+        set_error("%s: rectangle (%d, %d, %d, %d) is not inside a %d x %d frame", name, left, top, right, bottom, W, H);
+        return MF_ERR_INVALID_ARG;
+    }
+    if (steps < 1 || steps > MF_PATH_LIMIT_MAX_STEPS) {
+        set_error("%s: steps must be in 1 .. %d (got %d)", name, MF_PATH_LIMIT_MAX_STEPS, steps);
+        return MF_ERR_INVALID_ARG;
+    }
+    if (rise < 1 || rise > steps) { set_error("%s: rise must be in 1 .. steps = %d (got %d)", name, steps, rise); return MF_ERR_INVALID_ARG; }
+    if (!(guard >= 0.0) || !(guard - guard == 0.0)) { set_error("%s: guard must be finite and >= 0 (got %g)", name, guard); return MF_ERR_INVALID_ARG; }
+    if (!d_unstab || !d_stab || !d_k_raw || !d_k || !d_out) { set_error("%s: null pointer", name); return MF_ERR_INVALID_ARG; }
+    if (((uintptr_t)d_unstab & 7) || ((uintptr_t)d_stab & 7) || ((uintptr_t)d_out & 7) || ((uintptr_t)d_k_prev & 3) || ((uintptr_t)d_k_raw & 3) ||
+        ((uintptr_t)d_k & 3)) {
+        set_error("%s: every float64 array must be 8-byte aligned, every int32 array 4-byte aligned", name);
+        return MF_ERR_INVALID_ARG;
+    }
+    const size_t path = (size_t)n * (size_t)(R + 1) * (size_t)(C + 1) * 2 * sizeof(double), words = (size_t)n * sizeof(int32_t);
+    const struct { const void* at; size_t bytes; } in[3] = {{d_unstab, path}, {d_stab, path}, {d_k_prev, d_k_prev ? sizeof(int32_t) : 0}},
+                                                   out[3] = {{d_k_raw, words}, {d_k, words}, {d_out, path}};
+    for (int a = 0; a < 3; ++a) {
+        for (const auto& i : in)
+            if (i.bytes && overlap(i.at, i.bytes, out[a].at, out[a].bytes)) { set_error("%s: an output aliases an input", name); return MF_ERR_INVALID_ARG; }
+        for (int b = a + 1; b < 3; ++b)
+            if (overlap(out[a].at, out[a].bytes, out[b].at, out[b].bytes)) { set_error("%s: two of the outputs alias", name); return MF_ERR_INVALID_ARG; }
+    }
+    return launch_path_limit(d_unstab, d_stab, n, W, H, R, C, left, top, right, bottom, guard, steps, rise, d_k_prev, d_k_raw, d_k, d_out,
+                             (hipStream_t)stream);
+}
+
 int mf_stability_score_f64(const double* d_stab, int F, int S, double* d_series, double* d_score, void* stream)
 {
     if (!d_stab || !d_series || !d_score) { set_error("mf_stability_score_f64: null pointer"); return MF_ERR_INVALID_ARG; }

@@ -387,6 +387,9 @@ int launch_online_smooth(const float* vel, const double* lam_known, const double
 // cuts.hip: mf_frame_signature_u8 and mf_cut_distance_i32 behind capi.hip's checks
 int launch_frame_signature(const uint8_t* luma, int n, int W, int H, int32_t* sig, hipStream_t st);
 int launch_cut_distance(const int32_t* prev, const int32_t* sig, int n, int32_t* dist, hipStream_t st);
+// path_limit.hip: mf_path_limit_f64 behind capi.hip's checks
+int launch_path_limit(const double* unstab, const double* stab, int n, int W, int H, int R, int C, int left, int top, int right, int bottom,
+                      double guard, int steps, int rise, const int32_t* k_prev, int32_t* k_raw, int32_t* k, double* out, hipStream_t st);
 int launch_selftest_sqrt(unsigned long long n, unsigned long long seed, unsigned long long* d_mismatches, hipStream_t st);
 int launch_stability_score(const double* stab, int F, int S, double* ratio, double* score, hipStream_t st);
 int launch_crop_reduce(const int32_t* crop, int n, int W, int H, int32_t* bounds, hipStream_t st);

@@ -4,9 +4,10 @@ The offline path needs a whole clip twice: `ops.jacobi` smooths every vertex pat
 reduction.  A session replaces the first by `ops.online_smooth` -- a sliding window that ends at the newest frame (include/meshflow_hip.h,
 mf_online_smooth_f64; tests/online_model.py) -- and the second by a rectangle fixed in advance from `crop_margin`.  Everything else is the
 offline path's own: `ops.luma`, the device tracker with the outlier step and the fit on the device, `ops.vertex_motion`, `ops.cell_table`,
-the format's warp and crop-resize.  What a session carries between pushes: the previous push's last luma frame, an `ops.OnlineState` and --
+the format's warp and crop-resize.  What a session carries between pushes: the previous push's last luma frame, an `ops.OnlineState`, --
 with on_cut='reset' -- that frame's scene-cut signature (`ops.find_cuts`; tests/cuts_model.py), by which a push finds the cuts in its frames
-and restarts the path at each."""
+and restarts the path at each, and -- with on_uncovered='limit' -- the last frame's step of `ops.path_limit` (tests/path_limit_model.py), which
+scales a frame's correction back until the warped mesh covers the fixed rectangle again."""
 import collections
 import math
 
@@ -58,7 +59,7 @@ class OnlineSession:
 
     def __init__(self, stabilizer, window=40, iters=10, beta=1.0, crop_margin=0.08, output_size=None,
                  adaptive_weights_definition=host.ADAPTIVE_WEIGHTS_DEFINITION_ORIGINAL, chunk_pairs=32, max_per_subframe=1024, red_first=False,
-                 on_lost='hold', on_cut='ignore', cut_threshold=0.30):
+                 on_lost='hold', on_cut='ignore', cut_threshold=0.30, on_uncovered='report', limit_steps=32, limit_guard=2.0, limit_rise=2):
         from . import _lib, ops
         stabilizer._check_definition(adaptive_weights_definition)
         omega = int(stabilizer.temporal_smoothing_radius)
@@ -76,6 +77,14 @@ class OnlineSession:
             raise ValueError(f"on_lost must be 'hold' or 'raise' (got {on_lost!r})")
         if on_cut not in ('ignore', 'reset'):
             raise ValueError(f"on_cut must be 'ignore' or 'reset' (got {on_cut!r})")
+        if on_uncovered not in ('report', 'limit'):
+            raise ValueError(f"on_uncovered must be 'report' or 'limit' (got {on_uncovered!r})")
+        self.on_uncovered = on_uncovered
+        self.limit_steps, self.limit_guard, self.limit_rise = ops.check_path_limit(limit_steps, limit_guard, limit_rise,
+                                                                                   ('limit_steps', 'limit_guard', 'limit_rise'))
+        # on_uncovered='limit': the last k of the part before (a 1-element int32 device tensor; None: no frame came before, k starts at K),
+        # the k of the parts of the push under way, and the last push's (n,) int32 k on the device
+        self._k_prev, self._limits, self.last_limit = None, [], None
         self.on_cut, self.cut_threshold = on_cut, ops.check_cut_threshold(cut_threshold, 'cut_threshold')
         self.stabilizer, self.window, self.omega, self.iters, self.beta = stabilizer, int(window), omega, int(iters), float(beta)
         self.crop_margin, self.output_size, self.definition = crop_margin, output_size, adaptive_weights_definition
@@ -97,7 +106,7 @@ class OnlineSession:
         a path at frame 0, as a fresh session's does, and its first frame is no cut.  The frame size and form stay."""
         if self.state is not None:
             self.state.reset()
-        self._last_luma = self._last_sig = None
+        self._last_luma = self._last_sig = self._k_prev = None
 
     def _luma_of(self, frames):
         """(form, luma (n, H, W) uint8) of a push, in any form `stabilize_scored` takes."""
@@ -126,6 +135,9 @@ class OnlineSession:
         covered are concatenated, `lost` is concatenated in each part's own numbering."""
         import torch
         from . import ops
+        if self.form is None and self.on_uncovered == 'limit':
+            self._check_limit_fits(frames)
+        self._limits = []
         form, luma = self._luma_of(frames)
         n, H, W = (int(v) for v in luma.shape)
         if n < 1:
@@ -136,7 +148,9 @@ class OnlineSession:
             raise ValueError(f'this session takes {self.form[1]} frames of shape {self.form[2]}{" as (d_y, d_uv) pairs" if self.form[0] else ""}; '
                              f'got {form[1]} frames of shape {form[2]}{" as a pair" if form[0] else ""}')
         if self.on_cut == 'ignore':
-            return self._push_part(frames, form, luma)
+            result = self._push_part(frames, form, luma)
+            self._join_limits()
+            return result
         cuts, distances, sig = ops.find_cuts(luma, self.cut_threshold, self._last_sig)
         if not cuts:
             result = self._push_part(frames, form, luma)
@@ -162,14 +176,35 @@ class OnlineSession:
                 result = out, OnlineReport(reports[0].first, torch.cat([r.d_unstab for r in reports]), torch.cat([r.d_stab for r in reports]),
                                            self.rectangle, torch.cat([r.covered for r in reports]), [t for r in reports for t in r.lost])
         self._last_sig, self.last_cuts, self.last_cut_distances = sig, cuts, distances
+        self._join_limits()
         return result
+
+    def _check_limit_fits(self, frames):
+        """on_uncovered='limit', before the first push touches the device: the rectangle widened by the guard must lie inside the untouched
+        frame with a pixel to spare, or no candidate could pass and every frame would come back unstabilized."""
+        first = frames[0] if isinstance(frames, (tuple, list)) and len(frames) == 2 else frames
+        shape = getattr(first, 'shape', ())
+        if len(shape) < 3:
+            return                                  # (not a clip: `luma_of` says what is wrong with it)
+        H, W = int(shape[1]), int(shape[2])
+        left, top, _, _ = margin_rectangle(self.crop_margin, W, H)
+        if left < self.limit_guard + 1 or top < self.limit_guard + 1:
+            raise ValueError(f"on_uncovered='limit': crop_margin={self.crop_margin} leaves {left} x {top} pixels around the rectangle of a "
+                             f'{W} x {H} frame, limit_guard={self.limit_guard} needs {self.limit_guard + 1:g} on every side: no correction would '
+                             'pass; widen crop_margin')
+
+    def _join_limits(self):
+        import torch
+        if self.on_uncovered == 'limit':
+            self.last_limit = self._limits[0] if len(self._limits) == 1 else torch.cat(self._limits)
+        self._limits = []
 
     def _snapshot(self):
         st = self.state
-        return (st.c.clone(), st.q.clone(), st.lam.clone(), st.seen), self._last_luma, self._last_sig, self.shots
+        return (st.c.clone(), st.q.clone(), st.lam.clone(), st.seen), self._last_luma, self._last_sig, self.shots, self._k_prev
 
     def _restore(self, saved):
-        (c, q, lam, seen), self._last_luma, self._last_sig, self.shots = saved
+        (c, q, lam, seen), self._last_luma, self._last_sig, self.shots, self._k_prev = saved
         st = self.state
         st.c.copy_(c), st.q.copy_(q), st.lam.copy_(lam)
         st.seen = seen
@@ -209,6 +244,11 @@ class OnlineSession:
                                  self._lam_newest)
         self._last_luma = luma[-1].clone()
         self.shots += int(first == 0)
+        if self.on_uncovered == 'limit':
+            # (behind the smoother, whose state keeps the unlimited path: blocks of any sizes give the bytes of one push)
+            p, k = ops.path_limit(c, p, W, H, R, C, self.rectangle, self.limit_steps, self.limit_guard, self.limit_rise, self._k_prev)
+            self._k_prev = k[-1:]
+            self._limits.append(k)
         table = ops.cell_table(c, p, W, H, R, C)
         left, top, right, bottom = self.rectangle
         whole = (left, top, right, bottom) == (0, 0, W - 1, H - 1) and self.output_size in (None, (W, H))

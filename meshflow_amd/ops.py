@@ -1064,6 +1064,67 @@ def find_cuts(d_luma, threshold=CUT_THRESHOLD, d_prev=None):
     return [int(i) for i in np.nonzero(dist.astype(np.int64) > bound)[0]], dist, sig[-1]
 
 
+PATH_LIMIT_STEPS, PATH_LIMIT_GUARD, PATH_LIMIT_RISE = 32, 2.0, 2          # the guard from CPU trials, the rest by design (profiles/path_limit.md)
+
+
+def check_path_limit(steps, guard, rise, names=('steps', 'guard', 'rise')):
+    """(steps, guard, rise) as (int, float, int): steps in 1 .. 64, guard finite and >= 0, rise in 1 .. steps; else ValueError."""
+    def whole(v):
+        return isinstance(v, (int, np.integer)) and not isinstance(v, bool)
+    if not whole(steps) or not 1 <= int(steps) <= _lib.PATH_LIMIT_MAX_STEPS:
+        raise ValueError(f'{names[0]} must be an integer in 1 .. {_lib.PATH_LIMIT_MAX_STEPS} (got {steps!r})')
+    if isinstance(guard, bool) or not isinstance(guard, (int, float, np.integer, np.floating)) or not 0.0 <= float(guard) < math.inf:
+        raise ValueError(f'{names[1]} must be a finite number >= 0 (got {guard!r})')                 # (a NaN fails both comparisons)
+    if not whole(rise) or not 1 <= int(rise) <= int(steps):
+        raise ValueError(f'{names[2]} must be an integer in 1 .. {names[0]} = {int(steps)} (got {rise!r})')
+    return int(steps), float(guard), int(rise)
+
+
+def path_limit(unstab, stab, W, H, R, C, rectangle, steps=PATH_LIMIT_STEPS, guard=PATH_LIMIT_GUARD, rise=PATH_LIMIT_RISE, k_prev=None, out=None):
+    """The stabilized path of n frames limited so that the warped mesh keeps covering `rectangle` (mf_path_limit_f64, bit for bit
+    tests/path_limit_model.py): per frame the correction stab - unstab is scaled by k / steps, k the largest step at which the mesh's
+    perimeter still encloses the rectangle widened by `guard` pixels, falling at once and rising by at most `rise` per frame.
+    unstab, stab: (n, S) or (n, R+1, C+1, 2) float64 device tensors (`cell_table`'s); rectangle: (left, top, right, bottom), inclusive,
+    `crop_resize`'s convention; k_prev: a 1-element int32 device tensor, the last k of the call before (a chain of calls so linked equals one
+    call), None: no frame came before.  out: an (n, S) float64 device tensor to write into.  Returns (limited (n, S) float64, k (n,) int32),
+    device tensors.  On torch's current stream; does not wait for it."""
+    name = 'path_limit'
+    W, H, R, C = int(W), int(H), int(R), int(C)
+    if R < 1 or C < 1 or 2 * (R + C) > _lib.PATH_LIMIT_MAX_BOUNDARY:
+        raise ValueError(f'{name}: the mesh needs R, C >= 1 and 2 (R + C) <= {_lib.PATH_LIMIT_MAX_BOUNDARY} (got R={R}, C={C})')
+    if W < 2 or H < 2:
+        raise ValueError(f'{name}: W and H must be at least 2 (got {W} x {H})')
+    try:
+        left, top, right, bottom = (int(v) for v in rectangle)
+    except (TypeError, ValueError):
+        raise ValueError(f'{name}: rectangle must be (left, top, right, bottom) (got {rectangle!r})') from None
+    if not (0 <= left <= right <= W - 1 and 0 <= top <= bottom <= H - 1):
+        raise ValueError(f'{name}: rectangle {(left, top, right, bottom)} is not inside a {W} x {H} frame')
+    steps, guard, rise = check_path_limit(steps, guard, rise)
+    _need(unstab, torch.float64, 'unstab')
+    _need(stab, torch.float64, 'stab')
+    S = (R + 1) * (C + 1) * 2
+    n = unstab.shape[0] if unstab.dim() else 0
+    if n < 1 or unstab.numel() != n * S or stab.numel() != n * S or stab.shape[0] != n:
+        raise ValueError(f'{name}: unstab and stab must both hold (n, {S}) values with n >= 1, got {tuple(unstab.shape)} and {tuple(stab.shape)}')
+    if stab.device != unstab.device:
+        raise ValueError(f'{name}: stab must be on the device of unstab, {unstab.device}, got {stab.device}')
+    if k_prev is not None:
+        _need(k_prev, torch.int32, 'k_prev')
+        if k_prev.numel() != 1 or k_prev.device != unstab.device:
+            raise ValueError(f'{name}: k_prev must hold 1 int32 on the device of unstab (got {tuple(k_prev.shape)} on {k_prev.device})')
+    if out is None:
+        out = torch.empty((n, S), dtype=torch.float64, device=unstab.device)
+    else:
+        _need(out, torch.float64, 'out')
+        if tuple(out.shape) != (n, S) or out.device != unstab.device:
+            raise ValueError(f'{name}: out must have shape ({n}, {S}) on the device of unstab (got {tuple(out.shape)} on {out.device})')
+    words = torch.empty((2, n), dtype=torch.int32, device=unstab.device)            # k_raw, k
+    _lib.check(_lib_.mf_path_limit_f64(_ptr(unstab), _ptr(stab), n, W, H, R, C, left, top, right, bottom, guard, steps, rise,
+                                       _ptr(k_prev) if k_prev is not None else None, _ptr(words[0]), _ptr(words[1]), _ptr(out), _stream()))
+    return out, words[1]
+
+
 def stability_score(stab):
     """Stability score (mfs.py:1216-1259) of device-resident paths: (F, R+1, C+1, 2) or (F, S) float64 tensor ->
     (score (1,) float64 tensor, per-series fractions (S,))."""

@@ -377,7 +377,8 @@ class MeshFlowStabilizer:
 
     def online_session(self, window=40, iters=10, beta=1.0, crop_margin=0.08, output_size=None,
                        adaptive_weights_definition=ADAPTIVE_WEIGHTS_DEFINITION_ORIGINAL, chunk_pairs=32, max_per_subframe=1024, red_first=False,
-                       on_lost='hold', on_cut='ignore', cut_threshold=0.30):
+                       on_lost='hold', on_cut='ignore', cut_threshold=0.30, on_uncovered='report', limit_steps=32, limit_guard=2.0,
+                       limit_rise=2):
         """Stabilization of a stream whose end nobody has seen -- a capture card, a decoder's ring, a clip longer than HBM: an
         `online.OnlineSession` whose `push(frames)` takes one or more new frames in any form `stabilize_scored` takes and returns
         (those frames stabilized and cropped, in the input's form, `online.OnlineReport`) at once, with zero latency.  The reference has no
@@ -397,11 +398,20 @@ class MeshFlowStabilizer:
         (`ops.find_cuts`: the tile-histogram distance of tests/cuts_model.py to the frame before, a cut where it exceeds
         floor(cut_threshold * 2 H W); cut_threshold a finite number in [0, 1], 0.30 by design, not tuned on footage), splits the block at
         every cut and calls `reset()` before each part that begins at one, so the pair across a cut is never tracked; the session's
-        `last_cuts`, `last_cut_distances` and `shots` say what it found.  Frame size and form are fixed by the first push; a later
-        mismatch is a ValueError."""
+        `last_cuts`, `last_cut_distances` and `shots` say what it found.  on_uncovered: 'report' leaves a frame whose warp does not cover
+        the rectangle as it is, border colour and all, and says so in `covered` -- no launch, wait or byte differs from a session without
+        the keyword --; 'limit' puts `ops.path_limit` (tests/path_limit_model.py) between the smoother and the cell table: the frame's
+        correction p - c is scaled by k / limit_steps, k the largest step (of limit_steps, 1 .. 64) at which the mesh's perimeter encloses
+        the rectangle widened by limit_guard pixels (finite, >= 0; 2 by CPU trials, profiles/path_limit.md), falling at once and rising by
+        at most limit_rise (1 .. limit_steps) per frame.  The limited path is what is warped and what the report's `d_stab` holds; the
+        smoother's own state keeps the unlimited one, so blocks still equal one push.  The session's `last_limit` is the last push's (n,)
+        int32 k on the device; `reset()` and every cut found start k at limit_steps again.  With 'limit' a rectangle that leaves less
+        than limit_guard + 1 pixels on its left or top is a ValueError at the first push: no correction would pass.  Frame size and form
+        are fixed by the first push; a later mismatch is a ValueError."""
         from . import online
         return online.OnlineSession(self, window, iters, beta, crop_margin, output_size, adaptive_weights_definition, chunk_pairs,
-                                    max_per_subframe, red_first, on_lost, on_cut, cut_threshold)
+                                    max_per_subframe, red_first, on_lost, on_cut, cut_threshold, on_uncovered, limit_steps, limit_guard,
+                                    limit_rise)
 
     def find_cuts(self, clip, threshold=0.30, red_first=False):
         """Where the shots of a resident clip begin: the list of frame indices t in 1 .. F-1 whose tile-histogram distance to frame t - 1
