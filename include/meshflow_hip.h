@@ -622,6 +622,24 @@ int mf_online_smooth_f64(const float* d_vel, const double* d_lam_known, const do
                          double beta, double lam_newest, int64_t seen, double* d_c_state, double* d_q_state, double* d_lam_state,
                          double* d_c_out, double* d_p_out, void* stream);
 
+/* ---- online path smoothing with a fixed lag: each frame handed out `lag` windows after it arrived ----
+ * mf_online_smooth_f64 with one more argument, `lag` in 0 .. window - 1, and another choice of what is handed out; bit for bit
+ * tests/online_lag_model.py.  Window xi's solution holds, beside x_xi, refined values of the frames before it; with lag frames of look-ahead
+ *   P^lag_t = x_t in window t + lag's solution after its last sweep;  C^lag_t = C_t.
+ * d_c_out, d_p_out [n][S] float64: row i holds C and x of frame seen + i - lag as they stand after window seen + i's last sweep.  A row whose
+ * frame does not exist (seen + i - lag < 0) is written as 0.0 in both arrays: no output byte is left undefined.  lag = 0 gives
+ * mf_online_smooth_f64's bytes.
+ * The solve, the state update and the second (weights) launch are mf_online_smooth_f64's: the state after a call does not depend on lag,
+ * which selects what is handed out and never enters the arithmetic.  When the stream ends, the frames not yet handed out are the last
+ * min(lag, seen) rows of d_c_state / d_q_state, oldest first: the final window's solution.
+ * The same mapping, from the sweep kernel's second instantiation: the lane whose frame has age `lag` in the window stores its own C and x,
+ * where the plain kernel's newest lane does.  No atomics; a second call on the same inputs gives the same bytes.
+ * Limits (MF_ERR_INVALID_ARG, nothing launched): those of mf_online_smooth_f64, then lag outside 0 .. window - 1.
+ * Asynchronous on `stream`. */
+int mf_online_smooth_lag_f64(const float* d_vel, const double* d_lam_known, const double* d_taps, int n, int S, int omega, int window, int lag,
+                             int iters, double beta, double lam_newest, int64_t seen, double* d_c_state, double* d_q_state,
+                             double* d_lam_state, double* d_c_out, double* d_p_out, void* stream);
+
 /* ---- scene cuts: a per-frame signature of tile histograms of luma, and the distance of adjacent signatures ----
  * The reference has nothing of the kind; this is a specification of the project's own, bit for bit tests/cuts_model.py, integers only -- any
  * order of summation gives the same bytes.

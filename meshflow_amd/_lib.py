@@ -106,6 +106,7 @@ SIGNATURES = {
     'mf_vertex_motion_workspace_bytes': (_sz, [_i, _i, _i, _i, _i]),
     'mf_vertex_motion_f64': (_i, [_vp, _vp, _vp, _vp] + [_i] * 9 + [_vp, _vp, _vp, _vp, _vp]),
     'mf_online_smooth_f64': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, ctypes.c_double, ctypes.c_double, ctypes.c_int64] + [_vp] * 6),
+    'mf_online_smooth_lag_f64': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, ctypes.c_double, ctypes.c_double, ctypes.c_int64] + [_vp] * 6),
     'mf_frame_signature_u8': (_i, [_vp, _i, _i, _i, _vp, _vp]),
     'mf_cut_distance_i32': (_i, [_vp, _vp, _i, _vp, _vp]),
     'mf_path_limit_f64': (_i, [_vp, _vp] + [_i] * 9 + [ctypes.c_double, _i, _i] + [_vp] * 5),

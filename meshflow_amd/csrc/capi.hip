@@ -817,11 +817,11 @@ int mf_vertex_motion_f64(const double* d_early, const double* d_late, const int3
                                 ellipse_rows, ellipse_cols, d_velocities, d_displacements, d_work, d_status, (hipStream_t)stream);
 }
 
-int mf_online_smooth_f64(const float* d_vel, const double* d_lam_known, const double* d_taps, int n, int S, int omega, int window, int iters,
-                         double beta, double lam_newest, int64_t seen, double* d_c_state, double* d_q_state, double* d_lam_state,
-                         double* d_c_out, double* d_p_out, void* stream)
+// What mf_online_smooth_f64 and mf_online_smooth_lag_f64 refuse alike, under the caller's name: MF_OK where the launches may go ahead.
+static int online_smooth_checks(const char* name, const float* d_vel, const double* d_lam_known, const double* d_taps, int n, int S, int omega,
+                                int window, int iters, double beta, double lam_newest, int64_t seen, double* d_c_state, double* d_q_state,
+                                double* d_lam_state, double* d_c_out, double* d_p_out)
 {
-    const char* name = "mf_online_smooth_f64";
     if (n < 1 || S < 1) { set_error("%s: n and S must be at least 1 (got %d, %d)", name, n, S); return MF_ERR_INVALID_ARG; }
     if (window < 2 || window > MF_ONLINE_MAX_WINDOW) {
         set_error("%s: window must be in 2 .. %d (got %d)", name, MF_ONLINE_MAX_WINDOW, window);
@@ -864,8 +864,34 @@ int mf_online_smooth_f64(const float* d_vel, const double* d_lam_known, const do
                 return MF_ERR_INVALID_ARG;
             }
     }
+    return MF_OK;
+}
+
+int mf_online_smooth_f64(const float* d_vel, const double* d_lam_known, const double* d_taps, int n, int S, int omega, int window, int iters,
+                         double beta, double lam_newest, int64_t seen, double* d_c_state, double* d_q_state, double* d_lam_state,
+                         double* d_c_out, double* d_p_out, void* stream)
+{
+    const int rc = online_smooth_checks("mf_online_smooth_f64", d_vel, d_lam_known, d_taps, n, S, omega, window, iters, beta, lam_newest, seen,
+                                        d_c_state, d_q_state, d_lam_state, d_c_out, d_p_out);
+    if (rc != MF_OK) return rc;
     return launch_online_smooth(d_vel, d_lam_known, d_taps, n, S, omega, window, iters, beta, lam_newest, (long long)seen, d_c_state, d_q_state,
                                 d_lam_state, d_c_out, d_p_out, (hipStream_t)stream);
+}
+
+int mf_online_smooth_lag_f64(const float* d_vel, const double* d_lam_known, const double* d_taps, int n, int S, int omega, int window, int lag,
+                             int iters, double beta, double lam_newest, int64_t seen, double* d_c_state, double* d_q_state,
+                             double* d_lam_state, double* d_c_out, double* d_p_out, void* stream)
+{
+    const char* name = "mf_online_smooth_lag_f64";
+    const int rc = online_smooth_checks(name, d_vel, d_lam_known, d_taps, n, S, omega, window, iters, beta, lam_newest, seen, d_c_state, d_q_state,
+                                        d_lam_state, d_c_out, d_p_out);
+    if (rc != MF_OK) return rc;
+    if (lag < 0 || lag > window - 1) {
+        set_error("%s: lag must be in 0 .. window - 1 = %d (got %d)", name, window - 1, lag);
+        return MF_ERR_INVALID_ARG;
+    }
+    return launch_online_smooth_lag(d_vel, d_lam_known, d_taps, n, S, omega, window, lag, iters, beta, lam_newest, (long long)seen, d_c_state,
+                                    d_q_state, d_lam_state, d_c_out, d_p_out, (hipStream_t)stream);
 }
 
 int mf_frame_signature_u8(const uint8_t* d_luma, int n, int W, int H, int32_t* d_sig, void* stream)

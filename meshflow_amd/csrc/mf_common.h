@@ -384,6 +384,10 @@ int launch_vertex_motion(const double* early, const double* late, const int32_t*
 int launch_online_smooth(const float* vel, const double* lam_known, const double* taps, int n, int S, int omega, int L, int iters,
                          double beta, double lam_newest, long long seen, double* c_state, double* q_state, double* lam_state,
                          double* c_out, double* p_out, hipStream_t st);
+// ... and mf_online_smooth_lag_f64: the same launches, the sweep kernel's lagged instantiation
+int launch_online_smooth_lag(const float* vel, const double* lam_known, const double* taps, int n, int S, int omega, int L, int lag, int iters,
+                             double beta, double lam_newest, long long seen, double* c_state, double* q_state, double* lam_state,
+                             double* c_out, double* p_out, hipStream_t st);
 // cuts.hip: mf_frame_signature_u8 and mf_cut_distance_i32 behind capi.hip's checks
 int launch_frame_signature(const uint8_t* luma, int n, int W, int H, int32_t* sig, hipStream_t st);
 int launch_cut_distance(const int32_t* prev, const int32_t* sig, int n, int32_t* dist, hipStream_t st);

@@ -25,6 +25,10 @@
 // row of lam (the newest frame, whose weight is not known before its successor arrives) holds lam_newest.  The C and q columns are a
 // workgroup's own and are updated by it in place; every workgroup READS the L - 1 weights, so they are shifted by a 64-lane launch of
 // its own behind the sweep kernel -- two launches per call whatever n is.
+//
+// Fixed lag (mf_online_smooth_lag_f64; tests/online_lag_model.py): window xi's solution also holds refined values of frames xi - 1,
+// xi - 2, ...; the lagged kernel hands out frame xi - lag -- the registers c and x of the lane whose age is `lag`, after the last sweep --
+// instead of the newest.  Both kernels are online_smooth_body.h, included with MF_ONLINE_LAG 0 and 1; they differ in that store alone.
 #include "mf_common.h"
 
 namespace mf {
@@ -39,105 +43,20 @@ __global__ __launch_bounds__(64) void online_smooth_kernel(const float* __restri
                                                            double* q_state, const double* __restrict__ lam_state,
                                                            double* __restrict__ c_out, double* __restrict__ p_out)
 {
-    __shared__ double xs[2][kOnlineMaxWindow];
-    const int s = blockIdx.x, lane = threadIdx.x;
-    const bool ring = lane < L;
-    const int reach = omega < L - 1 ? omega : L - 1;
-    int slot = (int)(seen % L);                              // the lane of frame `seen`
+#define MF_ONLINE_LAG 0
+#include "online_smooth_body.h"
+#undef MF_ONLINE_LAG
+}
 
-    // the frame this lane holds from the state: frame seen - 1 - k sits in lane (slot - 1 - k) mod L, state row L - 2 - k
-    double c = 0.0, lam = 0.0, x = 0.0;
-    {
-        int k = slot - 1 - lane;
-        if (k < 0) k += L;
-        if (ring && k <= L - 2 && (long long)k < seen) {
-            const int j = L - 2 - k;
-            c = c_state[(size_t)j * S + s];
-            x = q_state[(size_t)j * S + s];
-            lam = lam_state[j];
-        }
-    }
-    double c_run = seen > 0 ? c_state[(size_t)(L - 2) * S + s] : 0.0;        // C of frame seen - 1
-    int cur = 0;
-    xs[0][lane] = x;
-    xs[1][lane] = 0.0;
-    __syncthreads();
-
-    for (int i = 0; i < n; ++i) {
-        const long long xi = seen + i;
-        const int count = xi + 1 < (long long)L ? (int)(xi + 1) : L;         // frames in window xi
-        int age = slot - lane;                                               // xi - (the frame this lane holds)
-        if (age < 0) age += L;
-        const bool in = ring && age < count;
-        const bool newest = lane == slot;
-        const double c_prev = c_run;
-        if (xi > 0) c_run = c_prev + (double)vel[(size_t)i * S + s];         // (row 0 of an empty state is not read)
-        if (xi > 0 && ring && age == 1) lam = lam_known[i];                  // the weight of frame xi - 1 has become known
-        double rhs, one;
-        if (newest) {
-            int before = slot - 1;
-            if (before < 0) before += L;
-            c = c_run;
-            lam = lam_newest;
-            x = xi > 0 ? c_run + (xs[cur][before] - c_prev) : c_run;
-            rhs = c;
-            one = 1.0;
-        } else {
-            rhs = c + beta * x;                                              // x still holds q_t
-            one = 1.0 + beta;
-        }
-        if (newest) xs[cur][lane] = x;                                       // (the slot of frame xi - L, which no window holds any more)
-        const double two_lam = 2.0 * lam;
-        double sw = 0.0;
-        for (int d = -reach; d <= reach; ++d) {
-            if (d == 0) continue;
-            if (in && (unsigned)(age - d) < (unsigned)count) sw = sw + taps[(d < 0 ? -d : d) - 1];
-        }
-        const double den = one + two_lam * sw;
-        __syncthreads();
-
-        for (int it = 0; it < iters; ++it) {
-            const double* __restrict__ from = xs[cur];
-            double acc = 0.0;
-            // (every slot is read and a select keeps or drops the term: no branch per tap, so the reads of a sweep are in flight together;
-            // a dropped term never enters the sum, whatever the slot holds)
-#pragma unroll 4
-            for (int d = -reach; d < 0; ++d) {                               // the older frames, oldest first
-                int at = lane + d;
-                if (at < 0) at += L;
-                const double sum = acc + taps[-d - 1] * from[at & (kOnlineMaxWindow - 1)];
-                acc = in && (unsigned)(age - d) < (unsigned)count ? sum : acc;
-            }
-#pragma unroll 4
-            for (int d = 1; d <= reach; ++d) {                               // the newer ones
-                int at = lane + d;
-                if (at >= L) at -= L;
-                const double sum = acc + taps[d - 1] * from[at & (kOnlineMaxWindow - 1)];
-                acc = in && (unsigned)(age - d) < (unsigned)count ? sum : acc;
-            }
-            x = (rhs + two_lam * acc) / den;
-            if (in) xs[cur ^ 1][lane] = x;
-            cur ^= 1;
-            __syncthreads();
-        }
-        if (newest) {
-            c_out[(size_t)i * S + s] = c;
-            p_out[(size_t)i * S + s] = x;
-        }
-        if (++slot == L) slot = 0;
-    }
-
-    // the last L - 1 frames back into the state (slot is now the lane of frame seen + n)
-    if (ring) {
-        int k = slot - 1 - lane;
-        if (k < 0) k += L;
-        if (k <= L - 2) {
-            const int j = L - 2 - k;
-            const bool exists = (long long)k < seen + n;
-            c_state[(size_t)j * S + s] = exists ? c : 0.0;
-            q_state[(size_t)j * S + s] = exists ? x : 0.0;
-        }
-    }
+__global__ __launch_bounds__(64) void online_smooth_lag_kernel(const float* __restrict__ vel, const double* __restrict__ lam_known,
+                                                               const double* __restrict__ taps, int n, int S, int omega, int L, int iters,
+                                                               double beta, double lam_newest, long long seen, int lag, double* c_state,
+                                                               double* q_state, const double* __restrict__ lam_state,
+                                                               double* __restrict__ c_out, double* __restrict__ p_out)
+{
+#define MF_ONLINE_LAG 1
+#include "online_smooth_body.h"
+#undef MF_ONLINE_LAG
 }
 
 // lam_state row j: frame seen + n - (L - 1) + j.  One workgroup, after the sweep kernel on the same stream.
@@ -165,6 +84,18 @@ int launch_online_smooth(const float* vel, const double* lam_known, const double
     static_assert(MF_ONLINE_MAX_WINDOW == kOnlineMaxWindow, "one lane per window slot");
     online_smooth_kernel<<<dim3((unsigned)S), 64, 0, st>>>(vel, lam_known, taps, n, S, omega, L, iters, beta, lam_newest, seen, c_state,
                                                             q_state, lam_state, c_out, p_out);
+    MF_HIP_TRY(hipGetLastError());
+    online_lam_state_kernel<<<1, 64, 0, st>>>(lam_known, n, L, lam_newest, seen, lam_state);
+    MF_HIP_TRY(hipGetLastError());
+    return MF_OK;
+}
+
+int launch_online_smooth_lag(const float* vel, const double* lam_known, const double* taps, int n, int S, int omega, int L, int lag, int iters,
+                             double beta, double lam_newest, long long seen, double* c_state, double* q_state, double* lam_state,
+                             double* c_out, double* p_out, hipStream_t st)
+{
+    online_smooth_lag_kernel<<<dim3((unsigned)S), 64, 0, st>>>(vel, lam_known, taps, n, S, omega, L, iters, beta, lam_newest, seen, lag,
+                                                                c_state, q_state, lam_state, c_out, p_out);
     MF_HIP_TRY(hipGetLastError());
     online_lam_state_kernel<<<1, 64, 0, st>>>(lam_known, n, L, lam_newest, seen, lam_state);
     MF_HIP_TRY(hipGetLastError());

@@ -7,7 +7,12 @@ offline path's own: `ops.luma`, the device tracker with the outlier step and the
 the format's warp and crop-resize.  What a session carries between pushes: the previous push's last luma frame, an `ops.OnlineState`, --
 with on_cut='reset' -- that frame's scene-cut signature (`ops.find_cuts`; tests/cuts_model.py), by which a push finds the cuts in its frames
 and restarts the path at each, and -- with on_uncovered='limit' -- the last frame's step of `ops.path_limit` (tests/path_limit_model.py), which
-scales a frame's correction back until the warped mesh covers the fixed rectangle again."""
+scales a frame's correction back until the warped mesh covers the fixed rectangle again.
+
+lag=k >= 1 trades k frames of latency for a smoother path (profiles/online_lag.md): the smoother is `ops.online_smooth_lag`
+(mf_online_smooth_lag_f64; tests/online_lag_model.py), which hands a frame out as it stands in the window that ends k frames after it, so a
+push returns the frames that have become final, [emitted, seen - k), and the session also carries the pixels of the at most k frames it still
+owes, as clones on the device.  `flush()` hands those out when the stream -- or, with on_cut='reset', a shot -- ends."""
 import collections
 import math
 
@@ -15,8 +20,8 @@ import numpy as np
 
 from . import host
 
-# What `push` reports beside its frames.  first: the session's index of the push's first frame; d_unstab, d_stab: (n, R+1, C+1, 2) float64
-# device tensors, the unstabilized and the stabilized vertex paths; rectangle: the fixed crop (left, top, right, bottom), inclusive, in
+# What `push` reports beside its frames.  first: the session's index of the first frame returned (the push's first frame unless the
+# session has a lag); d_unstab, d_stab: (n, R+1, C+1, 2) float64 device tensors, n the frames returned, the unstabilized and the stabilized vertex paths; rectangle: the fixed crop (left, top, right, bottom), inclusive, in
 # `ops.crop_resize`'s convention; covered: (n,) bool device tensor, True where the frame's own crop values (`CellTable.crop`, mfs.py:1075-1098)
 # contain the rectangle -- False says the margin was too small for that frame and border colour shows --; lost: the session's indices of the
 # frames whose pair (frame - 1 -> frame) could not be fitted.
@@ -59,12 +64,14 @@ class OnlineSession:
 
     def __init__(self, stabilizer, window=40, iters=10, beta=1.0, crop_margin=0.08, output_size=None,
                  adaptive_weights_definition=host.ADAPTIVE_WEIGHTS_DEFINITION_ORIGINAL, chunk_pairs=32, max_per_subframe=1024, red_first=False,
-                 on_lost='hold', on_cut='ignore', cut_threshold=0.30, on_uncovered='report', limit_steps=32, limit_guard=2.0, limit_rise=2):
+                 on_lost='hold', on_cut='ignore', cut_threshold=0.30, on_uncovered='report', limit_steps=32, limit_guard=2.0, limit_rise=2,
+                 lag=0):
         from . import _lib, ops
         stabilizer._check_definition(adaptive_weights_definition)
         omega = int(stabilizer.temporal_smoothing_radius)
         if not 2 <= int(window) <= _lib.ONLINE_MAX_WINDOW:
             raise ValueError(f'window must be in 2 .. {_lib.ONLINE_MAX_WINDOW} frames (got {window})')
+        self.lag = ops.check_online_lag(lag, int(window))
         if not 1 <= omega <= _lib.ONLINE_MAX_OMEGA:
             raise ValueError(f'an online session needs temporal_smoothing_radius in 1 .. {_lib.ONLINE_MAX_OMEGA} (got {omega})')
         if not 1 <= int(iters) <= _lib.ONLINE_MAX_ITERS:
@@ -96,17 +103,41 @@ class OnlineSession:
         # shots: the shots begun so far (the first frame, every frame after a `reset()`, every cut found); last_cuts: the indices, relative to
         # the last push, of its frames that started a shot, and last_cut_distances: that push's (n,) int32 distances -- on_cut='reset' only
         self.shots, self.last_cuts, self.last_cut_distances = 0, [], None
+        # lag >= 1: the input frames not handed out yet, oldest first, as a tuple of the input's planes (one for a stack, two for a 4:2:0
+        # pair; the session's own copies; None: none), and how many frames of the path begun at the last reset have been handed out
+        self._held, self.emitted = None, 0
 
     @property
     def seen(self):
         return self.state.seen if self.state is not None else 0
 
+    @property
+    def pending(self):
+        """The frames pushed but not handed out yet: seen - emitted, at most `lag`."""
+        return self.seen - self.emitted
+
     def reset(self):
         """Forget every frame pushed so far (a caller that knows of a cut; on_cut='reset' calls it at the cuts it finds): the next push starts
-        a path at frame 0, as a fresh session's does, and its first frame is no cut.  The frame size and form stay."""
+        a path at frame 0, as a fresh session's does, and its first frame is no cut.  The frame size and form stay.  With lag >= 1 the
+        pending frames are DISCARDED, pixels and all: `flush()` first hands them out."""
         if self.state is not None:
             self.state.reset()
-        self._last_luma = self._last_sig = self._k_prev = None
+        self._last_luma = self._last_sig = self._k_prev = self._held = None
+        self.emitted = 0
+
+    def flush(self):
+        """The end of the stream (or of a shot the caller knows of): (the pending frames stabilized and cropped, `OnlineReport`), with the
+        paths of `ops.online_pending` -- the last window's solution, beyond which there is nothing to wait for -- through the same limiter,
+        warp and crop as a push's; then the session is left as `reset()` leaves it.  With lag=0, or nothing pending, the empty result: 0
+        frames of the output's dtype and trailing shape and a report with 0-row tensors.  Before the first push, whose frames fix that
+        shape, it is a ValueError."""
+        if self.form is None:
+            raise ValueError('flush before the first push: the frame size and form are not known yet')
+        self._limits = []
+        result = self._flush_part()
+        self.reset()
+        self._join_limits()
+        return result
 
     def _luma_of(self, frames):
         """(form, luma (n, H, W) uint8) of a push, in any form `stabilize_scored` takes."""
@@ -132,7 +163,13 @@ class OnlineSession:
         (`ops.find_cuts` against the signature of the last frame pushed: two small launches and one wait for n integers), the block is
         split at every cut and each part pushed as a plain session would, with `reset()` before each part that begins at a cut -- the pair
         across a cut is never tracked --; the parts' frames and reports come back joined: `first` is the first part's, d_unstab, d_stab and
-        covered are concatenated, `lost` is concatenated in each part's own numbering."""
+        covered are concatenated, `lost` is concatenated in each part's own numbering.
+        lag=k >= 1: what comes back is the frames that have become final with this push, session indices [emitted, seen - k): `first` is
+        the first of them (`emitted` where none came out -- the frames are then a 0-frame tensor, a pair for 4:2:0, of the output's dtype
+        and trailing shape, and the report's tensors have 0 rows), d_unstab, d_stab and covered are theirs, `lost` stays that of the frames
+        PUSHED.  The session keeps its own copies of the frames it still owes: the caller's buffers are free when push returns.  With
+        on_cut='reset' the old shot is flushed before the `reset()` at each cut: its tail comes out of this push, in front of the new
+        shot's frames."""
         import torch
         from . import ops
         if self.form is None and self.on_uncovered == 'limit':
@@ -162,6 +199,8 @@ class OnlineSession:
                 parts = []
                 for lo, hi in zip(starts[:-1], starts[1:]):
                     if lo in cuts:
+                        if self.pending:
+                            parts.append(self._flush_part())              # the old shot's tail, ahead of the new shot's frames
                         self.reset()
                     parts.append(self._push_part(_part(frames, lo, hi), form, luma[lo:hi]))
             except ValueError:
@@ -171,10 +210,7 @@ class OnlineSession:
             if len(parts) == 1:
                 result = parts[0]
             else:
-                outs, reports = [p[0] for p in parts], [p[1] for p in parts]
-                out = tuple(torch.cat([o[i] for o in outs]) for i in range(2)) if form[0] else torch.cat(outs)
-                result = out, OnlineReport(reports[0].first, torch.cat([r.d_unstab for r in reports]), torch.cat([r.d_stab for r in reports]),
-                                           self.rectangle, torch.cat([r.covered for r in reports]), [t for r in reports for t in r.lost])
+                result = self._join(parts)
         self._last_sig, self.last_cuts, self.last_cut_distances = sig, cuts, distances
         self._join_limits()
         return result
@@ -199,12 +235,22 @@ class OnlineSession:
             self.last_limit = self._limits[0] if len(self._limits) == 1 else torch.cat(self._limits)
         self._limits = []
 
+    def _join(self, parts):
+        """Several (frames, report) of one stream in order as one: `first` is the first part's, `lost` in each part's own numbering."""
+        import torch
+        outs, reports = [p[0] for p in parts], [p[1] for p in parts]
+        out = tuple(torch.cat([o[i] for o in outs]) for i in range(2)) if self.form[0] else torch.cat(outs)
+        return out, OnlineReport(reports[0].first, torch.cat([r.d_unstab for r in reports]), torch.cat([r.d_stab for r in reports]),
+                                 self.rectangle, torch.cat([r.covered for r in reports]), [t for r in reports for t in r.lost])
+
     def _snapshot(self):
+        # (the held frames are replaced, never written to: the reference is the snapshot)
         st = self.state
-        return (st.c.clone(), st.q.clone(), st.lam.clone(), st.seen), self._last_luma, self._last_sig, self.shots, self._k_prev
+        return ((st.c.clone(), st.q.clone(), st.lam.clone(), st.seen), self._last_luma, self._last_sig, self.shots, self._k_prev, self._held,
+                self.emitted)
 
     def _restore(self, saved):
-        (c, q, lam, seen), self._last_luma, self._last_sig, self.shots, self._k_prev = saved
+        (c, q, lam, seen), self._last_luma, self._last_sig, self.shots, self._k_prev, self._held, self.emitted = saved
         st = self.state
         st.c.copy_(c), st.q.copy_(q), st.lam.copy_(lam)
         st.seen = seen
@@ -240,10 +286,71 @@ class OnlineSession:
                 lost = [first + k0 + int(b) for b in bad]
             vel[k0:] = d_vel
             lam_known[k0:] = host.adaptive_weights(len(homographies), W, H, self.definition, homographies)
+        if self.lag:
+            c, p = ops.online_smooth_lag(vel, torch.from_numpy(lam_known).to(self.device), self.state, self._taps, self.omega, self.iters,
+                                         self.beta, self._lam_newest, self.lag)
+            self._last_luma = luma[-1].clone()
+            self.shots += int(first == 0)
+            # the frames that became final are the oldest m of (held, new); the rest are held, as copies: the caller's buffers are free.
+            # Every new frame is copied once, into the stack it is held in or the one it is handed out from, and a held frame at most once
+            # more; a held stack is replaced, never written to (`_snapshot` keeps a reference)
+            m = int(c.shape[0])
+            planes = frames if form[0] else (frames,)
+            held = self._held if self._held is not None else tuple(f[:0] for f in planes)
+            h = int(held[0].shape[0])
+            if m <= h:
+                final = tuple(x[:m] for x in held)
+                held = tuple(torch.cat([x[m:], f]) if m < h else f.clone() for x, f in zip(held, planes))
+            else:
+                final = tuple(torch.cat([x, f[:m - h]]) if h else f[:m] for x, f in zip(held, planes))
+                held = tuple(f[m - h:].clone() for f in planes) if m - h < n else None
+            self._held = held
+            if m == 0:
+                return self._nothing(lost)
+            return self._hand_out(final if form[0] else final[0], c, p, lost)
         c, p = ops.online_smooth(vel, torch.from_numpy(lam_known).to(self.device), self.state, self._taps, self.omega, self.iters, self.beta,
                                  self._lam_newest)
         self._last_luma = luma[-1].clone()
         self.shots += int(first == 0)
+        return self._hand_out(frames, c, p, lost)
+
+    def _flush_part(self):
+        """The pending frames of the shot under way with `ops.online_pending`'s paths: (frames out, `OnlineReport`).  Leaves the reset to
+        the caller."""
+        from . import ops
+        if not self.pending:
+            return self._nothing([])
+        c, p = ops.online_pending(self.state, self.lag)
+        held, self._held = self._held, None
+        return self._hand_out(held if self.form[0] else held[0], c, p, [])
+
+    def _nothing(self, lost):
+        """What a push that hands out no frame returns: 0 frames of the output's dtype and trailing shape, a report with 0-row tensors.  No
+        op is called."""
+        import torch
+        s = self.stabilizer
+        pair, dtype, shape = self.form
+        H, W = shape[0], shape[1]
+        whole = self.rectangle == (0, 0, W - 1, H - 1) and self.output_size in (None, (W, H))
+        w, h = (W, H) if whole or self.output_size is None else self.output_size
+        if pair:
+            out = (torch.empty((0, h, w), dtype=dtype, device=self.device), torch.empty((0, h // 2, w // 2, 2), dtype=dtype, device=self.device))
+        else:
+            out = torch.empty((0, h, w) + tuple(shape[2:]), dtype=dtype, device=self.device)
+        if self.on_uncovered == 'limit':
+            self._limits.append(torch.empty(0, dtype=torch.int32, device=self.device))
+        path = torch.empty((0, s.mesh_row_count + 1, s.mesh_col_count + 1, 2), dtype=torch.float64, device=self.device)
+        return out, OnlineReport(self.emitted, path, path.clone(), self.rectangle, torch.empty(0, dtype=torch.bool, device=self.device), lost)
+
+    def _hand_out(self, frames, c, p, lost):
+        """Frames of one shot whose paths are final -- session indices from `emitted` on -- through the limiter, the cell table, the format's
+        warp and the crop-resize: (frames out, `OnlineReport`)."""
+        import torch
+        from . import ops
+        s, form = self.stabilizer, self.form
+        n, (H, W) = int(c.shape[0]), form[2][:2]
+        R, C, first = s.mesh_row_count, s.mesh_col_count, self.emitted
+        self.emitted += n
         if self.on_uncovered == 'limit':
             # (behind the smoother, whose state keeps the unlimited path: blocks of any sizes give the bytes of one push)
             p, k = ops.path_limit(c, p, W, H, R, C, self.rectangle, self.limit_steps, self.limit_guard, self.limit_rise, self._k_prev)

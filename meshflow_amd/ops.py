@@ -977,7 +977,18 @@ def online_smooth(vel, lam_known, state, taps, omega, iters, beta, lam_newest):
     the frame before new frame i; row 0 / entry 0 are not read while the state is empty.  taps: (omega,) float64, `host.online_taps`.
     Returns (c, p): the unstabilized and the stabilized path of the n frames, (n, S) float64; `state` is updated in place.  Runs on
     torch's current stream and does not wait for it."""
-    name = 'online_smooth'
+    n = _online_smooth_args('online_smooth', vel, lam_known, state, taps, omega)
+    c = torch.empty((n, state.S), dtype=torch.float64, device=state.device)
+    p = torch.empty((n, state.S), dtype=torch.float64, device=state.device)
+    _lib.check(_lib_.mf_online_smooth_f64(_ptr(vel), _ptr(lam_known), _ptr(taps), n, state.S, int(omega), state.L, int(iters), float(beta),
+                                          float(lam_newest), state.seen, _ptr(state.c), _ptr(state.q), _ptr(state.lam), _ptr(c), _ptr(p),
+                                          _stream()))
+    state.seen += n
+    return c, p
+
+
+def _online_smooth_args(name, vel, lam_known, state, taps, omega):
+    """What `online_smooth` and `online_smooth_lag` ask of their tensors; returns n."""
     if not isinstance(state, OnlineState):
         raise ValueError(f'{name}: state must be an OnlineState')
     _need(vel, torch.float32, 'vel')
@@ -993,13 +1004,49 @@ def online_smooth(vel, lam_known, state, taps, omega, iters, beta, lam_newest):
     for t, what in ((vel, 'vel'), (lam_known, 'lam_known'), (taps, 'taps')):
         if t.device != state.device:
             raise ValueError(f'{name}: {what} must be on the device of the state, {state.device}, got {t.device}')
+    return n
+
+
+def check_online_lag(lag, L, name='lag'):
+    """`lag` as an int: an int (no bool) in 0 .. L - 1 -- the lagged frame must be in the window, and the state must still hold every frame
+    not yet handed out --, else ValueError."""
+    if isinstance(lag, bool) or not isinstance(lag, (int, np.integer)) or not 0 <= int(lag) <= int(L) - 1:
+        raise ValueError(f'{name} must be an int in 0 .. window - 1 = {int(L) - 1} (got {lag!r})')
+    return int(lag)
+
+
+def online_smooth_lag(vel, lam_known, state, taps, omega, iters, beta, lam_newest, lag):
+    """`online_smooth` with `lag` frames of look-ahead (mf_online_smooth_lag_f64, bit for bit tests/online_lag_model.py): the n new frames
+    are smoothed as `online_smooth` smooths them and leave the same state, but what comes back is each frame as it stands in the window
+    that ends `lag` frames after it -- P_t = x_t of window t + lag after its last sweep, C_t unchanged.  Arguments and checks are
+    `online_smooth`'s; lag: an int (no bool) in 0 .. state.L - 1.  Returns (c, p) of the frames that became final with this block, session
+    indices max(0, seen - lag) .. seen + n - lag - 1: (m, S) float64 with m = max(0, seen + n - lag) - max(0, seen - lag), which is 0 while the
+    session has no more than `lag` frames (the rows of frames that do not exist are dropped).  `online_pending` has the rest when the stream
+    ends.  lag = 0 gives `online_smooth`'s bytes.  Runs on torch's current stream and does not wait for it."""
+    name = 'online_smooth_lag'
+    if not isinstance(state, OnlineState):
+        raise ValueError(f'{name}: state must be an OnlineState')
+    lag = check_online_lag(lag, state.L, f'{name}: lag')
+    n = _online_smooth_args(name, vel, lam_known, state, taps, omega)
     c = torch.empty((n, state.S), dtype=torch.float64, device=state.device)
     p = torch.empty((n, state.S), dtype=torch.float64, device=state.device)
-    _lib.check(_lib_.mf_online_smooth_f64(_ptr(vel), _ptr(lam_known), _ptr(taps), n, state.S, int(omega), state.L, int(iters), float(beta),
-                                          float(lam_newest), state.seen, _ptr(state.c), _ptr(state.q), _ptr(state.lam), _ptr(c), _ptr(p),
-                                          _stream()))
+    _lib.check(_lib_.mf_online_smooth_lag_f64(_ptr(vel), _ptr(lam_known), _ptr(taps), n, state.S, int(omega), state.L, lag, int(iters),
+                                              float(beta), float(lam_newest), state.seen, _ptr(state.c), _ptr(state.q), _ptr(state.lam),
+                                              _ptr(c), _ptr(p), _stream()))
+    drop = min(n, max(0, lag - state.seen))                 # the leading rows whose frame seen + i - lag does not exist
     state.seen += n
-    return c, p
+    return c[drop:], p[drop:]
+
+
+def online_pending(state, lag):
+    """The frames `online_smooth_lag` has not handed out when the stream ends: (c, p), clones of the last min(lag, state.seen) rows of
+    `state.c` / `state.q` -- the final window's solution for frames seen - min(lag, seen) .. seen - 1, oldest first.  No kernel of the
+    library's; the state is left as it is."""
+    if not isinstance(state, OnlineState):
+        raise ValueError('online_pending: state must be an OnlineState')
+    lag = check_online_lag(lag, state.L, 'online_pending: lag')
+    rows = min(lag, state.seen)
+    return state.c[state.L - 1 - rows:].clone(), state.q[state.L - 1 - rows:].clone()
 
 
 CUT_THRESHOLD = 0.30            # a design choice, not a value tuned on footage (profiles/cuts.md)

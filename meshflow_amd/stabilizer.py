@@ -378,7 +378,7 @@ class MeshFlowStabilizer:
     def online_session(self, window=40, iters=10, beta=1.0, crop_margin=0.08, output_size=None,
                        adaptive_weights_definition=ADAPTIVE_WEIGHTS_DEFINITION_ORIGINAL, chunk_pairs=32, max_per_subframe=1024, red_first=False,
                        on_lost='hold', on_cut='ignore', cut_threshold=0.30, on_uncovered='report', limit_steps=32, limit_guard=2.0,
-                       limit_rise=2):
+                       limit_rise=2, lag=0):
         """Stabilization of a stream whose end nobody has seen -- a capture card, a decoder's ring, a clip longer than HBM: an
         `online.OnlineSession` whose `push(frames)` takes one or more new frames in any form `stabilize_scored` takes and returns
         (those frames stabilized and cropped, in the input's form, `online.OnlineReport`) at once, with zero latency.  The reference has no
@@ -407,11 +407,27 @@ class MeshFlowStabilizer:
         smoother's own state keeps the unlimited one, so blocks still equal one push.  The session's `last_limit` is the last push's (n,)
         int32 k on the device; `reset()` and every cut found start k at limit_steps again.  With 'limit' a rectangle that leaves less
         than limit_guard + 1 pixels on its left or top is a ValueError at the first push: no correction would pass.  Frame size and form
-        are fixed by the first push; a later mismatch is a ValueError."""
+        are fixed by the first push; a later mismatch is a ValueError.
+        lag: frames of look-ahead, an int (no bool) in 0 .. window - 1, else ValueError.  0 is the zero-latency session above -- no launch,
+        wait or byte differs from a session without the keyword.  With lag = k >= 1 a frame is handed out k frames after it was pushed,
+        with the path value it has in the window that ends k frames after it (`ops.online_smooth_lag`, mf_online_smooth_lag_f64;
+        tests/online_lag_model.py): on the model's 60-frame random walk five frames of latency halve the residual shake and shrink the
+        correction by a quarter, and the gain saturates at about lag = temporal_smoothing_radius (profiles/online_lag.md; synthetic paths
+        only, nobody has looked at footage).  `push` then returns the frames that have become final, session indices [emitted, seen - k) --
+        possibly none: a 0-frame tensor (a pair for 4:2:0) of the output's dtype and trailing shape, and a report with 0-row tensors --;
+        the report's `first`, d_unstab, d_stab and covered are those frames', `lost` stays that of the frames pushed, and the number of
+        frames out is d_stab.shape[0].  The session keeps the at most k frames it still owes on the device as clones, both planes of a
+        4:2:0 pair, so the caller's buffers are free when push returns; `pending` says how many.  `flush()` ends the stream: it returns
+        (the pending frames, report) with the last window's solution as their path (`ops.online_pending`), through the same limiter, warp
+        and crop, and leaves the session as `reset()` does; over push ... push, flush every pushed frame comes out exactly once, in
+        order, and the joined bytes do not depend on the block sizes.  `reset()` DISCARDS pending frames.  on_cut='reset' flushes the old
+        shot before the reset at each cut: its tail comes out of the same push, in front of the new shot's frames.  on_lost='raise'
+        leaves held frames, `emitted` and the limiter's carry as they were.  The path limit runs on the frames handed out, carrying its
+        step across them in order."""
         from . import online
         return online.OnlineSession(self, window, iters, beta, crop_margin, output_size, adaptive_weights_definition, chunk_pairs,
                                     max_per_subframe, red_first, on_lost, on_cut, cut_threshold, on_uncovered, limit_steps, limit_guard,
-                                    limit_rise)
+                                    limit_rise, lag)
 
     def find_cuts(self, clip, threshold=0.30, red_first=False):
         """Where the shots of a resident clip begin: the list of frame indices t in 1 .. F-1 whose tile-histogram distance to frame t - 1
@@ -427,8 +443,13 @@ class MeshFlowStabilizer:
         return ops.find_cuts(luma, threshold)[0]
 
     def stabilize_online(self, clip, **session):
-        """One `online_session(**session)` and one push of the whole clip: (stabilized and cropped clip, `online.OnlineReport`)."""
-        return self.online_session(**session).push(clip)
+        """One `online_session(**session)` and one push of the whole clip: (stabilized and cropped clip, `online.OnlineReport`).  With
+        lag >= 1 the push and the `flush()` behind it, joined: still the whole clip."""
+        session = self.online_session(**session)
+        result = session.push(clip)
+        if session.lag:
+            result = session._join([result, session.flush()])
+        return result
 
     def _write_stabilized_video(self, output_path, num_frames, frames_per_second, codec, stabilized_frames):
         """mfs.py:1290-1322."""
