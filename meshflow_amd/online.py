@@ -4,15 +4,15 @@ The offline path needs a whole clip twice: `ops.jacobi` smooths every vertex pat
 reduction.  A session replaces the first by `ops.online_smooth` -- a sliding window that ends at the newest frame (include/meshflow_hip.h,
 mf_online_smooth_f64; tests/online_model.py) -- and the second by a rectangle fixed in advance from `crop_margin`.  Everything else is the
 offline path's own: `ops.luma`, the device tracker with the outlier step and the fit on the device, `ops.vertex_motion`, `ops.cell_table`,
-the format's warp and crop-resize.  What a session carries between pushes: the previous push's last luma frame, an `ops.OnlineState`, --
-with on_cut='reset' -- that frame's scene-cut signature (`ops.find_cuts`; tests/cuts_model.py), by which a push finds the cuts in its frames
-and restarts the path at each, and -- with on_uncovered='limit' -- the last frame's step of `ops.path_limit` (tests/path_limit_model.py), which
-scales a frame's correction back until the warped mesh covers the fixed rectangle again.
+the format's warp and crop-resize (`ClipForm`).  What a session carries between pushes is listed once, in `_CARRIED`: the previous push's
+last luma frame, an `ops.OnlineState`, -- with on_cut='reset' -- that frame's scene-cut signature (`ops.find_cuts`; tests/cuts_model.py), by
+which a push finds the cuts in its frames and restarts the path at each, and -- with on_uncovered='limit' -- the last frame's step of
+`ops.path_limit` (tests/path_limit_model.py), which scales a frame's correction back until the warped mesh covers the fixed rectangle again.
 
 lag=k >= 1 trades k frames of latency for a smoother path (profiles/online_lag.md): the smoother is `ops.online_smooth_lag`
 (mf_online_smooth_lag_f64; tests/online_lag_model.py), which hands a frame out as it stands in the window that ends k frames after it, so a
 push returns the frames that have become final, [emitted, seen - k), and the session also carries the pixels of the at most k frames it still
-owes, as clones on the device.  `flush()` hands those out when the stream -- or, with on_cut='reset', a shot -- ends."""
+owes, as clones on the device (`hold_frames`).  `flush()` hands those out when the stream -- or, with on_cut='reset', a shot -- ends."""
 import collections
 import math
 
@@ -38,25 +38,84 @@ def margin_rectangle(crop_margin, W, H):
     return left, top, right, bottom
 
 
+class ClipForm(collections.namedtuple('ClipForm', 'fmt dtype shape')):
+    """The form of a clip, whatever its length: fmt, the `ops._Format420` row of a 4:2:0 pair (d_y, d_uv) or None for a stack (n, ...);
+    the dtype; the shape of a frame -- of a luma plane for a pair.  Two clips of one form compare equal."""
+    pair = property(lambda self: self.fmt is not None)
+
+    def planes(self, clip):
+        """The clip's plane stacks as a tuple: two for a pair, the stack itself otherwise; `clip(planes)` puts them back."""
+        return tuple(clip) if self.pair else (clip,)
+
+    def clip(self, planes):
+        return tuple(planes) if self.pair else planes[0]
+
+    def part(self, clip, lo, hi):
+        return self.clip([p[lo:hi] for p in self.planes(clip)])
+
+    def cat(self, clips):
+        import torch
+        return self.clip([torch.cat(planes) for planes in zip(*(self.planes(c) for c in clips))])
+
+    def warp_crop(self, clip, table, border_bgr, crop):
+        """The format's warp from `table` -- border_bgr for a stack, the format's red for a pair -- and, unless `crop` is None, its
+        crop-resize to crop = (rectangle, output size or None)."""
+        from . import ops
+        if self.pair:
+            out = ops._warp_420(self.fmt, *clip, table, ops.P010_BORDER_RED if self.fmt is ops._P010 else ops.NV12_BORDER_RED, None, None)
+            return out if crop is None else ops._crop_resize_420(self.fmt, out[0], out[1], crop[0], crop[1], None, None)
+        out = ops.warp(clip, table, border_bgr)
+        return out if crop is None else ops.crop_resize(out, crop[0], size=crop[1])
+
+    def empty(self, w, h, device):
+        """0 frames of this form at w x h."""
+        import torch
+        shapes = ((h, w), (h // 2, w // 2, 2)) if self.pair else ((h, w) + self.shape[2:],)
+        return self.clip([torch.empty((0,) + shape, dtype=self.dtype, device=device) for shape in shapes])
+
+
 def luma_of(frames, red_first=False):
-    """(form, luma (n, H, W) uint8) of a clip in any form `stabilize_scored` takes; form = (pair?, dtype, frame shape)."""
+    """(form, luma (n, H, W) uint8) of a clip in any form `stabilize_scored` takes; form: its `ClipForm`."""
     import torch
     from . import ops
     if isinstance(frames, (tuple, list)):
         if len(frames) != 2:
             raise ValueError('an NV12 or P010 clip is the pair (d_y, d_uv)')
         d_y, d_uv = frames
-        fmt = ops._P010 if isinstance(d_y, torch.Tensor) and d_y.dtype == torch.uint16 else ops._NV12
+        fmt = {torch.uint16: ops._P010}.get(getattr(d_y, 'dtype', None), ops._NV12)         # (whatever is neither fails NV12's checks)
         ops._need_420(fmt, d_y, d_uv)
-        return (True, d_y.dtype, tuple(d_y.shape[1:])), (ops.luma(d_y) if fmt is ops._P010 else d_y)
+        return ClipForm(fmt, d_y.dtype, tuple(d_y.shape[1:])), (ops.luma(d_y) if fmt is ops._P010 else d_y)
     if isinstance(frames, torch.Tensor) and frames.dtype == torch.uint16 and frames.dim() == 3:
         raise ValueError('a (n, H, W) uint16 stack is the luma plane of a P010 clip: pass the pair (d_y, d_uv)')
     ops._frames_format(frames)
-    return (False, frames.dtype, tuple(frames.shape[1:])), (ops.luma(frames, red_first) if ops.luma_source(frames) is not None else frames)
+    return ClipForm(None, frames.dtype, tuple(frames.shape[1:])), (ops.luma(frames, red_first) if ops.luma_source(frames) is not None else frames)
 
 
-def _part(frames, lo, hi):
-    return tuple(p[lo:hi] for p in frames) if isinstance(frames, (tuple, list)) else frames[lo:hi]
+def hold_frames(held, planes, m):
+    """The pixels of a lagged push: of the frames (held, then new) the oldest m are final and the rest are held.  held: a tuple of plane
+    stacks or None; planes: the caller's new ones, as many; returns (final planes, new held planes or None: none).  With nothing held,
+    `final` is the caller's planes or a view of them, no copy; what is held is a copy -- the caller's buffers are free --; every new frame is copied once,
+    into the stack it is held in or the one it is handed out from, and a held frame at most once more; an old held stack is never written
+    to.  Any torch tensors; no session is touched."""
+    import torch
+    n = int(planes[0].shape[0])
+    if held is None:
+        return (planes if m == n else tuple(f[:m] for f in planes)), (tuple(f[m:].clone() for f in planes) if m < n else None)
+    h = int(held[0].shape[0])
+    if m <= h:
+        return tuple(x[:m] for x in held), tuple(torch.cat([x[m:], f]) if m < h else f.clone() for x, f in zip(held, planes))
+    return tuple(torch.cat([x, f[:m - h]]) for x, f in zip(held, planes)), (tuple(f[m - h:].clone() for f in planes) if m - h < n else None)
+
+
+# What a shot carries from push to push beside the `ops.OnlineState` (its tensors and `seen`), and what each starts from: the one list
+# that the constructor, `reset()`, `_snapshot()` and `_restore()` go by.
+#   _last_luma: the last luma frame pushed, the early frame of the next push's first pair;
+#   _last_sig:  on_cut='reset': that frame's scene-cut signature;
+#   _k_prev:    on_uncovered='limit': the limiter's k of the last frame handed out, a 1-element int32 device tensor (None: k starts at K);
+#   _held:      lag >= 1: the input frames not handed out yet, oldest first, as a tuple of the input's planes (`hold_frames`);
+#   emitted:    how many frames of the path begun at the last reset have been handed out.
+# Every one is REPLACED, never written to -- and so are the tensors behind them --, which is why a snapshot keeps references, not clones.
+_CARRIED = {'_last_luma': None, '_last_sig': None, '_k_prev': None, '_held': None, 'emitted': 0}
 
 
 class OnlineSession:
@@ -89,23 +148,19 @@ class OnlineSession:
         self.on_uncovered = on_uncovered
         self.limit_steps, self.limit_guard, self.limit_rise = ops.check_path_limit(limit_steps, limit_guard, limit_rise,
                                                                                    ('limit_steps', 'limit_guard', 'limit_rise'))
-        # on_uncovered='limit': the last k of the part before (a 1-element int32 device tensor; None: no frame came before, k starts at K),
-        # the k of the parts of the push under way, and the last push's (n,) int32 k on the device
-        self._k_prev, self._limits, self.last_limit = None, [], None
+        self.last_limit = None        # on_uncovered='limit': the last push's (n,) int32 k on the device
         self.on_cut, self.cut_threshold = on_cut, ops.check_cut_threshold(cut_threshold, 'cut_threshold')
         self.stabilizer, self.window, self.omega, self.iters, self.beta = stabilizer, int(window), omega, int(iters), float(beta)
         self.crop_margin, self.output_size, self.definition = crop_margin, output_size, adaptive_weights_definition
         self.chunk_pairs, self.red_first, self.on_lost = chunk_pairs, red_first, on_lost
         self.device = stabilizer._torch_device()
         self.tracker = stabilizer.device_tracker(max_per_subframe, 'device', 'device')
-        self.form = None              # (pair?, dtype, frame shape) of the first push; the rectangle and the state follow from it
-        self.rectangle = self.state = self._last_luma = self._last_sig = self._taps = self._lam_newest = None
+        # fixed by the first push (`_start`): its `ClipForm`, the rectangle, the output's (width, height), `ClipForm.warp_crop`'s crop, the state
+        self.form = self.rectangle = self._out_size = self._crop = self.state = self._taps = self._lam_newest = None
         # shots: the shots begun so far (the first frame, every frame after a `reset()`, every cut found); last_cuts: the indices, relative to
         # the last push, of its frames that started a shot, and last_cut_distances: that push's (n,) int32 distances -- on_cut='reset' only
         self.shots, self.last_cuts, self.last_cut_distances = 0, [], None
-        # lag >= 1: the input frames not handed out yet, oldest first, as a tuple of the input's planes (one for a stack, two for a 4:2:0
-        # pair; the session's own copies; None: none), and how many frames of the path begun at the last reset have been handed out
-        self._held, self.emitted = None, 0
+        self.reset()
 
     @property
     def seen(self):
@@ -122,8 +177,17 @@ class OnlineSession:
         pending frames are DISCARDED, pixels and all: `flush()` first hands them out."""
         if self.state is not None:
             self.state.reset()
-        self._last_luma = self._last_sig = self._k_prev = self._held = None
-        self.emitted = 0
+        vars(self).update(_CARRIED)
+
+    def _snapshot(self):
+        st = self.state
+        return [getattr(self, name) for name in _CARRIED], self.shots, (st.c.clone(), st.q.clone(), st.lam.clone(), st.seen)
+
+    def _restore(self, saved):
+        st = self.state
+        carried, self.shots, (c, q, lam, st.seen) = saved
+        vars(self).update(zip(_CARRIED, carried))
+        st.c.copy_(c), st.q.copy_(q), st.lam.copy_(lam)
 
     def flush(self):
         """The end of the stream (or of a shot the caller knows of): (the pending frames stabilized and cropped, `OnlineReport`), with the
@@ -133,28 +197,24 @@ class OnlineSession:
         shape, it is a ValueError."""
         if self.form is None:
             raise ValueError('flush before the first push: the frame size and form are not known yet')
-        self._limits = []
-        result = self._flush_part()
+        parts = [self._flush_part()]
         self.reset()
-        self._join_limits()
-        return result
-
-    def _luma_of(self, frames):
-        """(form, luma (n, H, W) uint8) of a push, in any form `stabilize_scored` takes."""
-        return luma_of(frames, self.red_first)
+        return self._result(parts)
 
     def _start(self, form, H, W):
         import torch
         from . import ops
-        pair = form[0]
         if self.output_size is not None:
-            self.output_size = (ops._even_output_size if pair else ops.check_output_size)(self.output_size, 'output_size')
+            self.output_size = (ops._even_output_size if form.pair else ops.check_output_size)(self.output_size, 'output_size')
         rectangle = margin_rectangle(self.crop_margin, W, H)
         s = self.stabilizer
         self.state = ops.OnlineState((s.mesh_row_count + 1) * (s.mesh_col_count + 1) * 2, self.window, self.device)
         self._taps = torch.from_numpy(host.online_taps(self.omega)).to(self.device)
         # the weight of the newest frame: the identity homography's under the chosen definition (mfs.py:273-274, 757)
         self._lam_newest = float(host.adaptive_weights(1, W, H, self.definition, np.identity(3)[None])[0])
+        whole = rectangle == (0, 0, W - 1, H - 1) and self.output_size in (None, (W, H))
+        self._crop = None if whole else (rectangle, self.output_size)
+        self._out_size = (W, H) if whole or self.output_size is None else self.output_size
         self.form, self.rectangle = form, rectangle
 
     def push(self, frames):
@@ -162,35 +222,30 @@ class OnlineSession:
         (the same n frames stabilized and cropped, in the input's form, `OnlineReport`).  on_cut='reset': the frames are scored first
         (`ops.find_cuts` against the signature of the last frame pushed: two small launches and one wait for n integers), the block is
         split at every cut and each part pushed as a plain session would, with `reset()` before each part that begins at a cut -- the pair
-        across a cut is never tracked --; the parts' frames and reports come back joined: `first` is the first part's, d_unstab, d_stab and
-        covered are concatenated, `lost` is concatenated in each part's own numbering.
+        across a cut is never tracked --; the parts' frames and reports come back joined (`join`): `first` is the first part's, d_unstab,
+        d_stab and covered are concatenated, `lost` is concatenated in each part's own numbering.
         lag=k >= 1: what comes back is the frames that have become final with this push, session indices [emitted, seen - k): `first` is
         the first of them (`emitted` where none came out -- the frames are then a 0-frame tensor, a pair for 4:2:0, of the output's dtype
         and trailing shape, and the report's tensors have 0 rows), d_unstab, d_stab and covered are theirs, `lost` stays that of the frames
         PUSHED.  The session keeps its own copies of the frames it still owes: the caller's buffers are free when push returns.  With
         on_cut='reset' the old shot is flushed before the `reset()` at each cut: its tail comes out of this push, in front of the new
         shot's frames."""
-        import torch
         from . import ops
         if self.form is None and self.on_uncovered == 'limit':
             self._check_limit_fits(frames)
-        self._limits = []
-        form, luma = self._luma_of(frames)
+        form, luma = luma_of(frames, self.red_first)
         n, H, W = (int(v) for v in luma.shape)
         if n < 1:
             raise ValueError('push needs at least one frame')
         if self.form is None:
             self._start(form, H, W)
         elif form != self.form:
-            raise ValueError(f'this session takes {self.form[1]} frames of shape {self.form[2]}{" as (d_y, d_uv) pairs" if self.form[0] else ""}; '
-                             f'got {form[1]} frames of shape {form[2]}{" as a pair" if form[0] else ""}')
-        if self.on_cut == 'ignore':
-            result = self._push_part(frames, form, luma)
-            self._join_limits()
-            return result
-        cuts, distances, sig = ops.find_cuts(luma, self.cut_threshold, self._last_sig)
+            raise ValueError(f'this session takes {self.form.dtype} frames of shape {self.form.shape}{" as (d_y, d_uv) pairs" if self.form.pair else ""}; '
+                             f'got {form.dtype} frames of shape {form.shape}{" as a pair" if form.pair else ""}')
+        # (what on_cut='ignore' puts in their place is what the three members hold from the start: nothing is looked for)
+        cuts, distances, sig = ops.find_cuts(luma, self.cut_threshold, self._last_sig) if self.on_cut == 'reset' else ([], None, None)
         if not cuts:
-            result = self._push_part(frames, form, luma)
+            parts = [self._push_part(frames, luma)]
         else:
             starts = sorted({0, *cuts}) + [n]
             # on_lost='raise' promises the session as it was: a part may fail after an earlier one, or a reset, has changed it
@@ -202,22 +257,17 @@ class OnlineSession:
                         if self.pending:
                             parts.append(self._flush_part())              # the old shot's tail, ahead of the new shot's frames
                         self.reset()
-                    parts.append(self._push_part(_part(frames, lo, hi), form, luma[lo:hi]))
+                    parts.append(self._push_part(form.part(frames, lo, hi), luma[lo:hi]))
             except ValueError:
                 if saved is not None:
                     self._restore(saved)
                 raise
-            if len(parts) == 1:
-                result = parts[0]
-            else:
-                result = self._join(parts)
         self._last_sig, self.last_cuts, self.last_cut_distances = sig, cuts, distances
-        self._join_limits()
-        return result
+        return self._result(parts)
 
     def _check_limit_fits(self, frames):
-        """on_uncovered='limit', before the first push touches the device: the rectangle widened by the guard must lie inside the untouched
-        frame with a pixel to spare, or no candidate could pass and every frame would come back unstabilized."""
+        """on_uncovered='limit', before the first push touches the device -- or has a form --: the rectangle widened by the guard must lie
+        inside the untouched frame with a pixel to spare, or no candidate could pass and every frame would come back unstabilized."""
         first = frames[0] if isinstance(frames, (tuple, list)) and len(frames) == 2 else frames
         shape = getattr(first, 'shape', ())
         if len(shape) < 3:
@@ -229,34 +279,23 @@ class OnlineSession:
                              f'{W} x {H} frame, limit_guard={self.limit_guard} needs {self.limit_guard + 1:g} on every side: no correction would '
                              'pass; widen crop_margin')
 
-    def _join_limits(self):
+    def _result(self, parts):
+        """What a push or a flush returns from its parts (frames, report, k), in order; on_uncovered='limit': their k is `last_limit`."""
         import torch
         if self.on_uncovered == 'limit':
-            self.last_limit = self._limits[0] if len(self._limits) == 1 else torch.cat(self._limits)
-        self._limits = []
+            self.last_limit = parts[0][2] if len(parts) == 1 else torch.cat([k for _, _, k in parts])
+        return parts[0][:2] if len(parts) == 1 else self.join([p[:2] for p in parts])
 
-    def _join(self, parts):
-        """Several (frames, report) of one stream in order as one: `first` is the first part's, `lost` in each part's own numbering."""
+    def join(self, parts):
+        """Several (frames, report) of this session's stream in order as one: `first` is the first part's, `lost` in each part's own
+        numbering."""
         import torch
-        outs, reports = [p[0] for p in parts], [p[1] for p in parts]
-        out = tuple(torch.cat([o[i] for o in outs]) for i in range(2)) if self.form[0] else torch.cat(outs)
-        return out, OnlineReport(reports[0].first, torch.cat([r.d_unstab for r in reports]), torch.cat([r.d_stab for r in reports]),
-                                 self.rectangle, torch.cat([r.covered for r in reports]), [t for r in reports for t in r.lost])
+        d_unstab, d_stab, covered = (torch.cat([getattr(r, field) for _, r in parts]) for field in ('d_unstab', 'd_stab', 'covered'))
+        return self.form.cat([out for out, _ in parts]), OnlineReport(parts[0][1].first, d_unstab, d_stab, self.rectangle, covered,
+                                                                      [t for _, r in parts for t in r.lost])
 
-    def _snapshot(self):
-        # (the held frames are replaced, never written to: the reference is the snapshot)
-        st = self.state
-        return ((st.c.clone(), st.q.clone(), st.lam.clone(), st.seen), self._last_luma, self._last_sig, self.shots, self._k_prev, self._held,
-                self.emitted)
-
-    def _restore(self, saved):
-        (c, q, lam, seen), self._last_luma, self._last_sig, self.shots, self._k_prev, self._held, self.emitted = saved
-        st = self.state
-        st.c.copy_(c), st.q.copy_(q), st.lam.copy_(lam)
-        st.seen = seen
-
-    def _push_part(self, frames, form, luma):
-        """A run of frames of one shot through the session: (frames out, `OnlineReport`)."""
+    def _push_part(self, frames, luma):
+        """A run of frames of one shot through the session: (frames out, `OnlineReport`, the limiter's k or None)."""
         import torch
         from . import _lib, ops
         s = self.stabilizer
@@ -286,90 +325,51 @@ class OnlineSession:
                 lost = [first + k0 + int(b) for b in bad]
             vel[k0:] = d_vel
             lam_known[k0:] = host.adaptive_weights(len(homographies), W, H, self.definition, homographies)
-        if self.lag:
-            c, p = ops.online_smooth_lag(vel, torch.from_numpy(lam_known).to(self.device), self.state, self._taps, self.omega, self.iters,
-                                         self.beta, self._lam_newest, self.lag)
-            self._last_luma = luma[-1].clone()
-            self.shots += int(first == 0)
-            # the frames that became final are the oldest m of (held, new); the rest are held, as copies: the caller's buffers are free.
-            # Every new frame is copied once, into the stack it is held in or the one it is handed out from, and a held frame at most once
-            # more; a held stack is replaced, never written to (`_snapshot` keeps a reference)
-            m = int(c.shape[0])
-            planes = frames if form[0] else (frames,)
-            held = self._held if self._held is not None else tuple(f[:0] for f in planes)
-            h = int(held[0].shape[0])
-            if m <= h:
-                final = tuple(x[:m] for x in held)
-                held = tuple(torch.cat([x[m:], f]) if m < h else f.clone() for x, f in zip(held, planes))
-            else:
-                final = tuple(torch.cat([x, f[:m - h]]) if h else f[:m] for x, f in zip(held, planes))
-                held = tuple(f[m - h:].clone() for f in planes) if m - h < n else None
-            self._held = held
-            if m == 0:
-                return self._nothing(lost)
-            return self._hand_out(final if form[0] else final[0], c, p, lost)
-        c, p = ops.online_smooth(vel, torch.from_numpy(lam_known).to(self.device), self.state, self._taps, self.omega, self.iters, self.beta,
-                                 self._lam_newest)
+        block = (vel, torch.from_numpy(lam_known).to(self.device), self.state, self._taps, self.omega, self.iters, self.beta, self._lam_newest)
+        c, p = ops.online_smooth_lag(*block, self.lag) if self.lag else ops.online_smooth(*block)
         self._last_luma = luma[-1].clone()
         self.shots += int(first == 0)
-        return self._hand_out(frames, c, p, lost)
+        # the frames that became final are the oldest of (held, new); without a lag that is the caller's frames, and nothing is held
+        final, self._held = hold_frames(self._held, self.form.planes(frames), int(c.shape[0]))
+        return self._hand_out(self.form.clip(final), c, p, lost) if c.shape[0] else self._nothing(lost)
 
     def _flush_part(self):
-        """The pending frames of the shot under way with `ops.online_pending`'s paths: (frames out, `OnlineReport`).  Leaves the reset to
-        the caller."""
+        """The pending frames of the shot under way with `ops.online_pending`'s paths: (frames out, `OnlineReport`, k or None).  Leaves
+        the reset to the caller."""
         from . import ops
         if not self.pending:
             return self._nothing([])
         c, p = ops.online_pending(self.state, self.lag)
         held, self._held = self._held, None
-        return self._hand_out(held if self.form[0] else held[0], c, p, [])
+        return self._hand_out(self.form.clip(held), c, p, [])
 
     def _nothing(self, lost):
-        """What a push that hands out no frame returns: 0 frames of the output's dtype and trailing shape, a report with 0-row tensors.  No
-        op is called."""
+        """What a part that hands out no frame returns: 0 frames of the output's dtype and trailing shape, a report with 0-row tensors,
+        0 steps of the limiter.  No op is called."""
         import torch
         s = self.stabilizer
-        pair, dtype, shape = self.form
-        H, W = shape[0], shape[1]
-        whole = self.rectangle == (0, 0, W - 1, H - 1) and self.output_size in (None, (W, H))
-        w, h = (W, H) if whole or self.output_size is None else self.output_size
-        if pair:
-            out = (torch.empty((0, h, w), dtype=dtype, device=self.device), torch.empty((0, h // 2, w // 2, 2), dtype=dtype, device=self.device))
-        else:
-            out = torch.empty((0, h, w) + tuple(shape[2:]), dtype=dtype, device=self.device)
-        if self.on_uncovered == 'limit':
-            self._limits.append(torch.empty(0, dtype=torch.int32, device=self.device))
+        k = torch.empty(0, dtype=torch.int32, device=self.device) if self.on_uncovered == 'limit' else None
         path = torch.empty((0, s.mesh_row_count + 1, s.mesh_col_count + 1, 2), dtype=torch.float64, device=self.device)
-        return out, OnlineReport(self.emitted, path, path.clone(), self.rectangle, torch.empty(0, dtype=torch.bool, device=self.device), lost)
+        return (self.form.empty(*self._out_size, self.device),
+                OnlineReport(self.emitted, path, path.clone(), self.rectangle, torch.empty(0, dtype=torch.bool, device=self.device), lost), k)
 
     def _hand_out(self, frames, c, p, lost):
         """Frames of one shot whose paths are final -- session indices from `emitted` on -- through the limiter, the cell table, the format's
-        warp and the crop-resize: (frames out, `OnlineReport`)."""
-        import torch
+        warp and the crop-resize: (frames out, `OnlineReport`, the limiter's k or None)."""
         from . import ops
-        s, form = self.stabilizer, self.form
-        n, (H, W) = int(c.shape[0]), form[2][:2]
-        R, C, first = s.mesh_row_count, s.mesh_col_count, self.emitted
+        s = self.stabilizer
+        n, (H, W) = int(c.shape[0]), self.form.shape[:2]
+        R, C, first, k = s.mesh_row_count, s.mesh_col_count, self.emitted, None
         self.emitted += n
         if self.on_uncovered == 'limit':
             # (behind the smoother, whose state keeps the unlimited path: blocks of any sizes give the bytes of one push)
             p, k = ops.path_limit(c, p, W, H, R, C, self.rectangle, self.limit_steps, self.limit_guard, self.limit_rise, self._k_prev)
             self._k_prev = k[-1:]
-            self._limits.append(k)
         table = ops.cell_table(c, p, W, H, R, C)
-        left, top, right, bottom = self.rectangle
-        whole = (left, top, right, bottom) == (0, 0, W - 1, H - 1) and self.output_size in (None, (W, H))
-        if form[0]:
-            fmt = ops._P010 if form[1] == torch.uint16 else ops._NV12
-            out = ops._warp_420(fmt, frames[0], frames[1], table, ops.P010_BORDER_RED if fmt is ops._P010 else ops.NV12_BORDER_RED, None, None)
-            if not whole:
-                out = ops._crop_resize_420(fmt, out[0], out[1], self.rectangle, self.output_size, None, None)
-        else:
-            out = ops.warp(frames, table, s.color_outside_image_area_bgr)
-            if not whole:
-                out = ops.crop_resize(out, self.rectangle, size=self.output_size)
+        out = self.form.warp_crop(frames, table, s.color_outside_image_area_bgr, self._crop)
         table.check()
         crop = table.crop
+        left, top, right, bottom = self.rectangle
         covered = (crop[:, 0] <= left) & (crop[:, 1] <= top) & (crop[:, 2] >= right) & (crop[:, 3] >= bottom)
         shape = (n, R + 1, C + 1, 2)
-        return out, OnlineReport(first, c.view(shape), p.view(shape), self.rectangle, covered, lost)
+        return out, OnlineReport(first, c.view(shape), p.view(shape), self.rectangle, covered, lost), k

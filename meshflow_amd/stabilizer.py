@@ -338,27 +338,18 @@ class MeshFlowStabilizer:
         """The reference's stabilize() between decoder and encoder (mfs.py:140-169) for a resident clip, without OpenCV: `clip` is an
         (F, H, W) uint8 grey tensor, (F, H, W, 3) uint8 or uint16 BGR frames, (F, H, W, 4) uint8 BGRA frames (red_first: RGB / RGBA), an NV12
         pair (d_y (F, H, W), d_uv (F, H/2, W/2, 2)) of uint8 or a P010 pair of the same shapes of uint16 -- the pair's dtype tells the two
-        apart.  In order: the clip's luma (itself for grey and NV12, `ops.luma` otherwise); `estimate_motion(luma, outliers='device',
-        fit='device')`; `stabilize_resident(crop=True)` on the frames, `stabilized_nv12(crop=True)` or `stabilized_p010_cropped` on the
-        pair; the luma of the cropped clip in the same way; `cropping_and_distortion_resident(luma, cropped luma)`;
+        apart.  In order: the clip's form and luma (`online.luma_of`: itself for grey and NV12, `ops.luma` otherwise);
+        `estimate_motion(luma, outliers='device', fit='device')`; `stabilize_resident(crop=True)` on the frames, `stabilized_nv12(crop=True)`
+        or `stabilized_p010_cropped` on the pair; the luma of the cropped clip in the same way; `cropping_and_distortion_resident(luma, cropped luma)`;
         `_compute_stability_score_device` on the stabilized vertex paths.  Returns (the cropped clip in the input's form,
         (cropping_ratio, distortion_score, stability_score)) -- the reference's order, mfs.py:169; the first two np.float32, the third a
         float.  Every ValueError of those calls is this one's."""
-        import torch
-        from . import ops
-        pair = isinstance(clip, (tuple, list))
-        if pair:
-            if len(clip) != 2:
-                raise ValueError('an NV12 or P010 clip is the pair (d_y, d_uv)')
-            d_y, d_uv = clip
-            deep = isinstance(d_y, torch.Tensor) and d_y.dtype == torch.uint16
-            luma = ops.luma(d_y) if deep else d_y
-        else:
-            if isinstance(clip, torch.Tensor) and clip.dtype == torch.uint16 and clip.dim() == 3:
-                raise ValueError('a (F, H, W) uint16 stack is the luma plane of a P010 clip: pass the pair (d_y, d_uv)')
-            luma = ops.luma(clip, red_first) if ops.luma_source(clip) is not None else clip
+        from . import online, ops
+        form, luma = online.luma_of(clip, red_first)
         d_disp, homographies = self.estimate_motion(luma, chunk_pairs, max_per_subframe, outliers='device', fit='device')
-        if pair:
+        if form.pair:
+            d_y, d_uv = clip
+            deep = form.fmt is ops._P010
             if deep:
                 out_y, out_uv, _ = self.stabilized_p010_cropped(d_y, d_uv, d_disp, homographies,
                                                                 adaptive_weights_definition=adaptive_weights_definition)
@@ -448,7 +439,7 @@ class MeshFlowStabilizer:
         session = self.online_session(**session)
         result = session.push(clip)
         if session.lag:
-            result = session._join([result, session.flush()])
+            result = session.join([result, session.flush()])
         return result
 
     def _write_stabilized_video(self, output_path, num_frames, frames_per_second, codec, stabilized_frames):

@@ -1,6 +1,5 @@
-"""What the scene-cut tests share, restated here so that no test module imports another: scene A, the ten 128 x 96 frames of
-tests/test_gpu_online_session.py's `grey_clip()` (canvas seed 21); scene B, the same ten offsets cut from another canvas (seed 77) made darker
-by 60 levels; and the clips with cuts made of the two."""
+"""What the scene-cut tests share: scene A, the ten 128 x 96 frames of tests/online_clips.py's `grey_clip()` (canvas seed 21); scene B, the same
+ten offsets cut from another canvas (seed 77) made darker by 60 levels; and the clips with cuts made of the two."""
 import os
 import sys
 
@@ -8,22 +7,11 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import tracker_clip  # noqa: E402
-from tracker_clip import SHIFTS  # noqa: E402
-
-W, H = 128, 96
-MORE_SHIFTS = ((-3, 2), (2, -4), (-5, 3), (4, 1))
-
-
-def _cut_from(big):
-    ox, oy, frames = 20, 20, []
-    for dx, dy in ((0, 0),) + SHIFTS + MORE_SHIFTS:
-        ox, oy = ox - dx, oy - dy
-        frames.append(np.ascontiguousarray(big[oy:oy + H, ox:ox + W]))
-    return np.stack(frames)
+from online_clips import H, W, cut_from as _cut_from, grey_clip  # noqa: E402,F401
 
 
 def scene_a():
-    return _cut_from(tracker_clip.canvas(140, 170, 21, boxes=160))
+    return grey_clip()
 
 
 def scene_b():

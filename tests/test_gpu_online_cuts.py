@@ -13,12 +13,12 @@ import cuts_model as cm  # noqa: E402
 import luma_clip  # noqa: E402
 import luma_model  # noqa: E402
 import tracker_clip  # noqa: E402
-from tracker_clip import MAX_PER, stabilizer  # noqa: E402
+from online_clips import SESSION, forms, part, planes, to_dev  # noqa: E402
+from tracker_clip import stabilizer  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 W, H = cuts_clip.W, cuts_clip.H
-SESSION = dict(window=4, iters=6, beta=1.0, crop_margin=0.08, max_per_subframe=MAX_PER)         # tests/test_gpu_online_session.py's
 FORMS = ['grey', 'bgr', 'nv12']
 
 
@@ -28,26 +28,6 @@ def dev():
     if not torch.cuda.is_available():
         pytest.fail('no GPU visible: the -m gpu tests must run on an MI355X')
     return torch.device('cuda:0')
-
-
-def forms(g):
-    uv = luma_clip._noise((len(g), H // 2, W // 2, 2), 256, 35).astype(np.uint8)
-    return {'grey': g, 'bgr': luma_clip.bgr(g), 'nv12': (g, uv), 'bgr16': luma_clip.bgr16(g), 'bgra': luma_clip.bgra(g), 'p010': luma_clip.p010(g)}
-
-
-def to_dev(clip, dev):
-    import torch
-    if isinstance(clip, tuple):
-        return tuple(torch.from_numpy(np.ascontiguousarray(p)).to(dev) for p in clip)
-    return torch.from_numpy(np.ascontiguousarray(clip)).to(dev)
-
-
-def part(clip, lo, hi):
-    return tuple(p[lo:hi] for p in clip) if isinstance(clip, tuple) else clip[lo:hi]
-
-
-def planes(frames):
-    return [p.cpu().numpy() for p in frames] if isinstance(frames, tuple) else [frames.cpu().numpy()]
 
 
 @pytest.fixture(scope='module')

@@ -1,5 +1,5 @@
 """`online_session(lag=k)` and `OnlineSession.flush()` against the composition of the ops written out by hand -- `ops.online_smooth_lag` and
-`ops.online_pending` into the cell table, the warp and the crop-resize -- on tests/test_gpu_online_session.py's ten 128 x 96 frames: every form,
+`ops.online_pending` into the cell table, the warp and the crop-resize -- on tests/online_clips.py's ten 128 x 96 frames: every form,
 blocks against one push, pushes that hand out nothing, the path limit, cuts, a refused push, reset, and the promise that lag=0 is the session
 without the keyword."""
 import os
@@ -11,14 +11,21 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import cuts_clip  # noqa: E402
 import cuts_model as cm  # noqa: E402
-import test_gpu_online_limit as limit_tests  # noqa: E402
-from test_gpu_online_session import (BETA, C, H, ITERS, MARGIN, R, S, SESSION, W, WINDOW, dev, forms, grey_clip, host_of, part,  # noqa: E402,F401
-                                     rectangle, same_frames, to_dev)
+from online_clips import (BETA, GUARD, ITERS, LIMIT_SESSION, MARGIN, RISE, SESSION, WINDOW, C, H, K, R, S, W, forms, grey_clip,  # noqa: E402
+                          limit_stabilizer, part, rectangle, same_frames, shaky_clip, to_dev)
 from tracker_clip import MAX_PER, same_bits, stabilizer  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 N, LAG = 10, 2
+
+
+@pytest.fixture(scope='module')
+def dev():
+    torch = pytest.importorskip('torch')
+    if not torch.cuda.is_available():
+        pytest.fail('no GPU visible: the -m gpu tests must run on an MI355X')
+    return torch.device('cuda:0')
 
 
 def run(session, clip, blocks, flush=True):
@@ -221,20 +228,20 @@ def test_the_largest_lag(dev, clips):
 
 
 def test_the_path_limit_runs_on_the_frames_handed_out(dev):
-    """tests/test_gpu_online_limit.py's shaky clip, stabilizer and session: the lagged session with 'limit' against `ops.path_limit` applied
-    by hand to what the lagged session without it hands out, the step carried from the push into the flush."""
+    """The path-limit suite's shaky clip, stabilizer and session (tests/online_clips.py): the lagged session with 'limit' against
+    `ops.path_limit` applied by hand to what the lagged session without it hands out, the step carried from the push into the flush."""
     import torch
     from meshflow_amd import ops
-    s = limit_tests.stabilizer(dev)
-    clip = torch.from_numpy(limit_tests.shaky_clip()).to(dev)
-    n, K, session_kw = clip.shape[0], limit_tests.K, limit_tests.SESSION
+    s = limit_stabilizer(dev)
+    clip = torch.from_numpy(shaky_clip()).to(dev)
+    n, session_kw = clip.shape[0], LIMIT_SESSION
     plain = run(s.online_session(lag=LAG, **session_kw), clip, [n])
     rect = plain[0][1].rectangle
     assert [count(p[0]) for p in plain] == [n - LAG, LAG] and rect == (10, 7, 117, 88)
     want_frames, want_k, want_p, want_covered, k_prev = [], [], [], [], None
     for lo, hi, (_, report) in ((0, n - LAG, plain[0]), (n - LAG, n, plain[1])):
         c, p = report.d_unstab.reshape(hi - lo, -1), report.d_stab.reshape(hi - lo, -1)
-        p, k = ops.path_limit(c, p, W, H, R, C, rect, K, limit_tests.GUARD, limit_tests.RISE, k_prev)
+        p, k = ops.path_limit(c, p, W, H, R, C, rect, K, GUARD, RISE, k_prev)
         k_prev = k[-1:]
         out, covered = frames_by_hand(s, clip[lo:hi], c, p, rect)
         want_frames.append(out), want_k.append(k), want_p.append(p), want_covered.append(covered)
@@ -257,7 +264,7 @@ def test_the_path_limit_runs_on_the_frames_handed_out(dev):
         same_bits(report.d_unstab.cpu().numpy(), torch.cat([p[1].d_unstab for p in plain]).cpu().numpy(), ('d_unstab', blocks))
         same_bits(report.covered.cpu().numpy(), torch.cat(want_covered).cpu().numpy(), ('covered', blocks))
         same_bits(out.cpu().numpy(), torch.cat(want_frames).cpu().numpy(), ('frames', blocks))
-        assert (np.diff(steps) <= limit_tests.RISE).all()               # (across the push and the flush too: the step is carried)
+        assert (np.diff(steps) <= RISE).all()               # (across the push and the flush too: the step is carried)
 
 
 def test_a_cut_flushes_the_old_shot_in_front_of_the_new_one(dev):
@@ -288,12 +295,9 @@ def test_a_cut_flushes_the_old_shot_in_front_of_the_new_one(dev):
         same_result(joined(parts), want, blocks)
 
 
-def test_a_refused_push_leaves_the_held_frames_as_they_were(dev):
-    """on_lost='raise' under on_cut='reset' with frames pending: the push hands out frames, flushes the old shot at the cut and resets,
-    then meets a pair that cannot be fitted (tests/test_gpu_online_cuts.py's device) -- and the session, held pixels, `emitted` and all, is
-    where it was; a good push afterwards gives the bytes of a session that never saw the bad one."""
-    import torch
-    s = stabilizer(dev)
+def one_cut_and_a_lost_pair():
+    """tests/cuts_clip.py's clip with the cut at frame 5, the pixels of every tile of frame 8 sorted: its signature is frame 8's, so no cut is
+    seen there, and too few features lead from it to frame 9."""
     g = cuts_clip.one_cut()
     rows, cols = cm.tile_edges(H), cm.tile_edges(W)
     for i in range(4):
@@ -301,7 +305,16 @@ def test_a_refused_push_leaves_the_held_frames_as_they_were(dev):
             tile = g[8, rows[i]:rows[i + 1], cols[j]:cols[j + 1]]
             tile[...] = np.sort(tile.reshape(-1)).reshape(tile.shape)
     assert cm.find_cuts(g)[0] == [5]
-    clip = torch.from_numpy(g).to(dev)
+    return g
+
+
+def test_a_refused_push_leaves_the_held_frames_as_they_were(dev):
+    """on_lost='raise' under on_cut='reset' with frames pending: the push hands out frames, flushes the old shot at the cut and resets,
+    then meets a pair that cannot be fitted (tests/test_gpu_online_cuts.py's device) -- and the session, held pixels, `emitted` and all, is
+    where it was; a good push afterwards gives the bytes of a session that never saw the bad one."""
+    import torch
+    s = stabilizer(dev)
+    clip = torch.from_numpy(one_cut_and_a_lost_pair()).to(dev)
     kw = dict(SESSION, lag=LAG, on_cut='reset', on_lost='raise', on_uncovered='limit')
 
     def snapshot(session):
@@ -332,6 +345,41 @@ def test_a_refused_push_leaves_the_held_frames_as_they_were(dev):
     with pytest.raises(ValueError, match='fewer than 4 features could be tracked'):
         session.push(clip2[4:])
     assert (session.seen, session.emitted, session.pending) == (4, 2, 2) and session._held[0].cpu().numpy().tobytes() == held
+
+
+@pytest.mark.parametrize('name', ['nv12', 'p010'])
+def test_a_refused_push_restores_both_planes(dev, name):
+    """The refused push above on a 4:2:0 pair, where the lag, the cut and the limiter all carry state at once: everything a shot carries,
+    BOTH planes of the held frames included, is where it was, and a good push and the flush afterwards give the bytes -- frames and
+    `last_limit` -- of a twin session that never saw the bad push."""
+    s = stabilizer(dev)
+    clip = to_dev(forms(one_cut_and_a_lost_pair())[name], dev)
+    kw = dict(SESSION, lag=LAG, on_cut='reset', on_lost='raise', on_uncovered='limit')
+
+    def snapshot(session):
+        assert len(session._held) == 2
+        return (session.seen, session.emitted, session.pending, session.shots, int(session._k_prev.item()),
+                [plane.cpu().numpy().tobytes() for plane in session._held], session._last_luma.cpu().numpy().tobytes(),
+                session._last_sig.cpu().numpy().tobytes(), [t.cpu().numpy().tobytes() for t in (session.state.c, session.state.q, session.state.lam)])
+
+    session, twin = s.online_session(**kw), s.online_session(**kw)
+    for one in (session, twin):
+        out, _ = one.push(part(clip, 0, 4))
+        assert count(out) == 2 and one.pending == 2
+    before = snapshot(session)
+    assert [len(b) for b in before[5]] == [clip[0][:2].numel() * clip[0].element_size(), clip[1][:2].numel() * clip[1].element_size()]
+    limit_before = session.last_limit.cpu().numpy().tobytes()
+    with pytest.raises(ValueError, match='fewer than 4 features could be tracked'):
+        session.push(part(clip, 4, N))
+    assert snapshot(session) == before == snapshot(twin)
+    assert session.last_limit.cpu().numpy().tobytes() == limit_before                    # (a push that raises leaves `last_limit` too)
+    got, want = session.push(part(clip, 4, 5)), twin.push(part(clip, 4, 5))
+    assert count(got[0]) == 1 and got[1].first == 2
+    same_result(got, want, (name, 'after the refused push'))
+    same_bits(session.last_limit.cpu().numpy(), twin.last_limit.cpu().numpy(), (name, 'k'))
+    same_result(session.flush(), twin.flush(), (name, 'flush'))
+    same_bits(session.last_limit.cpu().numpy(), twin.last_limit.cpu().numpy(), (name, 'k of the flush'))
+    assert tuple(session.last_limit.shape) == (LAG,)
 
 
 def test_reset_drops_the_pending_frames(dev, clips):

@@ -11,19 +11,14 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import cuts_clip  # noqa: E402
 import cuts_model as cm  # noqa: E402
-import luma_clip  # noqa: E402
-import tracker_clip  # noqa: E402
-from tracker_clip import MAX_PER, SHIFTS, same_bits  # noqa: E402
+import online_clips  # noqa: E402
+from online_clips import FLOOR, GUARD, LIMIT_SESSION, RISE, C, H, K, R, W, part, planes, shaky_clip, to_dev  # noqa: E402
+from online_clips import limit_stabilizer as stabilizer  # noqa: E402
+from tracker_clip import same_bits  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-W, H, R, C = 128, 96, 4, 4
-K, RISE, GUARD = 32, 2, 2.0
-FLOOR = 16                                                               # the canvas raised to it: the grey border byte, 0, is below every pixel
-MORE_SHIFTS = ((-3, 2), (2, -4), (-5, 3), (4, 1))
-STEP = (0, -12)                                                          # content motion into frame 4; the margin leaves 7 rows, 10 columns
-# a radius of 10 frames in a window of 12: at tests/tracker_clip.py's radius of 2 the smoother follows a step within two pixels
-SESSION = dict(window=12, iters=6, beta=1.0, crop_margin=0.08, max_per_subframe=MAX_PER)
+SESSION = LIMIT_SESSION
 FORMS = ['grey', 'bgr', 'nv12']
 
 
@@ -35,43 +30,10 @@ def dev():
     return torch.device('cuda:0')
 
 
-def stabilizer(dev):
-    from meshflow_amd.stabilizer import MeshFlowStabilizer
-    return MeshFlowStabilizer(mesh_row_count=R, mesh_col_count=C, mesh_outlier_subframe_row_count=2, mesh_outlier_subframe_col_count=2,
-                              homography_min_number_corresponding_features=4, temporal_smoothing_radius=10,
-                              optimization_num_iterations=10, device=str(dev))
-
-
-def shaky_clip():
-    """14 frames of the session tests' canvas, not below FLOOR, the fourth move replaced by STEP."""
-    big = np.maximum(tracker_clip.canvas(140, 170, 21, boxes=160), FLOOR)
-    moves = SHIFTS + MORE_SHIFTS
-    ox, oy = 20, 8
-    frames = [big[oy:oy + H, ox:ox + W]]
-    for dx, dy in moves[:3] + (STEP,) + moves[3:] + moves[:3]:
-        ox, oy = ox - dx, oy - dy
-        frames.append(big[oy:oy + H, ox:ox + W])
-    return np.stack([np.ascontiguousarray(f) for f in frames])
-
-
 def forms(g):
-    uv = luma_clip._noise((len(g), H // 2, W // 2, 2), 256, 35).astype(np.uint8)
-    return {'grey': g, 'bgr': np.ascontiguousarray(np.stack([g, g, g], axis=-1)), 'nv12': (g, uv)}
-
-
-def to_dev(clip, dev):
-    import torch
-    if isinstance(clip, tuple):
-        return tuple(torch.from_numpy(np.ascontiguousarray(p)).to(dev) for p in clip)
-    return torch.from_numpy(np.ascontiguousarray(clip)).to(dev)
-
-
-def part(clip, lo, hi):
-    return tuple(p[lo:hi] for p in clip) if isinstance(clip, tuple) else clip[lo:hi]
-
-
-def planes(frames):
-    return [p.cpu().numpy() for p in frames] if isinstance(frames, tuple) else [frames.cpu().numpy()]
+    """grey and NV12 as every session suite has them; BGR with three equal channels, whose red border has B = G = 0, below FLOOR."""
+    made = online_clips.forms(g)
+    return {'grey': g, 'bgr': np.ascontiguousarray(np.stack([g, g, g], axis=-1)), 'nv12': made['nv12']}
 
 
 def same_push(got, want, what):

@@ -1,7 +1,6 @@
 """`MeshFlowStabilizer.online_session` against the composition of the ops written out by hand, on tests/tracker_clip.py's canvas cut into ten
 128 x 96 frames: every form a push takes, blocks against one push, the fixed rectangle and its `covered` flags, a lost pair, reset, and the
 refusals."""
-import math
 import os
 import sys
 
@@ -9,17 +8,12 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import luma_clip  # noqa: E402
 import tracker_clip  # noqa: E402
+from online_clips import (BETA, C, H, ITERS, MARGIN, R, S, SESSION, W, WINDOW, forms, grey_clip, host_of, part, rectangle,  # noqa: E402
+                          same_frames, to_dev)
 from tracker_clip import MAX_PER, SHIFTS, stabilizer  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-
-W, H, R, C = 128, 96, 4, 4
-S = (R + 1) * (C + 1) * 2
-MORE_SHIFTS = ((-3, 2), (2, -4), (-5, 3), (4, 1))
-WINDOW, ITERS, BETA, MARGIN = 4, 6, 1.0, 0.08
-SESSION = dict(window=WINDOW, iters=ITERS, beta=BETA, crop_margin=MARGIN, max_per_subframe=MAX_PER)
 
 
 @pytest.fixture(scope='module')
@@ -28,52 +22,6 @@ def dev():
     if not torch.cuda.is_available():
         pytest.fail('no GPU visible: the -m gpu tests must run on an MI355X')
     return torch.device('cuda:0')
-
-
-def grey_clip():
-    """tests/tracker_clip.py's clip with four more frames cut from the same canvas."""
-    big = tracker_clip.canvas(140, 170, 21, boxes=160)
-    ox, oy, frames = 20, 20, []
-    for dx, dy in ((0, 0),) + SHIFTS + MORE_SHIFTS:
-        ox, oy = ox - dx, oy - dy
-        frames.append(np.ascontiguousarray(big[oy:oy + H, ox:ox + W]))
-    return np.stack(frames)
-
-
-def forms(g):
-    """name -> the clip in that form, as NumPy (a pair for the 4:2:0 forms)."""
-    uv = luma_clip._noise((len(g), H // 2, W // 2, 2), 256, 35).astype(np.uint8)
-    return {'grey': g, 'bgr': luma_clip.bgr(g), 'nv12': (g, uv), 'bgr16': luma_clip.bgr16(g), 'bgra': luma_clip.bgra(g), 'p010': luma_clip.p010(g)}
-
-
-def to_dev(clip, dev):
-    import torch
-    if isinstance(clip, tuple):
-        return tuple(torch.from_numpy(np.ascontiguousarray(p)).to(dev) for p in clip)
-    return torch.from_numpy(np.ascontiguousarray(clip)).to(dev)
-
-
-def part(clip, lo, hi):
-    return tuple(p[lo:hi] for p in clip) if isinstance(clip, tuple) else clip[lo:hi]
-
-
-def host_of(frames):
-    return tuple(p.cpu().numpy() for p in frames) if isinstance(frames, tuple) else frames.cpu().numpy()
-
-
-def same_frames(got, want, what):
-    got, want = host_of(got), host_of(want)
-    if isinstance(want, tuple):
-        assert isinstance(got, tuple) and len(got) == 2, what
-        for g, w, plane in zip(got, want, ('y', 'uv')):
-            tracker_clip.same_bits(g, w, (what, plane))
-    else:
-        tracker_clip.same_bits(got, want, what)
-
-
-def rectangle(margin):
-    left, top = math.floor(margin * (W - 1)), math.floor(margin * (H - 1))
-    return left, top, (W - 1) - left, (H - 1) - top
 
 
 def by_hand(s, clip, margin=MARGIN, output_size=None):
