@@ -329,23 +329,25 @@ static_assert(sizeof(Resize16Tab) == 8, "the 8-bit call's workspace holds the ta
 int launch_crop_resize_to(Px px, const void* frames, void* out, int n, int W, int H, int left, int top, int right, int bottom, int oW, int oH,
                           void* work, hipStream_t st);
 // What those two launch behind their checks (the host units of the kernel headers; `up`: oW >= cw and oH >= ch, which instantiation):
-// resize16.hip: resize16_body.h's tables of the cw x ch crop for oW x oH in the same workspace, then resize16_kernel (oW x oH == W x H) or,
-// through resize_to.hip's launch_resize16_to_kernel, resize16_to_kernel
+// resize16.hip: resize16_body.h's tables of the cw x ch crop for oW x oH in the same workspace, then resize16_kernel (oW x oH == W x H) or
+// resize16_to_kernel
 int launch_resize16(const uint16_t* frames, uint16_t* out, int W, int H, int left, int top, int cw, int ch, int oW, int oH,
                     const TileOrder& order, void* work, hipStream_t st);
-int launch_resize16_to_kernel(const uint16_t* frames, uint16_t* out, int W, int H, int left, int top, int cw, int oW, int oH, bool area,
-                              const Resize16Tab* xtab, const Resize16Tab* ytab, const TileOrder& order, hipStream_t st);
-// resize_c1.hip: resize8c1_kernel on resize.hip's tables (already built in `work`)
+// resize_c1.hip: resize8c1_kernel, or resize8c1_to_kernel for an oW x oH output, on resize.hip's tables (already built in `work`), and their
+// tile rows
 int launch_resize8c1(const uint8_t* frames, uint8_t* out, int n, int W, int H, int left, int top, int cw, const void* work,
                      const TileOrder& order, hipStream_t st);
+int launch_resize8c1_to(const uint8_t* frames, uint8_t* out, int n, int W, int H, int left, int top, int cw, int oW, int oH, bool up,
+                        const void* work, const TileOrder& order, hipStream_t st);
+int resize8c1_tile_rows(bool up);
 // resize_c4.hip: the u8c4 kernels on resize.hip's tables for an oW x oH output (oW x oH == W x H: the same-size call), and their tile rows
 int launch_resize8c4(const uint8_t* frames, uint8_t* out, int n, int W, int H, int left, int top, int cw, int oW, int oH, bool up,
                      const void* work, const TileOrder& order, hipStream_t st);
 int resize8c4_tile_rows(bool up);
-// resize_to.hip: the u8c3 / u8c1 kernels to a chosen size on resize.hip's tables for (oW, oH), and every format's output rows per tile
-int launch_resize8_to(Px px, const uint8_t* frames, uint8_t* out, int n, int W, int H, int left, int top, int cw, int oW, int oH, bool up,
-                      const void* work, const TileOrder& order, hipStream_t st);
+// resize.hip: every format's output rows per tile, and whether the widest span of 256 output pixels fits a staged row (which `down`
+// instantiation a launcher picks)
 int resize_to_tile_rows(Px px, bool up);
+bool resize_span_fits(int cw, int oW, int px_bytes, int slack, int pitch);
 // resize_dev.hip: mf_crop_resize_dev_*: the host-side checks, then the tables and the kernels that read the rectangle from d_bounds
 int launch_crop_resize_dev(Px px, const void* frames, void* out, int n, int W, int H, const int32_t* d_bounds, int oW, int oH, void* work,
                            int32_t* d_status, hipStream_t st);

@@ -1,8 +1,10 @@
-// The host side of mf_crop_resize_* and mf_crop_resize_to_* (rectangle known to the host): every check of the call, the tables launch, and the
-// u8c3 same-size kernel's launch (resize_body.h).  The other formats' kernels are launched from their own units (resize16.hip, resize_c1.hip,
-// resize_c4.hip, resize_to.hip).
+// The host side of mf_crop_resize_* and mf_crop_resize_to_* (rectangle known to the host): every check of the call, the tables launch, which
+// instantiation a call to a chosen size takes, and the u8c3 kernels' launches (resize_body.h).  The other formats' kernels are launched from
+// their own units (resize16.hip, resize_c1.hip, resize_c4.hip).
 #include "resize_body.h"
 #include "resize_checks.h"
+
+#include <cmath>
 
 namespace mf {
 
@@ -42,6 +44,42 @@ int launch_crop_resize(Px px, const void* frames, void* out, int n, int W, int H
     return hip_fail(hipGetLastError(), "resize_kernel launch");
 }
 
+// Whether the widest span 256 output pixels of a cw -> oW row can take (3 (ceil(255 scale_x) + 3) bytes of `px_bytes`-byte pixels, with the
+// kernels' slack of `slack` bytes) fits `pitch`: the launchers pick the instantiation by it (each wavefront still checks its own span).
+bool resize_span_fits(int cw, int oW, int px_bytes, int slack, int pitch)
+{
+    const double widest = (double)px_bytes * (std::ceil(255.0 * ((double)cw / (double)oW)) + 3.0);
+    return widest + slack <= (double)pitch;
+}
+
+// output rows per tile of the format's instantiations (`up`: oW >= cw and oH >= ch)
+int resize_to_tile_rows(Px px, bool up)
+{
+    if (px == Px::U16C3) return 1;
+    if (px == Px::U8C4) return resize8c4_tile_rows(up);
+    if (px == Px::U8C1) return resize8c1_tile_rows(up);
+    return kWaves * (up ? kRows : kDownRows);
+}
+
+// launch_crop_resize_to's u8c3 launch (checks done and the tables for (oW, oH) built)
+static int launch_resize_to(const uint8_t* frames, uint8_t* out, int n, int W, int H, int left, int top, int cw, int oW, int oH, bool up,
+                            const void* work, const TileOrder& order, hipStream_t st)
+{
+    const ResizeTab* xtab = (const ResizeTab*)work;
+    const ResizeTab* ytab = xtab + oW;
+    const dim3 grid(order.per_xcd * 8u), block(64 * kWaves);
+    if (up)
+        hipLaunchKernelGGL((resize_to_kernel<kRows, kSrcRows, kRowPitch, false>), grid, block, 0, st, frames, out, n, W, H, left, top, cw, oW,
+                           oH, xtab, ytab, order);
+    else if (resize_span_fits(cw, oW, 3, 15, kDownPitch))
+        hipLaunchKernelGGL((resize_to_kernel<kDownRows, 2 * kDownRows, kDownPitch, true>), grid, block, 0, st, frames, out, n, W, H, left, top,
+                           cw, oW, oH, xtab, ytab, order);
+    else
+        hipLaunchKernelGGL((resize_to_kernel<kDownRows, 1, 0, true>), grid, block, 0, st, frames, out, n, W, H, left, top, cw, oW, oH, xtab,
+                           ytab, order);
+    return hip_fail(hipGetLastError(), "resize_to_kernel launch");
+}
+
 int launch_crop_resize_to(Px px, const void* frames, void* out, int n, int W, int H, int left, int top, int right, int bottom, int oW, int oH,
                           void* work, hipStream_t st)
 {
@@ -64,7 +102,9 @@ int launch_crop_resize_to(Px px, const void* frames, void* out, int n, int W, in
     if (const int rc = launch_resize_tables_to(cw, ch, oW, oH, work, st)) return rc;
     if (px == Px::U8C4)
         return launch_resize8c4((const uint8_t*)frames, (uint8_t*)out, n, W, H, left, top, cw, oW, oH, up, work, order, st);
-    return launch_resize8_to(px, (const uint8_t*)frames, (uint8_t*)out, n, W, H, left, top, cw, oW, oH, up, work, order, st);
+    if (px == Px::U8C1)
+        return launch_resize8c1_to((const uint8_t*)frames, (uint8_t*)out, n, W, H, left, top, cw, oW, oH, up, work, order, st);
+    return launch_resize_to((const uint8_t*)frames, (uint8_t*)out, n, W, H, left, top, cw, oW, oH, up, work, order, st);
 }
 
 }  // namespace mf

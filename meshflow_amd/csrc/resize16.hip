@@ -1,5 +1,5 @@
 // The uint16 launches of mf_crop_resize_u16c3 / mf_crop_resize_to_u16c3 behind resize.hip's checks: resize16_body.h's tables kernel, then
-// resize16_kernel (here) or resize16_to_kernel (resize_to.hip).
+// resize16_kernel or resize16_to_kernel.
 #include "resize16_body.h"
 
 namespace mf {
@@ -24,8 +24,11 @@ int launch_resize16(const uint16_t* frames, uint16_t* out, int W, int H, int lef
     if (const int rc = launch_resize16_tables(cw, ch, oW, oH, work, st)) return rc;
     Resize16Tab* xtab = (Resize16Tab*)work;
     Resize16Tab* ytab = xtab + oW;
-    if (oW != W || oH != H)
-        return launch_resize16_to_kernel(frames, out, W, H, left, top, cw, oW, oH, 2 * oW == cw && 2 * oH == ch, xtab, ytab, order, st);
+    if (oW != W || oH != H) {
+        hipLaunchKernelGGL(resize16_to_kernel, dim3(order.per_xcd * 8u), dim3(256), 0, st, frames, out, W, H, left, top, cw, oW, oH,
+                           2 * oW == cw && 2 * oH == ch, xtab, ytab, order);
+        return hip_fail(hipGetLastError(), "resize16_to_kernel launch");
+    }
     hipLaunchKernelGGL(resize16_kernel, dim3(order.per_xcd * 8u), dim3(256), 0, st, frames, out, W, H, left, top, cw, xtab, ytab, order);
     return hip_fail(hipGetLastError(), "resize16_kernel launch");
 }

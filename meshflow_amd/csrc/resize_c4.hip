@@ -1,8 +1,6 @@
 // The u8c4 kernel launches of mf_crop_resize_u8c4 / mf_crop_resize_to_u8c4 (resize_c4_body.h) behind resize.hip's checks and tables.
 #include "resize_c4_body.h"
 
-#include <cmath>
-
 namespace mf {
 
 int resize8c4_tile_rows(bool up) { return kWaves * (up ? kUpRows : kDown4Rows); }
@@ -14,12 +12,10 @@ int launch_resize8c4(const uint8_t* frames, uint8_t* out, int n, int W, int H, i
     const ResizeTab* xtab = (const ResizeTab*)work;
     const ResizeTab* ytab = xtab + oW;
     const dim3 grid(order.per_xcd * 8u), block(64 * kWaves);
-    // the widest span 256 output pixels can take, 4 (ceil(255 cw / oW) + 3) bytes, picks the down instantiation (each wavefront checks its own)
-    const bool down_fits = 4.0 * (std::ceil(255.0 * ((double)cw / (double)oW)) + 3.0) <= (double)kDown4Pitch;
     if (up)
         hipLaunchKernelGGL((resize8c4_kernel<kUpRows, kUpSlots, kUpPitch, false>), grid, block, 0, st, frames, out, n, W, H, left, top, cw, oW, oH,
                            xtab, ytab, order);
-    else if (down_fits)
+    else if (resize_span_fits(cw, oW, 4, 0, kDown4Pitch))
         hipLaunchKernelGGL((resize8c4_kernel<kDown4Rows, 2 * kDown4Rows, kDown4Pitch, true>), grid, block, 0, st, frames, out, n, W, H, left, top,
                            cw, oW, oH, xtab, ytab, order);
     else

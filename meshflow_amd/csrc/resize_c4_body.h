@@ -61,61 +61,25 @@ __global__ __launch_bounds__(64 * kWaves) void resize8c4_kernel(const uint8_t* _
                                                                 const ResizeTab* __restrict__ ytab, TileOrder order)
 {
     MF_RECT_LOAD(W, H)
-    __shared__ __attribute__((aligned(16))) uint32_t s_rows[kWaves][SLOTS][PITCH > 0 ? PITCH / 4 : 1];
-    int f, tile_y, tile_x;
-    if (!order.decode(blockIdx.x, f, tile_y, tile_x)) return;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-    const int ya = (tile_y * kWaves + wave) * ROWS;
-    const int xw = tile_x * 256, x0 = xw + lane * 4;
-    if (ya >= oH) return;
-    const int rows = min(ROWS, oH - ya);
-    const size_t frame_bytes = (size_t)W * H * 4, out_frame_bytes = (size_t)oW * oH * 4;
-    const uint8_t* __restrict__ src = frames + (size_t)f * frame_bytes;
-    uint8_t* __restrict__ dst = out + (size_t)f * out_frame_bytes;
-    const size_t limit = (size_t)(n - f) * frame_bytes;           // bytes from src to the end of the stack
-
-    const uint32_t sx_first = (uint32_t)xtab[xw].ofs, sx_last = (uint32_t)xtab[min(xw + 255, oW - 1)].ofs;
-    const uint32_t span = 4u * (sx_last + 2u - sx_first);
-    const int r_first = ytab[ya].ofs & 0xFFFF, r_last = ytab[ya + rows - 1].ofs >> 16;
-    const int nsrc = PAIRS ? 2 * rows : r_last - r_first + 1;
-    const auto src_row = [&](int i) {
-        if (!PAIRS) return r_first + i;
-        const int32_t o = ytab[ya + (i >> 1)].ofs;
-        return (i & 1) ? (o >> 16) : (o & 0xFFFF);
-    };
-    const auto g_of = [&](int r) { return ((size_t)(top + r) * (size_t)W + (size_t)left + sx_first) * 4u; };
-    // (the rows are monotone: the first and the last staged row bound every copy)
-    const bool staged = PITCH > 0 && ((uintptr_t)frames & 3u) == 0 && nsrc <= SLOTS && span <= (uint32_t)PITCH &&
-                        g_of(r_last) + (size_t)PITCH <= limit;
-    if (staged) {
-#pragma unroll 1
-        for (int i = 0; i < nsrc; ++i) {
-            const uint8_t* const a = src + g_of(src_row(i));
-#pragma unroll
-            for (int c = 0; c < PITCH / 16; c += 64) {
-                if (lane + c < PITCH / 16) {
-                    uint32_t o = (uint32_t)(lane + c) << 4;
-                    asm("" : "+v"(o));
-                    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(a + o),
-                                                     (__attribute__((address_space(3))) void*)&s_rows[wave][i][c * 4], 16, 0, 0);
-                }
-            }
-        }
-    }
+    constexpr int STRIDE = PITCH > 0 ? PITCH : 4;
+    __shared__ __attribute__((aligned(16))) uint32_t s_rows[kWaves][SLOTS][STRIDE / 4];
+    Tile8<4, ROWS, PAIRS> t;
+    if (!t.decode(frames, out, n, W, H, left, top, oW, oH, xtab, ytab, order)) return;
+    // (Tile8::fits, ALIGNED: a pixel is a dword, so on a 4-byte aligned stack every copy starts at its first tap -- no misalignment, no slack)
+    const bool staged = t.template fits<SLOTS, PITCH, 0, true>(frames);
     ResizeTab xt[4];
-    if (x0 < oW) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) xt[j] = xtab[min(x0 + j, oW - 1)];
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // staged rows (and the column table) have landed
+    t.template stage_rows<PITCH, STRIDE, true>(staged, (uint8_t*)&s_rows[t.wave][0][0], xtab, oW, xt);
+    const int ya = t.ya, rows = t.rows, x0 = t.x0;
+    const uint8_t* __restrict__ src = t.src;
+    uint8_t* __restrict__ dst = t.dst;
     if (x0 >= oW) return;
 
     if (staged) {
         uint32_t rel[4];
 #pragma unroll
-        for (int j = 0; j < 4; ++j) rel[j] = (uint32_t)xt[j].ofs - sx_first;        // in dwords
+        for (int j = 0; j < 4; ++j) rel[j] = (uint32_t)xt[j].ofs - t.sx_first;        // in dwords
         const auto hpass_slot = [&](int i, uint32_t (&T)[4][4]) {
-            const uint32_t* const s = &s_rows[wave][i][0];
+            const uint32_t* const s = &s_rows[t.wave][i][0];
 #pragma unroll
             for (int j = 0; j < 4; ++j) hpass_c4(s[rel[j]], s[rel[j] + 1], xt[j].w, T[j]);
         };
@@ -130,7 +94,7 @@ __global__ __launch_bounds__(64 * kWaves) void resize8c4_kernel(const uint8_t* _
                 const int y = ya + q + h;
                 if (y >= ya + rows) break;
                 const ResizeTab yt = ytab[y];
-                const int i0 = PAIRS ? 2 * (q + h) : (yt.ofs & 0xFFFF) - r_first, i1 = PAIRS ? 2 * (q + h) + 1 : (yt.ofs >> 16) - r_first;
+                const int i0 = PAIRS ? 2 * (q + h) : (yt.ofs & 0xFFFF) - t.r_first, i1 = PAIRS ? 2 * (q + h) + 1 : (yt.ofs >> 16) - t.r_first;
                 const uint32_t b0s = (yt.w & 0xFFFFu) << 8, b1s = (yt.w >> 16) << 8;
                 const uint32_t o = ((uint32_t)y * (uint32_t)oW + (uint32_t)x0) * 4u;
                 if (h == 0) {

@@ -1,7 +1,7 @@
 // _crop_frames (mfs.py:1111-1157) from a rectangle that stays on the device: mf_crop_resize_dev_u8c3 / _u16c3 / _u8c1 / _u8c4.  The rectangle
 // {left, top, right, bottom} is the 16 bytes a warp's clip-level reduction left in device memory; the host never reads it, so these calls
-// never wait for the warp.  The kernels are the five kernel headers' (resize_body.h, resize16_body.h, resize_to_body.h, resize_c1_body.h,
-// resize_c4_body.h) compiled a second time, under MF_RESIZE_DEV (resize_rect.h) and other names: the rectangle is loaded instead of passed,
+// never wait for the warp.  The kernels are the four kernel headers' (resize_body.h, resize16_body.h, resize_c1_body.h, resize_c4_body.h)
+// compiled a second time, under MF_RESIZE_DEV (resize_rect.h) and other names: the rectangle is loaded instead of passed,
 // everything else is the same code.
 //
 // What the host still decides, from (W, H, oW, oH) alone:
@@ -23,7 +23,6 @@
 #define resize8c4_kernel resize_bgra_dev_kernel
 #include "resize_body.h"
 #include "resize16_body.h"
-#include "resize_to_body.h"
 #include "resize_c1_body.h"
 #include "resize_c4_body.h"
 #include "resize_checks.h"

@@ -2,7 +2,7 @@
 // plane uv [n][H/2][W/2][2] uint16, U first, to out_uv [n][oH/2][oW/2][2].  W, H, oW, oH and the rectangle {left, top, right, bottom}
 // (inclusive, any parity) are the LUMA frame's everywhere.  Samples are plain 16-bit numbers; nothing is masked.
 //
-// Luma is channel 0 of resize16_to_kernel (resize_to_body.h) on stack(Y, Y, Y), bit for bit: cv2.resize INTER_LINEAR of CV_16UC1 -- the tables
+// Luma is channel 0 of resize16_to_kernel (resize16_body.h) on stack(Y, Y, Y), bit for bit: cv2.resize INTER_LINEAR of CV_16UC1 -- the tables
 // are resize16_tables_kernel's for (oW, oH) (resize16_body.h; launched by the units that own that kernel), float32 weights (1 - f, f),
 //   t = float(S[sx]) a0 + float(S[sx+1]) a1,   out = min(rint(t0 b0 + t1 b1), 65535)        (every product and sum rounded on its own)
 // and, where the crop is exactly twice the output in both axes (`area`, uniform per launch), INTER_AREA's (S00 + S01 + S10 + S11 + 2) >> 2.

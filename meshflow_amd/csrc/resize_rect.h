@@ -1,10 +1,12 @@
-// Where a crop-resize kernel gets its rectangle from.  The kernel headers (resize_body.h, resize16_body.h, resize_c1_body.h, resize_c4_body.h,
-// resize_to_body.h) are written against these macros.  Included from resize.hip, resize16.hip, resize_c1.hip, resize_c4.hip and resize_to.hip,
-// their kernels take `left, top, cw` as launch arguments (MF_RECT_ARGS) -- the host knows the rectangle.  The translation unit of the
-// device-rectangle calls (mf_crop_resize_dev_*: resize_dev.hip) defines MF_RESIZE_DEV, renames the kernels and includes the same headers:
-// MF_RECT_ARGS is then a pointer to {left, top, right, bottom} in device memory and MF_RECT_LOAD, the first statement of every body, reads
-// it (four uniform dwords: one scalar 16-byte load per wavefront) and RETURNS if the rectangle cannot be used, before the kernel has read a
-// frame byte or written an output byte.  Without MF_RESIZE_DEV both macros leave the kernels exactly what they were (tools/isa_compare.py).
+// Where a crop-resize kernel gets its rectangle from.  The kernel headers (resize_body.h, resize16_body.h, resize_c1_body.h, resize_c4_body.h)
+// are written against these macros, and only their kernel entries: a __global__ loads the rectangle and hands plain left, top, cw to the
+// format's tile function, which is the same text in both flavours.  Included from resize.hip, resize16.hip, resize_c1.hip and
+// resize_c4.hip, their kernels take `left, top, cw` as launch arguments (MF_RECT_ARGS) -- the host knows the rectangle.  The translation
+// unit of the device-rectangle calls (mf_crop_resize_dev_*: resize_dev.hip) defines MF_RESIZE_DEV, renames the kernels and includes the
+// same headers: MF_RECT_ARGS is then a pointer to {left, top, right, bottom} in device memory and MF_RECT_LOAD, the first statement of
+// every kernel entry, reads it (four uniform dwords: one scalar 16-byte load per wavefront) and RETURNS if the rectangle cannot be used,
+// before the kernel has read a frame byte or written an output byte.  Without MF_RESIZE_DEV both macros expand to launch arguments and to
+// nothing.
 #pragma once
 #include "mf_common.h"
 

@@ -1,5 +1,6 @@
-// The device helpers and tile constants every 8-bit crop-resize kernel shares (resize_body.h, resize_c1_body.h, resize_c4_body.h,
-// resize_to_body.h), each defined here once; the BGR row passes (hpass_row, vpass_store) are resize_kernel's and resize_to_kernel's.
+// The device pieces every 8-bit crop-resize kernel shares (resize_body.h: u8c3, resize_c1_body.h: u8c1, resize_c4_body.h: u8c4), each defined
+// here once: the tile constants, a wavefront's tile (Tile8: decode, geometry, the test that a staged copy stays inside the frame stack, the
+// global->LDS copy of its source rows), and the BGR row passes (hpass_row, vpass_store) of resize_body.h.
 #pragma once
 #include "mf_common.h"
 
@@ -35,6 +36,111 @@ __device__ __forceinline__ uint32_t mulhi_u24(uint32_t a, uint32_t b)
 {
     return (uint32_t)(((unsigned long long)(a & 0xFFFFFFu) * (unsigned long long)(b & 0xFFFFFFu)) >> 32);
 }
+
+// One wavefront's tile of an 8-bit crop-resize, the part that does not depend on the pixel format beyond its BPP bytes per pixel: ROWS
+// consecutive output rows x 256 output pixels (a lane: 4 consecutive pixels per row) of frame f, source pitch W and frame W H BPP bytes,
+// output oW x oH (the same-size kernels: oW = W, oH = H); the tables are resize_tables_kernel's for (oW, oH).  The tile's source rows go to
+// LDS slots: slot i holds source row r_first + i (!PAIRS, an upscale: consecutive output rows advance by at most one source row), or row h
+// of output row ya + q for i = 2q + h (PAIRS: exactly the two rows of each output row, nothing unused copied).
+template <int BPP, int ROWS, bool PAIRS>
+struct Tile8 {
+    int wave, lane;
+    int ya, rows, x0;                        // first output row and how many; the lane's first output pixel
+    const uint8_t* src;                      // frame f; `limit` bytes from here to the end of the stack, `base` its address
+    uint8_t* dst;
+    size_t limit, base;
+    // span of source columns the wavefront touches: taps sx .. sx+1 for its first .. last pixel (the tables are monotone), in bytes, and of
+    // source rows: sy0 of its first .. sy1 of its last output row
+    uint32_t sx_first, span;
+    int r_first, r_last, nsrc;
+    const ResizeTab* ytab;
+    int W, left, top;
+
+    // false: the workgroup or the wavefront has no tile (nothing read or written yet)
+    __device__ __forceinline__ bool decode(const uint8_t* __restrict__ frames, uint8_t* __restrict__ out, int n, int W_, int H, int left_, int top_,
+                                           int oW, int oH, const ResizeTab* __restrict__ xtab, const ResizeTab* __restrict__ ytab_,
+                                           const TileOrder& order)
+    {
+        int f, tile_y, tile_x;
+        if (!order.decode(blockIdx.x, f, tile_y, tile_x)) return false;
+        wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+        ya = (tile_y * kWaves + wave) * ROWS;
+        const int xw = tile_x * 256;
+        x0 = xw + lane * 4;
+        if (ya >= oH) return false;
+        rows = min(ROWS, oH - ya);
+        const size_t frame_bytes = (size_t)W_ * H * BPP, out_frame_bytes = (size_t)oW * oH * BPP;
+        src = frames + (size_t)f * frame_bytes;
+        dst = out + (size_t)f * out_frame_bytes;
+        limit = (size_t)(n - f) * frame_bytes;
+        base = (size_t)(uintptr_t)src;
+        ytab = ytab_, W = W_, left = left_, top = top_;
+        sx_first = (uint32_t)xtab[xw].ofs;
+        span = (uint32_t)BPP * ((uint32_t)xtab[min(xw + 255, oW - 1)].ofs + 2u - sx_first);
+        r_first = ytab[ya].ofs & 0xFFFF, r_last = ytab[ya + rows - 1].ofs >> 16;
+        nsrc = PAIRS ? 2 * rows : r_last - r_first + 1;
+        return true;
+    }
+    // the source row (in the crop) slot i holds
+    __device__ __forceinline__ int src_row(int i) const
+    {
+        if (!PAIRS) return r_first + i;
+        const int32_t o = ytab[ya + (i >> 1)].ofs;
+        return (i & 1) ? (o >> 16) : (o & 0xFFFF);
+    }
+    // byte offset in the frame of the first tap of source row r: ((top + r) W + left + sx_first) BPP
+    __device__ __forceinline__ size_t g_of(int r) const { return ((size_t)(top + r) * (size_t)W + (size_t)left + sx_first) * (size_t)BPP; }
+    // Bytes in front of slot i's first tap: a copy starts at the dword holding the tap.  !PAIRS: the rows are consecutive, so the
+    // misalignment advances by (BPP W) & 3 per slot and nothing is loaded for it.
+    __device__ __forceinline__ uint32_t mis_of(int i) const
+    {
+        if (!PAIRS) return ((uint32_t)(base + g_of(r_first)) + (uint32_t)i * (uint32_t)(BPP * W)) & 3u;
+        return (uint32_t)((base + g_of(src_row(i))) & 3u);
+    }
+    // Whether the tile is staged: it has LDS at all (PITCH > 0), its rows fit the SLOTS, its span plus the format's SLACK bytes (the misalignment
+    // in front of the first tap, and the margin the format keeps behind the last) fit a PITCH-byte row, and every copy stays inside the frame
+    // stack.  The rows are monotone, so the first and the last staged row bound every copy: behind, PITCH bytes from the last row's first tap
+    // (conservative by the misalignment); in front, the 3 bytes a copy may start before its tap -- or, ALIGNED (4-byte pixels), a 4-byte
+    // aligned stack, where every tap is a dword of its own and no copy starts in front of it.
+    template <int SLOTS, int PITCH, int SLACK, bool ALIGNED>
+    __device__ __forceinline__ bool fits(const uint8_t* frames) const
+    {
+        return PITCH > 0 && nsrc <= SLOTS && span + (uint32_t)SLACK <= (uint32_t)PITCH &&
+               (ALIGNED ? ((uintptr_t)frames & 3u) == 0 : g_of(r_first) >= 3u) && g_of(r_last) + (size_t)PITCH <= limit;
+    }
+    // The staged copy, the column table entries of the lane's four pixels, and the one wait for both.  Slot i is the STRIDE bytes at
+    // lds + i STRIDE; the wavefront copies PITCH bytes of each source row there, from the dword holding the row's first tap, with one 16-byte
+    // global->LDS load per lane and chunk (the LDS address of such a load is wavefront-uniform: the lanes land 16 bytes apart).
+    template <int PITCH, int STRIDE, bool ALIGNED>
+    __device__ __forceinline__ void stage_rows(bool staged, uint8_t* lds, const ResizeTab* __restrict__ xtab, int oW, ResizeTab (&xt)[4]) const
+    {
+        // A row of at most 64 chunks (u8c3 and u8c1 `up`) is one load per lane: which lanes have a chunk is decided once, in front of the row
+        // loop, as the same-size kernels did (per row it cost u8c1 3-5 %, profiles/crop_resize_one_body.md); wider rows decide per chunk.
+        constexpr int CHUNKS = PITCH / 16;
+        if (staged && (CHUNKS > 64 || lane < CHUNKS)) {
+            const size_t g_first = g_of(r_first), row_bytes = (size_t)W * (size_t)BPP;
+#pragma unroll 1
+            for (int i = 0; i < nsrc; ++i) {
+                const size_t g = PAIRS ? g_of(src_row(i)) : g_first + (size_t)i * row_bytes;     // (consecutive rows advance by a row)
+                const uint8_t* const a = src + (ALIGNED ? g : g - ((base + g) & 3u));
+#pragma unroll
+                for (int c = 0; c < CHUNKS; c += 64) {
+                    if (CHUNKS <= 64 || lane + c < CHUNKS) {
+                        uint32_t o = (uint32_t)(lane + c) << 4;
+                        asm("" : "+v"(o));
+                        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(a + o),
+                                                         (__attribute__((address_space(3))) void*)(lds + i * STRIDE + c * 16), 16, 0, 0);
+                    }
+                }
+            }
+        }
+        if (x0 < oW) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) xt[j] = xtab[min(x0 + j, oW - 1)];
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // staged rows (and the column table) have landed
+    }
+};
 
 // The horizontal pass of ONE staged source row for the lane's four pixels.  The wavefront has copied the span of the row it needs into LDS
 // (from the dword holding its first tap, 16-byte global->LDS chunks); at[j] is the LDS byte address of pixel j's first tap there.

@@ -203,8 +203,8 @@ def test_ops_size_checks(dev):
 # ---- seeded random sweep ----------------------------------------------------------------------------------------------------------
 
 # scale_x = crop width / output width at which each format's down instantiation leaves its staged form for the direct one: the widest span
-# 256 output pixels can take, px (ceil(255 scale_x) + 3) bytes (+ slack), must fit its LDS row -- u8c3: kDownPitch 2048 (resize_to_body.h,
-# slack 15), u8c1: kDown1Pitch 1024 (slack 3), u8c4: kDown4Pitch 2432 (resize_c4_body.h).  As the largest ceil(255 scale_x) that still fits.
+# 256 output pixels can take, px (ceil(255 scale_x) + 3) bytes (+ slack), must fit its LDS row -- u8c3: kDownPitch 2048 (resize_body.h,
+# slack 15), u8c1: kDown1Pitch 1024 (resize_c1_body.h, slack 3), u8c4: kDown4Pitch 2432 (resize_c4_body.h).  As the largest ceil(255 scale_x) that still fits.
 # uint16 has one kernel (no staging): its draws sit at u8c3's.
 CUT_CEIL = {'u8c3': 674, 'u8c1': 1018, 'u8c4': 605, 'u16c3': 674}
 SWEEP_OFFSETS = {'u8c3': ((None, None), (1, 3), (2, 1), (3, 2)), 'u8c1': ((None, None), (1, 3), (2, 1), (3, 2)),

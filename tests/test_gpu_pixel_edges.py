@@ -371,7 +371,10 @@ def test_crop_resize_corner_cases(dev, pixel):
     pairs = {'u16c3': ((None, None), (2, 2), (2, 0), (0, 2)), 'u8c1': ((None, None), (1, 3), (2, 1), (3, 2), (0, 1)),
              'u8c4': ((None, None), (1, 3), (2, 1), (3, 2), (0, 1), (8, 12))}[pixel]
     n = 0
-    for W, H, nfr in itertools.product((1, 2, 3, 4, 5, 7, 8, 9, 31, 32, 33, 100, 255, 256, 257, 300), (1, 2, 3, 5, 8, 9, 17, 33, 40), (1, 3)):
+    # (259-261 and 271-273: where tile 0 of the last rows of the last frame flips between staged and direct -- u8c4: 4 W against the staged
+    # row's 1040 bytes, u8c1: W against 272)
+    for W, H, nfr in itertools.product((1, 2, 3, 4, 5, 7, 8, 9, 31, 32, 33, 100, 255, 256, 257, 259, 260, 261, 271, 272, 273, 300),
+                                       (1, 2, 3, 5, 8, 9, 17, 33, 40), (1, 3)):
         frames = rand_frames(pixel, rng, nfr, H, W)
         srcs = {off: put(frames, dev, off) for off in {p[0] for p in pairs}}
         dsts = {off: put(np.zeros_like(frames), dev, off) for off in {p[1] for p in pairs} if off is not None}
