@@ -640,6 +640,28 @@ int mf_online_smooth_lag_f64(const float* d_vel, const double* d_lam_known, cons
                              int iters, double beta, double lam_newest, int64_t seen, double* d_c_state, double* d_q_state,
                              double* d_lam_state, double* d_c_out, double* d_p_out, void* stream);
 
+/* ---- online path smoothing of a group: K rows of n frames, each row a different stream of B, in one pair of launches ----
+ * mf_online_smooth_f64 per row, bit for bit (tests/online_model.py remains the specification): row r is the single call on
+ *   d_vel + r n S, d_lam_known + r n, d_c_out + r n S, d_p_out + r n S      the row's velocities [n][S], weights [n] and outputs [n][S]
+ *   seen = d_seen[r]                                                        that stream's frames so far, [K] int64 ON THE DEVICE
+ *   d_c_state + id (window - 1) S, d_q_state likewise, d_lam_state + id (window - 1)     with id = d_ids[r], [K] int32 on the device
+ * with the same operations in the same order, no fma, IEEE division.  d_c_state, d_q_state [B][window - 1][S] and d_lam_state [B][window - 1]
+ * are the states of B streams stacked; d_taps, omega, window, iters, beta and lam_newest are shared by the rows.
+ * A row with d_seen[r] == 0 reads nothing of its stream's state (a per-stream reset is that zero, no memset); a stream not named in d_ids
+ * keeps its state bytes; a row whose id is outside 0 .. B - 1 or whose d_seen[r] is negative touches no memory at all, its output rows
+ * included.  The ids of one call must be DISTINCT: that is the caller's duty, the library cannot see them without a wait (two rows on one
+ * stream would race on its state; every access still lies inside the stacks).  The caller adds n to each pushed stream's count.
+ * Two launches whatever K and n are: the sweep on a grid (S, K), one wavefront per workgroup, workgroup (s, r) series s of row r; then one
+ * workgroup per row shifts that stream's weights.  No atomics; a second call on the same inputs gives the same bytes; a non-finite value
+ * stays in its series of its stream.
+ * Limits (MF_ERR_INVALID_ARG, nothing launched): those of mf_online_smooth_f64 (there is no host `seen`), plus K < 1, B < 1, K > B,
+ * K > MF_ONLINE_GROUP_MAX_ROWS, null d_ids or d_seen, d_ids not 4-byte or d_seen not 8-byte aligned; the overlap rules take d_ids and d_seen
+ * as inputs, the K n rows as the outputs and the whole stacks as the state.  Asynchronous on `stream`. */
+#define MF_ONLINE_GROUP_MAX_ROWS 65535
+int mf_online_smooth_group_f64(const float* d_vel, const double* d_lam_known, const double* d_taps, const int32_t* d_ids, const int64_t* d_seen,
+                               int K, int B, int n, int S, int omega, int window, int iters, double beta, double lam_newest, double* d_c_state,
+                               double* d_q_state, double* d_lam_state, double* d_c_out, double* d_p_out, void* stream);
+
 /* ---- scene cuts: a per-frame signature of tile histograms of luma, and the distance of adjacent signatures ----
  * The reference has nothing of the kind; this is a specification of the project's own, bit for bit tests/cuts_model.py, integers only -- any
  * order of summation gives the same bytes.
@@ -660,6 +682,11 @@ int mf_online_smooth_lag_f64(const float* d_vel, const double* d_lam_known, cons
 #define MF_CUT_MAX_DIM 32767
 int mf_frame_signature_u8(const uint8_t* d_luma, int n, int W, int H, int32_t* d_sig, void* stream);
 int mf_cut_distance_i32(const int32_t* d_sig_prev, const int32_t* d_sig, int n, int32_t* d_dist, void* stream);
+/* mf_cut_distance_pairs_i32: the rows are frames of n different streams, each with a predecessor of its own: d_dist[r] = D(d_prev[r], d_sig[r])
+ * for d_prev, d_sig [n][256] int32 -- mf_cut_distance_i32's arithmetic, one launch of one workgroup per row, no atomics.
+ * Limits (MF_ERR_INVALID_ARG, nothing launched): a null pointer; n < 1; an array not 4-byte aligned; d_dist overlapping either stack.
+ * Asynchronous on `stream`. */
+int mf_cut_distance_pairs_i32(const int32_t* d_prev, const int32_t* d_sig, int n, int32_t* d_dist, void* stream);
 
 /* ---- path limit: scale a frame's correction so that the mesh still covers a fixed crop rectangle ----
  * The reference has nothing of the kind (its rectangle is a reduction over the whole clip, mfs.py:1103-1106); this is a specification of the
@@ -692,6 +719,14 @@ int mf_cut_distance_i32(const int32_t* d_sig_prev, const int32_t* d_sig, int n, 
 #define MF_PATH_LIMIT_MAX_BOUNDARY 1024
 int mf_path_limit_f64(const double* d_unstab, const double* d_stab, int n, int W, int H, int R, int C, int left, int top, int right, int bottom,
                       double guard, int steps, int rise, const int32_t* d_k_prev, int32_t* d_k_raw, int32_t* d_k, double* d_out, void* stream);
+/* mf_path_limit_group_f64: K rows, each ONE frame of a different stream: nothing is chained between the rows.  d_k_prev [K] int32 holds each
+ * row's carried step; row r gets the bytes of a one-frame mf_path_limit_f64 call with that word as *d_k_prev:
+ *   k_r = min(K_steps, k_raw_r, clamp(d_k_prev[r], 0, K_steps) + rise);  a NEGATIVE d_k_prev[r] says that nothing is carried -- the null
+ *   d_k_prev of the single call -- and leaves the rise term out.
+ * The candidate test is mf_path_limit_f64's launch as it is (it is per frame); the second launch forms k_r and scales the row with the same
+ * statement.  Limits: those of mf_path_limit_f64 with K in the place of n, and d_k_prev, K words, must be given.  Asynchronous on `stream`. */
+int mf_path_limit_group_f64(const double* d_unstab, const double* d_stab, int K, int W, int H, int R, int C, int left, int top, int right, int bottom,
+                            double guard, int steps, int rise, const int32_t* d_k_prev, int32_t* d_k_raw, int32_t* d_k, double* d_out, void* stream);
 
 /* ---- stability score (mfs.py:1216-1259) of device-resident vertex paths ----
  * d_stab: [F][S] float64 as for mf_jacobi_f64 (S = V*2: x and y of every vertex interleaved).  Per series the fraction of

@@ -817,12 +817,19 @@ int mf_vertex_motion_f64(const double* d_early, const double* d_late, const int3
                                 ellipse_rows, ellipse_cols, d_velocities, d_displacements, d_work, d_status, (hipStream_t)stream);
 }
 
-// What mf_online_smooth_f64 and mf_online_smooth_lag_f64 refuse alike, under the caller's name: MF_OK where the launches may go ahead.
+// What mf_online_smooth_f64, mf_online_smooth_lag_f64 and mf_online_smooth_group_f64 refuse alike, under the caller's name: MF_OK where the
+// launches may go ahead.  K rows of n frames on the state stacks of B streams; the single calls are K = B = 1 with `seen` on the host and
+// no d_ids / d_seen (group false).
 static int online_smooth_checks(const char* name, const float* d_vel, const double* d_lam_known, const double* d_taps, int n, int S, int omega,
                                 int window, int iters, double beta, double lam_newest, int64_t seen, double* d_c_state, double* d_q_state,
-                                double* d_lam_state, double* d_c_out, double* d_p_out)
+                                double* d_lam_state, double* d_c_out, double* d_p_out, bool group = false, int K = 1, int B = 1,
+                                const int32_t* d_ids = nullptr, const int64_t* d_seen = nullptr)
 {
     if (n < 1 || S < 1) { set_error("%s: n and S must be at least 1 (got %d, %d)", name, n, S); return MF_ERR_INVALID_ARG; }
+    if (K < 1 || B < 1 || K > B || K > MF_ONLINE_GROUP_MAX_ROWS) {
+        set_error("%s: K rows of B streams need 1 <= K <= B and K <= %d (got K=%d, B=%d)", name, MF_ONLINE_GROUP_MAX_ROWS, K, B);
+        return MF_ERR_INVALID_ARG;
+    }
     if (window < 2 || window > MF_ONLINE_MAX_WINDOW) {
         set_error("%s: window must be in 2 .. %d (got %d)", name, MF_ONLINE_MAX_WINDOW, window);
         return MF_ERR_INVALID_ARG;
@@ -835,7 +842,7 @@ static int online_smooth_checks(const char* name, const float* d_vel, const doub
         return MF_ERR_INVALID_ARG;
     }
     if (seen < 0) { set_error("%s: seen must not be negative (got %lld)", name, (long long)seen); return MF_ERR_INVALID_ARG; }
-    if (!d_vel || !d_lam_known || !d_taps || !d_c_state || !d_q_state || !d_lam_state || !d_c_out || !d_p_out) {
+    if (!d_vel || !d_lam_known || !d_taps || !d_c_state || !d_q_state || !d_lam_state || !d_c_out || !d_p_out || (group && (!d_ids || !d_seen))) {
         set_error("%s: null pointer", name);
         return MF_ERR_INVALID_ARG;
     }
@@ -844,20 +851,25 @@ static int online_smooth_checks(const char* name, const float* d_vel, const doub
         set_error("%s: d_vel must be 4-byte aligned, every float64 array 8-byte aligned", name);
         return MF_ERR_INVALID_ARG;
     }
-    const size_t rows = (size_t)n, series = (size_t)S, held = (size_t)window - 1;
-    const struct { const void* at; size_t bytes; } in[3] = {{d_vel, rows * series * 4}, {d_lam_known, rows * 8}, {d_taps, (size_t)omega * 8}},
+    if (((uintptr_t)d_ids & 3) || ((uintptr_t)d_seen & 7)) {
+        set_error("%s: d_ids must be 4-byte aligned, d_seen 8-byte aligned", name);
+        return MF_ERR_INVALID_ARG;
+    }
+    const size_t rows = (size_t)K * (size_t)n, series = (size_t)S, held = (size_t)B * ((size_t)window - 1);
+    const struct { const void* at; size_t bytes; } in[5] = {{d_vel, rows * series * 4}, {d_lam_known, rows * 8}, {d_taps, (size_t)omega * 8},
+                                                            {d_ids, group ? (size_t)K * 4 : 0}, {d_seen, group ? (size_t)K * 8 : 0}},
                                                    state[3] = {{d_c_state, held * series * 8}, {d_q_state, held * series * 8}, {d_lam_state, held * 8}},
                                                    out[2] = {{d_c_out, rows * series * 8}, {d_p_out, rows * series * 8}};
     for (const auto& o : out) {
         for (const auto& i : in)
-            if (overlap(i.at, i.bytes, o.at, o.bytes)) { set_error("%s: an output aliases an input", name); return MF_ERR_INVALID_ARG; }
+            if (i.bytes && overlap(i.at, i.bytes, o.at, o.bytes)) { set_error("%s: an output aliases an input", name); return MF_ERR_INVALID_ARG; }
         for (const auto& q : state)
             if (overlap(q.at, q.bytes, o.at, o.bytes)) { set_error("%s: an output aliases the state", name); return MF_ERR_INVALID_ARG; }
     }
     if (overlap(out[0].at, out[0].bytes, out[1].at, out[1].bytes)) { set_error("%s: d_c_out and d_p_out alias", name); return MF_ERR_INVALID_ARG; }
     for (int a = 0; a < 3; ++a) {                           // (the state is updated in place while the inputs are still being read)
         for (const auto& i : in)
-            if (overlap(i.at, i.bytes, state[a].at, state[a].bytes)) { set_error("%s: the state aliases an input", name); return MF_ERR_INVALID_ARG; }
+            if (i.bytes && overlap(i.at, i.bytes, state[a].at, state[a].bytes)) { set_error("%s: the state aliases an input", name); return MF_ERR_INVALID_ARG; }
         for (int b = a + 1; b < 3; ++b)
             if (overlap(state[a].at, state[a].bytes, state[b].at, state[b].bytes)) {
                 set_error("%s: two of the state arrays alias", name);
@@ -894,6 +906,18 @@ int mf_online_smooth_lag_f64(const float* d_vel, const double* d_lam_known, cons
                                     d_q_state, d_lam_state, d_c_out, d_p_out, (hipStream_t)stream);
 }
 
+int mf_online_smooth_group_f64(const float* d_vel, const double* d_lam_known, const double* d_taps, const int32_t* d_ids, const int64_t* d_seen,
+                               int K, int B, int n, int S, int omega, int window, int iters, double beta, double lam_newest, double* d_c_state,
+                               double* d_q_state, double* d_lam_state, double* d_c_out, double* d_p_out, void* stream)
+{
+    static_assert(sizeof(long long) == sizeof(int64_t), "d_seen is read as long long on the device");
+    const int rc = online_smooth_checks("mf_online_smooth_group_f64", d_vel, d_lam_known, d_taps, n, S, omega, window, iters, beta, lam_newest, 0,
+                                        d_c_state, d_q_state, d_lam_state, d_c_out, d_p_out, true, K, B, d_ids, d_seen);
+    if (rc != MF_OK) return rc;
+    return launch_online_smooth_group(d_vel, d_lam_known, d_taps, d_ids, reinterpret_cast<const long long*>(d_seen), K, B, n, S, omega, window,
+                                      iters, beta, lam_newest, d_c_state, d_q_state, d_lam_state, d_c_out, d_p_out, (hipStream_t)stream);
+}
+
 int mf_frame_signature_u8(const uint8_t* d_luma, int n, int W, int H, int32_t* d_sig, void* stream)
 {
     const char* name = "mf_frame_signature_u8";
@@ -928,10 +952,28 @@ int mf_cut_distance_i32(const int32_t* d_sig_prev, const int32_t* d_sig, int n, 
     return launch_cut_distance(d_sig_prev, d_sig, n, d_dist, (hipStream_t)stream);
 }
 
-int mf_path_limit_f64(const double* d_unstab, const double* d_stab, int n, int W, int H, int R, int C, int left, int top, int right, int bottom,
-                      double guard, int steps, int rise, const int32_t* d_k_prev, int32_t* d_k_raw, int32_t* d_k, double* d_out, void* stream)
+int mf_cut_distance_pairs_i32(const int32_t* d_prev, const int32_t* d_sig, int n, int32_t* d_dist, void* stream)
 {
-    const char* name = "mf_path_limit_f64";
+    const char* name = "mf_cut_distance_pairs_i32";
+    if (!d_prev || !d_sig || !d_dist) { set_error("%s: null pointer", name); return MF_ERR_INVALID_ARG; }
+    if (n < 1) { set_error("%s: n must be at least 1 (got %d)", name, n); return MF_ERR_INVALID_ARG; }
+    if (((uintptr_t)d_prev & 3) || ((uintptr_t)d_sig & 3) || ((uintptr_t)d_dist & 3)) {
+        set_error("%s: d_prev, d_sig and d_dist must be 4-byte aligned", name);
+        return MF_ERR_INVALID_ARG;
+    }
+    if (overlap(d_sig, (size_t)n * MF_CUT_COUNTERS * 4, d_dist, (size_t)n * 4) || overlap(d_prev, (size_t)n * MF_CUT_COUNTERS * 4, d_dist, (size_t)n * 4)) {
+        set_error("%s: d_dist overlaps a signature", name);
+        return MF_ERR_INVALID_ARG;
+    }
+    return launch_cut_distance_pairs(d_prev, d_sig, n, d_dist, (hipStream_t)stream);
+}
+
+// What mf_path_limit_f64 and mf_path_limit_group_f64 refuse alike, under the caller's name; carried: the int32 words d_k_prev holds where it is
+// given (1, or a word per row of a group, where it must be given).
+static int path_limit_checks(const char* name, const double* d_unstab, const double* d_stab, int n, int W, int H, int R, int C, int left, int top,
+                             int right, int bottom, double guard, int steps, int rise, const int32_t* d_k_prev, size_t carried, int32_t* d_k_raw,
+                             int32_t* d_k, double* d_out)
+{
     if (n < 1) { set_error("%s: n must be at least 1 (got %d)", name, n); return MF_ERR_INVALID_ARG; }
     if (R < 1 || C < 1 || (long long)R + (long long)C > MF_PATH_LIMIT_MAX_BOUNDARY / 2) {
         set_error("%s: mesh R=%d C=%d: each at least 1 with 2 (R + C) <= %d boundary vertices", name, R, C, MF_PATH_LIMIT_MAX_BOUNDARY);
@@ -955,7 +997,7 @@ int mf_path_limit_f64(const double* d_unstab, const double* d_stab, int n, int W
         return MF_ERR_INVALID_ARG;
     }
     const size_t path = (size_t)n * (size_t)(R + 1) * (size_t)(C + 1) * 2 * sizeof(double), words = (size_t)n * sizeof(int32_t);
-    const struct { const void* at; size_t bytes; } in[3] = {{d_unstab, path}, {d_stab, path}, {d_k_prev, d_k_prev ? sizeof(int32_t) : 0}},
+    const struct { const void* at; size_t bytes; } in[3] = {{d_unstab, path}, {d_stab, path}, {d_k_prev, d_k_prev ? carried * sizeof(int32_t) : 0}},
                                                    out[3] = {{d_k_raw, words}, {d_k, words}, {d_out, path}};
     for (int a = 0; a < 3; ++a) {
         for (const auto& i : in)
@@ -963,8 +1005,29 @@ int mf_path_limit_f64(const double* d_unstab, const double* d_stab, int n, int W
         for (int b = a + 1; b < 3; ++b)
             if (overlap(out[a].at, out[a].bytes, out[b].at, out[b].bytes)) { set_error("%s: two of the outputs alias", name); return MF_ERR_INVALID_ARG; }
     }
+    return MF_OK;
+}
+
+int mf_path_limit_f64(const double* d_unstab, const double* d_stab, int n, int W, int H, int R, int C, int left, int top, int right, int bottom,
+                      double guard, int steps, int rise, const int32_t* d_k_prev, int32_t* d_k_raw, int32_t* d_k, double* d_out, void* stream)
+{
+    const int rc = path_limit_checks("mf_path_limit_f64", d_unstab, d_stab, n, W, H, R, C, left, top, right, bottom, guard, steps, rise, d_k_prev, 1,
+                                     d_k_raw, d_k, d_out);
+    if (rc != MF_OK) return rc;
     return launch_path_limit(d_unstab, d_stab, n, W, H, R, C, left, top, right, bottom, guard, steps, rise, d_k_prev, d_k_raw, d_k, d_out,
                              (hipStream_t)stream);
+}
+
+int mf_path_limit_group_f64(const double* d_unstab, const double* d_stab, int K, int W, int H, int R, int C, int left, int top, int right, int bottom,
+                            double guard, int steps, int rise, const int32_t* d_k_prev, int32_t* d_k_raw, int32_t* d_k, double* d_out, void* stream)
+{
+    const char* name = "mf_path_limit_group_f64";
+    const int rc = path_limit_checks(name, d_unstab, d_stab, K, W, H, R, C, left, top, right, bottom, guard, steps, rise, d_k_prev,
+                                     K > 0 ? (size_t)K : 0, d_k_raw, d_k, d_out);
+    if (rc != MF_OK) return rc;
+    if (!d_k_prev) { set_error("%s: null pointer (d_k_prev holds a word per row; a negative word says that nothing is carried)", name); return MF_ERR_INVALID_ARG; }
+    return launch_path_limit_group(d_unstab, d_stab, K, W, H, R, C, left, top, right, bottom, guard, steps, rise, d_k_prev, d_k_raw, d_k, d_out,
+                                   (hipStream_t)stream);
 }
 
 int mf_stability_score_f64(const double* d_stab, int F, int S, double* d_series, double* d_score, void* stream)

@@ -22,6 +22,7 @@
 //
 // distance_kernel: one workgroup of 256 lanes per frame, lane c takes counter c of the frame and of the one before (d_sig_prev for frame 0;
 // without it frame 0's distance is 0), |a - b| summed over the workgroup in a fixed tree.  No atomics.  A distance is at most 2 H W < 2^31.
+// distance_pairs_kernel: the same workgroup with row r's predecessor taken from a second stack, prev[r] (mf_cut_distance_pairs_i32).
 #include "mf_common.h"
 #include "cuts_body.h"
 
@@ -51,23 +52,36 @@ __global__ void __launch_bounds__(cuts::LANES) signature_kernel(const uint8_t* _
     if (lane16 == 0 && sum != 0) atomicAdd(sig + ((size_t)frame * cuts::COUNTERS + (size_t)tile * BINS + bin), (int32_t)sum);
 }
 
-__global__ void __launch_bounds__(cuts::LANES) distance_kernel(const int32_t* __restrict__ prev, const int32_t* __restrict__ sig,
-                                                               int32_t* __restrict__ dist)
+// *dist = the distance of the signatures `before` (null: 0) and `now`, by the workgroup's 256 lanes.
+__device__ __forceinline__ void store_distance(const int32_t* __restrict__ before, const int32_t* __restrict__ now, int32_t* __restrict__ dist)
 {
     __shared__ uint32_t waves[cuts::LANES / 64];
     const uint32_t tid = threadIdx.x;
-    const size_t frame = blockIdx.x;
-    const int32_t* const before = frame ? sig + (frame - 1) * cuts::COUNTERS : prev;
     uint32_t d = 0;
     if (before) {
-        const int32_t a = before[tid], b = sig[frame * cuts::COUNTERS + tid];
+        const int32_t a = before[tid], b = now[tid];
         d = (uint32_t)(a > b ? a - b : b - a);
     }
 #pragma unroll
     for (int step = 32; step >= 1; step >>= 1) d += __shfl_xor(d, step, 64);
     if ((tid & 63u) == 0) waves[tid >> 6] = d;
     __syncthreads();
-    if (tid == 0) dist[frame] = (int32_t)((waves[0] + waves[1]) + (waves[2] + waves[3]));
+    if (tid == 0) *dist = (int32_t)((waves[0] + waves[1]) + (waves[2] + waves[3]));
+}
+
+__global__ void __launch_bounds__(cuts::LANES) distance_kernel(const int32_t* __restrict__ prev, const int32_t* __restrict__ sig,
+                                                               int32_t* __restrict__ dist)
+{
+    const size_t frame = blockIdx.x;
+    store_distance(frame ? sig + (frame - 1) * cuts::COUNTERS : prev, sig + frame * cuts::COUNTERS, dist + frame);
+}
+
+// Row r against ITS OWN predecessor prev[r] (mf_cut_distance_pairs_i32): the rows are frames of different streams.
+__global__ void __launch_bounds__(cuts::LANES) distance_pairs_kernel(const int32_t* __restrict__ prev, const int32_t* __restrict__ sig,
+                                                                     int32_t* __restrict__ dist)
+{
+    const size_t row = blockIdx.x;
+    store_distance(prev + row * cuts::COUNTERS, sig + row * cuts::COUNTERS, dist + row);
 }
 
 int launch_frame_signature(const uint8_t* luma, int n, int W, int H, int32_t* sig, hipStream_t st)
@@ -92,6 +106,13 @@ int launch_frame_signature(const uint8_t* luma, int n, int W, int H, int32_t* si
 int launch_cut_distance(const int32_t* prev, const int32_t* sig, int n, int32_t* dist, hipStream_t st)
 {
     hipLaunchKernelGGL(distance_kernel, dim3((unsigned)n), dim3(cuts::LANES), 0, st, prev, sig, dist);
+    MF_HIP_TRY(hipGetLastError());
+    return MF_OK;
+}
+
+int launch_cut_distance_pairs(const int32_t* prev, const int32_t* sig, int n, int32_t* dist, hipStream_t st)
+{
+    hipLaunchKernelGGL(distance_pairs_kernel, dim3((unsigned)n), dim3(cuts::LANES), 0, st, prev, sig, dist);
     MF_HIP_TRY(hipGetLastError());
     return MF_OK;
 }

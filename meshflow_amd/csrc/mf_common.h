@@ -390,12 +390,20 @@ int launch_online_smooth(const float* vel, const double* lam_known, const double
 int launch_online_smooth_lag(const float* vel, const double* lam_known, const double* taps, int n, int S, int omega, int L, int lag, int iters,
                              double beta, double lam_newest, long long seen, double* c_state, double* q_state, double* lam_state,
                              double* c_out, double* p_out, hipStream_t st);
-// cuts.hip: mf_frame_signature_u8 and mf_cut_distance_i32 behind capi.hip's checks
+// ... and mf_online_smooth_group_f64: K rows of n frames, row r on the state slices of stream ids[r] of B
+int launch_online_smooth_group(const float* vel, const double* lam_known, const double* taps, const int32_t* ids, const long long* seen, int K,
+                               int B, int n, int S, int omega, int L, int iters, double beta, double lam_newest, double* c_state, double* q_state,
+                               double* lam_state, double* c_out, double* p_out, hipStream_t st);
+// cuts.hip: mf_frame_signature_u8, mf_cut_distance_i32 and mf_cut_distance_pairs_i32 behind capi.hip's checks
 int launch_frame_signature(const uint8_t* luma, int n, int W, int H, int32_t* sig, hipStream_t st);
 int launch_cut_distance(const int32_t* prev, const int32_t* sig, int n, int32_t* dist, hipStream_t st);
+int launch_cut_distance_pairs(const int32_t* prev, const int32_t* sig, int n, int32_t* dist, hipStream_t st);
 // path_limit.hip: mf_path_limit_f64 behind capi.hip's checks
 int launch_path_limit(const double* unstab, const double* stab, int n, int W, int H, int R, int C, int left, int top, int right, int bottom,
                       double guard, int steps, int rise, const int32_t* k_prev, int32_t* k_raw, int32_t* k, double* out, hipStream_t st);
+// ... and mf_path_limit_group_f64: K frames of K streams, k_prev [K]
+int launch_path_limit_group(const double* unstab, const double* stab, int K, int W, int H, int R, int C, int left, int top, int right, int bottom,
+                            double guard, int steps, int rise, const int32_t* k_prev, int32_t* k_raw, int32_t* k, double* out, hipStream_t st);
 int launch_selftest_sqrt(unsigned long long n, unsigned long long seed, unsigned long long* d_mismatches, hipStream_t st);
 int launch_stability_score(const double* stab, int F, int S, double* ratio, double* score, hipStream_t st);
 int launch_crop_reduce(const int32_t* crop, int n, int W, int H, int32_t* bounds, hipStream_t st);

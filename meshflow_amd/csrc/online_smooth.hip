@@ -29,6 +29,11 @@
 // Fixed lag (mf_online_smooth_lag_f64; tests/online_lag_model.py): window xi's solution also holds refined values of frames xi - 1,
 // xi - 2, ...; the lagged kernel hands out frame xi - lag -- the registers c and x of the lane whose age is `lag`, after the last sweep --
 // instead of the newest.  Both kernels are online_smooth_body.h, included with MF_ONLINE_LAG 0 and 1; they differ in that store alone.
+//
+// Groups (mf_online_smooth_group_f64): K rows of n frames, each row a different stream of B whose states lie stacked.  The grid is (S, K):
+// workgroup (s, r) sets up row r's slices -- its velocities, weights and outputs, its stream's three state slices, its stream's `seen` -- under
+// the names the body reads and then IS the plain kernel's text, so a row's bytes are those of the single call on those slices.  A row whose
+// stream id is outside 0 .. B - 1, or whose `seen` is negative, touches no memory.  The weights launch is one workgroup per row.
 #include "mf_common.h"
 
 namespace mf {
@@ -59,11 +64,34 @@ __global__ __launch_bounds__(64) void online_smooth_lag_kernel(const float* __re
 #undef MF_ONLINE_LAG
 }
 
-// lam_state row j: frame seen + n - (L - 1) + j.  One workgroup, after the sweep kernel on the same stream.
-__global__ __launch_bounds__(64) void online_lam_state_kernel(const double* __restrict__ lam_known, int n, int L, double lam_newest,
-                                                              long long seen, double* lam_state)
+// The plain kernel per row r = blockIdx.y of a group: the body's names are bound to the row's slices in front of it.
+__global__ __launch_bounds__(64) void online_smooth_group_kernel(const float* __restrict__ vel_rows, const double* __restrict__ lam_known_rows,
+                                                                 const double* __restrict__ taps, const int32_t* __restrict__ ids,
+                                                                 const long long* __restrict__ seen_rows, int B, int n, int S, int omega, int L,
+                                                                 int iters, double beta, double lam_newest, double* c_stack, double* q_stack,
+                                                                 const double* __restrict__ lam_stack, double* __restrict__ c_out_rows,
+                                                                 double* __restrict__ p_out_rows)
 {
-    const int j = threadIdx.x;
+    const size_t r = blockIdx.y, held = (size_t)(L - 1), block = (size_t)n * (size_t)S;
+    const int id = ids[r];
+    const long long seen = seen_rows[r];
+    if ((unsigned)id >= (unsigned)B || seen < 0) return;                     // (workgroup-uniform, before the first barrier)
+    const float* __restrict__ vel = vel_rows + r * block;
+    const double* __restrict__ lam_known = lam_known_rows + r * (size_t)n;
+    double* c_state = c_stack + (size_t)id * held * (size_t)S;
+    double* q_state = q_stack + (size_t)id * held * (size_t)S;
+    const double* __restrict__ lam_state = lam_stack + (size_t)id * held;
+    double* __restrict__ c_out = c_out_rows + r * block;
+    double* __restrict__ p_out = p_out_rows + r * block;
+#define MF_ONLINE_LAG 0
+#include "online_smooth_body.h"
+#undef MF_ONLINE_LAG
+}
+
+// What lane j of a weights launch stores in lam_state row j: frame seen + n - (L - 1) + j.
+__device__ __forceinline__ double shifted_lam(const double* __restrict__ lam_known, int n, int L, double lam_newest, long long seen,
+                                              const double* lam_state, int j)
+{
     double v = 0.0;
     if (j < L - 1) {
         const long long t = seen + n - (L - 1) + j;
@@ -71,6 +99,30 @@ __global__ __launch_bounds__(64) void online_lam_state_kernel(const double* __re
         else if (t >= 0 && t >= seen - 1) v = lam_known[t - seen + 1];      // (t >= 0: entry 0 of an empty state is not read)
         else if (t >= 0) v = lam_state[j + n];                               // frame t was row t - (seen - (L - 1)) = j + n
     }
+    return v;
+}
+
+// lam_state row j: frame seen + n - (L - 1) + j.  One workgroup, after the sweep kernel on the same stream.
+__global__ __launch_bounds__(64) void online_lam_state_kernel(const double* __restrict__ lam_known, int n, int L, double lam_newest,
+                                                              long long seen, double* lam_state)
+{
+    const int j = threadIdx.x;
+    const double v = shifted_lam(lam_known, n, L, lam_newest, seen, lam_state, j);
+    __syncthreads();
+    if (j < L - 1) lam_state[j] = v;
+}
+
+// ... and of a group: workgroup r shifts the weights of row r's stream, skipping the rows the sweep kernel skipped.
+__global__ __launch_bounds__(64) void online_lam_state_group_kernel(const double* __restrict__ lam_known_rows, const int32_t* __restrict__ ids,
+                                                                    const long long* __restrict__ seen_rows, int B, int n, int L,
+                                                                    double lam_newest, double* lam_stack)
+{
+    const size_t r = blockIdx.x;
+    const int id = ids[r], j = threadIdx.x;
+    const long long seen = seen_rows[r];
+    if ((unsigned)id >= (unsigned)B || seen < 0) return;                     // (workgroup-uniform, before the barrier)
+    double* lam_state = lam_stack + (size_t)id * (size_t)(L - 1);
+    const double v = shifted_lam(lam_known_rows + r * (size_t)n, n, L, lam_newest, seen, lam_state, j);
     __syncthreads();
     if (j < L - 1) lam_state[j] = v;
 }
@@ -98,6 +150,19 @@ int launch_online_smooth_lag(const float* vel, const double* lam_known, const do
                                                                 c_state, q_state, lam_state, c_out, p_out);
     MF_HIP_TRY(hipGetLastError());
     online_lam_state_kernel<<<1, 64, 0, st>>>(lam_known, n, L, lam_newest, seen, lam_state);
+    MF_HIP_TRY(hipGetLastError());
+    return MF_OK;
+}
+
+int launch_online_smooth_group(const float* vel, const double* lam_known, const double* taps, const int32_t* ids, const long long* seen, int K,
+                               int B, int n, int S, int omega, int L, int iters, double beta, double lam_newest, double* c_state, double* q_state,
+                               double* lam_state, double* c_out, double* p_out, hipStream_t st)
+{
+    static_assert(MF_ONLINE_GROUP_MAX_ROWS <= 65535, "a row per grid y");
+    online_smooth_group_kernel<<<dim3((unsigned)S, (unsigned)K), 64, 0, st>>>(vel, lam_known, taps, ids, seen, B, n, S, omega, L, iters, beta,
+                                                                               lam_newest, c_state, q_state, lam_state, c_out, p_out);
+    MF_HIP_TRY(hipGetLastError());
+    online_lam_state_group_kernel<<<dim3((unsigned)K), 64, 0, st>>>(lam_known, ids, seen, B, n, L, lam_newest, lam_state);
     MF_HIP_TRY(hipGetLastError());
     return MF_OK;
 }

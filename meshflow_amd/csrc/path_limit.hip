@@ -17,6 +17,9 @@
 // An integer minimum over the wavefront gives k_t; the 64 lanes then stride over the frame's S series.  k_t == K copies p, k_t == 0 copies c:
 // bit for bit, a NaN included.  The carry is read from the device; there is no wait and no atomic anywhere, so the same inputs give the
 // same bytes.
+//
+// path_limit_apply_rows_kernel (mf_path_limit_group_f64): the rows are frames of different streams, each with a carried step of its own; the
+// test kernel is per frame already and runs as it is.
 #include "mf_common.h"
 #include "path_limit_body.h"
 
@@ -67,6 +70,18 @@ __global__ __launch_bounds__(plimit::LANES) void path_limit_test_kernel(const do
     if (lane == 0) k_raw[blockIdx.x] = plimit::leading_passes(verdicts);
 }
 
+// The scaling statement of both apply kernels: the 64 lanes stride over the S series of the row that starts at `row`.
+__device__ __forceinline__ void scale_row(const double* __restrict__ unstab, const double* __restrict__ stab, size_t row, int S, int k, int steps,
+                                          int lane, double* __restrict__ out)
+{
+    const double f = (double)k / (double)steps;
+    for (int s = lane; s < S; s += plimit::LANES) {
+        const double c = unstab[row + s], p = stab[row + s];
+        const double scaled = c + f * (p - c);
+        out[row + s] = k == steps ? p : (k == 0 ? c : scaled);
+    }
+}
+
 __global__ __launch_bounds__(plimit::LANES) void path_limit_apply_kernel(const double* __restrict__ unstab, const double* __restrict__ stab,
                                                                          const int32_t* __restrict__ k_raw, const int32_t* __restrict__ k_prev,
                                                                          int S, int steps, int rise, int32_t* __restrict__ k_out,
@@ -89,14 +104,28 @@ __global__ __launch_bounds__(plimit::LANES) void path_limit_apply_kernel(const d
     }
     const int k = term < steps ? term : steps;
     if (lane == 0) k_out[t] = k;
+    scale_row(unstab, stab, (size_t)t * (size_t)S, S, k, steps, lane, out);
+}
 
-    const size_t row = (size_t)t * (size_t)S;
-    const double f = (double)k / (double)steps;
-    for (int s = lane; s < S; s += plimit::LANES) {
-        const double c = unstab[row + s], p = stab[row + s];
-        const double scaled = c + f * (p - c);
-        out[row + s] = k == steps ? p : (k == 0 ? c : scaled);
+// The apply step of a group (mf_path_limit_group_f64): row t is a frame of a stream of its own with its own carried step, so nothing is
+// chained between rows: k = min(steps, k_raw[t], clamp(k_prev[t], 0, steps) + rise), the rise term left out where k_prev[t] is negative --
+// what path_limit_apply_kernel gives a one-frame call with that k_prev, or with none.  Every lane forms the same k (wave-uniform loads).
+__global__ __launch_bounds__(plimit::LANES) void path_limit_apply_rows_kernel(const double* __restrict__ unstab, const double* __restrict__ stab,
+                                                                              const int32_t* __restrict__ k_raw, const int32_t* __restrict__ k_prev,
+                                                                              int S, int steps, int rise, int32_t* __restrict__ k_out,
+                                                                              double* __restrict__ out)
+{
+    const int lane = threadIdx.x;
+    const size_t t = blockIdx.x;
+    int k = k_raw[t];
+    const int carried = k_prev[t];
+    if (carried >= 0) {
+        const int risen = (carried > steps ? steps : carried) + rise;
+        k = risen < k ? risen : k;
     }
+    k = k < steps ? k : steps;
+    if (lane == 0) k_out[t] = k;
+    scale_row(unstab, stab, t * (size_t)S, S, k, steps, lane, out);
 }
 
 }  // namespace
@@ -110,6 +139,18 @@ int launch_path_limit(const double* unstab, const double* stab, int n, int W, in
     path_limit_test_kernel<<<dim3((unsigned)n), plimit::LANES, 0, st>>>(unstab, stab, W, H, R, C, rect, steps, k_raw);
     MF_HIP_TRY(hipGetLastError());
     path_limit_apply_kernel<<<dim3((unsigned)n), plimit::LANES, 0, st>>>(unstab, stab, k_raw, k_prev, (R + 1) * (C + 1) * 2, steps, rise, k, out);
+    MF_HIP_TRY(hipGetLastError());
+    return MF_OK;
+}
+
+int launch_path_limit_group(const double* unstab, const double* stab, int K, int W, int H, int R, int C, int left, int top, int right, int bottom,
+                            double guard, int steps, int rise, const int32_t* k_prev, int32_t* k_raw, int32_t* k, double* out, hipStream_t st)
+{
+    const plimit::Rect rect = plimit::guarded(left, top, right, bottom, guard);
+    path_limit_test_kernel<<<dim3((unsigned)K), plimit::LANES, 0, st>>>(unstab, stab, W, H, R, C, rect, steps, k_raw);
+    MF_HIP_TRY(hipGetLastError());
+    path_limit_apply_rows_kernel<<<dim3((unsigned)K), plimit::LANES, 0, st>>>(unstab, stab, k_raw, k_prev, (R + 1) * (C + 1) * 2, steps, rise, k,
+                                                                               out);
     MF_HIP_TRY(hipGetLastError());
     return MF_OK;
 }

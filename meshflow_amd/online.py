@@ -12,7 +12,10 @@ which a push finds the cuts in its frames and restarts the path at each, and -- 
 lag=k >= 1 trades k frames of latency for a smoother path (profiles/online_lag.md): the smoother is `ops.online_smooth_lag`
 (mf_online_smooth_lag_f64; tests/online_lag_model.py), which hands a frame out as it stands in the window that ends k frames after it, so a
 push returns the frames that have become final, [emitted, seen - k), and the session also carries the pixels of the at most k frames it still
-owes, as clones on the device (`hold_frames`).  `flush()` hands those out when the stream -- or, with on_cut='reset', a shot -- ends."""
+owes, as clones on the device (`hold_frames`).  `flush()` hands those out when the stream -- or, with on_cut='reset', a shot -- ends.
+
+Many live streams of one size go through an `OnlineGroup` (`MeshFlowStabilizer.online_group`; profiles/online_group.md): one new frame of each
+of any subset of them per push, in one set of launches, with the bytes of a session per stream."""
 import collections
 import math
 
@@ -373,3 +376,139 @@ class OnlineSession:
         covered = (crop[:, 0] <= left) & (crop[:, 1] <= top) & (crop[:, 2] >= right) & (crop[:, 3] >= bottom)
         shape = (n, R + 1, C + 1, 2)
         return out, OnlineReport(first, c.view(shape), p.view(shape), self.rectangle, covered, lost), k
+
+
+class OnlineGroup:
+    """`streams` live streams of one size and form through `stabilizer`, a frame of each of any subset per `push`, in ONE set of launches
+    whatever the subset's size.  Made by `MeshFlowStabilizer.online_group`, which documents the keywords.  What a stream gets is what an
+    `OnlineSession` of its own with the same keywords, pushed its frames one at a time, returns, byte for byte: every stage shared between
+    the streams works per pair or per frame, and the three that carry a stream's memory have a batched form that restates the single one per
+    row -- `ops.online_smooth_group`, `ops.path_limit_group`, `ops.cut_distance_pairs`.
+    The keywords are checked, and the rectangle, taps and crop fixed at the first push, by an `OnlineSession` that is never pushed
+    (`settings`): one copy of those rules.  Per stream the group carries, on the device: its slices of an `ops.OnlineGroupState`, its last
+    luma frame (B, H, W), that frame's signature (B, 256) and the limiter's last step (B,), -1 where nothing is carried; on the host: `seen`
+    and `shots`."""
+
+    def __init__(self, stabilizer, streams, **keywords):
+        if isinstance(streams, bool) or not isinstance(streams, (int, np.integer)) or int(streams) < 1:
+            raise ValueError(f'streams must be an int >= 1 (got {streams!r})')
+        if keywords.get('lag', 0) != 0 or isinstance(keywords.get('lag', 0), bool):
+            raise ValueError(f"a group takes lag=0 only (got {keywords['lag']!r}): the pixels held per stream and a flush per stream are not "
+                             'built; use an online_session per stream for look-ahead')
+        if keywords.get('on_lost', 'hold') == 'raise':
+            raise ValueError(f"a group takes on_lost='hold' only (got {keywords['on_lost']!r}): one stream's lost pair must not stop the "
+                             "others; it is reported in that stream's report.lost")
+        self.streams = int(streams)
+        self.settings = OnlineSession(stabilizer, **keywords)
+        self.stabilizer, self.device = stabilizer, self.settings.device
+        self.state = self._last_luma = self._last_sig = self._k_prev = None       # made by the first push, which fixes the frame size
+        self.shots = [0] * self.streams
+        # of the last push, per pushed row: the limiter's (K,) int32 k on the device (on_uncovered='limit'); the rows at which a cut was
+        # found and the (K,) int32 distances, 0 for a stream with no frame before (on_cut='reset')
+        self.last_limit, self.last_cuts, self.last_cut_distances = None, [], None
+
+    form = property(lambda self: self.settings.form)
+    rectangle = property(lambda self: self.settings.rectangle)
+
+    @property
+    def seen(self):
+        """The frames of each stream's path since its last reset: a list of `streams` ints."""
+        return list(self.state.seen) if self.state is not None else [0] * self.streams
+
+    def reset(self, stream=None):
+        """Forget every frame of `stream` (None: of every stream), as `OnlineSession.reset` does for its one: the stream's next frame
+        starts a path at frame 0 and is no cut.  No byte of the state is cleared: a stream at seen = 0 reads none of it."""
+        from . import ops
+        ids = list(range(self.streams)) if stream is None else ops.check_streams([stream], self.streams, 'stream')
+        if self.state is not None:
+            for b in ids:
+                self.state.reset(b)
+            self._k_prev[ids] = -1
+
+    def push(self, frames, streams=None):
+        """One new frame of each stream of `streams` (K distinct indices, any order; None: all of them, in order): a stack (K, ...) in any
+        form a session takes, row r the frame of streams[r].  Returns (the K frames stabilized and cropped, in the input's form, a list of
+        K `OnlineReport`): row r and report r belong to streams[r] and hold what that stream's own session would have returned for the
+        frame.  A stream at its first frame, after `reset(stream)` or at a cut found is not tracked: it pushes a zero velocity at seen = 0."""
+        import torch
+        from . import _lib, ops
+        cfg, s = self.settings, self.stabilizer
+        ids = ops.check_streams(range(self.streams) if streams is None else streams, self.streams)
+        K = len(ids)
+        if cfg.form is None and cfg.on_uncovered == 'limit':
+            cfg._check_limit_fits(frames)
+        form, luma = luma_of(frames, cfg.red_first)
+        n, H, W = (int(v) for v in luma.shape)
+        if n != K:
+            raise ValueError(f'push takes one frame per pushed stream: {K} streams, {n} frames')
+        if cfg.form is None:
+            cfg._start(form, H, W)
+            self.state = ops.OnlineGroupState(self.streams, cfg.state.S, cfg.window, self.device)
+            self._last_luma = torch.empty((self.streams, H, W), dtype=torch.uint8, device=self.device)
+            self._last_sig = torch.zeros((self.streams, _lib.CUT_COUNTERS), dtype=torch.int32, device=self.device)
+            self._k_prev = torch.full((self.streams,), -1, dtype=torch.int32, device=self.device)
+        elif form != cfg.form:
+            raise ValueError(f'this group takes {cfg.form.dtype} frames of shape {cfg.form.shape}{" as (d_y, d_uv) pairs" if cfg.form.pair else ""}; '
+                             f'got {form.dtype} frames of shape {form.shape}{" as a pair" if form.pair else ""}')
+        R, C, S, seen = s.mesh_row_count, s.mesh_col_count, self.state.S, self.state.seen
+        d_ids = torch.tensor(ids, dtype=torch.int64, device=self.device)
+
+        # cuts: every row against its own stream's last signature, one wait for the K distances
+        cuts, distances = [], None
+        if cfg.on_cut == 'reset':
+            sig = ops.frame_signatures(luma)
+            distances = ops.cut_distance_pairs(self._last_sig[d_ids], sig).cpu().numpy()
+            distances[np.array([seen[b] == 0 for b in ids])] = 0           # no frame before: nothing to be far from, never a cut
+            cuts = [int(r) for r in np.nonzero(distances.astype(np.int64) > ops.cut_bound(cfg.cut_threshold, W, H))[0]]
+            self._last_sig[d_ids] = sig
+            for r in cuts:                                                 # (the pair across a cut is never tracked)
+                self.reset(ids[r])
+        self.last_cuts, self.last_cut_distances = cuts, distances
+
+        # the pairs (a stream's last luma -> its new frame) of the streams that have a frame before, through the tracker together
+        first = [seen[b] for b in ids]
+        rows = [r for r in range(K) if first[r] > 0]
+        vel = torch.zeros((K, 1, S), dtype=torch.float32, device=self.device)
+        lam_known = np.full((K, 1), cfg._lam_newest)
+        lost = [[] for _ in ids]
+        if rows:
+            everyone = len(rows) == K
+            d_rows = None if everyone else torch.tensor(rows, dtype=torch.int64, device=self.device)
+            early = self._last_luma[d_ids if everyone else d_ids[d_rows]]
+            late = luma if everyone else luma[d_rows]
+            early, late, offsets, kmax, d_hom, d_info = cfg.tracker.track_stacks_resident(early, late, cfg.chunk_pairs)
+            _, d_vel, status = ops.vertex_motion(early, late, offsets, d_hom, kmax, W, H, R, C, s.feature_ellipse_row_count,
+                                                 s.feature_ellipse_col_count)
+            homographies, info = d_hom.cpu().numpy(), d_info.cpu().numpy()          # (the one wait of a push beyond the tracker's own)
+            ops.vertex_motion_check(status)
+            bad = np.nonzero(info[:, 0] != _lib.HFIT_OK)[0]
+            d_vel = d_vel.reshape(-1, 1, S)
+            if bad.size:                                                            # 'hold': no motion for such a pair (`OnlineSession`)
+                d_vel = d_vel.index_fill(0, torch.from_numpy(bad).to(self.device), 0.0)
+                for b in bad:
+                    lost[rows[int(b)]] = [first[rows[int(b)]]]
+            if everyone:
+                vel = d_vel.contiguous()
+            else:
+                vel[d_rows] = d_vel
+            lam_known[rows, 0] = host.adaptive_weights(len(homographies), W, H, cfg.definition, homographies)
+        c, p = ops.online_smooth_group(vel, torch.from_numpy(lam_known).to(self.device), self.state, ids, cfg._taps, cfg.omega, cfg.iters,
+                                       cfg.beta, cfg._lam_newest)
+        c, p = c.view(K, S), p.view(K, S)
+        self._last_luma[d_ids] = luma
+        for r, b in enumerate(ids):
+            self.shots[b] += int(first[r] == 0)
+
+        k = None
+        if cfg.on_uncovered == 'limit':
+            p, k = ops.path_limit_group(c, p, W, H, R, C, cfg.rectangle, cfg.limit_steps, cfg.limit_guard, cfg.limit_rise, self._k_prev[d_ids])
+            self._k_prev[d_ids] = k
+        self.last_limit = k
+        table = ops.cell_table(c, p, W, H, R, C)
+        out = form.warp_crop(frames, table, s.color_outside_image_area_bgr, cfg._crop)
+        table.check()
+        crop = table.crop
+        left, top, right, bottom = cfg.rectangle
+        covered = (crop[:, 0] <= left) & (crop[:, 1] <= top) & (crop[:, 2] >= right) & (crop[:, 3] >= bottom)
+        c, p = c.view(K, R + 1, C + 1, 2), p.view(K, R + 1, C + 1, 2)
+        return out, [OnlineReport(first[r], c[r:r + 1], p[r:r + 1], cfg.rectangle, covered[r:r + 1], lost[r]) for r in range(K)]

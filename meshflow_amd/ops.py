@@ -1007,6 +1007,82 @@ def _online_smooth_args(name, vel, lam_known, state, taps, omega):
     return n
 
 
+class OnlineGroupState:
+    """The `OnlineState` of B streams stacked, for `online_smooth_group` (mf_online_smooth_group_f64): `c`, `q` (B, L - 1, S) and `lam`
+    (B, L - 1) float64 on `device`, and `seen`, a host list of B frame counts.  `reset(stream)` forgets one stream -- its count goes to 0,
+    at which the kernel reads none of its slices, so no byte is cleared --, `reset()` all of them."""
+
+    def __init__(self, B, S, L, device):
+        B, S, L = int(B), int(S), int(L)
+        if B < 1 or S < 1 or not 2 <= L <= _lib.ONLINE_MAX_WINDOW:
+            raise ValueError(f'OnlineGroupState: B and S must be at least 1 and L in 2 .. {_lib.ONLINE_MAX_WINDOW} (got B={B}, S={S}, L={L})')
+        self.B, self.S, self.L = B, S, L
+        self.c = torch.zeros((B, L - 1, S), dtype=torch.float64, device=device)
+        self.device = self.c.device
+        self.q = torch.zeros((B, L - 1, S), dtype=torch.float64, device=self.device)
+        self.lam = torch.zeros((B, L - 1), dtype=torch.float64, device=self.device)
+        self.seen = [0] * B
+
+    def reset(self, stream=None):
+        for b in (range(self.B) if stream is None else check_streams([stream], self.B, 'OnlineGroupState.reset: stream')):
+            self.seen[b] = 0
+
+
+def check_streams(streams, B, name='streams'):
+    """`streams` as a list of ints: ints (no bool), distinct, each in 0 .. B - 1, at least one; else ValueError."""
+    try:
+        ids = list(streams)
+    except TypeError:
+        raise ValueError(f'{name} must be a sequence of stream indices (got {streams!r})') from None
+    if not ids or any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) for v in ids):
+        raise ValueError(f'{name} must be a non-empty sequence of ints (got {streams!r})')
+    ids = [int(v) for v in ids]
+    if any(not 0 <= v < B for v in ids):
+        raise ValueError(f'{name} must lie in 0 .. {B - 1} (got {ids})')
+    if len(set(ids)) != len(ids):
+        raise ValueError(f'{name} must be distinct: a stream takes one row per call (got {ids})')
+    return ids
+
+
+def online_smooth_group(vel, lam_known, state, streams, taps, omega, iters, beta, lam_newest):
+    """`online_smooth` for K rows of n new frames, row r of stream streams[r] of `state`, an `OnlineGroupState`, in one pair of launches
+    (mf_online_smooth_group_f64): every row's bytes are `online_smooth`'s on an `OnlineState` of that stream's history.  vel: (K, n, S)
+    float32; lam_known: (K, n) float64; streams: K ints (no bool), distinct, in 0 .. state.B - 1; taps, omega, iters, beta, lam_newest are
+    shared.  Returns (c, p), (K, n, S) float64; the named streams' slices of `state` are updated in place and their `seen` advanced by n, the
+    others keep their bytes.  The ids and counts go up in one small copy; runs on torch's current stream and does not wait for it."""
+    name = 'online_smooth_group'
+    if not isinstance(state, OnlineGroupState):
+        raise ValueError(f'{name}: state must be an OnlineGroupState')
+    ids = check_streams(streams, state.B, f'{name}: streams')
+    K = len(ids)
+    _need(vel, torch.float32, 'vel')
+    _need(lam_known, torch.float64, 'lam_known')
+    _need(taps, torch.float64, 'taps')
+    n = int(vel.shape[1]) if vel.dim() == 3 else 0
+    if n < 1 or tuple(vel.shape) != (K, n, state.S):
+        raise ValueError(f'{name}: vel must have shape ({K}, n, {state.S}) with n >= 1, got {tuple(vel.shape)}')
+    if tuple(lam_known.shape) != (K, n):
+        raise ValueError(f'{name}: lam_known must have shape ({K}, {n}), got {tuple(lam_known.shape)}')
+    if tuple(taps.shape) != (int(omega),):
+        raise ValueError(f'{name}: taps must have shape ({int(omega)},), got {tuple(taps.shape)}')
+    for t, what in ((vel, 'vel'), (lam_known, 'lam_known'), (taps, 'taps')):
+        if t.device != state.device:
+            raise ValueError(f'{name}: {what} must be on the device of the state, {state.device}, got {t.device}')
+    # one upload: K int64 counts, then K int32 ids behind them (8-byte aligned in front, 4-byte behind)
+    rows = np.empty(K * 3, dtype=np.int32)
+    rows[:2 * K].view(np.int64)[:] = [state.seen[b] for b in ids]
+    rows[2 * K:] = ids
+    d_rows = torch.from_numpy(rows).to(state.device, non_blocking=True)
+    c = torch.empty((K, n, state.S), dtype=torch.float64, device=state.device)
+    p = torch.empty((K, n, state.S), dtype=torch.float64, device=state.device)
+    _lib.check(_lib_.mf_online_smooth_group_f64(_ptr(vel), _ptr(lam_known), _ptr(taps), _ptr(d_rows[2 * K:]), _ptr(d_rows), K, state.B, n, state.S,
+                                                int(omega), state.L, int(iters), float(beta), float(lam_newest), _ptr(state.c), _ptr(state.q),
+                                                _ptr(state.lam), _ptr(c), _ptr(p), _stream()))
+    for b in ids:
+        state.seen[b] += n
+    return c, p
+
+
 def check_online_lag(lag, L, name='lag'):
     """`lag` as an int: an int (no bool) in 0 .. L - 1 -- the lagged frame must be in the window, and the state must still hold every frame
     not yet handed out --, else ValueError."""
@@ -1098,6 +1174,22 @@ def cut_distances(d_sig, d_prev=None):
     return dist
 
 
+def cut_distance_pairs(d_prev, d_sig):
+    """`cut_distances` for rows that are frames of n different streams: entry r is the distance of d_sig[r] from d_prev[r], both (n, 256)
+    int32 on the device (mf_cut_distance_pairs_i32).  A (n,) int32 device tensor.  On torch's current stream; does not wait for it."""
+    name = 'cut_distance_pairs'
+    _need(d_sig, torch.int32, 'd_sig')
+    if d_sig.dim() != 2 or d_sig.shape[0] < 1 or d_sig.shape[1] != _lib.CUT_COUNTERS:
+        raise ValueError(f'{name}: d_sig must have shape (n, {_lib.CUT_COUNTERS}) with n >= 1 (got {tuple(d_sig.shape)})')
+    _need(d_prev, torch.int32, 'd_prev')
+    if d_prev.shape != d_sig.shape or d_prev.device != d_sig.device:
+        raise ValueError(f'{name}: d_prev must have shape {tuple(d_sig.shape)} on the device of d_sig (got {tuple(d_prev.shape)} on {d_prev.device})')
+    n = int(d_sig.shape[0])
+    dist = torch.empty(n, dtype=torch.int32, device=d_sig.device)
+    _lib.check(_lib_.mf_cut_distance_pairs_i32(_ptr(d_prev), _ptr(d_sig), n, _ptr(dist), _stream()))
+    return dist
+
+
 def find_cuts(d_luma, threshold=CUT_THRESHOLD, d_prev=None):
     """Where the shots of a (n, H, W) uint8 luma stack on the device begin: (the indices i, relative to the stack, of the frames with
     distance[i] > floor(threshold * 2 H W); the distances as a NumPy (n,) int32 array; the last frame's signature, a (256,) int32 device
@@ -1127,15 +1219,8 @@ def check_path_limit(steps, guard, rise, names=('steps', 'guard', 'rise')):
     return int(steps), float(guard), int(rise)
 
 
-def path_limit(unstab, stab, W, H, R, C, rectangle, steps=PATH_LIMIT_STEPS, guard=PATH_LIMIT_GUARD, rise=PATH_LIMIT_RISE, k_prev=None, out=None):
-    """The stabilized path of n frames limited so that the warped mesh keeps covering `rectangle` (mf_path_limit_f64, bit for bit
-    tests/path_limit_model.py): per frame the correction stab - unstab is scaled by k / steps, k the largest step at which the mesh's
-    perimeter still encloses the rectangle widened by `guard` pixels, falling at once and rising by at most `rise` per frame.
-    unstab, stab: (n, S) or (n, R+1, C+1, 2) float64 device tensors (`cell_table`'s); rectangle: (left, top, right, bottom), inclusive,
-    `crop_resize`'s convention; k_prev: a 1-element int32 device tensor, the last k of the call before (a chain of calls so linked equals one
-    call), None: no frame came before.  out: an (n, S) float64 device tensor to write into.  Returns (limited (n, S) float64, k (n,) int32),
-    device tensors.  On torch's current stream; does not wait for it."""
-    name = 'path_limit'
+def _path_limit_args(name, unstab, stab, W, H, R, C, rectangle, steps, guard, rise, out):
+    """What `path_limit` and `path_limit_group` ask alike; returns (n, the rectangle as ints, steps, guard, rise, out -- made where None)."""
     W, H, R, C = int(W), int(H), int(R), int(C)
     if R < 1 or C < 1 or 2 * (R + C) > _lib.PATH_LIMIT_MAX_BOUNDARY:
         raise ValueError(f'{name}: the mesh needs R, C >= 1 and 2 (R + C) <= {_lib.PATH_LIMIT_MAX_BOUNDARY} (got R={R}, C={C})')
@@ -1156,19 +1241,48 @@ def path_limit(unstab, stab, W, H, R, C, rectangle, steps=PATH_LIMIT_STEPS, guar
         raise ValueError(f'{name}: unstab and stab must both hold (n, {S}) values with n >= 1, got {tuple(unstab.shape)} and {tuple(stab.shape)}')
     if stab.device != unstab.device:
         raise ValueError(f'{name}: stab must be on the device of unstab, {unstab.device}, got {stab.device}')
-    if k_prev is not None:
-        _need(k_prev, torch.int32, 'k_prev')
-        if k_prev.numel() != 1 or k_prev.device != unstab.device:
-            raise ValueError(f'{name}: k_prev must hold 1 int32 on the device of unstab (got {tuple(k_prev.shape)} on {k_prev.device})')
     if out is None:
         out = torch.empty((n, S), dtype=torch.float64, device=unstab.device)
     else:
         _need(out, torch.float64, 'out')
         if tuple(out.shape) != (n, S) or out.device != unstab.device:
             raise ValueError(f'{name}: out must have shape ({n}, {S}) on the device of unstab (got {tuple(out.shape)} on {out.device})')
+    return n, (left, top, right, bottom), steps, guard, rise, out
+
+
+def path_limit(unstab, stab, W, H, R, C, rectangle, steps=PATH_LIMIT_STEPS, guard=PATH_LIMIT_GUARD, rise=PATH_LIMIT_RISE, k_prev=None, out=None):
+    """The stabilized path of n frames limited so that the warped mesh keeps covering `rectangle` (mf_path_limit_f64, bit for bit
+    tests/path_limit_model.py): per frame the correction stab - unstab is scaled by k / steps, k the largest step at which the mesh's
+    perimeter still encloses the rectangle widened by `guard` pixels, falling at once and rising by at most `rise` per frame.
+    unstab, stab: (n, S) or (n, R+1, C+1, 2) float64 device tensors (`cell_table`'s); rectangle: (left, top, right, bottom), inclusive,
+    `crop_resize`'s convention; k_prev: a 1-element int32 device tensor, the last k of the call before (a chain of calls so linked equals one
+    call), None: no frame came before.  out: an (n, S) float64 device tensor to write into.  Returns (limited (n, S) float64, k (n,) int32),
+    device tensors.  On torch's current stream; does not wait for it."""
+    name = 'path_limit'
+    n, (left, top, right, bottom), steps, guard, rise, out = _path_limit_args(name, unstab, stab, W, H, R, C, rectangle, steps, guard, rise, out)
+    if k_prev is not None:
+        _need(k_prev, torch.int32, 'k_prev')
+        if k_prev.numel() != 1 or k_prev.device != unstab.device:
+            raise ValueError(f'{name}: k_prev must hold 1 int32 on the device of unstab (got {tuple(k_prev.shape)} on {k_prev.device})')
     words = torch.empty((2, n), dtype=torch.int32, device=unstab.device)            # k_raw, k
-    _lib.check(_lib_.mf_path_limit_f64(_ptr(unstab), _ptr(stab), n, W, H, R, C, left, top, right, bottom, guard, steps, rise,
+    _lib.check(_lib_.mf_path_limit_f64(_ptr(unstab), _ptr(stab), n, int(W), int(H), int(R), int(C), left, top, right, bottom, guard, steps, rise,
                                        _ptr(k_prev) if k_prev is not None else None, _ptr(words[0]), _ptr(words[1]), _ptr(out), _stream()))
+    return out, words[1]
+
+
+def path_limit_group(unstab, stab, W, H, R, C, rectangle, steps=PATH_LIMIT_STEPS, guard=PATH_LIMIT_GUARD, rise=PATH_LIMIT_RISE, k_prev=None, out=None):
+    """`path_limit` for K rows that are ONE frame each of K different streams (mf_path_limit_group_f64): nothing is chained between the rows;
+    row r gets the bytes of a one-frame `path_limit` call with k_prev[r] carried.  Arguments and checks are `path_limit`'s, but k_prev: a
+    (K,) int32 device tensor, a NEGATIVE entry saying that the row carries nothing (`path_limit`'s k_prev=None), and required.  Returns
+    (limited (K, S) float64, k (K,) int32).  On torch's current stream; does not wait for it."""
+    name = 'path_limit_group'
+    n, (left, top, right, bottom), steps, guard, rise, out = _path_limit_args(name, unstab, stab, W, H, R, C, rectangle, steps, guard, rise, out)
+    _need(k_prev, torch.int32, 'k_prev')
+    if tuple(k_prev.shape) != (n,) or k_prev.device != unstab.device:
+        raise ValueError(f'{name}: k_prev must have shape ({n},) on the device of unstab (got {tuple(k_prev.shape)} on {k_prev.device})')
+    words = torch.empty((2, n), dtype=torch.int32, device=unstab.device)            # k_raw, k
+    _lib.check(_lib_.mf_path_limit_group_f64(_ptr(unstab), _ptr(stab), n, int(W), int(H), int(R), int(C), left, top, right, bottom, guard, steps,
+                                             rise, _ptr(k_prev), _ptr(words[0]), _ptr(words[1]), _ptr(out), _stream()))
     return out, words[1]
 
 

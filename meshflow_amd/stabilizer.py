@@ -420,6 +420,26 @@ class MeshFlowStabilizer:
                                     max_per_subframe, red_first, on_lost, on_cut, cut_threshold, on_uncovered, limit_steps, limit_guard,
                                     limit_rise, lag)
 
+    def online_group(self, streams, **keywords):
+        """`streams` live streams of one frame size and form -- the cameras of one server -- stabilized together: an `online.OnlineGroup`
+        whose `push(frames, streams=None)` takes ONE new frame of each of K distinct streams (a stack (K, ...) in any form a session
+        takes, a (d_y, d_uv) pair of (K, ...) stacks for 4:2:0; `streams` lists the K indices in any order and defaults to all) and
+        returns (the K frames stabilized and cropped, [an `online.OnlineReport` per pushed stream]); row r and report r belong to
+        streams[r].  The keywords are `online_session`'s and mean the same, except lag, which must be 0 (the held pixels and a flush per
+        stream are not built), and on_lost, which must be 'hold' (one camera's lost pair must not stop the others; it is listed in that
+        stream's `report.lost`): both are a ValueError otherwise.
+        The contract: a stream gets the bytes that an `online_session` of its own with the same keywords returns when pushed the same
+        frames one at a time -- frames, d_unstab, d_stab, covered, first, lost, the limiter's k, the cut decisions and distances, shots --
+        in whatever grouping of ticks the frames arrive.  One push issues one set of launches whatever K is: `ops.luma` and the cut
+        signatures once, the K distances in one wait (`ops.cut_distance_pairs`), the pairs (a stream's last luma -> its new frame) of
+        every stream that has a frame before and no cut through the tracker, `ops.vertex_motion`, the one download and
+        `host.adaptive_weights` together, then `ops.online_smooth_group`, `ops.path_limit_group`, one cell table, one warp, one
+        crop-resize (profiles/online_group.md).  A stream at its first frame, after `reset(stream)` or at a cut found is not tracked and
+        starts its path at frame 0.  The group's `seen` and `shots` are lists per stream; `last_limit`, `last_cuts` and
+        `last_cut_distances` are per pushed row of the last push; `reset(stream=None)` forgets one stream or all."""
+        from . import online
+        return online.OnlineGroup(self, streams, **keywords)
+
     def find_cuts(self, clip, threshold=0.30, red_first=False):
         """Where the shots of a resident clip begin: the list of frame indices t in 1 .. F-1 whose tile-histogram distance to frame t - 1
         (`ops.find_cuts`, tests/cuts_model.py) exceeds floor(threshold * 2 H W).  `clip` in any form `stabilize_scored` takes; its luma comes
