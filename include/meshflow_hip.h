@@ -312,6 +312,42 @@ int mf_warp_p010(const uint16_t* d_y, const uint16_t* d_uv, uint16_t* d_out_y, u
 int mf_warp_bounds_p010(const uint16_t* d_y, const uint16_t* d_uv, uint16_t* d_out_y, uint16_t* d_out_uv, const void* d_table, int n, int W, int H,
                         int R, int C, const uint16_t border_yuv[3], int32_t* d_crop, int32_t* d_bounds, void* stream);
 
+/* ---- NV16 clips: the 4:2:2 layout of capture cards, SDI / HDMI grabbers and webcams in its semi-planar form -- a full-resolution luma plane
+ * and one interleaved chroma plane of half the WIDTH and the full height -- warped from ONE cell table like an NV12 clip, with the arrays the
+ * reference hands to cv2.remap at mfs.py:1063-1069, without a conversion to BGR and without dropping chroma rows.  A clip is two contiguous stacks: d_y [n][H][W] uint8 and d_uv [n][H][W/2][2] uint8, U first; W is
+ * even, H of either parity, both 2 .. 32,767.  The packed forms (YUY2, UYVY) come in and go out through mf_unpack_422_u8 / mf_pack_422_u8 below.
+ * Luma: d_out_y is byte for byte mf_warp_u8c1 of d_y with border border_yuv[0] -- that very launch; the per-frame crop values in d_crop, the
+ * clip rectangle and the ownership are that call's.
+ * Chroma: chroma is DEFINED as sited at the even luma sample of the same row: output chroma sample (cx, y) of frame f takes the float32 map
+ * (u, v) of luma pixel (2 cx, y) -- exactly what mf_warp_maps_f32 returns for it, (W + 1, H + 1) for a pixel no cell owns included --, halves u
+ * in float32 (uc = u * 0.5f: exact; vc = v as it is) and applies cv2.remap's 8-bit fixed-point INTER_LINEAR with BORDER_CONSTANT to the
+ * (H, W/2) two-channel plane: sx = cvRound(32 uc), ix = sat_short(sx >> 5), fx = sx & 31 (the same in y), weights from the 2^15 table, out =
+ * (sum w s + 2^14) >> 15 per channel.  A 2 x 2 tap footprint wholly outside the plane gives (border_yuv[1], border_yuv[2]), otherwise each
+ * outside tap is that border sample inside the sum; an unowned pixel lands at ((W + 1) / 2, H + 1), which lies outside the plane.  U and V
+ * never mix.  (No sub-pixel correction for other chroma sitings is applied.)  The chroma launch follows the luma launch on the same stream; it
+ * reads nothing outside the plane's bytes and touches neither d_crop nor the rectangle.  All plane offsets are 64-bit.
+ * border_yuv: {Y, U, V} as given; BT.601 limited-range red, the reference's default BGR (0, 0, 255), is (81, 90, 240).
+ * mf_warp_bounds_nv16: the rectangle in the caller's d_bounds[4], as mf_warp_bounds_u8c1.
+ * Refused with MF_ERR_INVALID_ARG before anything is launched: null pointers, n <= 0, any two of the four planes overlapping (the chroma stacks
+ * are n W H bytes), an odd W, W or H outside 2 .. 32,767, R or C outside 1 .. 64, a d_uv or d_out_uv that is not 2-byte aligned.
+ * Not provided for 4:2:2: crop-resize, the clip pipelines (mf_clip_*), 10-bit samples (P210, v210). */
+int mf_warp_nv16(const uint8_t* d_y, const uint8_t* d_uv, uint8_t* d_out_y, uint8_t* d_out_uv, const void* d_table, int n, int W, int H,
+                 int R, int C, const uint8_t border_yuv[3], int32_t* d_crop, void* stream);
+int mf_warp_bounds_nv16(const uint8_t* d_y, const uint8_t* d_uv, uint8_t* d_out_y, uint8_t* d_out_uv, const void* d_table, int n, int W, int H,
+                        int R, int C, const uint8_t border_yuv[3], int32_t* d_crop, int32_t* d_bounds, void* stream);
+
+/* Packed 4:2:2 against the NV16 pair.  d_packed [n][H][W][2] uint8 with W even is a flat stream of 4-byte words; word k covers luma pixels 2k
+ * and 2k + 1 of the flat [n][H][W] stream (W is even, so no row or frame boundary falls inside a word).  order 0, yuyv (YUY2): bytes Y0 U Y1 V;
+ * order 1, uyvy (2vuy): bytes U Y0 V Y1.  mf_unpack_422_u8 writes y[2k] = Y0, y[2k + 1] = Y1, uv[2k] = U, uv[2k + 1] = V -- exactly the NV16
+ * pair d_y [n][H][W], d_uv [n][H][W/2][2]; mf_pack_422_u8 is the inverse.  The warp of a packed clip is unpack, mf_warp_nv16, pack.
+ * One streaming kernel each: dwordx4 loads and 16-byte stores where the addresses allow them, narrower accesses where they do not -- no access
+ * is wider than its address's alignment; 64-bit indices, any clip length.
+ * Refused with MF_ERR_INVALID_ARG before anything is launched: a null pointer, n < 1, W odd or outside 2 .. 32,767, H outside 1 .. 32,767, an
+ * order other than 0 or 1, a d_packed that is not 4-byte aligned, a d_y or d_uv that is not 2-byte aligned (whole frames of contiguous stacks
+ * always are), any overlap of the three buffers. */
+int mf_unpack_422_u8(const uint8_t* d_packed, uint8_t* d_y, uint8_t* d_uv, int n, int W, int H, int order, void* stream);
+int mf_pack_422_u8(const uint8_t* d_y, const uint8_t* d_uv, uint8_t* d_packed, int n, int W, int H, int order, void* stream);
+
 /* Clip-level crop bounds (mfs.py:1103-1106): {max left, max top, min right, min bottom} over n frames.
  * d_bounds: [4] int32. */
 int mf_crop_reduce(const int32_t* d_crop, int n, int W, int H, int32_t* d_bounds, void* stream);

@@ -85,6 +85,10 @@ SIGNATURES = {
     'mf_warp_bounds_nv12': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     'mf_warp_p010': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     'mf_warp_bounds_p010': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    'mf_warp_nv16': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    'mf_warp_bounds_nv16': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    'mf_unpack_422_u8': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    'mf_pack_422_u8': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     'mf_crop_resize_nv12_workspace_bytes': (_sz, [_i, _i]),
     'mf_crop_resize_nv12': (_i, [_vp, _vp, _vp, _vp] + [_i] * 9 + [_vp, _vp]),
     'mf_crop_resize_dev_nv12': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp]),

@@ -111,6 +111,36 @@ static int warp_420_entry(const char* name, const Fmt420& f, const void* d_y, co
     return launch_warp(f.chroma, d_uv, d_out_uv, tv, n, W, H, R, C, pack_border(f.chroma, border_uv), d_crop, (hipStream_t)stream);
 }
 
+// The two NV16 (4:2:2) warp entries: warp_420_entry's checks under their own names for a chroma plane of half the width and the FULL height --
+// only W must be even, and the chroma stacks are n W H bytes --, then the grey warp of the luma planes and launch_warp's Px::NV16_UV launches
+// behind it on the same stream.
+static int warp_nv16_entry(const char* name, const uint8_t* d_y, const uint8_t* d_uv, uint8_t* d_out_y, uint8_t* d_out_uv, const void* d_table, int n,
+                           int W, int H, int R, int C, const uint8_t* border_yuv, int32_t* d_crop, bool has_bounds, int32_t* d_bounds, void* stream)
+{
+    if (!d_y || !d_uv || !d_out_y || !d_out_uv || !d_table || !border_yuv || !d_crop || (has_bounds && !d_bounds)) {
+        set_error("%s: null pointer", name);
+        return MF_ERR_INVALID_ARG;
+    }
+    if (n <= 0) { set_error("%s: bad sizes", name); return MF_ERR_INVALID_ARG; }
+    if (W < 2 || H < 2 || W > 32767 || H > 32767) { set_error("%s: W=%d H=%d outside 2 .. 32,767", name, W, H); return MF_ERR_INVALID_ARG; }
+    if (W & 1) { set_error("%s: an NV16 frame has an even W, got W=%d", name, W); return MF_ERR_INVALID_ARG; }
+    if (R < 1 || C < 1 || R > 64 || C > 64) { set_error("%s: mesh R=%d C=%d outside 1 .. 64", name, R, C); return MF_ERR_INVALID_ARG; }
+    if ((((uintptr_t)d_uv | (uintptr_t)d_out_uv) & 1u) != 0) { set_error("%s: d_uv and d_out_uv must be 2-byte aligned", name); return MF_ERR_INVALID_ARG; }
+    const size_t bytes = (size_t)n * W * H;                                 // of each of the four stacks (nv16_uv_frame_bytes is W H too)
+    const struct { uintptr_t at; const char* what; } pl[4] = {
+        { (uintptr_t)d_y, "d_y" }, { (uintptr_t)d_uv, "d_uv" }, { (uintptr_t)d_out_y, "d_out_y" }, { (uintptr_t)d_out_uv, "d_out_uv" } };
+    for (int i = 0; i < 4; ++i)
+        for (int j = i + 1; j < 4; ++j)
+            if (pl[i].at < pl[j].at + bytes && pl[j].at < pl[i].at + bytes) {
+                set_error("%s: %s and %s alias", name, pl[i].what, pl[j].what);
+                return MF_ERR_INVALID_ARG;
+            }
+    TableView tv = table_view(const_cast<void*>(d_table), n, W, H, R, C);
+    if (has_bounds) tv.bounds = d_bounds;
+    if (const int rc = launch_warp(Px::U8C1, d_y, d_out_y, tv, n, W, H, R, C, pack_border(Px::U8C1, border_yuv), d_crop, (hipStream_t)stream)) return rc;
+    return launch_warp(Px::NV16_UV, d_uv, d_out_uv, tv, n, W, H, R, C, pack_border(Px::NV16_UV, border_yuv + 1), d_crop, (hipStream_t)stream);
+}
+
 // The element checks every plane entry shares: elem_bytes is 0 (the float32 calls) or 1, 2, 4, 8, and both pointers are aligned to the element
 static bool plane_elem_ok(const char* name, int elem_bytes, const void* d_planes, const void* d_out)
 {
@@ -402,6 +432,18 @@ int mf_warp_bounds_nv12(const uint8_t* d_y, const uint8_t* d_uv, uint8_t* d_out_
 {
     return warp_420_entry("mf_warp_bounds_nv12", kNv12, d_y, d_uv, d_out_y, d_out_uv, d_table, n, W, H, R, C, border_yuv, d_crop, true, d_bounds,
                           stream);
+}
+
+int mf_warp_nv16(const uint8_t* d_y, const uint8_t* d_uv, uint8_t* d_out_y, uint8_t* d_out_uv, const void* d_table, int n, int W, int H,
+                 int R, int C, const uint8_t border_yuv[3], int32_t* d_crop, void* stream)
+{
+    return warp_nv16_entry("mf_warp_nv16", d_y, d_uv, d_out_y, d_out_uv, d_table, n, W, H, R, C, border_yuv, d_crop, false, nullptr, stream);
+}
+
+int mf_warp_bounds_nv16(const uint8_t* d_y, const uint8_t* d_uv, uint8_t* d_out_y, uint8_t* d_out_uv, const void* d_table, int n, int W, int H,
+                        int R, int C, const uint8_t border_yuv[3], int32_t* d_crop, int32_t* d_bounds, void* stream)
+{
+    return warp_nv16_entry("mf_warp_bounds_nv16", d_y, d_uv, d_out_y, d_out_uv, d_table, n, W, H, R, C, border_yuv, d_crop, true, d_bounds, stream);
 }
 
 int mf_warp_p010(const uint16_t* d_y, const uint16_t* d_uv, uint16_t* d_out_y, uint16_t* d_out_uv, const void* d_table, int n, int W, int H,

@@ -243,11 +243,13 @@ inline bool make_tile_order(int tiles_x, int tiles_y, int n, TileOrder& o)
 // Px::U16C3 stack (cv2.remap of CV_16UC1).  No public frame format: only the P010 entries launch it.
 // Px::P010_UV: the interleaved half-resolution chroma plane of such a clip (warp_p010.hip): [n][H/2][W/2] pixels of two uint16 samples, U
 // first -- Px::NV12_UV's geometry and lane mapping with Px::U16C3's arithmetic; frame stride p010_uv_frame_bytes.
-enum class Px { U8C3, U16C3, U8C1, U8C4, MAPS, PLANE_F32, PLANE_N1, PLANE_N2, PLANE_N4, PLANE_N8, NV12_UV, U16C1, P010_UV };
+// Px::NV16_UV: the interleaved half-WIDTH chroma plane of an NV16 (4:2:2) clip (mf_warp_nv16, warp_nv16.hip): [n][H][W/2] pixels of two bytes, U
+// first, sampled at (u / 2, v) of the even luma pixels of every row; H of either parity; frame stride nv16_uv_frame_bytes.  Luma: Px::U8C1.
+enum class Px { U8C3, U16C3, U8C1, U8C4, MAPS, PLANE_F32, PLANE_N1, PLANE_N2, PLANE_N4, PLANE_N8, NV12_UV, U16C1, P010_UV, NV16_UV };
 constexpr bool px_is_plane(Px p) { return p == Px::PLANE_F32 || p == Px::PLANE_N1 || p == Px::PLANE_N2 || p == Px::PLANE_N4 || p == Px::PLANE_N8; }
 constexpr int px_channels(Px p)
 {
-    return p == Px::U8C1 || p == Px::U16C1 || px_is_plane(p) ? 1 : p == Px::U8C4 ? 4 : p == Px::MAPS || p == Px::NV12_UV || p == Px::P010_UV ? 2 : 3;
+    return p == Px::U8C1 || p == Px::U16C1 || px_is_plane(p) ? 1 : p == Px::U8C4 ? 4 : p == Px::MAPS || p == Px::NV12_UV || p == Px::P010_UV || p == Px::NV16_UV ? 2 : 3;
 }
 // (the formats whose samples, and border samples, are uint16)
 constexpr bool px_is_u16(Px p) { return p == Px::U16C3 || p == Px::U16C1 || p == Px::P010_UV; }
@@ -259,14 +261,16 @@ constexpr int px_bytes(Px p) { return px_channels(p) * px_sample_bytes(p); }
 constexpr const char* px_name(Px p)
 {
     return p == Px::U8C3 ? "u8c3" : p == Px::U16C3 ? "u16c3" : p == Px::U8C1 ? "u8c1" : p == Px::U8C4 ? "u8c4" : p == Px::MAPS ? "maps_f32" :
-           p == Px::PLANE_F32 ? "plane_f32" : p == Px::NV12_UV ? "nv12_uv" : p == Px::U16C1 ? "u16c1" : p == Px::P010_UV ? "p010_uv" : "plane_nearest";
+           p == Px::PLANE_F32 ? "plane_f32" : p == Px::NV12_UV ? "nv12_uv" : p == Px::U16C1 ? "u16c1" : p == Px::P010_UV ? "p010_uv" : p == Px::NV16_UV ? "nv16_uv" : "plane_nearest";
 }
 // bytes of one frame's chroma plane of an NV12 clip of W x H luma pixels (W, H even): (W / 2) (H / 2) pixels of 2 bytes
 constexpr size_t nv12_uv_frame_bytes(int W, int H) { return (size_t)(W / 2) * (size_t)(H / 2) * 2u; }
 // ... of a P010 clip: (W / 2) (H / 2) pixels of 4 bytes
 constexpr size_t p010_uv_frame_bytes(int W, int H) { return (size_t)(W / 2) * (size_t)(H / 2) * 4u; }
+// ... of an NV16 clip of W x H luma pixels (W even, H of either parity): (W / 2) H pixels of 2 bytes
+constexpr size_t nv16_uv_frame_bytes(int W, int H) { return (size_t)W * (size_t)H; }
 // The border colour as the warp kernels take it, from the caller's px_channels(p) samples: B | G << 8 | R << 16 (u8c3),
-// B | G << 16 | R << 32 (u16c3), the byte (u8c1), B | G << 8 | R << 16 | A << 24 (u8c4), U | V << 8 (nv12_uv), the sample (u16c1), U | V << 16 (p010_uv).
+// B | G << 16 | R << 32 (u16c3), the byte (u8c1), B | G << 8 | R << 16 | A << 24 (u8c4), U | V << 8 (nv12_uv, nv16_uv), the sample (u16c1), U | V << 16 (p010_uv).
 inline uint64_t pack_border(Px p, const void* samples)
 {
     uint64_t v = 0;
@@ -308,6 +312,7 @@ void launch_warp8c4_range(const WarpGeom& g, const WarpRange& r, int W, int H, i
 void launch_maps_range(const WarpGeom& g, const WarpRange& r, int W, int H, int C, hipStream_t st);  // warp_maps.hip (r.frames unused, r.out: float32 maps)
 void launch_plane_range(Px px, const WarpGeom& g, const WarpRange& r, int W, int H, int C, uint64_t fill, hipStream_t st);  // warp_planes.hip (fill: the element's bits)
 void launch_nv12_chroma_range(const WarpGeom& g, const WarpRange& r, int W, int H, int C, uint32_t border_uv, hipStream_t st);  // warp_nv12.hip (r.crop, r.bounds unused)
+void launch_nv16_chroma_range(const WarpGeom& g, const WarpRange& r, int W, int H, int C, uint32_t border_uv, hipStream_t st);  // warp_nv16.hip (r.crop, r.bounds unused)
 void launch_warp16c1_range(const WarpGeom& g, const WarpRange& r, int W, int H, int C, uint32_t border, hipStream_t st);  // warp_c1_16.hip
 void launch_p010_chroma_range(const WarpGeom& g, const WarpRange& r, int W, int H, int C, uint32_t border_uv, hipStream_t st);  // warp_p010.hip (r.crop, r.bounds unused)
 int launch_crop_scan(const TableView& tv, int n, int W, int H, int R, int C, int32_t* crop, hipStream_t st);

@@ -1,4 +1,4 @@
-// What the warp translation units share (warp.hip, warp_c1.hip, warp_c4.hip, warp_maps.hip, warp_planes.hip, warp_nv12.hip, warp_c1_16.hip, warp_p010.hip): footprint_body and the blocks its
+// What the warp translation units share (warp.hip, warp_c1.hip, warp_c4.hip, warp_maps.hip, warp_planes.hip, warp_nv12.hip, warp_nv16.hip, warp_c1_16.hip, warp_p010.hip): footprint_body and the blocks its
 // paths share.  The constants and the coordinate code are in warp_coords.h, the uint8 BGR taps and blend in warp_taps_u8c3.h, the other
 // formats' tails in warp_tails.h; the units include this header only.  The design note is at the head of warp.hip.
 #ifndef MF_WARP_BODY_H
@@ -99,6 +99,7 @@ __device__ __forceinline__ void store_tail(const float (&u)[4], const float (&v)
 {
     if constexpr (PX == Px::MAPS) maps_store_f32(u, v, f, x0, y, active, W, H, reinterpret_cast<float*>(out));
     else if constexpr (PX == Px::NV12_UV) remap_store_nv12_uv(u, v, f, x0, y, active, W, H, frames, out, border);
+    else if constexpr (PX == Px::NV16_UV) remap_store_nv16_uv(u, v, f, x0, y, active, W, H, frames, out, border);
     else if constexpr (PX == Px::P010_UV)
         remap_store_p010_uv(u, v, f, x0, y, active, W, H, reinterpret_cast<const uint16_t*>(frames), reinterpret_cast<uint16_t*>(out), border);
     else if constexpr (PX == Px::U16C1)
@@ -141,6 +142,9 @@ __device__ __forceinline__ void store_bgr4(uint8_t* __restrict__ dst, int W, int
 // ownership and the coordinates are the luma frame's -- the maps kernel's paths, so (u, v) are its values bit for bit --, `frames` / `out` hold
 // (W / 2) (H / 2) pixels of two bytes per frame, the border is U | V << 8 in `border`, and the pixels go through remap_store_nv12_uv, which halves
 // the coordinates of the even luma pixels.  Taps from global memory; `crop` / `clip` are never touched (null: the luma launch owns them).
+// PX = Px::NV16_UV: the chroma plane of an NV16 clip (nv16_chroma_footprint, warp_nv16.hip): Px::NV12_UV on a plane of full height -- `frames` /
+// `out` hold (W / 2) H pixels of two bytes per frame, H of either parity, and the pixels go through remap_store_nv16_uv, where every row emits and
+// only the x coordinate is halved.  Taps from global memory, the hot and pair shortcuts (NOWIN), `crop` / `clip` never touched, like NV12.
 // PX = Px::U16C1: the luma planes of a P010 clip (warp16c1_footprint, warp_c1_16.hip): `frames` / `out` hold W H uint16 samples per frame, the
 // border sample is `border`, and the pixels go through remap_store_u16c1 -- Px::U16C3's arithmetic on one channel, taps from global memory.
 // Unlike Px::U16C3 it takes the hot and pair shortcuts (NOWIN), like the float32 plane whose tail has the same shape: one third of the
@@ -165,8 +169,9 @@ __device__ __forceinline__ void footprint_body(const uint32_t f, const uint32_t 
     constexpr bool MAPS = PX == Px::MAPS;
     static_assert(!MAPS || (!STAGE && !SCAN), "the maps kernel reads no frame: nothing to stage");
     // NOWIN: the instantiations that take the hot and pair shortcuts without a window (the maps read no frame, the planes tap global memory)
-    constexpr bool PLANE = px_is_plane(PX), NV12 = PX == Px::NV12_UV, P010 = PX == Px::U16C1 || PX == Px::P010_UV, NOWIN = MAPS || PLANE || NV12 || P010;
-    static_assert(!(PLANE || NV12 || P010) || (!STAGE && !SCAN), "the plane and chroma warps take their taps from global memory");
+    constexpr bool PLANE = px_is_plane(PX), NV12 = PX == Px::NV12_UV, P010 = PX == Px::U16C1 || PX == Px::P010_UV, NV16 = PX == Px::NV16_UV;
+    constexpr bool NOWIN = MAPS || PLANE || NV12 || P010 || NV16;
+    static_assert(!(PLANE || NV12 || P010 || NV16) || (!STAGE && !SCAN), "the plane and chroma warps take their taps from global memory");
     // inverse homographies of the footprint's candidate cells: [entry][Hi0..Hi8, pad] (80-byte rows)
     __shared__ __attribute__((aligned(16))) double s_hi[1][9][10];                // row 8: the "no cell" matrix, see OWN_NONE
     // source region of the footprint: MF_STAGE_ROWS rows of MF_STAGE_PITCH bytes (+ slack for the third dword of the last tap); the 4-byte

@@ -1,0 +1,36 @@
+// Kernel 2b for the chroma plane of an NV16 clip -- 4:2:2, what capture cards deliver (mf_warp_nv16, mf_warp_bounds_nv16): footprint_body's
+// NV16_UV instantiation -- the interleaved half-WIDTH plane [n][H][W/2][2], U first, sampled like cv2.remap INTER_LINEAR / BORDER_CONSTANT of
+// CV_8UC2 at (u / 2, v) of the coordinates the reference hands to cv2.remap at mfs.py:1063-1069 for the even luma pixels of every row.  The
+// luma plane needs no kernel of its own: it is the grey warp (warp8c1_footprint, warp_c1.hip), launched unchanged in front of this one.  Like
+// warp_nv12.hip a translation unit of its own, so that every existing code object stays what it is, instruction for instruction
+// (tools/isa_compare.py): this file takes footprint_body and its helpers from warp_body.h and adds the chroma kernel and its range launch.
+// Contract, registers and measurements: profiles/nv16.md.
+#include "warp_body.h"
+
+namespace mf {
+
+// nv12_chroma_footprint on a plane of full height: warp_kernel's footprint order and ownership / coordinate code on the LUMA frame's plan (W, H:
+// the luma size), the maps kernel's hot and pair shortcuts, footprint_body's general path for everything else, then remap_store_nv16_uv -- a
+// lane owns four consecutive luma pixels, the lanes of EVERY row emit the chroma samples of their pixels 0 and 2 as one 4-byte store.  It reads
+// the cell table and the chroma plane and never touches the crop rows or the clip rectangle.  `uv` / `out`: [n][H][W/2][2] bytes of THIS
+// launch's frames; `border`: U | V << 8.
+__global__ __launch_bounds__(64) void nv16_chroma_footprint(const FootPlan* __restrict__ plan, const FootRegion* __restrict__ regions, WarpGeom g,
+                                                            const uint8_t* __restrict__ uv, const double* __restrict__ records,
+                                                            uint8_t* __restrict__ out, const float* __restrict__ edges, int n, int W, int H, int C,
+                                                            uint32_t border)
+{
+    const uint32_t f = blockIdx.y;
+    const uint32_t t = ((blockIdx.x + f) & 7u) * g.per_xcd + (blockIdx.x >> 3);
+    if (t >= g.per_frame) return;
+    footprint_body<Px::NV16_UV, false, false>(f, t, plan, regions, g, uv, records, out, edges, n, W, H, C, border, nullptr, nullptr);
+}
+
+// launch_warp's launch for one frame range of chroma planes (r.frames / r.out advanced by nv16_uv_frame_bytes per frame; r.crop, r.bounds unused)
+void launch_nv16_chroma_range(const WarpGeom& g, const WarpRange& r, int W, int H, int C, uint32_t border_uv, hipStream_t st)
+{
+    const dim3 grid(g.per_xcd * 8u, (uint32_t)r.m);
+    hipLaunchKernelGGL(nv16_chroma_footprint, grid, dim3(64), 0, st, r.plan, r.regions, g, (const uint8_t*)r.frames, r.records, (uint8_t*)r.out,
+                       r.edges, r.m, W, H, C, border_uv);
+}
+
+}  // namespace mf

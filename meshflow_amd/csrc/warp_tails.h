@@ -1,5 +1,5 @@
 // The tails of footprint_body's other formats (device only, included through warp_body.h): the lane's four pixels at source coordinates
-// (u, v) -- taps, blend, crop flags, store -- for uint16 BGR, grey, 4-channel uint8, the coordinate maps, the side planes, NV12 chroma and the two planes of a P010 clip.
+// (u, v) -- taps, blend, crop flags, store -- for uint16 BGR, grey, 4-channel uint8, the coordinate maps, the side planes, NV12 and NV16 chroma and the two planes of a P010 clip.
 #ifndef MF_WARP_TAILS_H
 #define MF_WARP_TAILS_H
 #include "warp_coords.h"
@@ -577,6 +577,75 @@ __device__ __forceinline__ void remap_store_nv12_uv(const float (&u)[4], const f
             }
         }
         uint8_t* __restrict__ d = out + (uint64_t)f * plane_bytes + 2ull * (uint64_t)((uint32_t)(y >> 1) * (uint32_t)Wc + (uint32_t)(x0 >> 1));
+        if (two) {                                                      // 4 bytes, dword-aligned unless W % 4 == 2 (then an unaligned store)
+            const uint32_t w4 = o[0] | (o[1] << 16);
+            __builtin_memcpy(d, &w4, 4);
+        } else {
+            const uint16_t w2 = (uint16_t)o[0];
+            __builtin_memcpy(d, &w2, 2);
+        }
+    }
+}
+
+// ---- the chroma plane of an NV16 clip (4:2:2): cv2.remap of CV_8UC2 on the half-WIDTH plane, at (u / 2, v) of the even luma pixels ----------
+// Footprint-level tail of the NV16_UV instantiation of footprint_body: remap_store_nv12_uv with chroma rows that are the luma rows.  The lane
+// owns four consecutive LUMA pixels of row y at coordinates (u, v) -- the maps kernel's, bit for bit -- and chroma is sited at the even luma
+// sample of the same row: EVERY row's lanes emit, chroma samples (x0 / 2, y) and (x0 / 2 + 1, y) from their pixels 0 and 2.  A sample's source
+// position is (u * 0.5f, v) -- the halving is exact in float32, v stays what it is --, then cv2.remap's 8-bit fixed point on the (H, W / 2) plane
+// of two-byte pixels: a pixel no cell owns, at (W + 1, H + 1), lands at ((W + 1) / 2, H + 1), outside that plane, and comes out as the border
+// like any other.  Deep-interior footprints (wave-uniform; the test, the clamped taps and the ballot all on (Wc, Hc) = (W / 2, H)) take each
+// sample's two tap rows as one 4-byte load apiece (the plane is only 2-byte aligned: unaligned dword loads); the others take every tap as a
+// 2-byte load at its position clamped into the plane and replace outside taps by `border` (U | V << 8).  Nothing outside the plane's bytes is
+// read, no crop value is touched (the luma launch owns them), and the lane's two samples go out as one 4-byte store (2 bytes in the lane that
+// holds the last sample of a row with W % 4 == 2; an unaligned dword store where the plane is only 2-byte aligned).  All plane offsets are
+// 64-bit (H may have either parity: the plane has W H bytes per frame).
+__device__ __forceinline__ void remap_store_nv16_uv(const float (&u)[4], const float (&v)[4], uint32_t f, int x0, int y, bool active, int W, int H,
+                                                    const uint8_t* __restrict__ planes, uint8_t* __restrict__ out, uint32_t border)
+{
+    const int Wc = W >> 1, Hc = H;
+    const uint64_t plane_bytes = 2ull * (uint64_t)((uint32_t)Wc * (uint32_t)Hc);
+    const uint8_t* __restrict__ src = planes + (uint64_t)f * plane_bytes;
+    const bool emit = active;                                           // (x0 is a multiple of 4: pixels 0 and 2 are even columns)
+    const bool two = x0 + 2 < W;                                        // (the lane's second sample exists; its pixel 2 stands in for nothing else)
+    // the lane's two samples twice over, so that the four-pixel helpers of warp_coords.h serve (the duplicates fold away)
+    const float h0 = u[0] * 0.5f, g0 = v[0], h1 = two ? u[2] * 0.5f : h0, g1 = two ? v[2] : g0;
+    const float uc[4] = { h0, h1, h0, h1 }, vc[4] = { g0, g1, g0, g1 };
+    uint32_t bx[4], by[4];
+    fixed_point(uc, vc, bx, by);
+    const bool deep = deep_interior(bx, by, Wc, Hc);
+    const bool fast = __ballot(emit && !deep) == 0;
+    uint32_t o[2];                                                      // the lane's two output pixels, U | V << 8
+    if (emit) {
+        if (fast) {
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const uint32_t ix = __builtin_amdgcn_ubfe(bx[j], 5, 17), iy = __builtin_amdgcn_ubfe(by[j], 5, 17);
+                const uint8_t* __restrict__ p = src + 2ull * (uint64_t)(iy * (uint32_t)Wc + ix);
+                uint32_t a, b;                                          // pixels ix and ix + 1 of rows iy and iy + 1
+                __builtin_memcpy(&a, p, 4);
+                __builtin_memcpy(&b, p + 2u * (uint32_t)Wc, 4);
+                o[j] = blend_uv(a, b, bx[j], by[j]);
+            }
+        } else {
+            // plane borders, uncovered pixels, out-of-range coordinates
+            const bool narrow = narrow_coords(bx, by);
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const int sxx = fixed_coord(narrow, bx[j], uc[j]), syy = fixed_coord(narrow, by[j], vc[j]);
+                const int ix = sxx >> 5, iy = syy >> 5;                 // (saturation to int16 cannot change any decision below)
+                // (a 2 x 2 footprint wholly outside needs no special case: four border taps with weights summing to 1024 give the border)
+                const ClampedTaps t = clamped_taps(ix, iy, Wc, Hc);
+                uint16_t p00, p01, p10, p11;
+                __builtin_memcpy(&p00, src + 2ull * (uint64_t)(t.r0 + t.cx0), 2);
+                __builtin_memcpy(&p01, src + 2ull * (uint64_t)(t.r0 + t.cx1), 2);
+                __builtin_memcpy(&p10, src + 2ull * (uint64_t)(t.r1 + t.cx0), 2);
+                __builtin_memcpy(&p11, src + 2ull * (uint64_t)(t.r1 + t.cx1), 2);
+                const uint32_t q00 = t.in_x0 && t.in_y0 ? (uint32_t)p00 : border, q01 = t.in_x1 && t.in_y0 ? (uint32_t)p01 : border;
+                const uint32_t q10 = t.in_x0 && t.in_y1 ? (uint32_t)p10 : border, q11 = t.in_x1 && t.in_y1 ? (uint32_t)p11 : border;
+                o[j] = blend_uv(q00 | (q01 << 16), q10 | (q11 << 16), (uint32_t)sxx, (uint32_t)syy);
+            }
+        }
+        uint8_t* __restrict__ d = out + (uint64_t)f * plane_bytes + 2ull * (uint64_t)((uint32_t)y * (uint32_t)Wc + (uint32_t)(x0 >> 1));
         if (two) {                                                      // 4 bytes, dword-aligned unless W % 4 == 2 (then an unaligned store)
             const uint32_t w4 = o[0] | (o[1] << 16);
             __builtin_memcpy(d, &w4, 4);

@@ -574,6 +574,118 @@ def warp_p010(y, uv, table, border_yuv=P010_BORDER_RED, out=None, bounds=None):
     return _warp_420(_P010, y, uv, table, border_yuv, out, bounds)
 
 
+# 4:2:2 -- what capture cards, SDI / HDMI grabbers and webcams deliver: the semi-planar NV16 pair and the two packed byte orders
+ORDERS_422 = {'yuyv': 0, 'uyvy': 1}
+_NV16 = _Format420(torch.uint8, 'an NV16', _nv12_border, _lib_.mf_warp_nv16, _lib_.mf_warp_bounds_nv16, None, None, None)
+
+
+def _need_nv16(y, uv):
+    """`_need_420` for an NV16 pair: only W must be even, and chroma has the luma's height; returns (n, H, W) of the luma stack."""
+    _need(y, torch.uint8, 'y')
+    if y.dim() != 3:
+        raise ValueError(f'y must be (n, H, W) luma planes, got shape {tuple(y.shape)}')
+    n, H, W = (int(v) for v in y.shape)
+    if W % 2:
+        raise ValueError(f'an NV16 frame has an even width, got W={W}')
+    _plane_420(uv, 'uv', (n, H, W // 2, 2), y.device, torch.uint8)
+    return n, H, W
+
+
+def _order_422(order):
+    if order not in ORDERS_422:
+        raise ValueError(f"order must be 'yuyv' or 'uyvy', got {order!r}")
+    return ORDERS_422[order]
+
+
+def _need_packed_422(packed, name='packed'):
+    """A packed 4:2:2 clip: a contiguous (n, H, W, 2) uint8 device tensor with W even; returns (n, H, W)."""
+    _need(packed, torch.uint8, name)
+    if packed.dim() != 4 or packed.shape[3] != 2:
+        raise ValueError(f'{name} must be (n, H, W, 2) packed 4:2:2 frames, got shape {tuple(packed.shape)}')
+    n, H, W = (int(v) for v in packed.shape[:3])
+    if W % 2:
+        raise ValueError(f'a packed 4:2:2 frame has an even width, got W={W}')
+    if n < 1 or H < 1 or W < 2:
+        raise ValueError(f'{name} is empty: shape {tuple(packed.shape)}')
+    return n, H, W
+
+
+def warp_nv16(y, uv, table, border_yuv=NV12_BORDER_RED, out=None, bounds=None):
+    """The mesh warp of an NV16 clip -- 4:2:2 in its semi-planar form, what capture cards and grabbers deliver (their packed forms go through
+    `warp_packed_422`) -- from one cell table, without a conversion to BGR and without dropping chroma rows (mf_warp_nv16).  y: (n, H, W) uint8
+    luma, uv: (n, H, W/2, 2) uint8 interleaved chroma, U first; both contiguous device tensors, W even, H of either parity, n == table.n.
+    Luma is byte for byte `warp(y, table, (border_yuv[0],))` -- that very launch: the per-frame crop values in table.crop and the clip-level
+    rectangle in `bounds` / table.clip_bounds are its.  Chroma is DEFINED as sited at the even luma sample of the same row: output chroma
+    sample (cx, y) takes `warp_maps(table)[f, y, 2 cx]`, halves its x in float32, leaves its y as it is, and samples the (H, W/2) two-channel
+    plane like cv2.remap's 8-bit INTER_LINEAR with BORDER_CONSTANT; where the source lies outside the plane, and where no cell owns the luma
+    pixel, the result is (border_yuv[1], border_yuv[2]).  No sub-pixel correction for other chroma sitings is applied.
+    border_yuv: (Y, U, V), each clamp(round(v), 0, 255); the default is `warp_nv12`'s.  out: an (out_y, out_uv) pair to fill.  Returns
+    (out_y, out_uv).  (Not provided for 4:2:2: crop-resize, `stabilize_scored`, online sessions and groups, 10-bit samples.)"""
+    n, H, W = _need_nv16(y, uv)
+    if (n, W, H) != (table.n, table.W, table.H):
+        raise ValueError(f'y {tuple(y.shape)} does not match the cell table (n, H, W) = {(table.n, table.H, table.W)}')
+    if len(border_yuv) != 3:
+        raise ValueError(f'border_yuv must be (Y, U, V), got {border_yuv!r}')
+    out_y, out_uv = _out_420(_NV16, y, y.shape, uv.shape, out)
+    border = _NV16.border(border_yuv)
+    if bounds is None:
+        _lib.check(_NV16.warp(_ptr(y), _ptr(uv), _ptr(out_y), _ptr(out_uv), _ptr(table.buf), n, W, H, table.R, table.C, border, _ptr(table.crop),
+                              _stream()))
+    else:
+        _need_bounds(bounds)
+        _lib.check(_NV16.warp_bounds(_ptr(y), _ptr(uv), _ptr(out_y), _ptr(out_uv), _ptr(table.buf), n, W, H, table.R, table.C, border,
+                                     _ptr(table.crop), _ptr(bounds), _stream()))
+    return out_y, out_uv
+
+
+def unpack_422(packed, order='yuyv', out=None):
+    """A packed 4:2:2 clip as the NV16 pair (mf_unpack_422_u8).  packed: a contiguous (n, H, W, 2) uint8 device tensor, W even -- a flat stream
+    of 4-byte words, Y0 U Y1 V for order 'yuyv' (YUY2) and U Y0 V Y1 for 'uyvy' (2vuy).  Returns (y, uv): (n, H, W) luma and (n, H, W/2, 2)
+    chroma, U first -- what `warp_nv16` takes, and y is what `estimate_motion` takes.  out: a (y, uv) pair to fill.  One streaming kernel,
+    2 bytes moved per byte of the clip."""
+    n, H, W = _need_packed_422(packed)
+    o = _order_422(order)
+    y, uv = _out_420(_NV16, packed, (n, H, W), (n, H, W // 2, 2), out)
+    _lib.check(_lib_.mf_unpack_422_u8(_ptr(packed), _ptr(y), _ptr(uv), n, W, H, o, _stream()))
+    return y, uv
+
+
+def pack_422(y, uv, order='yuyv', out=None):
+    """The inverse of `unpack_422` (mf_pack_422_u8): the NV16 pair y (n, H, W), uv (n, H, W/2, 2) as a packed (n, H, W, 2) uint8 clip of the
+    given byte order.  out: the packed tensor to fill.  Returns it."""
+    n, H, W = _need_nv16(y, uv)
+    o = _order_422(order)
+    if out is None:
+        out = torch.empty((n, H, W, 2), dtype=torch.uint8, device=y.device)
+    else:
+        _plane_420(out, 'out', (n, H, W, 2), y.device, torch.uint8)
+    if n < 1 or H < 1 or W < 2:
+        raise ValueError(f'y is empty: shape {tuple(y.shape)}')
+    _lib.check(_lib_.mf_pack_422_u8(_ptr(y), _ptr(uv), _ptr(out), n, W, H, o, _stream()))
+    return out
+
+
+def warp_packed_422(packed, table, order='yuyv', border_yuv=NV12_BORDER_RED, out=None, bounds=None):
+    """The mesh warp of a packed 4:2:2 clip (YUY2 / UYVY), DEFINED as `unpack_422`, `warp_nv16`, `pack_422`: four launches beside the luma's
+    own (unpack, the grey warp, the chroma warp, pack).  packed: (n, H, W, 2) uint8, n == table.n; out: the packed tensor to fill.  The crop
+    values and the rectangle are `warp_nv16`'s.  Temporary memory: the unpacked pair and its warped twin, 2 n W H bytes each -- twice the
+    clip's own size, released on return.  (A tail that reads and writes the packed words directly is not built; profiles/nv16.md has the
+    measurement that decides whether it is worth one.)  Returns the warped packed clip."""
+    n, H, W = _need_packed_422(packed)
+    _order_422(order)
+    if out is not None:
+        _plane_420(out, 'out', (n, H, W, 2), packed.device, torch.uint8)
+    if (n, W, H) != (table.n, table.W, table.H):
+        raise ValueError(f'packed {tuple(packed.shape)} does not match the cell table (n, H, W) = {(table.n, table.H, table.W)}')
+    if len(border_yuv) != 3:
+        raise ValueError(f'border_yuv must be (Y, U, V), got {border_yuv!r}')
+    if bounds is not None:
+        _need_bounds(bounds)
+    y, uv = unpack_422(packed, order)
+    out_y, out_uv = warp_nv16(y, uv, table, border_yuv, None, bounds)
+    return pack_422(out_y, out_uv, order, out)
+
+
 def _even_output_size(size, name='size'):
     """`check_output_size` for an NV12 output: both numbers even as well (the smallest is 2 x 2)."""
     oW, oH = check_output_size(size, name)

@@ -1173,6 +1173,38 @@ class MeshFlowStabilizer:
         from . import ops
         return self._stabilized_420(ops._P010, d_y, d_uv, d_disp, homographies, border_yuv, out, adaptive_weights_definition, True, output_size)
 
+    def stabilized_nv16(self, d_y, d_uv, d_disp, homographies, border_yuv=(81, 90, 240), out=None,
+                        adaptive_weights_definition=ADAPTIVE_WEIGHTS_DEFINITION_ORIGINAL):
+        """`stabilized_nv12` for an NV16 clip -- 4:2:2 as capture cards and grabbers deliver it: d_y (F, H, W) uint8 luma, d_uv (F, H, W/2, 2)
+        uint8 interleaved chroma, U first, W even, H of either parity -- stabilized without ever becoming BGR and without dropping chroma rows:
+        the Jacobi sweep (mfs.py:695-704) on d_disp, the cell table + plan of all F frames, then `ops.warp_nv16` (which has the definition),
+        everything on torch's current stream.  d_disp and homographies come from `estimate_motion(d_y)`: the tracker takes the luma plane as it
+        is.  This call does not crop or scale (crop-resize of 4:2:2 clips is not built) and takes no `crop` or `output_size`.  out: an
+        (out_y, out_uv) pair to fill.  Returns (out_y, out_uv, bounds): bounds = int32[4] device tensor {left, top, right, bottom}, the
+        rectangle `stabilization_maps` returns for the same inputs.  A degenerate mesh raises `DegenerateMeshError` (clip_serial None) here,
+        synchronously, before a plane is written."""
+        from . import ops
+        self._check_definition(adaptive_weights_definition)
+        self._check_mesh_shape(d_disp, d_disp.shape[0])
+        _, H, W = ops._need_nv16(d_y, d_uv)
+        table, bounds = self._checked_table(d_disp, W, H, adaptive_weights_definition, homographies)
+        out_y, out_uv = ops.warp_nv16(d_y, d_uv, table, border_yuv, out, bounds)
+        return out_y, out_uv, bounds
+
+    def stabilized_packed_422(self, d_packed, d_disp, homographies, order='yuyv', border_yuv=(81, 90, 240), out=None,
+                              adaptive_weights_definition=ADAPTIVE_WEIGHTS_DEFINITION_ORIGINAL):
+        """`stabilized_nv16` for a packed 4:2:2 clip -- d_packed (F, H, W, 2) uint8, order 'yuyv' (YUY2: bytes Y0 U Y1 V) or 'uyvy' (2vuy: U Y0
+        V Y1), W even -- through `ops.warp_packed_422`: unpack, the NV16 warp, pack, with temporaries of twice the clip's size.  d_disp and
+        homographies come from `estimate_motion` on the clip's luma plane, which for a packed clip is `ops.unpack_422(d_packed, order)[0]`.
+        No `crop` or `output_size`, as for `stabilized_nv16`.  out: the packed tensor to fill.  Returns (out_packed, bounds)."""
+        from . import ops
+        self._check_definition(adaptive_weights_definition)
+        self._check_mesh_shape(d_disp, d_disp.shape[0])
+        _, H, W = ops._need_packed_422(d_packed, 'd_packed')
+        ops._order_422(order)
+        table, bounds = self._checked_table(d_disp, W, H, adaptive_weights_definition, homographies)
+        return ops.warp_packed_422(d_packed, table, order, border_yuv, out, bounds), bounds
+
     def _stabilized_frames_device(self, d_frames, d_unstab, d_stab, out=None, table=None):
         """d_frames: (n, H, W, 3) uint8; d_unstab/d_stab: (n, R+1, C+1, 2) float64, all in HBM.
         Returns (stabilized frames (n, H, W, 3) uint8, per-frame crop values (n, 4) int32), in HBM.
