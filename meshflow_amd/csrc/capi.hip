@@ -58,25 +58,27 @@ static int warp_maps_entry(const char* name, const void* d_table, float* d_maps,
                        (hipStream_t)stream);
 }
 
-// A 4:2:0 format with a luma plane stack and an interleaved half-resolution chroma one: NV12 (uint8 samples) and P010 (uint16 samples)
-struct Fmt420 {
+// A semi-planar YUV format -- a luma plane stack and an interleaved chroma one of half the width: NV12 and NV16 (uint8 samples), P010 (uint16)
+struct FmtYuv {
     int bytes;              // of a sample: 1 or 2
     const char* noun;       // with its article, for the messages
     Px luma, chroma;        // launch_warp's formats of the two plane stacks
+    bool half_rows;         // chroma has half the luma rows (4:2:0: H is even too); else as many (4:2:2: H of either parity)
 };
-constexpr Fmt420 kNv12 = { 1, "an NV12", Px::U8C1, Px::NV12_UV }, kP010 = { 2, "a P010", Px::U16C1, Px::P010_UV };
+constexpr FmtYuv kNv12 = { 1, "an NV12", Px::U8C1, Px::NV12_UV, true }, kP010 = { 2, "a P010", Px::U16C1, Px::P010_UV, true },
+                 kNv16 = { 1, "an NV16", Px::U8C1, Px::NV16_UV, false };
 
-// The plane stacks of a 4:2:0 call, n frames of W x H in and of oW x oH out: aligned to 2 bytes -- the chroma pair of an NV12 clip, all four of a
-// P010 clip -- and no two of them share a byte
-static bool planes_420_ok(const char* name, const Fmt420& f, const void* d_y, const void* d_uv, const void* d_out_y, const void* d_out_uv, int n, int W,
+// The plane stacks of a semi-planar call, n frames of W x H in and of oW x oH out: aligned to 2 bytes -- the chroma pair of an NV12 or NV16 clip,
+// all four of a P010 clip -- and no two of them share a byte
+static bool planes_yuv_ok(const char* name, const FmtYuv& f, const void* d_y, const void* d_uv, const void* d_out_y, const void* d_out_uv, int n, int W,
                           int H, int oW, int oH)
 {
-    const size_t b = (size_t)f.bytes;
     const struct { uintptr_t at; size_t bytes; const char* what; } pl[4] = {
-        { (uintptr_t)d_y, (size_t)n * W * H * b, "d_y" }, { (uintptr_t)d_uv, (size_t)n * nv12_uv_frame_bytes(W, H) * b, "d_uv" },
-        { (uintptr_t)d_out_y, (size_t)n * oW * oH * b, "d_out_y" }, { (uintptr_t)d_out_uv, (size_t)n * nv12_uv_frame_bytes(oW, oH) * b, "d_out_uv" } };
-    if ((((b == 2 ? pl[0].at | pl[2].at : 0) | pl[1].at | pl[3].at) & 1u) != 0) {
-        set_error("%s: %s must be 2-byte aligned", name, b == 2 ? "d_y, d_uv, d_out_y and d_out_uv" : "d_uv and d_out_uv");
+        { (uintptr_t)d_y, (size_t)n * px_frame_bytes(f.luma, W, H), "d_y" }, { (uintptr_t)d_uv, (size_t)n * px_frame_bytes(f.chroma, W, H), "d_uv" },
+        { (uintptr_t)d_out_y, (size_t)n * px_frame_bytes(f.luma, oW, oH), "d_out_y" },
+        { (uintptr_t)d_out_uv, (size_t)n * px_frame_bytes(f.chroma, oW, oH), "d_out_uv" } };
+    if ((((f.bytes == 2 ? pl[0].at | pl[2].at : 0) | pl[1].at | pl[3].at) & 1u) != 0) {
+        set_error("%s: %s must be 2-byte aligned", name, f.bytes == 2 ? "d_y, d_uv, d_out_y and d_out_uv" : "d_uv and d_out_uv");
         return false;
     }
     for (int i = 0; i < 4; ++i)
@@ -88,10 +90,10 @@ static bool planes_420_ok(const char* name, const Fmt420& f, const void* d_y, co
     return true;
 }
 
-// The checks of the four NV12 and P010 warp entries, then the warp of the luma planes (launch_warp's f.luma launches: the grey warp, unchanged, for
-// NV12) and the chroma launches behind it on the same stream.  border_yuv: three samples of f.bytes each.  has_bounds: the clip-level rectangle
-// goes to the caller's d_bounds instead of the table's.
-static int warp_420_entry(const char* name, const Fmt420& f, const void* d_y, const void* d_uv, void* d_out_y, void* d_out_uv, const void* d_table,
+// The checks of the six NV12, NV16 and P010 warp entries, then the warp of the luma planes (launch_warp's f.luma launches: the grey warp, unchanged,
+// for NV12 and NV16) and the chroma launches behind it on the same stream.  border_yuv: three samples of f.bytes each.  has_bounds: the clip-level
+// rectangle goes to the caller's d_bounds instead of the table's.
+static int warp_yuv_entry(const char* name, const FmtYuv& f, const void* d_y, const void* d_uv, void* d_out_y, void* d_out_uv, const void* d_table,
                           int n, int W, int H, int R, int C, const void* border_yuv, int32_t* d_crop, bool has_bounds, int32_t* d_bounds,
                           void* stream)
 {
@@ -101,44 +103,18 @@ static int warp_420_entry(const char* name, const Fmt420& f, const void* d_y, co
     }
     if (n <= 0) { set_error("%s: bad sizes", name); return MF_ERR_INVALID_ARG; }
     if (W < 2 || H < 2 || W > 32767 || H > 32767) { set_error("%s: W=%d H=%d outside 2 .. 32,767", name, W, H); return MF_ERR_INVALID_ARG; }
-    if ((W | H) & 1) { set_error("%s: %s frame has an even W and H, got W=%d H=%d", name, f.noun, W, H); return MF_ERR_INVALID_ARG; }
+    if ((f.half_rows ? W | H : W) & 1) {
+        if (f.half_rows) set_error("%s: %s frame has an even W and H, got W=%d H=%d", name, f.noun, W, H);
+        else set_error("%s: %s frame has an even W, got W=%d", name, f.noun, W);
+        return MF_ERR_INVALID_ARG;
+    }
     if (R < 1 || C < 1 || R > 64 || C > 64) { set_error("%s: mesh R=%d C=%d outside 1 .. 64", name, R, C); return MF_ERR_INVALID_ARG; }
-    if (!planes_420_ok(name, f, d_y, d_uv, d_out_y, d_out_uv, n, W, H, W, H)) return MF_ERR_INVALID_ARG;
+    if (!planes_yuv_ok(name, f, d_y, d_uv, d_out_y, d_out_uv, n, W, H, W, H)) return MF_ERR_INVALID_ARG;
     TableView tv = table_view(const_cast<void*>(d_table), n, W, H, R, C);
     if (has_bounds) tv.bounds = d_bounds;
     const void* const border_uv = (const char*)border_yuv + f.bytes;
     if (const int rc = launch_warp(f.luma, d_y, d_out_y, tv, n, W, H, R, C, pack_border(f.luma, border_yuv), d_crop, (hipStream_t)stream)) return rc;
     return launch_warp(f.chroma, d_uv, d_out_uv, tv, n, W, H, R, C, pack_border(f.chroma, border_uv), d_crop, (hipStream_t)stream);
-}
-
-// The two NV16 (4:2:2) warp entries: warp_420_entry's checks under their own names for a chroma plane of half the width and the FULL height --
-// only W must be even, and the chroma stacks are n W H bytes --, then the grey warp of the luma planes and launch_warp's Px::NV16_UV launches
-// behind it on the same stream.
-static int warp_nv16_entry(const char* name, const uint8_t* d_y, const uint8_t* d_uv, uint8_t* d_out_y, uint8_t* d_out_uv, const void* d_table, int n,
-                           int W, int H, int R, int C, const uint8_t* border_yuv, int32_t* d_crop, bool has_bounds, int32_t* d_bounds, void* stream)
-{
-    if (!d_y || !d_uv || !d_out_y || !d_out_uv || !d_table || !border_yuv || !d_crop || (has_bounds && !d_bounds)) {
-        set_error("%s: null pointer", name);
-        return MF_ERR_INVALID_ARG;
-    }
-    if (n <= 0) { set_error("%s: bad sizes", name); return MF_ERR_INVALID_ARG; }
-    if (W < 2 || H < 2 || W > 32767 || H > 32767) { set_error("%s: W=%d H=%d outside 2 .. 32,767", name, W, H); return MF_ERR_INVALID_ARG; }
-    if (W & 1) { set_error("%s: an NV16 frame has an even W, got W=%d", name, W); return MF_ERR_INVALID_ARG; }
-    if (R < 1 || C < 1 || R > 64 || C > 64) { set_error("%s: mesh R=%d C=%d outside 1 .. 64", name, R, C); return MF_ERR_INVALID_ARG; }
-    if ((((uintptr_t)d_uv | (uintptr_t)d_out_uv) & 1u) != 0) { set_error("%s: d_uv and d_out_uv must be 2-byte aligned", name); return MF_ERR_INVALID_ARG; }
-    const size_t bytes = (size_t)n * W * H;                                 // of each of the four stacks (nv16_uv_frame_bytes is W H too)
-    const struct { uintptr_t at; const char* what; } pl[4] = {
-        { (uintptr_t)d_y, "d_y" }, { (uintptr_t)d_uv, "d_uv" }, { (uintptr_t)d_out_y, "d_out_y" }, { (uintptr_t)d_out_uv, "d_out_uv" } };
-    for (int i = 0; i < 4; ++i)
-        for (int j = i + 1; j < 4; ++j)
-            if (pl[i].at < pl[j].at + bytes && pl[j].at < pl[i].at + bytes) {
-                set_error("%s: %s and %s alias", name, pl[i].what, pl[j].what);
-                return MF_ERR_INVALID_ARG;
-            }
-    TableView tv = table_view(const_cast<void*>(d_table), n, W, H, R, C);
-    if (has_bounds) tv.bounds = d_bounds;
-    if (const int rc = launch_warp(Px::U8C1, d_y, d_out_y, tv, n, W, H, R, C, pack_border(Px::U8C1, border_yuv), d_crop, (hipStream_t)stream)) return rc;
-    return launch_warp(Px::NV16_UV, d_uv, d_out_uv, tv, n, W, H, R, C, pack_border(Px::NV16_UV, border_yuv + 1), d_crop, (hipStream_t)stream);
 }
 
 // The element checks every plane entry shares: elem_bytes is 0 (the float32 calls) or 1, 2, 4, 8, and both pointers are aligned to the element
@@ -210,7 +186,7 @@ static int crop_resize_dev_entry(const char* name, Px px, const void* d_frames, 
 // the format's launches on one stream.  NV12: the luma call as it is (launch_crop_resize_to / launch_crop_resize_dev on Px::U8C1) and the chroma
 // launches behind it.  P010: the luma tables, the luma kernel, the chroma tables and the chroma kernel (resize_hdr.hip / resize_hdr_dev.hip).
 // dev: an mf_crop_resize_dev_* call (the rectangle in d_bounds, left .. bottom unused).
-static int crop_resize_420_entry(const char* name, const Fmt420& f, bool dev, const void* d_y, const void* d_uv, void* d_out_y, void* d_out_uv,
+static int crop_resize_420_entry(const char* name, const FmtYuv& f, bool dev, const void* d_y, const void* d_uv, void* d_out_y, void* d_out_uv,
                                  int n, int W, int H, int left, int top, int right, int bottom, const int32_t* d_bounds, int oW, int oH,
                                  void* d_work, int32_t* d_status, void* stream)
 {
@@ -226,7 +202,7 @@ static int crop_resize_420_entry(const char* name, const Fmt420& f, bool dev, co
     }
     if ((W | H) & 1) { set_error("%s: %s frame has an even W and H, got W=%d H=%d", name, f.noun, W, H); return MF_ERR_INVALID_ARG; }
     if ((oW | oH) & 1) { set_error("%s: %s output has an even size, got %dx%d", name, f.noun, oW, oH); return MF_ERR_INVALID_ARG; }
-    if (!planes_420_ok(name, f, d_y, d_uv, d_out_y, d_out_uv, n, W, H, oW, oH)) return MF_ERR_INVALID_ARG;
+    if (!planes_yuv_ok(name, f, d_y, d_uv, d_out_y, d_out_uv, n, W, H, oW, oH)) return MF_ERR_INVALID_ARG;
     if (!dev && !resize_rect_ok(name, "", left, top, right, bottom, W, H)) return MF_ERR_INVALID_ARG;
     hipStream_t st = (hipStream_t)stream;
     if (f.bytes == 2) {
@@ -424,38 +400,39 @@ int mf_warp_plane_nearest(const void* d_planes, void* d_out, const void* d_table
 int mf_warp_nv12(const uint8_t* d_y, const uint8_t* d_uv, uint8_t* d_out_y, uint8_t* d_out_uv, const void* d_table, int n, int W, int H,
                  int R, int C, const uint8_t border_yuv[3], int32_t* d_crop, void* stream)
 {
-    return warp_420_entry("mf_warp_nv12", kNv12, d_y, d_uv, d_out_y, d_out_uv, d_table, n, W, H, R, C, border_yuv, d_crop, false, nullptr, stream);
+    return warp_yuv_entry("mf_warp_nv12", kNv12, d_y, d_uv, d_out_y, d_out_uv, d_table, n, W, H, R, C, border_yuv, d_crop, false, nullptr, stream);
 }
 
 int mf_warp_bounds_nv12(const uint8_t* d_y, const uint8_t* d_uv, uint8_t* d_out_y, uint8_t* d_out_uv, const void* d_table, int n, int W, int H,
                         int R, int C, const uint8_t border_yuv[3], int32_t* d_crop, int32_t* d_bounds, void* stream)
 {
-    return warp_420_entry("mf_warp_bounds_nv12", kNv12, d_y, d_uv, d_out_y, d_out_uv, d_table, n, W, H, R, C, border_yuv, d_crop, true, d_bounds,
+    return warp_yuv_entry("mf_warp_bounds_nv12", kNv12, d_y, d_uv, d_out_y, d_out_uv, d_table, n, W, H, R, C, border_yuv, d_crop, true, d_bounds,
                           stream);
 }
 
 int mf_warp_nv16(const uint8_t* d_y, const uint8_t* d_uv, uint8_t* d_out_y, uint8_t* d_out_uv, const void* d_table, int n, int W, int H,
                  int R, int C, const uint8_t border_yuv[3], int32_t* d_crop, void* stream)
 {
-    return warp_nv16_entry("mf_warp_nv16", d_y, d_uv, d_out_y, d_out_uv, d_table, n, W, H, R, C, border_yuv, d_crop, false, nullptr, stream);
+    return warp_yuv_entry("mf_warp_nv16", kNv16, d_y, d_uv, d_out_y, d_out_uv, d_table, n, W, H, R, C, border_yuv, d_crop, false, nullptr, stream);
 }
 
 int mf_warp_bounds_nv16(const uint8_t* d_y, const uint8_t* d_uv, uint8_t* d_out_y, uint8_t* d_out_uv, const void* d_table, int n, int W, int H,
                         int R, int C, const uint8_t border_yuv[3], int32_t* d_crop, int32_t* d_bounds, void* stream)
 {
-    return warp_nv16_entry("mf_warp_bounds_nv16", d_y, d_uv, d_out_y, d_out_uv, d_table, n, W, H, R, C, border_yuv, d_crop, true, d_bounds, stream);
+    return warp_yuv_entry("mf_warp_bounds_nv16", kNv16, d_y, d_uv, d_out_y, d_out_uv, d_table, n, W, H, R, C, border_yuv, d_crop, true, d_bounds,
+                          stream);
 }
 
 int mf_warp_p010(const uint16_t* d_y, const uint16_t* d_uv, uint16_t* d_out_y, uint16_t* d_out_uv, const void* d_table, int n, int W, int H,
                  int R, int C, const uint16_t border_yuv[3], int32_t* d_crop, void* stream)
 {
-    return warp_420_entry("mf_warp_p010", kP010, d_y, d_uv, d_out_y, d_out_uv, d_table, n, W, H, R, C, border_yuv, d_crop, false, nullptr, stream);
+    return warp_yuv_entry("mf_warp_p010", kP010, d_y, d_uv, d_out_y, d_out_uv, d_table, n, W, H, R, C, border_yuv, d_crop, false, nullptr, stream);
 }
 
 int mf_warp_bounds_p010(const uint16_t* d_y, const uint16_t* d_uv, uint16_t* d_out_y, uint16_t* d_out_uv, const void* d_table, int n, int W, int H,
                         int R, int C, const uint16_t border_yuv[3], int32_t* d_crop, int32_t* d_bounds, void* stream)
 {
-    return warp_420_entry("mf_warp_bounds_p010", kP010, d_y, d_uv, d_out_y, d_out_uv, d_table, n, W, H, R, C, border_yuv, d_crop, true, d_bounds,
+    return warp_yuv_entry("mf_warp_bounds_p010", kP010, d_y, d_uv, d_out_y, d_out_uv, d_table, n, W, H, R, C, border_yuv, d_crop, true, d_bounds,
                           stream);
 }
 

@@ -238,13 +238,13 @@ inline bool make_tile_order(int tiles_x, int tiles_y, int n, TileOrder& o)
 // INTER_NEAREST.  One channel of px_sample_bytes bytes; the pixel calls (launch_crop_resize*, the clip and host pipelines) never see them.
 // Px::NV12_UV: the interleaved half-resolution chroma plane of an NV12 clip (mf_warp_nv12, warp_nv12.hip): [n][H/2][W/2] pixels of two bytes,
 // U first, sampled at half the luma coordinates of the even luma pixels.  W and H stay the LUMA frame's everywhere (the cell table's); only
-// launch_warp's frame stride (nv12_uv_frame_bytes) and the kernel's tail know the plane's own size.  The luma plane is a Px::U8C1 stack.
+// launch_warp's frame stride (px_frame_bytes) and the kernel's tail know the plane's own size.  The luma plane is a Px::U8C1 stack.
 // Px::U16C1: the luma planes of a P010 / P012 / P016 clip (mf_warp_p010, warp_c1_16.hip): [n][H][W] uint16 samples, sampled like channel 0 of a
 // Px::U16C3 stack (cv2.remap of CV_16UC1).  No public frame format: only the P010 entries launch it.
 // Px::P010_UV: the interleaved half-resolution chroma plane of such a clip (warp_p010.hip): [n][H/2][W/2] pixels of two uint16 samples, U
-// first -- Px::NV12_UV's geometry and lane mapping with Px::U16C3's arithmetic; frame stride p010_uv_frame_bytes.
+// first -- Px::NV12_UV's geometry and lane mapping with Px::U16C3's arithmetic.
 // Px::NV16_UV: the interleaved half-WIDTH chroma plane of an NV16 (4:2:2) clip (mf_warp_nv16, warp_nv16.hip): [n][H][W/2] pixels of two bytes, U
-// first, sampled at (u / 2, v) of the even luma pixels of every row; H of either parity; frame stride nv16_uv_frame_bytes.  Luma: Px::U8C1.
+// first, sampled at (u / 2, v) of the even luma pixels of every row; H of either parity.  Luma: Px::U8C1.
 enum class Px { U8C3, U16C3, U8C1, U8C4, MAPS, PLANE_F32, PLANE_N1, PLANE_N2, PLANE_N4, PLANE_N8, NV12_UV, U16C1, P010_UV, NV16_UV };
 constexpr bool px_is_plane(Px p) { return p == Px::PLANE_F32 || p == Px::PLANE_N1 || p == Px::PLANE_N2 || p == Px::PLANE_N4 || p == Px::PLANE_N8; }
 constexpr int px_channels(Px p)
@@ -263,12 +263,15 @@ constexpr const char* px_name(Px p)
     return p == Px::U8C3 ? "u8c3" : p == Px::U16C3 ? "u16c3" : p == Px::U8C1 ? "u8c1" : p == Px::U8C4 ? "u8c4" : p == Px::MAPS ? "maps_f32" :
            p == Px::PLANE_F32 ? "plane_f32" : p == Px::NV12_UV ? "nv12_uv" : p == Px::U16C1 ? "u16c1" : p == Px::P010_UV ? "p010_uv" : p == Px::NV16_UV ? "nv16_uv" : "plane_nearest";
 }
-// bytes of one frame's chroma plane of an NV12 clip of W x H luma pixels (W, H even): (W / 2) (H / 2) pixels of 2 bytes
-constexpr size_t nv12_uv_frame_bytes(int W, int H) { return (size_t)(W / 2) * (size_t)(H / 2) * 2u; }
-// ... of a P010 clip: (W / 2) (H / 2) pixels of 4 bytes
-constexpr size_t p010_uv_frame_bytes(int W, int H) { return (size_t)(W / 2) * (size_t)(H / 2) * 4u; }
-// ... of an NV16 clip of W x H luma pixels (W even, H of either parity): (W / 2) H pixels of 2 bytes
-constexpr size_t nv16_uv_frame_bytes(int W, int H) { return (size_t)W * (size_t)H; }
+// Bytes of one frame of a stack of format p in a clip of W x H (luma) pixels: launch_warp's frame stride.  A chroma plane has W / 2 pixels a row (W
+// even) and H / 2 rows (NV12, P010: H even) or H rows (NV16: H of either parity); everything else has W H pixels.
+constexpr size_t px_frame_bytes(Px p, int W, int H)
+{
+    const bool chroma = p == Px::NV12_UV || p == Px::P010_UV || p == Px::NV16_UV;
+    return (size_t)(chroma ? W / 2 : W) * (size_t)(chroma && p != Px::NV16_UV ? H / 2 : H) * (size_t)px_bytes(p);
+}
+static_assert(px_frame_bytes(Px::NV12_UV, 6, 4) == 12 && px_frame_bytes(Px::P010_UV, 6, 4) == 24, "4:2:0 chroma: (W / 2) (H / 2) pixels of 2 or 4 bytes");
+static_assert(px_frame_bytes(Px::NV16_UV, 6, 3) == 18 && px_frame_bytes(Px::U8C3, 6, 3) == 54, "4:2:2 chroma: (W / 2) H pixels of 2 bytes; a frame: W H pixels");
 // The border colour as the warp kernels take it, from the caller's px_channels(p) samples: B | G << 8 | R << 16 (u8c3),
 // B | G << 16 | R << 32 (u16c3), the byte (u8c1), B | G << 8 | R << 16 | A << 24 (u8c4), U | V << 8 (nv12_uv, nv16_uv), the sample (u16c1), U | V << 16 (p010_uv).
 inline uint64_t pack_border(Px p, const void* samples)

@@ -323,7 +323,7 @@ int launch_warp(Px px, const void* frames, void* out, const TableView& tv, int n
     // are re-cut for 1- and 4-byte pixels, not for 6-byte ones, so uint16 frames never stage
     const bool stage = px != Px::U16C3 && ((uintptr_t)frames & 3u) == 0;       // (the planes' kernels take no window either: unused there)
     // (Px::MAPS: `frames` is null and stays unused, `out` holds 8 W H bytes per frame; Px::NV12_UV, Px::P010_UV, Px::NV16_UV: the chroma plane's own bytes)
-    const size_t frame_bytes = px == Px::NV12_UV ? nv12_uv_frame_bytes(W, H) : px == Px::NV16_UV ? nv16_uv_frame_bytes(W, H) : px == Px::P010_UV ? p010_uv_frame_bytes(W, H) : (size_t)W * H * px_bytes(px);
+    const size_t frame_bytes = px_frame_bytes(px, W, H);
     for (int f0 = 0; f0 < n; f0 += (int)per_launch) {
         const int m = n - f0 < (int)per_launch ? n - f0 : (int)per_launch;
         const WarpRange r{ tv.plan + (size_t)f0 * g.per_frame, tv.regions + (size_t)f0 * g.per_frame,

@@ -98,10 +98,7 @@ __device__ __forceinline__ void store_tail(const float (&u)[4], const float (&v)
                                            int32_t* __restrict__ crop, int32_t* __restrict__ clip, const GreyWindow& win, const uint8_t* s_win)
 {
     if constexpr (PX == Px::MAPS) maps_store_f32(u, v, f, x0, y, active, W, H, reinterpret_cast<float*>(out));
-    else if constexpr (PX == Px::NV12_UV) remap_store_nv12_uv(u, v, f, x0, y, active, W, H, frames, out, border);
-    else if constexpr (PX == Px::NV16_UV) remap_store_nv16_uv(u, v, f, x0, y, active, W, H, frames, out, border);
-    else if constexpr (PX == Px::P010_UV)
-        remap_store_p010_uv(u, v, f, x0, y, active, W, H, reinterpret_cast<const uint16_t*>(frames), reinterpret_cast<uint16_t*>(out), border);
+    else if constexpr (PX == Px::NV12_UV || PX == Px::NV16_UV || PX == Px::P010_UV) remap_store_chroma<PX>(u, v, f, x0, y, active, W, H, frames, out, border);
     else if constexpr (PX == Px::U16C1)
         remap_store_u16c1(u, v, f, x0, y, active, W, H, reinterpret_cast<const uint16_t*>(frames), reinterpret_cast<uint16_t*>(out), border, crop, clip);
     else if constexpr (px_is_plane(PX)) remap_store_plane<PX, SCAN>(u, v, f, x0, y, active, W, H, frames, out, border16, crop, clip);
@@ -140,17 +137,18 @@ __device__ __forceinline__ void store_bgr4(uint8_t* __restrict__ dst, int W, int
 // warp (the plan's windows are cut for 3-byte pixels), the hot and pair shortcuts like the maps (they need no window), the general path for the rest.
 // PX = Px::NV12_UV: the chroma plane of an NV12 clip (nv12_chroma_footprint, warp_nv12.hip) on the LUMA frame's plan: W, H, the footprints, the
 // ownership and the coordinates are the luma frame's -- the maps kernel's paths, so (u, v) are its values bit for bit --, `frames` / `out` hold
-// (W / 2) (H / 2) pixels of two bytes per frame, the border is U | V << 8 in `border`, and the pixels go through remap_store_nv12_uv, which halves
+// (W / 2) (H / 2) pixels of two bytes per frame, the border is U | V << 8 in `border`, and the pixels go through remap_store_chroma, which halves
 // the coordinates of the even luma pixels.  Taps from global memory; `crop` / `clip` are never touched (null: the luma launch owns them).
 // PX = Px::NV16_UV: the chroma plane of an NV16 clip (nv16_chroma_footprint, warp_nv16.hip): Px::NV12_UV on a plane of full height -- `frames` /
-// `out` hold (W / 2) H pixels of two bytes per frame, H of either parity, and the pixels go through remap_store_nv16_uv, where every row emits and
+// `out` hold (W / 2) H pixels of two bytes per frame, H of either parity, and the pixels go through remap_store_chroma, where every row emits and
 // only the x coordinate is halved.  Taps from global memory, the hot and pair shortcuts (NOWIN), `crop` / `clip` never touched, like NV12.
 // PX = Px::U16C1: the luma planes of a P010 clip (warp16c1_footprint, warp_c1_16.hip): `frames` / `out` hold W H uint16 samples per frame, the
 // border sample is `border`, and the pixels go through remap_store_u16c1 -- Px::U16C3's arithmetic on one channel, taps from global memory.
 // Unlike Px::U16C3 it takes the hot and pair shortcuts (NOWIN), like the float32 plane whose tail has the same shape: one third of the
 // uint16 BGR taps leaves the ownership and coordinate code as most of a footprint's work, and the shortcuts are what shortens that.
 // PX = Px::P010_UV: the chroma plane of a P010 clip (p010_chroma_footprint, warp_p010.hip): Px::NV12_UV on pixels of two uint16 samples --
-// (W / 2) (H / 2) pixels of four bytes per frame, the border is U | V << 16 in `border`, the pixels go through remap_store_p010_uv.
+// (W / 2) (H / 2) pixels of four bytes per frame, the border is U | V << 16 in `border`, the pixels go through remap_store_chroma's
+// uint16 arithmetic.
 template <Px PX, bool STAGE, bool SCAN>
 __device__ __forceinline__ void footprint_body(const uint32_t f, const uint32_t t, const FootPlan* __restrict__ plan, const FootRegion* __restrict__ regions,
                                                const WarpGeom& g, const uint8_t* __restrict__ frames,

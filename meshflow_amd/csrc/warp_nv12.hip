@@ -10,7 +10,7 @@
 namespace mf {
 
 // warp_kernel's footprint order and ownership / coordinate code on the LUMA frame's plan (W, H: the luma size): the maps kernel's hot and pair
-// shortcuts, footprint_body's general path for everything else, then remap_store_nv12_uv -- a lane owns four consecutive luma pixels, the lanes
+// shortcuts, footprint_body's general path for everything else, then remap_store_chroma -- a lane owns four consecutive luma pixels, the lanes
 // of even rows emit the chroma samples of their pixels 0 and 2 as one 4-byte store.  It reads the cell table and the chroma plane and never
 // touches the crop rows or the clip rectangle.  `uv` / `out`: [n][H/2][W/2][2] bytes of THIS launch's frames; `border`: U | V << 8.
 __global__ __launch_bounds__(64) void nv12_chroma_footprint(const FootPlan* __restrict__ plan, const FootRegion* __restrict__ regions, WarpGeom g,
@@ -24,7 +24,7 @@ __global__ __launch_bounds__(64) void nv12_chroma_footprint(const FootPlan* __re
     footprint_body<Px::NV12_UV, false, false>(f, t, plan, regions, g, uv, records, out, edges, n, W, H, C, border, nullptr, nullptr);
 }
 
-// launch_warp's launch for one frame range of chroma planes (r.frames / r.out advanced by nv12_uv_frame_bytes per frame; r.crop, r.bounds unused)
+// launch_warp's launch for one frame range of chroma planes (r.frames / r.out advanced by px_frame_bytes per frame; r.crop, r.bounds unused)
 void launch_nv12_chroma_range(const WarpGeom& g, const WarpRange& r, int W, int H, int C, uint32_t border_uv, hipStream_t st)
 {
     const dim3 grid(g.per_xcd * 8u, (uint32_t)r.m);

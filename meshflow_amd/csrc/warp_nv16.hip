@@ -10,7 +10,7 @@
 namespace mf {
 
 // nv12_chroma_footprint on a plane of full height: warp_kernel's footprint order and ownership / coordinate code on the LUMA frame's plan (W, H:
-// the luma size), the maps kernel's hot and pair shortcuts, footprint_body's general path for everything else, then remap_store_nv16_uv -- a
+// the luma size), the maps kernel's hot and pair shortcuts, footprint_body's general path for everything else, then remap_store_chroma -- a
 // lane owns four consecutive luma pixels, the lanes of EVERY row emit the chroma samples of their pixels 0 and 2 as one 4-byte store.  It reads
 // the cell table and the chroma plane and never touches the crop rows or the clip rectangle.  `uv` / `out`: [n][H][W/2][2] bytes of THIS
 // launch's frames; `border`: U | V << 8.
@@ -25,7 +25,7 @@ __global__ __launch_bounds__(64) void nv16_chroma_footprint(const FootPlan* __re
     footprint_body<Px::NV16_UV, false, false>(f, t, plan, regions, g, uv, records, out, edges, n, W, H, C, border, nullptr, nullptr);
 }
 
-// launch_warp's launch for one frame range of chroma planes (r.frames / r.out advanced by nv16_uv_frame_bytes per frame; r.crop, r.bounds unused)
+// launch_warp's launch for one frame range of chroma planes (r.frames / r.out advanced by px_frame_bytes per frame; r.crop, r.bounds unused)
 void launch_nv16_chroma_range(const WarpGeom& g, const WarpRange& r, int W, int H, int C, uint32_t border_uv, hipStream_t st)
 {
     const dim3 grid(g.per_xcd * 8u, (uint32_t)r.m);

@@ -9,7 +9,7 @@
 namespace mf {
 
 // nv12_chroma_footprint on 4-byte pixels: the LUMA frame's plan (W, H: the luma size), the maps kernel's hot and pair shortcuts,
-// footprint_body's general path for everything else, then remap_store_p010_uv -- a lane owns four consecutive luma pixels, the lanes of even
+// footprint_body's general path for everything else, then remap_store_chroma -- a lane owns four consecutive luma pixels, the lanes of even
 // rows emit the chroma samples of their pixels 0 and 2 as one 8-byte store.  It reads the cell table and the chroma plane, uses no atomic and
 // never touches the crop rows or the clip rectangle.  `uv` / `out`: [n][H/2][W/2][2] uint16 samples of THIS launch's frames; `border`: U | V << 16.
 __global__ __launch_bounds__(64) void p010_chroma_footprint(const FootPlan* __restrict__ plan, const FootRegion* __restrict__ regions, WarpGeom g,
@@ -24,7 +24,7 @@ __global__ __launch_bounds__(64) void p010_chroma_footprint(const FootPlan* __re
                                               edges, n, W, H, C, border, nullptr, nullptr);
 }
 
-// launch_warp's launch for one frame range of chroma planes (r.frames / r.out advanced by p010_uv_frame_bytes per frame; r.crop, r.bounds unused)
+// launch_warp's launch for one frame range of chroma planes (r.frames / r.out advanced by px_frame_bytes per frame; r.crop, r.bounds unused)
 void launch_p010_chroma_range(const WarpGeom& g, const WarpRange& r, int W, int H, int C, uint32_t border_uv, hipStream_t st)
 {
     const dim3 grid(g.per_xcd * 8u, (uint32_t)r.m);

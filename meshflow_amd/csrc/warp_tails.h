@@ -1,5 +1,6 @@
 // The tails of footprint_body's other formats (device only, included through warp_body.h): the lane's four pixels at source coordinates
-// (u, v) -- taps, blend, crop flags, store -- for uint16 BGR, grey, 4-channel uint8, the coordinate maps, the side planes, NV12 and NV16 chroma and the two planes of a P010 clip.
+// (u, v) -- taps, blend, crop flags, store -- for uint16 BGR, grey, 4-channel uint8, the coordinate maps, the side planes, the luma plane of a P010 clip
+// and the chroma plane of every semi-planar YUV clip (remap_store_chroma: NV12, NV16, P010).
 #ifndef MF_WARP_TAILS_H
 #define MF_WARP_TAILS_H
 #include "warp_coords.h"
@@ -508,155 +509,7 @@ __device__ __forceinline__ void remap_store_plane(const float (&u)[4], const flo
         remap_store_plane_nearest<px_sample_bytes(PX), SCAN>(u, v, f, x0, y, active, W, H, planes, out, fill, crop, clip);
 }
 
-// ---- the chroma plane of an NV12 clip: cv2.remap of CV_8UC2 on the half-resolution plane, at half the luma coordinates ----------------
-// The blend of one two-byte pixel from its tap rows `a` (row iy: U0 V0 U1 V1, the pixels ix and ix + 1) and `b` (row iy + 1) at fixed-point
-// coordinates (sx, sy): blend_c4's arithmetic on two channels -- the two horizontal neighbours of a channel are bytes c and c + 2 of a tap
-// row, lerped vertically at once in 16-bit fields, then v_dot2_u32_u16 horizontally: (sum w_k s_k + 2^14) >> 15 per channel.  Returns U | V << 8.
-__device__ __forceinline__ uint32_t blend_uv(uint32_t a, uint32_t b, uint32_t sx, uint32_t sy)
-{
-    const uint32_t fy = sy & 31u, wy = 32u - fy;
-    const uint32_t wq = umad24(sx & 31u, 0x3FFFC0u, 2048u);               // 64 (32 - fx) | 64 fx << 16
-    const uint32_t vu = umad24(b & 0x00FF00FFu, fy, __umul24(a & 0x00FF00FFu, wy));
-    const uint32_t vv = umad24((b >> 8) & 0x00FF00FFu, fy, __umul24((a >> 8) & 0x00FF00FFu, wy));
-    return __builtin_amdgcn_perm(udot2(vv, wq, 32768u), udot2(vu, wq, 32768u), 0x0C0C0602u);
-}
-
-// Footprint-level tail of the NV12_UV instantiation of footprint_body.  The lane owns four consecutive LUMA pixels of row y at coordinates
-// (u, v) -- the maps kernel's, bit for bit -- and chroma is sited at the even luma sample: a lane of an even row emits chroma samples
-// (x0 / 2, y / 2) and (x0 / 2 + 1, y / 2) from its pixels 0 and 2, the lanes of odd rows emit nothing.  A sample's source position is half
-// its luma pixel's, halved in float32 (exact), then cv2.remap's 8-bit fixed point on the (H / 2, W / 2) plane of two-byte pixels: a pixel no
-// cell owns, at (W + 1, H + 1), halves to a position outside that plane and comes out as the border like any other.  Deep-interior
-// footprints (wave-uniform) take each sample's two tap rows as one 4-byte load apiece (the plane is only 2-byte aligned: unaligned dword
-// loads); the others take every tap as a 2-byte load at its position clamped into the plane and replace outside taps by `border`
-// (U | V << 8).  Nothing outside the plane's bytes is read, no crop value is touched (the luma launch owns them), and the lane's two samples
-// go out as one 4-byte store (2 bytes in the lane that holds the last sample of a row with W % 4 == 2).  All plane offsets are 64-bit.
-__device__ __forceinline__ void remap_store_nv12_uv(const float (&u)[4], const float (&v)[4], uint32_t f, int x0, int y, bool active, int W, int H,
-                                                    const uint8_t* __restrict__ planes, uint8_t* __restrict__ out, uint32_t border)
-{
-    const int Wc = W >> 1, Hc = H >> 1;
-    const uint64_t plane_bytes = 2ull * (uint64_t)((uint32_t)Wc * (uint32_t)Hc);
-    const uint8_t* __restrict__ src = planes + (uint64_t)f * plane_bytes;
-    const bool emit = active && (y & 1) == 0;                           // (x0 is a multiple of 4: pixels 0 and 2 are even columns)
-    const bool two = x0 + 2 < W;                                        // (the lane's second sample exists; its pixel 2 stands in for nothing else)
-    // the lane's two samples twice over, so that the four-pixel helpers of warp_coords.h serve (the duplicates fold away)
-    const float h0 = u[0] * 0.5f, g0 = v[0] * 0.5f, h1 = two ? u[2] * 0.5f : h0, g1 = two ? v[2] * 0.5f : g0;
-    const float uc[4] = { h0, h1, h0, h1 }, vc[4] = { g0, g1, g0, g1 };
-    uint32_t bx[4], by[4];
-    fixed_point(uc, vc, bx, by);
-    const bool deep = deep_interior(bx, by, Wc, Hc);
-    const bool fast = __ballot(emit && !deep) == 0;
-    uint32_t o[2];                                                      // the lane's two output pixels, U | V << 8
-    if (emit) {
-        if (fast) {
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                const uint32_t ix = __builtin_amdgcn_ubfe(bx[j], 5, 17), iy = __builtin_amdgcn_ubfe(by[j], 5, 17);
-                const uint8_t* __restrict__ p = src + 2ull * (uint64_t)(iy * (uint32_t)Wc + ix);
-                uint32_t a, b;                                          // pixels ix and ix + 1 of rows iy and iy + 1
-                __builtin_memcpy(&a, p, 4);
-                __builtin_memcpy(&b, p + 2u * (uint32_t)Wc, 4);
-                o[j] = blend_uv(a, b, bx[j], by[j]);
-            }
-        } else {
-            // plane borders, uncovered pixels, out-of-range coordinates
-            const bool narrow = narrow_coords(bx, by);
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                const int sxx = fixed_coord(narrow, bx[j], uc[j]), syy = fixed_coord(narrow, by[j], vc[j]);
-                const int ix = sxx >> 5, iy = syy >> 5;                 // (saturation to int16 cannot change any decision below)
-                // (a 2 x 2 footprint wholly outside needs no special case: four border taps with weights summing to 1024 give the border)
-                const ClampedTaps t = clamped_taps(ix, iy, Wc, Hc);
-                uint16_t p00, p01, p10, p11;
-                __builtin_memcpy(&p00, src + 2ull * (uint64_t)(t.r0 + t.cx0), 2);
-                __builtin_memcpy(&p01, src + 2ull * (uint64_t)(t.r0 + t.cx1), 2);
-                __builtin_memcpy(&p10, src + 2ull * (uint64_t)(t.r1 + t.cx0), 2);
-                __builtin_memcpy(&p11, src + 2ull * (uint64_t)(t.r1 + t.cx1), 2);
-                const uint32_t q00 = t.in_x0 && t.in_y0 ? (uint32_t)p00 : border, q01 = t.in_x1 && t.in_y0 ? (uint32_t)p01 : border;
-                const uint32_t q10 = t.in_x0 && t.in_y1 ? (uint32_t)p10 : border, q11 = t.in_x1 && t.in_y1 ? (uint32_t)p11 : border;
-                o[j] = blend_uv(q00 | (q01 << 16), q10 | (q11 << 16), (uint32_t)sxx, (uint32_t)syy);
-            }
-        }
-        uint8_t* __restrict__ d = out + (uint64_t)f * plane_bytes + 2ull * (uint64_t)((uint32_t)(y >> 1) * (uint32_t)Wc + (uint32_t)(x0 >> 1));
-        if (two) {                                                      // 4 bytes, dword-aligned unless W % 4 == 2 (then an unaligned store)
-            const uint32_t w4 = o[0] | (o[1] << 16);
-            __builtin_memcpy(d, &w4, 4);
-        } else {
-            const uint16_t w2 = (uint16_t)o[0];
-            __builtin_memcpy(d, &w2, 2);
-        }
-    }
-}
-
-// ---- the chroma plane of an NV16 clip (4:2:2): cv2.remap of CV_8UC2 on the half-WIDTH plane, at (u / 2, v) of the even luma pixels ----------
-// Footprint-level tail of the NV16_UV instantiation of footprint_body: remap_store_nv12_uv with chroma rows that are the luma rows.  The lane
-// owns four consecutive LUMA pixels of row y at coordinates (u, v) -- the maps kernel's, bit for bit -- and chroma is sited at the even luma
-// sample of the same row: EVERY row's lanes emit, chroma samples (x0 / 2, y) and (x0 / 2 + 1, y) from their pixels 0 and 2.  A sample's source
-// position is (u * 0.5f, v) -- the halving is exact in float32, v stays what it is --, then cv2.remap's 8-bit fixed point on the (H, W / 2) plane
-// of two-byte pixels: a pixel no cell owns, at (W + 1, H + 1), lands at ((W + 1) / 2, H + 1), outside that plane, and comes out as the border
-// like any other.  Deep-interior footprints (wave-uniform; the test, the clamped taps and the ballot all on (Wc, Hc) = (W / 2, H)) take each
-// sample's two tap rows as one 4-byte load apiece (the plane is only 2-byte aligned: unaligned dword loads); the others take every tap as a
-// 2-byte load at its position clamped into the plane and replace outside taps by `border` (U | V << 8).  Nothing outside the plane's bytes is
-// read, no crop value is touched (the luma launch owns them), and the lane's two samples go out as one 4-byte store (2 bytes in the lane that
-// holds the last sample of a row with W % 4 == 2; an unaligned dword store where the plane is only 2-byte aligned).  All plane offsets are
-// 64-bit (H may have either parity: the plane has W H bytes per frame).
-__device__ __forceinline__ void remap_store_nv16_uv(const float (&u)[4], const float (&v)[4], uint32_t f, int x0, int y, bool active, int W, int H,
-                                                    const uint8_t* __restrict__ planes, uint8_t* __restrict__ out, uint32_t border)
-{
-    const int Wc = W >> 1, Hc = H;
-    const uint64_t plane_bytes = 2ull * (uint64_t)((uint32_t)Wc * (uint32_t)Hc);
-    const uint8_t* __restrict__ src = planes + (uint64_t)f * plane_bytes;
-    const bool emit = active;                                           // (x0 is a multiple of 4: pixels 0 and 2 are even columns)
-    const bool two = x0 + 2 < W;                                        // (the lane's second sample exists; its pixel 2 stands in for nothing else)
-    // the lane's two samples twice over, so that the four-pixel helpers of warp_coords.h serve (the duplicates fold away)
-    const float h0 = u[0] * 0.5f, g0 = v[0], h1 = two ? u[2] * 0.5f : h0, g1 = two ? v[2] : g0;
-    const float uc[4] = { h0, h1, h0, h1 }, vc[4] = { g0, g1, g0, g1 };
-    uint32_t bx[4], by[4];
-    fixed_point(uc, vc, bx, by);
-    const bool deep = deep_interior(bx, by, Wc, Hc);
-    const bool fast = __ballot(emit && !deep) == 0;
-    uint32_t o[2];                                                      // the lane's two output pixels, U | V << 8
-    if (emit) {
-        if (fast) {
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                const uint32_t ix = __builtin_amdgcn_ubfe(bx[j], 5, 17), iy = __builtin_amdgcn_ubfe(by[j], 5, 17);
-                const uint8_t* __restrict__ p = src + 2ull * (uint64_t)(iy * (uint32_t)Wc + ix);
-                uint32_t a, b;                                          // pixels ix and ix + 1 of rows iy and iy + 1
-                __builtin_memcpy(&a, p, 4);
-                __builtin_memcpy(&b, p + 2u * (uint32_t)Wc, 4);
-                o[j] = blend_uv(a, b, bx[j], by[j]);
-            }
-        } else {
-            // plane borders, uncovered pixels, out-of-range coordinates
-            const bool narrow = narrow_coords(bx, by);
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                const int sxx = fixed_coord(narrow, bx[j], uc[j]), syy = fixed_coord(narrow, by[j], vc[j]);
-                const int ix = sxx >> 5, iy = syy >> 5;                 // (saturation to int16 cannot change any decision below)
-                // (a 2 x 2 footprint wholly outside needs no special case: four border taps with weights summing to 1024 give the border)
-                const ClampedTaps t = clamped_taps(ix, iy, Wc, Hc);
-                uint16_t p00, p01, p10, p11;
-                __builtin_memcpy(&p00, src + 2ull * (uint64_t)(t.r0 + t.cx0), 2);
-                __builtin_memcpy(&p01, src + 2ull * (uint64_t)(t.r0 + t.cx1), 2);
-                __builtin_memcpy(&p10, src + 2ull * (uint64_t)(t.r1 + t.cx0), 2);
-                __builtin_memcpy(&p11, src + 2ull * (uint64_t)(t.r1 + t.cx1), 2);
-                const uint32_t q00 = t.in_x0 && t.in_y0 ? (uint32_t)p00 : border, q01 = t.in_x1 && t.in_y0 ? (uint32_t)p01 : border;
-                const uint32_t q10 = t.in_x0 && t.in_y1 ? (uint32_t)p10 : border, q11 = t.in_x1 && t.in_y1 ? (uint32_t)p11 : border;
-                o[j] = blend_uv(q00 | (q01 << 16), q10 | (q11 << 16), (uint32_t)sxx, (uint32_t)syy);
-            }
-        }
-        uint8_t* __restrict__ d = out + (uint64_t)f * plane_bytes + 2ull * (uint64_t)((uint32_t)y * (uint32_t)Wc + (uint32_t)(x0 >> 1));
-        if (two) {                                                      // 4 bytes, dword-aligned unless W % 4 == 2 (then an unaligned store)
-            const uint32_t w4 = o[0] | (o[1] << 16);
-            __builtin_memcpy(d, &w4, 4);
-        } else {
-            const uint16_t w2 = (uint16_t)o[0];
-            __builtin_memcpy(d, &w2, 2);
-        }
-    }
-}
-
-// ---- the planes of a P010 / P012 / P016 clip: cv2.remap's CV_16U arithmetic (blend16 at the head of this file) on one and on two channels ----
+// ---- the luma plane of a P010 / P012 / P016 clip: cv2.remap's CV_16U arithmetic (blend16 at the head of this file) on one channel -----------
 // Footprint-level tail of the U16C1 instantiation of footprint_body: remap_store_u16 on one channel -- out is, bit for bit, channel 0 of
 // remap_store_u16 on the plane repeated three times.  Deep-interior footprints (every tap two pixels inside the frame, no crop flag possible)
 // take each pixel's two tap rows as one 4-byte load apiece (the frame may be only 2-byte aligned: unaligned dword loads) and blend pixels
@@ -743,47 +596,82 @@ __device__ __forceinline__ void remap_store_u16c1(const float (&u)[4], const flo
     }
 }
 
-// Footprint-level tail of the P010_UV instantiation of footprint_body: remap_store_nv12_uv's lane mapping and coordinates -- a lane of an even
-// row emits chroma samples (x0 / 2, y / 2) and (x0 / 2 + 1, y / 2) from its luma pixels 0 and 2 at half their (u, v), halved in float32
-// (exact) -- with the CV_16U arithmetic on the (H / 2, W / 2) plane of 4-byte pixels.  A tap is one 4-byte word, U | V << 16; the pair goes
-// through blend16x2 with the sample's four weights computed once, so U and V never mix.  Deep-interior footprints (wave-uniform) fetch a tap
-// row's two words as one 8-byte load (the plane may be only 2-byte aligned: unaligned loads); the others take every tap as a 4-byte load at
-// its position clamped into the plane and replace outside taps by `border` (U | V << 16), and a 2 x 2 footprint wholly outside the plane
-// -- an unowned pixel's, at ((W + 1) / 2, (H + 1) / 2), among them -- gives `border` itself.  Nothing outside the plane's bytes is read, no
-// crop value is touched (the luma launch owns them), and the lane's two samples go out as one 8-byte store (4 bytes in the lane that holds the
-// last sample of a row with W % 4 == 2).  All plane offsets are 64-bit.
-__device__ __forceinline__ void remap_store_p010_uv(const float (&u)[4], const float (&v)[4], uint32_t f, int x0, int y, bool active, int W, int H,
-                                                    const uint16_t* __restrict__ planes, uint16_t* __restrict__ out, uint32_t border)
+// ---- the interleaved chroma plane of a semi-planar YUV clip (NV12, NV16, P010): cv2.remap of a two-channel plane at the luma coordinates ----
+// The blend of one two-byte pixel from its tap rows `a` (row iy: U0 V0 U1 V1, the pixels ix and ix + 1) and `b` (row iy + 1) at fixed-point
+// coordinates (sx, sy): blend_c4's arithmetic on two channels -- the two horizontal neighbours of a channel are bytes c and c + 2 of a tap
+// row, lerped vertically at once in 16-bit fields, then v_dot2_u32_u16 horizontally: (sum w_k s_k + 2^14) >> 15 per channel.  Returns U | V << 8.
+__device__ __forceinline__ uint32_t blend_uv(uint32_t a, uint32_t b, uint32_t sx, uint32_t sy)
 {
-    const int Wc = W >> 1, Hc = H >> 1;
+    const uint32_t fy = sy & 31u, wy = 32u - fy;
+    const uint32_t wq = umad24(sx & 31u, 0x3FFFC0u, 2048u);               // 64 (32 - fx) | 64 fx << 16
+    const uint32_t vu = umad24(b & 0x00FF00FFu, fy, __umul24(a & 0x00FF00FFu, wy));
+    const uint32_t vv = umad24((b >> 8) & 0x00FF00FFu, fy, __umul24((a >> 8) & 0x00FF00FFu, wy));
+    return __builtin_amdgcn_perm(udot2(vv, wq, 32768u), udot2(vu, wq, 32768u), 0x0C0C0602u);
+}
+
+// Footprint-level tail of the NV12_UV, NV16_UV and P010_UV instantiations of footprint_body.  The lane owns four consecutive LUMA pixels of
+// row y at coordinates (u, v) -- the maps kernel's, bit for bit -- and chroma is sited at the even luma sample: a lane that emits writes the
+// chroma samples x0 / 2 and x0 / 2 + 1 of its chroma row from its pixels 0 and 2.  A sample's source position is its luma pixel's, halved in
+// float32 (exact) along every axis the plane subsamples, then cv2.remap's 8-bit fixed point on the (Hc, Wc) plane of pixels of two samples T,
+// U first: a pixel no cell owns, at (W + 1, H + 1), lands outside that plane and comes out as the border like any other.  Deep-interior
+// footprints (wave-uniform: the test, the clamped taps and the ballot are all on (Wc, Hc)) take each sample's two tap rows as one load of two
+// pixels apiece (the plane is only 2-byte aligned: unaligned loads); the others take every tap as a one-pixel load at its position clamped
+// into the plane and replace outside taps by `border`.  Nothing outside the plane's bytes is read, no crop value is touched (the luma launch
+// owns them), and the lane's two samples go out as one store of two pixels (of one in the lane that holds the last sample of a row with
+// W % 4 == 2; an unaligned store where W % 4 == 2 or the plane is only 2-byte aligned).  All plane offsets are 64-bit, in units of T.
+// NV12_UV (4:2:0, T = uint8): Wc = W / 2, Hc = H / 2; the lanes of even rows emit, into chroma row y / 2, the lanes of odd rows nothing; the
+// position is (u / 2, v / 2), an unowned pixel's ((W + 1) / 2, (H + 1) / 2).  Pixels are 2 bytes, `border` is U | V << 8, the blend is
+// blend_uv's integer one: a 2 x 2 footprint wholly outside needs no special case.
+// NV16_UV (4:2:2, T = uint8): NV12_UV with chroma rows that are the luma rows -- Wc = W / 2, Hc = H, H of either parity (the plane has W H
+// bytes per frame); EVERY row's lanes emit, into chroma row y; the position is (u / 2, v), v staying what it is, an unowned pixel's
+// ((W + 1) / 2, H + 1).
+// P010_UV (4:2:0, T = uint16): NV12_UV's lane mapping and coordinates with the CV_16U arithmetic.  Pixels are 4 bytes, a tap is one word
+// U | V << 16 and so is `border`; the pair goes through blend16x2 with the sample's four weights computed once, so U and V never mix.  Float
+// products of the border need not sum back to it, so a 2 x 2 footprint wholly outside the plane -- an unowned pixel's among them -- gives
+// `border` itself.  The deep-interior blend needs no clamp (rint(t) <= 65535 there, see remap_store_u16); the other saturates like blend16.
+template <Px PX>
+__device__ __forceinline__ void remap_store_chroma(const float (&u)[4], const float (&v)[4], uint32_t f, int x0, int y, bool active, int W, int H,
+                                                   const uint8_t* __restrict__ planes, uint8_t* __restrict__ out, uint32_t border)
+{
+    static_assert(PX == Px::NV12_UV || PX == Px::NV16_UV || PX == Px::P010_UV, "the semi-planar chroma planes");
+    constexpr bool HALF_ROWS = PX != Px::NV16_UV, U16 = PX == Px::P010_UV;
+    typedef typename PlaneElem<U16 ? 2 : 1>::type T;
+    const int Wc = W >> 1, Hc = HALF_ROWS ? H >> 1 : H;
     const uint64_t plane_samples = 2ull * (uint64_t)((uint32_t)Wc * (uint32_t)Hc);
-    const uint16_t* __restrict__ src = planes + (uint64_t)f * plane_samples;
-    const bool emit = active && (y & 1) == 0;                           // (x0 is a multiple of 4: pixels 0 and 2 are even columns)
-    const bool two = x0 + 2 < W;                                        // (the lane's second sample exists)
+    const T* __restrict__ src = reinterpret_cast<const T*>(planes) + (uint64_t)f * plane_samples;
+    const bool emit = HALF_ROWS ? active && (y & 1) == 0 : active;      // (x0 is a multiple of 4: pixels 0 and 2 are even columns)
+    const bool two = x0 + 2 < W;                                        // (the lane's second sample exists; its pixel 2 stands in for nothing else)
     // the lane's two samples twice over, so that the four-pixel helpers of warp_coords.h serve (the duplicates fold away)
-    const float h0 = u[0] * 0.5f, g0 = v[0] * 0.5f, h1 = two ? u[2] * 0.5f : h0, g1 = two ? v[2] * 0.5f : g0;
+    const float h0 = u[0] * 0.5f, g0 = HALF_ROWS ? v[0] * 0.5f : v[0], h1 = two ? u[2] * 0.5f : h0, g1 = two ? (HALF_ROWS ? v[2] * 0.5f : v[2]) : g0;
     const float uc[4] = { h0, h1, h0, h1 }, vc[4] = { g0, g1, g0, g1 };
     uint32_t bx[4], by[4];
     fixed_point(uc, vc, bx, by);
     const bool deep = deep_interior(bx, by, Wc, Hc);
     const bool fast = __ballot(emit && !deep) == 0;
-    uint32_t o[2];                                                      // the lane's two output pixels, U | V << 16
+    uint32_t o[2];                                                      // the lane's two output pixels, U | V << 8 (U | V << 16 for U16)
     if (emit) {
         if (fast) {
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
                 const uint32_t ix = __builtin_amdgcn_ubfe(bx[j], 5, 17), iy = __builtin_amdgcn_ubfe(by[j], 5, 17);
-                const uint16_t* __restrict__ p = src + 2ull * (uint64_t)(iy * (uint32_t)Wc + ix);
-                uint2 a, b;                                             // pixels ix and ix + 1 of rows iy and iy + 1
-                __builtin_memcpy(&a, p, 8);
-                __builtin_memcpy(&b, p + 2u * (uint32_t)Wc, 8);
-                const float ax = (float)(bx[j] & 31u) * 0.03125f, ay = (float)(by[j] & 31u) * 0.03125f;
-                const float ax0 = 1.0f - ax, ay0 = 1.0f - ay;
-                const float w0 = ay0 * ax0, w1 = ay0 * ax, w2 = ay * ax0, w3 = ay * ax;
-                const f32x2 t = blend16x2(f32x2{ (float)(a.x & 0xFFFFu), (float)(a.x >> 16) }, f32x2{ (float)(a.y & 0xFFFFu), (float)(a.y >> 16) },
-                                          f32x2{ (float)(b.x & 0xFFFFu), (float)(b.x >> 16) }, f32x2{ (float)(b.y & 0xFFFFu), (float)(b.y >> 16) },
-                                          f32x2{ w0, w0 }, f32x2{ w1, w1 }, f32x2{ w2, w2 }, f32x2{ w3, w3 });
-                o[j] = (uint32_t)rintf(t.x) | ((uint32_t)rintf(t.y) << 16);         // (no clamp: rint(t) <= 65535 here, see remap_store_u16)
+                const T* __restrict__ p = src + 2ull * (uint64_t)(iy * (uint32_t)Wc + ix);
+                if constexpr (U16) {
+                    uint2 a, b;                                         // pixels ix and ix + 1 of rows iy and iy + 1
+                    __builtin_memcpy(&a, p, 8);
+                    __builtin_memcpy(&b, p + 2u * (uint32_t)Wc, 8);
+                    const float ax = (float)(bx[j] & 31u) * 0.03125f, ay = (float)(by[j] & 31u) * 0.03125f;
+                    const float ax0 = 1.0f - ax, ay0 = 1.0f - ay;
+                    const float w0 = ay0 * ax0, w1 = ay0 * ax, w2 = ay * ax0, w3 = ay * ax;
+                    const f32x2 t = blend16x2(f32x2{ (float)(a.x & 0xFFFFu), (float)(a.x >> 16) }, f32x2{ (float)(a.y & 0xFFFFu), (float)(a.y >> 16) },
+                                              f32x2{ (float)(b.x & 0xFFFFu), (float)(b.x >> 16) }, f32x2{ (float)(b.y & 0xFFFFu), (float)(b.y >> 16) },
+                                              f32x2{ w0, w0 }, f32x2{ w1, w1 }, f32x2{ w2, w2 }, f32x2{ w3, w3 });
+                    o[j] = (uint32_t)rintf(t.x) | ((uint32_t)rintf(t.y) << 16);     // (no clamp: rint(t) <= 65535 here, see remap_store_u16)
+                } else {
+                    uint32_t a, b;                                      // pixels ix and ix + 1 of rows iy and iy + 1
+                    __builtin_memcpy(&a, p, 4);
+                    __builtin_memcpy(&b, p + 2u * (uint32_t)Wc, 4);
+                    o[j] = blend_uv(a, b, bx[j], by[j]);
+                }
             }
         } else {
             // plane borders, uncovered pixels, out-of-range coordinates
@@ -792,31 +680,56 @@ __device__ __forceinline__ void remap_store_p010_uv(const float (&u)[4], const f
             for (int j = 0; j < 2; ++j) {
                 const int sxx = fixed_coord(narrow, bx[j], uc[j]), syy = fixed_coord(narrow, by[j], vc[j]);
                 const int ix = sxx >> 5, iy = syy >> 5;                 // (saturation to int16 cannot change any decision below)
-                o[j] = border;
-                if (ix >= Wc || ix + 1 < 0 || iy >= Hc || iy + 1 < 0) continue;     // the 2 x 2 footprint lies wholly outside: the border pixel
+                if constexpr (U16) {
+                    o[j] = border;
+                    if (ix >= Wc || ix + 1 < 0 || iy >= Hc || iy + 1 < 0) continue; // the 2 x 2 footprint lies wholly outside: the border pixel
+                }
                 const ClampedTaps t = clamped_taps(ix, iy, Wc, Hc);
-                uint32_t p00, p01, p10, p11;
-                __builtin_memcpy(&p00, src + 2ull * (uint64_t)(t.r0 + t.cx0), 4);
-                __builtin_memcpy(&p01, src + 2ull * (uint64_t)(t.r0 + t.cx1), 4);
-                __builtin_memcpy(&p10, src + 2ull * (uint64_t)(t.r1 + t.cx0), 4);
-                __builtin_memcpy(&p11, src + 2ull * (uint64_t)(t.r1 + t.cx1), 4);
-                p00 = t.in_x0 && t.in_y0 ? p00 : border; p01 = t.in_x1 && t.in_y0 ? p01 : border;
-                p10 = t.in_x0 && t.in_y1 ? p10 : border; p11 = t.in_x1 && t.in_y1 ? p11 : border;
-                const float ax = (float)(sxx & 31) * 0.03125f, ay = (float)(syy & 31) * 0.03125f;
-                const float ax0 = 1.0f - ax, ay0 = 1.0f - ay;
-                const float w0 = ay0 * ax0, w1 = ay0 * ax, w2 = ay * ax0, w3 = ay * ax;
-                const f32x2 t2 = blend16x2(f32x2{ (float)(p00 & 0xFFFFu), (float)(p00 >> 16) }, f32x2{ (float)(p01 & 0xFFFFu), (float)(p01 >> 16) },
-                                           f32x2{ (float)(p10 & 0xFFFFu), (float)(p10 >> 16) }, f32x2{ (float)(p11 & 0xFFFFu), (float)(p11 >> 16) },
-                                           f32x2{ w0, w0 }, f32x2{ w1, w1 }, f32x2{ w2, w2 }, f32x2{ w3, w3 });
-                o[j] = min((uint32_t)rintf(t2.x), 65535u) | (min((uint32_t)rintf(t2.y), 65535u) << 16);      // saturate_cast<ushort>, as blend16
+                if constexpr (U16) {
+                    uint32_t p00, p01, p10, p11;
+                    __builtin_memcpy(&p00, src + 2ull * (uint64_t)(t.r0 + t.cx0), 4);
+                    __builtin_memcpy(&p01, src + 2ull * (uint64_t)(t.r0 + t.cx1), 4);
+                    __builtin_memcpy(&p10, src + 2ull * (uint64_t)(t.r1 + t.cx0), 4);
+                    __builtin_memcpy(&p11, src + 2ull * (uint64_t)(t.r1 + t.cx1), 4);
+                    p00 = t.in_x0 && t.in_y0 ? p00 : border; p01 = t.in_x1 && t.in_y0 ? p01 : border;
+                    p10 = t.in_x0 && t.in_y1 ? p10 : border; p11 = t.in_x1 && t.in_y1 ? p11 : border;
+                    const float ax = (float)(sxx & 31) * 0.03125f, ay = (float)(syy & 31) * 0.03125f;
+                    const float ax0 = 1.0f - ax, ay0 = 1.0f - ay;
+                    const float w0 = ay0 * ax0, w1 = ay0 * ax, w2 = ay * ax0, w3 = ay * ax;
+                    const f32x2 t2 = blend16x2(f32x2{ (float)(p00 & 0xFFFFu), (float)(p00 >> 16) }, f32x2{ (float)(p01 & 0xFFFFu), (float)(p01 >> 16) },
+                                               f32x2{ (float)(p10 & 0xFFFFu), (float)(p10 >> 16) }, f32x2{ (float)(p11 & 0xFFFFu), (float)(p11 >> 16) },
+                                               f32x2{ w0, w0 }, f32x2{ w1, w1 }, f32x2{ w2, w2 }, f32x2{ w3, w3 });
+                    o[j] = min((uint32_t)rintf(t2.x), 65535u) | (min((uint32_t)rintf(t2.y), 65535u) << 16);  // saturate_cast<ushort>, as blend16
+                } else {
+                    // (a 2 x 2 footprint wholly outside needs no special case: four border taps with weights summing to 1024 give the border)
+                    uint16_t p00, p01, p10, p11;
+                    __builtin_memcpy(&p00, src + 2ull * (uint64_t)(t.r0 + t.cx0), 2);
+                    __builtin_memcpy(&p01, src + 2ull * (uint64_t)(t.r0 + t.cx1), 2);
+                    __builtin_memcpy(&p10, src + 2ull * (uint64_t)(t.r1 + t.cx0), 2);
+                    __builtin_memcpy(&p11, src + 2ull * (uint64_t)(t.r1 + t.cx1), 2);
+                    const uint32_t q00 = t.in_x0 && t.in_y0 ? (uint32_t)p00 : border, q01 = t.in_x1 && t.in_y0 ? (uint32_t)p01 : border;
+                    const uint32_t q10 = t.in_x0 && t.in_y1 ? (uint32_t)p10 : border, q11 = t.in_x1 && t.in_y1 ? (uint32_t)p11 : border;
+                    o[j] = blend_uv(q00 | (q01 << 16), q10 | (q11 << 16), (uint32_t)sxx, (uint32_t)syy);
+                }
             }
         }
-        uint16_t* __restrict__ d = out + (uint64_t)f * plane_samples + 2ull * (uint64_t)((uint32_t)(y >> 1) * (uint32_t)Wc + (uint32_t)(x0 >> 1));
-        if (two) {                                                      // 8 bytes at a 2-byte aligned address: one unaligned store
-            const uint2 q = make_uint2(o[0], o[1]);
-            __builtin_memcpy(d, &q, 8);
+        T* __restrict__ d = reinterpret_cast<T*>(out) + (uint64_t)f * plane_samples +
+                            2ull * (uint64_t)((uint32_t)(HALF_ROWS ? y >> 1 : y) * (uint32_t)Wc + (uint32_t)(x0 >> 1));
+        if constexpr (U16) {
+            if (two) {                                                  // 8 bytes at a 2-byte aligned address: one unaligned store
+                const uint2 q = make_uint2(o[0], o[1]);
+                __builtin_memcpy(d, &q, 8);
+            } else {
+                __builtin_memcpy(d, &o[0], 4);
+            }
         } else {
-            __builtin_memcpy(d, &o[0], 4);
+            if (two) {                                                  // 4 bytes, dword-aligned unless W % 4 == 2 or the plane is not (then an unaligned store)
+                const uint32_t w4 = o[0] | (o[1] << 16);
+                __builtin_memcpy(d, &w4, 4);
+            } else {
+                const uint16_t w2 = (uint16_t)o[0];
+                __builtin_memcpy(d, &w2, 2);
+            }
         }
     }
 }

@@ -42,7 +42,7 @@ def margin_rectangle(crop_margin, W, H):
 
 
 class ClipForm(collections.namedtuple('ClipForm', 'fmt dtype shape')):
-    """The form of a clip, whatever its length: fmt, the `ops._Format420` row of a 4:2:0 pair (d_y, d_uv) or None for a stack (n, ...);
+    """The form of a clip, whatever its length: fmt, the `ops._FormatYuv` row of a 4:2:0 pair (d_y, d_uv) or None for a stack (n, ...);
     the dtype; the shape of a frame -- of a luma plane for a pair.  Two clips of one form compare equal."""
     pair = property(lambda self: self.fmt is not None)
 
@@ -65,7 +65,7 @@ class ClipForm(collections.namedtuple('ClipForm', 'fmt dtype shape')):
         crop-resize to crop = (rectangle, output size or None)."""
         from . import ops
         if self.pair:
-            out = ops._warp_420(self.fmt, *clip, table, ops.P010_BORDER_RED if self.fmt is ops._P010 else ops.NV12_BORDER_RED, None, None)
+            out = ops._warp_yuv(self.fmt, *clip, table, ops.P010_BORDER_RED if self.fmt is ops._P010 else ops.NV12_BORDER_RED, None, None)
             return out if crop is None else ops._crop_resize_420(self.fmt, out[0], out[1], crop[0], crop[1], None, None)
         out = ops.warp(clip, table, border_bgr)
         return out if crop is None else ops.crop_resize(out, crop[0], size=crop[1])
@@ -86,7 +86,7 @@ def luma_of(frames, red_first=False):
             raise ValueError('an NV12 or P010 clip is the pair (d_y, d_uv)')
         d_y, d_uv = frames
         fmt = {torch.uint16: ops._P010}.get(getattr(d_y, 'dtype', None), ops._NV12)         # (whatever is neither fails NV12's checks)
-        ops._need_420(fmt, d_y, d_uv)
+        ops._need_yuv(fmt, d_y, d_uv)
         return ClipForm(fmt, d_y.dtype, tuple(d_y.shape[1:])), (ops.luma(d_y) if fmt is ops._P010 else d_y)
     if isinstance(frames, torch.Tensor) and frames.dtype == torch.uint16 and frames.dim() == 3:
         raise ValueError('a (n, H, W) uint16 stack is the luma plane of a P010 clip: pass the pair (d_y, d_uv)')

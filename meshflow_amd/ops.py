@@ -473,24 +473,26 @@ NV12_BORDER_RED = (81, 90, 240)
 # ... at 10 bits, in P010's high bits: NV12_BORDER_RED << 8
 P010_BORDER_RED = (81 << 8, 90 << 8, 240 << 8)
 
-# One row per 4:2:0 format -- a luma plane stack and a half-resolution interleaved chroma one --: the samples, the format's noun in the
-# messages and the C calls that serve it.
-_Format420 = collections.namedtuple('_Format420', 'dtype noun border warp warp_bounds crop_resize crop_resize_dev workspace_bytes')
+# One row per semi-planar YUV format -- a luma plane stack and an interleaved chroma one of half the width --: the samples, the format's noun
+# in the messages, whether chroma has half the luma rows (4:2:0; else as many: 4:2:2) and the C calls that serve it.
+_FormatYuv = collections.namedtuple('_FormatYuv', 'dtype noun border half_rows warp warp_bounds crop_resize crop_resize_dev workspace_bytes')
 
 
-def _row_420(name, dtype, noun, border):
+def _row_yuv(name, dtype, noun, border, half_rows):
     calls = (getattr(_lib_, f'mf_{op}_{name}') for op in ('warp', 'warp_bounds', 'crop_resize', 'crop_resize_dev'))
-    return _Format420(dtype, noun, border, *calls, getattr(_lib_, f'mf_crop_resize_{name}_workspace_bytes'))
+    return _FormatYuv(dtype, noun, border, half_rows, *calls, getattr(_lib_, f'mf_crop_resize_{name}_workspace_bytes'))
 
 
 _nv12_border = _border_samples(ctypes.c_uint8, 255, 3)
 _p010_border = _border_samples(ctypes.c_uint16, 65535, 3)
-_NV12 = _row_420('nv12', torch.uint8, 'an NV12', _nv12_border)
-_P010 = _row_420('p010', torch.uint16, 'a P010', _p010_border)        # P012 and P016 alike: plain 16-bit samples
+_NV12 = _row_yuv('nv12', torch.uint8, 'an NV12', _nv12_border, True)
+_P010 = _row_yuv('p010', torch.uint16, 'a P010', _p010_border, True)  # P012 and P016 alike: plain 16-bit samples
+# (4:2:2 -- what capture cards, SDI / HDMI grabbers and webcams deliver; its crop-resize is not built)
+_NV16 = _FormatYuv(torch.uint8, 'an NV16', _nv12_border, False, _lib_.mf_warp_nv16, _lib_.mf_warp_bounds_nv16, None, None, None)
 
 
-def _plane_420(t, name, shape, device, dtype):
-    """One plane stack of a 4:2:0 clip: a contiguous device tensor of that dtype and of exactly `shape` on `device`."""
+def _plane_yuv(t, name, shape, device, dtype):
+    """One plane stack of a semi-planar or packed YUV clip: a contiguous device tensor of that dtype and of exactly `shape` on `device`."""
     _need(t, dtype, name)
     if tuple(t.shape) != tuple(shape):
         raise ValueError(f'{name} must have shape {tuple(shape)}, got {tuple(t.shape)}')
@@ -498,38 +500,42 @@ def _plane_420(t, name, shape, device, dtype):
         raise ValueError(f'{name} must be on the device of y, {device}, got {t.device}')
 
 
-def _need_420(fmt, y, uv):
-    """Check the (y, uv) pair of a clip of format `fmt`; returns (n, H, W) of the luma stack."""
-    _need(y, fmt.dtype, 'y')
+def _need_yuv(fmt, y, uv, y_name='y', count='n'):
+    """Check the (y, uv) pair of a clip of format `fmt` -- W even, H too where chroma rows are halved; returns (n, H, W) of the luma stack.
+    y_name, count: what the caller's messages call the luma stack and its length."""
+    _need(y, fmt.dtype, y_name)
     if y.dim() != 3:
-        raise ValueError(f'y must be (n, H, W) luma planes, got shape {tuple(y.shape)}')
+        raise ValueError(f'{y_name} must be ({count}, H, W) luma planes, got shape {tuple(y.shape)}')
     n, H, W = (int(v) for v in y.shape)
-    if W % 2 or H % 2:
-        raise ValueError(f'{fmt.noun} frame has an even width and height, got W={W} H={H}')
-    _plane_420(uv, 'uv', (n, H // 2, W // 2, 2), y.device, fmt.dtype)
+    if fmt.half_rows:
+        if W % 2 or H % 2:
+            raise ValueError(f'{fmt.noun} frame has an even width and height, got W={W} H={H}')
+    elif W % 2:
+        raise ValueError(f'{fmt.noun} frame has an even width, got W={W}')
+    _plane_yuv(uv, 'uv', (n, H // 2 if fmt.half_rows else H, W // 2, 2), y.device, fmt.dtype)
     return n, H, W
 
 
-def _out_420(fmt, y, y_shape, uv_shape, out):
+def _out_yuv(fmt, y, y_shape, uv_shape, out):
     """`out` (None: a new pair) checked as an (out_y, out_uv) pair of these shapes beside `y`."""
     if out is None:
         return torch.empty(y_shape, dtype=fmt.dtype, device=y.device), torch.empty(uv_shape, dtype=fmt.dtype, device=y.device)
     if not isinstance(out, (tuple, list)) or len(out) != 2:
         raise ValueError('out must be a pair (out_y, out_uv)')
     out_y, out_uv = out
-    _plane_420(out_y, 'out_y', y_shape, y.device, fmt.dtype)
-    _plane_420(out_uv, 'out_uv', uv_shape, y.device, fmt.dtype)
+    _plane_yuv(out_y, 'out_y', y_shape, y.device, fmt.dtype)
+    _plane_yuv(out_uv, 'out_uv', uv_shape, y.device, fmt.dtype)
     return out_y, out_uv
 
 
-def _warp_420(fmt, y, uv, table, border_yuv, out, bounds):
-    """`warp_nv12` / `warp_p010`: the checks, then the format's C call."""
-    n, H, W = _need_420(fmt, y, uv)
+def _warp_yuv(fmt, y, uv, table, border_yuv, out, bounds):
+    """`warp_nv12` / `warp_p010` / `warp_nv16`: the checks, then the format's C call."""
+    n, H, W = _need_yuv(fmt, y, uv)
     if (n, W, H) != (table.n, table.W, table.H):
         raise ValueError(f'y {tuple(y.shape)} does not match the cell table (n, H, W) = {(table.n, table.H, table.W)}')
     if len(border_yuv) != 3:
         raise ValueError(f'border_yuv must be (Y, U, V), got {border_yuv!r}')
-    out_y, out_uv = _out_420(fmt, y, y.shape, uv.shape, out)
+    out_y, out_uv = _out_yuv(fmt, y, y.shape, uv.shape, out)
     border = fmt.border(border_yuv)
     if bounds is None:
         _lib.check(fmt.warp(_ptr(y), _ptr(uv), _ptr(out_y), _ptr(out_uv), _ptr(table.buf), n, W, H, table.R, table.C, border, _ptr(table.crop),
@@ -554,7 +560,7 @@ def warp_nv12(y, uv, table, border_yuv=NV12_BORDER_RED, out=None, bounds=None):
     tests' `second_opinion` module: a float64 sampler of both planes, and a ramp on which chroma must equal the luma of its even pixel.)
     border_yuv: (Y, U, V), each clamp(round(v), 0, 255).  The default (81, 90, 240) is BT.601 limited-range red, i.e. the reference's default
     BGR (0, 0, 255).  out: an (out_y, out_uv) pair to fill.  Returns (out_y, out_uv)."""
-    return _warp_420(_NV12, y, uv, table, border_yuv, out, bounds)
+    return _warp_yuv(_NV12, y, uv, table, border_yuv, out, bounds)
 
 
 def warp_p010(y, uv, table, border_yuv=P010_BORDER_RED, out=None, bounds=None):
@@ -571,24 +577,11 @@ def warp_p010(y, uv, table, border_yuv=P010_BORDER_RED, out=None, bounds=None):
     `second_opinion` module, as for `warp_nv12`.)
     border_yuv: (Y, U, V), each clamp(round(v), 0, 65535).  The default (20736, 23040, 61440) is BT.601 limited-range red at 10 bits in P010's
     high bits.  out: an (out_y, out_uv) pair to fill.  Returns (out_y, out_uv)."""
-    return _warp_420(_P010, y, uv, table, border_yuv, out, bounds)
+    return _warp_yuv(_P010, y, uv, table, border_yuv, out, bounds)
 
 
-# 4:2:2 -- what capture cards, SDI / HDMI grabbers and webcams deliver: the semi-planar NV16 pair and the two packed byte orders
+# the two packed byte orders of 4:2:2 (the semi-planar form is the NV16 pair)
 ORDERS_422 = {'yuyv': 0, 'uyvy': 1}
-_NV16 = _Format420(torch.uint8, 'an NV16', _nv12_border, _lib_.mf_warp_nv16, _lib_.mf_warp_bounds_nv16, None, None, None)
-
-
-def _need_nv16(y, uv):
-    """`_need_420` for an NV16 pair: only W must be even, and chroma has the luma's height; returns (n, H, W) of the luma stack."""
-    _need(y, torch.uint8, 'y')
-    if y.dim() != 3:
-        raise ValueError(f'y must be (n, H, W) luma planes, got shape {tuple(y.shape)}')
-    n, H, W = (int(v) for v in y.shape)
-    if W % 2:
-        raise ValueError(f'an NV16 frame has an even width, got W={W}')
-    _plane_420(uv, 'uv', (n, H, W // 2, 2), y.device, torch.uint8)
-    return n, H, W
 
 
 def _order_422(order):
@@ -621,21 +614,7 @@ def warp_nv16(y, uv, table, border_yuv=NV12_BORDER_RED, out=None, bounds=None):
     pixel, the result is (border_yuv[1], border_yuv[2]).  No sub-pixel correction for other chroma sitings is applied.
     border_yuv: (Y, U, V), each clamp(round(v), 0, 255); the default is `warp_nv12`'s.  out: an (out_y, out_uv) pair to fill.  Returns
     (out_y, out_uv).  (Not provided for 4:2:2: crop-resize, `stabilize_scored`, online sessions and groups, 10-bit samples.)"""
-    n, H, W = _need_nv16(y, uv)
-    if (n, W, H) != (table.n, table.W, table.H):
-        raise ValueError(f'y {tuple(y.shape)} does not match the cell table (n, H, W) = {(table.n, table.H, table.W)}')
-    if len(border_yuv) != 3:
-        raise ValueError(f'border_yuv must be (Y, U, V), got {border_yuv!r}')
-    out_y, out_uv = _out_420(_NV16, y, y.shape, uv.shape, out)
-    border = _NV16.border(border_yuv)
-    if bounds is None:
-        _lib.check(_NV16.warp(_ptr(y), _ptr(uv), _ptr(out_y), _ptr(out_uv), _ptr(table.buf), n, W, H, table.R, table.C, border, _ptr(table.crop),
-                              _stream()))
-    else:
-        _need_bounds(bounds)
-        _lib.check(_NV16.warp_bounds(_ptr(y), _ptr(uv), _ptr(out_y), _ptr(out_uv), _ptr(table.buf), n, W, H, table.R, table.C, border,
-                                     _ptr(table.crop), _ptr(bounds), _stream()))
-    return out_y, out_uv
+    return _warp_yuv(_NV16, y, uv, table, border_yuv, out, bounds)
 
 
 def unpack_422(packed, order='yuyv', out=None):
@@ -645,7 +624,7 @@ def unpack_422(packed, order='yuyv', out=None):
     2 bytes moved per byte of the clip."""
     n, H, W = _need_packed_422(packed)
     o = _order_422(order)
-    y, uv = _out_420(_NV16, packed, (n, H, W), (n, H, W // 2, 2), out)
+    y, uv = _out_yuv(_NV16, packed, (n, H, W), (n, H, W // 2, 2), out)
     _lib.check(_lib_.mf_unpack_422_u8(_ptr(packed), _ptr(y), _ptr(uv), n, W, H, o, _stream()))
     return y, uv
 
@@ -653,12 +632,12 @@ def unpack_422(packed, order='yuyv', out=None):
 def pack_422(y, uv, order='yuyv', out=None):
     """The inverse of `unpack_422` (mf_pack_422_u8): the NV16 pair y (n, H, W), uv (n, H, W/2, 2) as a packed (n, H, W, 2) uint8 clip of the
     given byte order.  out: the packed tensor to fill.  Returns it."""
-    n, H, W = _need_nv16(y, uv)
+    n, H, W = _need_yuv(_NV16, y, uv)
     o = _order_422(order)
     if out is None:
         out = torch.empty((n, H, W, 2), dtype=torch.uint8, device=y.device)
     else:
-        _plane_420(out, 'out', (n, H, W, 2), y.device, torch.uint8)
+        _plane_yuv(out, 'out', (n, H, W, 2), y.device, torch.uint8)
     if n < 1 or H < 1 or W < 2:
         raise ValueError(f'y is empty: shape {tuple(y.shape)}')
     _lib.check(_lib_.mf_pack_422_u8(_ptr(y), _ptr(uv), _ptr(out), n, W, H, o, _stream()))
@@ -674,7 +653,7 @@ def warp_packed_422(packed, table, order='yuyv', border_yuv=NV12_BORDER_RED, out
     n, H, W = _need_packed_422(packed)
     _order_422(order)
     if out is not None:
-        _plane_420(out, 'out', (n, H, W, 2), packed.device, torch.uint8)
+        _plane_yuv(out, 'out', (n, H, W, 2), packed.device, torch.uint8)
     if (n, W, H) != (table.n, table.W, table.H):
         raise ValueError(f'packed {tuple(packed.shape)} does not match the cell table (n, H, W) = {(table.n, table.H, table.W)}')
     if len(border_yuv) != 3:
@@ -696,10 +675,10 @@ def _even_output_size(size, name='size'):
 
 def _crop_resize_420(fmt, y, uv, bounds, size, out, status):
     """`crop_resize_nv12` / `crop_resize_p010`: the checks, then the format's C call for a host or a device rectangle."""
-    n, H, W = _need_420(fmt, y, uv)
+    n, H, W = _need_yuv(fmt, y, uv)
     oW, oH = (W, H) if size is None else _even_output_size(size)
     resident = _device_rectangle(bounds, status)
-    out_y, out_uv = _out_420(fmt, y, (n, oH, oW), (n, oH // 2, oW // 2, 2), out)
+    out_y, out_uv = _out_yuv(fmt, y, (n, oH, oW), (n, oH // 2, oW // 2, 2), out)
     if resident:
         status = _status_for(status, y.device)
     work = torch.empty(fmt.workspace_bytes(oW, oH), dtype=torch.uint8, device=y.device)

@@ -1107,8 +1107,9 @@ class MeshFlowStabilizer:
         cropped, _ = ops.crop_resize_planes(warped, bounds, interpolation, size=output_size, out=out)
         return cropped, bounds
 
-    def _stabilized_420(self, fmt, d_y, d_uv, d_disp, homographies, border_yuv, out, adaptive_weights_definition, crop, output_size):
-        """`stabilized_nv12`, `stabilized_p010` and `stabilized_p010_cropped` for the 4:2:0 format `fmt` (a row of ops.py): the argument checks,
+    def _stabilized_yuv(self, fmt, d_y, d_uv, d_disp, homographies, border_yuv, out, adaptive_weights_definition, crop, output_size):
+        """`stabilized_nv12`, `stabilized_p010`, `stabilized_p010_cropped` and `stabilized_nv16` for the semi-planar format `fmt` (a row of
+        ops.py): the argument checks -- the (d_y, d_uv) pair among them, so that a bad d_uv is a ValueError whatever the mesh is --,
         `_checked_table`, the warp and, with crop=True, the crop-resize of the warped temporaries from the rectangle on the device."""
         from . import ops
         if output_size is not None:
@@ -1117,15 +1118,12 @@ class MeshFlowStabilizer:
             ops._even_output_size(output_size, 'output_size')
         self._check_definition(adaptive_weights_definition)
         self._check_mesh_shape(d_disp, d_disp.shape[0])
-        ops._need(d_y, fmt.dtype, 'd_y')
-        if d_y.dim() != 3:
-            raise ValueError(f'd_y must be (F, H, W) luma planes, got shape {tuple(d_y.shape)}')
-        H, W = int(d_y.shape[1]), int(d_y.shape[2])
+        _, H, W = ops._need_yuv(fmt, d_y, d_uv, 'd_y', 'F')
         table, bounds = self._checked_table(d_disp, W, H, adaptive_weights_definition, homographies)
         if not crop:
-            out_y, out_uv = ops._warp_420(fmt, d_y, d_uv, table, border_yuv, out, bounds)
+            out_y, out_uv = ops._warp_yuv(fmt, d_y, d_uv, table, border_yuv, out, bounds)
             return out_y, out_uv, bounds
-        warped_y, warped_uv = ops._warp_420(fmt, d_y, d_uv, table, border_yuv, None, bounds)
+        warped_y, warped_uv = ops._warp_yuv(fmt, d_y, d_uv, table, border_yuv, None, bounds)
         out_y, out_uv, _ = ops._crop_resize_420(fmt, warped_y, warped_uv, bounds, output_size, out, None)
         return out_y, out_uv, bounds
 
@@ -1142,7 +1140,7 @@ class MeshFlowStabilizer:
         bottom}, the rectangle `stabilization_maps` returns for the same inputs.  A degenerate mesh raises `DegenerateMeshError`
         (clip_serial None) here, synchronously, before a plane is written."""
         from . import ops
-        return self._stabilized_420(ops._NV12, d_y, d_uv, d_disp, homographies, border_yuv, out, adaptive_weights_definition, crop, output_size)
+        return self._stabilized_yuv(ops._NV12, d_y, d_uv, d_disp, homographies, border_yuv, out, adaptive_weights_definition, crop, output_size)
 
     def stabilized_p010(self, d_y, d_uv, d_disp, homographies, border_yuv=(81 << 8, 90 << 8, 240 << 8), out=None,
                         adaptive_weights_definition=ADAPTIVE_WEIGHTS_DEFINITION_ORIGINAL, crop=False, output_size=None):
@@ -1159,7 +1157,7 @@ class MeshFlowStabilizer:
         if crop or output_size is not None:
             raise ValueError('crop-resize of 16-bit 4:2:0 clips is not built yet into stabilized_p010, which takes neither crop=True nor '
                              'output_size: call stabilized_p010_cropped')
-        return self._stabilized_420(ops._P010, d_y, d_uv, d_disp, homographies, border_yuv, out, adaptive_weights_definition, False, None)
+        return self._stabilized_yuv(ops._P010, d_y, d_uv, d_disp, homographies, border_yuv, out, adaptive_weights_definition, False, None)
 
     def stabilized_p010_cropped(self, d_y, d_uv, d_disp, homographies, border_yuv=(81 << 8, 90 << 8, 240 << 8), out=None,
                                 adaptive_weights_definition=ADAPTIVE_WEIGHTS_DEFINITION_ORIGINAL, output_size=None):
@@ -1171,7 +1169,7 @@ class MeshFlowStabilizer:
         tensor {left, top, right, bottom} `stabilized_p010` returns for the same inputs.  A degenerate mesh raises `DegenerateMeshError`
         (clip_serial None) here, synchronously, before a plane is written."""
         from . import ops
-        return self._stabilized_420(ops._P010, d_y, d_uv, d_disp, homographies, border_yuv, out, adaptive_weights_definition, True, output_size)
+        return self._stabilized_yuv(ops._P010, d_y, d_uv, d_disp, homographies, border_yuv, out, adaptive_weights_definition, True, output_size)
 
     def stabilized_nv16(self, d_y, d_uv, d_disp, homographies, border_yuv=(81, 90, 240), out=None,
                         adaptive_weights_definition=ADAPTIVE_WEIGHTS_DEFINITION_ORIGINAL):
@@ -1184,12 +1182,7 @@ class MeshFlowStabilizer:
         rectangle `stabilization_maps` returns for the same inputs.  A degenerate mesh raises `DegenerateMeshError` (clip_serial None) here,
         synchronously, before a plane is written."""
         from . import ops
-        self._check_definition(adaptive_weights_definition)
-        self._check_mesh_shape(d_disp, d_disp.shape[0])
-        _, H, W = ops._need_nv16(d_y, d_uv)
-        table, bounds = self._checked_table(d_disp, W, H, adaptive_weights_definition, homographies)
-        out_y, out_uv = ops.warp_nv16(d_y, d_uv, table, border_yuv, out, bounds)
-        return out_y, out_uv, bounds
+        return self._stabilized_yuv(ops._NV16, d_y, d_uv, d_disp, homographies, border_yuv, out, adaptive_weights_definition, False, None)
 
     def stabilized_packed_422(self, d_packed, d_disp, homographies, order='yuyv', border_yuv=(81, 90, 240), out=None,
                               adaptive_weights_definition=ADAPTIVE_WEIGHTS_DEFINITION_ORIGINAL):

@@ -132,7 +132,7 @@ def per_footprint_any(mask):
 def tail_fast_map(mx, my, W, H, plane):
     """Per footprint (F, ceil(H / 8), ceil(W / 32)): True where the tail takes its FAST form -- every emitting sample of the wavefront is deep
     interior by the tail's own test on its own plane.  plane 'luma' (remap_store_plane_f32, remap_store_u16c1): every pixel of the footprint
-    inside the frame emits, tested at (u, v) on (W, H).  plane 'chroma' (remap_store_nv12_uv, remap_store_p010_uv): the even pixels of the even
+    inside the frame emits, tested at (u, v) on (W, H).  plane 'chroma' (remap_store_chroma for NV12 and P010): the even pixels of the even
     rows emit, tested at (u / 2, v / 2) -- halved in float32 -- on (W / 2, H / 2); the other pixels' coordinates take no part."""
     if plane == 'luma':
         return per_footprint_all(deep_interior(mx, my, W, H))
