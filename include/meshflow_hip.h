@@ -347,6 +347,38 @@ int mf_warp_bounds_nv16(const uint8_t* d_y, const uint8_t* d_uv, uint8_t* d_out_
  * always are), any overlap of the three buffers. */
 int mf_unpack_422_u8(const uint8_t* d_packed, uint8_t* d_y, uint8_t* d_uv, int n, int W, int H, int order, void* stream);
 int mf_pack_422_u8(const uint8_t* d_y, const uint8_t* d_uv, uint8_t* d_packed, int n, int W, int H, int order, void* stream);
+/* _crop_frames (mfs.py:1111-1157) for an NV16 clip -- d_y [n][H][W], d_uv [n][H][W/2][2], U first, as mf_warp_nv16 takes them -- to d_out_y
+ * [n][out_H][out_W] and d_out_uv [n][out_H][out_W/2][2], without a conversion to BGR and without dropping chroma rows.  W and out_W are even,
+ * H and out_H of either parity, all four 2 .. 32,767; the rectangle is inclusive, in luma pixels, of any parity, usable under the rule of
+ * mf_crop_resize_u8c3.  DEFINED here, modelled on cv2.resize (OpenCV 4.5 - 4.10), not pinned (like mf_crop_resize_nv12's chroma).  A packed
+ * clip goes through mf_unpack_422_u8, this call, mf_pack_422_u8.
+ * Luma: d_out_y is byte for byte mf_crop_resize_to_u8c1 of d_y (mf_crop_resize_dev_u8c1 for the device rectangle) -- that very launch.
+ * Chroma, x axis: exactly mf_crop_resize_nv12's.  Output chroma sample cx sits on output luma pixel 2 cx, and its source is that pixel's luma
+ * source position, made absolute in the frame and halved.  With cw = right - left + 1, scale_x = 1.0 / ((double)out_W / (double)cw) (the luma
+ * tables' value), c1 = right >> 1 and c0 = min((left + 1) >> 1, c1) -- the chroma samples whose siting luma pixel lies inside the crop --:
+ *   fc = (float)(((double)left + (((double)(2 cx) + 0.5) * scale_x - 0.5)) * 0.5);  s = floor(fc);  f = fc - (float)s
+ *   s < c0 -> (s, f) = (c0, 0);  s >= c1 -> (c1, 0);  a0 = cvRound((1 - f) * 2048), a1 = cvRound(f * 2048)
+ * Chroma, y axis: chroma has luma's rows, so output chroma row y takes the LUMA table's own entry for row y: with ch = bottom - top + 1 and
+ * scale_y = 1.0 / ((double)out_H / (double)ch), fy = (float)(((double)y + 0.5) * scale_y - 0.5), sy = floor(fy), the rows are top + clip(sy, 0,
+ * ch - 1) and top + clip(sy + 1, 0, ch - 1), the weights b0 = cvRound((1 - (fy - sy)) * 2048), b1 = cvRound((fy - sy) * 2048), kept where a row was
+ * clipped.  No second y table, nothing halved.
+ * Then mf_crop_resize_u8c3's two passes per channel: t = S[s] a0 + S[s+1] a1, out = (((b0 (t0 >> 4)) >> 16) + ((b1 (t1 >> 4)) >> 16) + 2) >> 2.
+ * U and V never mix; no INTER_AREA special case (for 8-bit data it is this arithmetic).  Nothing outside chroma columns c0 .. c1 and rows
+ * top .. bottom of the frame's own chroma plane influences the result, and no byte outside the d_uv stack is read: where s == c1 only the 2-byte
+ * sample is read.  Consequences: the full-frame rectangle at out_W x out_H == W x H is a copy of d_uv; a rectangle with an even left at its own
+ * size is a copy of the sub-plane, for any top; where left is even and out_W == cw, the y axis is luma's byte for byte.
+ * d_work: mf_crop_resize_nv16_workspace_bytes(out_W, out_H) bytes (the luma tables, then out_W / 2 chroma x entries).  The luma launch goes
+ * first, then chroma, on the same stream.  mf_crop_resize_dev_nv16: the rectangle read from d_bounds when the kernels execute; one that cannot be
+ * used adds exactly 1 to *d_status (the luma tables kernel does, once) and leaves both outputs and the workspace untouched: the chroma kernels
+ * return before they read anything, the luma y table included (d_status as in mf_crop_resize_dev_u8c3).
+ * Refused with MF_ERR_INVALID_ARG before anything is launched: null pointers, n <= 0, any two of the four plane stacks overlapping, an odd W or
+ * out_W, a W, H, out_W or out_H outside 2 .. 32,767, a d_uv or d_out_uv that is not 2-byte aligned, too many tiles, and (host rectangle) an
+ * empty or out-of-frame rectangle.  An odd H or out_H is not refused. */
+size_t mf_crop_resize_nv16_workspace_bytes(int out_W, int out_H);
+int mf_crop_resize_nv16(const uint8_t* d_y, const uint8_t* d_uv, uint8_t* d_out_y, uint8_t* d_out_uv, int n, int W, int H, int left, int top,
+                        int right, int bottom, int out_W, int out_H, void* d_work, void* stream);
+int mf_crop_resize_dev_nv16(const uint8_t* d_y, const uint8_t* d_uv, uint8_t* d_out_y, uint8_t* d_out_uv, int n, int W, int H,
+                            const int32_t* d_bounds, int out_W, int out_H, void* d_work, int32_t* d_status, void* stream);
 
 /* Clip-level crop bounds (mfs.py:1103-1106): {max left, max top, min right, min bottom} over n frames.
  * d_bounds: [4] int32. */

@@ -92,6 +92,9 @@ SIGNATURES = {
     'mf_crop_resize_nv12_workspace_bytes': (_sz, [_i, _i]),
     'mf_crop_resize_nv12': (_i, [_vp, _vp, _vp, _vp] + [_i] * 9 + [_vp, _vp]),
     'mf_crop_resize_dev_nv12': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp]),
+    'mf_crop_resize_nv16_workspace_bytes': (_sz, [_i, _i]),
+    'mf_crop_resize_nv16': (_i, [_vp, _vp, _vp, _vp] + [_i] * 9 + [_vp, _vp]),
+    'mf_crop_resize_dev_nv16': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp]),
     'mf_crop_resize_p010_workspace_bytes': (_sz, [_i, _i]),
     'mf_crop_resize_p010': (_i, [_vp, _vp, _vp, _vp] + [_i] * 9 + [_vp, _vp]),
     'mf_crop_resize_dev_p010': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp]),

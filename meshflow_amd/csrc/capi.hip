@@ -182,11 +182,12 @@ static int crop_resize_dev_entry(const char* name, Px px, const void* d_frames, 
     return launch_crop_resize_dev(px, d_frames, d_out, n, W, H, d_bounds, out_W, out_H, d_work, d_status, (hipStream_t)stream);
 }
 
-// The checks of the four NV12 and P010 crop-resize entries -- all of them ahead of the first launch, under the call's own name `name` --, then
-// the format's launches on one stream.  NV12: the luma call as it is (launch_crop_resize_to / launch_crop_resize_dev on Px::U8C1) and the chroma
-// launches behind it.  P010: the luma tables, the luma kernel, the chroma tables and the chroma kernel (resize_hdr.hip / resize_hdr_dev.hip).
+// The checks of the six NV12, NV16 and P010 crop-resize entries -- all of them ahead of the first launch, under the call's own name `name` --,
+// then the format's launches on one stream.  NV12 and NV16: the luma call as it is (launch_crop_resize_to / launch_crop_resize_dev on Px::U8C1)
+// and the chroma launches behind it (NV16's on the luma call's own y table: chroma has luma's rows, so H and oH may be odd).  P010: the luma
+// tables, the luma kernel, the chroma tables and the chroma kernel (resize_hdr.hip / resize_hdr_dev.hip).
 // dev: an mf_crop_resize_dev_* call (the rectangle in d_bounds, left .. bottom unused).
-static int crop_resize_420_entry(const char* name, const FmtYuv& f, bool dev, const void* d_y, const void* d_uv, void* d_out_y, void* d_out_uv,
+static int crop_resize_yuv_entry(const char* name, const FmtYuv& f, bool dev, const void* d_y, const void* d_uv, void* d_out_y, void* d_out_uv,
                                  int n, int W, int H, int left, int top, int right, int bottom, const int32_t* d_bounds, int oW, int oH,
                                  void* d_work, int32_t* d_status, void* stream)
 {
@@ -200,8 +201,16 @@ static int crop_resize_420_entry(const char* name, const FmtYuv& f, bool dev, co
         set_error("%s: unsupported output size %dx%d (2 .. 32,767 each)", name, oW, oH);
         return MF_ERR_INVALID_ARG;
     }
-    if ((W | H) & 1) { set_error("%s: %s frame has an even W and H, got W=%d H=%d", name, f.noun, W, H); return MF_ERR_INVALID_ARG; }
-    if ((oW | oH) & 1) { set_error("%s: %s output has an even size, got %dx%d", name, f.noun, oW, oH); return MF_ERR_INVALID_ARG; }
+    if ((f.half_rows ? W | H : W) & 1) {
+        if (f.half_rows) set_error("%s: %s frame has an even W and H, got W=%d H=%d", name, f.noun, W, H);
+        else set_error("%s: %s frame has an even W, got W=%d", name, f.noun, W);
+        return MF_ERR_INVALID_ARG;
+    }
+    if ((f.half_rows ? oW | oH : oW) & 1) {
+        if (f.half_rows) set_error("%s: %s output has an even size, got %dx%d", name, f.noun, oW, oH);
+        else set_error("%s: %s output has an even width, got %dx%d", name, f.noun, oW, oH);
+        return MF_ERR_INVALID_ARG;
+    }
     if (!planes_yuv_ok(name, f, d_y, d_uv, d_out_y, d_out_uv, n, W, H, oW, oH)) return MF_ERR_INVALID_ARG;
     if (!dev && !resize_rect_ok(name, "", left, top, right, bottom, W, H)) return MF_ERR_INVALID_ARG;
     hipStream_t st = (hipStream_t)stream;
@@ -216,13 +225,21 @@ static int crop_resize_420_entry(const char* name, const FmtYuv& f, bool dev, co
     // the luma call's tiles at their smallest (the `down` instantiation's rows: the most tiles any of its paths counts), then chroma's
     TileOrder luma_order, order;
     if (!resize_tiles_ok(name, "", oW, oH, resize_to_tile_rows(Px::U8C1, false), n, luma_order)) return MF_ERR_INVALID_ARG;
-    if (!resize_uv_tile_order(oW, oH, n, order)) { set_error("%s: too many tiles", name); return MF_ERR_INVALID_ARG; }
+    if (!(f.half_rows ? resize_uv_tile_order(oW, oH, n, order) : resize_uv422_tile_order(oW, oH, n, order))) {
+        set_error("%s: too many tiles", name);
+        return MF_ERR_INVALID_ARG;
+    }
     void* const tabs = (char*)d_work + crop_resize_workspace_bytes(oW, oH);
+    const void* const luma_ytab = (const ResizeTab*)d_work + oW;      // (the luma call's y table: NV16 chroma rows are luma's)
     if (dev) {
         if (const int rc = launch_crop_resize_dev(Px::U8C1, d_y, d_out_y, n, W, H, d_bounds, oW, oH, d_work, d_status, st)) return rc;
+        if (!f.half_rows) return launch_resize_uv422_dev((const uint8_t*)d_uv, (uint8_t*)d_out_uv, W, H, d_bounds, oW, oH, luma_ytab, tabs, order, st);
         return launch_resize_uv_dev((const uint8_t*)d_uv, (uint8_t*)d_out_uv, W, H, d_bounds, oW, oH, tabs, order, st);
     }
     if (const int rc = launch_crop_resize_to(Px::U8C1, d_y, d_out_y, n, W, H, left, top, right, bottom, oW, oH, d_work, st)) return rc;
+    if (!f.half_rows) {
+        return launch_resize_uv422((const uint8_t*)d_uv, (uint8_t*)d_out_uv, W, H, left, top, right, bottom, oW, oH, luma_ytab, tabs, order, st);
+    }
     return launch_resize_uv((const uint8_t*)d_uv, (uint8_t*)d_out_uv, W, H, left, top, right, bottom, oW, oH, tabs, order, st);
 }
 
@@ -576,14 +593,33 @@ size_t mf_crop_resize_nv12_workspace_bytes(int out_W, int out_H)
 int mf_crop_resize_nv12(const uint8_t* d_y, const uint8_t* d_uv, uint8_t* d_out_y, uint8_t* d_out_uv, int n, int W, int H, int left, int top,
                         int right, int bottom, int out_W, int out_H, void* d_work, void* stream)
 {
-    return crop_resize_420_entry("mf_crop_resize_nv12", kNv12, false, d_y, d_uv, d_out_y, d_out_uv, n, W, H, left, top, right, bottom, nullptr, out_W,
+    return crop_resize_yuv_entry("mf_crop_resize_nv12", kNv12, false, d_y, d_uv, d_out_y, d_out_uv, n, W, H, left, top, right, bottom, nullptr, out_W,
                                  out_H, d_work, nullptr, stream);
 }
 
 int mf_crop_resize_dev_nv12(const uint8_t* d_y, const uint8_t* d_uv, uint8_t* d_out_y, uint8_t* d_out_uv, int n, int W, int H,
                             const int32_t* d_bounds, int out_W, int out_H, void* d_work, int32_t* d_status, void* stream)
 {
-    return crop_resize_420_entry("mf_crop_resize_dev_nv12", kNv12, true, d_y, d_uv, d_out_y, d_out_uv, n, W, H, 0, 0, 0, 0, d_bounds, out_W, out_H,
+    return crop_resize_yuv_entry("mf_crop_resize_dev_nv12", kNv12, true, d_y, d_uv, d_out_y, d_out_uv, n, W, H, 0, 0, 0, 0, d_bounds, out_W, out_H,
+                                 d_work, d_status, stream);
+}
+
+size_t mf_crop_resize_nv16_workspace_bytes(int out_W, int out_H)
+{
+    return (out_W > 0 && out_H > 0) ? crop_resize_nv16_workspace_bytes(out_W, out_H) : 0;
+}
+
+int mf_crop_resize_nv16(const uint8_t* d_y, const uint8_t* d_uv, uint8_t* d_out_y, uint8_t* d_out_uv, int n, int W, int H, int left, int top,
+                        int right, int bottom, int out_W, int out_H, void* d_work, void* stream)
+{
+    return crop_resize_yuv_entry("mf_crop_resize_nv16", kNv16, false, d_y, d_uv, d_out_y, d_out_uv, n, W, H, left, top, right, bottom, nullptr, out_W,
+                                 out_H, d_work, nullptr, stream);
+}
+
+int mf_crop_resize_dev_nv16(const uint8_t* d_y, const uint8_t* d_uv, uint8_t* d_out_y, uint8_t* d_out_uv, int n, int W, int H,
+                            const int32_t* d_bounds, int out_W, int out_H, void* d_work, int32_t* d_status, void* stream)
+{
+    return crop_resize_yuv_entry("mf_crop_resize_dev_nv16", kNv16, true, d_y, d_uv, d_out_y, d_out_uv, n, W, H, 0, 0, 0, 0, d_bounds, out_W, out_H,
                                  d_work, d_status, stream);
 }
 
@@ -595,14 +631,14 @@ size_t mf_crop_resize_p010_workspace_bytes(int out_W, int out_H)
 int mf_crop_resize_p010(const uint16_t* d_y, const uint16_t* d_uv, uint16_t* d_out_y, uint16_t* d_out_uv, int n, int W, int H, int left, int top,
                         int right, int bottom, int out_W, int out_H, void* d_work, void* stream)
 {
-    return crop_resize_420_entry("mf_crop_resize_p010", kP010, false, d_y, d_uv, d_out_y, d_out_uv, n, W, H, left, top, right, bottom, nullptr, out_W,
+    return crop_resize_yuv_entry("mf_crop_resize_p010", kP010, false, d_y, d_uv, d_out_y, d_out_uv, n, W, H, left, top, right, bottom, nullptr, out_W,
                                  out_H, d_work, nullptr, stream);
 }
 
 int mf_crop_resize_dev_p010(const uint16_t* d_y, const uint16_t* d_uv, uint16_t* d_out_y, uint16_t* d_out_uv, int n, int W, int H,
                             const int32_t* d_bounds, int out_W, int out_H, void* d_work, int32_t* d_status, void* stream)
 {
-    return crop_resize_420_entry("mf_crop_resize_dev_p010", kP010, true, d_y, d_uv, d_out_y, d_out_uv, n, W, H, 0, 0, 0, 0, d_bounds, out_W, out_H,
+    return crop_resize_yuv_entry("mf_crop_resize_dev_p010", kP010, true, d_y, d_uv, d_out_y, d_out_uv, n, W, H, 0, 0, 0, 0, d_bounds, out_W, out_H,
                                  d_work, d_status, stream);
 }
 

@@ -374,6 +374,14 @@ int launch_resize_uv(const uint8_t* uv, uint8_t* out_uv, int W, int H, int left,
                      const TileOrder& order, hipStream_t st);
 int launch_resize_uv_dev(const uint8_t* uv, uint8_t* out_uv, int W, int H, const int32_t* d_bounds, int oW, int oH, void* tabs,
                          const TileOrder& order, hipStream_t st);
+// resize_uv422.hip / resize_uv422_dev.hip: the chroma half of mf_crop_resize_nv16 / mf_crop_resize_dev_nv16, the same way -- resize_uv422_body.h's
+// x tables in `tabs` (behind the luma tables), then its kernel on them and on `luma_ytab`, the y table the luma call has just built (oH entries)
+size_t crop_resize_nv16_workspace_bytes(int oW, int oH);
+bool resize_uv422_tile_order(int oW, int oH, int n, TileOrder& order);
+int launch_resize_uv422(const uint8_t* uv, uint8_t* out_uv, int W, int H, int left, int top, int right, int bottom, int oW, int oH,
+                        const void* luma_ytab, void* tabs, const TileOrder& order, hipStream_t st);
+int launch_resize_uv422_dev(const uint8_t* uv, uint8_t* out_uv, int W, int H, const int32_t* d_bounds, int oW, int oH, const void* luma_ytab,
+                            void* tabs, const TileOrder& order, hipStream_t st);
 // resize16.hip / resize_dev.hip: resize16_tables_kernel's / resize16_tables_dev_kernel's tables for (oW, oH) in `work`, on their own
 int launch_resize16_tables(int cw, int ch, int oW, int oH, void* work, hipStream_t st);
 int launch_resize16_tables_dev(const int32_t* d_bounds, int W, int H, int oW, int oH, void* work, int32_t* d_status, hipStream_t st);

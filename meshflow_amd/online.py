@@ -33,7 +33,7 @@ OnlineReport = collections.namedtuple('OnlineReport', 'first d_unstab d_stab rec
 
 def margin_rectangle(crop_margin, W, H):
     """The fixed rectangle of a W x H frame: left = floor(m (W - 1)), right = (W - 1) - left, the same vertically; inclusive edges, any
-    parity (`ops.crop_resize_nv12` takes the rectangle in luma pixels of any parity, so a 4:2:0 pair needs no other)."""
+    parity (`ops.crop_resize_nv12` and `ops.crop_resize_nv16` take the rectangle in luma pixels of any parity, so a pair needs no other)."""
     left, top = math.floor(crop_margin * (W - 1)), math.floor(crop_margin * (H - 1))
     right, bottom = (W - 1) - left, (H - 1) - top
     if right - left + 1 < 2 or bottom - top + 1 < 2:
@@ -42,7 +42,7 @@ def margin_rectangle(crop_margin, W, H):
 
 
 class ClipForm(collections.namedtuple('ClipForm', 'fmt dtype shape')):
-    """The form of a clip, whatever its length: fmt, the `ops._FormatYuv` row of a 4:2:0 pair (d_y, d_uv) or None for a stack (n, ...);
+    """The form of a clip, whatever its length: fmt, the `ops._FormatYuv` row of a 4:2:0 or 4:2:2 pair (d_y, d_uv) or None for a stack (n, ...);
     the dtype; the shape of a frame -- of a luma plane for a pair.  Two clips of one form compare equal."""
     pair = property(lambda self: self.fmt is not None)
 
@@ -66,15 +66,27 @@ class ClipForm(collections.namedtuple('ClipForm', 'fmt dtype shape')):
         from . import ops
         if self.pair:
             out = ops._warp_yuv(self.fmt, *clip, table, ops.P010_BORDER_RED if self.fmt is ops._P010 else ops.NV12_BORDER_RED, None, None)
-            return out if crop is None else ops._crop_resize_420(self.fmt, out[0], out[1], crop[0], crop[1], None, None)
+            return out if crop is None else ops._crop_resize_yuv(self.fmt, out[0], out[1], crop[0], crop[1], None, None)
         out = ops.warp(clip, table, border_bgr)
         return out if crop is None else ops.crop_resize(out, crop[0], size=crop[1])
 
     def empty(self, w, h, device):
         """0 frames of this form at w x h."""
         import torch
-        shapes = ((h, w), (h // 2, w // 2, 2)) if self.pair else ((h, w) + self.shape[2:],)
+        shapes = ((h, w), (h // 2 if self.fmt.half_rows else h, w // 2, 2)) if self.pair else ((h, w) + self.shape[2:],)
         return self.clip([torch.empty((0,) + shape, dtype=self.dtype, device=device) for shape in shapes])
+
+
+def _is_nv16_pair(d_y, d_uv):
+    """Whether a pair is an NV16 clip: uint8 planes, d_y (n, H, W) and d_uv (n, H, W/2, 2) -- chroma with luma's rows.  (A 4:2:0 pair has
+    H/2 of them, and H >= 2, so no clip is both.)"""
+    import torch
+    if not (isinstance(d_y, torch.Tensor) and isinstance(d_uv, torch.Tensor) and d_y.dtype == d_uv.dtype == torch.uint8):
+        return False
+    if d_y.dim() != 3 or d_uv.dim() != 4:
+        return False
+    n, H, W = (int(v) for v in d_y.shape)
+    return W % 2 == 0 and H >= 1 and tuple(d_uv.shape) == (n, H, W // 2, 2)
 
 
 def luma_of(frames, red_first=False):
@@ -86,6 +98,8 @@ def luma_of(frames, red_first=False):
             raise ValueError('an NV12 or P010 clip is the pair (d_y, d_uv)')
         d_y, d_uv = frames
         fmt = {torch.uint16: ops._P010}.get(getattr(d_y, 'dtype', None), ops._NV12)         # (whatever is neither fails NV12's checks)
+        if fmt is ops._NV12 and _is_nv16_pair(d_y, d_uv):
+            fmt = ops._NV16
         ops._need_yuv(fmt, d_y, d_uv)
         return ClipForm(fmt, d_y.dtype, tuple(d_y.shape[1:])), (ops.luma(d_y) if fmt is ops._P010 else d_y)
     if isinstance(frames, torch.Tensor) and frames.dtype == torch.uint16 and frames.dim() == 3:
@@ -208,7 +222,8 @@ class OnlineSession:
         import torch
         from . import ops
         if self.output_size is not None:
-            self.output_size = (ops._even_output_size if form.pair else ops.check_output_size)(self.output_size, 'output_size')
+            self.output_size = (ops._yuv_output_size(form.fmt, self.output_size, 'output_size') if form.pair else
+                                ops.check_output_size(self.output_size, 'output_size'))
         rectangle = margin_rectangle(self.crop_margin, W, H)
         s = self.stabilizer
         self.state = ops.OnlineState((s.mesh_row_count + 1) * (s.mesh_col_count + 1) * 2, self.window, self.device)
@@ -228,7 +243,7 @@ class OnlineSession:
         across a cut is never tracked --; the parts' frames and reports come back joined (`join`): `first` is the first part's, d_unstab,
         d_stab and covered are concatenated, `lost` is concatenated in each part's own numbering.
         lag=k >= 1: what comes back is the frames that have become final with this push, session indices [emitted, seen - k): `first` is
-        the first of them (`emitted` where none came out -- the frames are then a 0-frame tensor, a pair for 4:2:0, of the output's dtype
+        the first of them (`emitted` where none came out -- the frames are then a 0-frame tensor, a pair for 4:2:0 and 4:2:2, of the output's dtype
         and trailing shape, and the report's tensors have 0 rows), d_unstab, d_stab and covered are theirs, `lost` stays that of the frames
         PUSHED.  The session keeps its own copies of the frames it still owes: the caller's buffers are free when push returns.  With
         on_cut='reset' the old shot is flushed before the `reset()` at each cut: its tail comes out of this push, in front of the new

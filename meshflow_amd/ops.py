@@ -487,8 +487,7 @@ _nv12_border = _border_samples(ctypes.c_uint8, 255, 3)
 _p010_border = _border_samples(ctypes.c_uint16, 65535, 3)
 _NV12 = _row_yuv('nv12', torch.uint8, 'an NV12', _nv12_border, True)
 _P010 = _row_yuv('p010', torch.uint16, 'a P010', _p010_border, True)  # P012 and P016 alike: plain 16-bit samples
-# (4:2:2 -- what capture cards, SDI / HDMI grabbers and webcams deliver; its crop-resize is not built)
-_NV16 = _FormatYuv(torch.uint8, 'an NV16', _nv12_border, False, _lib_.mf_warp_nv16, _lib_.mf_warp_bounds_nv16, None, None, None)
+_NV16 = _row_yuv('nv16', torch.uint8, 'an NV16', _nv12_border, False)  # 4:2:2 -- what capture cards, SDI / HDMI grabbers and webcams deliver
 
 
 def _plane_yuv(t, name, shape, device, dtype):
@@ -613,7 +612,7 @@ def warp_nv16(y, uv, table, border_yuv=NV12_BORDER_RED, out=None, bounds=None):
     plane like cv2.remap's 8-bit INTER_LINEAR with BORDER_CONSTANT; where the source lies outside the plane, and where no cell owns the luma
     pixel, the result is (border_yuv[1], border_yuv[2]).  No sub-pixel correction for other chroma sitings is applied.
     border_yuv: (Y, U, V), each clamp(round(v), 0, 255); the default is `warp_nv12`'s.  out: an (out_y, out_uv) pair to fill.  Returns
-    (out_y, out_uv).  (Not provided for 4:2:2: crop-resize, `stabilize_scored`, online sessions and groups, 10-bit samples.)"""
+    (out_y, out_uv).  The next step on the path is `crop_resize_nv16`.  (Not provided for 4:2:2: 10-bit samples.)"""
     return _warp_yuv(_NV16, y, uv, table, border_yuv, out, bounds)
 
 
@@ -673,12 +672,22 @@ def _even_output_size(size, name='size'):
     return oW, oH
 
 
-def _crop_resize_420(fmt, y, uv, bounds, size, out, status):
-    """`crop_resize_nv12` / `crop_resize_p010`: the checks, then the format's C call for a host or a device rectangle."""
+def _yuv_output_size(fmt, size, name='size'):
+    """`check_output_size` for an output of format `fmt`: an even width, and an even height too where chroma rows are halved."""
+    if fmt.half_rows:
+        return _even_output_size(size, name)
+    oW, oH = check_output_size(size, name)
+    if oW % 2:
+        raise ValueError(f'{fmt.noun} output has an even width, got {name}={(oW, oH)}')
+    return oW, oH
+
+
+def _crop_resize_yuv(fmt, y, uv, bounds, size, out, status):
+    """`crop_resize_nv12` / `crop_resize_p010` / `crop_resize_nv16`: the checks, then the format's C call for a host or a device rectangle."""
     n, H, W = _need_yuv(fmt, y, uv)
-    oW, oH = (W, H) if size is None else _even_output_size(size)
+    oW, oH = (W, H) if size is None else _yuv_output_size(fmt, size)
     resident = _device_rectangle(bounds, status)
-    out_y, out_uv = _out_yuv(fmt, y, (n, oH, oW), (n, oH // 2, oW // 2, 2), out)
+    out_y, out_uv = _out_yuv(fmt, y, (n, oH, oW), (n, oH // 2 if fmt.half_rows else oH, oW // 2, 2), out)
     if resident:
         status = _status_for(status, y.device)
     work = torch.empty(fmt.workspace_bytes(oW, oH), dtype=torch.uint8, device=y.device)
@@ -705,7 +714,7 @@ def crop_resize_nv12(y, uv, bounds, size=None, out=None, status=None):
     out: an (out_y, out_uv) pair to fill.  status (device rectangle only): as in `crop_resize_resident` -- an int32[1] device tensor, the
     caller's (it accumulates) or a new zeroed one, that an unusable rectangle adds exactly 1 to, leaving both outputs untouched.
     Returns (out_y, out_uv), or (out_y, out_uv, status) for a device rectangle."""
-    return _crop_resize_420(_NV12, y, uv, bounds, size, out, status)
+    return _crop_resize_yuv(_NV12, y, uv, bounds, size, out, status)
 
 
 def crop_resize_p010(y, uv, bounds, size=None, out=None, status=None):
@@ -722,7 +731,43 @@ def crop_resize_p010(y, uv, bounds, size=None, out=None, status=None):
     out: an (out_y, out_uv) pair to fill.  status (device rectangle only): as in `crop_resize_resident` -- an int32[1] device tensor, the
     caller's (it accumulates) or a new zeroed one, that an unusable rectangle adds exactly 1 to, leaving both outputs untouched.
     Returns (out_y, out_uv), or (out_y, out_uv, status) for a device rectangle."""
-    return _crop_resize_420(_P010, y, uv, bounds, size, out, status)
+    return _crop_resize_yuv(_P010, y, uv, bounds, size, out, status)
+
+
+def crop_resize_nv16(y, uv, bounds, size=None, out=None, status=None):
+    """`crop_resize_nv12` for an NV16 (4:2:2) clip (mfs.py:1111-1157 without a conversion to BGR and without dropping chroma rows;
+    mf_crop_resize_nv16 / mf_crop_resize_dev_nv16): crop to the inclusive {left, top, right, bottom} -- in luma pixels, of any parity -- and scale
+    to `size` = (width, height), the width even and the height of either parity, by default back to (W, H).  y, uv as in `warp_nv16`.  bounds: a
+    4-tuple the host knows, or an int32[4] DEVICE tensor (what `stabilized_nv16` returns) that the kernels read when they execute -- the host
+    never reads it and the call never waits; the bytes are the same.
+    Luma is byte for byte `crop_resize(y, bounds, size=size)` (`crop_resize_resident` for a device rectangle) -- that very launch.  Chroma, x
+    axis: `crop_resize_nv12`'s -- sited at the even luma sample, the luma source position of output luma pixel 2 cx made absolute in the frame
+    and halved, clamped to the chroma samples whose siting luma pixel lies inside the crop.  Chroma, y axis: chroma has luma's rows, so output
+    chroma row y takes the luma table's own rows and weights for row y.  cv2.resize's 8-bit INTER_LINEAR arithmetic per channel
+    (include/meshflow_hip.h has every expression).  The full frame at its own size is a copy, and so is an even-`left` rectangle at its own size.
+    out: an (out_y, out_uv) pair to fill, (n, height, width) and (n, height, width/2, 2).  status (device rectangle only): as in
+    `crop_resize_resident` -- an int32[1] device tensor, the caller's (it accumulates) or a new zeroed one, that an unusable rectangle adds
+    exactly 1 to, leaving both outputs untouched.
+    Returns (out_y, out_uv), or (out_y, out_uv, status) for a device rectangle."""
+    return _crop_resize_yuv(_NV16, y, uv, bounds, size, out, status)
+
+
+def crop_resize_packed_422(packed, bounds, order='yuyv', size=None, out=None, status=None):
+    """`crop_resize_nv16` for a packed 4:2:2 clip (YUY2 / UYVY), DEFINED as `unpack_422`, `crop_resize_nv16`, `pack_422`.  packed: (n, H, W, 2)
+    uint8; bounds, size and status as in `crop_resize_nv16`; out: the packed (n, height, width, 2) tensor to fill.  Temporary memory: the
+    unpacked pair and its resized twin, released on return.  (A kernel that crops the packed words directly is not built;
+    profiles/nv16_crop.md has the measurement that decides whether it is worth one.)
+    Returns the packed clip, or (packed clip, status) for a device rectangle."""
+    n, H, W = _need_packed_422(packed)
+    _order_422(order)
+    oW, oH = (W, H) if size is None else _yuv_output_size(_NV16, size)
+    if out is not None:
+        _plane_yuv(out, 'out', (n, oH, oW, 2), packed.device, torch.uint8)
+    _device_rectangle(bounds, status)
+    y, uv = unpack_422(packed, order)
+    res = crop_resize_nv16(y, uv, bounds, (oW, oH), None, status)
+    out = pack_422(res[0], res[1], order, out)
+    return out if len(res) == 2 else (out, res[2])
 
 
 def crop_resize_planes(planes, bounds, interpolation='linear', size=None, out=None, status=None):

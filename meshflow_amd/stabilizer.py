@@ -338,9 +338,11 @@ class MeshFlowStabilizer:
         """The reference's stabilize() between decoder and encoder (mfs.py:140-169) for a resident clip, without OpenCV: `clip` is an
         (F, H, W) uint8 grey tensor, (F, H, W, 3) uint8 or uint16 BGR frames, (F, H, W, 4) uint8 BGRA frames (red_first: RGB / RGBA), an NV12
         pair (d_y (F, H, W), d_uv (F, H/2, W/2, 2)) of uint8 or a P010 pair of the same shapes of uint16 -- the pair's dtype tells the two
-        apart.  In order: the clip's form and luma (`online.luma_of`: itself for grey and NV12, `ops.luma` otherwise);
-        `estimate_motion(luma, outliers='device', fit='device')`; `stabilize_resident(crop=True)` on the frames, `stabilized_nv12(crop=True)`
-        or `stabilized_p010_cropped` on the pair; the luma of the cropped clip in the same way; `cropping_and_distortion_resident(luma, cropped luma)`;
+        apart --, or an NV16 pair (d_y (F, H, W), d_uv (F, H, W/2, 2)) of uint8, which its d_uv's rows tell from NV12 (a packed 4:2:2 clip is
+        unpacked by the caller: `ops.unpack_422`).  In order: the clip's form and luma (`online.luma_of`: itself for grey, NV12 and NV16,
+        `ops.luma` otherwise);
+        `estimate_motion(luma, outliers='device', fit='device')`; `stabilize_resident(crop=True)` on the frames, `stabilized_nv12(crop=True)`,
+        `stabilized_p010_cropped` or `stabilized_nv16_cropped` on the pair; the luma of the cropped clip in the same way; `cropping_and_distortion_resident(luma, cropped luma)`;
         `_compute_stability_score_device` on the stabilized vertex paths.  Returns (the cropped clip in the input's form,
         (cropping_ratio, distortion_score, stability_score)) -- the reference's order, mfs.py:169; the first two np.float32, the third a
         float.  Every ValueError of those calls is this one's."""
@@ -352,6 +354,9 @@ class MeshFlowStabilizer:
             deep = form.fmt is ops._P010
             if deep:
                 out_y, out_uv, _ = self.stabilized_p010_cropped(d_y, d_uv, d_disp, homographies,
+                                                                adaptive_weights_definition=adaptive_weights_definition)
+            elif form.fmt is ops._NV16:
+                out_y, out_uv, _ = self.stabilized_nv16_cropped(d_y, d_uv, d_disp, homographies,
                                                                 adaptive_weights_definition=adaptive_weights_definition)
             else:
                 out_y, out_uv, _ = self.stabilized_nv12(d_y, d_uv, d_disp, homographies,
@@ -405,7 +410,7 @@ class MeshFlowStabilizer:
         tests/online_lag_model.py): on the model's 60-frame random walk five frames of latency halve the residual shake and shrink the
         correction by a quarter, and the gain saturates at about lag = temporal_smoothing_radius (profiles/online_lag.md; synthetic paths
         only, nobody has looked at footage).  `push` then returns the frames that have become final, session indices [emitted, seen - k) --
-        possibly none: a 0-frame tensor (a pair for 4:2:0) of the output's dtype and trailing shape, and a report with 0-row tensors --;
+        possibly none: a 0-frame tensor (a pair for 4:2:0 and 4:2:2) of the output's dtype and trailing shape, and a report with 0-row tensors --;
         the report's `first`, d_unstab, d_stab and covered are those frames', `lost` stays that of the frames pushed, and the number of
         frames out is d_stab.shape[0].  The session keeps the at most k frames it still owes on the device as clones, both planes of a
         4:2:0 pair, so the caller's buffers are free when push returns; `pending` says how many.  `flush()` ends the stream: it returns
@@ -423,7 +428,7 @@ class MeshFlowStabilizer:
     def online_group(self, streams, **keywords):
         """`streams` live streams of one frame size and form -- the cameras of one server -- stabilized together: an `online.OnlineGroup`
         whose `push(frames, streams=None)` takes ONE new frame of each of K distinct streams (a stack (K, ...) in any form a session
-        takes, a (d_y, d_uv) pair of (K, ...) stacks for 4:2:0; `streams` lists the K indices in any order and defaults to all) and
+        takes, a (d_y, d_uv) pair of (K, ...) stacks for 4:2:0 and NV16 (a packed 4:2:2 clip is no session form: callers unpack once per push); `streams` lists the K indices in any order and defaults to all) and
         returns (the K frames stabilized and cropped, [an `online.OnlineReport` per pushed stream]); row r and report r belong to
         streams[r].  The keywords are `online_session`'s and mean the same, except lag, which must be 0 (the held pixels and a flush per
         stream are not built), and on_lost, which must be 'hold' (one camera's lost pair must not stop the others; it is listed in that
@@ -1108,14 +1113,14 @@ class MeshFlowStabilizer:
         return cropped, bounds
 
     def _stabilized_yuv(self, fmt, d_y, d_uv, d_disp, homographies, border_yuv, out, adaptive_weights_definition, crop, output_size):
-        """`stabilized_nv12`, `stabilized_p010`, `stabilized_p010_cropped` and `stabilized_nv16` for the semi-planar format `fmt` (a row of
-        ops.py): the argument checks -- the (d_y, d_uv) pair among them, so that a bad d_uv is a ValueError whatever the mesh is --,
+        """`stabilized_nv12`, `stabilized_p010`, `stabilized_p010_cropped`, `stabilized_nv16` and `stabilized_nv16_cropped` for the semi-planar
+        format `fmt` (a row of ops.py): the argument checks -- the (d_y, d_uv) pair among them, so that a bad d_uv is a ValueError whatever the mesh is --,
         `_checked_table`, the warp and, with crop=True, the crop-resize of the warped temporaries from the rectangle on the device."""
         from . import ops
         if output_size is not None:
             if not crop:
                 raise ValueError('output_size belongs to crop=True')
-            ops._even_output_size(output_size, 'output_size')
+            ops._yuv_output_size(fmt, output_size, 'output_size')
         self._check_definition(adaptive_weights_definition)
         self._check_mesh_shape(d_disp, d_disp.shape[0])
         _, H, W = ops._need_yuv(fmt, d_y, d_uv, 'd_y', 'F')
@@ -1124,7 +1129,7 @@ class MeshFlowStabilizer:
             out_y, out_uv = ops._warp_yuv(fmt, d_y, d_uv, table, border_yuv, out, bounds)
             return out_y, out_uv, bounds
         warped_y, warped_uv = ops._warp_yuv(fmt, d_y, d_uv, table, border_yuv, None, bounds)
-        out_y, out_uv, _ = ops._crop_resize_420(fmt, warped_y, warped_uv, bounds, output_size, out, None)
+        out_y, out_uv, _ = ops._crop_resize_yuv(fmt, warped_y, warped_uv, bounds, output_size, out, None)
         return out_y, out_uv, bounds
 
     def stabilized_nv12(self, d_y, d_uv, d_disp, homographies, border_yuv=(81, 90, 240), out=None,
@@ -1177,7 +1182,7 @@ class MeshFlowStabilizer:
         uint8 interleaved chroma, U first, W even, H of either parity -- stabilized without ever becoming BGR and without dropping chroma rows:
         the Jacobi sweep (mfs.py:695-704) on d_disp, the cell table + plan of all F frames, then `ops.warp_nv16` (which has the definition),
         everything on torch's current stream.  d_disp and homographies come from `estimate_motion(d_y)`: the tracker takes the luma plane as it
-        is.  This call does not crop or scale (crop-resize of 4:2:2 clips is not built) and takes no `crop` or `output_size`.  out: an
+        is.  This call does not crop or scale and takes no `crop` or `output_size`: `stabilized_nv16_cropped` is the call that does.  out: an
         (out_y, out_uv) pair to fill.  Returns (out_y, out_uv, bounds): bounds = int32[4] device tensor {left, top, right, bottom}, the
         rectangle `stabilization_maps` returns for the same inputs.  A degenerate mesh raises `DegenerateMeshError` (clip_serial None) here,
         synchronously, before a plane is written."""
@@ -1189,7 +1194,8 @@ class MeshFlowStabilizer:
         """`stabilized_nv16` for a packed 4:2:2 clip -- d_packed (F, H, W, 2) uint8, order 'yuyv' (YUY2: bytes Y0 U Y1 V) or 'uyvy' (2vuy: U Y0
         V Y1), W even -- through `ops.warp_packed_422`: unpack, the NV16 warp, pack, with temporaries of twice the clip's size.  d_disp and
         homographies come from `estimate_motion` on the clip's luma plane, which for a packed clip is `ops.unpack_422(d_packed, order)[0]`.
-        No `crop` or `output_size`, as for `stabilized_nv16`.  out: the packed tensor to fill.  Returns (out_packed, bounds)."""
+        No `crop` or `output_size`, as for `stabilized_nv16`: `stabilized_packed_422_cropped` is the call that crops and scales.  out: the packed
+        tensor to fill.  Returns (out_packed, bounds)."""
         from . import ops
         self._check_definition(adaptive_weights_definition)
         self._check_mesh_shape(d_disp, d_disp.shape[0])
@@ -1197,6 +1203,35 @@ class MeshFlowStabilizer:
         ops._order_422(order)
         table, bounds = self._checked_table(d_disp, W, H, adaptive_weights_definition, homographies)
         return ops.warp_packed_422(d_packed, table, order, border_yuv, out, bounds), bounds
+
+    def stabilized_nv16_cropped(self, d_y, d_uv, d_disp, homographies, border_yuv=(81, 90, 240), out=None,
+                                adaptive_weights_definition=ADAPTIVE_WEIGHTS_DEFINITION_ORIGINAL, output_size=None):
+        """`stabilized_nv16` followed by the reference's last step, _crop_frames (mfs.py:1111-1157), without the clip ever becoming BGR: the
+        cell table + plan of all F frames, `ops.warp_nv16` into temporaries, then `ops.crop_resize_nv16` from the clip rectangle as the warp
+        left it on the device (the host never reads it), scaled to output_size = (width, height) -- the width even, the height of either
+        parity --, by default back to (W, H); everything on torch's current stream.  d_y, d_uv, d_disp, homographies and border_yuv as in
+        `stabilized_nv16`.  out: an (out_y, out_uv) pair of the OUTPUT's size to fill.  Returns (out_y, out_uv, bounds): the cropped pair and
+        the int32[4] device tensor {left, top, right, bottom} `stabilized_nv16` returns for the same inputs.  A degenerate mesh raises
+        `DegenerateMeshError` (clip_serial None) here, synchronously, before a plane is written."""
+        from . import ops
+        return self._stabilized_yuv(ops._NV16, d_y, d_uv, d_disp, homographies, border_yuv, out, adaptive_weights_definition, True, output_size)
+
+    def stabilized_packed_422_cropped(self, d_packed, d_disp, homographies, order='yuyv', border_yuv=(81, 90, 240), out=None,
+                                      adaptive_weights_definition=ADAPTIVE_WEIGHTS_DEFINITION_ORIGINAL, output_size=None):
+        """`stabilized_nv16_cropped` for a packed 4:2:2 clip (d_packed and order as in `stabilized_packed_422`): unpack, the NV16 warp, the
+        NV16 crop-resize from the rectangle on the device, pack -- the pair stays unpacked between the warp and the crop.  out: the packed
+        (F, height, width, 2) tensor of the OUTPUT's size to fill.  Returns (out_packed, bounds)."""
+        import torch
+        from . import ops
+        n, H, W = ops._need_packed_422(d_packed, 'd_packed')
+        ops._order_422(order)
+        oW, oH = (W, H) if output_size is None else ops._yuv_output_size(ops._NV16, output_size, 'output_size')
+        if out is not None:
+            ops._plane_yuv(out, 'out', (n, oH, oW, 2), d_packed.device, torch.uint8)
+        d_y, d_uv = ops.unpack_422(d_packed, order)
+        out_y, out_uv, bounds = self._stabilized_yuv(ops._NV16, d_y, d_uv, d_disp, homographies, border_yuv, None, adaptive_weights_definition, True,
+                                                     (oW, oH))
+        return ops.pack_422(out_y, out_uv, order, out), bounds
 
     def _stabilized_frames_device(self, d_frames, d_unstab, d_stab, out=None, table=None):
         """d_frames: (n, H, W, 3) uint8; d_unstab/d_stab: (n, R+1, C+1, 2) float64, all in HBM.
