@@ -330,7 +330,8 @@ int mf_warp_bounds_p010(const uint16_t* d_y, const uint16_t* d_uv, uint16_t* d_o
  * mf_warp_bounds_nv16: the rectangle in the caller's d_bounds[4], as mf_warp_bounds_u8c1.
  * Refused with MF_ERR_INVALID_ARG before anything is launched: null pointers, n <= 0, any two of the four planes overlapping (the chroma stacks
  * are n W H bytes), an odd W, W or H outside 2 .. 32,767, R or C outside 1 .. 64, a d_uv or d_out_uv that is not 2-byte aligned.
- * Not provided for 4:2:2: crop-resize, the clip pipelines (mf_clip_*), 10-bit samples (P210, v210). */
+ * 10-bit 4:2:2 is the P210 section below (mf_warp_p210, mf_crop_resize_p210, mf_unpack_y210_u16).  Not provided for 4:2:2: the clip pipelines
+ * (mf_clip_*), v210. */
 int mf_warp_nv16(const uint8_t* d_y, const uint8_t* d_uv, uint8_t* d_out_y, uint8_t* d_out_uv, const void* d_table, int n, int W, int H,
                  int R, int C, const uint8_t border_yuv[3], int32_t* d_crop, void* stream);
 int mf_warp_bounds_nv16(const uint8_t* d_y, const uint8_t* d_uv, uint8_t* d_out_y, uint8_t* d_out_uv, const void* d_table, int n, int W, int H,
@@ -378,6 +379,69 @@ size_t mf_crop_resize_nv16_workspace_bytes(int out_W, int out_H);
 int mf_crop_resize_nv16(const uint8_t* d_y, const uint8_t* d_uv, uint8_t* d_out_y, uint8_t* d_out_uv, int n, int W, int H, int left, int top,
                         int right, int bottom, int out_W, int out_H, void* d_work, void* stream);
 int mf_crop_resize_dev_nv16(const uint8_t* d_y, const uint8_t* d_uv, uint8_t* d_out_y, uint8_t* d_out_uv, int n, int W, int H,
+                            const int32_t* d_bounds, int out_W, int out_H, void* d_work, int32_t* d_status, void* stream);
+
+/* ---- P210 clips: 10-bit 4:2:2 -- what SDI / HDMI capture, ProRes and XAVC decoders and contribution feeds deliver -- in its semi-planar form:
+ * NV16's geometry with P010's samples.  A clip is two contiguous stacks: d_y [n][H][W] uint16 and d_uv [n][H][W/2][2] uint16, U first; W is
+ * even, H of either parity, both 2 .. 32,767.  Samples are plain 16-bit numbers, 0 .. 65535, nothing is masked: P210, P212 and P216 are the
+ * same bytes to these calls.  The packed form (Y210 / Y216) comes in and goes out through mf_unpack_y210_u16 / mf_pack_y210_u16 below.  Warped
+ * from ONE cell table with the arrays the reference hands to cv2.remap at mfs.py:1063-1069.
+ * Luma: d_out_y is bit for bit mf_warp_p010's luma (cv2.remap of CV_16UC1: channel 0 of mf_warp_u16c3 on stack(Y, Y, Y)) -- that very launch;
+ * the per-frame crop values in d_crop, the clip rectangle and the ownership are that call's.
+ * Chroma: sited at the even luma sample of the same row, as in mf_warp_nv16: output chroma sample (cx, y) of frame f takes the float32 map
+ * (u, v) of luma pixel (2 cx, y) -- what mf_warp_maps_f32 returns for it, (W + 1, H + 1) for a pixel no cell owns included --, halves u in
+ * float32 (uc = u * 0.5f: exact; vc = v as it is) and samples the (H, W/2) two-channel plane with mf_warp_p010's chroma arithmetic: cv2.remap's
+ * fixed-point coordinates (sx = cvRound(32 uc), ix = sat_short(sx >> 5), fx = sx & 31, the same in y) and CV_16U float weights per channel.  A
+ * 2 x 2 tap footprint wholly outside the plane -- an unowned pixel's, at ((W + 1) / 2, H + 1), among them -- gives (border_yuv[1],
+ * border_yuv[2]) itself; otherwise each outside tap is that border sample inside the sum.  U and V never mix.  The chroma launch follows the
+ * luma launch on the same stream; it reads nothing outside the plane's bytes and touches neither d_crop nor the rectangle.  All plane offsets
+ * are 64-bit.
+ * border_yuv: {Y, U, V} as given.  mf_warp_bounds_p210: the rectangle in the caller's d_bounds[4], as mf_warp_bounds_u8c1.
+ * Refused with MF_ERR_INVALID_ARG before anything is launched: null pointers, n <= 0, any two of the four planes overlapping (each stack is
+ * 2 n W H bytes), an odd W, W or H outside 2 .. 32,767, R or C outside 1 .. 64, a plane pointer that is not 2-byte aligned.  An odd H is not
+ * refused.
+ * Not provided: v210 (three 10-bit samples per 32-bit word), kernels that warp or crop the packed words directly, the host and clip pipelines
+ * (mf_*_host_frames, mf_clip_*). */
+int mf_warp_p210(const uint16_t* d_y, const uint16_t* d_uv, uint16_t* d_out_y, uint16_t* d_out_uv, const void* d_table, int n, int W, int H,
+                 int R, int C, const uint16_t border_yuv[3], int32_t* d_crop, void* stream);
+int mf_warp_bounds_p210(const uint16_t* d_y, const uint16_t* d_uv, uint16_t* d_out_y, uint16_t* d_out_uv, const void* d_table, int n, int W, int H,
+                        int R, int C, const uint16_t border_yuv[3], int32_t* d_crop, int32_t* d_bounds, void* stream);
+
+/* Packed Y210 / Y216 against the P210 pair.  d_packed [n][H][W][2] uint16 with W even is a flat stream of 8-byte words Y0 U Y1 V; word k covers
+ * luma pixels 2k and 2k + 1 of the flat [n][H][W] stream.  mf_unpack_y210_u16 writes y[2k] = Y0, y[2k + 1] = Y1, uv[2k] = U, uv[2k + 1] = V --
+ * exactly the P210 pair; mf_pack_y210_u16 is the inverse.  Samples move as bits (nothing masked or shifted); there is one sample order.  The
+ * warp of a packed clip is unpack, mf_warp_p210, pack.  One streaming kernel each: dwordx4 loads and 16-byte stores where the addresses allow
+ * them, narrower accesses where they do not -- no access is wider than its address's alignment; 64-bit indices, any clip length.
+ * Alignment contract: d_packed 8-byte aligned (a word is never split), d_y and d_uv 2-byte aligned.
+ * Refused with MF_ERR_INVALID_ARG before anything is launched: a null pointer, n < 1, W odd or outside 2 .. 32,767, H outside 1 .. 32,767, a
+ * d_packed that is not 8-byte aligned, a d_y or d_uv that is not 2-byte aligned, any overlap of the three buffers. */
+int mf_unpack_y210_u16(const uint16_t* d_packed, uint16_t* d_y, uint16_t* d_uv, int n, int W, int H, void* stream);
+int mf_pack_y210_u16(const uint16_t* d_y, const uint16_t* d_uv, uint16_t* d_packed, int n, int W, int H, void* stream);
+/* _crop_frames (mfs.py:1111-1157) for a P210 clip -- d_y [n][H][W], d_uv [n][H][W/2][2] uint16, U first, as mf_warp_p210 takes them -- to
+ * d_out_y [n][out_H][out_W] and d_out_uv [n][out_H][out_W/2][2].  W and out_W are even, H and out_H of either parity, all four 2 .. 32,767; the
+ * rectangle is inclusive, in luma pixels, of any parity.  DEFINED here, modelled on cv2.resize (OpenCV 4.5 - 4.10), not pinned.
+ * Luma: d_out_y is bit for bit mf_crop_resize_p010's luma -- that very launch: the float path of CV_16UC1, and INTER_AREA's
+ * (S00 + S01 + S10 + S11 + 2) >> 2 where 2 out_W == cw and 2 out_H == ch.
+ * Chroma, x axis: exactly mf_crop_resize_p010's (column s clamped into c0 .. c1, float32 fraction f, weights (1 - f, f) as they are).
+ * Chroma, y axis: chroma has luma's rows, so output chroma row y takes the LUMA table's own entry for row y: with ch = bottom - top + 1 and
+ * scale_y = 1.0 / ((double)out_H / (double)ch), fy = (float)(((double)y + 0.5) * scale_y - 0.5), sy = floor(fy), the rows are top + clip(sy, 0,
+ * ch - 1) and top + clip(sy + 1, 0, ch - 1) and the weights (1 - (fy - sy), fy - sy) in float32, kept where a row was clipped.  No second y
+ * table, nothing halved.  Then per channel t = float(S[s]) a0 + float(S[s+1]) a1, out = min(rint(t0 b0 + t1 b1), 65535), every product and sum
+ * rounded on its own.  U and V never mix.  Chroma has NO area branch: at exactly 2x down, where luma takes the box, chroma takes this float
+ * path on the luma table's entries.  Nothing outside chroma columns c0 .. c1 and rows top .. bottom influences the result, and no byte outside
+ * the d_uv stack is read (where s == c1 only that one 4-byte sample is loaded).  The full-frame rectangle at out_W x out_H == W x H is a copy
+ * of both planes.
+ * d_work: mf_crop_resize_p210_workspace_bytes(out_W, out_H) bytes (the luma tables, then out_W / 2 chroma x entries of 8 bytes).  The luma
+ * launch goes first, then chroma, on the same stream.  mf_crop_resize_dev_p210: the rectangle read from d_bounds when the kernels execute; one
+ * that cannot be used adds exactly 1 to *d_status (the luma tables kernel does, once) and leaves both outputs and the workspace untouched: the
+ * chroma kernels return before they read anything, the luma y table included.
+ * Refused with MF_ERR_INVALID_ARG before anything is launched: null pointers, n <= 0, any two of the four plane stacks overlapping, an odd W or
+ * out_W, a W, H, out_W or out_H outside 2 .. 32,767, a plane pointer that is not 2-byte aligned, too many tiles, and (host rectangle) an empty
+ * or out-of-frame rectangle.  An odd H or out_H is not refused. */
+size_t mf_crop_resize_p210_workspace_bytes(int out_W, int out_H);
+int mf_crop_resize_p210(const uint16_t* d_y, const uint16_t* d_uv, uint16_t* d_out_y, uint16_t* d_out_uv, int n, int W, int H, int left, int top,
+                        int right, int bottom, int out_W, int out_H, void* d_work, void* stream);
+int mf_crop_resize_dev_p210(const uint16_t* d_y, const uint16_t* d_uv, uint16_t* d_out_y, uint16_t* d_out_uv, int n, int W, int H,
                             const int32_t* d_bounds, int out_W, int out_H, void* d_work, int32_t* d_status, void* stream);
 
 /* Clip-level crop bounds (mfs.py:1103-1106): {max left, max top, min right, min bottom} over n frames.

@@ -87,6 +87,10 @@ SIGNATURES = {
     'mf_warp_bounds_p010': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     'mf_warp_nv16': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     'mf_warp_bounds_nv16': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    'mf_warp_p210': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    'mf_warp_bounds_p210': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    'mf_unpack_y210_u16': (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
+    'mf_pack_y210_u16': (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
     'mf_unpack_422_u8': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     'mf_pack_422_u8': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     'mf_crop_resize_nv12_workspace_bytes': (_sz, [_i, _i]),
@@ -98,6 +102,9 @@ SIGNATURES = {
     'mf_crop_resize_p010_workspace_bytes': (_sz, [_i, _i]),
     'mf_crop_resize_p010': (_i, [_vp, _vp, _vp, _vp] + [_i] * 9 + [_vp, _vp]),
     'mf_crop_resize_dev_p010': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp]),
+    'mf_crop_resize_p210_workspace_bytes': (_sz, [_i, _i]),
+    'mf_crop_resize_p210': (_i, [_vp, _vp, _vp, _vp] + [_i] * 9 + [_vp, _vp]),
+    'mf_crop_resize_dev_p210': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp]),
     'mf_track_workspace_bytes': (_sz, [_i] * 6),
     'mf_fast_corners_u8': (_i, [_vp] + [_i] * 7 + [_vp] * 5),
     'mf_lk_track_u8': (_i, [_vp, _vp] + [_i] * 6 + [_vp] * 6),

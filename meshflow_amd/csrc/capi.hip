@@ -58,7 +58,7 @@ static int warp_maps_entry(const char* name, const void* d_table, float* d_maps,
                        (hipStream_t)stream);
 }
 
-// A semi-planar YUV format -- a luma plane stack and an interleaved chroma one of half the width: NV12 and NV16 (uint8 samples), P010 (uint16)
+// A semi-planar YUV format -- a luma plane stack and an interleaved chroma one of half the width: NV12 and NV16 (uint8 samples), P010 and P210 (uint16)
 struct FmtYuv {
     int bytes;              // of a sample: 1 or 2
     const char* noun;       // with its article, for the messages
@@ -66,10 +66,10 @@ struct FmtYuv {
     bool half_rows;         // chroma has half the luma rows (4:2:0: H is even too); else as many (4:2:2: H of either parity)
 };
 constexpr FmtYuv kNv12 = { 1, "an NV12", Px::U8C1, Px::NV12_UV, true }, kP010 = { 2, "a P010", Px::U16C1, Px::P010_UV, true },
-                 kNv16 = { 1, "an NV16", Px::U8C1, Px::NV16_UV, false };
+                 kNv16 = { 1, "an NV16", Px::U8C1, Px::NV16_UV, false }, kP210 = { 2, "a P210", Px::U16C1, Px::P210_UV, false };
 
 // The plane stacks of a semi-planar call, n frames of W x H in and of oW x oH out: aligned to 2 bytes -- the chroma pair of an NV12 or NV16 clip,
-// all four of a P010 clip -- and no two of them share a byte
+// all four of a P010 or P210 clip -- and no two of them share a byte
 static bool planes_yuv_ok(const char* name, const FmtYuv& f, const void* d_y, const void* d_uv, const void* d_out_y, const void* d_out_uv, int n, int W,
                           int H, int oW, int oH)
 {
@@ -90,7 +90,7 @@ static bool planes_yuv_ok(const char* name, const FmtYuv& f, const void* d_y, co
     return true;
 }
 
-// The checks of the six NV12, NV16 and P010 warp entries, then the warp of the luma planes (launch_warp's f.luma launches: the grey warp, unchanged,
+// The checks of the eight NV12, NV16, P010 and P210 warp entries, then the warp of the luma planes (launch_warp's f.luma launches: the grey warp, unchanged,
 // for NV12 and NV16) and the chroma launches behind it on the same stream.  border_yuv: three samples of f.bytes each.  has_bounds: the clip-level
 // rectangle goes to the caller's d_bounds instead of the table's.
 static int warp_yuv_entry(const char* name, const FmtYuv& f, const void* d_y, const void* d_uv, void* d_out_y, void* d_out_uv, const void* d_table,
@@ -182,10 +182,11 @@ static int crop_resize_dev_entry(const char* name, Px px, const void* d_frames, 
     return launch_crop_resize_dev(px, d_frames, d_out, n, W, H, d_bounds, out_W, out_H, d_work, d_status, (hipStream_t)stream);
 }
 
-// The checks of the six NV12, NV16 and P010 crop-resize entries -- all of them ahead of the first launch, under the call's own name `name` --,
+// The checks of the eight NV12, NV16, P010 and P210 crop-resize entries -- all of them ahead of the first launch, under the call's own name `name` --,
 // then the format's launches on one stream.  NV12 and NV16: the luma call as it is (launch_crop_resize_to / launch_crop_resize_dev on Px::U8C1)
 // and the chroma launches behind it (NV16's on the luma call's own y table: chroma has luma's rows, so H and oH may be odd).  P010: the luma
-// tables, the luma kernel, the chroma tables and the chroma kernel (resize_hdr.hip / resize_hdr_dev.hip).
+// tables, the luma kernel, the chroma tables and the chroma kernel (resize_hdr.hip / resize_hdr_dev.hip); P210: the same luma launches, then the
+// chroma x table and the chroma kernel on the luma y table (the same two units).
 // dev: an mf_crop_resize_dev_* call (the rectangle in d_bounds, left .. bottom unused).
 static int crop_resize_yuv_entry(const char* name, const FmtYuv& f, bool dev, const void* d_y, const void* d_uv, void* d_out_y, void* d_out_uv,
                                  int n, int W, int H, int left, int top, int right, int bottom, const int32_t* d_bounds, int oW, int oH,
@@ -218,7 +219,14 @@ static int crop_resize_yuv_entry(const char* name, const FmtYuv& f, bool dev, co
         const uint16_t* const y = (const uint16_t*)d_y, * const uv = (const uint16_t*)d_uv;
         uint16_t* const out_y = (uint16_t*)d_out_y, * const out_uv = (uint16_t*)d_out_uv;
         TileOrder luma, chroma;
-        if (!resize_hdr_tile_orders(oW, oH, n, luma, chroma)) { set_error("%s: too many tiles", name); return MF_ERR_INVALID_ARG; }
+        if (!(f.half_rows ? resize_hdr_tile_orders(oW, oH, n, luma, chroma) : resize_p210_tile_orders(oW, oH, n, luma, chroma))) {
+            set_error("%s: too many tiles", name);
+            return MF_ERR_INVALID_ARG;
+        }
+        if (!f.half_rows) {
+            if (dev) return launch_resize_p210_dev(y, uv, out_y, out_uv, W, H, d_bounds, oW, oH, d_work, d_status, luma, chroma, st);
+            return launch_resize_p210(y, uv, out_y, out_uv, W, H, left, top, right, bottom, oW, oH, d_work, luma, chroma, st);
+        }
         if (dev) return launch_resize_hdr_dev(y, uv, out_y, out_uv, W, H, d_bounds, oW, oH, d_work, d_status, luma, chroma, st);
         return launch_resize_hdr(y, uv, out_y, out_uv, W, H, left, top, right, bottom, oW, oH, d_work, luma, chroma, st);
     }
@@ -440,6 +448,19 @@ int mf_warp_bounds_nv16(const uint8_t* d_y, const uint8_t* d_uv, uint8_t* d_out_
                           stream);
 }
 
+int mf_warp_p210(const uint16_t* d_y, const uint16_t* d_uv, uint16_t* d_out_y, uint16_t* d_out_uv, const void* d_table, int n, int W, int H,
+                 int R, int C, const uint16_t border_yuv[3], int32_t* d_crop, void* stream)
+{
+    return warp_yuv_entry("mf_warp_p210", kP210, d_y, d_uv, d_out_y, d_out_uv, d_table, n, W, H, R, C, border_yuv, d_crop, false, nullptr, stream);
+}
+
+int mf_warp_bounds_p210(const uint16_t* d_y, const uint16_t* d_uv, uint16_t* d_out_y, uint16_t* d_out_uv, const void* d_table, int n, int W, int H,
+                        int R, int C, const uint16_t border_yuv[3], int32_t* d_crop, int32_t* d_bounds, void* stream)
+{
+    return warp_yuv_entry("mf_warp_bounds_p210", kP210, d_y, d_uv, d_out_y, d_out_uv, d_table, n, W, H, R, C, border_yuv, d_crop, true, d_bounds,
+                          stream);
+}
+
 int mf_warp_p010(const uint16_t* d_y, const uint16_t* d_uv, uint16_t* d_out_y, uint16_t* d_out_uv, const void* d_table, int n, int W, int H,
                  int R, int C, const uint16_t border_yuv[3], int32_t* d_crop, void* stream)
 {
@@ -620,6 +641,25 @@ int mf_crop_resize_dev_nv16(const uint8_t* d_y, const uint8_t* d_uv, uint8_t* d_
                             const int32_t* d_bounds, int out_W, int out_H, void* d_work, int32_t* d_status, void* stream)
 {
     return crop_resize_yuv_entry("mf_crop_resize_dev_nv16", kNv16, true, d_y, d_uv, d_out_y, d_out_uv, n, W, H, 0, 0, 0, 0, d_bounds, out_W, out_H,
+                                 d_work, d_status, stream);
+}
+
+size_t mf_crop_resize_p210_workspace_bytes(int out_W, int out_H)
+{
+    return (out_W > 0 && out_H > 0) ? crop_resize_p210_workspace_bytes(out_W, out_H) : 0;
+}
+
+int mf_crop_resize_p210(const uint16_t* d_y, const uint16_t* d_uv, uint16_t* d_out_y, uint16_t* d_out_uv, int n, int W, int H, int left, int top,
+                        int right, int bottom, int out_W, int out_H, void* d_work, void* stream)
+{
+    return crop_resize_yuv_entry("mf_crop_resize_p210", kP210, false, d_y, d_uv, d_out_y, d_out_uv, n, W, H, left, top, right, bottom, nullptr, out_W,
+                                 out_H, d_work, nullptr, stream);
+}
+
+int mf_crop_resize_dev_p210(const uint16_t* d_y, const uint16_t* d_uv, uint16_t* d_out_y, uint16_t* d_out_uv, int n, int W, int H,
+                            const int32_t* d_bounds, int out_W, int out_H, void* d_work, int32_t* d_status, void* stream)
+{
+    return crop_resize_yuv_entry("mf_crop_resize_dev_p210", kP210, true, d_y, d_uv, d_out_y, d_out_uv, n, W, H, 0, 0, 0, 0, d_bounds, out_W, out_H,
                                  d_work, d_status, stream);
 }
 

@@ -245,14 +245,20 @@ inline bool make_tile_order(int tiles_x, int tiles_y, int n, TileOrder& o)
 // first -- Px::NV12_UV's geometry and lane mapping with Px::U16C3's arithmetic.
 // Px::NV16_UV: the interleaved half-WIDTH chroma plane of an NV16 (4:2:2) clip (mf_warp_nv16, warp_nv16.hip): [n][H][W/2] pixels of two bytes, U
 // first, sampled at (u / 2, v) of the even luma pixels of every row; H of either parity.  Luma: Px::U8C1.
-enum class Px { U8C3, U16C3, U8C1, U8C4, MAPS, PLANE_F32, PLANE_N1, PLANE_N2, PLANE_N4, PLANE_N8, NV12_UV, U16C1, P010_UV, NV16_UV };
+// Px::P210_UV: the interleaved half-WIDTH chroma plane of a P210 / P212 / P216 (10-bit 4:2:2) clip (mf_warp_p210, warp_p210.hip): [n][H][W/2]
+// pixels of two uint16 samples, U first -- Px::NV16_UV's geometry (every row emits, only x is halved, H of either parity) with Px::P010_UV's
+// arithmetic and border word.  Luma: Px::U16C1.
+enum class Px { U8C3, U16C3, U8C1, U8C4, MAPS, PLANE_F32, PLANE_N1, PLANE_N2, PLANE_N4, PLANE_N8, NV12_UV, U16C1, P010_UV, NV16_UV, P210_UV };
+// (the interleaved chroma plane of a semi-planar clip, and the ones with as many rows as luma)
+constexpr bool px_is_chroma(Px p) { return p == Px::NV12_UV || p == Px::P010_UV || p == Px::NV16_UV || p == Px::P210_UV; }
+constexpr bool px_is_chroma422(Px p) { return p == Px::NV16_UV || p == Px::P210_UV; }
 constexpr bool px_is_plane(Px p) { return p == Px::PLANE_F32 || p == Px::PLANE_N1 || p == Px::PLANE_N2 || p == Px::PLANE_N4 || p == Px::PLANE_N8; }
 constexpr int px_channels(Px p)
 {
-    return p == Px::U8C1 || p == Px::U16C1 || px_is_plane(p) ? 1 : p == Px::U8C4 ? 4 : p == Px::MAPS || p == Px::NV12_UV || p == Px::P010_UV || p == Px::NV16_UV ? 2 : 3;
+    return p == Px::U8C1 || p == Px::U16C1 || px_is_plane(p) ? 1 : p == Px::U8C4 ? 4 : p == Px::MAPS || px_is_chroma(p) ? 2 : 3;
 }
 // (the formats whose samples, and border samples, are uint16)
-constexpr bool px_is_u16(Px p) { return p == Px::U16C3 || p == Px::U16C1 || p == Px::P010_UV; }
+constexpr bool px_is_u16(Px p) { return p == Px::U16C3 || p == Px::U16C1 || p == Px::P010_UV || p == Px::P210_UV; }
 constexpr int px_sample_bytes(Px p)
 {
     return px_is_u16(p) || p == Px::PLANE_N2 ? 2 : p == Px::MAPS || p == Px::PLANE_F32 || p == Px::PLANE_N4 ? 4 : p == Px::PLANE_N8 ? 8 : 1;
@@ -261,19 +267,20 @@ constexpr int px_bytes(Px p) { return px_channels(p) * px_sample_bytes(p); }
 constexpr const char* px_name(Px p)
 {
     return p == Px::U8C3 ? "u8c3" : p == Px::U16C3 ? "u16c3" : p == Px::U8C1 ? "u8c1" : p == Px::U8C4 ? "u8c4" : p == Px::MAPS ? "maps_f32" :
-           p == Px::PLANE_F32 ? "plane_f32" : p == Px::NV12_UV ? "nv12_uv" : p == Px::U16C1 ? "u16c1" : p == Px::P010_UV ? "p010_uv" : p == Px::NV16_UV ? "nv16_uv" : "plane_nearest";
+           p == Px::PLANE_F32 ? "plane_f32" : p == Px::NV12_UV ? "nv12_uv" : p == Px::U16C1 ? "u16c1" : p == Px::P010_UV ? "p010_uv" : p == Px::NV16_UV ? "nv16_uv" : p == Px::P210_UV ? "p210_uv" : "plane_nearest";
 }
 // Bytes of one frame of a stack of format p in a clip of W x H (luma) pixels: launch_warp's frame stride.  A chroma plane has W / 2 pixels a row (W
-// even) and H / 2 rows (NV12, P010: H even) or H rows (NV16: H of either parity); everything else has W H pixels.
+// even) and H / 2 rows (NV12, P010: H even) or H rows (NV16, P210: H of either parity); everything else has W H pixels.
 constexpr size_t px_frame_bytes(Px p, int W, int H)
 {
-    const bool chroma = p == Px::NV12_UV || p == Px::P010_UV || p == Px::NV16_UV;
-    return (size_t)(chroma ? W / 2 : W) * (size_t)(chroma && p != Px::NV16_UV ? H / 2 : H) * (size_t)px_bytes(p);
+    const bool chroma = px_is_chroma(p);
+    return (size_t)(chroma ? W / 2 : W) * (size_t)(chroma && !px_is_chroma422(p) ? H / 2 : H) * (size_t)px_bytes(p);
 }
 static_assert(px_frame_bytes(Px::NV12_UV, 6, 4) == 12 && px_frame_bytes(Px::P010_UV, 6, 4) == 24, "4:2:0 chroma: (W / 2) (H / 2) pixels of 2 or 4 bytes");
 static_assert(px_frame_bytes(Px::NV16_UV, 6, 3) == 18 && px_frame_bytes(Px::U8C3, 6, 3) == 54, "4:2:2 chroma: (W / 2) H pixels of 2 bytes; a frame: W H pixels");
+static_assert(px_frame_bytes(Px::P210_UV, 6, 3) == 36 && px_frame_bytes(Px::U16C1, 6, 3) == 36, "10-bit 4:2:2: chroma (W / 2) H pixels of 4 bytes, as many bytes as luma");
 // The border colour as the warp kernels take it, from the caller's px_channels(p) samples: B | G << 8 | R << 16 (u8c3),
-// B | G << 16 | R << 32 (u16c3), the byte (u8c1), B | G << 8 | R << 16 | A << 24 (u8c4), U | V << 8 (nv12_uv, nv16_uv), the sample (u16c1), U | V << 16 (p010_uv).
+// B | G << 16 | R << 32 (u16c3), the byte (u8c1), B | G << 8 | R << 16 | A << 24 (u8c4), U | V << 8 (nv12_uv, nv16_uv), the sample (u16c1), U | V << 16 (p010_uv, p210_uv).
 inline uint64_t pack_border(Px p, const void* samples)
 {
     uint64_t v = 0;
@@ -318,6 +325,7 @@ void launch_nv12_chroma_range(const WarpGeom& g, const WarpRange& r, int W, int 
 void launch_nv16_chroma_range(const WarpGeom& g, const WarpRange& r, int W, int H, int C, uint32_t border_uv, hipStream_t st);  // warp_nv16.hip (r.crop, r.bounds unused)
 void launch_warp16c1_range(const WarpGeom& g, const WarpRange& r, int W, int H, int C, uint32_t border, hipStream_t st);  // warp_c1_16.hip
 void launch_p010_chroma_range(const WarpGeom& g, const WarpRange& r, int W, int H, int C, uint32_t border_uv, hipStream_t st);  // warp_p010.hip (r.crop, r.bounds unused)
+void launch_p210_chroma_range(const WarpGeom& g, const WarpRange& r, int W, int H, int C, uint32_t border_uv, hipStream_t st);  // warp_p210.hip (r.crop, r.bounds unused)
 int launch_crop_scan(const TableView& tv, int n, int W, int H, int R, int C, int32_t* crop, hipStream_t st);
 int check_d16_zero_fill(hipStream_t st);          // warp.hip: one-time device check the byte-tap kernels rely on
 int launch_selftest_recip(unsigned long long n, unsigned long long seed, unsigned long long* d_mismatches, hipStream_t st);
@@ -394,6 +402,14 @@ int launch_resize_hdr(const uint16_t* y, const uint16_t* uv, uint16_t* out_y, ui
                       int bottom, int oW, int oH, void* work, const TileOrder& luma, const TileOrder& chroma, hipStream_t st);
 int launch_resize_hdr_dev(const uint16_t* y, const uint16_t* uv, uint16_t* out_y, uint16_t* out_uv, int W, int H, const int32_t* d_bounds, int oW,
                           int oH, void* work, int32_t* d_status, const TileOrder& luma, const TileOrder& chroma, hipStream_t st);
+// ... and mf_crop_resize_p210 / mf_crop_resize_dev_p210 (10-bit 4:2:2) in the same two units: the same luma tables and luma kernel, then
+// resize_wide422_body.h's x table (oW/2 entries behind the luma tables) and its chroma kernel on the luma call's own y table
+size_t crop_resize_p210_workspace_bytes(int oW, int oH);
+bool resize_p210_tile_orders(int oW, int oH, int n, TileOrder& luma, TileOrder& chroma);
+int launch_resize_p210(const uint16_t* y, const uint16_t* uv, uint16_t* out_y, uint16_t* out_uv, int W, int H, int left, int top, int right,
+                       int bottom, int oW, int oH, void* work, const TileOrder& luma, const TileOrder& chroma, hipStream_t st);
+int launch_resize_p210_dev(const uint16_t* y, const uint16_t* uv, uint16_t* out_y, uint16_t* out_uv, int W, int H, const int32_t* d_bounds, int oW,
+                           int oH, void* work, int32_t* d_status, const TileOrder& luma, const TileOrder& chroma, hipStream_t st);
 size_t vertex_motion_workspace_bytes(int total_features, int max_per_pair, int P, int R, int C);
 int launch_vertex_motion(const double* early, const double* late, const int32_t* offsets, const double* hom, int P,
                          int total_features, int max_per_pair, int W, int H, int R, int C, int ell_rows, int ell_cols,

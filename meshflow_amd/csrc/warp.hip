@@ -322,7 +322,7 @@ int launch_warp(Px px, const void* frames, void* out, const TableView& tv, int n
     // staging reads dword-aligned 16-byte chunks: needs a 4-byte aligned clip (W % 4 == 0 is checked by the plan); the plan's windows
     // are re-cut for 1- and 4-byte pixels, not for 6-byte ones, so uint16 frames never stage
     const bool stage = px != Px::U16C3 && ((uintptr_t)frames & 3u) == 0;       // (the planes' kernels take no window either: unused there)
-    // (Px::MAPS: `frames` is null and stays unused, `out` holds 8 W H bytes per frame; Px::NV12_UV, Px::P010_UV, Px::NV16_UV: the chroma plane's own bytes)
+    // (Px::MAPS: `frames` is null and stays unused, `out` holds 8 W H bytes per frame; Px::NV12_UV, Px::P010_UV, Px::NV16_UV, Px::P210_UV: the chroma plane's own bytes)
     const size_t frame_bytes = px_frame_bytes(px, W, H);
     for (int f0 = 0; f0 < n; f0 += (int)per_launch) {
         const int m = n - f0 < (int)per_launch ? n - f0 : (int)per_launch;
@@ -346,6 +346,8 @@ int launch_warp(Px px, const void* frames, void* out, const TableView& tv, int n
             launch_warp16c1_range(g, r, W, H, C, (uint32_t)border, st);
         else if (px == Px::P010_UV)
             launch_p010_chroma_range(g, r, W, H, C, (uint32_t)border, st);
+        else if (px == Px::P210_UV)
+            launch_p210_chroma_range(g, r, W, H, C, (uint32_t)border, st);
         else if (px == Px::U16C3)
             hipLaunchKernelGGL(warp16_footprint, grid, dim3(64), 0, st, r.plan, r.regions, g, (const uint16_t*)r.frames, r.records, (uint16_t*)r.out,
                                r.edges, m, W, H, C, border, r.crop, r.bounds);
@@ -359,7 +361,7 @@ int launch_warp(Px px, const void* frames, void* out, const TableView& tv, int n
     return hip_fail(hipGetLastError(), px == Px::U8C3 ? "warp_kernel launch" : px == Px::U16C3 ? "warp16_footprint launch" :
                                        px == Px::U8C1 ? "warp8c1_footprint launch" : px == Px::U8C4 ? "warp8c4_footprint launch" : px == Px::MAPS ? "maps_footprint launch" :
                                        px == Px::NV12_UV ? "nv12_chroma_footprint launch" : px == Px::NV16_UV ? "nv16_chroma_footprint launch" : px == Px::U16C1 ? "warp16c1_footprint launch" :
-                                       px == Px::P010_UV ? "p010_chroma_footprint launch" : "plane_footprint launch");
+                                       px == Px::P010_UV ? "p010_chroma_footprint launch" : px == Px::P210_UV ? "p210_chroma_footprint launch" : "plane_footprint launch");
 }
 
 int launch_crop_scan(const TableView& tv, int n, int W, int H, int R, int C, int32_t* crop, hipStream_t st)

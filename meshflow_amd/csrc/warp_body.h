@@ -98,7 +98,7 @@ __device__ __forceinline__ void store_tail(const float (&u)[4], const float (&v)
                                            int32_t* __restrict__ crop, int32_t* __restrict__ clip, const GreyWindow& win, const uint8_t* s_win)
 {
     if constexpr (PX == Px::MAPS) maps_store_f32(u, v, f, x0, y, active, W, H, reinterpret_cast<float*>(out));
-    else if constexpr (PX == Px::NV12_UV || PX == Px::NV16_UV || PX == Px::P010_UV) remap_store_chroma<PX>(u, v, f, x0, y, active, W, H, frames, out, border);
+    else if constexpr (px_is_chroma(PX)) remap_store_chroma<PX>(u, v, f, x0, y, active, W, H, frames, out, border);
     else if constexpr (PX == Px::U16C1)
         remap_store_u16c1(u, v, f, x0, y, active, W, H, reinterpret_cast<const uint16_t*>(frames), reinterpret_cast<uint16_t*>(out), border, crop, clip);
     else if constexpr (px_is_plane(PX)) remap_store_plane<PX, SCAN>(u, v, f, x0, y, active, W, H, frames, out, border16, crop, clip);
@@ -149,6 +149,8 @@ __device__ __forceinline__ void store_bgr4(uint8_t* __restrict__ dst, int W, int
 // PX = Px::P010_UV: the chroma plane of a P010 clip (p010_chroma_footprint, warp_p010.hip): Px::NV12_UV on pixels of two uint16 samples --
 // (W / 2) (H / 2) pixels of four bytes per frame, the border is U | V << 16 in `border`, the pixels go through remap_store_chroma's
 // uint16 arithmetic.
+// PX = Px::P210_UV: the chroma plane of a P210 clip (p210_chroma_footprint, warp_p210.hip): Px::NV16_UV on pixels of two uint16 samples --
+// (W / 2) H pixels of four bytes per frame, H of either parity, the border is U | V << 16, remap_store_chroma's uint16 arithmetic on every row.
 template <Px PX, bool STAGE, bool SCAN>
 __device__ __forceinline__ void footprint_body(const uint32_t f, const uint32_t t, const FootPlan* __restrict__ plan, const FootRegion* __restrict__ regions,
                                                const WarpGeom& g, const uint8_t* __restrict__ frames,
@@ -167,8 +169,8 @@ __device__ __forceinline__ void footprint_body(const uint32_t f, const uint32_t 
     constexpr bool MAPS = PX == Px::MAPS;
     static_assert(!MAPS || (!STAGE && !SCAN), "the maps kernel reads no frame: nothing to stage");
     // NOWIN: the instantiations that take the hot and pair shortcuts without a window (the maps read no frame, the planes tap global memory)
-    constexpr bool PLANE = px_is_plane(PX), NV12 = PX == Px::NV12_UV, P010 = PX == Px::U16C1 || PX == Px::P010_UV, NV16 = PX == Px::NV16_UV;
-    constexpr bool NOWIN = MAPS || PLANE || NV12 || P010 || NV16;
+    constexpr bool PLANE = px_is_plane(PX), NV12 = PX == Px::NV12_UV, P010 = PX == Px::U16C1 || PX == Px::P010_UV, NV16 = px_is_chroma422(PX);
+    constexpr bool NOWIN = MAPS || PLANE || NV12 || P010 || NV16;       // (NV16: either 4:2:2 chroma plane, NV16_UV or P210_UV)
     static_assert(!(PLANE || NV12 || P010 || NV16) || (!STAGE && !SCAN), "the plane and chroma warps take their taps from global memory");
     // inverse homographies of the footprint's candidate cells: [entry][Hi0..Hi8, pad] (80-byte rows)
     __shared__ __attribute__((aligned(16))) double s_hi[1][9][10];                // row 8: the "no cell" matrix, see OWN_NONE

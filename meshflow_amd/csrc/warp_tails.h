@@ -1,6 +1,6 @@
 // The tails of footprint_body's other formats (device only, included through warp_body.h): the lane's four pixels at source coordinates
 // (u, v) -- taps, blend, crop flags, store -- for uint16 BGR, grey, 4-channel uint8, the coordinate maps, the side planes, the luma plane of a P010 clip
-// and the chroma plane of every semi-planar YUV clip (remap_store_chroma: NV12, NV16, P010).
+// and the chroma plane of every semi-planar YUV clip (remap_store_chroma: NV12, NV16, P010, P210).
 #ifndef MF_WARP_TAILS_H
 #define MF_WARP_TAILS_H
 #include "warp_coords.h"
@@ -609,7 +609,7 @@ __device__ __forceinline__ uint32_t blend_uv(uint32_t a, uint32_t b, uint32_t sx
     return __builtin_amdgcn_perm(udot2(vv, wq, 32768u), udot2(vu, wq, 32768u), 0x0C0C0602u);
 }
 
-// Footprint-level tail of the NV12_UV, NV16_UV and P010_UV instantiations of footprint_body.  The lane owns four consecutive LUMA pixels of
+// Footprint-level tail of the NV12_UV, NV16_UV, P010_UV and P210_UV instantiations of footprint_body.  The lane owns four consecutive LUMA pixels of
 // row y at coordinates (u, v) -- the maps kernel's, bit for bit -- and chroma is sited at the even luma sample: a lane that emits writes the
 // chroma samples x0 / 2 and x0 / 2 + 1 of its chroma row from its pixels 0 and 2.  A sample's source position is its luma pixel's, halved in
 // float32 (exact) along every axis the plane subsamples, then cv2.remap's 8-bit fixed point on the (Hc, Wc) plane of pixels of two samples T,
@@ -629,12 +629,15 @@ __device__ __forceinline__ uint32_t blend_uv(uint32_t a, uint32_t b, uint32_t sx
 // U | V << 16 and so is `border`; the pair goes through blend16x2 with the sample's four weights computed once, so U and V never mix.  Float
 // products of the border need not sum back to it, so a 2 x 2 footprint wholly outside the plane -- an unowned pixel's among them -- gives
 // `border` itself.  The deep-interior blend needs no clamp (rint(t) <= 65535 there, see remap_store_u16); the other saturates like blend16.
+// P210_UV (4:2:2, T = uint16): the product of the two rows above and no text of its own -- NV16_UV's geometry (Wc = W / 2, Hc = H of either
+// parity, every row's lanes emit into chroma row y, the position is (u / 2, v), an unowned pixel's ((W + 1) / 2, H + 1)) with P010_UV's
+// pixels, taps, border word, blend16x2 arithmetic and whole-footprint-outside rule.  The body takes no branch that one of those two does not.
 template <Px PX>
 __device__ __forceinline__ void remap_store_chroma(const float (&u)[4], const float (&v)[4], uint32_t f, int x0, int y, bool active, int W, int H,
                                                    const uint8_t* __restrict__ planes, uint8_t* __restrict__ out, uint32_t border)
 {
-    static_assert(PX == Px::NV12_UV || PX == Px::NV16_UV || PX == Px::P010_UV, "the semi-planar chroma planes");
-    constexpr bool HALF_ROWS = PX != Px::NV16_UV, U16 = PX == Px::P010_UV;
+    static_assert(px_is_chroma(PX), "the semi-planar chroma planes");
+    constexpr bool HALF_ROWS = PX == Px::NV12_UV || PX == Px::P010_UV, U16 = PX == Px::P010_UV || PX == Px::P210_UV;
     typedef typename PlaneElem<U16 ? 2 : 1>::type T;
     const int Wc = W >> 1, Hc = HALF_ROWS ? H >> 1 : H;
     const uint64_t plane_samples = 2ull * (uint64_t)((uint32_t)Wc * (uint32_t)Hc);

@@ -65,7 +65,7 @@ class ClipForm(collections.namedtuple('ClipForm', 'fmt dtype shape')):
         crop-resize to crop = (rectangle, output size or None)."""
         from . import ops
         if self.pair:
-            out = ops._warp_yuv(self.fmt, *clip, table, ops.P010_BORDER_RED if self.fmt is ops._P010 else ops.NV12_BORDER_RED, None, None)
+            out = ops._warp_yuv(self.fmt, *clip, table, ops.P010_BORDER_RED if self.fmt.border is ops._p010_border else ops.NV12_BORDER_RED, None, None)
             return out if crop is None else ops._crop_resize_yuv(self.fmt, out[0], out[1], crop[0], crop[1], None, None)
         out = ops.warp(clip, table, border_bgr)
         return out if crop is None else ops.crop_resize(out, crop[0], size=crop[1])
@@ -77,11 +77,11 @@ class ClipForm(collections.namedtuple('ClipForm', 'fmt dtype shape')):
         return self.clip([torch.empty((0,) + shape, dtype=self.dtype, device=device) for shape in shapes])
 
 
-def _is_nv16_pair(d_y, d_uv):
-    """Whether a pair is an NV16 clip: uint8 planes, d_y (n, H, W) and d_uv (n, H, W/2, 2) -- chroma with luma's rows.  (A 4:2:0 pair has
-    H/2 of them, and H >= 2, so no clip is both.)"""
+def _is_422_pair(d_y, d_uv, dtype):
+    """Whether a pair is a 4:2:2 clip of that dtype -- NV16 (uint8) or P210 (uint16): d_y (n, H, W) and d_uv (n, H, W/2, 2) -- chroma with
+    luma's rows.  (A 4:2:0 pair has H/2 of them, and H >= 2, so no clip is both.)"""
     import torch
-    if not (isinstance(d_y, torch.Tensor) and isinstance(d_uv, torch.Tensor) and d_y.dtype == d_uv.dtype == torch.uint8):
+    if not (isinstance(d_y, torch.Tensor) and isinstance(d_uv, torch.Tensor) and d_y.dtype == d_uv.dtype == dtype):
         return False
     if d_y.dim() != 3 or d_uv.dim() != 4:
         return False
@@ -90,7 +90,9 @@ def _is_nv16_pair(d_y, d_uv):
 
 
 def luma_of(frames, red_first=False):
-    """(form, luma (n, H, W) uint8) of a clip in any form `stabilize_scored` takes; form: its `ClipForm`."""
+    """(form, luma (n, H, W) uint8) of a clip in any form `stabilize_scored` takes; form: its `ClipForm`.  A pair's dtype tells NV12 / NV16
+    (uint8) from P010 / P210 (uint16), and its d_uv's rows 4:2:2 (as many as luma's) from 4:2:0 (half); a uint16 luma plane goes through
+    `ops.luma`."""
     import torch
     from . import ops
     if isinstance(frames, (tuple, list)):
@@ -98,10 +100,12 @@ def luma_of(frames, red_first=False):
             raise ValueError('an NV12 or P010 clip is the pair (d_y, d_uv)')
         d_y, d_uv = frames
         fmt = {torch.uint16: ops._P010}.get(getattr(d_y, 'dtype', None), ops._NV12)         # (whatever is neither fails NV12's checks)
-        if fmt is ops._NV12 and _is_nv16_pair(d_y, d_uv):
+        if fmt is ops._NV12 and _is_422_pair(d_y, d_uv, torch.uint8):
             fmt = ops._NV16
+        elif fmt is ops._P010 and _is_422_pair(d_y, d_uv, torch.uint16):
+            fmt = ops._P210
         ops._need_yuv(fmt, d_y, d_uv)
-        return ClipForm(fmt, d_y.dtype, tuple(d_y.shape[1:])), (ops.luma(d_y) if fmt is ops._P010 else d_y)
+        return ClipForm(fmt, d_y.dtype, tuple(d_y.shape[1:])), (ops.luma(d_y) if fmt.dtype == torch.uint16 else d_y)
     if isinstance(frames, torch.Tensor) and frames.dtype == torch.uint16 and frames.dim() == 3:
         raise ValueError('a (n, H, W) uint16 stack is the luma plane of a P010 clip: pass the pair (d_y, d_uv)')
     ops._frames_format(frames)

@@ -488,6 +488,7 @@ _p010_border = _border_samples(ctypes.c_uint16, 65535, 3)
 _NV12 = _row_yuv('nv12', torch.uint8, 'an NV12', _nv12_border, True)
 _P010 = _row_yuv('p010', torch.uint16, 'a P010', _p010_border, True)  # P012 and P016 alike: plain 16-bit samples
 _NV16 = _row_yuv('nv16', torch.uint8, 'an NV16', _nv12_border, False)  # 4:2:2 -- what capture cards, SDI / HDMI grabbers and webcams deliver
+_P210 = _row_yuv('p210', torch.uint16, 'a P210', _p010_border, False)  # 10-bit 4:2:2 (P212 and P216 alike) -- SDI / HDMI capture, ProRes, XAVC
 
 
 def _plane_yuv(t, name, shape, device, dtype):
@@ -528,7 +529,7 @@ def _out_yuv(fmt, y, y_shape, uv_shape, out):
 
 
 def _warp_yuv(fmt, y, uv, table, border_yuv, out, bounds):
-    """`warp_nv12` / `warp_p010` / `warp_nv16`: the checks, then the format's C call."""
+    """`warp_nv12` / `warp_p010` / `warp_nv16` / `warp_p210`: the checks, then the format's C call."""
     n, H, W = _need_yuv(fmt, y, uv)
     if (n, W, H) != (table.n, table.W, table.H):
         raise ValueError(f'y {tuple(y.shape)} does not match the cell table (n, H, W) = {(table.n, table.H, table.W)}')
@@ -612,7 +613,7 @@ def warp_nv16(y, uv, table, border_yuv=NV12_BORDER_RED, out=None, bounds=None):
     plane like cv2.remap's 8-bit INTER_LINEAR with BORDER_CONSTANT; where the source lies outside the plane, and where no cell owns the luma
     pixel, the result is (border_yuv[1], border_yuv[2]).  No sub-pixel correction for other chroma sitings is applied.
     border_yuv: (Y, U, V), each clamp(round(v), 0, 255); the default is `warp_nv12`'s.  out: an (out_y, out_uv) pair to fill.  Returns
-    (out_y, out_uv).  The next step on the path is `crop_resize_nv16`.  (Not provided for 4:2:2: 10-bit samples.)"""
+    (out_y, out_uv).  The next step on the path is `crop_resize_nv16`.  (10-bit 4:2:2 is `warp_p210`.)"""
     return _warp_yuv(_NV16, y, uv, table, border_yuv, out, bounds)
 
 
@@ -664,6 +665,79 @@ def warp_packed_422(packed, table, order='yuyv', border_yuv=NV12_BORDER_RED, out
     return pack_422(out_y, out_uv, order, out)
 
 
+def warp_p210(y, uv, table, border_yuv=P010_BORDER_RED, out=None, bounds=None):
+    """The mesh warp of a P210 clip -- 10-bit 4:2:2 in its semi-planar form, what SDI / HDMI capture and ProRes / XAVC decoders deliver (the
+    packed form, Y210 / Y216, goes through `warp_y210`) -- from one cell table, without truncating to 8 bits or converting to 3-channel uint16
+    (mf_warp_p210).  y: (n, H, W) uint16 luma, uv: (n, H, W/2, 2) uint16 interleaved chroma, U first; both contiguous device tensors, W even,
+    H of either parity, n == table.n.  Samples are plain 16-bit numbers, nothing is masked: P210, P212 and P216 alike.
+    Luma is bit for bit `warp_p010`'s luma -- that very launch: the per-frame crop values in table.crop and the clip-level rectangle in
+    `bounds` / table.clip_bounds are its.  Chroma is sited at the even luma sample of the same row, as in `warp_nv16`: output chroma sample
+    (cx, y) takes `warp_maps(table)[f, y, 2 cx]`, halves its x in float32, leaves its y as it is, and samples the (H, W/2) two-channel plane
+    with `warp_p010`'s CV_16U arithmetic per channel; where the 2 x 2 taps lie wholly outside the plane, and where no cell owns the luma
+    pixel, the result is (border_yuv[1], border_yuv[2]) itself.
+    border_yuv: (Y, U, V), each clamp(round(v), 0, 65535); the default is `warp_p010`'s.  out: an (out_y, out_uv) pair to fill.  Returns
+    (out_y, out_uv).  The next step on the path is `crop_resize_p210`.  (Not provided: v210 -- three 10-bit samples per 32-bit word --,
+    kernels that warp the packed words directly, the host and clip pipelines.)"""
+    return _warp_yuv(_P210, y, uv, table, border_yuv, out, bounds)
+
+
+def _need_y210(packed, name='packed'):
+    """A packed Y210 / Y216 clip: a contiguous (n, H, W, 2) uint16 device tensor with W even; returns (n, H, W)."""
+    _need(packed, torch.uint16, name)
+    if packed.dim() != 4 or packed.shape[3] != 2:
+        raise ValueError(f'{name} must be (n, H, W, 2) packed Y210 frames, got shape {tuple(packed.shape)}')
+    n, H, W = (int(v) for v in packed.shape[:3])
+    if W % 2:
+        raise ValueError(f'a packed Y210 frame has an even width, got W={W}')
+    if n < 1 or H < 1 or W < 2:
+        raise ValueError(f'{name} is empty: shape {tuple(packed.shape)}')
+    return n, H, W
+
+
+def unpack_y210(packed, out=None):
+    """A packed Y210 / Y216 clip as the P210 pair (mf_unpack_y210_u16).  packed: a contiguous (n, H, W, 2) uint16 device tensor, W even, its
+    storage 8-byte aligned -- a flat stream of 8-byte words Y0 U Y1 V.  Samples move as bits; nothing is masked or shifted.  Returns (y, uv):
+    (n, H, W) luma and (n, H, W/2, 2) chroma, U first -- what `warp_p210` takes.  out: a (y, uv) pair to fill.  One streaming kernel.  (v210 is
+    not this layout and is not provided.)"""
+    n, H, W = _need_y210(packed)
+    y, uv = _out_yuv(_P210, packed, (n, H, W), (n, H, W // 2, 2), out)
+    _lib.check(_lib_.mf_unpack_y210_u16(_ptr(packed), _ptr(y), _ptr(uv), n, W, H, _stream()))
+    return y, uv
+
+
+def pack_y210(y, uv, out=None):
+    """The inverse of `unpack_y210` (mf_pack_y210_u16): the P210 pair y (n, H, W), uv (n, H, W/2, 2) as a packed (n, H, W, 2) uint16 clip.
+    out: the packed tensor to fill (8-byte aligned).  Returns it."""
+    n, H, W = _need_yuv(_P210, y, uv)
+    if out is None:
+        out = torch.empty((n, H, W, 2), dtype=torch.uint16, device=y.device)
+    else:
+        _plane_yuv(out, 'out', (n, H, W, 2), y.device, torch.uint16)
+    if n < 1 or H < 1 or W < 2:
+        raise ValueError(f'y is empty: shape {tuple(y.shape)}')
+    _lib.check(_lib_.mf_pack_y210_u16(_ptr(y), _ptr(uv), _ptr(out), n, W, H, _stream()))
+    return out
+
+
+def warp_y210(packed, table, border_yuv=P010_BORDER_RED, out=None, bounds=None):
+    """The mesh warp of a packed Y210 / Y216 clip, DEFINED as `unpack_y210`, `warp_p210`, `pack_y210`.  packed: (n, H, W, 2) uint16,
+    n == table.n; out: the packed tensor to fill.  The crop values and the rectangle are `warp_p210`'s.  Temporary memory: the unpacked pair
+    and its warped twin, released on return.  (A tail that reads and writes the packed words directly is not built; profiles/p210.md.)
+    Returns the warped packed clip."""
+    n, H, W = _need_y210(packed)
+    if out is not None:
+        _plane_yuv(out, 'out', (n, H, W, 2), packed.device, torch.uint16)
+    if (n, W, H) != (table.n, table.W, table.H):
+        raise ValueError(f'packed {tuple(packed.shape)} does not match the cell table (n, H, W) = {(table.n, table.H, table.W)}')
+    if len(border_yuv) != 3:
+        raise ValueError(f'border_yuv must be (Y, U, V), got {border_yuv!r}')
+    if bounds is not None:
+        _need_bounds(bounds)
+    y, uv = unpack_y210(packed)
+    out_y, out_uv = warp_p210(y, uv, table, border_yuv, None, bounds)
+    return pack_y210(out_y, out_uv, out)
+
+
 def _even_output_size(size, name='size'):
     """`check_output_size` for an NV12 output: both numbers even as well (the smallest is 2 x 2)."""
     oW, oH = check_output_size(size, name)
@@ -683,7 +757,8 @@ def _yuv_output_size(fmt, size, name='size'):
 
 
 def _crop_resize_yuv(fmt, y, uv, bounds, size, out, status):
-    """`crop_resize_nv12` / `crop_resize_p010` / `crop_resize_nv16`: the checks, then the format's C call for a host or a device rectangle."""
+    """`crop_resize_nv12` / `crop_resize_p010` / `crop_resize_nv16` / `crop_resize_p210`: the checks, then the format's C call for a host or a
+    device rectangle."""
     n, H, W = _need_yuv(fmt, y, uv)
     oW, oH = (W, H) if size is None else _yuv_output_size(fmt, size)
     resident = _device_rectangle(bounds, status)
@@ -767,6 +842,37 @@ def crop_resize_packed_422(packed, bounds, order='yuyv', size=None, out=None, st
     y, uv = unpack_422(packed, order)
     res = crop_resize_nv16(y, uv, bounds, (oW, oH), None, status)
     out = pack_422(res[0], res[1], order, out)
+    return out if len(res) == 2 else (out, res[2])
+
+
+def crop_resize_p210(y, uv, bounds, size=None, out=None, status=None):
+    """`crop_resize_nv16` for a P210 (10-bit 4:2:2) clip (mf_crop_resize_p210 / mf_crop_resize_dev_p210): crop to the inclusive {left, top,
+    right, bottom} -- in luma pixels, of any parity -- and scale to `size` = (width, height), the width even and the height of either parity,
+    by default back to (W, H).  y, uv as in `warp_p210`: uint16, plain 16-bit numbers, nothing masked.  bounds: a 4-tuple the host knows, or an
+    int32[4] DEVICE tensor (what `stabilized_p210` returns) that the kernels read when they execute.
+    Luma is bit for bit `crop_resize_p010`'s luma -- that very launch: cv2.resize's float path on CV_16UC1, and INTER_AREA's box where the crop
+    is exactly twice the output in both axes.  Chroma, x axis: `crop_resize_p010`'s -- sited at the even luma sample, float32 weights (1 - f, f).
+    Chroma, y axis: chroma has luma's rows, so output chroma row y takes the luma table's own rows and fraction for row y.  The same float
+    arithmetic per channel; NO area branch for chroma, also at exactly 2x where luma takes the box (include/meshflow_hip.h has every
+    expression).  The full frame at its own size is a copy.
+    out: an (out_y, out_uv) pair to fill, (n, height, width) and (n, height, width/2, 2).  status (device rectangle only): as in
+    `crop_resize_resident`.  Returns (out_y, out_uv), or (out_y, out_uv, status) for a device rectangle."""
+    return _crop_resize_yuv(_P210, y, uv, bounds, size, out, status)
+
+
+def crop_resize_y210(packed, bounds, size=None, out=None, status=None):
+    """`crop_resize_p210` for a packed Y210 / Y216 clip, DEFINED as `unpack_y210`, `crop_resize_p210`, `pack_y210`.  packed: (n, H, W, 2)
+    uint16; bounds, size and status as in `crop_resize_p210`; out: the packed (n, height, width, 2) tensor to fill.  Temporary memory: the
+    unpacked pair and its resized twin, released on return.  (A kernel that crops the packed words directly is not built.)
+    Returns the packed clip, or (packed clip, status) for a device rectangle."""
+    n, H, W = _need_y210(packed)
+    oW, oH = (W, H) if size is None else _yuv_output_size(_P210, size)
+    if out is not None:
+        _plane_yuv(out, 'out', (n, oH, oW, 2), packed.device, torch.uint16)
+    _device_rectangle(bounds, status)
+    y, uv = unpack_y210(packed)
+    res = crop_resize_p210(y, uv, bounds, (oW, oH), None, status)
+    out = pack_y210(res[0], res[1], out)
     return out if len(res) == 2 else (out, res[2])
 
 

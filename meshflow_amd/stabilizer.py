@@ -338,22 +338,26 @@ class MeshFlowStabilizer:
         """The reference's stabilize() between decoder and encoder (mfs.py:140-169) for a resident clip, without OpenCV: `clip` is an
         (F, H, W) uint8 grey tensor, (F, H, W, 3) uint8 or uint16 BGR frames, (F, H, W, 4) uint8 BGRA frames (red_first: RGB / RGBA), an NV12
         pair (d_y (F, H, W), d_uv (F, H/2, W/2, 2)) of uint8 or a P010 pair of the same shapes of uint16 -- the pair's dtype tells the two
-        apart --, or an NV16 pair (d_y (F, H, W), d_uv (F, H, W/2, 2)) of uint8, which its d_uv's rows tell from NV12 (a packed 4:2:2 clip is
-        unpacked by the caller: `ops.unpack_422`).  In order: the clip's form and luma (`online.luma_of`: itself for grey, NV12 and NV16,
+        apart --, or an NV16 pair (d_y (F, H, W), d_uv (F, H, W/2, 2)) of uint8 or a P210 pair of the same shapes of uint16, which their d_uv's rows
+        tell from NV12 and P010 (a packed 4:2:2 clip is unpacked by the caller: `ops.unpack_422`, `ops.unpack_y210`).  In order: the clip's form and luma (`online.luma_of`: itself for grey, NV12 and NV16,
         `ops.luma` otherwise);
         `estimate_motion(luma, outliers='device', fit='device')`; `stabilize_resident(crop=True)` on the frames, `stabilized_nv12(crop=True)`,
-        `stabilized_p010_cropped` or `stabilized_nv16_cropped` on the pair; the luma of the cropped clip in the same way; `cropping_and_distortion_resident(luma, cropped luma)`;
+        `stabilized_p010_cropped`, `stabilized_nv16_cropped` or `stabilized_p210_cropped` on the pair; the luma of the cropped clip in the same way; `cropping_and_distortion_resident(luma, cropped luma)`;
         `_compute_stability_score_device` on the stabilized vertex paths.  Returns (the cropped clip in the input's form,
         (cropping_ratio, distortion_score, stability_score)) -- the reference's order, mfs.py:169; the first two np.float32, the third a
         float.  Every ValueError of those calls is this one's."""
+        import torch
         from . import online, ops
         form, luma = online.luma_of(clip, red_first)
         d_disp, homographies = self.estimate_motion(luma, chunk_pairs, max_per_subframe, outliers='device', fit='device')
         if form.pair:
             d_y, d_uv = clip
-            deep = form.fmt is ops._P010
-            if deep:
+            deep = form.dtype == torch.uint16                  # (P010, P210: the tracker's luma is `ops.luma` of the plane)
+            if form.fmt is ops._P010:
                 out_y, out_uv, _ = self.stabilized_p010_cropped(d_y, d_uv, d_disp, homographies,
+                                                                adaptive_weights_definition=adaptive_weights_definition)
+            elif form.fmt is ops._P210:
+                out_y, out_uv, _ = self.stabilized_p210_cropped(d_y, d_uv, d_disp, homographies,
                                                                 adaptive_weights_definition=adaptive_weights_definition)
             elif form.fmt is ops._NV16:
                 out_y, out_uv, _ = self.stabilized_nv16_cropped(d_y, d_uv, d_disp, homographies,
@@ -428,7 +432,7 @@ class MeshFlowStabilizer:
     def online_group(self, streams, **keywords):
         """`streams` live streams of one frame size and form -- the cameras of one server -- stabilized together: an `online.OnlineGroup`
         whose `push(frames, streams=None)` takes ONE new frame of each of K distinct streams (a stack (K, ...) in any form a session
-        takes, a (d_y, d_uv) pair of (K, ...) stacks for 4:2:0 and NV16 (a packed 4:2:2 clip is no session form: callers unpack once per push); `streams` lists the K indices in any order and defaults to all) and
+        takes, a (d_y, d_uv) pair of (K, ...) stacks for 4:2:0, NV16 and P210 (a packed 4:2:2 clip is no session form: callers unpack once per push); `streams` lists the K indices in any order and defaults to all) and
         returns (the K frames stabilized and cropped, [an `online.OnlineReport` per pushed stream]); row r and report r belong to
         streams[r].  The keywords are `online_session`'s and mean the same, except lag, which must be 0 (the held pixels and a flush per
         stream are not built), and on_lost, which must be 'hold' (one camera's lost pair must not stop the others; it is listed in that
@@ -1113,7 +1117,8 @@ class MeshFlowStabilizer:
         return cropped, bounds
 
     def _stabilized_yuv(self, fmt, d_y, d_uv, d_disp, homographies, border_yuv, out, adaptive_weights_definition, crop, output_size):
-        """`stabilized_nv12`, `stabilized_p010`, `stabilized_p010_cropped`, `stabilized_nv16` and `stabilized_nv16_cropped` for the semi-planar
+        """`stabilized_nv12`, `stabilized_p010`, `stabilized_p010_cropped`, `stabilized_nv16`, `stabilized_nv16_cropped`, `stabilized_p210` and
+        `stabilized_p210_cropped` for the semi-planar
         format `fmt` (a row of ops.py): the argument checks -- the (d_y, d_uv) pair among them, so that a bad d_uv is a ValueError whatever the mesh is --,
         `_checked_table`, the warp and, with crop=True, the crop-resize of the warped temporaries from the rectangle on the device."""
         from . import ops
@@ -1232,6 +1237,55 @@ class MeshFlowStabilizer:
         out_y, out_uv, bounds = self._stabilized_yuv(ops._NV16, d_y, d_uv, d_disp, homographies, border_yuv, None, adaptive_weights_definition, True,
                                                      (oW, oH))
         return ops.pack_422(out_y, out_uv, order, out), bounds
+
+    def stabilized_p210(self, d_y, d_uv, d_disp, homographies, border_yuv=(81 << 8, 90 << 8, 240 << 8), out=None,
+                        adaptive_weights_definition=ADAPTIVE_WEIGHTS_DEFINITION_ORIGINAL):
+        """`stabilized_nv16` for a P210 clip -- 10-bit 4:2:2 as SDI / HDMI capture and ProRes / XAVC decoders deliver it: d_y (F, H, W) uint16
+        luma, d_uv (F, H, W/2, 2) uint16 interleaved chroma, U first, W even, H of either parity, plain 16-bit samples (P212 and P216 alike) --
+        stabilized without truncating to 8 bits: the Jacobi sweep (mfs.py:695-704) on d_disp, the cell table + plan of all F frames, then
+        `ops.warp_p210` (which has the definition), everything on torch's current stream.  d_disp and homographies come from
+        `estimate_motion(ops.luma(d_y))`.  border_yuv: as in `stabilized_p010`.  This call does not crop or scale: `stabilized_p210_cropped`
+        does.  out: an (out_y, out_uv) pair to fill.  Returns (out_y, out_uv, bounds), as `stabilized_nv16`.  (Not provided: v210, kernels
+        on the packed words, the host and clip pipelines.)"""
+        from . import ops
+        return self._stabilized_yuv(ops._P210, d_y, d_uv, d_disp, homographies, border_yuv, out, adaptive_weights_definition, False, None)
+
+    def stabilized_p210_cropped(self, d_y, d_uv, d_disp, homographies, border_yuv=(81 << 8, 90 << 8, 240 << 8), out=None,
+                                adaptive_weights_definition=ADAPTIVE_WEIGHTS_DEFINITION_ORIGINAL, output_size=None):
+        """`stabilized_p210` followed by the reference's last step, _crop_frames (mfs.py:1111-1157): `ops.warp_p210` into temporaries, then
+        `ops.crop_resize_p210` from the clip rectangle as the warp left it on the device, scaled to output_size = (width, height) -- the width
+        even, the height of either parity --, by default back to (W, H).  out: an (out_y, out_uv) pair of the OUTPUT's size to fill.  Returns
+        (out_y, out_uv, bounds), as `stabilized_nv16_cropped`."""
+        from . import ops
+        return self._stabilized_yuv(ops._P210, d_y, d_uv, d_disp, homographies, border_yuv, out, adaptive_weights_definition, True, output_size)
+
+    def stabilized_y210(self, d_packed, d_disp, homographies, border_yuv=(81 << 8, 90 << 8, 240 << 8), out=None,
+                        adaptive_weights_definition=ADAPTIVE_WEIGHTS_DEFINITION_ORIGINAL):
+        """`stabilized_p210` for a packed Y210 / Y216 clip -- d_packed (F, H, W, 2) uint16, words Y0 U Y1 V, W even -- through `ops.warp_y210`:
+        unpack, the P210 warp, pack.  d_disp and homographies come from `estimate_motion` on `ops.luma(ops.unpack_y210(d_packed)[0])`.  out: the
+        packed tensor to fill.  Returns (out_packed, bounds)."""
+        from . import ops
+        self._check_definition(adaptive_weights_definition)
+        self._check_mesh_shape(d_disp, d_disp.shape[0])
+        _, H, W = ops._need_y210(d_packed, 'd_packed')
+        table, bounds = self._checked_table(d_disp, W, H, adaptive_weights_definition, homographies)
+        return ops.warp_y210(d_packed, table, border_yuv, out, bounds), bounds
+
+    def stabilized_y210_cropped(self, d_packed, d_disp, homographies, border_yuv=(81 << 8, 90 << 8, 240 << 8), out=None,
+                                adaptive_weights_definition=ADAPTIVE_WEIGHTS_DEFINITION_ORIGINAL, output_size=None):
+        """`stabilized_p210_cropped` for a packed Y210 / Y216 clip (d_packed as in `stabilized_y210`): unpack, the P210 warp, the P210
+        crop-resize from the rectangle on the device, pack -- the pair stays unpacked between the warp and the crop.  out: the packed
+        (F, height, width, 2) tensor of the OUTPUT's size to fill.  Returns (out_packed, bounds)."""
+        import torch
+        from . import ops
+        n, H, W = ops._need_y210(d_packed, 'd_packed')
+        oW, oH = (W, H) if output_size is None else ops._yuv_output_size(ops._P210, output_size, 'output_size')
+        if out is not None:
+            ops._plane_yuv(out, 'out', (n, oH, oW, 2), d_packed.device, torch.uint16)
+        d_y, d_uv = ops.unpack_y210(d_packed)
+        out_y, out_uv, bounds = self._stabilized_yuv(ops._P210, d_y, d_uv, d_disp, homographies, border_yuv, None, adaptive_weights_definition, True,
+                                                     (oW, oH))
+        return ops.pack_y210(out_y, out_uv, out), bounds
 
     def _stabilized_frames_device(self, d_frames, d_unstab, d_stab, out=None, table=None):
         """d_frames: (n, H, W, 3) uint8; d_unstab/d_stab: (n, R+1, C+1, 2) float64, all in HBM.
