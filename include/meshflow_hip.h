@@ -794,6 +794,39 @@ int mf_online_smooth_group_f64(const float* d_vel, const double* d_lam_known, co
                                int K, int B, int n, int S, int omega, int window, int iters, double beta, double lam_newest, double* d_c_state,
                                double* d_q_state, double* d_lam_state, double* d_c_out, double* d_p_out, void* stream);
 
+/* ---- online path smoothing of a group with a fixed lag: mf_online_smooth_lag_f64 per row ----
+ * mf_online_smooth_group_f64 with one more argument, `lag` in 0 .. window - 1, shared by the rows; row r is mf_online_smooth_lag_f64 on the
+ * slices mf_online_smooth_group_f64 names, bit for bit (tests/online_lag_model.py is the specification): row i of row r's outputs holds C and
+ * x of frame d_seen[r] + i - lag as they stand after window d_seen[r] + i's last sweep, 0.0 in both arrays where that frame does not exist.
+ * Of row r's n output rows the trailing max(0, d_seen[r] + n - lag) - max(0, d_seen[r] - lag) are frames, so rows of one call may differ in
+ * how many they hand out.  The state after a call does not depend on lag; the frames a stream still owes are the last min(lag, seen) rows of
+ * its slices of d_c_state / d_q_state.  lag = 0 gives mf_online_smooth_group_f64's bytes.
+ * The same two launches: the sweep on a grid (S, K) from the group kernel's lagged twin, then mf_online_smooth_group_f64's own weights launch.
+ * A row whose id is outside 0 .. B - 1 or whose d_seen[r] is negative touches no memory; distinct ids are the caller's duty.
+ * Limits (MF_ERR_INVALID_ARG, nothing launched): those of mf_online_smooth_group_f64, then lag outside 0 .. window - 1.
+ * Asynchronous on `stream`. */
+int mf_online_smooth_group_lag_f64(const float* d_vel, const double* d_lam_known, const double* d_taps, const int32_t* d_ids, const int64_t* d_seen,
+                                   int K, int B, int n, int S, int omega, int window, int lag, int iters, double beta, double lam_newest,
+                                   double* d_c_state, double* d_q_state, double* d_lam_state, double* d_c_out, double* d_p_out, void* stream);
+
+/* ---- the pixels a lagged group owes: store K new frames in a ring and hand out the frames whose slots they take, in one launch ----
+ * A specification of the project's own, bit for bit tests/ring_model.py (`exchange`).  d_ring [B][lag][N] bytes: frame t of stream b lives in
+ * slot t mod lag while it is owed.  d_new [K][N]: one new frame per row.  d_rows [K][3] int32 ON THE DEVICE: (id, slot, out_row) per row.
+ *   out_row >= 0   d_out[out_row] = d_ring[id][slot], then d_ring[id][slot] = d_new[r]
+ *   out_row <  0   d_ring[id][slot] = d_new[r] only
+ * d_out [K][N]: room for K frames, of which the first M <= K are written, M the number of rows that hand a frame out; the caller numbers
+ * them 0 .. M - 1 (the rows are on the device, so the library takes d_out as K frames long).  A row whose id is outside
+ * 0 .. B - 1, whose slot is outside 0 .. lag - 1 or whose out_row is K or more touches no memory.  The ids of one call must be DISTINCT: the
+ * caller's duty, as in mf_online_smooth_group_f64 (every access still lies inside the arrays).  Planes of 16-bit samples go through as bytes.
+ * One launch on a grid (ceil(N / 4096), K): each lane loads its 16 bytes of the ring and of the new frame, then stores both -- every ring
+ * byte is read by the lane that overwrites it, so there are no barriers and no atomics.  16-byte accesses where N is a multiple of 16 and
+ * d_ring, d_new and d_out are 16-byte aligned, byte accesses otherwise; nothing past a frame's last byte is read or written.
+ * Limits (MF_ERR_INVALID_ARG, nothing launched): K < 1, B < 1, lag < 1, N < 1, K > MF_ONLINE_GROUP_MAX_ROWS; N > MF_RING_MAX_FRAME_BYTES or
+ * B lag N above 2^62; a null pointer; d_rows not 4-byte aligned; d_out [K][N] overlapping d_ring or d_new; d_new overlapping d_ring.
+ * Asynchronous on `stream`. */
+#define MF_RING_MAX_FRAME_BYTES ((int64_t)4096 * 2147483647)
+int mf_ring_exchange_u8(uint8_t* d_ring, const uint8_t* d_new, uint8_t* d_out, const int32_t* d_rows, int K, int B, int lag, int64_t N, void* stream);
+
 /* ---- scene cuts: a per-frame signature of tile histograms of luma, and the distance of adjacent signatures ----
  * The reference has nothing of the kind; this is a specification of the project's own, bit for bit tests/cuts_model.py, integers only -- any
  * order of summation gives the same bytes.

@@ -19,6 +19,7 @@ HFIT_OK, HFIT_TOO_FEW, HFIT_COLLINEAR, HFIT_AT_INFINITY, HFIT_NOT_CONVERGED, HFI
 SCORES_MAX_PAIRS = 1 << 20
 ONLINE_MAX_WINDOW, ONLINE_MAX_OMEGA, ONLINE_MAX_ITERS = 64, 64, 1000
 ONLINE_GROUP_MAX_ROWS = 65535
+RING_MAX_FRAME_BYTES = 4096 * 2147483647
 CUT_COUNTERS, CUT_MAX_DIM = 256, 32767
 PATH_LIMIT_MAX_STEPS, PATH_LIMIT_MAX_BOUNDARY = 64, 1024
 CELL_OFF_M, CELL_OFF_HI, CELL_OFF_RECT, CELL_OFF_BBOX, CELL_OFF_STATUS = 0, 9, 18, 22, 26
@@ -123,7 +124,9 @@ SIGNATURES = {
     'mf_online_smooth_f64': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, ctypes.c_double, ctypes.c_double, ctypes.c_int64] + [_vp] * 6),
     'mf_online_smooth_lag_f64': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, ctypes.c_double, ctypes.c_double, ctypes.c_int64] + [_vp] * 6),
     'mf_online_smooth_group_f64': (_i, [_vp] * 5 + [_i] * 7 + [ctypes.c_double, ctypes.c_double] + [_vp] * 6),
-    'mf_frame_signature_u8': (_i, [_vp, _i, _i, _i, _vp, _vp]),
+    'mf_online_smooth_group_lag_f64': (_i, [_vp] * 5 + [_i] * 8 + [ctypes.c_double, ctypes.c_double] + [_vp] * 6),
+    'mf_ring_exchange_u8': (_i, [_vp] * 4 + [_i] * 3 + [ctypes.c_int64, _vp]),
+    'mf_frame_signature_u8':(_i, [_vp, _i, _i, _i, _vp, _vp]),
     'mf_cut_distance_i32': (_i, [_vp, _vp, _i, _vp, _vp]),
     'mf_cut_distance_pairs_i32': (_i, [_vp, _vp, _i, _vp, _vp]),
     'mf_path_limit_f64': (_i, [_vp, _vp] + [_i] * 9 + [ctypes.c_double, _i, _i] + [_vp] * 5),

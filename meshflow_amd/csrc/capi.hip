@@ -1013,6 +1013,22 @@ int mf_online_smooth_group_f64(const float* d_vel, const double* d_lam_known, co
                                       iters, beta, lam_newest, d_c_state, d_q_state, d_lam_state, d_c_out, d_p_out, (hipStream_t)stream);
 }
 
+int mf_online_smooth_group_lag_f64(const float* d_vel, const double* d_lam_known, const double* d_taps, const int32_t* d_ids, const int64_t* d_seen,
+                                   int K, int B, int n, int S, int omega, int window, int lag, int iters, double beta, double lam_newest,
+                                   double* d_c_state, double* d_q_state, double* d_lam_state, double* d_c_out, double* d_p_out, void* stream)
+{
+    const char* name = "mf_online_smooth_group_lag_f64";
+    const int rc = online_smooth_checks(name, d_vel, d_lam_known, d_taps, n, S, omega, window, iters, beta, lam_newest, 0, d_c_state, d_q_state,
+                                        d_lam_state, d_c_out, d_p_out, true, K, B, d_ids, d_seen);
+    if (rc != MF_OK) return rc;
+    if (lag < 0 || lag > window - 1) {
+        set_error("%s: lag must be in 0 .. window - 1 = %d (got %d)", name, window - 1, lag);
+        return MF_ERR_INVALID_ARG;
+    }
+    return launch_online_smooth_group_lag(d_vel, d_lam_known, d_taps, d_ids, reinterpret_cast<const long long*>(d_seen), K, B, n, S, omega, window,
+                                          lag, iters, beta, lam_newest, d_c_state, d_q_state, d_lam_state, d_c_out, d_p_out, (hipStream_t)stream);
+}
+
 int mf_frame_signature_u8(const uint8_t* d_luma, int n, int W, int H, int32_t* d_sig, void* stream)
 {
     const char* name = "mf_frame_signature_u8";

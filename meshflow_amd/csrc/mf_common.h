@@ -426,6 +426,10 @@ int launch_online_smooth_lag(const float* vel, const double* lam_known, const do
 int launch_online_smooth_group(const float* vel, const double* lam_known, const double* taps, const int32_t* ids, const long long* seen, int K,
                                int B, int n, int S, int omega, int L, int iters, double beta, double lam_newest, double* c_state, double* q_state,
                                double* lam_state, double* c_out, double* p_out, hipStream_t st);
+// ... and mf_online_smooth_group_lag_f64: the group's launches, the sweep kernel's lagged twin
+int launch_online_smooth_group_lag(const float* vel, const double* lam_known, const double* taps, const int32_t* ids, const long long* seen,
+                                   int K, int B, int n, int S, int omega, int L, int lag, int iters, double beta, double lam_newest,
+                                   double* c_state, double* q_state, double* lam_state, double* c_out, double* p_out, hipStream_t st);
 // cuts.hip: mf_frame_signature_u8, mf_cut_distance_i32 and mf_cut_distance_pairs_i32 behind capi.hip's checks
 int launch_frame_signature(const uint8_t* luma, int n, int W, int H, int32_t* sig, hipStream_t st);
 int launch_cut_distance(const int32_t* prev, const int32_t* sig, int n, int32_t* dist, hipStream_t st);

@@ -34,6 +34,7 @@
 // workgroup (s, r) sets up row r's slices -- its velocities, weights and outputs, its stream's three state slices, its stream's `seen` -- under
 // the names the body reads and then IS the plain kernel's text, so a row's bytes are those of the single call on those slices.  A row whose
 // stream id is outside 0 .. B - 1, or whose `seen` is negative, touches no memory.  The weights launch is one workgroup per row.
+// mf_online_smooth_group_lag_f64 is that prologue in front of the lagged text: the two group kernels differ as the two single ones do.
 #include "mf_common.h"
 
 namespace mf {
@@ -84,6 +85,31 @@ __global__ __launch_bounds__(64) void online_smooth_group_kernel(const float* __
     double* __restrict__ c_out = c_out_rows + r * block;
     double* __restrict__ p_out = p_out_rows + r * block;
 #define MF_ONLINE_LAG 0
+#include "online_smooth_body.h"
+#undef MF_ONLINE_LAG
+}
+
+// ... and the lagged kernel per row: the same prologue, the body's fourth inclusion (MF_ONLINE_LAG 1).  Row r hands out frame
+// seen_r + i - lag, so rows of one launch may differ in how many of their n outputs are real frames (the others are the body's zeros).
+__global__ __launch_bounds__(64) void online_smooth_group_lag_kernel(const float* __restrict__ vel_rows, const double* __restrict__ lam_known_rows,
+                                                                     const double* __restrict__ taps, const int32_t* __restrict__ ids,
+                                                                     const long long* __restrict__ seen_rows, int B, int n, int S, int omega, int L,
+                                                                     int iters, double beta, double lam_newest, int lag, double* c_stack,
+                                                                     double* q_stack, const double* __restrict__ lam_stack,
+                                                                     double* __restrict__ c_out_rows, double* __restrict__ p_out_rows)
+{
+    const size_t r = blockIdx.y, held = (size_t)(L - 1), block = (size_t)n * (size_t)S;
+    const int id = ids[r];
+    const long long seen = seen_rows[r];
+    if ((unsigned)id >= (unsigned)B || seen < 0) return;                     // (workgroup-uniform, before the first barrier)
+    const float* __restrict__ vel = vel_rows + r * block;
+    const double* __restrict__ lam_known = lam_known_rows + r * (size_t)n;
+    double* c_state = c_stack + (size_t)id * held * (size_t)S;
+    double* q_state = q_stack + (size_t)id * held * (size_t)S;
+    const double* __restrict__ lam_state = lam_stack + (size_t)id * held;
+    double* __restrict__ c_out = c_out_rows + r * block;
+    double* __restrict__ p_out = p_out_rows + r * block;
+#define MF_ONLINE_LAG 1
 #include "online_smooth_body.h"
 #undef MF_ONLINE_LAG
 }
@@ -161,6 +187,18 @@ int launch_online_smooth_group(const float* vel, const double* lam_known, const 
     static_assert(MF_ONLINE_GROUP_MAX_ROWS <= 65535, "a row per grid y");
     online_smooth_group_kernel<<<dim3((unsigned)S, (unsigned)K), 64, 0, st>>>(vel, lam_known, taps, ids, seen, B, n, S, omega, L, iters, beta,
                                                                                lam_newest, c_state, q_state, lam_state, c_out, p_out);
+    MF_HIP_TRY(hipGetLastError());
+    online_lam_state_group_kernel<<<dim3((unsigned)K), 64, 0, st>>>(lam_known, ids, seen, B, n, L, lam_newest, lam_state);
+    MF_HIP_TRY(hipGetLastError());
+    return MF_OK;
+}
+
+int launch_online_smooth_group_lag(const float* vel, const double* lam_known, const double* taps, const int32_t* ids, const long long* seen,
+                                   int K, int B, int n, int S, int omega, int L, int lag, int iters, double beta, double lam_newest,
+                                   double* c_state, double* q_state, double* lam_state, double* c_out, double* p_out, hipStream_t st)
+{
+    online_smooth_group_lag_kernel<<<dim3((unsigned)S, (unsigned)K), 64, 0, st>>>(vel, lam_known, taps, ids, seen, B, n, S, omega, L, iters, beta,
+                                                                                   lam_newest, lag, c_state, q_state, lam_state, c_out, p_out);
     MF_HIP_TRY(hipGetLastError());
     online_lam_state_group_kernel<<<dim3((unsigned)K), 64, 0, st>>>(lam_known, ids, seen, B, n, L, lam_newest, lam_state);
     MF_HIP_TRY(hipGetLastError());

@@ -2,7 +2,8 @@
 // a function, so that the plain kernel compiles to the instructions it had before the lagged one existed (an inlined template body did not:
 // tools/isa_compare.py, profiles/online_lag.md).  It reads the kernel's parameters by name: vel, lam_known, taps, n, S, omega, L, iters, beta,
 // lam_newest, seen, c_state, q_state, lam_state, c_out, p_out, and with MF_ONLINE_LAG also lag.  The group kernel includes it a third time
-// (MF_ONLINE_LAG 0) behind locals of those names bound to one row's slices; s is blockIdx.x there too, the row is blockIdx.y.
+// (MF_ONLINE_LAG 0) behind locals of those names bound to one row's slices; s is blockIdx.x there too, the row is blockIdx.y.  The lagged group
+// kernel is the fourth inclusion (MF_ONLINE_LAG 1) behind the same locals.
 // MF_ONLINE_LAG 0: row i of the outputs is the newest frame of window seen + i, written by its lane.  MF_ONLINE_LAG 1: row i is frame
 // seen + i - lag -- the lane whose age in window seen + i is `lag` writes its own C and x after the last sweep --, or 0.0 from the newest lane
 // while the session has fewer than lag + 1 frames.  Nothing else differs: the lag selects what is handed out and never enters the solve or

@@ -397,6 +397,11 @@ class OnlineSession:
         return out, OnlineReport(first, c.view(shape), p.view(shape), self.rectangle, covered, lost), k
 
 
+def _check_stream_count(streams):
+    if isinstance(streams, bool) or not isinstance(streams, (int, np.integer)) or int(streams) < 1:
+        raise ValueError(f'streams must be an int >= 1 (got {streams!r})')
+
+
 class OnlineGroup:
     """`streams` live streams of one size and form through `stabilizer`, a frame of each of any subset per `push`, in ONE set of launches
     whatever the subset's size.  Made by `MeshFlowStabilizer.online_group`, which documents the keywords.  What a stream gets is what an
@@ -409,11 +414,14 @@ class OnlineGroup:
     and `shots`."""
 
     def __init__(self, stabilizer, streams, **keywords):
-        if isinstance(streams, bool) or not isinstance(streams, (int, np.integer)) or int(streams) < 1:
-            raise ValueError(f'streams must be an int >= 1 (got {streams!r})')
+        _check_stream_count(streams)
         if keywords.get('lag', 0) != 0 or isinstance(keywords.get('lag', 0), bool):
-            raise ValueError(f"a group takes lag=0 only (got {keywords['lag']!r}): the pixels held per stream and a flush per stream are not "
-                             'built; use an online_session per stream for look-ahead')
+            raise ValueError(f"a group takes lag=0 only (got {keywords['lag']!r}): online_lag_group(streams, lag) is the group with "
+                             'look-ahead, the bytes of an online_session(lag=lag) per stream')
+        self._setup(stabilizer, streams, keywords)
+
+    def _setup(self, stabilizer, streams, keywords):
+        """What every group is made of, behind the checks of `streams` and `lag`."""
         if keywords.get('on_lost', 'hold') == 'raise':
             raise ValueError(f"a group takes on_lost='hold' only (got {keywords['on_lost']!r}): one stream's lost pair must not stop the "
                              "others; it is reported in that stream's report.lost")
@@ -449,6 +457,60 @@ class OnlineGroup:
         form a session takes, row r the frame of streams[r].  Returns (the K frames stabilized and cropped, in the input's form, a list of
         K `OnlineReport`): row r and report r belong to streams[r] and hold what that stream's own session would have returned for the
         frame.  A stream at its first frame, after `reset(stream)` or at a cut found is not tracked: it pushes a zero velocity at seen = 0."""
+        from . import ops
+        cfg, s = self.settings, self.stabilizer
+        ids, d_ids, form, luma, first, vel, lam_known, lost = self._front(frames, streams)
+        K, (H, W), R, C, S = len(ids), form.shape[:2], s.mesh_row_count, s.mesh_col_count, self.state.S
+        c, p = ops.online_smooth_group(vel, lam_known, self.state, ids, cfg._taps, cfg.omega, cfg.iters, cfg.beta, cfg._lam_newest)
+        c, p = c.view(K, S), p.view(K, S)
+        self._carry(ids, d_ids, luma, first)
+
+        k = None
+        if cfg.on_uncovered == 'limit':
+            p, k = ops.path_limit_group(c, p, W, H, R, C, cfg.rectangle, cfg.limit_steps, cfg.limit_guard, cfg.limit_rise, self._k_prev[d_ids])
+            self._k_prev[d_ids] = k
+        self.last_limit = k
+        out, covered = self._warp_rows(frames, c, p)
+        c, p = c.view(K, R + 1, C + 1, 2), p.view(K, R + 1, C + 1, 2)
+        return out, [OnlineReport(first[r], c[r:r + 1], p[r:r + 1], cfg.rectangle, covered[r:r + 1], lost[r]) for r in range(K)]
+
+    def _warp_rows(self, frames, c, p):
+        """Frames with their paths (n, S) through one cell table, the format's warp and the crop-resize: (frames out, covered (n,) bool)."""
+        from . import ops
+        cfg, s = self.settings, self.stabilizer
+        H, W = cfg.form.shape[:2]
+        table = ops.cell_table(c, p, W, H, s.mesh_row_count, s.mesh_col_count)
+        out = cfg.form.warp_crop(frames, table, s.color_outside_image_area_bgr, cfg._crop)
+        table.check()
+        crop = table.crop
+        left, top, right, bottom = cfg.rectangle
+        return out, (crop[:, 0] <= left) & (crop[:, 1] <= top) & (crop[:, 2] >= right) & (crop[:, 3] >= bottom)
+
+    def _carry(self, ids, d_ids, luma, first):
+        """Behind the smoother: every pushed stream's last luma frame, and the shots begun."""
+        self._last_luma[d_ids] = luma
+        for r, b in enumerate(ids):
+            self.shots[b] += int(first[r] == 0)
+
+    def _begin(self, form, H, W, frames):
+        """The first push: the frame size and form fix the settings and the per-stream state."""
+        import torch
+        from . import _lib, ops
+        cfg = self.settings
+        cfg._start(form, H, W)
+        self.state = ops.OnlineGroupState(self.streams, cfg.state.S, cfg.window, self.device)
+        self._last_luma = torch.empty((self.streams, H, W), dtype=torch.uint8, device=self.device)
+        self._last_sig = torch.zeros((self.streams, _lib.CUT_COUNTERS), dtype=torch.int32, device=self.device)
+        self._k_prev = torch.full((self.streams,), -1, dtype=torch.int32, device=self.device)
+
+    def _at_cut(self, row, stream):
+        """A cut found at `row`, the frame of `stream` (the pair across a cut is never tracked)."""
+        self.reset(stream)
+
+    def _front(self, frames, streams):
+        """A push up to the smoother, shared by the groups: the checks, luma, the cut decisions, the tracked pairs, `ops.vertex_motion` and
+        the one download.  Returns (ids, d_ids, form, luma, first -- each row's stream's `seen` --, vel (K, 1, S), lam_known (K, 1) on the
+        device, lost per row)."""
         import torch
         from . import _lib, ops
         cfg, s = self.settings, self.stabilizer
@@ -461,11 +523,7 @@ class OnlineGroup:
         if n != K:
             raise ValueError(f'push takes one frame per pushed stream: {K} streams, {n} frames')
         if cfg.form is None:
-            cfg._start(form, H, W)
-            self.state = ops.OnlineGroupState(self.streams, cfg.state.S, cfg.window, self.device)
-            self._last_luma = torch.empty((self.streams, H, W), dtype=torch.uint8, device=self.device)
-            self._last_sig = torch.zeros((self.streams, _lib.CUT_COUNTERS), dtype=torch.int32, device=self.device)
-            self._k_prev = torch.full((self.streams,), -1, dtype=torch.int32, device=self.device)
+            self._begin(form, H, W, frames)
         elif form != cfg.form:
             raise ValueError(f'this group takes {cfg.form.dtype} frames of shape {cfg.form.shape}{" as (d_y, d_uv) pairs" if cfg.form.pair else ""}; '
                              f'got {form.dtype} frames of shape {form.shape}{" as a pair" if form.pair else ""}')
@@ -480,8 +538,8 @@ class OnlineGroup:
             distances[np.array([seen[b] == 0 for b in ids])] = 0           # no frame before: nothing to be far from, never a cut
             cuts = [int(r) for r in np.nonzero(distances.astype(np.int64) > ops.cut_bound(cfg.cut_threshold, W, H))[0]]
             self._last_sig[d_ids] = sig
-            for r in cuts:                                                 # (the pair across a cut is never tracked)
-                self.reset(ids[r])
+            for r in cuts:
+                self._at_cut(r, ids[r])
         self.last_cuts, self.last_cut_distances = cuts, distances
 
         # the pairs (a stream's last luma -> its new frame) of the streams that have a frame before, through the tracker together
@@ -511,23 +569,171 @@ class OnlineGroup:
             else:
                 vel[d_rows] = d_vel
             lam_known[rows, 0] = host.adaptive_weights(len(homographies), W, H, cfg.definition, homographies)
-        c, p = ops.online_smooth_group(vel, torch.from_numpy(lam_known).to(self.device), self.state, ids, cfg._taps, cfg.omega, cfg.iters,
-                                       cfg.beta, cfg._lam_newest)
-        c, p = c.view(K, S), p.view(K, S)
-        self._last_luma[d_ids] = luma
-        for r, b in enumerate(ids):
-            self.shots[b] += int(first[r] == 0)
+        return ids, d_ids, form, luma, first, vel, torch.from_numpy(lam_known).to(self.device), lost
 
-        k = None
+
+class OnlineLagGroup(OnlineGroup):
+    """An `OnlineGroup` whose streams each have `lag` frames of look-ahead.  Made by `MeshFlowStabilizer.online_lag_group`, which documents
+    the contract: a stream gets the bytes of an `OnlineSession` of its own with lag=lag.  Everything up to the smoother is `OnlineGroup`'s
+    (`_front`); behind it the smoother is `ops.online_smooth_group_lag`, and the pixels a stream still owes live in a ring per plane of the
+    clip form, (streams, lag, ...) on the device -- frame t of a stream in slot t mod lag --, which one `ops.ring_exchange` per plane and
+    tick both fills and hands out from.  Memory: streams * lag frames per plane, allocated at the first push.  Beside `OnlineGroup`'s state
+    the group carries, on the host, `emitted` per stream (the frames handed out since its last reset) and whether the limiter carries a
+    step for it."""
+
+    def __init__(self, stabilizer, streams, lag, **keywords):
+        _check_stream_count(streams)
+        if not isinstance(lag, bool) and isinstance(lag, (int, np.integer)) and int(lag) == 0:
+            raise ValueError('a lagged group takes lag in 1 .. window - 1 (got 0): online_group(streams) is the group without look-ahead')
+        self._setup(stabilizer, streams, dict(keywords, lag=lag))         # (the session's own checks of window and lag)
+        self.lag = self.settings.lag
+        self.emitted, self._limited = [0] * self.streams, [False] * self.streams
+        self._rings = None                                                  # per plane (streams, lag, ...), made by the first push
+        self._tails = {}                                                    # of the push under way: row -> the old shot's tail at a cut
+        self.last_counts = []                                               # of the last push or flush: the frames of `out` per row
+
+    @property
+    def pending(self):
+        """The frames of each stream pushed but not handed out yet, at most `lag`: a list of `streams` ints."""
+        return [a - b for a, b in zip(self.seen, self.emitted)]
+
+    def reset(self, stream=None):
+        """`OnlineGroup.reset`; the pending frames of those streams are DISCARDED -- `flush(stream)` first hands them out.  No ring byte is
+        cleared: a stream at seen = 0 reads none of its slots."""
+        from . import ops
+        ids = list(range(self.streams)) if stream is None else ops.check_streams([stream], self.streams, 'stream')
+        super().reset(stream)
+        for b in ids:
+            self.emitted[b], self._limited[b] = 0, False
+
+    def _begin(self, form, H, W, frames):
+        import torch
+        planes = form.planes(frames)
+        size = sum(self.streams * self.lag * int(p[0].numel()) * p.element_size() for p in planes)
+        try:
+            rings = tuple(torch.empty((self.streams, self.lag) + tuple(p.shape[1:]), dtype=p.dtype, device=self.device) for p in planes)
+        except RuntimeError as e:                                           # (torch's out-of-memory error is one)
+            raise ValueError(f'a lagged group of {self.streams} streams at lag={self.lag} holds streams * lag frames on the device: '
+                             f'{size} bytes could not be allocated ({str(e).splitlines()[0]})') from None
+        super()._begin(form, H, W, frames)
+        self._rings = rings
+
+    def _at_cut(self, row, stream):
+        if self.pending[stream]:
+            self._tails[row] = self._tail(stream)                           # the old shot's tail, ahead of the new shot's frames
+        self.reset(stream)
+
+    def _nothing(self, stream, lost):
+        """What a row that hands out no frame reports: 0-row tensors, `first` the stream's `emitted`."""
+        import torch
+        s = self.stabilizer
+        path = torch.empty((0, s.mesh_row_count + 1, s.mesh_col_count + 1, 2), dtype=torch.float64, device=self.device)
+        return OnlineReport(self.emitted[stream], path, path.clone(), self.settings.rectangle,
+                            torch.empty(0, dtype=torch.bool, device=self.device), lost)
+
+    def _tail(self, stream):
+        """The pending frames of `stream` with `ops.online_pending_group`'s paths through the single-stream limiter, the cell table and the
+        warp -- `OnlineSession._flush_part` on the stream's slices, launches of its own --: (frames out, `OnlineReport`, k or None).  Leaves
+        the reset to the caller."""
+        import torch
+        from . import ops
+        cfg, s = self.settings, self.stabilizer
+        n, seen, first, k = self.pending[stream], self.state.seen[stream], self.emitted[stream], None
+        (c, p), = ops.online_pending_group(self.state, [stream], self.lag)
+        # oldest first: slots (seen - n) mod lag onwards, in one run or two around the ring's end (slices: torch indexes no uint16 tensor);
+        # the warp below reads them on this stream before the tick's exchange writes a slot
+        lo = (seen - n) % self.lag
+        wrap = max(0, lo + n - self.lag)
+        frames = cfg.form.clip([torch.cat([ring[stream, lo:], ring[stream, :wrap]]) if wrap else ring[stream, lo:lo + n] for ring in self._rings])
+        (H, W), R, C = cfg.form.shape[:2], s.mesh_row_count, s.mesh_col_count
         if cfg.on_uncovered == 'limit':
-            p, k = ops.path_limit_group(c, p, W, H, R, C, cfg.rectangle, cfg.limit_steps, cfg.limit_guard, cfg.limit_rise, self._k_prev[d_ids])
-            self._k_prev[d_ids] = k
-        self.last_limit = k
-        table = ops.cell_table(c, p, W, H, R, C)
-        out = form.warp_crop(frames, table, s.color_outside_image_area_bgr, cfg._crop)
-        table.check()
-        crop = table.crop
-        left, top, right, bottom = cfg.rectangle
-        covered = (crop[:, 0] <= left) & (crop[:, 1] <= top) & (crop[:, 2] >= right) & (crop[:, 3] >= bottom)
-        c, p = c.view(K, R + 1, C + 1, 2), p.view(K, R + 1, C + 1, 2)
-        return out, [OnlineReport(first[r], c[r:r + 1], p[r:r + 1], cfg.rectangle, covered[r:r + 1], lost[r]) for r in range(K)]
+            p, k = ops.path_limit(c, p, W, H, R, C, cfg.rectangle, cfg.limit_steps, cfg.limit_guard, cfg.limit_rise,
+                                  self._k_prev[stream:stream + 1].clone() if self._limited[stream] else None)
+        out, covered = self._warp_rows(frames, c, p)
+        self.emitted[stream] += n
+        shape = (n, R + 1, C + 1, 2)
+        return out, OnlineReport(first, c.view(shape), p.view(shape), cfg.rectangle, covered, []), k
+
+    def _result(self, parts):
+        """What a push or a flush returns from its rows' parts -- per row a list of (frames or None, report, k) in order --: (the frames
+        joined in order, a report per row).  Sets `last_counts` and, with on_uncovered='limit', `last_limit`: the k of every frame of `out`."""
+        import torch
+        cfg = self.settings
+        clips = [out for row in parts for out, _, _ in row if out is not None]
+        ks = [k for row in parts for _, _, k in row if k is not None]
+        self.last_counts = [sum(int(r.d_stab.shape[0]) for _, r, _ in row) for row in parts]
+        if cfg.on_uncovered == 'limit':
+            self.last_limit = ks[0] if len(ks) == 1 else torch.cat(ks) if ks else torch.empty(0, dtype=torch.int32, device=self.device)
+        out = cfg.form.empty(*cfg._out_size, self.device) if not clips else clips[0] if len(clips) == 1 else cfg.form.cat(clips)
+        reports = []
+        for row in parts:
+            if len(row) == 1:
+                reports.append(row[0][1])
+            else:                                                           # a tail and the new shot's part, as `OnlineSession.join` joins them
+                d_unstab, d_stab, covered = (torch.cat([getattr(r, field) for _, r, _ in row]) for field in ('d_unstab', 'd_stab', 'covered'))
+                reports.append(OnlineReport(row[0][1].first, d_unstab, d_stab, cfg.rectangle, covered, [t for _, r, _ in row for t in r.lost]))
+        return out, reports
+
+    def flush(self, stream=None):
+        """The end of `stream` (None: of every stream): (its pending frames stabilized and cropped -- of all the named streams, in order --,
+        a list of an `OnlineReport` per named stream), with the last window's solution as their paths, as `OnlineSession.flush` does for
+        its one; then `reset(stream)`.  A stream with nothing pending gives a 0-row report.  Before the first push it is a ValueError."""
+        from . import ops
+        if self.form is None:
+            raise ValueError('flush before the first push: the frame size and form are not known yet')
+        ids = list(range(self.streams)) if stream is None else ops.check_streams([stream], self.streams, 'stream')
+        parts = []
+        for b in ids:
+            parts.append([self._tail(b) if self.pending[b] else (None, self._nothing(b, []), None)])
+            self.reset(b)
+        return self._result(parts)
+
+    def push(self, frames, streams=None):
+        """One new frame of each stream of `streams`, as `OnlineGroup.push` takes them.  Returns (the frames handed out this tick, in row
+        order, a list of K `OnlineReport`): row r hands out its stream's frame seen - lag once the stream has more than `lag` frames -- a
+        report of one row --, nothing before -- a report of 0 rows --, and at a cut found its old shot's tail; `last_counts[r]` is how many
+        frames of the output are row r's, `first` the stream's index of the first of them, `lost` that of the frame PUSHED."""
+        import torch
+        from . import ops
+        cfg, s = self.settings, self.stabilizer
+        self._tails = {}
+        ids, d_ids, form, luma, first, vel, lam_known, lost = self._front(frames, streams)
+        K, (H, W), R, C, S = len(ids), form.shape[:2], s.mesh_row_count, s.mesh_col_count, self.state.S
+        c, p, final = ops.online_smooth_group_lag(vel, lam_known, self.state, ids, cfg._taps, cfg.omega, cfg.iters, cfg.beta, cfg._lam_newest,
+                                                  self.lag)
+        c, p = c.view(K, S), p.view(K, S)
+        self._carry(ids, d_ids, luma, first)
+
+        # the new frames into their slots, the owed ones out of them: row r's frame `first[r]` takes the slot of frame first[r] - lag
+        emit = [r for r in range(K) if final[r] == 1]
+        M = len(emit)
+        out_row = {r: j for j, r in enumerate(emit)}
+        rows = np.array([(b, first[r] % self.lag, out_row.get(r, -1)) for r, b in enumerate(ids)], dtype=np.int32)
+        owed = [ops.ring_exchange(ring, plane, rows, M) for ring, plane in zip(self._rings, form.planes(frames))]
+
+        parts = [[self._tails[r]] if r in self._tails else [] for r in range(K)]
+        if M:
+            k = None
+            if M < K:
+                d_emit = torch.tensor(emit, dtype=torch.int64, device=self.device)
+                c, p, d_ids = c[d_emit], p[d_emit], d_ids[d_emit]
+            if cfg.on_uncovered == 'limit':
+                p, k = ops.path_limit_group(c, p, W, H, R, C, cfg.rectangle, cfg.limit_steps, cfg.limit_guard, cfg.limit_rise, self._k_prev[d_ids])
+                self._k_prev[d_ids] = k
+            out, covered = self._warp_rows(form.clip(owed), c, p)
+            c, p = c.view(M, R + 1, C + 1, 2), p.view(M, R + 1, C + 1, 2)
+            for j, r in enumerate(emit):
+                b = ids[r]
+                report = OnlineReport(self.emitted[b], c[j:j + 1], p[j:j + 1], cfg.rectangle, covered[j:j + 1], lost[r])
+                parts[r].append((out if M == 1 else form.part(out, j, j + 1), report, None if k is None else k if M == 1 else k[j:j + 1]))
+                self.emitted[b] += 1
+                self._limited[b] = k is not None
+        for r, b in enumerate(ids):
+            if r not in out_row:
+                parts[r].append((None, self._nothing(b, lost[r]), None))
+        self._tails = {}
+        if M == K:                                                          # the steady tick: the warp's output and the limiter's k as they are
+            reports = [row[0][1] for row in parts]
+            self.last_counts, self.last_limit = [1] * K, k
+            return out, reports
+        return self._result(parts)

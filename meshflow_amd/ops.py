@@ -1292,7 +1292,18 @@ def online_smooth_group(vel, lam_known, state, streams, taps, omega, iters, beta
     float32; lam_known: (K, n) float64; streams: K ints (no bool), distinct, in 0 .. state.B - 1; taps, omega, iters, beta, lam_newest are
     shared.  Returns (c, p), (K, n, S) float64; the named streams' slices of `state` are updated in place and their `seen` advanced by n, the
     others keep their bytes.  The ids and counts go up in one small copy; runs on torch's current stream and does not wait for it."""
-    name = 'online_smooth_group'
+    ids, K, n, d_rows, c, p = _online_smooth_group_args('online_smooth_group', vel, lam_known, state, streams, taps, omega)
+    _lib.check(_lib_.mf_online_smooth_group_f64(_ptr(vel), _ptr(lam_known), _ptr(taps), _ptr(d_rows[2 * K:]), _ptr(d_rows), K, state.B, n, state.S,
+                                                int(omega), state.L, int(iters), float(beta), float(lam_newest), _ptr(state.c), _ptr(state.q),
+                                                _ptr(state.lam), _ptr(c), _ptr(p), _stream()))
+    for b in ids:
+        state.seen[b] += n
+    return c, p
+
+
+def _online_smooth_group_args(name, vel, lam_known, state, streams, taps, omega):
+    """What `online_smooth_group` and `online_smooth_group_lag` ask alike; returns (ids, K, n, the uploaded counts and ids, c, p): the outputs
+    (K, n, S) float64, not written yet."""
     if not isinstance(state, OnlineGroupState):
         raise ValueError(f'{name}: state must be an OnlineGroupState')
     ids = check_streams(streams, state.B, f'{name}: streams')
@@ -1317,12 +1328,7 @@ def online_smooth_group(vel, lam_known, state, streams, taps, omega, iters, beta
     d_rows = torch.from_numpy(rows).to(state.device, non_blocking=True)
     c = torch.empty((K, n, state.S), dtype=torch.float64, device=state.device)
     p = torch.empty((K, n, state.S), dtype=torch.float64, device=state.device)
-    _lib.check(_lib_.mf_online_smooth_group_f64(_ptr(vel), _ptr(lam_known), _ptr(taps), _ptr(d_rows[2 * K:]), _ptr(d_rows), K, state.B, n, state.S,
-                                                int(omega), state.L, int(iters), float(beta), float(lam_newest), _ptr(state.c), _ptr(state.q),
-                                                _ptr(state.lam), _ptr(c), _ptr(p), _stream()))
-    for b in ids:
-        state.seen[b] += n
-    return c, p
+    return ids, K, n, d_rows, c, p
 
 
 def check_online_lag(lag, L, name='lag'):
@@ -1365,6 +1371,81 @@ def online_pending(state, lag):
     lag = check_online_lag(lag, state.L, 'online_pending: lag')
     rows = min(lag, state.seen)
     return state.c[state.L - 1 - rows:].clone(), state.q[state.L - 1 - rows:].clone()
+
+
+def online_smooth_group_lag(vel, lam_known, state, streams, taps, omega, iters, beta, lam_newest, lag):
+    """`online_smooth_lag` for K rows of n new frames, row r of stream streams[r] of `state`, an `OnlineGroupState`, in one pair of launches
+    (mf_online_smooth_group_lag_f64; tests/online_lag_model.py per row).  Arguments and checks are `online_smooth_group`'s; lag: an int (no
+    bool) in 0 .. state.L - 1, shared by the rows.  The state after a call is `online_smooth_group`'s: it does not depend on lag.  Returns
+    (c, p, final): c, p (K, n, S) float64, and final, a host list of K counts, final[r] = max(0, seen_r + n - lag) - max(0, seen_r - lag) with
+    seen_r the stream's count before the call: the TRAILING final[r] rows of row r are the frames that became final, session indices
+    max(0, seen_r - lag) .. seen_r + n - lag - 1, and the rows in front of them hold the kernel's zeros (`online_smooth_lag` drops them; the
+    rows of a group differ in how many there are).  `online_pending_group` has the rest when a stream ends.  lag = 0 gives
+    `online_smooth_group`'s bytes.  Runs on torch's current stream and does not wait for it."""
+    name = 'online_smooth_group_lag'
+    if not isinstance(state, OnlineGroupState):
+        raise ValueError(f'{name}: state must be an OnlineGroupState')
+    lag = check_online_lag(lag, state.L, f'{name}: lag')
+    ids, K, n, d_rows, c, p = _online_smooth_group_args(name, vel, lam_known, state, streams, taps, omega)
+    _lib.check(_lib_.mf_online_smooth_group_lag_f64(_ptr(vel), _ptr(lam_known), _ptr(taps), _ptr(d_rows[2 * K:]), _ptr(d_rows), K, state.B, n,
+                                                    state.S, int(omega), state.L, lag, int(iters), float(beta), float(lam_newest), _ptr(state.c),
+                                                    _ptr(state.q), _ptr(state.lam), _ptr(c), _ptr(p), _stream()))
+    final = [max(0, state.seen[b] + n - lag) - max(0, state.seen[b] - lag) for b in ids]
+    for b in ids:
+        state.seen[b] += n
+    return c, p, final
+
+
+def online_pending_group(state, streams, lag):
+    """`online_pending` for each stream of `streams` on its slices of an `OnlineGroupState`: a list of (c, p), one per named stream, clones of
+    the last min(lag, state.seen[b]) rows of state.c[b] / state.q[b], oldest first.  No kernel of the library's; the state is left as it is."""
+    name = 'online_pending_group'
+    if not isinstance(state, OnlineGroupState):
+        raise ValueError(f'{name}: state must be an OnlineGroupState')
+    lag = check_online_lag(lag, state.L, f'{name}: lag')
+    pending = []
+    for b in check_streams(streams, state.B, f'{name}: streams'):
+        rows = min(lag, state.seen[b])
+        pending.append((state.c[b, state.L - 1 - rows:].clone(), state.q[b, state.L - 1 - rows:].clone()))
+    return pending
+
+
+def ring_exchange(ring, new, rows, M):
+    """One tick of a ring of owed frames (mf_ring_exchange_u8, bit for bit tests/ring_model.py): ring (B, lag, ...) and new (K, ...) device
+    tensors of one dtype and trailing shape, contiguous; rows: a (K, 3) int32 host array of (id, slot, out_row) per row of `new`, uploaded in
+    one small copy.  Row r with out_row >= 0: out[out_row] = ring[id, slot], then ring[id, slot] = new[r]; with out_row < 0 only the store.
+    M: the number of rows that hand a frame out, their out_row 0 .. M - 1, each once; the ids distinct.  Returns out (M, ...); M = 0 gives
+    0 frames.  `ring` is updated in place.  Samples of any width go through as bytes.  Runs on torch's current stream and does not wait."""
+    name = 'ring_exchange'
+    if not isinstance(ring, torch.Tensor) or not isinstance(new, torch.Tensor):
+        raise ValueError(f'{name}: ring and new must be torch tensors')
+    if ring.dim() < 3 or new.dim() != ring.dim() - 1 or new.dtype != ring.dtype or new.shape[1:] != ring.shape[2:]:
+        raise ValueError(f'{name}: ring must be (B, lag, ...) and new (K, ...) of the same dtype and trailing shape (got {ring.dtype} '
+                         f'{tuple(ring.shape)} and {new.dtype} {tuple(new.shape)})')
+    for t, what in ((ring, 'ring'), (new, 'new')):
+        if not t.is_cuda or t.device != ring.device:
+            raise ValueError(f'{name}: {what} must be a CUDA/HIP torch tensor, both on one device')
+        if not t.is_contiguous():
+            raise ValueError(f'{name}: {what} must be contiguous')
+    B, lag, K = int(ring.shape[0]), int(ring.shape[1]), int(new.shape[0])
+    N = int(new[0].numel()) * new.element_size() if K else 0
+    if B < 1 or lag < 1 or K < 1 or N < 1 or K > _lib.ONLINE_GROUP_MAX_ROWS:
+        raise ValueError(f'{name}: B, lag, K and the bytes of a frame must be at least 1 and K <= {_lib.ONLINE_GROUP_MAX_ROWS} (got ring '
+                         f'{tuple(ring.shape)}, new {tuple(new.shape)})')
+    rows = np.ascontiguousarray(rows)
+    if rows.dtype != np.int32 or rows.shape != (K, 3):
+        raise ValueError(f'{name}: rows must be a ({K}, 3) int32 array of (id, slot, out_row) (got {rows.dtype} {rows.shape})')
+    M = int(M)
+    handed = sorted(int(v) for v in rows[:, 2] if v >= 0)
+    if handed != list(range(M)):
+        raise ValueError(f'{name}: the out_row of the rows that hand a frame out must be 0 .. M - 1 = {M - 1}, each once (got {handed})')
+    if ((rows[:, 0] < 0) | (rows[:, 0] >= B) | (rows[:, 1] < 0) | (rows[:, 1] >= lag)).any() or len(set(rows[:, 0].tolist())) != K:
+        raise ValueError(f'{name}: ids must be distinct and in 0 .. {B - 1}, slots in 0 .. {lag - 1} (got {rows[:, :2].tolist()})')
+    d_rows = torch.from_numpy(rows).to(ring.device, non_blocking=True)
+    # (room for K frames, as the library's overlap rule takes d_out -- it cannot see M --; the steady tick has M = K)
+    out = torch.empty((K,) + tuple(new.shape[1:]), dtype=new.dtype, device=new.device)
+    _lib.check(_lib_.mf_ring_exchange_u8(_ptr(ring), _ptr(new), _ptr(out), _ptr(d_rows), K, B, lag, N, _stream()))
+    return out[:M]
 
 
 CUT_THRESHOLD = 0.30            # a design choice, not a value tuned on footage (profiles/cuts.md)

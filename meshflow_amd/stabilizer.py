@@ -434,8 +434,8 @@ class MeshFlowStabilizer:
         whose `push(frames, streams=None)` takes ONE new frame of each of K distinct streams (a stack (K, ...) in any form a session
         takes, a (d_y, d_uv) pair of (K, ...) stacks for 4:2:0, NV16 and P210 (a packed 4:2:2 clip is no session form: callers unpack once per push); `streams` lists the K indices in any order and defaults to all) and
         returns (the K frames stabilized and cropped, [an `online.OnlineReport` per pushed stream]); row r and report r belong to
-        streams[r].  The keywords are `online_session`'s and mean the same, except lag, which must be 0 (the held pixels and a flush per
-        stream are not built), and on_lost, which must be 'hold' (one camera's lost pair must not stop the others; it is listed in that
+        streams[r].  The keywords are `online_session`'s and mean the same, except lag, which must be 0 (`online_lag_group` is the
+        group with look-ahead), and on_lost, which must be 'hold' (one camera's lost pair must not stop the others; it is listed in that
         stream's `report.lost`): both are a ValueError otherwise.
         The contract: a stream gets the bytes that an `online_session` of its own with the same keywords returns when pushed the same
         frames one at a time -- frames, d_unstab, d_stab, covered, first, lost, the limiter's k, the cut decisions and distances, shots --
@@ -448,6 +448,27 @@ class MeshFlowStabilizer:
         `last_cut_distances` are per pushed row of the last push; `reset(stream=None)` forgets one stream or all."""
         from . import online
         return online.OnlineGroup(self, streams, **keywords)
+
+    def online_lag_group(self, streams, lag, **keywords):
+        """`online_group` with `lag` frames of look-ahead per stream: an `online.OnlineLagGroup`.  lag: an int (no bool) in
+        1 .. window - 1 (0 is `online_group`); the keywords are `online_group`'s, on_lost='hold' only -- on_lost='raise' remains a keyword
+        of sessions: one camera's lost pair must not stop the others.
+        The contract is `online_group`'s against `online_session(lag=lag, **keywords)`: stream b gets, byte for byte, what a lagged session
+        of its own returns when pushed the same frames one at a time -- frames, d_unstab, d_stab, covered, first, lost, the limiter's k,
+        the cut decisions and distances, shots, and `pending`.  `push(frames, streams=None)` takes one new frame of each of K distinct
+        streams and returns (the frames handed out this tick, concatenated in row order, [an `online.OnlineReport` per pushed row]): a row
+        hands out the frame its stream was pushed `lag` frames of its own earlier, none while the stream has no more than `lag` frames,
+        and `last_counts[r]` says how many frames of the output are row r's.  `lost` is reported at the tick of the push.  With
+        on_cut='reset' a stream found at a cut hands out its old shot's tail in that tick, in front, and starts again.
+        `flush(stream=None)` ends one stream or all: (the pending frames with the last window's solution as their path, a report per
+        named stream), then `reset(stream)`; `reset` DISCARDS pending frames.  `pending` is a list per stream.
+        A steady tick issues `online_group`'s launches with `ops.online_smooth_group_lag` as the smoother, plus one `ops.ring_exchange`
+        per plane, which stores the K new frames in a ring on the device and hands out the owed ones (profiles/online_group_lag.md);
+        the limiter, the cell table, the warp and the crop-resize run on the rows that hand a frame out.
+        Memory: the ring holds streams * lag frames per plane of the clip form on the device, allocated at the first push (16 streams of
+        1080p BGR at lag 5: 498 MB); a ValueError names the size if it cannot be had."""
+        from . import online
+        return online.OnlineLagGroup(self, streams, lag, **keywords)
 
     def find_cuts(self, clip, threshold=0.30, red_first=False):
         """Where the shots of a resident clip begin: the list of frame indices t in 1 .. F-1 whose tile-histogram distance to frame t - 1

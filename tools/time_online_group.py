@@ -5,7 +5,8 @@ group first when i is even and the sessions first when it is odd.  The sessions'
 end, which favours them.  Beside it `ops.online_smooth_group` at K = --streams against K `ops.online_smooth` calls on a full window, by HIP
 events.  The better and the median of --repeats after a warm-up pass each.  One JSON line; run it in a fresh process per sample.
     python tools/time_online_group.py [--streams 16] [--form grey|bgr|nv12] [--mesh 16] [--window 40] [--omega 10] [--iters 10]
-                                      [--height 1080] [--width 1920] [--warm 32] [--max-per-subframe 128] [--chunk-pairs 32] [--repeats 5]"""
+                                      [--height 1080] [--width 1920] [--warm 32] [--max-per-subframe 128] [--chunk-pairs 32] [--repeats 5]
+--lag k times the tick of an `OnlineLagGroup` instead (`lagged` below; profiles/online_group_lag.md)."""
 import argparse
 import json
 import os
@@ -31,7 +32,12 @@ def main():
     ap.add_argument('--chunk-pairs', type=int, default=32)
     ap.add_argument('--repeats', type=int, default=5)
     ap.add_argument('--no-sessions', action='store_true', help='time the group alone')
+    ap.add_argument('--lag', type=int, default=0, help='k >= 1: time the lagged group tick against lagged sessions and the lag-0 group tick')
+    ap.add_argument('--contenders', default='lag_group,group,sessions',
+                    help='--lag: which of the three to time (group,sessions is what a build without online_lag_group can run)')
     a = ap.parse_args()
+    if a.lag:
+        return lagged(a)
     import numpy as np
     import torch
     from meshflow_amd import host, ops, synthetic
@@ -128,6 +134,130 @@ def main():
         report('sessions_push_ms', apart)
         out['lost_pairs_sessions'] = lost[1]
         out['group_over_sessions_median'] = out['group_push_ms_median'] / out['sessions_push_ms_median']
+    print(json.dumps(out))
+
+
+def lagged(a):
+    """--lag k (profiles/online_group_lag.md): per tick of --streams running streams, by HIP events around each and one wait behind it, in an
+    order that turns with the repetition, (a) one `OnlineLagGroup.push`, (b) that many `online_session(lag=k)` pushes, (c) one lag-0
+    `OnlineGroup.push`; and, alone, one `ops.ring_exchange` per plane of a steady tick (about 4 N K bytes) against `Tensor.copy_` of 2 N K
+    bytes, which moves as many."""
+    import numpy as np
+    import torch
+    from meshflow_amd import ops, synthetic
+    from meshflow_amd.stabilizer import MeshFlowStabilizer
+    if not torch.cuda.is_available():
+        raise SystemExit('time_online_group.py measures on an MI355X: no GPU visible')
+    dev = torch.device('cuda:0')
+    B, k = a.streams, a.lag
+    out = dict(streams=B, lag=k, form=a.form, mesh=a.mesh, window=a.window, omega=a.omega, iters=a.iters, width=a.width, height=a.height,
+               warm=a.warm, max_per_subframe=a.max_per_subframe, chunk_pairs=a.chunk_pairs, repeats=a.repeats)
+
+    def report(key, samples):
+        out[key + '_best'], out[key + '_median'] = min(samples), statistics.median(samples)
+
+    ticks = a.warm + a.repeats + 1
+    count = ticks + B
+    pool = torch.cat([synthetic.frames_torch(min(50, count - lo), a.height, a.width, dev, seed=1, first_frame=lo) for lo in range(0, count, 50)])
+    if a.form != 'bgr':
+        pool = pool[..., 1].contiguous()
+    uv = torch.randint(0, 256, (count, a.height // 2, a.width // 2, 2), dtype=torch.uint8, device=dev) if a.form == 'nv12' else None
+    rows = torch.arange(B, device=dev)
+
+    def tick(t):
+        return (pool[rows + t], uv[rows + t]) if uv is not None else pool[rows + t]
+
+    def row(frames, b):
+        return tuple(p[b:b + 1] for p in frames) if uv is not None else frames[b:b + 1]
+
+    s = MeshFlowStabilizer(mesh_row_count=a.mesh, mesh_col_count=a.mesh, temporal_smoothing_radius=a.omega, device='cuda:0')
+    kw = dict(window=a.window, iters=a.iters, max_per_subframe=a.max_per_subframe, chunk_pairs=a.chunk_pairs)
+    wanted = [name for name in a.contenders.split(',') if not (name == 'sessions' and a.no_sessions)]
+    if not wanted or set(wanted) - {'lag_group', 'group', 'sessions'}:
+        raise SystemExit(f'--contenders takes lag_group, group and sessions (got {a.contenders!r})')
+    lag_group = s.online_lag_group(B, k, **kw) if 'lag_group' in wanted else None
+    plain_group = s.online_group(B, **kw) if 'group' in wanted else None
+    sessions = [s.online_session(lag=k, **kw) for _ in range(B)] if 'sessions' in wanted else []
+
+    def push_lag_group(frames):
+        lag_group.push(frames)
+
+    def push_sessions(frames):
+        for b, session in enumerate(sessions):
+            session.push(row(frames, b))
+
+    def push_plain_group(frames):
+        plain_group.push(frames)
+
+    contenders = [dict(lag_group=push_lag_group, group=push_plain_group, sessions=push_sessions)[name] for name in wanted]
+    out['contenders'] = wanted
+
+    def timed(fn, frames):
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        w0 = time.perf_counter()
+        ev[0].record()
+        fn(frames)
+        ev[1].record()
+        torch.cuda.synchronize()
+        return ev[0].elapsed_time(ev[1]), (time.perf_counter() - w0) * 1e3
+
+    for t in range(a.warm):                                             # (fills the windows and the rings, warms every kernel up)
+        frames = tick(t)
+        for fn in contenders:
+            fn(frames)
+    torch.cuda.synchronize()
+    assert lag_group is None or lag_group.pending == [k] * B
+    samples = {fn: [] for fn in contenders}
+    for i in range(a.repeats + 1):
+        frames = tick(a.warm + i)
+        torch.cuda.synchronize()
+        turn = i % len(contenders)
+        for fn in contenders[turn:] + contenders[:turn]:
+            ms = timed(fn, frames)
+            if i:
+                samples[fn].append(ms)
+    for fn, key in ((push_lag_group, 'lag_group_push'), (push_plain_group, 'group_push'), (push_sessions, 'lag_sessions_push')):
+        if fn in samples:
+            report(key + '_event_ms', [e for e, _ in samples[fn]])
+            report(key + '_wall_ms', [w for _, w in samples[fn]])
+    if lag_group is not None and plain_group is not None:
+        out['lag_group_over_group_median'] = out['lag_group_push_wall_ms_median'] / out['group_push_wall_ms_median']
+    if lag_group is not None and sessions:
+        out['lag_group_over_lag_sessions_median'] = out['lag_group_push_wall_ms_median'] / out['lag_sessions_push_wall_ms_median']
+    if lag_group is None:
+        print(json.dumps(out))
+        return
+
+    # the exchange of a steady tick alone, per plane, against a device copy that moves as many bytes
+    frames = tick(ticks - 1)
+    planes = frames if uv is not None else (frames,)
+    exchange, copy, runs = [], [], 20                                   # 20 ticks per sample, the slot turning as it does in a group
+    rings = [torch.zeros((B, k) + tuple(p.shape[1:]), dtype=p.dtype, device=dev) for p in planes]
+    twice = [torch.zeros((2,) + tuple(p.shape), dtype=p.dtype, device=dev) for p in planes]
+    landing = [torch.empty_like(t) for t in twice]
+    for i in range(a.repeats + 1):
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+        ev[0].record()
+        for j in range(runs):
+            table = np.array([(b, j % k, b) for b in range(B)], dtype=np.int32)
+            for ring, p in zip(rings, planes):
+                ops.ring_exchange(ring, p, table, B)
+        ev[1].record()
+        ev[2].record()
+        for j in range(runs):
+            for src, dst in zip(twice, landing):
+                dst.copy_(src)
+        ev[3].record()
+        torch.cuda.synchronize()
+        if i:
+            exchange.append(ev[0].elapsed_time(ev[1]) / runs)
+            copy.append(ev[2].elapsed_time(ev[3]) / runs)
+    moved = sum(4 * p.numel() * p.element_size() for p in planes)
+    report('exchange_ms', exchange)
+    report('copy_ms', copy)
+    out['exchange_bytes_moved'] = moved
+    out['exchange_tb_per_s_median'] = moved / (out['exchange_ms_median'] * 1e-3) / 1e12
+    out['copy_tb_per_s_median'] = moved / (out['copy_ms_median'] * 1e-3) / 1e12
     print(json.dumps(out))
 
 
