@@ -15,7 +15,9 @@ push returns the frames that have become final, [emitted, seen - k), and the ses
 owes, as clones on the device (`hold_frames`).  `flush()` hands those out when the stream -- or, with on_cut='reset', a shot -- ends.
 
 Many live streams of one size go through an `OnlineGroup` (`MeshFlowStabilizer.online_group`; profiles/online_group.md): one new frame of each
-of any subset of them per push, in one set of launches, with the bytes of a session per stream."""
+of any subset of them per push, in one set of launches, with the bytes of a session per stream; an `OnlineLagGroup` gives each `lag` frames
+of look-ahead (profiles/online_group_lag.md).  What the three are told lives in an `OnlineSettings` each, and the stages they share exist
+once, as functions of it: `track_pairs`, `warp_rows`, `empty_result`, `join_reports`."""
 import collections
 import math
 
@@ -59,6 +61,12 @@ class ClipForm(collections.namedtuple('ClipForm', 'fmt dtype shape')):
     def cat(self, clips):
         import torch
         return self.clip([torch.cat(planes) for planes in zip(*(self.planes(c) for c in clips))])
+
+    def check_same(self, other, who):
+        """ValueError unless `other`, the form of a later push to `who` -- 'session' or 'group' --, is this form, that of its first."""
+        if other != self:
+            raise ValueError(f'this {who} takes {self.dtype} frames of shape {self.shape}{" as (d_y, d_uv) pairs" if self.pair else ""}; '
+                             f'got {other.dtype} frames of shape {other.shape}{" as a pair" if other.pair else ""}')
 
     def warp_crop(self, clip, table, border_bgr, crop):
         """The format's warp from `table` -- border_bgr for a stack, the format's red for a pair -- and, unless `crop` is None, its
@@ -128,19 +136,12 @@ def hold_frames(held, planes, m):
     return tuple(torch.cat([x, f[:m - h]]) for x, f in zip(held, planes)), (tuple(f[m - h:].clone() for f in planes) if m - h < n else None)
 
 
-# What a shot carries from push to push beside the `ops.OnlineState` (its tensors and `seen`), and what each starts from: the one list
-# that the constructor, `reset()`, `_snapshot()` and `_restore()` go by.
-#   _last_luma: the last luma frame pushed, the early frame of the next push's first pair;
-#   _last_sig:  on_cut='reset': that frame's scene-cut signature;
-#   _k_prev:    on_uncovered='limit': the limiter's k of the last frame handed out, a 1-element int32 device tensor (None: k starts at K);
-#   _held:      lag >= 1: the input frames not handed out yet, oldest first, as a tuple of the input's planes (`hold_frames`);
-#   emitted:    how many frames of the path begun at the last reset have been handed out.
-# Every one is REPLACED, never written to -- and so are the tensors behind them --, which is why a snapshot keeps references, not clones.
-_CARRIED = {'_last_luma': None, '_last_sig': None, '_k_prev': None, '_held': None, 'emitted': 0}
-
-
-class OnlineSession:
-    """One stream of frames through `stabilizer`.  Made by `MeshFlowStabilizer.online_session`, which documents the keywords."""
+class OnlineSettings:
+    """What a session or a group is told and what its first push finds out; nothing that a stream carries.  The keywords are
+    `MeshFlowStabilizer.online_session`'s, checked here for sessions and groups alike; with them come the tracker and the device.  The
+    first push (`start`) adds form, the frames' `ClipForm`; rectangle, the fixed crop; crop, `ClipForm.warp_crop`'s (None: the warp goes
+    out whole); out_size, the output's (width, height); taps, the smoother's, on the device; lam_newest, the newest frame's weight; dims,
+    the (W, H, R, C) that the ops take; grid, a frame's path as a report shapes it, and S, its floats.  The shared stages below take one."""
 
     def __init__(self, stabilizer, window=40, iters=10, beta=1.0, crop_margin=0.08, output_size=None,
                  adaptive_weights_definition=host.ADAPTIVE_WEIGHTS_DEFINITION_ORIGINAL, chunk_pairs=32, max_per_subframe=1024, red_first=False,
@@ -169,19 +170,137 @@ class OnlineSession:
         self.on_uncovered = on_uncovered
         self.limit_steps, self.limit_guard, self.limit_rise = ops.check_path_limit(limit_steps, limit_guard, limit_rise,
                                                                                    ('limit_steps', 'limit_guard', 'limit_rise'))
-        self.last_limit = None        # on_uncovered='limit': the last push's (n,) int32 k on the device
         self.on_cut, self.cut_threshold = on_cut, ops.check_cut_threshold(cut_threshold, 'cut_threshold')
         self.stabilizer, self.window, self.omega, self.iters, self.beta = stabilizer, int(window), omega, int(iters), float(beta)
         self.crop_margin, self.output_size, self.definition = crop_margin, output_size, adaptive_weights_definition
         self.chunk_pairs, self.red_first, self.on_lost = chunk_pairs, red_first, on_lost
         self.device = stabilizer._torch_device()
         self.tracker = stabilizer.device_tracker(max_per_subframe, 'device', 'device')
-        # fixed by the first push (`_start`): its `ClipForm`, the rectangle, the output's (width, height), `ClipForm.warp_crop`'s crop, the state
-        self.form = self.rectangle = self._out_size = self._crop = self.state = self._taps = self._lam_newest = None
+        self.form = self.rectangle = self.crop = self.out_size = self.taps = self.lam_newest = self.dims = self.grid = self.S = None   # (`start`)
+
+    def check_limit_fits(self, frames):
+        """on_uncovered='limit', before the first push touches the device -- or has a form --: the rectangle widened by the guard must lie
+        inside the untouched frame with a pixel to spare, or no candidate could pass and every frame would come back unstabilized."""
+        first = frames[0] if isinstance(frames, (tuple, list)) and len(frames) == 2 else frames
+        shape = getattr(first, 'shape', ())
+        if len(shape) < 3:
+            return                                  # (not a clip: `luma_of` says what is wrong with it)
+        H, W = int(shape[1]), int(shape[2])
+        left, top, _, _ = margin_rectangle(self.crop_margin, W, H)
+        if left < self.limit_guard + 1 or top < self.limit_guard + 1:
+            raise ValueError(f"on_uncovered='limit': crop_margin={self.crop_margin} leaves {left} x {top} pixels around the rectangle of a "
+                             f'{W} x {H} frame, limit_guard={self.limit_guard} needs {self.limit_guard + 1:g} on every side: no correction would '
+                             'pass; widen crop_margin')
+
+    def read(self, frames):
+        """What every push begins with: (the frames' `ClipForm`, their luma), behind `check_limit_fits` while no push has fixed a form."""
+        if self.form is None and self.on_uncovered == 'limit':
+            self.check_limit_fits(frames)
+        return luma_of(frames, self.red_first)
+
+    def start(self, form, H, W):
+        """The first push: frames of `form`, H x W in luma, fix everything listed above."""
+        import torch
+        from . import ops
+        if self.output_size is not None:
+            self.output_size = (ops._yuv_output_size(form.fmt, self.output_size, 'output_size') if form.pair else
+                                ops.check_output_size(self.output_size, 'output_size'))
+        rectangle = margin_rectangle(self.crop_margin, W, H)
+        R, C = self.stabilizer.mesh_row_count, self.stabilizer.mesh_col_count
+        self.dims, self.grid, self.S = (W, H, R, C), (R + 1, C + 1, 2), (R + 1) * (C + 1) * 2
+        self.taps = torch.from_numpy(host.online_taps(self.omega)).to(self.device)
+        # the weight of the newest frame: the identity homography's under the chosen definition (mfs.py:273-274, 757)
+        self.lam_newest = float(host.adaptive_weights(1, W, H, self.definition, np.identity(3)[None])[0])
+        whole = rectangle == (0, 0, W - 1, H - 1) and self.output_size in (None, (W, H))
+        self.crop = None if whole else (rectangle, self.output_size)
+        self.out_size = (W, H) if whole or self.output_size is None else self.output_size
+        self.form, self.rectangle = form, rectangle
+
+    def check_started(self):
+        if self.form is None:
+            raise ValueError('flush before the first push: the frame size and form are not known yet')
+
+
+def track_pairs(cfg, early, late, t0=None):
+    """A run of pairs early[i] -> late[i], luma stacks (P, H, W), through the tracker and `ops.vertex_motion`: (their velocities (P, S)
+    float32 on the device, their weights (P,) float64 from the homographies, the indices of the pairs that could not be fitted).  Such a
+    pair has no motion ('hold'), or -- on_lost='raise' -- the first is a ValueError about frames t0 + i and t0 + i + 1, before any further launch."""
+    import torch
+    from . import _lib, ops
+    s, (W, H, _, _) = cfg.stabilizer, cfg.dims
+    early, late, offsets, kmax, d_hom, d_info = cfg.tracker.track_stacks_resident(early, late, cfg.chunk_pairs)
+    _, d_vel, status = ops.vertex_motion(early, late, offsets, d_hom, kmax, *cfg.dims, s.feature_ellipse_row_count, s.feature_ellipse_col_count)
+    homographies, info = d_hom.cpu().numpy(), d_info.cpu().numpy()          # (the one wait of a push beyond the tracker's own)
+    ops.vertex_motion_check(status)
+    bad = np.nonzero(info[:, 0] != _lib.HFIT_OK)[0]
+    if bad.size and cfg.on_lost == 'raise':
+        t = t0 + int(bad[0])
+        raise ValueError(f'fewer than {s.homography_min_number_corresponding_features} features could be '
+                         f'tracked from frame {t} to frame {t + 1}')
+    d_vel = d_vel.reshape(-1, cfg.S)
+    if bad.size:
+        # The fit left the identity there, whose weight is lam_newest's; an empty feature range gives a zero velocity by itself
+        # (oracle/motion_oracle.py), a refused fit over a non-empty range does not
+        d_vel = d_vel.index_fill(0, torch.from_numpy(bad).to(cfg.device), 0.0)
+    return d_vel, host.adaptive_weights(len(homographies), W, H, cfg.definition, homographies), bad
+
+
+def warp_rows(cfg, frames, c, p):
+    """Frames with their paths (n, S) through one cell table, the format's warp and the crop-resize: (frames out, covered (n,) bool)."""
+    from . import ops
+    table = ops.cell_table(c, p, *cfg.dims)
+    out = cfg.form.warp_crop(frames, table, cfg.stabilizer.color_outside_image_area_bgr, cfg.crop)
+    table.check()
+    crop = table.crop
+    left, top, right, bottom = cfg.rectangle
+    return out, (crop[:, 0] <= left) & (crop[:, 1] <= top) & (crop[:, 2] >= right) & (crop[:, 3] >= bottom)
+
+
+def empty_result(cfg, first, lost):
+    """What a part that hands out no frame returns: (0 frames of the output's dtype and trailing shape, a report with 0-row tensors, 0
+    steps of the limiter or None).  No op is called."""
+    import torch
+    k = torch.empty(0, dtype=torch.int32, device=cfg.device) if cfg.on_uncovered == 'limit' else None
+    path = torch.empty((0,) + cfg.grid, dtype=torch.float64, device=cfg.device)
+    return (cfg.form.empty(*cfg.out_size, cfg.device),
+            OnlineReport(first, path, path.clone(), cfg.rectangle, torch.empty(0, dtype=torch.bool, device=cfg.device), lost), k)
+
+
+def join_reports(reports):
+    """The reports of consecutive parts of one stream as one: `first` is the first part's, `lost` in each part's own numbering."""
+    import torch
+    d_unstab, d_stab, covered = (torch.cat([getattr(r, field) for r in reports]) for field in ('d_unstab', 'd_stab', 'covered'))
+    return OnlineReport(reports[0].first, d_unstab, d_stab, reports[0].rectangle, covered, [t for r in reports for t in r.lost])
+
+
+# What a shot carries from push to push beside the `ops.OnlineState` (its tensors and `seen`), and what each starts from: the one list
+# that the constructor, `reset()`, `_snapshot()` and `_restore()` go by.
+#   _last_luma: the last luma frame pushed, the early frame of the next push's first pair;
+#   _last_sig:  on_cut='reset': that frame's scene-cut signature;
+#   _k_prev:    on_uncovered='limit': the limiter's k of the last frame handed out, a 1-element int32 device tensor (None: k starts at K);
+#   _held:      lag >= 1: the input frames not handed out yet, oldest first, as a tuple of the input's planes (`hold_frames`);
+#   emitted:    how many frames of the path begun at the last reset have been handed out.
+# Every one is REPLACED, never written to -- and so are the tensors behind them --, which is why a snapshot keeps references, not clones.
+_CARRIED = {'_last_luma': None, '_last_sig': None, '_k_prev': None, '_held': None, 'emitted': 0}
+
+
+class OnlineSession:
+    """One stream of frames through `stabilizer`.  Made by `MeshFlowStabilizer.online_session`, which documents the keywords; they live in
+    `settings` (`OnlineSettings`) and read as the session's own.  The session itself holds what the stream carries: `state`, an `ops.OnlineState` made by the first
+    push, and the members of `_CARRIED`."""
+
+    def __init__(self, stabilizer, *args, **keywords):
+        self.settings = OnlineSettings(stabilizer, *args, **keywords)
+        self.state = None             # made by the first push (`_start`)
+        self.last_limit = None        # on_uncovered='limit': the last push's (n,) int32 k on the device
         # shots: the shots begun so far (the first frame, every frame after a `reset()`, every cut found); last_cuts: the indices, relative to
         # the last push, of its frames that started a shot, and last_cut_distances: that push's (n,) int32 distances -- on_cut='reset' only
         self.shots, self.last_cuts, self.last_cut_distances = 0, [], None
         self.reset()
+
+    def __getattr__(self, name):
+        """What the settings hold reads as the session's own, as when the session held it: `form`, `rectangle`, `lag`, `on_uncovered` and the rest."""
+        return getattr(object.__getattribute__(self, 'settings'), name)    # (no settings, on a session made without its constructor: AttributeError)
 
     @property
     def seen(self):
@@ -216,28 +335,17 @@ class OnlineSession:
         warp and crop as a push's; then the session is left as `reset()` leaves it.  With lag=0, or nothing pending, the empty result: 0
         frames of the output's dtype and trailing shape and a report with 0-row tensors.  Before the first push, whose frames fix that
         shape, it is a ValueError."""
-        if self.form is None:
-            raise ValueError('flush before the first push: the frame size and form are not known yet')
+        self.settings.check_started()
         parts = [self._flush_part()]
         self.reset()
         return self._result(parts)
 
+    _check_limit_fits = OnlineSettings.check_limit_fits                  # (it reads `crop_margin` and `limit_guard`, which a session has as above)
+
     def _start(self, form, H, W):
-        import torch
         from . import ops
-        if self.output_size is not None:
-            self.output_size = (ops._yuv_output_size(form.fmt, self.output_size, 'output_size') if form.pair else
-                                ops.check_output_size(self.output_size, 'output_size'))
-        rectangle = margin_rectangle(self.crop_margin, W, H)
-        s = self.stabilizer
-        self.state = ops.OnlineState((s.mesh_row_count + 1) * (s.mesh_col_count + 1) * 2, self.window, self.device)
-        self._taps = torch.from_numpy(host.online_taps(self.omega)).to(self.device)
-        # the weight of the newest frame: the identity homography's under the chosen definition (mfs.py:273-274, 757)
-        self._lam_newest = float(host.adaptive_weights(1, W, H, self.definition, np.identity(3)[None])[0])
-        whole = rectangle == (0, 0, W - 1, H - 1) and self.output_size in (None, (W, H))
-        self._crop = None if whole else (rectangle, self.output_size)
-        self._out_size = (W, H) if whole or self.output_size is None else self.output_size
-        self.form, self.rectangle = form, rectangle
+        self.settings.start(form, H, W)
+        self.state = ops.OnlineState(self.settings.S, self.settings.window, self.settings.device)
 
     def push(self, frames):
         """One or more new frames -- a stack (n, ...) in any form `stabilize_scored` takes, on the session's device -- in; returns
@@ -253,25 +361,23 @@ class OnlineSession:
         on_cut='reset' the old shot is flushed before the `reset()` at each cut: its tail comes out of this push, in front of the new
         shot's frames."""
         from . import ops
-        if self.form is None and self.on_uncovered == 'limit':
-            self._check_limit_fits(frames)
-        form, luma = luma_of(frames, self.red_first)
+        cfg = self.settings
+        form, luma = cfg.read(frames)
         n, H, W = (int(v) for v in luma.shape)
         if n < 1:
             raise ValueError('push needs at least one frame')
-        if self.form is None:
+        if cfg.form is None:
             self._start(form, H, W)
-        elif form != self.form:
-            raise ValueError(f'this session takes {self.form.dtype} frames of shape {self.form.shape}{" as (d_y, d_uv) pairs" if self.form.pair else ""}; '
-                             f'got {form.dtype} frames of shape {form.shape}{" as a pair" if form.pair else ""}')
+        else:
+            cfg.form.check_same(form, 'session')
         # (what on_cut='ignore' puts in their place is what the three members hold from the start: nothing is looked for)
-        cuts, distances, sig = ops.find_cuts(luma, self.cut_threshold, self._last_sig) if self.on_cut == 'reset' else ([], None, None)
+        cuts, distances, sig = ops.find_cuts(luma, cfg.cut_threshold, self._last_sig) if cfg.on_cut == 'reset' else ([], None, None)
         if not cuts:
             parts = [self._push_part(frames, luma)]
         else:
             starts = sorted({0, *cuts}) + [n]
             # on_lost='raise' promises the session as it was: a part may fail after an earlier one, or a reset, has changed it
-            saved = self._snapshot() if self.on_lost == 'raise' else None
+            saved = self._snapshot() if cfg.on_lost == 'raise' else None
             try:
                 parts = []
                 for lo, hi in zip(starts[:-1], starts[1:]):
@@ -287,114 +393,62 @@ class OnlineSession:
         self._last_sig, self.last_cuts, self.last_cut_distances = sig, cuts, distances
         return self._result(parts)
 
-    def _check_limit_fits(self, frames):
-        """on_uncovered='limit', before the first push touches the device -- or has a form --: the rectangle widened by the guard must lie
-        inside the untouched frame with a pixel to spare, or no candidate could pass and every frame would come back unstabilized."""
-        first = frames[0] if isinstance(frames, (tuple, list)) and len(frames) == 2 else frames
-        shape = getattr(first, 'shape', ())
-        if len(shape) < 3:
-            return                                  # (not a clip: `luma_of` says what is wrong with it)
-        H, W = int(shape[1]), int(shape[2])
-        left, top, _, _ = margin_rectangle(self.crop_margin, W, H)
-        if left < self.limit_guard + 1 or top < self.limit_guard + 1:
-            raise ValueError(f"on_uncovered='limit': crop_margin={self.crop_margin} leaves {left} x {top} pixels around the rectangle of a "
-                             f'{W} x {H} frame, limit_guard={self.limit_guard} needs {self.limit_guard + 1:g} on every side: no correction would '
-                             'pass; widen crop_margin')
-
     def _result(self, parts):
         """What a push or a flush returns from its parts (frames, report, k), in order; on_uncovered='limit': their k is `last_limit`."""
         import torch
-        if self.on_uncovered == 'limit':
+        if self.settings.on_uncovered == 'limit':
             self.last_limit = parts[0][2] if len(parts) == 1 else torch.cat([k for _, _, k in parts])
         return parts[0][:2] if len(parts) == 1 else self.join([p[:2] for p in parts])
 
     def join(self, parts):
-        """Several (frames, report) of this session's stream in order as one: `first` is the first part's, `lost` in each part's own
-        numbering."""
-        import torch
-        d_unstab, d_stab, covered = (torch.cat([getattr(r, field) for _, r in parts]) for field in ('d_unstab', 'd_stab', 'covered'))
-        return self.form.cat([out for out, _ in parts]), OnlineReport(parts[0][1].first, d_unstab, d_stab, self.rectangle, covered,
-                                                                      [t for _, r in parts for t in r.lost])
+        """Several (frames, report) of this session's stream in order as one: the frames concatenated, the reports as `join_reports` joins them."""
+        return self.form.cat([out for out, _ in parts]), join_reports([r for _, r in parts])
 
     def _push_part(self, frames, luma):
         """A run of frames of one shot through the session: (frames out, `OnlineReport`, the limiter's k or None)."""
         import torch
-        from . import _lib, ops
-        s = self.stabilizer
-        n, H, W = (int(v) for v in luma.shape)
-        R, C, S, first = s.mesh_row_count, s.mesh_col_count, self.state.S, self.state.seen
+        from . import ops
+        cfg = self.settings
+        n, first = int(luma.shape[0]), self.state.seen
         # pairs: (the frame kept from the previous push -> new frame 0), then the adjacent new frames
         stack, k0 = (luma, 1) if self._last_luma is None else (torch.cat([self._last_luma[None], luma]), 0)
-        vel = torch.zeros((n, S), dtype=torch.float32, device=self.device)
-        lam_known = np.full(n, self._lam_newest)
+        vel = torch.zeros((n, cfg.S), dtype=torch.float32, device=cfg.device)
+        lam_known = np.full(n, cfg.lam_newest)
         lost = []
         if stack.shape[0] >= 2:
-            early, late, offsets, kmax, d_hom, d_info = self.tracker.track_stacks_resident(stack[:-1], stack[1:], self.chunk_pairs)
-            _, d_vel, status = ops.vertex_motion(early, late, offsets, d_hom, kmax, W, H, R, C, s.feature_ellipse_row_count,
-                                                 s.feature_ellipse_col_count)
-            homographies, info = d_hom.cpu().numpy(), d_info.cpu().numpy()          # (the one wait of a push beyond the tracker's own)
-            ops.vertex_motion_check(status)
-            bad = np.nonzero(info[:, 0] != _lib.HFIT_OK)[0]
-            if bad.size and self.on_lost == 'raise':
-                t = first + k0 + int(bad[0]) - 1
-                raise ValueError(f'fewer than {s.homography_min_number_corresponding_features} features could be '
-                                 f'tracked from frame {t} to frame {t + 1}')
-            d_vel = d_vel.reshape(-1, S)
-            if bad.size:
-                # 'hold': no motion for such a pair.  The fit left the identity there, whose weight is lam_newest's; an empty feature range
-                # gives a zero velocity by itself (oracle/motion_oracle.py), a refused fit over a non-empty range does not
-                d_vel = d_vel.index_fill(0, torch.from_numpy(bad).to(self.device), 0.0)
-                lost = [first + k0 + int(b) for b in bad]
-            vel[k0:] = d_vel
-            lam_known[k0:] = host.adaptive_weights(len(homographies), W, H, self.definition, homographies)
-        block = (vel, torch.from_numpy(lam_known).to(self.device), self.state, self._taps, self.omega, self.iters, self.beta, self._lam_newest)
-        c, p = ops.online_smooth_lag(*block, self.lag) if self.lag else ops.online_smooth(*block)
+            vel[k0:], lam_known[k0:], bad = track_pairs(cfg, stack[:-1], stack[1:], first + k0 - 1)
+            lost = [first + k0 + int(b) for b in bad]
+        block = (vel, torch.from_numpy(lam_known).to(cfg.device), self.state, cfg.taps, cfg.omega, cfg.iters, cfg.beta, cfg.lam_newest)
+        c, p = ops.online_smooth_lag(*block, cfg.lag) if cfg.lag else ops.online_smooth(*block)
         self._last_luma = luma[-1].clone()
         self.shots += int(first == 0)
         # the frames that became final are the oldest of (held, new); without a lag that is the caller's frames, and nothing is held
-        final, self._held = hold_frames(self._held, self.form.planes(frames), int(c.shape[0]))
-        return self._hand_out(self.form.clip(final), c, p, lost) if c.shape[0] else self._nothing(lost)
+        final, self._held = hold_frames(self._held, cfg.form.planes(frames), int(c.shape[0]))
+        return self._hand_out(cfg.form.clip(final), c, p, lost) if c.shape[0] else empty_result(cfg, self.emitted, lost)
 
     def _flush_part(self):
         """The pending frames of the shot under way with `ops.online_pending`'s paths: (frames out, `OnlineReport`, k or None).  Leaves
         the reset to the caller."""
         from . import ops
+        cfg = self.settings
         if not self.pending:
-            return self._nothing([])
-        c, p = ops.online_pending(self.state, self.lag)
+            return empty_result(cfg, self.emitted, [])
+        c, p = ops.online_pending(self.state, cfg.lag)
         held, self._held = self._held, None
-        return self._hand_out(self.form.clip(held), c, p, [])
-
-    def _nothing(self, lost):
-        """What a part that hands out no frame returns: 0 frames of the output's dtype and trailing shape, a report with 0-row tensors,
-        0 steps of the limiter.  No op is called."""
-        import torch
-        s = self.stabilizer
-        k = torch.empty(0, dtype=torch.int32, device=self.device) if self.on_uncovered == 'limit' else None
-        path = torch.empty((0, s.mesh_row_count + 1, s.mesh_col_count + 1, 2), dtype=torch.float64, device=self.device)
-        return (self.form.empty(*self._out_size, self.device),
-                OnlineReport(self.emitted, path, path.clone(), self.rectangle, torch.empty(0, dtype=torch.bool, device=self.device), lost), k)
+        return self._hand_out(cfg.form.clip(held), c, p, [])
 
     def _hand_out(self, frames, c, p, lost):
-        """Frames of one shot whose paths are final -- session indices from `emitted` on -- through the limiter, the cell table, the format's
-        warp and the crop-resize: (frames out, `OnlineReport`, the limiter's k or None)."""
+        """Frames of one shot whose paths are final, session indices from `emitted` on, through the limiter and `warp_rows`: a part, as `_push_part`'s."""
         from . import ops
-        s = self.stabilizer
-        n, (H, W) = int(c.shape[0]), self.form.shape[:2]
-        R, C, first, k = s.mesh_row_count, s.mesh_col_count, self.emitted, None
-        self.emitted += n
-        if self.on_uncovered == 'limit':
+        cfg = self.settings
+        first, k = self.emitted, None
+        self.emitted += int(c.shape[0])
+        if cfg.on_uncovered == 'limit':
             # (behind the smoother, whose state keeps the unlimited path: blocks of any sizes give the bytes of one push)
-            p, k = ops.path_limit(c, p, W, H, R, C, self.rectangle, self.limit_steps, self.limit_guard, self.limit_rise, self._k_prev)
+            p, k = ops.path_limit(c, p, *cfg.dims, cfg.rectangle, cfg.limit_steps, cfg.limit_guard, cfg.limit_rise, self._k_prev)
             self._k_prev = k[-1:]
-        table = ops.cell_table(c, p, W, H, R, C)
-        out = self.form.warp_crop(frames, table, s.color_outside_image_area_bgr, self._crop)
-        table.check()
-        crop = table.crop
-        left, top, right, bottom = self.rectangle
-        covered = (crop[:, 0] <= left) & (crop[:, 1] <= top) & (crop[:, 2] >= right) & (crop[:, 3] >= bottom)
-        shape = (n, R + 1, C + 1, 2)
-        return out, OnlineReport(first, c.view(shape), p.view(shape), self.rectangle, covered, lost), k
+        out, covered = warp_rows(cfg, frames, c, p)
+        return out, OnlineReport(first, c.view(-1, *cfg.grid), p.view(-1, *cfg.grid), cfg.rectangle, covered, lost), k
 
 
 def _check_stream_count(streams):
@@ -405,13 +459,12 @@ def _check_stream_count(streams):
 class OnlineGroup:
     """`streams` live streams of one size and form through `stabilizer`, a frame of each of any subset per `push`, in ONE set of launches
     whatever the subset's size.  Made by `MeshFlowStabilizer.online_group`, which documents the keywords.  What a stream gets is what an
-    `OnlineSession` of its own with the same keywords, pushed its frames one at a time, returns, byte for byte: every stage shared between
-    the streams works per pair or per frame, and the three that carry a stream's memory have a batched form that restates the single one per
-    row -- `ops.online_smooth_group`, `ops.path_limit_group`, `ops.cut_distance_pairs`.
-    The keywords are checked, and the rectangle, taps and crop fixed at the first push, by an `OnlineSession` that is never pushed
-    (`settings`): one copy of those rules.  Per stream the group carries, on the device: its slices of an `ops.OnlineGroupState`, its last
-    luma frame (B, H, W), that frame's signature (B, 256) and the limiter's last step (B,), -1 where nothing is carried; on the host: `seen`
-    and `shots`."""
+    `OnlineSession` of its own with the same keywords, pushed its frames one at a time, returns, byte for byte: the stages shared between
+    the streams work per pair or per frame and are the functions a session calls (`track_pairs`, `warp_rows`), and the three that carry a
+    stream's memory have a batched form that restates the single one per row -- `ops.online_smooth_group`, `ops.path_limit_group`,
+    `ops.cut_distance_pairs`.  The keywords, and what the first push fixes, are in `settings`, an `OnlineSettings` as a session has one.
+    Per stream the group carries, on the device: its slices of an `ops.OnlineGroupState`, its last luma frame (B, H, W), that frame's
+    signature (B, 256) and the limiter's last step (B,), -1 where nothing is carried; on the host: `seen` and `shots`."""
 
     def __init__(self, stabilizer, streams, **keywords):
         _check_stream_count(streams)
@@ -426,8 +479,7 @@ class OnlineGroup:
             raise ValueError(f"a group takes on_lost='hold' only (got {keywords['on_lost']!r}): one stream's lost pair must not stop the "
                              "others; it is reported in that stream's report.lost")
         self.streams = int(streams)
-        self.settings = OnlineSession(stabilizer, **keywords)
-        self.stabilizer, self.device = stabilizer, self.settings.device
+        self.settings = OnlineSettings(stabilizer, **keywords)
         self.state = self._last_luma = self._last_sig = self._k_prev = None       # made by the first push, which fixes the frame size
         self.shots = [0] * self.streams
         # of the last push, per pushed row: the limiter's (K,) int32 k on the device (on_uncovered='limit'); the rows at which a cut was
@@ -442,11 +494,15 @@ class OnlineGroup:
         """The frames of each stream's path since its last reset: a list of `streams` ints."""
         return list(self.state.seen) if self.state is not None else [0] * self.streams
 
+    def _named(self, stream):
+        """The streams that `reset(stream)` or `flush(stream)` means: that one, or all of them for None."""
+        from . import ops
+        return list(range(self.streams)) if stream is None else ops.check_streams([stream], self.streams, 'stream')
+
     def reset(self, stream=None):
         """Forget every frame of `stream` (None: of every stream), as `OnlineSession.reset` does for its one: the stream's next frame
         starts a path at frame 0 and is no cut.  No byte of the state is cleared: a stream at seen = 0 reads none of it."""
-        from . import ops
-        ids = list(range(self.streams)) if stream is None else ops.check_streams([stream], self.streams, 'stream')
+        ids = self._named(stream)
         if self.state is not None:
             for b in ids:
                 self.state.reset(b)
@@ -458,33 +514,20 @@ class OnlineGroup:
         K `OnlineReport`): row r and report r belong to streams[r] and hold what that stream's own session would have returned for the
         frame.  A stream at its first frame, after `reset(stream)` or at a cut found is not tracked: it pushes a zero velocity at seen = 0."""
         from . import ops
-        cfg, s = self.settings, self.stabilizer
-        ids, d_ids, form, luma, first, vel, lam_known, lost = self._front(frames, streams)
-        K, (H, W), R, C, S = len(ids), form.shape[:2], s.mesh_row_count, s.mesh_col_count, self.state.S
-        c, p = ops.online_smooth_group(vel, lam_known, self.state, ids, cfg._taps, cfg.omega, cfg.iters, cfg.beta, cfg._lam_newest)
-        c, p = c.view(K, S), p.view(K, S)
+        cfg = self.settings
+        ids, d_ids, form, luma, first, vel, lam_known, lost, _ = self._front(frames, streams)
+        K = len(ids)
+        c, p = ops.online_smooth_group(vel, lam_known, self.state, ids, cfg.taps, cfg.omega, cfg.iters, cfg.beta, cfg.lam_newest)
+        c, p = c.view(K, cfg.S), p.view(K, cfg.S)
         self._carry(ids, d_ids, luma, first)
-
         k = None
         if cfg.on_uncovered == 'limit':
-            p, k = ops.path_limit_group(c, p, W, H, R, C, cfg.rectangle, cfg.limit_steps, cfg.limit_guard, cfg.limit_rise, self._k_prev[d_ids])
+            p, k = ops.path_limit_group(c, p, *cfg.dims, cfg.rectangle, cfg.limit_steps, cfg.limit_guard, cfg.limit_rise, self._k_prev[d_ids])
             self._k_prev[d_ids] = k
         self.last_limit = k
-        out, covered = self._warp_rows(frames, c, p)
-        c, p = c.view(K, R + 1, C + 1, 2), p.view(K, R + 1, C + 1, 2)
+        out, covered = warp_rows(cfg, frames, c, p)
+        c, p = c.view(K, *cfg.grid), p.view(K, *cfg.grid)
         return out, [OnlineReport(first[r], c[r:r + 1], p[r:r + 1], cfg.rectangle, covered[r:r + 1], lost[r]) for r in range(K)]
-
-    def _warp_rows(self, frames, c, p):
-        """Frames with their paths (n, S) through one cell table, the format's warp and the crop-resize: (frames out, covered (n,) bool)."""
-        from . import ops
-        cfg, s = self.settings, self.stabilizer
-        H, W = cfg.form.shape[:2]
-        table = ops.cell_table(c, p, W, H, s.mesh_row_count, s.mesh_col_count)
-        out = cfg.form.warp_crop(frames, table, s.color_outside_image_area_bgr, cfg._crop)
-        table.check()
-        crop = table.crop
-        left, top, right, bottom = cfg.rectangle
-        return out, (crop[:, 0] <= left) & (crop[:, 1] <= top) & (crop[:, 2] >= right) & (crop[:, 3] >= bottom)
 
     def _carry(self, ids, d_ids, luma, first):
         """Behind the smoother: every pushed stream's last luma frame, and the shots begun."""
@@ -497,79 +540,63 @@ class OnlineGroup:
         import torch
         from . import _lib, ops
         cfg = self.settings
-        cfg._start(form, H, W)
-        self.state = ops.OnlineGroupState(self.streams, cfg.state.S, cfg.window, self.device)
-        self._last_luma = torch.empty((self.streams, H, W), dtype=torch.uint8, device=self.device)
-        self._last_sig = torch.zeros((self.streams, _lib.CUT_COUNTERS), dtype=torch.int32, device=self.device)
-        self._k_prev = torch.full((self.streams,), -1, dtype=torch.int32, device=self.device)
+        cfg.start(form, H, W)
+        self.state = ops.OnlineGroupState(self.streams, cfg.S, cfg.window, cfg.device)
+        self._last_luma = torch.empty((self.streams, H, W), dtype=torch.uint8, device=cfg.device)
+        self._last_sig = torch.zeros((self.streams, _lib.CUT_COUNTERS), dtype=torch.int32, device=cfg.device)
+        self._k_prev = torch.full((self.streams,), -1, dtype=torch.int32, device=cfg.device)
 
-    def _at_cut(self, row, stream):
-        """A cut found at `row`, the frame of `stream` (the pair across a cut is never tracked)."""
-        self.reset(stream)
-
-    def _front(self, frames, streams):
-        """A push up to the smoother, shared by the groups: the checks, luma, the cut decisions, the tracked pairs, `ops.vertex_motion` and
-        the one download.  Returns (ids, d_ids, form, luma, first -- each row's stream's `seen` --, vel (K, 1, S), lam_known (K, 1) on the
-        device, lost per row)."""
+    def _front(self, frames, streams, tail=None):
+        """A push up to the smoother, shared by the groups: the checks, luma, the cut decisions, the tracked pairs (`track_pairs`).
+        Returns (ids, d_ids, form, luma, first -- each row's stream's `seen` --, vel (K, 1, S), lam_known (K, 1) on the device, lost per
+        row, tails: per row at which a cut was found, what `tail(stream)` returned for the old shot before the stream's reset, or None)."""
         import torch
-        from . import _lib, ops
-        cfg, s = self.settings, self.stabilizer
+        from . import ops
+        cfg = self.settings
         ids = ops.check_streams(range(self.streams) if streams is None else streams, self.streams)
         K = len(ids)
-        if cfg.form is None and cfg.on_uncovered == 'limit':
-            cfg._check_limit_fits(frames)
-        form, luma = luma_of(frames, cfg.red_first)
+        form, luma = cfg.read(frames)
         n, H, W = (int(v) for v in luma.shape)
         if n != K:
             raise ValueError(f'push takes one frame per pushed stream: {K} streams, {n} frames')
         if cfg.form is None:
             self._begin(form, H, W, frames)
-        elif form != cfg.form:
-            raise ValueError(f'this group takes {cfg.form.dtype} frames of shape {cfg.form.shape}{" as (d_y, d_uv) pairs" if cfg.form.pair else ""}; '
-                             f'got {form.dtype} frames of shape {form.shape}{" as a pair" if form.pair else ""}')
-        R, C, S, seen = s.mesh_row_count, s.mesh_col_count, self.state.S, self.state.seen
-        d_ids = torch.tensor(ids, dtype=torch.int64, device=self.device)
+        else:
+            cfg.form.check_same(form, 'group')
+        seen = self.state.seen
+        d_ids = torch.tensor(ids, dtype=torch.int64, device=cfg.device)
 
         # cuts: every row against its own stream's last signature, one wait for the K distances
-        cuts, distances = [], None
+        cuts, distances, tails = [], None, {}
         if cfg.on_cut == 'reset':
             sig = ops.frame_signatures(luma)
             distances = ops.cut_distance_pairs(self._last_sig[d_ids], sig).cpu().numpy()
             distances[np.array([seen[b] == 0 for b in ids])] = 0           # no frame before: nothing to be far from, never a cut
             cuts = [int(r) for r in np.nonzero(distances.astype(np.int64) > ops.cut_bound(cfg.cut_threshold, W, H))[0]]
             self._last_sig[d_ids] = sig
-            for r in cuts:
-                self._at_cut(r, ids[r])
+            for r in cuts:                                                  # (the pair across a cut is never tracked)
+                tails[r] = tail(ids[r]) if tail else None
+                self.reset(ids[r])
         self.last_cuts, self.last_cut_distances = cuts, distances
 
         # the pairs (a stream's last luma -> its new frame) of the streams that have a frame before, through the tracker together
         first = [seen[b] for b in ids]
         rows = [r for r in range(K) if first[r] > 0]
-        vel = torch.zeros((K, 1, S), dtype=torch.float32, device=self.device)
-        lam_known = np.full((K, 1), cfg._lam_newest)
+        vel = torch.zeros((K, 1, cfg.S), dtype=torch.float32, device=cfg.device)
+        lam_known = np.full((K, 1), cfg.lam_newest)
         lost = [[] for _ in ids]
         if rows:
             everyone = len(rows) == K
-            d_rows = None if everyone else torch.tensor(rows, dtype=torch.int64, device=self.device)
+            d_rows = None if everyone else torch.tensor(rows, dtype=torch.int64, device=cfg.device)
             early = self._last_luma[d_ids if everyone else d_ids[d_rows]]
-            late = luma if everyone else luma[d_rows]
-            early, late, offsets, kmax, d_hom, d_info = cfg.tracker.track_stacks_resident(early, late, cfg.chunk_pairs)
-            _, d_vel, status = ops.vertex_motion(early, late, offsets, d_hom, kmax, W, H, R, C, s.feature_ellipse_row_count,
-                                                 s.feature_ellipse_col_count)
-            homographies, info = d_hom.cpu().numpy(), d_info.cpu().numpy()          # (the one wait of a push beyond the tracker's own)
-            ops.vertex_motion_check(status)
-            bad = np.nonzero(info[:, 0] != _lib.HFIT_OK)[0]
-            d_vel = d_vel.reshape(-1, 1, S)
-            if bad.size:                                                            # 'hold': no motion for such a pair (`OnlineSession`)
-                d_vel = d_vel.index_fill(0, torch.from_numpy(bad).to(self.device), 0.0)
-                for b in bad:
-                    lost[rows[int(b)]] = [first[rows[int(b)]]]
+            d_vel, lam_known[rows, 0], bad = track_pairs(cfg, early, luma if everyone else luma[d_rows])
+            for b in bad:
+                lost[rows[int(b)]] = [first[rows[int(b)]]]
             if everyone:
-                vel = d_vel.contiguous()
+                vel = d_vel[:, None].contiguous()
             else:
-                vel[d_rows] = d_vel
-            lam_known[rows, 0] = host.adaptive_weights(len(homographies), W, H, cfg.definition, homographies)
-        return ids, d_ids, form, luma, first, vel, torch.from_numpy(lam_known).to(self.device), lost
+                vel[d_rows] = d_vel[:, None]
+        return ids, d_ids, form, luma, first, vel, torch.from_numpy(lam_known).to(cfg.device), lost, tails
 
 
 class OnlineLagGroup(OnlineGroup):
@@ -585,11 +612,10 @@ class OnlineLagGroup(OnlineGroup):
         _check_stream_count(streams)
         if not isinstance(lag, bool) and isinstance(lag, (int, np.integer)) and int(lag) == 0:
             raise ValueError('a lagged group takes lag in 1 .. window - 1 (got 0): online_group(streams) is the group without look-ahead')
-        self._setup(stabilizer, streams, dict(keywords, lag=lag))         # (the session's own checks of window and lag)
+        self._setup(stabilizer, streams, dict(keywords, lag=lag))         # (the settings' own checks of window and lag)
         self.lag = self.settings.lag
         self.emitted, self._limited = [0] * self.streams, [False] * self.streams
         self._rings = None                                                  # per plane (streams, lag, ...), made by the first push
-        self._tails = {}                                                    # of the push under way: row -> the old shot's tail at a cut
         self.last_counts = []                                               # of the last push or flush: the frames of `out` per row
 
     @property
@@ -600,10 +626,8 @@ class OnlineLagGroup(OnlineGroup):
     def reset(self, stream=None):
         """`OnlineGroup.reset`; the pending frames of those streams are DISCARDED -- `flush(stream)` first hands them out.  No ring byte is
         cleared: a stream at seen = 0 reads none of its slots."""
-        from . import ops
-        ids = list(range(self.streams)) if stream is None else ops.check_streams([stream], self.streams, 'stream')
         super().reset(stream)
-        for b in ids:
+        for b in self._named(stream):
             self.emitted[b], self._limited[b] = 0, False
 
     def _begin(self, form, H, W, frames):
@@ -611,80 +635,58 @@ class OnlineLagGroup(OnlineGroup):
         planes = form.planes(frames)
         size = sum(self.streams * self.lag * int(p[0].numel()) * p.element_size() for p in planes)
         try:
-            rings = tuple(torch.empty((self.streams, self.lag) + tuple(p.shape[1:]), dtype=p.dtype, device=self.device) for p in planes)
+            rings = tuple(torch.empty((self.streams, self.lag) + tuple(p.shape[1:]), dtype=p.dtype, device=self.settings.device) for p in planes)
         except RuntimeError as e:                                           # (torch's out-of-memory error is one)
             raise ValueError(f'a lagged group of {self.streams} streams at lag={self.lag} holds streams * lag frames on the device: '
                              f'{size} bytes could not be allocated ({str(e).splitlines()[0]})') from None
         super()._begin(form, H, W, frames)
         self._rings = rings
 
-    def _at_cut(self, row, stream):
-        if self.pending[stream]:
-            self._tails[row] = self._tail(stream)                           # the old shot's tail, ahead of the new shot's frames
-        self.reset(stream)
-
-    def _nothing(self, stream, lost):
-        """What a row that hands out no frame reports: 0-row tensors, `first` the stream's `emitted`."""
-        import torch
-        s = self.stabilizer
-        path = torch.empty((0, s.mesh_row_count + 1, s.mesh_col_count + 1, 2), dtype=torch.float64, device=self.device)
-        return OnlineReport(self.emitted[stream], path, path.clone(), self.settings.rectangle,
-                            torch.empty(0, dtype=torch.bool, device=self.device), lost)
-
     def _tail(self, stream):
-        """The pending frames of `stream` with `ops.online_pending_group`'s paths through the single-stream limiter, the cell table and the
-        warp -- `OnlineSession._flush_part` on the stream's slices, launches of its own --: (frames out, `OnlineReport`, k or None).  Leaves
-        the reset to the caller."""
+        """The pending frames of `stream` with `ops.online_pending_group`'s paths through the single-stream limiter and `warp_rows` --
+        `OnlineSession._flush_part` on the stream's slices, launches of its own --: (frames out, `OnlineReport`, k or None), or None where
+        nothing is pending.  Leaves the reset to the caller."""
         import torch
         from . import ops
-        cfg, s = self.settings, self.stabilizer
+        cfg = self.settings
         n, seen, first, k = self.pending[stream], self.state.seen[stream], self.emitted[stream], None
+        if not n:
+            return None
         (c, p), = ops.online_pending_group(self.state, [stream], self.lag)
         # oldest first: slots (seen - n) mod lag onwards, in one run or two around the ring's end (slices: torch indexes no uint16 tensor);
         # the warp below reads them on this stream before the tick's exchange writes a slot
         lo = (seen - n) % self.lag
         wrap = max(0, lo + n - self.lag)
         frames = cfg.form.clip([torch.cat([ring[stream, lo:], ring[stream, :wrap]]) if wrap else ring[stream, lo:lo + n] for ring in self._rings])
-        (H, W), R, C = cfg.form.shape[:2], s.mesh_row_count, s.mesh_col_count
         if cfg.on_uncovered == 'limit':
-            p, k = ops.path_limit(c, p, W, H, R, C, cfg.rectangle, cfg.limit_steps, cfg.limit_guard, cfg.limit_rise,
+            p, k = ops.path_limit(c, p, *cfg.dims, cfg.rectangle, cfg.limit_steps, cfg.limit_guard, cfg.limit_rise,
                                   self._k_prev[stream:stream + 1].clone() if self._limited[stream] else None)
-        out, covered = self._warp_rows(frames, c, p)
+        out, covered = warp_rows(cfg, frames, c, p)
         self.emitted[stream] += n
-        shape = (n, R + 1, C + 1, 2)
-        return out, OnlineReport(first, c.view(shape), p.view(shape), cfg.rectangle, covered, []), k
+        return out, OnlineReport(first, c.view(n, *cfg.grid), p.view(n, *cfg.grid), cfg.rectangle, covered, []), k
 
     def _result(self, parts):
-        """What a push or a flush returns from its rows' parts -- per row a list of (frames or None, report, k) in order --: (the frames
-        joined in order, a report per row).  Sets `last_counts` and, with on_uncovered='limit', `last_limit`: the k of every frame of `out`."""
+        """What a push or a flush returns from its rows' parts -- per row a list of (frames, report, k) in order, as a session's parts
+        are --: (the frames joined in order, a report per row).  Sets `last_counts` and, with on_uncovered='limit', `last_limit`: the k of
+        every frame of `out`."""
         import torch
         cfg = self.settings
-        clips = [out for row in parts for out, _, _ in row if out is not None]
-        ks = [k for row in parts for _, _, k in row if k is not None]
+        flat = [part for row in parts for part in row]
         self.last_counts = [sum(int(r.d_stab.shape[0]) for _, r, _ in row) for row in parts]
         if cfg.on_uncovered == 'limit':
-            self.last_limit = ks[0] if len(ks) == 1 else torch.cat(ks) if ks else torch.empty(0, dtype=torch.int32, device=self.device)
-        out = cfg.form.empty(*cfg._out_size, self.device) if not clips else clips[0] if len(clips) == 1 else cfg.form.cat(clips)
-        reports = []
-        for row in parts:
-            if len(row) == 1:
-                reports.append(row[0][1])
-            else:                                                           # a tail and the new shot's part, as `OnlineSession.join` joins them
-                d_unstab, d_stab, covered = (torch.cat([getattr(r, field) for _, r, _ in row]) for field in ('d_unstab', 'd_stab', 'covered'))
-                reports.append(OnlineReport(row[0][1].first, d_unstab, d_stab, cfg.rectangle, covered, [t for _, r, _ in row for t in r.lost]))
-        return out, reports
+            self.last_limit = flat[0][2] if len(flat) == 1 else torch.cat([k for _, _, k in flat])
+        clips = [out for out, r, _ in flat if r.d_stab.shape[0]] or [flat[0][0]]           # (no frame at all: 0 frames are the answer)
+        out = clips[0] if len(clips) == 1 else cfg.form.cat(clips)
+        return out, [row[0][1] if len(row) == 1 else join_reports([r for _, r, _ in row]) for row in parts]
 
     def flush(self, stream=None):
         """The end of `stream` (None: of every stream): (its pending frames stabilized and cropped -- of all the named streams, in order --,
         a list of an `OnlineReport` per named stream), with the last window's solution as their paths, as `OnlineSession.flush` does for
         its one; then `reset(stream)`.  A stream with nothing pending gives a 0-row report.  Before the first push it is a ValueError."""
-        from . import ops
-        if self.form is None:
-            raise ValueError('flush before the first push: the frame size and form are not known yet')
-        ids = list(range(self.streams)) if stream is None else ops.check_streams([stream], self.streams, 'stream')
+        self.settings.check_started()
         parts = []
-        for b in ids:
-            parts.append([self._tail(b) if self.pending[b] else (None, self._nothing(b, []), None)])
+        for b in self._named(stream):
+            parts.append([self._tail(b) or empty_result(self.settings, self.emitted[b], [])])
             self.reset(b)
         return self._result(parts)
 
@@ -695,13 +697,11 @@ class OnlineLagGroup(OnlineGroup):
         frames of the output are row r's, `first` the stream's index of the first of them, `lost` that of the frame PUSHED."""
         import torch
         from . import ops
-        cfg, s = self.settings, self.stabilizer
-        self._tails = {}
-        ids, d_ids, form, luma, first, vel, lam_known, lost = self._front(frames, streams)
-        K, (H, W), R, C, S = len(ids), form.shape[:2], s.mesh_row_count, s.mesh_col_count, self.state.S
-        c, p, final = ops.online_smooth_group_lag(vel, lam_known, self.state, ids, cfg._taps, cfg.omega, cfg.iters, cfg.beta, cfg._lam_newest,
-                                                  self.lag)
-        c, p = c.view(K, S), p.view(K, S)
+        cfg = self.settings
+        ids, d_ids, form, luma, first, vel, lam_known, lost, tails = self._front(frames, streams, self._tail)
+        K = len(ids)
+        c, p, final = ops.online_smooth_group_lag(vel, lam_known, self.state, ids, cfg.taps, cfg.omega, cfg.iters, cfg.beta, cfg.lam_newest, self.lag)
+        c, p = c.view(K, cfg.S), p.view(K, cfg.S)
         self._carry(ids, d_ids, luma, first)
 
         # the new frames into their slots, the owed ones out of them: row r's frame `first[r]` takes the slot of frame first[r] - lag
@@ -711,17 +711,17 @@ class OnlineLagGroup(OnlineGroup):
         rows = np.array([(b, first[r] % self.lag, out_row.get(r, -1)) for r, b in enumerate(ids)], dtype=np.int32)
         owed = [ops.ring_exchange(ring, plane, rows, M) for ring, plane in zip(self._rings, form.planes(frames))]
 
-        parts = [[self._tails[r]] if r in self._tails else [] for r in range(K)]
+        parts = [[tails[r]] if tails.get(r) else [] for r in range(K)]         # the old shot's tail, ahead of the new shot's frames
         if M:
             k = None
             if M < K:
-                d_emit = torch.tensor(emit, dtype=torch.int64, device=self.device)
+                d_emit = torch.tensor(emit, dtype=torch.int64, device=cfg.device)
                 c, p, d_ids = c[d_emit], p[d_emit], d_ids[d_emit]
             if cfg.on_uncovered == 'limit':
-                p, k = ops.path_limit_group(c, p, W, H, R, C, cfg.rectangle, cfg.limit_steps, cfg.limit_guard, cfg.limit_rise, self._k_prev[d_ids])
+                p, k = ops.path_limit_group(c, p, *cfg.dims, cfg.rectangle, cfg.limit_steps, cfg.limit_guard, cfg.limit_rise, self._k_prev[d_ids])
                 self._k_prev[d_ids] = k
-            out, covered = self._warp_rows(form.clip(owed), c, p)
-            c, p = c.view(M, R + 1, C + 1, 2), p.view(M, R + 1, C + 1, 2)
+            out, covered = warp_rows(cfg, form.clip(owed), c, p)
+            c, p = c.view(M, *cfg.grid), p.view(M, *cfg.grid)
             for j, r in enumerate(emit):
                 b = ids[r]
                 report = OnlineReport(self.emitted[b], c[j:j + 1], p[j:j + 1], cfg.rectangle, covered[j:j + 1], lost[r])
@@ -730,10 +730,8 @@ class OnlineLagGroup(OnlineGroup):
                 self._limited[b] = k is not None
         for r, b in enumerate(ids):
             if r not in out_row:
-                parts[r].append((None, self._nothing(b, lost[r]), None))
-        self._tails = {}
+                parts[r].append(empty_result(cfg, self.emitted[b], lost[r]))
         if M == K:                                                          # the steady tick: the warp's output and the limiter's k as they are
-            reports = [row[0][1] for row in parts]
             self.last_counts, self.last_limit = [1] * K, k
-            return out, reports
+            return out, [row[0][1] for row in parts]
         return self._result(parts)

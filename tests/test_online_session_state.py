@@ -106,3 +106,56 @@ def test_reset_snapshot_and_restore_cover_everything_a_shot_carries():
     session.shots = 4
     session._restore(saved)
     assert carried(session) == filled and session.shots == 2
+
+
+def test_settings_hold_what_the_first_push_fixes_and_no_state():
+    from meshflow_amd import online
+    form = online.ClipForm(None, torch.uint8, (8, 8))
+    for margin, rectangle in ((0, (0, 0, 7, 7)), (0.2, (1, 1, 6, 6))):
+        settings = online.OnlineSettings(Stub(), window=3, crop_margin=margin)
+        assert settings.form is None and settings.rectangle is None
+        settings.start(form, 8, 8)
+        assert settings.form == form and settings.rectangle == rectangle == online.margin_rectangle(margin, 8, 8)
+        assert settings.S == 8 and settings.out_size == (8, 8) and (settings.crop is None) == (margin == 0)
+        assert not hasattr(settings, 'state') and not set(online._CARRIED) & set(vars(settings)) and not hasattr(settings, 'shots')
+    for group in (online.OnlineGroup(Stub(), 3), online.OnlineLagGroup(Stub(), 3, 2, window=3)):
+        assert isinstance(group.settings, online.OnlineSettings) and not hasattr(group.settings, 'state')
+        assert group.state is None and group.form is None and group.seen == [0] * 3
+
+
+def test_join_reports_of_an_empty_a_two_frame_and_a_one_frame_part():
+    from meshflow_amd import online
+
+    def report(first, values, lost):
+        path = torch.tensor(values, dtype=torch.float64).reshape(-1, 1, 1, 1).expand(-1, 2, 2, 2).contiguous()
+        return online.OnlineReport(first, path, path + 0.5, (1, 1, 6, 6), torch.tensor([v > 1 for v in values], dtype=torch.bool), lost)
+
+    joined = online.join_reports([report(4, [], [3]), report(0, [1.0, 2.0], []), report(2, [3.0], [2, 5])])
+    assert joined.first == 4 and joined.rectangle == (1, 1, 6, 6) and joined.lost == [3, 2, 5]
+    assert joined.d_unstab.shape == joined.d_stab.shape == (3, 2, 2, 2) and joined.d_unstab.dtype == joined.d_stab.dtype == torch.float64
+    assert joined.d_unstab[:, 0, 0, 0].tolist() == [1.0, 2.0, 3.0] and joined.d_stab[:, 1, 1, 1].tolist() == [1.5, 2.5, 3.5]
+    assert joined.covered.dtype == torch.bool and joined.covered.tolist() == [False, True, True]
+    # a session's public join is this one, with the frames concatenated beside it
+    session = started()
+    frames, again = session.join([(torch.full((n, 8, 8), n, dtype=torch.uint8), r) for n, r in
+                                  ((0, report(4, [], [3])), (2, report(0, [1.0, 2.0], [])), (1, report(2, [3.0], [2, 5])))])
+    assert frames.dtype == torch.uint8 and frames[:, 0, 0].tolist() == [2, 2, 1] and again.first == 4 and again.lost == [3, 2, 5]
+    assert torch.equal(again.d_unstab, joined.d_unstab) and torch.equal(again.d_stab, joined.d_stab) and torch.equal(again.covered, joined.covered)
+
+
+@pytest.mark.parametrize('pair', (False, True), ids=('a stack', 'an NV12 pair'))
+def test_the_empty_result(pair):
+    from meshflow_amd import online, ops
+    settings = online.OnlineSettings(Stub(), window=3, on_uncovered='limit' if pair else 'report')
+    settings.start(online.ClipForm(ops._NV12 if pair else None, torch.uint8, (8, 8) if pair else (8, 8, 3)), 8, 8)
+    frames, report, k = online.empty_result(settings, 5, [4])
+    planes = frames if pair else (frames,)
+    assert isinstance(frames, tuple) == pair and all(p.dtype == torch.uint8 for p in planes)
+    assert [tuple(p.shape) for p in planes] == ([(0, 8, 8), (0, 4, 4, 2)] if pair else [(0, 8, 8, 3)])
+    assert report.first == 5 and report.lost == [4] and report.rectangle == settings.rectangle == (0, 0, 7, 7)
+    for path in (report.d_unstab, report.d_stab):
+        assert tuple(path.shape) == (0, 2, 2, 2) and path.dtype == torch.float64
+    assert report.d_unstab.data_ptr() != report.d_stab.data_ptr() or report.d_unstab is not report.d_stab
+    assert tuple(report.covered.shape) == (0,) and report.covered.dtype == torch.bool
+    # the limiter's part of it: 0 steps where the session limits, nothing where it does not
+    assert (k is None) if not pair else (tuple(k.shape) == (0,) and k.dtype == torch.int32)
